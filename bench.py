@@ -14,7 +14,11 @@ rank, no data-path collective per frame; the shared global grid is formed by ONE
 grids (float32 payload: 80 MB for the 2000 x 2000 x 5 grid), inside the timed region and also timed on its own
 with HIP events (`exchange_ms`, `exchange_bytes`) ("weak" scaling: per-GPU work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0) as DIR/<name>.npy: the label map and
+the logits of the network, and the grid after that step as a seeded sample of cells plus its row and column sums (all in
+float32 / float64, ~35 MB; `bench_outputs/` is ignored by git).  The inputs are seeded: the same arguments give the same inputs
+on every run, so two builds can be compared output for output.
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts its N ranks itself: a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` started BEFORE anything
 touches the GPU; its exit code is this process's.  Launched under torch.distributed.run it just runs its rank.
@@ -64,6 +68,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup",
            str(args.warmup), "--precision", args.precision, "--mixed-opts", args.mixed_opts]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.no_other_precisions:
@@ -81,7 +87,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle runs (no parity block, no cpu_baseline)")
     ap.add_argument("--no-other-precisions", action="store_true", help="skip the bf16 / f16 context runs (other_precisions block)")
     ap.add_argument("--mixed-opts", default="", help="comma list of key=0|1 overrides for the mixed mode (conv2_split, mx, trunk_fp4, conv1_split)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -161,6 +170,8 @@ def main():
         shared = exchange()
     sync()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net, sm)           # before anything else runs the path again
     exchange_ms, exchange_bytes, per_rank_fps, exchange_sparse = None, None, None, None
     if world > 1:
         own_elapsed = elapsed
@@ -240,6 +251,27 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return result
+
+
+DUMP_GRID_CELLS = 500000          # grid cells sampled by --dump-outputs (of 2000 x 2000; x 5 classes x 8 bytes = 20 MB)
+
+
+def dump_outputs(out_dir, net, sm):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the network's label map and logits,
+    and the log-odds grid (float64, 160 MB in full: a fixed seeded sample of cells, and its row / column sums over every cell)."""
+    os.makedirs(out_dir, exist_ok=True)
+    grid = sm.map
+    cells = np.sort(np.random.default_rng(12345).choice(grid.shape[0] * grid.shape[1], size=min(DUMP_GRID_CELLS, grid.shape[0] * grid.shape[1]),
+                                                          replace=False))
+    outs = {"labels": net.labels.cpu().numpy().astype(np.float32),
+            "logits": net.logits.cpu().numpy().astype(np.float32),
+            "grid_sample": np.ascontiguousarray(grid.reshape(-1, grid.shape[2])[cells], dtype=np.float64),
+            "grid_sample_cells": cells.astype(np.float64),
+            "grid_row_sums": grid.sum(axis=1, dtype=np.float64),
+            "grid_col_sums": grid.sum(axis=0, dtype=np.float64)}
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return outs
 
 
 PARITY_EXTRA_SEEDS = (2,)          # weight seed 2 is the worst draw of tools/seed_sweep.py

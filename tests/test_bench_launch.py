@@ -25,3 +25,11 @@ def test_world_size_mismatch_is_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=env, capture_output=True,
                        text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=3" in (p.stdout + p.stderr)
+
+
+def test_steps_below_one_is_refused():
+    """--steps sets the number of timed steps, and ms_per_step divides by it: zero steps is an argument error, before any GPU work."""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+    env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr, (p.stdout + p.stderr)[-2000:]

@@ -212,6 +212,28 @@ int avl_grid_box_filter(const void* src, void* dst, int map_dtype, int Hm, int W
 int avl_eval_map(const uint8_t* color_map, int H, int W, const uint8_t* mask, int mask_ld, const uint8_t* gt, int gt_ld,
                  uint8_t* labels_out, unsigned long long* counts, void* stream);
 
+/* ---- full-resolution predictions and validation (DeepLabV3Plus.forward(x, upsample_pred=True), deeplab_v3_plus.py:51,67-69) ----
+ * Both read a plan's fp32 logits as the plan leaves them: NHWC [h*w][K], row stride ld (>= K) floats, h x w = the network's output.
+ * The source coordinate is AVL_OP_BILINEAR's: src = dst * (in-1)/(out-1), 0 when out = 1 (F.interpolate(..., align_corners=True)). */
+/* model(x) for a batch of one: out fp32 [K][H][W] (NCHW planes), K <= 256 (AVL_E_UNSUPPORTED above). */
+int avl_upsample_logits(const float* logits, int h, int w, int K, int64_t ld, float* out, int H, int W, void* stream);
+/* bytes of scratch avl_seg_eval_full_res needs for its loss at an H x W output (per-workgroup partials) */
+int64_t avl_seg_eval_scratch_bytes(int H, int W);
+/* The validation step of train.py:138-141 (distributed_train.py:175) for a batch of one, fused: every output pixel interpolates its K
+ * logits (never written out), then
+ *   labels_out uint8 [H][W] (or NULL): torch.argmax over the classes (AVL_OP_ARGMAX's rule: first maximal index, a NaN is maximal);
+ *   confusion uint64 [K][K] (or NULL): MeanIOU.evaluate (models/metrics.py:29-59) -- confusion[gt][pred] += 1 for every pixel with
+ *       gt < K (255 and every other value >= K skipped); ACCUMULATES across calls (the caller zeroes it);
+ *   loss_out double[2], counts_out uint64[2], scratch (avl_seg_eval_scratch_bytes; the three together, or all NULL):
+ *       CrossEntropyLoss(ignore_index) (models/loss.py, models/build.py:20) -- terms logsumexp(z) - z[gt] in fp32 for gt < K and
+ *       gt != ignore_index, summed in a fixed order in fp64 (bitwise reproducible): loss_out = {sum, mean (NaN when no pixel counts)},
+ *       counts_out = {pixels that contributed, ground-truth values neither < K nor ignore_index (torch's cross_entropy raises on those;
+ *       they are skipped here and the caller decides)}.
+ * gt uint8 [H][W] is needed by the confusion matrix and the loss.  K <= 64 (AVL_E_UNSUPPORTED above).  Two launches on `stream`. */
+int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, int H, int W, const uint8_t* gt, int ignore_index,
+                          uint8_t* labels_out, unsigned long long* confusion, double* loss_out, unsigned long long* counts_out,
+                          void* scratch, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

@@ -54,6 +54,9 @@ _SIGNATURES = {
     "avl_render_bev_map_thresholds": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avl_grid_box_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "avl_eval_map": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "avl_upsample_logits": (_i, [_vp, _i, _i, _i, _i64, _vp, _i, _i, _vp]),
+    "avl_seg_eval_scratch_bytes": (_i64, [_i, _i]),
+    "avl_seg_eval_full_res": (_i, [_vp, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

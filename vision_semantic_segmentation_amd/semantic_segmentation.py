@@ -13,7 +13,7 @@ GPU and ``segmentation_device`` hands back the uint8 label map without leaving H
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, seg_head
 from .network import SegNet, check_state_dict, load_checkpoint, random_state_dict
 
 
@@ -52,6 +52,7 @@ class SemanticSegmentation(object):
             self.state = random_state_dict(seed=getattr(cfg.MODEL, "SEED", 0), **kw)
         check_state_dict(self.state, **kw)
         self._nets = {}
+        self._heads = {}                   # (h, w) -> _FullResBuffers of the upsample_pred / validate_step paths
         # "mixed" self-check: the logits error of the mixed mode follows the WEIGHTS and was measured on seeded
         # draws only, so a real checkpoint is checked once, before its first plan, against the fp32-input HIP path (itself 2e-6 from
         # the fp32 reference) on several seeded frames, and every 16-bit tensor of the plan is scanned for Inf / NaN where it is
@@ -180,11 +181,19 @@ class SemanticSegmentation(object):
         self.mixed_check.update(rung=self._rung, layer1_lo=self._layer1_lo, rel_err=err)
         return self.mixed_check
 
-    def segmentation_device(self, image_in):
-        """uint8 RGB [h,w,3] (ndarray or CUDA tensor) -> uint8 CUDA tensor [h/4-4, w/4-4]."""
+    def segmentation_device(self, image_in, upsample_pred=False):
+        """uint8 RGB [h,w,3] (ndarray or CUDA tensor) -> uint8 CUDA tensor [h/4-4, w/4-4].
+        upsample_pred=True: labels at the input's size [h, w] -- the arg-max of model(x, upsample_pred=True) (deeplab_v3_plus.py:67-69),
+        from the fused full-resolution kernel (the upsampled logits are never written).  A view of a buffer owned per input size: the
+        next call of the same size overwrites it."""
         h, w = int(image_in.shape[0]), int(image_in.shape[1])
         net = self.net_for(h, w)
-        return net.forward(image_in)
+        labels = net.forward(image_in)
+        if not upsample_pred:
+            return labels
+        head = self._full_res(h, w)
+        seg_head.full_res_eval(net.logits, h, w, labels_out=head.labels)
+        return head.labels
 
     def segmentation_device_raw(self, bgr, K=None, dist=None, factor=1):
         """The node's chain from the camera frame on (vision_semantic_segmentation_node.py:83-102) in the network's own kernels:
@@ -198,14 +207,80 @@ class SemanticSegmentation(object):
         net.set_camera(K, dist)
         return net.forward(bgr)
 
-    def segmentation(self, image_in):
-        """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map."""
-        labels = self.segmentation_device(image_in)
+    def segmentation(self, image_in, upsample_pred=False):
+        """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map ([h, w] with upsample_pred=True)."""
+        labels = self.segmentation_device(image_in, upsample_pred=upsample_pred)
         return labels.cpu().numpy().astype(np.int64)
 
-    def logits(self, image_in):
-        """float32 CUDA tensor [K, h', w'] (the reference's layout) of model(x, upsample_pred=False)."""
+    def logits(self, image_in, upsample_pred=False):
+        """float32 CUDA tensor [K, h', w'] (the reference's layout) of model(x, upsample_pred=False).
+        upsample_pred=True: model(x) as the reference's default returns it for a batch of one -- [K, h, w] at the input's size,
+        F.interpolate(..., mode='bilinear', align_corners=True) of the logits (deeplab_v3_plus.py:67-69).  Either way the result is a
+        VIEW of a buffer the plan owns per input size: the next call of the same size overwrites it (clone() to keep it)."""
         h, w = int(image_in.shape[0]), int(image_in.shape[1])
         net = self.net_for(h, w)
         net.forward(image_in)
-        return net.logits.permute(2, 0, 1)
+        if not upsample_pred:
+            return net.logits.permute(2, 0, 1)
+        head = self._full_res(h, w)
+        if head.logits is None:
+            head.logits = torch.empty((self.num_classes, h, w), dtype=torch.float32, device=self.device)
+        return seg_head.upsample_logits(net.logits, h, w, out=head.logits)
+
+    def validate_step(self, image_in, label, metric=None):
+        """The reference's validation step for a batch of one (train.py:138-141: preds = model(x); loss = loss_fn(preds, label);
+        metric.evaluate(preds, label)) on the current plan: one forward, then ONE fused kernel at the input's resolution that
+        interpolates the logits, takes the arg-max, adds MeanIOU's counts into `metric` (a metrics.MeanIOU, or None) and sums
+        CrossEntropyLoss(ignore_index=255) in fp64.  image_in: uint8 RGB [h, w, 3]; label: int64 or uint8 [h, w] (ndarray or tensor).
+        Returns the frame's loss (NaN when every label is 255).  Labels outside [0, K) and not 255 raise ValueError, as torch's
+        cross_entropy does, and then leave `metric` unchanged."""
+        h, w = int(image_in.shape[0]), int(image_in.shape[1])
+        head = self._full_res(h, w)
+        head.gt.copy_(self._label_u8(label, h, w), non_blocking=True)
+        net = self.net_for(h, w)
+        net.forward(image_in)
+        if metric is not None:
+            if metric.num_class != self.num_classes:
+                raise ValueError("the metric counts %d classes, the network has %d" % (metric.num_class, self.num_classes))
+            head.confusion.zero_()
+        seg_head.full_res_eval(net.logits, h, w, gt=head.gt, confusion=head.confusion if metric is not None else None,
+                               workspace=head.workspace)
+        res = head.workspace.result()
+        if res["invalid"]:
+            raise ValueError("%d label values are outside [0, %d) and not %d (the ignore index)"
+                             % (res["invalid"], self.num_classes, seg_head.IGNORE_INDEX))
+        if metric is not None:
+            metric.add_confusion(head.confusion)
+        return res["loss"]
+
+    def _label_u8(self, label, h, w):
+        """ground truth [h, w] (int64 / uint8 ndarray or tensor) -> uint8 tensor; values that uint8 cannot hold raise ValueError"""
+        t = label if isinstance(label, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(label))
+        if tuple(t.shape) != (h, w):
+            raise ValueError("label has shape %s, the image is %d x %d" % (tuple(t.shape), h, w))
+        if t.dtype == torch.uint8:
+            return t
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+            raise ValueError("label must hold integers, not %s" % t.dtype)
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) > 255):
+            raise ValueError("label values outside [0, %d) and not %d (the ignore index): range [%d, %d]"
+                             % (self.num_classes, seg_head.IGNORE_INDEX, int(t.min()), int(t.max())))
+        return t.to(torch.uint8)
+
+    def _full_res(self, h, w):
+        """the buffers of the full-resolution paths for an h x w input (made on first use, kept per size)"""
+        key = (int(h), int(w))
+        head = self._heads.get(key)
+        if head is None:
+            head = _FullResBuffers(self.device, h, w, self.num_classes)
+            self._heads[key] = head
+        return head
+
+
+class _FullResBuffers(object):
+    def __init__(self, device, h, w, num_classes):
+        self.logits = None                 # fp32 [K, h, w], allocated by the first logits(upsample_pred=True)
+        self.labels = torch.empty((h, w), dtype=torch.uint8, device=device)
+        self.gt = torch.empty((h, w), dtype=torch.uint8, device=device)
+        self.confusion = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=device)
+        self.workspace = seg_head.EvalWorkspace(h, w, device)

@@ -251,7 +251,7 @@ int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, 
 #define AVL_OP_STEM 1        /* uint8 RGB [H][W][3] -> normalise (semantic_segmentation.py:35-39) -> 7x7 s2 p3 conv +bias+ReLU */
 #define AVL_OP_MAXPOOL 2     /* 3x3 s2 p1 (torchvision ResNet.maxpool)                                          */
 #define AVL_OP_GEMM 3        /* 1x1 conv: out[m][n] = act(sum_k in[row(m)][k] w[n][k] + bias[n] (+ in2[m][n])) */
-#define AVL_OP_GCONV 4       /* grouped 3x3 conv, stride 1|2, dilation d, pad d, +bias+ReLU (Bottleneck.conv2)  */
+#define AVL_OP_GCONV 4       /* grouped or dense 3x3 conv, stride 1|2, dilation d, pad d, +bias+ReLU (Bottleneck.conv2; w_layout) */
 #define AVL_OP_DWCONV 5      /* depthwise 3x3 conv, dilation d, pad p, +bias+ReLU (core/nn/modules/conv.py:131)  */
 #define AVL_OP_BILINEAR 6    /* F.interpolate(mode='bilinear', align_corners=True) (aspp.py:88, decoder.py:47)   */
 #define AVL_OP_GAP 7         /* AdaptiveAvgPool2d((1,1)) -> fp32 [C] (aspp.py:69)                                */
@@ -312,6 +312,13 @@ typedef struct avl_seg_op {
     int32_t w_layout;        /* DWPW:  0 = tiles of 128 consecutive pixels, 1 = 8 x 16-pixel blocks (split input only, see AVL_OP_DWPW)
                                 GCONV: 0 = float [group][tap][ci][co] (direct kernel),
                                        1 = bf16 block-diagonal 32-channel windows [window][2][9][16][32] (MFMA kernel)
+                                       2 = DENSE 3x3 as an implicit GEMM (k_conv3x3; channels per group % 64 == 0: the ResNet /
+                                           wide ResNet conv2, ResNeXt-101's layer4): MFMA fragments [group][chunk][tap 9][cg/32]
+                                           [nj 2][part][h 2][lane 64][16 B] (network.pack_conv3x3; a chunk = one 128-byte pixel row
+                                           = 64 channels of a 16-bit type, 32 of fp32).  AVL_BF16 / AVL_F16 / AVL_F32 on one plane
+                                           (fp32: v_mfma_f32_16x16x4_f32), or AVL_F16 with w_split = 1: weights as f16 pairs (part
+                                           0 = hi, 1 = lo), optional in_lo (three passes Wh.xh + Wl.xh + Wh.xl), out (+ out_lo).
+                                           relu = 1; no MX bundle in or out; stride 1 or 2, any dilation whose input tile fits LDS
                                 STEM:  0 = float [7][7][3][64] (direct kernel), 1 = bf16 [4][6][16][32] (MFMA kernel)
                                 GEMM:  0 = the library picks the kernel; 1 .. 4 force one tile configuration of the 16-bit
                                        kernels (A/B experiments: 1 = 128 x 128 two-buffer kernel, 2 = 256 x 128 ring,

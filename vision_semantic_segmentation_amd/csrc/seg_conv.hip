@@ -779,7 +779,7 @@ int validate_conv_op(const avl_seg_op& op) {
     if (op.in_lo || op.out_lo || op.in2_lo) {
         // split (hi + lo) planes: same shape and stride as the high plane; f16 only
         AVL_REQUIRE(op.dtype == AVL_F16 && !op.in2_lo, "op %d: split planes need AVL_F16 (and no in2_lo)", op.kind);
-        AVL_REQUIRE(op.kind == AVL_OP_BILINEAR || op.kind == AVL_OP_DWCONV || (op.kind == AVL_OP_GCONV && op.w_layout == 1) || op.kind == AVL_OP_MAXPOOL ||
+        AVL_REQUIRE(op.kind == AVL_OP_BILINEAR || op.kind == AVL_OP_DWCONV || (op.kind == AVL_OP_GCONV && (op.w_layout == 1 || op.w_layout == 2)) || op.kind == AVL_OP_MAXPOOL ||
                         (op.kind == AVL_OP_STEM && op.w_layout == 1 && op.w_split == 1 && !op.in_lo),
                     "op %d does not take split planes", op.kind);
         AVL_REQUIRE(op.kind != AVL_OP_MAXPOOL || (op.in_lo != nullptr) == (op.out_lo != nullptr), "maxpool: both sides split or none");
@@ -795,6 +795,7 @@ int validate_conv_op(const avl_seg_op& op) {
             AVL_REQUIRE(op.out_h == (op.in_h + 2 * op.pad - 2 * op.dil - 1) / op.stride + 1 &&
                         op.out_w == (op.in_w + 2 * op.pad - 2 * op.dil - 1) / op.stride + 1, "gconv output size");
             if (op.w_layout == 1) return validate_gconv_mfma(op);
+            if (op.w_layout == 2) return validate_conv3x3(op);
             AVL_REQUIRE(op.w_layout == 0, "gconv weight layout %d", op.w_layout);
             break;
         }
@@ -846,6 +847,7 @@ int launch_set_camera(void* cam_dev, const double* K, const double* dist, hipStr
 
 int launch_conv_op(const avl_seg_op& op, hipStream_t s) {
     if (op.kind == AVL_OP_GCONV && op.w_layout == 1) return launch_gconv_mfma(op, s);
+    if (op.kind == AVL_OP_GCONV && op.w_layout == 2) return launch_conv3x3(op, s);
     if (op.kind == AVL_OP_STEM && op.w_layout == 1) return launch_stem_mfma(op, s);
     if (op.kind == AVL_OP_GEMV) {
         hipLaunchKernelGGL(k_gemv, dim3((op.out_c + 3) / 4), dim3(kThreads), 0, s, static_cast<const float*>(op.in),

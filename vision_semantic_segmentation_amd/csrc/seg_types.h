@@ -157,6 +157,8 @@ int launch_conv_op(const avl_seg_op& op, hipStream_t s);
 int validate_conv_op(const avl_seg_op& op);
 int launch_gconv_mfma(const avl_seg_op& op, hipStream_t s);
 int validate_gconv_mfma(const avl_seg_op& op);
+int launch_conv3x3(const avl_seg_op& op, hipStream_t s);
+int validate_conv3x3(const avl_seg_op& op);
 int launch_stem_mfma(const avl_seg_op& op, hipStream_t s);
 int launch_dwpw(const avl_seg_op& op, hipStream_t s);
 int validate_dwpw(const avl_seg_op& op);

@@ -66,9 +66,38 @@ _lib._register_seg({
 # state dict: names and shapes of the reference checkpoint
 # ----------------------------------------------------------------------------------------------
 
-LAYERS = (3, 4, 6, 3)
 PLANES = (64, 128, 256, 512)
-GROUPS, WIDTH_PER_GROUP, EXPANSION = 32, 4, 4
+EXPANSION = 4
+# MODEL.BACKBONE -> (blocks per layer, groups, width per group) of the torchvision Bottleneck ResNet builder of that name
+# (reference backbone/build.py:11-20 takes any name of backbone/resnet.py:__all__).  conv2 of a block has
+# planes * width_per_group / 64 channels per group: 4..32 for resnext50_32x4d (block-diagonal window kernels), 8..64 for
+# resnext101_32x8d, >= 64 for the others (the dense 3x3 kernel, AVL_OP_GCONV w_layout 2).
+BACKBONES = {
+    "resnet50": ((3, 4, 6, 3), 1, 64),
+    "resnet101": ((3, 4, 23, 3), 1, 64),
+    "resnet152": ((3, 8, 36, 3), 1, 64),
+    "resnext50_32x4d": ((3, 4, 6, 3), 32, 4),
+    "resnext101_32x8d": ((3, 4, 23, 3), 32, 8),
+    "wide_resnet50_2": ((3, 4, 6, 3), 1, 128),
+    "wide_resnet101_2": ((3, 4, 23, 3), 1, 128),
+}
+DEFAULT_BACKBONE = "resnext50_32x4d"
+# in backbone/resnet.py:__all__ too, but they cannot build in the reference: MyResNet hard-codes out_channels = 2048 and
+# low_level_channels = 256 (resnet.py:17-18), which BasicBlock nets (512 / 64 channels) do not produce
+UNBUILDABLE_BACKBONES = ("ResNet", "resnet18", "resnet34")
+# the reference configuration's values (kept for importers)
+LAYERS, GROUPS, WIDTH_PER_GROUP = BACKBONES[DEFAULT_BACKBONE]
+
+
+def backbone_arch(name):
+    """(layers, groups, width_per_group) of MODEL.BACKBONE `name`; NotImplementedError for anything else"""
+    if name in BACKBONES:
+        return BACKBONES[name]
+    if name in UNBUILDABLE_BACKBONES:
+        raise NotImplementedError("MODEL.BACKBONE %r is a BasicBlock ResNet: the reference's MyResNet (backbone/resnet.py:17-18) "
+                                  "hard-codes 2048 output and 256 low-level channels, so it cannot build either; supported: %s"
+                                  % (name, ", ".join(sorted(BACKBONES))))
+    raise NotImplementedError("MODEL.BACKBONE %r is not supported; supported: %s" % (name, ", ".join(sorted(BACKBONES))))
 
 
 def _bn_keys(prefix, c):
@@ -77,17 +106,18 @@ def _bn_keys(prefix, c):
 
 
 def state_spec(num_classes=19, in_channels=3, aspp_out=256, atrous_channels=(256, 256, 256, 256), low_level_out=256,
-               refine_channels=(256, 256)):
-    """[(key, shape)] of DeepLabV3Plus.state_dict() for MODEL.BACKBONE = resnext50_32x4d (keys as
+               refine_channels=(256, 256), backbone=DEFAULT_BACKBONE):
+    """[(key, shape)] of DeepLabV3Plus.state_dict() for MODEL.BACKBONE = `backbone` (keys as
     saved by the reference, without the DataParallel 'module.' prefix)."""
+    layers, groups, wpg = backbone_arch(backbone)
     spec = [("backbone.conv1.weight", (64, in_channels, 7, 7))] + _bn_keys("backbone.bn1", 64)
     inplanes = 64
-    for li, (planes, nblocks) in enumerate(zip(PLANES, LAYERS), start=1):
-        width = int(planes * (WIDTH_PER_GROUP / 64.0)) * GROUPS
+    for li, (planes, nblocks) in enumerate(zip(PLANES, layers), start=1):
+        width = int(planes * (wpg / 64.0)) * groups
         for b in range(nblocks):
             p = "backbone.layer%d.%d" % (li, b)
             spec += [(p + ".conv1.weight", (width, inplanes, 1, 1))] + _bn_keys(p + ".bn1", width)
-            spec += [(p + ".conv2.weight", (width, width // GROUPS, 3, 3))] + _bn_keys(p + ".bn2", width)
+            spec += [(p + ".conv2.weight", (width, width // groups, 3, 3))] + _bn_keys(p + ".bn2", width)
             spec += [(p + ".conv3.weight", (planes * EXPANSION, width, 1, 1))] + _bn_keys(p + ".bn3", planes * EXPANSION)
             if b == 0:
                 spec += [(p + ".downsample.0.weight", (planes * EXPANSION, inplanes, 1, 1))] + _bn_keys(p + ".downsample.1", planes * EXPANSION)
@@ -117,6 +147,8 @@ def random_state_dict(seed=0, **kw):
     convolutions, and NON-trivial BatchNorm statistics so that folding is exercised.  The gains are
     chosen so activations keep O(1) scale through all 50+ layers."""
     g = torch.Generator().manual_seed(seed)
+    backbone = kw.get("backbone", DEFAULT_BACKBONE)
+    depth = sum(backbone_arch(backbone)[0])
     st = {}
     for key, shape in state_spec(**kw):
         if key.endswith("running_var"):
@@ -127,6 +159,8 @@ def random_state_dict(seed=0, **kw):
             t = torch.rand(shape, generator=g) * 0.4 + 0.8
             if ".bn3." in key or "downsample.1" in key:
                 t = t * 0.6          # keep the residual sum from growing block after block
+                if backbone != DEFAULT_BACKBONE and depth > 16 and ".bn3." in key:
+                    t = t * math.sqrt(16.0 / depth)      # the 101 / 152-block nets: the residual branches' gains shrink with depth
         elif key.endswith(".bias"):
             t = torch.randn(shape, generator=g) * 0.05
         else:
@@ -249,6 +283,30 @@ def pack_gconv_mx(w, groups):
             sb = sbyte.permute(0, 3, 1, 2).reshape(nwin, 64, 3).to(torch.uint8)             # [win][lane][g]
             w4s[:, :, nj * 6 + pair * 3:nj * 6 + pair * 3 + 3] = sb
     return frag_hi, torch.cat([w4.reshape(-1), w4s.reshape(-1)])
+
+
+def pack_conv3x3(w, groups, elem=8, split=False):
+    """Dense 3x3 weights [C][C/groups][3][3] float64 (BN folded; C/groups % 64 == 0) -> MFMA fragments of the implicit-GEMM kernel
+    (seg_conv3x3.hip, AVL_OP_GCONV w_layout 2): [group][chunk][tap 9][nb cg/32][nj 2][part][h 2][lane 64][elem], where a chunk is
+    8 elem input channels (one 128-byte pixel row: elem = 8 for the 16-bit types, 4 for fp32), lane = kq * 16 + i holds output channel
+    nb * 32 + (i >> 2) * 8 + nj * 4 + (i & 3) of the group and input channels chunk * 8 elem + (4 h + kq) * elem + e.
+    split: part 0 = f16(w), part 1 = f16(w - hi) (float16 result); else one part (float64 result, the caller casts)."""
+    C_, cg = w.shape[0], w.shape[1]
+    assert C_ == cg * groups and cg % 64 == 0 and elem in (4, 8)
+    ck = 8 * elem
+    i, kq, h, e = torch.arange(16), torch.arange(4), torch.arange(2), torch.arange(elem)
+    rows = torch.stack([(i >> 2) * 8 + nj * 4 + (i & 3) for nj in range(2)])                          # [nj][i]
+    rows = (torch.arange(cg // 32).view(-1, 1, 1) * 32 + rows).reshape(-1)                              # [nb][nj][i]
+    cols = ((4 * h.view(2, 1, 1) + kq.view(1, 4, 1)) * elem + e.view(1, 1, elem))                      # [h][kq][e]
+    cols = (torch.arange(cg // ck).view(-1, 1, 1, 1) * ck + cols).reshape(-1)                           # [cc][h][kq][e]
+    parts = list(split_f16(w)) if split else [w.to(torch.float64)]
+    out = []
+    for part in parts:
+        wt = part.reshape(groups, cg, cg, 9).permute(0, 3, 1, 2)                                        # [g][t][co][ci]
+        m = wt[:, :, rows][:, :, :, cols]
+        m = m.reshape(groups, 9, cg // 32, 2, 16, cg // ck, 2, 4, elem)                                 # [g][t][nb][nj][i][cc][h][kq][e]
+        out.append(m.permute(0, 5, 1, 2, 3, 6, 7, 4, 8))                                                # [g][cc][t][nb][nj][h][kq][i][e]
+    return torch.stack(out, dim=5).reshape(-1).contiguous()                                             # part axis behind nj
 
 
 def pack_dw_f32(w, b):
@@ -503,12 +561,14 @@ class SegNet(object):
     MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier")    # keyword switches of the "mixed" mode
 
     def __init__(self, state, height, width, precision="bf16", device=None, num_classes=19, output_stride=8, fuse_dwpw=True, raw_frame=None,
-                 part=None, **mixed_opts):
+                 part=None, backbone=DEFAULT_BACKBONE, **mixed_opts):
         """raw_frame = (src_h, src_w): the plan's input is the RAW BGR camera frame and the node's pre-processing
         (vision_semantic_segmentation_node.py:83-98: BGR->RGB, undistort, INTER_AREA by src_w // width) runs inside the stem's loader
         (16-bit precisions); ``set_camera`` chooses the camera model, ``forward`` takes the raw frame."""
         assert output_stride in (8, 16), "deeplab_v3_plus.py:30-36 / backbone/build.py:11-16 know output strides 8 (the reference configuration, base_cfg.py:106) and 16"
         self.output_stride = int(output_stride)
+        self.backbone = backbone
+        self.layers, self.groups, self.width_per_group = backbone_arch(backbone)
         assert precision in ("bf16", "f16", "f32", "mixed")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.H, self.W = int(height), int(width)
@@ -657,13 +717,13 @@ class SegNet(object):
         assert src2 is None or use_mx, "%s: a second input needs the MX GEMM" % name
         w_mx = None
         if use_mx:
-            whi, bundle = _cached_pack((self._fp, name, "mx", tuple(wp.shape)), lambda: pack_mx_weights(wp))
+            whi, bundle = _cached_pack((self._fp, self.backbone, name, "mx", tuple(wp.shape)), lambda: pack_mx_weights(wp))
             wdev = self._dev(whi, torch.float16)
             w_mx = bundle.to(self.device)
             self._keep.append(w_mx)
         elif self.mixed:
             nsub = 3 if in_lo else 2
-            wdev = self._dev(_cached_pack((self._fp, name, "split", nsub, tuple(wp.shape)), lambda: pack_split_rows(wp, nsub)), torch.float16)
+            wdev = self._dev(_cached_pack((self._fp, self.backbone, name, "split", nsub, tuple(wp.shape)), lambda: pack_split_rows(wp, nsub)), torch.float16)
         else:
             wdev = self._dev(wp, self.act_dtype)
         if bias_dev is None:
@@ -716,13 +776,13 @@ class SegNet(object):
             wd, bd = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
             wd, b3 = wd.reshape(cout, cin), b3 + bd
         p1, p2, p3 = (self._dev(t, torch.float16) for t in _cached_pack(
-            (self._fp, p, "bottleneck"), lambda: pack_bottleneck(w1.reshape(width, cin), w2, w3.reshape(cout, width), wd, GROUPS)))
+            (self._fp, self.backbone, p, "bottleneck"), lambda: pack_bottleneck(w1.reshape(width, cin), w2, w3.reshape(cout, width), wd, self.groups)))
         bias = self._dev(torch.cat([b1, b2, b3]), torch.float32)
         ip, ild, irows = self._view(x)
         op_, old, orows = self._view(y)
         self._op(p, OP_BOTTLENECK, in_=ip, in_lo=self._lo(x), out=op_, out_lo=self._lo(y), weight=p1.data_ptr(), in2=p2.data_ptr(), in3=p3.data_ptr(),
                  in3_c=width, bias=bias.data_ptr(), in_h=hw[0], in_w=hw[1], in_c=cin, in_ld=ild, in_rows=irows, out_h=hw[0], out_w=hw[1],
-                 out_c=cout, out_ld=old, out_rows=orows, ksize=3, stride=1, pad=1, dil=1, groups=GROUPS, relu=1, w_layout=int(wd is not None),
+                 out_c=cout, out_ld=old, out_rows=orows, ksize=3, stride=1, pad=1, dil=1, groups=self.groups, relu=1, w_layout=int(wd is not None),
                  w_split=int(wd is not None))
 
     def _dwpw(self, name, src, hw, cin, w_dw, b_dw, w_pw, b_pw, dst, dst_col, dilation, padding=None, classifier=None):
@@ -832,8 +892,14 @@ class SegNet(object):
         low = None
         # replace_stride_with_dilation (backbone/build.py:11-16): OS8 (False, True, True), OS16 (False, False, True)
         dilated = (False, False, True, True) if self.output_stride == 8 else (False, False, False, True)
-        for li, (planes, nblocks, stride0, dilate) in enumerate(zip(PLANES, LAYERS, (1, 2, 2, 2), dilated), start=1):
-            width = int(planes * (WIDTH_PER_GROUP / 64.0)) * GROUPS
+        groups = self.groups
+        for li, (planes, nblocks, stride0, dilate) in enumerate(zip(PLANES, self.layers, (1, 2, 2, 2), dilated), start=1):
+            width = int(planes * (self.width_per_group / 64.0)) * groups
+            cg = width // groups
+            # conv2 routes by channels per group: <= 32 and dividing 32 -> the block-diagonal window kernels (w_layout 1, or the direct
+            # fp32 kernel); a multiple of 64 -> the dense implicit-GEMM kernel (w_layout 2, every precision, no MX-FP4 variant)
+            dense = cg % 64 == 0
+            assert dense or (cg <= 32 and 32 % cg == 0), "%s: %d channels per group" % (self.backbone, cg)
             cout = planes * EXPANSION
             previous_dilation = dilation
             stride = stride0
@@ -846,7 +912,7 @@ class SegNet(object):
                 s = stride if bi == 0 else 1
                 d = previous_dilation if bi == 0 else dilation
                 ohw = ((hw[0] + 2 * d - 2 * d - 1) // s + 1, (hw[1] + 2 * d - 2 * d - 1) // s + 1)
-                if (self.mixed_fuse_block and s == 1 and d == 1 and width == 128 and cout == 256 and cin in (64, 256)
+                if (self.mixed_fuse_block and s == 1 and d == 1 and width == 128 and cout == 256 and cin in (64, 256) and groups == 32 and 16 % cg == 0
                         and ((p + ".downsample.0.weight") in st) == (cin == 64) and x.hi.shape[1] == cin and (cin == 256 or x.lo is None)):
                     y = self._act(ohw[0] * ohw[1], cout, split=trunk_lo)
                     self._bottleneck(p, st, x, hw, cin, width, cout, y)
@@ -859,17 +925,30 @@ class SegNet(object):
                 # where conv1 runs as an MX GEMM its output keeps FP4 copies of both parts (the lo part only so): the grouped conv
                 # then corrects for the rounding of conv1's output too -- the largest single error term otherwise
                 conv1_mx = (self.mixed_mx and self.mixed_gconv_mx and x.mx is not None and x.mx_valid and x.hi.shape[1] == cin
-                            and cin % 256 == 0 and width % 256 == 0 and 32 % (width // GROUPS) == 0)
-                t1 = self._act(hw[0] * hw[1], width, split=self.full_split, mx=conv1_mx, lo_fp4=conv1_mx)
+                            and cin % 256 == 0 and width % 256 == 0 and not dense and 32 % cg == 0)
+                # a split GEMM output needs N % 128 (the ring GEMM): the 64-wide conv1 of the ResNets' layer1 writes 64 zero channels more,
+                # which conv2 does not read (its input is a channel slice of t1)
+                t1_c = _round_up(width, 128) if self.full_split else width
+                if t1_c != width:
+                    w = torch.cat([w, torch.zeros((t1_c - width,) + tuple(w.shape[1:]), dtype=w.dtype)])
+                    b = torch.cat([b, torch.zeros(t1_c - width, dtype=b.dtype)])
+                t1 = self._act(hw[0] * hw[1], t1_c, split=self.full_split, mx=conv1_mx, lo_fp4=conv1_mx)
                 self._gemm(p + ".conv1", x, hw, cin, w, b, t1, read_lo=self.mixed_conv1_split)
                 # conv2 3x3 grouped + bn2 + relu
                 w, b = fold_bn(st, p + ".conv2.weight", p + ".bn2")
-                cg = width // GROUPS
-                gconv_mx = self.mixed and t1.mx is not None and t1.mx_valid and t1.lo_fp4
+                gconv_mx = self.mixed and t1.mx is not None and t1.mx_valid and t1.lo_fp4 and not dense
                 wsplit = int(self.mixed)
                 extra_g = {}
-                if gconv_mx:
-                    frag_hi, bundle = _cached_pack((self._fp, p + ".conv2", "gconv_mx"), lambda: pack_gconv_mx(w, GROUPS))
+                if dense:
+                    if self.mixed:
+                        wg_d = self._dev(_cached_pack((self._fp, self.backbone, p + ".conv2", "dense_split"),
+                                                      lambda: pack_conv3x3(w, groups, 8, split=True)), torch.float16)
+                    else:
+                        wg_d = self._dev(_cached_pack((self._fp, self.backbone, p + ".conv2", "dense", self.half),
+                                                      lambda: pack_conv3x3(w, groups, 8 if self.half else 4)), self.act_dtype)
+                    layout = 2
+                elif gconv_mx:
+                    frag_hi, bundle = _cached_pack((self._fp, self.backbone, p + ".conv2", "gconv_mx"), lambda: pack_gconv_mx(w, groups))
                     wg_d, layout, wsplit = self._dev(frag_hi.reshape(-1), torch.float16), 1, 2
                     wb = bundle.to(self.device)
                     self._keep.append(wb)
@@ -878,33 +957,34 @@ class SegNet(object):
                     if self.mixed:       # f16 pairs: 18 "taps" = 9 hi + 9 lo per window and n-tile
                         nwin = width // 32
                         whi, wlo = split_f16(w)
-                        packed = torch.cat([pack_gconv_windows(whi.to(torch.float64), GROUPS).reshape(nwin, 2, 9, 16, 32),
-                                            pack_gconv_windows(wlo.to(torch.float64), GROUPS).reshape(nwin, 2, 9, 16, 32)], dim=2)
+                        packed = torch.cat([pack_gconv_windows(whi.to(torch.float64), groups).reshape(nwin, 2, 9, 16, 32),
+                                            pack_gconv_windows(wlo.to(torch.float64), groups).reshape(nwin, 2, 9, 16, 32)], dim=2)
                         wg_d, layout = self._dev(packed.reshape(-1), torch.float16), 1
                     else:
-                        wg_d, layout = self._dev(pack_gconv_windows(w, GROUPS), self.act_dtype), 1
+                        wg_d, layout = self._dev(pack_gconv_windows(w, groups), self.act_dtype), 1
                 else:
-                    wg = w.reshape(GROUPS, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).reshape(-1)   # [g][ky][kx][ci][co]
+                    wg = w.reshape(groups, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).reshape(-1)   # [g][ky][kx][ci][co]
                     wg_d, layout = self._dev(wg, torch.float32), 0
                 bg_d = self._dev(b, torch.float32)
                 # (conv3 as an MX GEMM reads the 3x3 output's lo part only through its FP4 copy: no f16 lo plane then)
                 t2_fp4 = self.mixed_conv2_split and self.mixed_trunk_fp4 and width % 256 == 0 and cout % 256 == 0 and layout == 1
-                t2 = self._act(ohw[0] * ohw[1], width, split=self.mixed_conv2_split, mx=True, lo_fp4=t2_fp4)
+                # (the dense kernel writes no MX bundle: conv3 then takes the non-MX split GEMM, as in full_split)
+                t2 = self._act(ohw[0] * ohw[1], width, split=self.mixed_conv2_split, mx=not dense, lo_fp4=t2_fp4)
                 if self.full_split:
-                    assert layout == 1 and wsplit == 1 and t1.lo is not None, "full_split needs the MFMA grouped conv with split weights"
+                    assert layout in (1, 2) and wsplit == 1 and t1.lo is not None, "full_split needs the MFMA grouped conv with split weights"
                     extra_g = dict(in_lo=self._lo(t1))
-                if self.full_split and s != 1:
+                if self.full_split and s != 1 and not dense:
                     # two tile buffers of a stride-2 tile do not fit the LDS with a lo plane beside the hi plane: the one strided 3x3 of the
                     # network (layer2.0) runs at stride 1 and its result is sub-sampled (pad 1: out(y, x) = out1(2 y, 2 x))
                     t2f = self._act(hw[0] * hw[1], width, split=True)
                     self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2f, hw, width, wg_d, bg_d, ksize=3, stride=1, pad=d, dil=d,
-                                  groups=GROUPS, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
+                                  groups=groups, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
                     self._spatial(p + ".conv2.sub", OP_SUBSAMPLE, t2f, hw, width, t2, ohw, width, stride=s)
                     self._spatial(p + ".conv2.sub[lo]", OP_SUBSAMPLE, t2f.lo, hw, width, t2.lo, ohw, width, stride=s)
                     self._release(t2f)
                 else:
                     self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2, ohw, width, wg_d, bg_d, ksize=3, stride=s, pad=d, dil=d,
-                                  groups=GROUPS, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
+                                  groups=groups, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
                 self._release(t1)
                 # identity / downsample.  Stride-1 downsamples (layer3.0, layer4.0) whose input and the 3x3 output both carry MX
                 # bundles are folded into conv3 as a second input along K: the identity tensor never exists

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, seg_head
-from .network import SegNet, check_state_dict, load_checkpoint, random_state_dict
+from .network import BACKBONES, SegNet, backbone_arch, check_state_dict, load_checkpoint, random_state_dict
 
 
 def _strict_bool(v, what):
@@ -35,15 +35,17 @@ class SemanticSegmentation(object):
         if not torch.cuda.is_available():
             raise RuntimeError("SemanticSegmentation needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if cfg.MODEL.TYPE != "DeepLabv3+" or cfg.MODEL.BACKBONE != "resnext50_32x4d" or cfg.MODEL.OUTPUT_STRIDE not in (8, 16):
-            raise NotImplementedError("only the reference configuration (DeepLabv3+, resnext50_32x4d; output stride 8, or 16) is built")
+        if cfg.MODEL.TYPE != "DeepLabv3+" or cfg.MODEL.OUTPUT_STRIDE not in (8, 16):
+            raise NotImplementedError("only DeepLabv3+ at output stride 8 or 16 is built (backbones: %s)" % ", ".join(sorted(BACKBONES)))
+        backbone_arch(cfg.MODEL.BACKBONE)        # NotImplementedError naming the supported set
+        self.backbone = str(cfg.MODEL.BACKBONE)
         self.output_stride = int(cfg.MODEL.OUTPUT_STRIDE)
         self.cfg = cfg
         self.num_classes = cfg.DATASET.NUM_CLASSES
         self.precision = getattr(cfg.MODEL, "PRECISION", "mixed")
         kw = dict(num_classes=self.num_classes, in_channels=cfg.DATASET.IN_CHANNELS, aspp_out=cfg.MODEL.ASPP.OUT_CHANNELS,
                   atrous_channels=tuple(cfg.MODEL.ASPP.ATROUS_CHANNELS), low_level_out=cfg.MODEL.DECODER.LOW_LEVEL_OUT_CHANNELS,
-                  refine_channels=tuple(cfg.MODEL.DECODER.REFINE_CHANNELS))
+                  refine_channels=tuple(cfg.MODEL.DECODER.REFINE_CHANNELS), backbone=self.backbone)
         if state_dict is not None:
             self.state = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         elif cfg.MODEL.WEIGHT:
@@ -92,7 +94,7 @@ class SemanticSegmentation(object):
 
     def _build(self, h, w, rung, raw_frame=None):
         """rung: a plan of the ladder ("mixed", "mixed+lo", "split16") or a plain precision ("f32", "f16", "bf16")"""
-        kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride)
+        kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride, backbone=self.backbone)
         if rung in ("f32", "f16", "bf16"):
             return SegNet(self.state, h, w, precision=rung, **kw)
         if rung == "split16":

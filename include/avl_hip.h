@@ -365,6 +365,19 @@ typedef struct avl_seg_op {
     const void* in3;
     const void* in3_mx;
     int32_t in3_c, in3_ld;
+    /* BATCH: the op runs on `batch` images at once (0 and 1 both mean one).  in_h x in_w / out_h x out_w stay the size of ONE image;
+     * the images are packed densely: image n occupies pixel rows [n * h * w, (n + 1) * h * w) of every activation (in, in_lo, in2,
+     * in2_lo, in3, out, out_lo; the uint8 labels of an arg-max), and *_rows counts the rows of all images (padding once, at the end).
+     * MX bundles keep their layout: image n's FP4 rows and scales sit at row offset n * h * w inside each plane and each C/256 slab,
+     * the slab stride stays the total row count.  GAP: in2 = fp32 scratch [batch][256][C], out = fp32 [batch][out_ld]; GEMV: in and out
+     * are [batch] vectors with strides in_ld / out_ld.  Every spatial kernel keeps its halo inside its own image, and every image
+     * computes exactly what a batch-1 op on it computes (bit for bit).  A pre-processing stem (in2 set) takes one image only
+     * (AVL_E_UNSUPPORTED otherwise). */
+    int32_t batch;
+    /* GEMM only: `bias` is fp32 [batch][w_rows] and output row r uses image r / (out_h * out_w)'s vector (the ASPP projection, whose
+     * bias comes from each image's pooling branch).  Such a GEMM runs as one launch per image, so in_rows must cover the last image's
+     * whole row tiles: in_rows >= (batch - 1) * out_h * out_w + round_up(out_h * out_w, 256).  Not with the MX GEMM (w_split 2). */
+    int32_t bias_per_image;
 } avl_seg_op;
 
 #define AVL_MX_IN_LO 1

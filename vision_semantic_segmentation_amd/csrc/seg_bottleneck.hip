@@ -111,6 +111,14 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
     const unsigned lds0 = lds_addr(lds);
     char* const A = lds + L::XBYTES;
 
+    {   // batch: image blockIdx.z (its planes; the store range shrinks by what lies in front of the image)
+        const long long ipix = (long long)p.H * p.W;
+        p.x = image_base(p.x, ipix, p.in_ld);
+        p.x_lo = image_base(p.x_lo, ipix, p.in_ld);
+        p.out = image_base(p.out, ipix, p.out_ld);
+        p.out_lo = image_base(p.out_lo, ipix, p.out_ld);
+        p.out_bytes -= (int)((long long)blockIdx.z * ipix * p.out_ld * 2);
+    }
     int bid = blockIdx.x;
     {   // XCD-aware bijective remap: the workgroups of one XCD take a contiguous run of tiles (neighbours share halo rows in one L2)
         const int nwg = gridDim.x, xcd = bid & 7, local = bid >> 3, qq = nwg >> 3, r = nwg & 7;
@@ -425,7 +433,7 @@ int device_cus() {
 }
 
 template <int CIN, bool DS, bool T1LO, bool XLO, bool OLO>
-int launch_bn(const BnArgs& a, hipStream_t s) {
+int launch_bn(const BnArgs& a, int nimg, hipStream_t s) {
     typedef BnLayout<CIN, DS, T1LO> L;
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bottleneck<CIN, DS, T1LO, XLO, OLO>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS));
     const int grid = a.ntiles < device_cus() ? a.ntiles : device_cus();
@@ -443,7 +451,7 @@ int launch_bn(const BnArgs& a, hipStream_t s) {
         if (grid <= 256) b.dbg = dbg;
     }
 #endif
-    hipLaunchKernelGGL((k_bottleneck<CIN, DS, T1LO, XLO, OLO>), dim3(grid), dim3(512), L::LDS, s, b);
+    hipLaunchKernelGGL((k_bottleneck<CIN, DS, T1LO, XLO, OLO>), dim3(grid, 1, nimg), dim3(512), L::LDS, s, b);
     AVL_LAUNCH_CHECK();
 #ifdef AVL_EXPERIMENTS
     if (b.dbg) {
@@ -472,7 +480,8 @@ int validate_bottleneck(const avl_seg_op& op) {
                 "fused bottleneck: 64 input channels with the downsample folded in, or 256 with the identity residual and no t1 lo plane");
     AVL_REQUIRE(op.in_h == op.out_h && op.in_w == op.out_w && op.in_h > 0 && op.in_w > 0, "fused bottleneck: same-size output");
     AVL_REQUIRE(op.in_ld >= op.in_c && op.in_ld % 8 == 0 && op.out_ld >= op.out_c && op.out_ld % 8 == 0, "fused bottleneck: row strides");
-    AVL_REQUIRE((long long)op.in_rows >= (long long)op.in_h * op.in_w && (long long)op.out_rows >= (long long)op.out_h * op.out_w, "fused bottleneck: rows allocated");
+    AVL_REQUIRE((long long)op.in_rows >= (long long)op.in_h * op.in_w * op_batch(op) && (long long)op.out_rows >= (long long)op.out_h * op.out_w * op_batch(op),
+                "fused bottleneck: rows allocated");
     AVL_REQUIRE((long long)op.in_rows * op.in_ld * 2 < (1LL << 31) && (long long)op.out_rows * op.out_ld * 2 < (1LL << 31), "fused bottleneck: planes beyond 2 GB (32-bit offsets)");
     AVL_REQUIRE(op.in && op.out && op.weight && op.in2 && op.in3 && op.bias, "fused bottleneck: in, out, weight (conv1), in2 (conv2 weights), in3 (conv3 weights), bias");
     AVL_REQUIRE(((reinterpret_cast<uintptr_t>(op.in) | reinterpret_cast<uintptr_t>(op.in_lo) | reinterpret_cast<uintptr_t>(op.out) | reinterpret_cast<uintptr_t>(op.out_lo) |
@@ -500,14 +509,14 @@ int launch_bottleneck(const avl_seg_op& op, hipStream_t s) {
     a.out_bytes = (int)((long long)op.out_rows * op.out_ld * 2);
     const int variant = (op.in_c == 64 ? 4 + 2 * (op.w_split ? 1 : 0) : 2 * (a.x_lo ? 1 : 0)) + (a.out_lo ? 1 : 0);
     switch (variant) {
-        case 0: return launch_bn<256, false, false, false, false>(a, s);
-        case 1: return launch_bn<256, false, false, false, true>(a, s);
-        case 2: return launch_bn<256, false, false, true, false>(a, s);
-        case 3: return launch_bn<256, false, false, true, true>(a, s);
-        case 4: return launch_bn<64, true, false, false, false>(a, s);
-        case 5: return launch_bn<64, true, false, false, true>(a, s);
-        case 6: return launch_bn<64, true, true, false, false>(a, s);
-        default: return launch_bn<64, true, true, false, true>(a, s);
+        case 0: return launch_bn<256, false, false, false, false>(a, op_batch(op), s);
+        case 1: return launch_bn<256, false, false, false, true>(a, op_batch(op), s);
+        case 2: return launch_bn<256, false, false, true, false>(a, op_batch(op), s);
+        case 3: return launch_bn<256, false, false, true, true>(a, op_batch(op), s);
+        case 4: return launch_bn<64, true, false, false, false>(a, op_batch(op), s);
+        case 5: return launch_bn<64, true, false, false, true>(a, op_batch(op), s);
+        case 6: return launch_bn<64, true, true, false, false>(a, op_batch(op), s);
+        default: return launch_bn<64, true, true, false, true>(a, op_batch(op), s);
     }
 }
 

@@ -23,6 +23,8 @@ __global__ void __launch_bounds__(kThreads) k_stem(const unsigned char* __restri
                                                   T* __restrict__ out, int OH, int OW, int out_ld) {
     const int idx = blockIdx.x * kThreads + threadIdx.x;
     if (idx >= OH * OW) return;
+    img = image_base(img, (long long)H * W, 3);
+    out = image_base(out, (long long)OH * OW, out_ld);
     const int oy = idx / OW, ox = idx % OW;
     float acc[64];
 #pragma unroll
@@ -63,6 +65,10 @@ __global__ void __launch_bounds__(kThreads) k_maxpool(const T* __restrict__ in, 
     const int c8n = C / 8;
     const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (idx >= (long long)OH * OW * c8n) return;
+    in = image_base(in, (long long)H * W, in_ld);
+    in_lo = image_base(in_lo, (long long)H * W, in_ld);
+    out = image_base(out, (long long)OH * OW, out_ld);
+    out_lo = image_base(out_lo, (long long)OH * OW, out_ld);
     const int c8 = (int)(idx % c8n);
     const int pix = (int)(idx / c8n), oy = pix / OW, ox = pix % OW;
     float m[8];
@@ -107,6 +113,8 @@ __global__ void __launch_bounds__(kThreads) k_gconv(const T* __restrict__ in, in
     const int g = blockIdx.y;
     const int pix = blockIdx.x * kThreads + threadIdx.x;
     if (pix >= OH * OW) return;
+    in = image_base(in, (long long)H * W, in_ld);
+    out = image_base(out, (long long)OH * OW, out_ld);
     const int oy = pix / OW, ox = pix % OW;
     float acc[CG];
 #pragma unroll
@@ -194,6 +202,18 @@ __global__ void __launch_bounds__(kThreads) k_dwconv(const T* __restrict__ in, c
     const int cgrp = blockIdx.x % g.cgroups, ub = blockIdx.x / g.cgroups;
     const int chunk = threadIdx.x % g.nchunk, cl = threadIdx.x / g.nchunk;
     if (cl >= g.cl) return;
+    {
+        const long long ipix = (long long)g.H * g.W, opix = (long long)g.OH * g.OW;
+        in = image_base(in, ipix, g.in_ld);
+        in_lo = image_base(in_lo, ipix, g.in_ld);
+        out = image_base(out, opix, g.out_ld);
+        out_lo = image_base(out_lo, opix, g.out_ld);
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {      // an image's FP4 rows and scales start at its first row; the slab stride stays srows
+            mx.q[pl] = image_base(mx.q[pl], opix, mx.ldq);
+            mx.s[pl] = image_base(mx.s[pl], opix, 8);
+        }
+    }
     const int c8 = cgrp * g.nchunk + chunk;
     float wt[9][8];
 #pragma unroll
@@ -366,6 +386,10 @@ __global__ void __launch_bounds__(kThreads) k_bilinear(const T* __restrict__ in,
     const int c8n = C / 8;
     const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (idx >= (long long)OH * OW * c8n) return;
+    in = image_base(in, (long long)H * W, in_ld);
+    in_lo = image_base(in_lo, (long long)H * W, in_ld);
+    out = image_base(out, (long long)OH * OW, out_ld);
+    out_lo = image_base(out_lo, (long long)OH * OW, out_ld);
     const int c8 = (int)(idx % c8n);
     const int pix = (int)(idx / c8n), oy = pix / OW, ox = pix % OW;
     const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
@@ -410,6 +434,10 @@ __global__ void __launch_bounds__(kThreads) k_dwconv_split(const T* __restrict__
     const int c8n = C / 8;
     const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (idx >= (long long)OH * OW * c8n) return;
+    in = image_base(in, (long long)H * W, in_ld);
+    in_lo = image_base(in_lo, (long long)H * W, in_ld);
+    out = image_base(out, (long long)OH * OW, out_ld);
+    out_lo = image_base(out_lo, (long long)OH * OW, out_ld);
     const int c8 = (int)(idx % c8n);
     const int pix = (int)(idx / c8n), oy = pix / OW, ox = pix % OW;
     float acc[8];
@@ -452,12 +480,15 @@ __global__ void __launch_bounds__(kThreads) k_dwconv_split(const T* __restrict__
 }
 
 // ---------------------------------------------------------------------------- global average pool
-// stage 1: block b sums rows b, b+G, b+2G, ... for its 8-channel chunks -> partial[b][C] (fp32)
+// stage 1: block b sums rows b, b+G, b+2G, ... for its 8-channel chunks -> partial[b][C] (fp32).  Image z of a batch: its own rows and
+// its own [G][C] partials, in the same order as a single image's
 template <typename T>
 __global__ void __launch_bounds__(kThreads) k_gap_partial(const T* __restrict__ in, int M, int C, int in_ld,
                                                          float* __restrict__ partial) {
     const int c8n = C / 8;
     const int G = gridDim.x;
+    in = image_base(in, M, in_ld);
+    partial = image_base(partial, G, C);
     for (int c8 = threadIdx.x; c8 < c8n; c8 += kThreads) {
         float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int r = blockIdx.x;
@@ -482,10 +513,12 @@ __global__ void __launch_bounds__(kThreads) k_gap_partial(const T* __restrict__ 
 }
 // stage 2: fixed-order sum of the partials, divide by M.  One workgroup = 32 channels x 8 slices of G.
 __global__ void __launch_bounds__(kThreads) k_gap_final(const float* __restrict__ partial, int G, int C, int M,
-                                                       float* __restrict__ out) {
+                                                       float* __restrict__ out, int out_ld) {
     __shared__ float red[8][32];
     const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + cl;
+    partial = image_base(partial, G, C);
+    out = image_base(out, 1, out_ld);
     float s = 0.f;
     if (c < C)
         for (int g = sl; g < G; g += 8) s += partial[(long long)g * C + c];
@@ -504,10 +537,13 @@ __global__ void __launch_bounds__(kThreads) k_gap_final(const float* __restrict_
 // four independent partial sums, all of a row's loads in flight at once -- with one float per lane and iteration the K = 2048
 // product of the ASPP image-pooling branch was a chain of 32 dependent load + FMA steps, 18 us for half a MFLOP).
 __global__ void __launch_bounds__(kThreads) k_gemv(const float* __restrict__ in, const float* __restrict__ w,
-                                                  const float* __restrict__ bias, float* __restrict__ out, int N, int K, int relu) {
+                                                  const float* __restrict__ bias, float* __restrict__ out, int N, int K, int relu,
+                                                  int in_ld, int out_ld) {
     const int n = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (n >= N) return;
+    in = image_base(in, 1, in_ld);          // image z: its own vectors
+    out = image_base(out, 1, out_ld);
     const float* wr = w + (long long)n * K;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     if ((K & 3) == 0 && (reinterpret_cast<uintptr_t>(wr) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
@@ -547,10 +583,12 @@ __global__ void __launch_bounds__(kThreads) k_argmax(const float* __restrict__ l
 // ------------------------------------------------------------------------------------- subsample
 template <typename T>
 __global__ void __launch_bounds__(kThreads) k_subsample(const T* __restrict__ in, int W, int C, int in_ld,
-                                                       T* __restrict__ out, int OH, int OW, int out_ld, int stride) {
+                                                       T* __restrict__ out, int H, int OH, int OW, int out_ld, int stride) {
     const int c8n = C / 8;
     const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (idx >= (long long)OH * OW * c8n) return;
+    in = image_base(in, (long long)H * W, in_ld);
+    out = image_base(out, (long long)OH * OW, out_ld);
     const int c8 = (int)(idx % c8n);
     const int pix = (int)(idx / c8n), oy = pix / OW, ox = pix % OW;
     float v[8];
@@ -621,20 +659,21 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
     const T* in = static_cast<const T*>(op.in);
     T* out = static_cast<T*>(op.out);
     const float* w = static_cast<const float*>(op.weight);
+    const unsigned nimg = (unsigned)op_batch(op);       // grid z = image (image_base)
     switch (op.kind) {
         case AVL_OP_STEM:
-            hipLaunchKernelGGL(k_stem<T>, dim3(blocks_for((long long)op.out_h * op.out_w)), dim3(kThreads), 0, s,
+            hipLaunchKernelGGL(k_stem<T>, dim3(blocks_for((long long)op.out_h * op.out_w), 1, nimg), dim3(kThreads), 0, s,
                                static_cast<const unsigned char*>(op.in), op.in_h, op.in_w, w, op.bias, out, op.out_h, op.out_w,
                                op.out_ld);
             break;
         case AVL_OP_MAXPOOL:
-            hipLaunchKernelGGL(k_maxpool<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8))), dim3(kThreads), 0, s,
+            hipLaunchKernelGGL(k_maxpool<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8)), 1, nimg), dim3(kThreads), 0, s,
                                in, op.in_h, op.in_w, op.in_c, op.in_ld, out, op.out_h, op.out_w, op.out_ld, static_cast<const T*>(op.in_lo),
                                static_cast<T*>(op.out_lo));
             break;
         case AVL_OP_GCONV: {
             const int cg = op.in_c / op.groups;
-            const dim3 grid(blocks_for((long long)op.out_h * op.out_w), op.groups);
+            const dim3 grid(blocks_for((long long)op.out_h * op.out_w), op.groups, nimg);
 #define AVL_GCONV(CG)                                                                                                   \
     hipLaunchKernelGGL((k_gconv<T, CG>), grid, dim3(kThreads), 0, s, in, op.in_h, op.in_w, op.in_ld, w, op.bias, out, \
                        op.out_h, op.out_w, op.out_ld, op.stride, op.dil)
@@ -649,7 +688,7 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
         }
         case AVL_OP_DWCONV: {
             if ((op.in_lo == nullptr) != (op.out_lo == nullptr) && !op.out_mx) {      // one side split only: the simple kernel
-                hipLaunchKernelGGL(k_dwconv_split<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8))), dim3(kThreads), 0, s,
+                hipLaunchKernelGGL(k_dwconv_split<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8)), 1, nimg), dim3(kThreads), 0, s,
                                    in, static_cast<const T*>(op.in_lo), w, op.bias, out, static_cast<T*>(op.out_lo), op.in_h, op.in_w,
                                    op.in_c, op.in_ld, op.out_h, op.out_w, op.out_ld, op.pad, op.dil, op.relu);
                 break;
@@ -694,32 +733,32 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
                         if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.q[1] = b + P + S; mx.s[1] = b + 2 * P + S; }
                         mx.srows = rows; mx.ldq = op.out_c / 2;
                     }
-                    hipLaunchKernelGGL((k_dwconv<T, true>), dim3(nblk), dim3(kThreads), 0, s, in, w, op.bias, out,
+                    hipLaunchKernelGGL((k_dwconv<T, true>), dim3(nblk, 1, nimg), dim3(kThreads), 0, s, in, w, op.bias, out,
                                        static_cast<const T*>(op.in2), g, static_cast<const T*>(op.in_lo), static_cast<T*>(op.out_lo), mx);
                     break;
                 }
             }
-            hipLaunchKernelGGL((k_dwconv<T, false>), dim3(nblk), dim3(kThreads), 0, s, in, w, op.bias, out,
+            hipLaunchKernelGGL((k_dwconv<T, false>), dim3(nblk, 1, nimg), dim3(kThreads), 0, s, in, w, op.bias, out,
                                static_cast<const T*>(op.in2), g, static_cast<const T*>(nullptr), static_cast<T*>(nullptr), MxOut());
             break;
         }
         case AVL_OP_BILINEAR:
-            hipLaunchKernelGGL(k_bilinear<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8))), dim3(kThreads), 0, s,
+            hipLaunchKernelGGL(k_bilinear<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8)), 1, nimg), dim3(kThreads), 0, s,
                                in, static_cast<const T*>(op.in_lo), op.in_h, op.in_w, op.in_c, op.in_ld, out, static_cast<T*>(op.out_lo),
                                op.out_h, op.out_w, op.out_ld);
             break;
         case AVL_OP_GAP: {
             const int G = 256;
             float* partial = static_cast<float*>(const_cast<void*>(op.in2));
-            hipLaunchKernelGGL(k_gap_partial<T>, dim3(G), dim3(kThreads), 0, s, in, op.in_h * op.in_w, op.in_c, op.in_ld, partial);
+            hipLaunchKernelGGL(k_gap_partial<T>, dim3(G, 1, nimg), dim3(kThreads), 0, s, in, op.in_h * op.in_w, op.in_c, op.in_ld, partial);
             AVL_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_gap_final, dim3((op.in_c + 31) / 32), dim3(kThreads), 0, s, partial, G, op.in_c,
-                               op.in_h * op.in_w, static_cast<float*>(op.out));
+            hipLaunchKernelGGL(k_gap_final, dim3((op.in_c + 31) / 32, 1, nimg), dim3(kThreads), 0, s, partial, G, op.in_c,
+                               op.in_h * op.in_w, static_cast<float*>(op.out), op.out_ld);
             break;
         }
         case AVL_OP_SUBSAMPLE:
-            hipLaunchKernelGGL(k_subsample<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8))), dim3(kThreads), 0, s,
-                               in, op.in_w, op.in_c, op.in_ld, out, op.out_h, op.out_w, op.out_ld, op.stride);
+            hipLaunchKernelGGL(k_subsample<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8)), 1, nimg), dim3(kThreads), 0, s,
+                               in, op.in_w, op.in_c, op.in_ld, out, op.in_h, op.out_h, op.out_w, op.out_ld, op.stride);
             break;
         default:
             return set_error(AVL_E_ARG, "op kind %d is not a typed conv op", op.kind);
@@ -734,9 +773,12 @@ int validate_conv_op(const avl_seg_op& op) {
     const int es = elem_size(op.dtype);
     AVL_REQUIRE(op.in && op.out, "op %d has NULL in/out", op.kind);
     AVL_REQUIRE(op.in_h > 0 && op.in_w > 0 && op.out_h > 0 && op.out_w > 0, "op %d has empty spatial dims", op.kind);
-    const long long in_pix = (long long)op.in_h * op.in_w, out_pix = (long long)op.out_h * op.out_w;
+    // (rows of all the images of a batch)
+    const long long in_pix = (long long)op.in_h * op.in_w * op_batch(op), out_pix = (long long)op.out_h * op.out_w * op_batch(op);
     switch (op.kind) {
         case AVL_OP_STEM:
+            if (op.in2 && op_batch(op) > 1)
+                return set_error(AVL_E_UNSUPPORTED, "a pre-processing stem (in2 = camera block) takes one raw frame: batch %d", op.batch);
             AVL_REQUIRE(op.weight && op.bias && op.out_c == 64 && op.in_c == 3, "stem expects 3 -> 64 channels");
             AVL_REQUIRE(op.out_h == (op.in_h + 6 - 7) / 2 + 1 && op.out_w == (op.in_w + 6 - 7) / 2 + 1, "stem output size");
             AVL_REQUIRE(op.out_rows >= out_pix && op.out_ld >= 64 && (op.out_ld * es) % 16 == 0, "stem output buffer");
@@ -754,6 +796,7 @@ int validate_conv_op(const avl_seg_op& op) {
             return AVL_OK;
         case AVL_OP_GEMV:
             AVL_REQUIRE(op.weight && op.in_c > 0 && op.out_c > 0, "gemv shapes");
+            AVL_REQUIRE(op_batch(op) == 1 || (op.in_ld >= op.in_c && op.out_ld >= op.out_c), "batched gemv: vector strides in_ld %d / out_ld %d", op.in_ld, op.out_ld);
             return AVL_OK;
         case AVL_OP_ARGMAX:
             AVL_REQUIRE(op.in_c > 0 && op.in_c <= 256 && op.in_ld >= op.in_c && op.in_rows >= in_pix && op.out_rows >= in_pix, "argmax shapes");
@@ -761,6 +804,7 @@ int validate_conv_op(const avl_seg_op& op) {
         case AVL_OP_GAP:
             AVL_REQUIRE(op.in2 && op.in_c % 8 == 0 && op.in_rows >= in_pix && op.in_ld >= op.in_c, "gap shapes / scratch");
             AVL_REQUIRE((op.in_ld * es) % 16 == 0, "gap in_ld");
+            AVL_REQUIRE(op_batch(op) == 1 || op.out_ld >= op.in_c, "batched gap: out_ld %d", op.out_ld);
             return AVL_OK;
         default:
             break;
@@ -850,13 +894,13 @@ int launch_conv_op(const avl_seg_op& op, hipStream_t s) {
     if (op.kind == AVL_OP_GCONV && op.w_layout == 2) return launch_conv3x3(op, s);
     if (op.kind == AVL_OP_STEM && op.w_layout == 1) return launch_stem_mfma(op, s);
     if (op.kind == AVL_OP_GEMV) {
-        hipLaunchKernelGGL(k_gemv, dim3((op.out_c + 3) / 4), dim3(kThreads), 0, s, static_cast<const float*>(op.in),
-                           static_cast<const float*>(op.weight), op.bias, static_cast<float*>(op.out), op.out_c, op.in_c, op.relu);
+        hipLaunchKernelGGL(k_gemv, dim3((op.out_c + 3) / 4, 1, op_batch(op)), dim3(kThreads), 0, s, static_cast<const float*>(op.in),
+                           static_cast<const float*>(op.weight), op.bias, static_cast<float*>(op.out), op.out_c, op.in_c, op.relu, op.in_ld, op.out_ld);
         AVL_LAUNCH_CHECK();
         return AVL_OK;
     }
     if (op.kind == AVL_OP_ARGMAX) {
-        const int M = op.in_h * op.in_w;
+        const int M = op.in_h * op.in_w * op_batch(op);      // row-wise: a batch is one long run of rows
         hipLaunchKernelGGL(k_argmax, dim3(blocks_for(M)), dim3(kThreads), 0, s, static_cast<const float*>(op.in), M, op.in_c,
                            op.in_ld, static_cast<unsigned char*>(op.out));
         AVL_LAUNCH_CHECK();

@@ -57,6 +57,13 @@ __global__ void __launch_bounds__(256) k_conv3x3(C3Args<T> p) {
     const int fr = lane & 15, kq = lane >> 4;
     const int pw = wave & 1, cw = wave >> 1;
 
+    {   // batch: image blockIdx.z
+        const long long ipix = (long long)p.H * p.W, opix = (long long)p.OH * p.OW;
+        p.in = image_base(p.in, ipix, p.in_ld);
+        p.in_lo = image_base(p.in_lo, ipix, p.in_ld);
+        p.out = image_base(p.out, opix, p.out_ld);
+        p.out_lo = image_base(p.out_lo, opix, p.out_ld);
+    }
     // ---- which tile, which channels
     const int bx = blockIdx.x;
     const int tx = bx % p.tiles_x, r1 = bx / p.tiles_x, ty = r1 % p.tiles_y, cmb = r1 / p.tiles_y;
@@ -265,11 +272,11 @@ int launch_conv3x3_typed(const avl_seg_op& op, hipStream_t s) {
     if (a.cg % 128 == 0) {
         a.nblk = a.cg / 128;
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<T, MODE, XS, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, C3_LDS_MAX));
-        hipLaunchKernelGGL((k_conv3x3<T, MODE, XS, 2>), dim3(nx, a.nblk * op.groups), dim3(256), q.lds_bytes, s, a);
+        hipLaunchKernelGGL((k_conv3x3<T, MODE, XS, 2>), dim3(nx, a.nblk * op.groups, op_batch(op)), dim3(256), q.lds_bytes, s, a);
     } else {
         a.nblk = a.cg / 64;
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<T, MODE, XS, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, C3_LDS_MAX));
-        hipLaunchKernelGGL((k_conv3x3<T, MODE, XS, 1>), dim3(nx, a.nblk * op.groups), dim3(256), q.lds_bytes, s, a);
+        hipLaunchKernelGGL((k_conv3x3<T, MODE, XS, 1>), dim3(nx, a.nblk * op.groups, op_batch(op)), dim3(256), q.lds_bytes, s, a);
     }
     AVL_LAUNCH_CHECK();
     return AVL_OK;

@@ -51,11 +51,25 @@ struct DwPwArgs {
     int mtiles, per_xcd;
     void* C;
     void* C_lo;              // "mixed" precision: low plane of the result (value - f16(value)), or NULL
-    int H, Wd, OW, ldx, ldc, M, N, K, dil, pad, ntiles;      // input H x Wd, output rows are OW wide, M = OH * OW
+    int H, Wd, OW, ldx, ldc, M, N, K, dil, pad, ntiles;      // input H x Wd, output rows are OW wide, M = OH * OW (one image)
     unsigned x_bytes;
+    int nimg;                // images of a batch (grid z)
 };
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+
+// batch: image blockIdx.z -- its input planes (the buffer-descriptor range shrinks by the bytes in front of them: a tap outside the
+// image still reads 0), its output rows, logits and labels
+__device__ __forceinline__ void dwpw_image(DwPwArgs& p) {
+    const long long ipix = (long long)p.H * p.Wd, orows = p.M;
+    p.X = image_base(static_cast<const char*>(p.X), ipix, 2LL * p.ldx);
+    p.X_lo = image_base(static_cast<const char*>(p.X_lo), ipix, 2LL * p.ldx);
+    p.x_bytes -= (unsigned)((long long)blockIdx.z * ipix * p.ldx * 2);
+    p.C = image_base(static_cast<char*>(p.C), orows, 2LL * p.ldc);
+    p.C_lo = image_base(static_cast<char*>(p.C_lo), orows, 2LL * p.ldc);
+    p.LG = image_base(p.LG, orows, p.ncls);
+    p.labels = image_base(p.labels, orows, 1);
+}
 
 // WSUB = 2 ("mixed" precision): the 1x1 weights come as f16 pairs, rows [K/64][hi 64 | lo 64]; every K-step then has
 // two MFMA passes over the same depthwise slice (hi weights, lo weights), and the depthwise work of the next slice is
@@ -74,6 +88,7 @@ __global__ void __launch_bounds__(512) k_dwpw(DwPwArgs p) {
     const int nt = blockIdx.x % p.ntiles;
     const int bm = blockIdx.x / p.ntiles, slot = (bm & 7) * p.per_xcd + (bm >> 3);
     if (slot >= p.mtiles) return;
+    dwpw_image(p);
     const int mt = p.order[slot];
     const int nk = p.K / 64;
 
@@ -294,6 +309,7 @@ __global__ void __launch_bounds__(512) k_dwpw_x(DwPwArgs p) {
     const int nt = blockIdx.x % p.ntiles;
     const int bm = blockIdx.x / p.ntiles, slot = (bm & 7) * p.per_xcd + (bm >> 3);
     if (slot >= p.mtiles) return;
+    dwpw_image(p);
     const int mt = p.order[slot];
     const int nk = p.K / 64;
 
@@ -512,7 +528,7 @@ int launch_dwpw_x(const DwPwArgs& a, hipStream_t s) {
     constexpr int lds_bytes = X_LDS_P + XP_RING * FP_STEP;
     static_assert(lds_bytes <= 160 * 1024, "k_dwpw_x LDS");
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwpw_x), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_dwpw_x, dim3(8 * a.per_xcd * a.ntiles), dim3(512), lds_bytes, s, a);
+    hipLaunchKernelGGL(k_dwpw_x, dim3(8 * a.per_xcd * a.ntiles, 1, a.nimg), dim3(512), lds_bytes, s, a);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
@@ -541,6 +557,7 @@ __global__ void __launch_bounds__(512) k_dwpw_xs(DwPwArgs p) {
     const int nt = blockIdx.x % p.ntiles;
     const int bm = blockIdx.x / p.ntiles, slot = (bm & 7) * p.per_xcd + (bm >> 3);
     if (slot >= p.mtiles) return;
+    dwpw_image(p);
     const int mt = p.order[slot];
     const int nk = p.K / 64;
 
@@ -899,7 +916,7 @@ int launch_dwpw_xs(const DwPwArgs& a, hipStream_t s) {
     constexpr int lds_bytes = S_LDS_P + XP_RING * FP_STEP;
     static_assert(lds_bytes <= 160 * 1024 && S_LDS_AH == 65536 && 4 * A_STAGE == 65536, "k_dwpw_xs LDS (the classifier epilogue keeps y hi at 0 and y lo at 64 KB, 64 KB each)");
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwpw_xs<CLS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k_dwpw_xs<CLS>, dim3(8 * a.per_xcd * a.ntiles), dim3(512), lds_bytes, s, a);
+    hipLaunchKernelGGL(k_dwpw_xs<CLS>, dim3(8 * a.per_xcd * a.ntiles, 1, a.nimg), dim3(512), lds_bytes, s, a);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
@@ -908,7 +925,7 @@ template <typename HT, int WSUB>
 int launch_dwpw_typed(const DwPwArgs& a, int mtiles, hipStream_t s) {
     const int lds_bytes = LDS_P + (a.K / 64) * P_STEP;
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwpw<HT, WSUB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_dwpw<HT, WSUB>), dim3(8 * a.per_xcd * a.ntiles), dim3(512), lds_bytes, s, a);
+    hipLaunchKernelGGL((k_dwpw<HT, WSUB>), dim3(8 * a.per_xcd * a.ntiles, 1, a.nimg), dim3(512), lds_bytes, s, a);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
@@ -938,7 +955,7 @@ int validate_dwpw(const avl_seg_op& op) {
     AVL_REQUIRE(N % 16 == 0 && op.w_rows >= (N + TN - 1) / TN * TN, "dwpw N = %d / weight rows %d", N, op.w_rows);
     AVL_REQUIRE(op.in_ld >= K && (op.in_ld * 2) % 16 == 0, "dwpw in_ld %d", op.in_ld);
     if (!op.out_f32) AVL_REQUIRE(op.out_ld >= N && (op.out_ld * 2) % 16 == 0, "dwpw out_ld %d", op.out_ld);
-    AVL_REQUIRE(op.in_rows >= op.in_h * op.in_w && op.out_rows >= M, "dwpw rows");
+    AVL_REQUIRE(op.in_rows >= op.in_h * op.in_w * op_batch(op) && op.out_rows >= M * op_batch(op), "dwpw rows");
     AVL_REQUIRE((long long)op.in_rows * op.in_ld * 2 < 0x7fffff00LL, "dwpw input larger than a buffer descriptor's range");
     AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.in) | reinterpret_cast<uintptr_t>(op.weight) | reinterpret_cast<uintptr_t>(op.out) |
                  reinterpret_cast<uintptr_t>(op.bias) | reinterpret_cast<uintptr_t>(op.in2)) % 16 == 0, "dwpw buffers must be 16-byte aligned");
@@ -954,6 +971,7 @@ int launch_dwpw(const avl_seg_op& op, hipStream_t s) {
     a.M = op.out_h * op.out_w; a.N = op.out_c; a.K = op.in_c; a.dil = op.dil;
     a.ntiles = (a.N + TN - 1) / TN;
     a.x_bytes = (unsigned)((long long)op.in_rows * op.in_ld * 2);
+    a.nimg = op_batch(op);
     const int mtiles = a.tiles_x > 0 ? a.tiles_x * ((op.out_h + 7) / 8) : (a.M + TM - 1) / TM;     // (the host's visiting order in2 has this many entries)
     a.mtiles = mtiles;
     a.per_xcd = (mtiles + 7) / 8;

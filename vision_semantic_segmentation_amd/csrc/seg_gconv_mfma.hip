@@ -77,6 +77,20 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    {   // batch: image blockIdx.z -- its planes, FP4 rows and scale rows (the slab strides o_srows / x_srows stay the total row count)
+        const long long ipix = (long long)p.H * p.W, opix = (long long)p.OH * p.OW;
+        p.in = image_base(p.in, ipix, p.in_ld);
+        p.in_lo = image_base(p.in_lo, ipix, p.in_ld);
+        p.out = image_base(p.out, opix, p.out_ld);
+        p.out_lo = image_base(p.out_lo, opix, p.out_ld);
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            p.oq[pl] = image_base(p.oq[pl], opix, p.C / 2);
+            p.os[pl] = image_base(p.os[pl], opix, 8);
+            p.xq[pl] = image_base(p.xq[pl], ipix, p.C / 2);
+            p.xs[pl] = image_base(p.xs[pl], ipix, 8);
+        }
+    }
     int bid = blockIdx.x;
     {
         // XCD-aware, bijective remap (workgroups b, b+8, ... share an XCD and its L2): each XCD takes a contiguous run of
@@ -569,7 +583,7 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
 #define AVL_GCONV_LAUNCH(NJ)                                                                                                          \
     do {                                                                                                                              \
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gconv_mfma<HT, WS, NJ, XS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gconv_mfma<HT, WS, NJ, XS>), dim3(a.nslots * a.cchunks), dim3(512), 2 * a.tile_bytes, s, a);             \
+        hipLaunchKernelGGL((k_gconv_mfma<HT, WS, NJ, XS>), dim3(a.nslots * a.cchunks, 1, op_batch(op)), dim3(512), 2 * a.tile_bytes, s, a); \
     } while (0)
     a.dephase = AVL_EXP_INT("AVL_GC_DEPHASE", 1);
     a.walk = AVL_EXP_INT("AVL_GC_WALK", 1);

@@ -1478,10 +1478,11 @@ int launch_ring_mx_t(const MxArgs& a0, hipStream_t s) {
     return AVL_OK;
 }
 
-int launch_ring_mx(const MxArgs& a, bool quantize_out, hipStream_t s) {
-    // 128-row tiles when 256-row tiles would leave more than a quarter of the 256 CUs idle (or give a ragged second wave)
+int launch_ring_mx(const MxArgs& a, int m_image, bool quantize_out, hipStream_t s) {
+    // 128-row tiles when 256-row tiles would leave more than a quarter of the 256 CUs idle (or give a ragged second wave); counted on ONE
+    // image's rows (m_image), so that a batch runs the kernel its batch-1 plan runs
     const int force = AVL_EXP_INT("AVL_MX_TILE", 0);       // 128 / 256: experiments
-    const long long t256 = (long long)((a.g.M + 255) / 256) * (a.g.N / 256);
+    const long long t256 = (long long)((m_image + 255) / 256) * (a.g.N / 256);
     const bool small = force ? force == 128 : (t256 < 192 || (t256 > 256 && t256 < 384));
     if (small) return quantize_out ? launch_ring_mx_t<1, 4>(a, s) : launch_ring_mx_t<0, 4>(a, s);
     return quantize_out ? launch_ring_mx_t<1, 8>(a, s) : launch_ring_mx_t<0, 8>(a, s);
@@ -1490,7 +1491,7 @@ int launch_ring_mx(const MxArgs& a, bool quantize_out, hipStream_t s) {
 struct TileCfg { int bm, bn; };
 inline TileCfg pick_tile(const avl_seg_op& op);
 inline bool ring_eligible(const avl_seg_op& op) {
-    const int M = op.out_h * op.out_w;
+    const int M = op.out_h * op.out_w * op_batch(op);
     return is_half(op.dtype) && op.w_layout != 1 && op.out_c > 64 && !op.out_f32 && op.out_c % 128 == 0 && op.in_rows >= (M + 255) / 256 * 256;
 }
 inline TileCfg pick_tile(const avl_seg_op& op) {
@@ -1500,13 +1501,46 @@ inline TileCfg pick_tile(const avl_seg_op& op) {
 
 }  // namespace
 
+// A GEMM with a per-image bias runs as one batch-1 GEMM per image: the op of image n (pointers at its first row, the rows that
+// follow it, its bias vector).
+static avl_seg_op gemm_image_op(const avl_seg_op& op, int n) {
+    avl_seg_op v = op;
+    const long long m = (long long)op.out_h * op.out_w * n;
+    const int es = elem_size(op.dtype), oes = op.out_f32 ? 4 : es;
+    auto at = [](const void* p, long long bytes) -> const void* { return p ? static_cast<const char*>(p) + bytes : p; };
+    v.in = at(op.in, m * op.in_ld * es);
+    v.in_lo = at(op.in_lo, m * op.in_ld * es);
+    v.in2 = at(op.in2, m * op.in2_ld * es);
+    v.in2_lo = at(op.in2_lo, m * op.in2_ld * es);
+    v.out = const_cast<void*>(at(op.out, m * op.out_ld * oes));
+    v.out_lo = const_cast<void*>(at(op.out_lo, m * op.out_ld * es));
+    if (op.out_f32) v.out_mx = const_cast<void*>(at(op.out_mx, m));         // the uint8 labels of the fused arg-max
+    v.bias = op.bias + (long long)n * op.w_rows;
+    v.in_rows = (int)(op.in_rows - m);
+    v.out_rows = (int)(op.out_rows - m);
+    v.batch = 1;
+    v.bias_per_image = 0;
+    return v;
+}
+
 int validate_gemm(const avl_seg_op& op) {
     const int es = elem_size(op.dtype);
     AVL_REQUIRE(is_half(op.dtype) || op.dtype == AVL_F32, "GEMM dtype %d", op.dtype);
     AVL_REQUIRE(op.in && op.out && op.weight && op.bias, "GEMM has NULL buffers");
-    const int M = op.out_h * op.out_w, K = op.in_c, N = op.out_c;
+    if (op.bias_per_image && op_batch(op) > 1) {
+        AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: a per-image bias is not supported by the MX GEMM");
+        for (int n = 0; n < op.batch; ++n) {
+            const avl_seg_op v = gemm_image_op(op, n);
+            AVL_REQUIRE(v.in_rows >= (op.out_h * op.out_w + 255) / 256 * 256,
+                        "GEMM with a per-image bias: image %d has %d input rows behind its first (the last image needs whole 256-row tiles)", n, v.in_rows);
+            const int rc = validate_gemm(v);
+            if (rc) return rc;
+        }
+        return AVL_OK;
+    }
+    const int M = op.out_h * op.out_w * op_batch(op), K = op.in_c, N = op.out_c;      // a batch is one long run of rows
     AVL_REQUIRE(M > 0 && N > 0 && K > 0, "GEMM M/N/K = %d/%d/%d", M, N, K);
-    AVL_REQUIRE(op.in_h * op.in_w == M, "GEMM in/out pixel counts differ (%d vs %d)", op.in_h * op.in_w, M);
+    AVL_REQUIRE(op.in_h * op.in_w == op.out_h * op.out_w, "GEMM in/out pixel counts differ (%d vs %d)", op.in_h * op.in_w, op.out_h * op.out_w);
     AVL_REQUIRE((K * es) % 128 == 0, "GEMM K = %d is not a multiple of %d", K, 128 / es);
     AVL_REQUIRE(op.in_ld >= K && (op.in_ld * es) % 16 == 0, "GEMM in_ld %d", op.in_ld);
     AVL_REQUIRE(op.out_ld >= N, "GEMM out_ld %d < N %d", op.out_ld, N);
@@ -1562,7 +1596,15 @@ int launch_gemm_w4(const avl_seg_op& op, hipStream_t s);      // seg_gemm_w4.hip
 #endif
 
 int launch_gemm(const avl_seg_op& op, hipStream_t s) {
+    if (op.bias_per_image && op_batch(op) > 1) {
+        for (int n = 0; n < op.batch; ++n) {
+            const int rc = launch_gemm(gemm_image_op(op, n), s);
+            if (rc) return rc;
+        }
+        return AVL_OK;
+    }
 #ifdef AVL_EXPERIMENTS
+    AVL_REQUIRE(op.w_layout != 5 || op_batch(op) == 1, "GEMM w_layout 5 (k_gemm_w4) takes one image");
     if (op.w_layout == 5) return launch_gemm_w4(op, s);
 #else
     AVL_REQUIRE(op.w_layout != 5, "GEMM w_layout 5 (k_gemm_w4) exists in the experiments build only (make experiments)");
@@ -1570,8 +1612,9 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
     GemmArgs a;
     a.A = op.in; a.W = op.weight; a.bias = op.bias; a.R = op.in2; a.C = op.out;
     a.lda = op.in_ld; a.ldr = op.in2_ld; a.ldc = op.out_ld;
-    a.M = op.out_h * op.out_w; a.N = op.out_c; a.K = op.in_c;
+    a.M = op.out_h * op.out_w * op_batch(op); a.N = op.out_c; a.K = op.in_c;
     a.relu = op.relu; a.out_f32 = op.out_f32;
+    const int m_image = op.out_h * op.out_w;      // tile choices look at one image: a batch runs what its batch-1 plan runs
     if (op.w_split == 2) {
         MxArgs mx;
         memset(&mx, 0, sizeof(mx));
@@ -1621,7 +1664,7 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
             mx.ldcq = a.N / 2;
             mx.c_srows = rows;
         }
-        return launch_ring_mx(mx, op.out_mx != nullptr, s);
+        return launch_ring_mx(mx, m_image, op.out_mx != nullptr, s);
     }
     a.nsub = op.w_split ? (op.in_lo ? 3 : 2) : 1;
     a.a_lo_delta = op.in_lo ? static_cast<const char*>(op.in_lo) - static_cast<const char*>(op.in) : 0;
@@ -1636,7 +1679,7 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
     if (ring_eligible(op)) {
         const bool can256 = a.N % 256 == 0 && op.w_rows % 256 == 0;
         int v = op.w_layout;
-        if (v == 0) v = (can256 && ((a.M + 255) / 256) * (a.N / 256) >= 192) ? 3 : 2;
+        if (v == 0) v = (can256 && ((m_image + 255) / 256) * (a.N / 256) >= 192) ? 3 : 2;
         if (a.nsub == 2) {
             const int deep = AVL_EXP_INT("AVL_GEMM_DEEP", 1);      // A/B: 0 = 2 + 2 tiles, one sub-step ahead
             if (v == 3 && can256) return deep ? launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s) : launch_ring<f16, 2, 4, 8, 2, 2, 1>(a, a.M, s);

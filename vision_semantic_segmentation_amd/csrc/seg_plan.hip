@@ -15,7 +15,9 @@ namespace {
 
 int validate(const avl_seg_op& op, int index) {
     int rc;
-    if (op.kind == AVL_OP_GEMM) rc = validate_gemm(op);
+    if (op.batch < 0) rc = set_error(AVL_E_ARG, "batch %d (0 or 1 = one image)", op.batch);
+    else if (op.bias_per_image && op.kind != AVL_OP_GEMM) rc = set_error(AVL_E_ARG, "bias_per_image is a GEMM field");
+    else if (op.kind == AVL_OP_GEMM) rc = validate_gemm(op);
     else if (op.kind == AVL_OP_DWPW) rc = validate_dwpw(op);
     else if (op.kind == AVL_OP_BOTTLENECK) rc = validate_bottleneck(op);
     else rc = validate_conv_op(op);
@@ -44,8 +46,9 @@ static double act_bytes(double es, bool lo_plane, bool mx, bool mx_lo) {
 }
 
 void work(const avl_seg_op& op, double& flops, double& bytes) {
-    const double es = elem_size(op.dtype);
-    const double in_pix = (double)op.in_h * op.in_w, out_pix = (double)op.out_h * op.out_w;
+    const double es = elem_size(op.dtype), nb = op_batch(op);
+    // (pixels of all the images of a batch: activations scale with it, weights are read once)
+    const double in_pix = (double)op.in_h * op.in_w * nb, out_pix = (double)op.out_h * op.out_w * nb;
     const double e_in = act_bytes(es, op.in_lo != nullptr, op.in_mx != nullptr, (op.mx_flags & AVL_MX_IN_LO) || op.in_lo);
     const double e_out = act_bytes(es, op.out_lo != nullptr, op.out_mx != nullptr, (op.mx_flags & AVL_MX_OUT_LO) || op.out_lo);
     flops = 0;
@@ -100,8 +103,8 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
             bytes = in_pix * op.in_c * es;
             break;
         case AVL_OP_GEMV:
-            flops = 2.0 * op.in_c * op.out_c;
-            bytes = 4.0 * op.in_c * op.out_c;
+            flops = 2.0 * op.in_c * op.out_c * nb;
+            bytes = 4.0 * op.in_c * op.out_c + 4.0 * (op.in_c + op.out_c) * nb;
             break;
         case AVL_OP_ARGMAX:
             bytes = in_pix * op.in_c * 4 + in_pix;
@@ -241,7 +244,7 @@ extern "C" int avl_seg_plan_nonfinite(avl_seg_plan* plan, void* stream, unsigned
         rc = avl::launch(op, s);
         if (rc) break;
         if (op.kind == AVL_OP_ARGMAX) continue;                 // uint8 labels
-        const long long rows = (op.kind == AVL_OP_GAP || op.kind == AVL_OP_GEMV) ? 1 : (long long)op.out_h * op.out_w;
+        const long long rows = (op.kind == AVL_OP_GAP || op.kind == AVL_OP_GEMV) ? avl::op_batch(op) : (long long)op.out_h * op.out_w * avl::op_batch(op);
         const bool f32 = op.dtype == AVL_F32 || op.out_f32 || op.kind == AVL_OP_GAP || op.kind == AVL_OP_GEMV;
         if (f32) avl::count_plane<float>(op.out, rows, (op.kind == AVL_OP_DWPW && op.out_f32) ? op.in3_c : op.out_c, op.out_ld, dev + i, s);
         else if (op.dtype == AVL_F16) {

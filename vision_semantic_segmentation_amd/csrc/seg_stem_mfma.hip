@@ -48,6 +48,11 @@ __global__ void __launch_bounds__(256) k_stem_mfma(StemArgs<HT> p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tx = blockIdx.x % p.tiles_x, ty = blockIdx.x / p.tiles_x;
     const int oy0 = ty * S_TH, ox0 = tx * S_TW;
+    if constexpr (!PRE) {       // batch: image blockIdx.z (a pre-processing stem takes one frame)
+        p.img = image_base(p.img, (long long)p.H * p.W, 3);
+        p.out = image_base(p.out, (long long)p.OH * p.OW, p.out_ld);
+        p.out_lo = image_base(p.out_lo, (long long)p.OH * p.OW, p.out_ld);
+    }
     const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     if constexpr (PRE) {
@@ -220,11 +225,11 @@ int launch_stem_typed(const avl_seg_op& op, hipStream_t s) {
         if (op.in2)
             hipLaunchKernelGGL((k_stem_mfma<HT, true, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
         else
-            hipLaunchKernelGGL((k_stem_mfma<HT, false, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((k_stem_mfma<HT, false, true>), dim3(a.tiles_x * tiles_y, 1, op_batch(op)), dim3(256), 0, s, a);
     } else if (op.in2)
         hipLaunchKernelGGL((k_stem_mfma<HT, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL((k_stem_mfma<HT, false>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_stem_mfma<HT, false>), dim3(a.tiles_x * tiles_y, 1, op_batch(op)), dim3(256), 0, s, a);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }

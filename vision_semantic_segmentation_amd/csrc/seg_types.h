@@ -148,6 +148,15 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 }
 
 inline int elem_size(int dtype) { return dtype == AVL_F32 ? 4 : 2; }
+
+// Batched ops (avl_seg_op.batch): images packed densely, image n at pixel row n * pixels of every plane.  A spatial kernel takes the
+// image index from blockIdx.z and moves its 64-bit base pointers there at entry (never its 32-bit per-lane offsets), so its tile decode,
+// halo clamping and XCD remap stay those of one image.  A NULL plane stays NULL.
+inline int op_batch(const avl_seg_op& op) { return op.batch > 1 ? op.batch : 1; }
+template <typename T>
+__device__ __forceinline__ T* image_base(T* p, long long pixels, long long ld) {
+    return p ? p + (long long)blockIdx.z * pixels * ld : p;
+}
 inline bool is_half(int dtype) { return dtype == AVL_BF16 || dtype == AVL_F16; }
 
 // launchers implemented in seg_gemm.hip / seg_conv.hip; each validates its op and returns AVL_*

@@ -45,6 +45,7 @@ class AvlSegOp(C.Structure):
         ("in_lo", C.c_void_p), ("in2_lo", C.c_void_p), ("out_lo", C.c_void_p),
         ("w_mx", C.c_void_p), ("in_mx", C.c_void_p), ("out_mx", C.c_void_p), ("in2_mx", C.c_void_p),
         ("in3", C.c_void_p), ("in3_mx", C.c_void_p), ("in3_c", C.c_int32), ("in3_ld", C.c_int32),
+        ("batch", C.c_int32), ("bias_per_image", C.c_int32),
     ]
 
 
@@ -561,10 +562,21 @@ class SegNet(object):
     MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier")    # keyword switches of the "mixed" mode
 
     def __init__(self, state, height, width, precision="bf16", device=None, num_classes=19, output_stride=8, fuse_dwpw=True, raw_frame=None,
-                 part=None, backbone=DEFAULT_BACKBONE, **mixed_opts):
+                 part=None, backbone=DEFAULT_BACKBONE, batch=1, **mixed_opts):
         """raw_frame = (src_h, src_w): the plan's input is the RAW BGR camera frame and the node's pre-processing
         (vision_semantic_segmentation_node.py:83-98: BGR->RGB, undistort, INTER_AREA by src_w // width) runs inside the stem's loader
-        (16-bit precisions); ``set_camera`` chooses the camera model, ``forward`` takes the raw frame."""
+        (16-bit precisions); ``set_camera`` chooses the camera model, ``forward`` takes the raw frame.
+        batch = N: the plan runs N images of height x width at once (DeepLabV3Plus.forward on an N x 3 x H x W batch); every op takes
+        them packed densely, image n at pixel rows [n h w, (n + 1) h w) of each activation, and computes for each exactly what the
+        batch-1 plan computes."""
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("SegNet: batch %d < 1" % batch)
+        if batch > 1 and raw_frame is not None:
+            raise NotImplementedError("SegNet: a raw_frame plan (pre-processing stem) takes one camera frame; batch %d" % batch)
+        if batch > 1 and part is not None:
+            raise NotImplementedError("SegNet: sub-plans (part=%r) take one image; batch %d" % (part, batch))
+        self.batch = batch
         assert output_stride in (8, 16), "deeplab_v3_plus.py:30-36 / backbone/build.py:11-16 know output strides 8 (the reference configuration, base_cfg.py:106) and 16"
         self.output_stride = int(output_stride)
         self.backbone = backbone
@@ -645,7 +657,9 @@ class SegNet(object):
     def _act(self, rows, ch, split=False, mx=False, lo_fp4=False):
         """activation buffer [rows padded][ch] (split: two planes; mx: plus the MX-FP4 bundle the next MX GEMM reads;
         lo_fp4: one f16 plane, the lo part only as FP4 in the bundle)"""
-        prow = _round_up(rows, self.ROW_PAD)
+        # a batch: `rows` per image, the images back to back, the padding once at the end -- one tile more than one image needs, so that
+        # the last image's whole row tiles stay inside the buffer when an op runs image by image (a GEMM with a per-image bias)
+        prow = _round_up(rows * self.batch, self.ROW_PAD) + (self.ROW_PAD if self.batch > 1 else 0)
         mx = bool(mx and self.mixed_mx and ch % 256 == 0)
         lo_fp4 = bool(lo_fp4 and mx)
         split = bool(split and not lo_fp4)
@@ -680,6 +694,7 @@ class SegNet(object):
         op = AvlSegOp()
         op.kind = kind
         op.dtype = self.avl_dtype
+        op.batch = self.batch
         for k, v in f.items():
             setattr(op, k, v)
         self.ops.append(op)
@@ -697,7 +712,7 @@ class SegNet(object):
         return 0 if (not isinstance(a, Act) or a.lo is None) else a.lo.data_ptr() + col * a.lo.element_size()
 
     def _gemm(self, name, src, hw, cin, w, b, dst, dst_col=0, relu=True, res=None, out_f32=False, src_col=0, bias_dev=None,
-              read_lo=True, src2=None, w2=None, b2=None, labels=None):
+              read_lo=True, src2=None, w2=None, b2=None, labels=None, bias_per_image=False):
         """1x1 conv.  w float64 [cout][cin] (BN folded), b float64 [cout].  "mixed": weights become f16 pairs; the low
         plane of `src` is read if it has one (unless read_lo = False), `res` and `dst` are used with all the planes they have."""
         h, wd = hw
@@ -764,6 +779,9 @@ class SegNet(object):
         if labels is not None:
             assert out_f32 and not use_mx and res is None and not relu
             f["out_mx"] = labels.data_ptr()
+        if bias_per_image and self.batch > 1:         # bias_dev = [batch][w_rows]: each image's own vector
+            assert not use_mx and bias_dev.shape == (self.batch, w_rows)
+            f["bias_per_image"] = 1
         self._op(name, OP_GEMM, **f)
 
     def _bottleneck(self, p, st, x, hw, cin, width, cout, y):
@@ -858,7 +876,8 @@ class SegNet(object):
         H, W = self.H, self.W
         dev = self.device
         # the plan's input: the RGB network input, or the raw BGR camera frame when the stem pre-processes
-        self.image = torch.zeros((H, W, 3) if self.raw_frame is None else self.raw_frame + (3,), dtype=torch.uint8, device=dev)
+        shape = (H, W, 3) if self.raw_frame is None else self.raw_frame + (3,)
+        self.image = torch.zeros(((self.batch,) if self.batch > 1 else ()) + shape, dtype=torch.uint8, device=dev)
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=dev)          # what a depthwise tap outside the image reads
         self.camera_block = torch.zeros(64, dtype=torch.uint8, device=dev)       # AVL_STEM_CAMERA_BYTES: zeros = no undistortion
         self._keep += [self.image, self.zero_page, self.camera_block]
@@ -877,7 +896,7 @@ class SegNet(object):
         stem = self._act(h2 * w2, 64, split=self.full_split)
         raw = {} if self.raw_frame is None else dict(in2=self.camera_block.data_ptr(), in2_ld=self.raw_frame[1])
         self._op("backbone.conv1", OP_STEM, in_=self.image.data_ptr(), out=stem.hi.data_ptr(), weight=w_stem.data_ptr(),
-                 bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.shape[0] * self.image.shape[1], out_h=h2, out_w=w2,
+                 bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.numel() // 3, out_h=h2, out_w=w2,
                  out_c=64, out_ld=64, out_rows=stem.shape[0], ksize=7, stride=2, pad=3, dil=1, groups=1, relu=1, w_layout=stem_layout,
                  w_split=int(self.full_split), out_lo=self._lo(stem), **raw)
         h4, w4 = (h2 + 2 - 3) // 2 + 1, (w2 + 2 - 3) // 2 + 1
@@ -1104,10 +1123,13 @@ class SegNet(object):
         npool = wg_.shape[0]
         aspp_out = wp_.shape[0]
         wp_ = wp_.reshape(aspp_out, ncat + npool)
-        gap_partial = torch.zeros((256, fc), dtype=torch.float32, device=dev)
-        gap_vec = torch.zeros(fc, dtype=torch.float32, device=dev)
-        pool_vec = torch.zeros(npool, dtype=torch.float32, device=dev)
-        proj_bias = torch.zeros(_round_up(aspp_out, 256), dtype=torch.float32, device=dev)
+        # per image of a batch: GAP partials [256][C], pooled vector, branch output and the projection's bias vector
+        B = self.batch
+        bshape = (lambda *s: (B,) + s) if B > 1 else (lambda *s: s)
+        gap_partial = torch.zeros(bshape(256, fc), dtype=torch.float32, device=dev)
+        gap_vec = torch.zeros(bshape(fc), dtype=torch.float32, device=dev)
+        pool_vec = torch.zeros(bshape(npool), dtype=torch.float32, device=dev)
+        proj_bias = torch.zeros(bshape(_round_up(aspp_out, 256)), dtype=torch.float32, device=dev)
         self._keep += [gap_partial, gap_vec, pool_vec, proj_bias]
         fp, fld, frows = self._view(feat)
         self._op("aspp.global_avg_pool.0", OP_GAP, in_=fp, in2=gap_partial.data_ptr(), out=gap_vec.data_ptr(), in_h=fhw[0], in_w=fhw[1],
@@ -1119,9 +1141,9 @@ class SegNet(object):
         wpd, bpd = self._dev(wp_[:, ncat:], torch.float32), self._dev(bp_, torch.float32)
         self._op("aspp.conv[pool slice]", OP_GEMV, dtype=_lib.AVL_F32, in_=pool_vec.data_ptr(), out=proj_bias.data_ptr(), weight=wpd.data_ptr(),
                  bias=bpd.data_ptr(), in_h=1, in_w=1, in_c=npool, in_ld=npool, in_rows=1, out_h=1, out_w=1, out_c=aspp_out,
-                 out_ld=aspp_out, out_rows=1, relu=0)
+                 out_ld=proj_bias.shape[-1] if B > 1 else aspp_out, out_rows=1, relu=0)
         aspp = self._act(M, aspp_out, split=self.mixed)
-        self._gemm("aspp.conv", cat, fhw, ncat, wp_[:, :ncat], None, aspp, bias_dev=proj_bias)       # dropout = identity (eval)
+        self._gemm("aspp.conv", cat, fhw, ncat, wp_[:, :ncat], None, aspp, bias_dev=proj_bias, bias_per_image=True)       # dropout = identity (eval)
         self._release(cat)
         self._release(feat)
         return aspp, aspp_out
@@ -1165,8 +1187,8 @@ class SegNet(object):
                 wc, bc = fold_bn(st, pc + ".conv.weight", None)
                 self.out_h, self.out_w = ohw
                 Mo = ohw[0] * ohw[1]
-                self.logits_buf = torch.zeros((_round_up(Mo, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
-                self.labels_buf = torch.zeros(_round_up(Mo, self.ROW_PAD), dtype=torch.uint8, device=dev)
+                self.logits_buf = torch.zeros((_round_up(Mo * self.batch, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
+                self.labels_buf = torch.zeros(_round_up(Mo * self.batch, self.ROW_PAD), dtype=torch.uint8, device=dev)
                 self._keep += [self.logits_buf, self.labels_buf]
                 self._dwpw(p + "+classifier", x, hw, cin, w, b, w2, b2, None, 0, 1, padding=0,
                            classifier=(wc.reshape(self.num_classes, w2.shape[0]), bc, self.logits_buf, self.labels_buf))
@@ -1197,8 +1219,8 @@ class SegNet(object):
         w, b = fold_bn(st, p + ".conv.weight", None)
         self.out_h, self.out_w = hw
         Mo = hw[0] * hw[1]
-        self.logits_buf = torch.zeros((_round_up(Mo, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
-        self.labels_buf = torch.zeros(_round_up(Mo, self.ROW_PAD), dtype=torch.uint8, device=dev)
+        self.logits_buf = torch.zeros((_round_up(Mo * self.batch, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
+        self.labels_buf = torch.zeros(_round_up(Mo * self.batch, self.ROW_PAD), dtype=torch.uint8, device=dev)
         self._keep += [self.logits_buf, self.labels_buf]
         # the arg-max (semantic_segmentation.py:56) rides in the classifier's epilogue: the 19 logits of a pixel sit in two lanes' registers there
         self._gemm(p, x, hw, cin, w, b, Act(self.logits_buf), relu=False, out_f32=True, labels=self.labels_buf if self.num_classes <= 32 else None)
@@ -1210,13 +1232,19 @@ class SegNet(object):
     # -------------------------------------------------------------------------------- running
     @property
     def labels(self):
-        """uint8 CUDA tensor [out_h, out_w] of the last forward (argmax over classes)."""
-        return self.labels_buf[:self.out_h * self.out_w].view(self.out_h, self.out_w)
+        """uint8 CUDA tensor [out_h, out_w] of the last forward (argmax over classes); [N, out_h, out_w] for a batch of N > 1."""
+        n = self.out_h * self.out_w
+        if self.batch > 1:
+            return self.labels_buf[:self.batch * n].view(self.batch, self.out_h, self.out_w)
+        return self.labels_buf[:n].view(self.out_h, self.out_w)
 
     @property
     def logits(self):
-        """float32 CUDA tensor [out_h, out_w, K] of the last forward (NHWC)."""
-        return self.logits_buf[:self.out_h * self.out_w].view(self.out_h, self.out_w, self.num_classes)
+        """float32 CUDA tensor [out_h, out_w, K] of the last forward (NHWC); [N, out_h, out_w, K] for a batch of N > 1."""
+        n = self.out_h * self.out_w
+        if self.batch > 1:
+            return self.logits_buf[:self.batch * n].view(self.batch, self.out_h, self.out_w, self.num_classes)
+        return self.logits_buf[:n].view(self.out_h, self.out_w, self.num_classes)
 
     def set_camera(self, K=None, dist=None, stream=None):
         """raw_frame plans: the camera model the stem undistorts with (3x3 K, k1 k2 p1 p2 k3); None = no undistortion.
@@ -1231,8 +1259,8 @@ class SegNet(object):
         _lib.check(_lib.lib().avl_stem_camera_set(C.c_void_p(self.camera_block.data_ptr()), k, d, C.c_void_p(s)), "avl_stem_camera_set")
 
     def forward(self, image_u8=None, stream=None):
-        """image_u8: CUDA/CPU uint8 [H,W,3] RGB -- or, for a raw_frame plan, the [src_h,src_w,3] BGR camera frame -- (copied
-        into the plan's input buffer) or None to reuse it."""
+        """image_u8: CUDA/CPU uint8 [H,W,3] RGB ([N,H,W,3] for a plan of batch N > 1) -- or, for a raw_frame plan, the
+        [src_h,src_w,3] BGR camera frame -- (copied into the plan's input buffer) or None to reuse it."""
         if image_u8 is not None:
             assert self.part is None, "a sub-plan takes its inputs through set_feature / set_low"
             if not isinstance(image_u8, torch.Tensor):
@@ -1267,7 +1295,7 @@ class SegNet(object):
         """float32 CPU tensor [out_h * out_w, out_c] of what op i wrote (hi + lo planes) -- valid right after a run of ops 0 .. i only (later ops
         recycle the buffers): diagnostics and tests (tools/layer_error_trace.py)."""
         op = self.ops[i]
-        rows, cols = op.out_h * op.out_w, (op.in3_c if (op.kind == OP_DWPW and op.out_f32) else op.out_c)     # (the fused classifier writes in3_c logits per pixel)
+        rows, cols = op.out_h * op.out_w * self.batch, (op.in3_c if (op.kind == OP_DWPW and op.out_f32) else op.out_c)     # (the fused classifier writes in3_c logits per pixel)
         dt = torch.float32 if (op.out_f32 or op.dtype == _lib.AVL_F32) else self.act_dtype
 
         def plane(ptr):

@@ -3,6 +3,7 @@ on the HIP conv stack.
 
     seg = SemanticSegmentation(cfg.VISION_SEM_SEG.SEM_SEG_NETWORK)
     labels = seg.segmentation(image_rgb_u8)        # int64 ndarray [h/4-4, w/4-4], as the reference returns
+    labels = seg.segmentation(np.stack(frames))    # a batch [N, h, w, 3] -> [N, h/4-4, w/4-4], one plan for all N
 
 Differences by design: weights come from a LOCAL checkpoint (``MODEL.WEIGHT``) in the reference's
 format or, when that is empty, from a seeded random init -- the reference's
@@ -55,6 +56,7 @@ class SemanticSegmentation(object):
         check_state_dict(self.state, **kw)
         self._nets = {}
         self._heads = {}                   # (h, w) -> _FullResBuffers of the upsample_pred / validate_step paths
+        self._batch_out = {}               # ("labels" | "logits", h, w, N) -> full-resolution output of a batch
         # "mixed" self-check: the logits error of the mixed mode follows the WEIGHTS and was measured on seeded
         # draws only, so a real checkpoint is checked once, before its first plan, against the fp32-input HIP path (itself 2e-6 from
         # the fp32 reference) on several seeded frames, and every 16-bit tensor of the plan is scanned for Inf / NaN where it is
@@ -75,10 +77,14 @@ class SemanticSegmentation(object):
 
     LADDER = ("mixed", "mixed+lo", "split16", "f32")
 
-    def net_for(self, h, w, raw_frame=None):
-        """The compiled plan for an h x w network input (built on first use, kept per size).  raw_frame = (src_h, src_w): the plan
-        that takes the raw BGR camera frame and pre-processes inside its first kernel."""
-        key = (int(h), int(w)) if raw_frame is None else (int(h), int(w), int(raw_frame[0]), int(raw_frame[1]))
+    def net_for(self, h, w, raw_frame=None, batch=1):
+        """The compiled plan for a batch of `batch` h x w network inputs (built on first use, kept per size and batch).  raw_frame =
+        (src_h, src_w): the plan that takes the raw BGR camera frame and pre-processes inside its first kernel (one frame only).
+        The mixed self-check runs once, on h x w frames of a batch of one; the rung it picks serves every batch."""
+        batch = int(batch)
+        if batch > 1 and raw_frame is not None:
+            raise NotImplementedError("a raw_frame plan (pre-processing stem) takes one camera frame, not a batch of %d" % batch)
+        key = (int(h), int(w), batch) + (() if raw_frame is None else (int(raw_frame[0]), int(raw_frame[1])))
         if key not in self._nets:
             if self._self_check and self.precision == "mixed" and self.mixed_check is None:
                 self.check_mixed_against_f32(key[0], key[1])
@@ -86,15 +92,16 @@ class SemanticSegmentation(object):
             if rung == "f32" and raw_frame is not None:
                 raise NotImplementedError("the self-check fell back to the fp32 plan, which has no pre-processing stem: "
                                           "use preprocess_device() + segmentation_device()")
-            net = self._build(key[0], key[1], rung, raw_frame)
+            net = self._build(key[0], key[1], rung, raw_frame, batch)
             if getattr(self.cfg.MODEL, "HIP_GRAPH", True):
                 net.capture_graph()
             self._nets[key] = net
         return self._nets[key]
 
-    def _build(self, h, w, rung, raw_frame=None):
+    def _build(self, h, w, rung, raw_frame=None, batch=1):
         """rung: a plan of the ladder ("mixed", "mixed+lo", "split16") or a plain precision ("f32", "f16", "bf16")"""
-        kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride, backbone=self.backbone)
+        kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride, backbone=self.backbone,
+                  batch=batch)
         if rung in ("f32", "f16", "bf16"):
             return SegNet(self.state, h, w, precision=rung, **kw)
         if rung == "split16":
@@ -183,19 +190,53 @@ class SemanticSegmentation(object):
         self.mixed_check.update(rung=self._rung, layer1_lo=self._layer1_lo, rel_err=err)
         return self.mixed_check
 
+    @staticmethod
+    def _geometry(image_in):
+        """[h, w, 3] -> (None, h, w); a batch [N, h, w, 3] -> (N, h, w)"""
+        if image_in.ndim == 4:
+            if int(image_in.shape[0]) < 1:
+                raise ValueError("an empty batch")
+            return int(image_in.shape[0]), int(image_in.shape[1]), int(image_in.shape[2])
+        if image_in.ndim != 3:
+            raise ValueError("expected an RGB image [h, w, 3] or a batch [N, h, w, 3], got shape %s" % (tuple(image_in.shape),))
+        return None, int(image_in.shape[0]), int(image_in.shape[1])
+
+    def _run(self, image_in):
+        """one forward of the plan for image_in's size and batch -> (plan, N or None, h, w)"""
+        n, h, w = self._geometry(image_in)
+        net = self.net_for(h, w, batch=n or 1)
+        net.forward(image_in[0] if n == 1 else image_in)
+        return net, n, h, w
+
+    def _batch_buffer(self, what, shape, dtype):
+        key = (what,) + tuple(shape)
+        t = self._batch_out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=self.device)
+            self._batch_out[key] = t
+        return t
+
     def segmentation_device(self, image_in, upsample_pred=False):
         """uint8 RGB [h,w,3] (ndarray or CUDA tensor) -> uint8 CUDA tensor [h/4-4, w/4-4].
         upsample_pred=True: labels at the input's size [h, w] -- the arg-max of model(x, upsample_pred=True) (deeplab_v3_plus.py:67-69),
         from the fused full-resolution kernel (the upsampled logits are never written).  A view of a buffer owned per input size: the
-        next call of the same size overwrites it."""
-        h, w = int(image_in.shape[0]), int(image_in.shape[1])
-        net = self.net_for(h, w)
-        labels = net.forward(image_in)
+        next call of the same size overwrites it.
+        A batch [N,h,w,3] runs through one plan of batch N -> [N, h/4-4, w/4-4] ([N, h, w] with upsample_pred: the full-resolution
+        kernel once per image, on that image's logits)."""
+        net, n, h, w = self._run(image_in)
+        if n is None:
+            if not upsample_pred:
+                return net.labels
+            head = self._full_res(h, w)
+            seg_head.full_res_eval(net.logits, h, w, labels_out=head.labels)
+            return head.labels
+        logits = net.logits if n > 1 else net.logits.unsqueeze(0)
         if not upsample_pred:
-            return labels
-        head = self._full_res(h, w)
-        seg_head.full_res_eval(net.logits, h, w, labels_out=head.labels)
-        return head.labels
+            return net.labels if n > 1 else net.labels.unsqueeze(0)
+        out = self._batch_buffer("labels", (n, h, w), torch.uint8)
+        for i in range(n):
+            seg_head.full_res_eval(logits[i], h, w, labels_out=out[i])
+        return out
 
     def segmentation_device_raw(self, bgr, K=None, dist=None, factor=1):
         """The node's chain from the camera frame on (vision_semantic_segmentation_node.py:83-102) in the network's own kernels:
@@ -210,7 +251,8 @@ class SemanticSegmentation(object):
         return net.forward(bgr)
 
     def segmentation(self, image_in, upsample_pred=False):
-        """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map ([h, w] with upsample_pred=True)."""
+        """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map ([h, w] with upsample_pred=True); a batch
+        (N, h, w, 3) -> (N, h', w')."""
         labels = self.segmentation_device(image_in, upsample_pred=upsample_pred)
         return labels.cpu().numpy().astype(np.int64)
 
@@ -218,10 +260,17 @@ class SemanticSegmentation(object):
         """float32 CUDA tensor [K, h', w'] (the reference's layout) of model(x, upsample_pred=False).
         upsample_pred=True: model(x) as the reference's default returns it for a batch of one -- [K, h, w] at the input's size,
         F.interpolate(..., mode='bilinear', align_corners=True) of the logits (deeplab_v3_plus.py:67-69).  Either way the result is a
-        VIEW of a buffer the plan owns per input size: the next call of the same size overwrites it (clone() to keep it)."""
-        h, w = int(image_in.shape[0]), int(image_in.shape[1])
-        net = self.net_for(h, w)
-        net.forward(image_in)
+        VIEW of a buffer the plan owns per input size: the next call of the same size overwrites it (clone() to keep it).
+        A batch [N,h,w,3] -> [N, K, h', w'] (the reference's NCHW batch), [N, K, h, w] with upsample_pred."""
+        net, n, h, w = self._run(image_in)
+        if n is not None:
+            logits = net.logits if n > 1 else net.logits.unsqueeze(0)
+            if not upsample_pred:
+                return logits.permute(0, 3, 1, 2)
+            out = self._batch_buffer("logits", (n, self.num_classes, h, w), torch.float32)
+            for i in range(n):
+                seg_head.upsample_logits(logits[i], h, w, out=out[i])
+            return out
         if not upsample_pred:
             return net.logits.permute(2, 0, 1)
         head = self._full_res(h, w)
@@ -236,6 +285,8 @@ class SemanticSegmentation(object):
         CrossEntropyLoss(ignore_index=255) in fp64.  image_in: uint8 RGB [h, w, 3]; label: int64 or uint8 [h, w] (ndarray or tensor).
         Returns the frame's loss (NaN when every label is 255).  Labels outside [0, K) and not 255 raise ValueError, as torch's
         cross_entropy does, and then leave `metric` unchanged."""
+        if image_in.ndim != 3:
+            raise NotImplementedError("validate_step takes one image [h, w, 3], not shape %s" % (tuple(image_in.shape),))
         h, w = int(image_in.shape[0]), int(image_in.shape[1])
         head = self._full_res(h, w)
         head.gt.copy_(self._label_u8(label, h, w), non_blocking=True)

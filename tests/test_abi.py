@@ -157,10 +157,10 @@ def test_mx_pipe_stream_holds_no_scalar_loads_and_no_scratch():
         assert any(l.startswith("s_waitcnt vmcnt(4)") for l in stream) or "Li4ELi" in sym, sym
 
 
-def test_release_library_reads_no_environment_and_holds_no_experiment_kernels():
-    """VERDICT r3 / ADVICE r3: timing probes (results are garbage by design), A/B switches and the k_gemm_w4 experiment live in
-    the experiments build only (`make experiments`, -DAVL_EXPERIMENTS -> libavl_hip_exp.so): the release library must not even
-    import getenv, and must not contain a probe instantiation of the MX GEMM or the experiment kernel."""
+def test_library_reads_no_environment_and_holds_only_launched_kernels():
+    """VERDICT r3 / ADVICE r3: the library takes no A/B switch from the environment -- it must not even import getenv -- and
+    holds no timing probe (results garbage by design) nor experiment kernel: k_gemm_mx_pipe is compiled for exactly the
+    <IO, MI, LATE> sets launch_ring_mx_t launches."""
     import subprocess
     kn = _notes()
     undefined = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
@@ -174,7 +174,7 @@ def test_release_library_reads_no_environment_and_holds_no_experiment_kernels():
     assert not any("k_gemm_w4" in n for n in names)
     assert not any("k_gemm_mx_pp" in n for n in names)
     import re as _re
-    pipe = [_re.search(r"k_gemm_mx_pipe<(\d+), (\d+), (\d+), (\d+), (\d+)>", n) for n in names if "k_gemm_mx_pipe<" in n]
-    assert len(pipe) >= 4 and all(pipe), "k_gemm_mx_pipe's template list changed: update this test (%s)" % [n for n in names if "k_gemm_mx_pipe<" in n][:2]
-    for m in pipe:          # <IO, MI, LATE, PROBE, SPREAD>
-        assert m.group(4) == "0" and m.group(5) == "0", "probe / experiment-schedule instantiation in the release library: %s" % m.group(0)
+    pipe = [_re.search(r"k_gemm_mx_pipe<(\d+), (\d+), (\d+)>", n) for n in names if "k_gemm_mx_pipe<" in n]
+    assert pipe and all(pipe), "k_gemm_mx_pipe's template list changed: update this test (%s)" % [n for n in names if "k_gemm_mx_pipe<" in n][:2]
+    # <IO, MI, LATE>: IO = quantised output or not; MI = 8 (256-row tiles) runs LATE = 0, MI = 4 (128-row tiles) LATE = 1
+    assert sorted(m.groups() for m in pipe) == [("0", "4", "1"), ("0", "8", "0"), ("1", "4", "1"), ("1", "8", "0")], [m.group(0) for m in pipe]

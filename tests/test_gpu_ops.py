@@ -203,14 +203,8 @@ def test_bilinear_align_corners(case, precision, cuda_device):
     assert float(dst[:, Cc:].abs().max()) == 0.0                     # the neighbouring columns are untouched
 
 
-def _experiments_build():
-    """True when AVL_HIP_LIB points at libavl_hip_exp.so (`make experiments`): only that build holds the experiment kernels."""
-    import os
-    return os.path.basename(os.environ.get("AVL_HIP_LIB", "")).startswith("libavl_hip_exp")
-
-
-# layout 5 = k_gemm_w4, the one-wave-per-SIMD experiment (16-bit, N % 256 == 0): compiled into the experiments build only
-@pytest.mark.parametrize("layout", [0, 5] if _experiments_build() else [0])
+# w_layout 0: the library picks the kernel by shape (1 .. 4 force one tile configuration: tools/bench_gemm.py)
+@pytest.mark.parametrize("layout", [0])
 @pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
 @pytest.mark.parametrize("case", [  # (M, K, N, residual, relu)
     (1000, 64, 128, False, True), (777, 256, 64, False, True), (2600, 128, 256, True, True), (50000, 512, 256, False, False),
@@ -218,8 +212,6 @@ def _experiments_build():
 ])
 def test_pointwise_gemm(case, precision, layout, cuda_device):
     import torch
-    if layout == 5 and (precision == "f32" or case[2] % 256):
-        pytest.skip("k_gemm_w4 takes 16-bit operands and N % 256 == 0")
     from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
     M, K, N, res, relu = case
     tdt, did, tol = _dt(precision)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times AVL_OP_DWPW alone at the frame's shapes: the three ASPP branches (k_dwpw_x: 135 x 240 x 2048 -> 256, dilation 12 / 24 / 36) and the
 decoder's two refine blocks (k_dwpw_xs, split input: 270 x 480 x 512 -> 256 and 268 x 478 x 256 -> 256, pad 0).  Random operands,
-`reps` launches between two events on the launch stream.  With a DW_EXP library (tools/ab_dwpw.sh) the numbers are phase ablations."""
+`reps` launches between two events on the launch stream."""
 import ctypes as C
 import os
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the multi-pass ("mixed" precision) ring GEMM on the network's layer shapes.
-    python tools/bench_gemm_split.py [--reps 20]     (AVL_GEMM_DEEP=0/1 selects the ring depth of the 2-pass 256x256 kernel)"""
+    python tools/bench_gemm_split.py [--reps 20]"""
 import argparse
 import ctypes as C
 import os

@@ -18,8 +18,9 @@ import csv, glob, collections, json, re
 def fam(name):
     m = re.search(r"k_[a-z0-9_]+", name)
     base = m.group(0) if m else name[:30]
-    t = re.search(r"k_gemm_ring<[^,]*, *(\d+), (\d+), (\d+), (\d+), (\d+), (\d+)", name) or re.search(r"k_gemm_ringI[^L]*Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", name)
-    if t and "ring_mx" not in name: base += "<%s,%s,%s,%s,probe %s,nsub %s>" % t.groups()
+    # k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST>
+    t = re.search(r"k_gemm_ring<[^,]*, *(\d+), (\d+), (\d+), (\d+), (\d+)", name) or re.search(r"k_gemm_ringI[^L]*Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", name)
+    if t and "ring_mx" not in name: base += "<%s,%s,%s,%s,nsub %s>" % t.groups()
     return base
 agg=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()
 for f in glob.glob('gpurun_out/pmc_seg/p*/**/*counter_collection.csv', recursive=True):

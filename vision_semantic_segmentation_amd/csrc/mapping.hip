@@ -495,12 +495,12 @@ __global__ void __launch_bounds__(kBlock) k_grid_apply_lists(MapT* __restrict__ 
 // (class i, then its lane bonus) and written back with every lane busy and every load independent.
 // Cells per workgroup round: a camera frustum puts most touched cells into a few grid rows, and the sweep ends when its BUSIEST
 // workgroup does -- 4096-cell rounds (one 16-byte mask vector per lane) instead of 16384: config E 38.4 -> 34.6 us per frame
-// (profiles/r04/mapping_sweep_chunk_ab.log; AVL_SWEEP_VEC = 4 / 2 / 1 in the experiments build).
-constexpr int kSweepVecDefault = 1;
-template <typename MapT, int kSweepVec>                       // 16-byte mask vectors per lane and round: 4 / 2 / 1 -> 16384 / 8192 / 4096 cells
+// (profiles/r04/mapping_sweep_chunk_ab.log).
+constexpr int kSweepVec = 1;                                  // 16-byte mask vectors per lane and round
+constexpr int kSweepCells = kBlock * kSweepVec * 16;          // cells per workgroup round
+template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_grid_sweep_bytes(MapT* __restrict__ map, int C, unsigned bonus_classes, CmParams cm,
-                                                             unsigned char* __restrict__ mask, long long ncell, int exp) {
-    constexpr int kSweepCells = kBlock * kSweepVec * 16;      // cells per workgroup round
+                                                             unsigned char* __restrict__ mask, long long ncell) {
     __shared__ unsigned list[kSweepCells];
     __shared__ int count;
     const long long rounds = (ncell + kSweepCells - 1) / kSweepCells;
@@ -530,9 +530,6 @@ __global__ void __launch_bounds__(kBlock) k_grid_sweep_bytes(MapT* __restrict__ 
                 mine += __builtin_popcount(t & 0x01010101u);
             }
         }
-#ifdef AVL_EXPERIMENTS
-        if (exp & 2) mine = 0;
-#endif
         const int lane = threadIdx.x & 63;
         int incl = mine;
 #pragma unroll
@@ -567,11 +564,7 @@ __global__ void __launch_bounds__(kBlock) k_grid_sweep_bytes(MapT* __restrict__ 
             if ((v[u].x | v[u].y | v[u].z | v[u].w) != 0u)
                 *reinterpret_cast<uint4*>(mask + base + (u * kBlock + threadIdx.x) * 16) = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
-#ifdef AVL_EXPERIMENTS
-        const int n = (exp & 1) ? 0 : count;
-#else
         const int n = count;
-#endif
         for (int k = threadIdx.x; k < n; k += kBlock) {
             const unsigned e = list[k];
             const unsigned m = e & 0xffu;
@@ -777,39 +770,18 @@ int launch_sweep_bytes(const avl_grid* g, const double* cm_host, unsigned bonus,
     memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
     const long long ncell = (long long)g->Hm * g->Wm;
     unsigned char* mask = reinterpret_cast<unsigned char*>(g->cell_mask);
-    const int exp = AVL_EXP_INT("AVL_SWEEP_EXP", 0);      // timing experiments only (experiments build; 0 in the release library)
-#ifdef AVL_EXPERIMENTS
-    const int vec = AVL_EXP_INT("AVL_SWEEP_VEC", kSweepVecDefault);
-#else
-    constexpr int vec = kSweepVecDefault;
-#endif
-#define AVL_SWEEP_LAUNCH(T, V)                                                                                                        \
-    do {                                                                                                                              \
-        const long long rounds = (ncell + kBlock * V * 16 - 1) / (kBlock * V * 16);                                                   \
-        const unsigned blocks = (unsigned)(rounds < 8192 ? rounds : 8192);                                                            \
-        hipLaunchKernelGGL((k_grid_sweep_bytes<T, V>), dim3(blocks), dim3(kBlock), 0, s, static_cast<T*>(g->map), g->C, bonus, cm, mask, ncell, exp); \
-    } while (0)
-    if (g->map_dtype == AVL_F64) {
-#ifdef AVL_EXPERIMENTS
-        if (vec == 4) AVL_SWEEP_LAUNCH(double, 4); else if (vec == 2) AVL_SWEEP_LAUNCH(double, 2); else
-#endif
-            AVL_SWEEP_LAUNCH(double, kSweepVecDefault);
-    } else {
-#ifdef AVL_EXPERIMENTS
-        if (vec == 4) AVL_SWEEP_LAUNCH(float, 4); else if (vec == 2) AVL_SWEEP_LAUNCH(float, 2); else
-#endif
-            AVL_SWEEP_LAUNCH(float, kSweepVecDefault);
-    }
-#undef AVL_SWEEP_LAUNCH
-    (void)vec;
+    const long long rounds = (ncell + kSweepCells - 1) / kSweepCells;
+    const unsigned blocks = (unsigned)(rounds < 8192 ? rounds : 8192);
+    if (g->map_dtype == AVL_F64)
+        hipLaunchKernelGGL(k_grid_sweep_bytes<double>, dim3(blocks), dim3(kBlock), 0, s, static_cast<double*>(g->map), g->C, bonus, cm, mask, ncell);
+    else
+        hipLaunchKernelGGL(k_grid_sweep_bytes<float>, dim3(blocks), dim3(kBlock), 0, s, static_cast<float*>(g->map), g->C, bonus, cm, mask, ncell);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
 
 // byte mask usable: class bits + bonus bits fit a byte, whole 16-byte vectors, aligned scratch
 bool byte_mask_ok(const avl_grid* g, unsigned bonus) {
-    const char* mode = AVL_EXP_STR("AVL_MASK_MODE");          // "32": keep the 32-bit mask (experiments build only)
-    if (mode && mode[0] == '3') return false;
     const long long cells = (long long)g->Hm * g->Wm;
     return g->C + __builtin_popcount(bonus) <= 8 && cells % 16 == 0 && (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
 }
@@ -828,13 +800,9 @@ ListGeom list_geom(int n) {
 // MODE 3 needs the big counter block, room for kLists x cap entries and a byte mask.  Its cost grows with the cloud (returning
 // atomics in the vote, rows visited in point order -- no locality -- in the apply), the sweep's is ~15 us whatever the cloud:
 // measured 17 vs 22 us per frame at 120 k points on 4 M cells (config C), 54 vs 38 us at 1 M points on 16 M cells (config E).
-// AVL_APPLY_MODE=plist forces it (experiments).
 bool use_lists(const avl_grid* g, int n, unsigned bonus) {
-    const char* mode = AVL_EXP_STR("AVL_APPLY_MODE");
     if (g->counter_len < kListBase + 2 * kLists || !byte_mask_ok(g, bonus)) return false;
     if ((long long)list_geom(n).cap * kLists > g->touched_cap) return false;
-    if (mode && mode[0] == 'p') return true;
-    if (mode) return false;
     return n <= 250000 && (long long)n * 2 <= (long long)g->Hm * g->Wm;
 }
 int launch_apply_lists(const avl_grid* g, const double* cm_host, unsigned bonus, int n, hipStream_t s) {
@@ -854,13 +822,10 @@ int launch_apply_lists(const avl_grid* g, const double* cm_host, unsigned bonus,
 }
 
 // list (sparse) vs sweep (dense) apply: the sweep reads Hm*Wm*4 bytes whatever the cloud; the list costs a
-// returning atomic + an append per first touch.  AVL_APPLY_MODE=list|scan overrides (experiments).
+// returning atomic + an append per first touch.
 bool use_scan(const avl_grid* g, int n, unsigned bonus) {
-    const char* mode = AVL_EXP_STR("AVL_APPLY_MODE");
     const long long cells = (long long)g->Hm * g->Wm;
     if (cells % 4 != 0 || (reinterpret_cast<uintptr_t>(g->cell_mask) & 15)) return false;
-    if (mode && mode[0] == 'l') return false;
-    if (mode && mode[0] == 's') return true;
     // measured (32-bit sweep): sweep wins at 120 k points on 4 M cells (25 vs 36 us) and 1 M on 16 M (73 vs 213 us); the byte
     // sweep reads a quarter of that, so it stays ahead down to much sparser clouds
     return (long long)n * (byte_mask_ok(g, bonus) ? 1024 : 128) >= cells;

@@ -20,13 +20,7 @@
 // Per tile: two barriers (t2 visible | t2 read + next X tile landed).  The next tile's X DMA is issued right behind the first
 // barrier and has all of conv3 to land.  Every product runs Wh.xh + Wl.xh (+ Wh.xl where the operand has a lo plane) on
 // v_mfma_f32_16x16x32_f16 with fp32 accumulation.
-#include <cstring>
-
 #include "seg_types.h"
-
-#ifndef BN_EXP
-#define BN_EXP 0          // hook for same-box A/B builds of tuning variants (tools/ab_bottleneck.sh: make EXPFLAGS=-DBN_EXP=n OUT=... BUILD=...); 0 = what ships
-#endif
 
 namespace avl {
 namespace {
@@ -54,7 +48,6 @@ struct BnArgs {
     int H, W, in_ld, out_ld;
     int tiles_x, ntiles;
     int out_bytes;       // one output plane (buffer stores are range-checked against it)
-    unsigned long long* dbg;   // experiments build, AVL_BN_PROBE=1: per-wave cycle sums of the tile loop's phases (host-visible memory), else NULL
 };
 
 template <int CIN, bool DS, bool T1LO>
@@ -155,16 +148,6 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
     const unsigned a_wr = (unsigned)(c * 256) + (unsigned)((((2 * wave) | (q >> 1)) ^ c) << 4) + (unsigned)((q & 1) * 8);   // t1 / t2 store: + m * 4096
     const unsigned t2_rd = (unsigned)(c * 256) + (unsigned)((q ^ c) << 4);                              // conv3 read: ^ (ks << 6), + m * 4096
 
-    unsigned long long tsum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // probe: conv1 | t1 store + conv2 + t2 store | t2 lo store + conv3 preloads | B2 | DMA issue | conv3 | landing + B3 | stores | - | tiles
-    unsigned long long t0 = 0;
-    auto stamp = [&](int slot) __attribute__((always_inline)) {
-        if (kStamps && p.dbg) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            if (slot >= 0) tsum[slot] += t - t0;
-            t0 = t;
-        }
-    };
     // weight fragments by BUFFER loads: wave-uniform resource (SGPRs) + 32-bit lane offset + scalar fragment offset -- per-request 64-bit
     // VGPR pointers were what hipcc hoisted out of the tile loop and spilled
     const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.w1)) + (size_t)wave * (KS1 * 2 * 1024), 0, KS1 * 2 * 1024, 0x00020000);
@@ -182,7 +165,6 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
 
     for (; tile < p.ntiles; tile += gridDim.x, ++it) {
         const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-        stamp(-1);
         const char* X = lds + (DS ? (it & 1) * L::XTILE : 0);
         // (opaque copies of the lane coordinates: hipcc would otherwise hoist the ~70 tile-invariant LDS offsets and pixel masks out of
         // the tile loop and spill them)
@@ -316,16 +298,11 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
             for (int r = 0; r < BT_H; ++r)
                 if (r >= next_row) conv2_row(r);
         }
-        stamp(0);
         if constexpr (!T1LO) {
 #pragma unroll
             for (int r = 0; r < BT_H; ++r) *reinterpret_cast<uint2*>(A + L::T2LO_OFF + a_wr + r * 4096) = t2lo[r];
         }
-        stamp(1);
-        stamp(2);
         __syncthreads();                                   // B2: t2 visible; every wave is done with the X tile it read in conv1
-        stamp(3);
-        stamp(4);
 
         // ================================================= conv3 (+ downsample) + residual, row by row; results packed in registers
         // The rows' results leave as they are produced, by BUFFER stores: a pixel outside the image gets an offset past the buffer's end
@@ -403,7 +380,6 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
                 }
             }
         }
-        stamp(5);
         // the next X tile has landed: behind its last DMA instruction this wave issued the stores of rows 2 .. 7 (all 8 rows where the DMA went
         // out at the top of the tile) -- at least; anything hipcc adds only makes the wait stricter
         {
@@ -411,13 +387,6 @@ __global__ void __launch_bounds__(512) k_bottleneck(BnArgs p) {
             if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NTAIL) : "memory");
         }
         __syncthreads();                                       // B3: ... for every wave; t2 (and, DS, this X tile) is read
-        stamp(6);
-        stamp(7);
-        if (kStamps && p.dbg) tsum[9] += 1;
-    }
-    if (kStamps && p.dbg && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) p.dbg[((size_t)blockIdx.x * 8 + wave) * 10 + i] = tsum[i];
     }
 }
 
@@ -437,34 +406,8 @@ int launch_bn(const BnArgs& a, int nimg, hipStream_t s) {
     typedef BnLayout<CIN, DS, T1LO> L;
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bottleneck<CIN, DS, T1LO, XLO, OLO>), hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS));
     const int grid = a.ntiles < device_cus() ? a.ntiles : device_cus();
-    BnArgs b = a;
-    b.dbg = nullptr;
-#ifdef AVL_EXPERIMENTS
-    // timing experiment: where do a wave's cycles go (s_memtime stamps; synchronises the stream: never inside a graph capture)
-    static unsigned long long* dbg = nullptr;
-    if (AVL_EXP_INT("AVL_BN_PROBE", 0)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        AVL_HIP_CHECK(hipStreamIsCapturing(s, &cap));
-        AVL_REQUIRE(cap == hipStreamCaptureStatusNone, "AVL_BN_PROBE synchronises the stream: not while it is being captured");
-        if (!dbg) AVL_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dbg), 256 * 8 * 10 * sizeof(unsigned long long), 0));
-        memset(dbg, 0, 256 * 8 * 10 * sizeof(unsigned long long));
-        if (grid <= 256) b.dbg = dbg;
-    }
-#endif
-    hipLaunchKernelGGL((k_bottleneck<CIN, DS, T1LO, XLO, OLO>), dim3(grid, 1, nimg), dim3(512), L::LDS, s, b);
+    hipLaunchKernelGGL((k_bottleneck<CIN, DS, T1LO, XLO, OLO>), dim3(grid, 1, nimg), dim3(512), L::LDS, s, a);
     AVL_LAUNCH_CHECK();
-#ifdef AVL_EXPERIMENTS
-    if (b.dbg) {
-        AVL_HIP_CHECK(hipStreamSynchronize(s));
-        double sum[10] = {};
-        for (int i = 0; i < grid * 8; ++i)
-            for (int k = 0; k < 10; ++k) sum[k] += (double)dbg[i * 10 + k];
-        const double n = sum[9] > 0 ? sum[9] : 1;
-        fprintf(stderr, "[bottleneck probe] cin %d ds %d t1lo %d xlo %d olo %d, %.1f tiles per wave; cycles per tile: conv1 + conv2 %.0f | t2 lo + preloads %.0f | - %.0f | B2 %.0f | - %.0f | conv3 + pack + stores %.0f | landing + B3 %.0f | - %.0f | - %.0f | sum %.0f\n",
-                CIN, (int)DS, (int)T1LO, (int)XLO, (int)OLO, n / (grid * 8), sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n, sum[5] / n, sum[6] / n, sum[7] / n, sum[8] / n,
-                (sum[0] + sum[1] + sum[2] + sum[3] + sum[4] + sum[5] + sum[6] + sum[7] + sum[8]) / n);
-    }
-#endif
     return AVL_OK;
 }
 
@@ -505,7 +448,6 @@ int launch_bottleneck(const avl_seg_op& op, hipStream_t s) {
     a.H = op.in_h; a.W = op.in_w; a.in_ld = op.in_ld; a.out_ld = op.out_ld;
     a.tiles_x = (op.in_w + BT_W - 1) / BT_W;
     a.ntiles = a.tiles_x * ((op.in_h + BT_H - 1) / BT_H);
-    a.dbg = nullptr;
     a.out_bytes = (int)((long long)op.out_rows * op.out_ld * 2);
     const int variant = (op.in_c == 64 ? 4 + 2 * (op.w_split ? 1 : 0) : 2 * (a.x_lo ? 1 : 0)) + (a.out_lo ? 1 : 0);
     switch (variant) {

@@ -18,14 +18,6 @@
 namespace avl {
 namespace {
 
-// DW_EXP (tools/ab_dwpw.sh; 0 in every shipped build): phase ablations of k_dwpw_x / k_dwpw_xs for timing only (results are wrong) --
-// bit 0: no MFMAs, bit 1: no depthwise arithmetic (zero tiles), bit 2: no tap loads, bit 3: no fragment reads from LDS (with bit 0);
-// k_dwpw_xs only: bit 7: no result stores
-#ifndef DW_EXP
-#define DW_EXP 0
-#endif
-// (bit 8: depthwise parameters are constants instead of LDS reads)
-#define DW_PARAM(T, ptr) ((DW_EXP & 256) ? T{} : *reinterpret_cast<const T*>(ptr))
 constexpr int TM = 128;              // pixels per workgroup
 constexpr int TN = 256;              // output channels per workgroup
 constexpr int A_STAGE = TM * 128;    // 16 KB: 128 rows x 64 k x 2 B
@@ -385,31 +377,22 @@ __global__ void __launch_bounds__(512) k_dwpw_x(DwPwArgs p) {
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.X), 0, (int)p.x_bytes, 0x00020000);
     auto load_taps = [&](int s, int q) {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) raw[q][t] = (DW_EXP & 4) ? v4i{0, 0, 0, 0} : __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)voff[q][t], s * 128, 0);
+        for (int t = 0; t < 9; ++t) raw[q][t] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)voff[q][t], s * 128, 0);
     };
 
     // depthwise 3x3 of K-step s for pixel q of this lane: fp32 sums of f16 x (f16 hi + f16 lo) products -> hi tile slot s & 1, lo tile
     auto produce_a = [&](int s, int q) {
-        if constexpr ((DW_EXP & 2) != 0) {
-#pragma unroll
-            for (int t = 0; t < 9; ++t) asm volatile("" :: "v"(raw[q][t]));
-            const int row = r0 + q * 64;
-            const int sw = row * 128 + ((chunk ^ (row & 7)) << 4);
-            *reinterpret_cast<v4i*>(lds + X_LDS_AH + (s & 1) * A_STAGE + sw) = v4i{0, 0, 0, 0};
-            *reinterpret_cast<v4i*>(lds + X_LDS_AL + sw) = v4i{0, 0, 0, 0};
-            return;
-        }
         float o[8];
         const float* pf = reinterpret_cast<const float*>(lds + X_LDS_P + (s & (XP_RING - 1)) * PSTEP + chunk * (10 * 8 * 4));
         {
-            const float4 b0 = DW_PARAM(float4, pf + 9 * 8), b1 = DW_PARAM(float4, pf + 9 * 8 + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(pf + 9 * 8), b1 = *reinterpret_cast<const float4*>(pf + 9 * 8 + 4);
             o[0] = b0.x; o[1] = b0.y; o[2] = b0.z; o[3] = b0.w;
             o[4] = b1.x; o[5] = b1.y; o[6] = b1.z; o[7] = b1.w;
         }
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const float4 w0 = DW_PARAM(float4, pf + t * 8), w1 = DW_PARAM(float4, pf + t * 8 + 4);
+            const float4 w0 = *reinterpret_cast<const float4*>(pf + t * 8), w1 = *reinterpret_cast<const float4*>(pf + t * 8 + 4);
             const float wt[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -462,11 +445,11 @@ __global__ void __launch_bounds__(512) k_dwpw_x(DwPwArgs p) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], al[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(al[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], al[mi], acc[mi][nj]);
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(ah[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]);
         }
         store_w(2 * s + 1);
         store_p(s + 3);
@@ -485,7 +468,7 @@ __global__ void __launch_bounds__(512) k_dwpw_x(DwPwArgs p) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(ah[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]);
             if (more) {
                 produce_a(s + 1, kk);
                 if (more2) load_taps(s + 2, kk);
@@ -646,33 +629,24 @@ __global__ void __launch_bounds__(512) k_dwpw_xs(DwPwArgs p) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int off = (vmask[q] >> t) & 1u ? vbase[q] + (t / 3) * tstep_y + (t % 3) * tstep_x : 0x7fffff00;   // >= x_bytes: reads as 0
-            rh[t] = (DW_EXP & 4) ? v4i{off, 0, 0, 0} : __builtin_amdgcn_raw_buffer_load_b128(xrsrc, off, s * 128, 0);
-            rl[t] = (DW_EXP & 4) ? v4i{off, 0, 0, 0} : __builtin_amdgcn_raw_buffer_load_b128(xlrsrc, off, s * 128, 0);
+            rh[t] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, off, s * 128, 0);
+            rl[t] = __builtin_amdgcn_raw_buffer_load_b128(xlrsrc, off, s * 128, 0);
         }
     };
 
     // depthwise 3x3 of K-step s for pixel q of this lane -> hi / lo tile slot s & 1
     auto produce_a = [&](int s, int q) {
-        if constexpr ((DW_EXP & 2) != 0) {
-#pragma unroll
-            for (int t = 0; t < 9; ++t) asm volatile("" :: "v"(rh[t]), "v"(rl[t]));
-            const int row = r0 + q * 64;
-            const int sw = (s & 1) * A_STAGE + row * 128 + ((chunk ^ (row & 7)) << 4);
-            *reinterpret_cast<v4i*>(lds + S_LDS_AH + sw) = v4i{0, 0, 0, 0};
-            *reinterpret_cast<v4i*>(lds + S_LDS_AL + sw) = v4i{0, 0, 0, 0};
-            return;
-        }
         float o[8];
         const float* pf = reinterpret_cast<const float*>(lds + S_LDS_P + (s & (XP_RING - 1)) * PSTEP + chunk * (10 * 8 * 4));
         {
-            const float4 b0 = DW_PARAM(float4, pf + 9 * 8), b1 = DW_PARAM(float4, pf + 9 * 8 + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(pf + 9 * 8), b1 = *reinterpret_cast<const float4*>(pf + 9 * 8 + 4);
             o[0] = b0.x; o[1] = b0.y; o[2] = b0.z; o[3] = b0.w;
             o[4] = b1.x; o[5] = b1.y; o[6] = b1.z; o[7] = b1.w;
         }
         float wt[9][8];
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const float4 w0 = DW_PARAM(float4, pf + t * 8), w1 = DW_PARAM(float4, pf + t * 8 + 4);
+            const float4 w0 = *reinterpret_cast<const float4*>(pf + t * 8), w1 = *reinterpret_cast<const float4*>(pf + t * 8 + 4);
             wt[t][0] = w0.x; wt[t][1] = w0.y; wt[t][2] = w0.z; wt[t][3] = w0.w;
             wt[t][4] = w1.x; wt[t][5] = w1.y; wt[t][6] = w1.z; wt[t][7] = w1.w;
         }
@@ -741,11 +715,11 @@ __global__ void __launch_bounds__(512) k_dwpw_xs(DwPwArgs p) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], al[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(al[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], al[mi], acc[mi][nj]);
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(ah[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]);
         };
         auto mfma_lo = [&](int kk) {            // weight slice lo (ring slot 1) x hi tile
             v8 wa[4], ah[4];
@@ -756,7 +730,7 @@ __global__ void __launch_bounds__(512) k_dwpw_xs(DwPwArgs p) {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) { if constexpr (!(DW_EXP & 1)) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]); else if constexpr (!(DW_EXP & 8)) asm volatile("" :: "v"(wa[nj]), "v"(ah[mi])); }
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<HT>::mfma(wa[nj], ah[mi], acc[mi][nj]);
         };
         // ---- j = 0: 64 MFMAs; pixel 0 of the depthwise slice s + 1, then the request for pixel 1's taps
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // own tile writes are in LDS
@@ -887,7 +861,7 @@ __global__ void __launch_bounds__(512) k_dwpw_xs(DwPwArgs p) {
                 const int y = tty * 8 + wm * 4 + mi, x = ttx * 16 + efr;
                 m = ((y < OHt) & (x < p.OW)) ? y * p.OW + x : p.M;
             }
-            if (m < ((DW_EXP & 128) ? (acc[mi][0][0] == 12345.f ? 1 : 0) : p.M)) {
+            if (m < p.M) {
                 float lo[8], hi[8];
 #pragma unroll
                 for (int nj = 0; nj < 2; ++nj)

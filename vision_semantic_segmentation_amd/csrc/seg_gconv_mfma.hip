@@ -50,8 +50,7 @@ struct GconvArgs {
     const char* xq[2];   // FP4 planes of the input [rows][C/2]: hi part, lo part (NULL: no lo correction)
     const char* xs[2];   // scales [C/256][rows][8]
     long long x_srows;
-    int dephase;               // 1: waves 4-7 stage the next tile in the middle of their MFMA phase (A/B switch AVL_GC_DEPHASE)
-    unsigned long long* dbg;   // AVL_GC_PROBE=1: per-wave cycle sums of the tile loop's phases (host-visible memory), else NULL
+    int dephase;         // 1: waves 4-7 stage the next tile in the middle of their MFMA phase
 };
 
 // WS = 1 ("mixed" precision): the weights come as f16 pairs hi + lo ([window][nj 2][tap 18 = 9 hi, 9 lo][16][32]); both
@@ -273,22 +272,13 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
     // Per tile: [DMA of the next tile -> other buffer] [MFMA phase: this wave's sub-tiles, results stay in registers]
     // [s_waitcnt vmcnt(0): the next tile has landed -- the only older stores are those of the PREVIOUS tile, long retired, so
     // the wait never sits on fresh stores] [epilogue phase: bias, ReLU, hi/lo split, FP4 copies, stores] [barrier].
-    unsigned long long tsum[6] = {0, 0, 0, 0, 0, 0};     // probe: [0] stage [1] MFMA phase [2] landing wait + zeroing [3] epilogue [4] barrier [5] tiles
-    auto stamp = [&]() __attribute__((always_inline)) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        return t;
-    };
     for (; sp < sp_end; sp += sp_step, buf ^= 1) {
-        unsigned long long t0 = 0, t1 = 0;
-        if (kStamps && p.dbg) t0 = stamp();
         // The two waves of a SIMD (w and w + 4) stage the next tile at DIFFERENT points: waves 0-3 in front of their MFMA phase,
         // waves 4-7 in the middle of theirs -- the staging is ~40 vector instructions per DMA instruction (pixel -> clamped source
         // address), so one wave of the SIMD computes addresses while the other one's MFMAs run.
         const bool late_stage = NJ >= 2 && wave >= 4 && p.dephase;
         oob = 0u;
         if (!late_stage && sp + sp_step < sp_end) oob = stage(sp + sp_step, buf ^ 1);
-        if (kStamps && p.dbg) { t1 = stamp(); tsum[0] += t1 - t0; t0 = t1; }
         const char* tile = lds + buf * p.tile_bytes;
         f32x4 acc[NJ][2];
 #pragma unroll
@@ -384,10 +374,8 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
             acc[j][0] = acc0; acc[j][1] = acc1;
             __builtin_amdgcn_sched_barrier(0);      // keep the next sub-tile's nine fragments out of this one's registers
         }
-        if (kStamps && p.dbg) { t1 = stamp(); tsum[1] += t1 - t0; t0 = t1; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         zero_oob(oob, buf ^ 1);
-        if (kStamps && p.dbg) { t1 = stamp(); tsum[2] += t1 - t0; t0 = t1; }
 
         int tx, ty, cmb;
         if (p.walk) { ty = sp % p.tiles_y; const int r1 = sp / p.tiles_y; tx = r1 % p.tiles_x; cmb = r1 / p.tiles_x; }
@@ -470,13 +458,7 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (kStamps && p.dbg) { t1 = stamp(); tsum[3] += t1 - t0; t0 = t1; }
         __syncthreads();
-        if (kStamps && p.dbg) { t1 = stamp(); tsum[4] += t1 - t0; tsum[5] += 1; }
-    }
-    if (kStamps && p.dbg && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) p.dbg[((size_t)blockIdx.x * 8 + wave) * 6 + i] = tsum[i];
     }
 }
 
@@ -516,7 +498,6 @@ static int gconv_pick_th(const avl_seg_op& op, int comb, int cus, int* nsp_out, 
     const int ncomb = comb ? op.dil * op.dil : 1, cchunks = op.in_c / CC;
     int best = 0;
     double best_cost = 0.;
-    const int env_th = AVL_EXP_INT("AVL_GCONV_TH", 0);      // experiments build only
     for (int th = 8; th >= 2; th >>= 1) {
         if (2 * gconv_tile_bytes(op.stride, d, th, mx, xs) > 160 * 1024) continue;
         if ((mx || xs) && th == 8) continue;         // the MX variant with four sub-tiles per wave spills; the split-input one has no LDS for it
@@ -526,9 +507,9 @@ static int gconv_pick_th(const avl_seg_op& op, int comb, int cus, int* nsp_out, 
         if (nslots > nsp) nslots = nsp;
         const int rounds = (nsp + nslots - 1) / nslots;
         const double cost = (double)rounds * (th + 0.5);
-        if (th == 2 && best != 0 && env_th != 2) break;
-        if (best == 0 || cost < best_cost || th == env_th) {
-            best = th; best_cost = th == env_th ? -1. : cost;
+        if (th == 2 && best != 0) break;
+        if (best == 0 || cost < best_cost) {
+            best = th; best_cost = cost;
             *nsp_out = nsp; *nslots_out = nslots;
         }
     }
@@ -585,21 +566,9 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gconv_mfma<HT, WS, NJ, XS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
         hipLaunchKernelGGL((k_gconv_mfma<HT, WS, NJ, XS>), dim3(a.nslots * a.cchunks, 1, op_batch(op)), dim3(512), 2 * a.tile_bytes, s, a); \
     } while (0)
-    a.dephase = AVL_EXP_INT("AVL_GC_DEPHASE", 1);
-    a.walk = AVL_EXP_INT("AVL_GC_WALK", 1);
-    a.dbg = nullptr;
-#ifdef AVL_EXPERIMENTS
-    // timing experiment: where do a wave's cycles go (s_memtime stamps; synchronises the stream: never inside a graph capture)
-    static unsigned long long* dbg = nullptr;
-    if (AVL_EXP_INT("AVL_GC_PROBE", 0)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        AVL_HIP_CHECK(hipStreamIsCapturing(s, &cap));
-        AVL_REQUIRE(cap == hipStreamCaptureStatusNone, "AVL_GC_PROBE synchronises the stream: not while it is being captured (MODEL.HIP_GRAPH = False)");
-        if (!dbg) AVL_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dbg), 256 * 8 * 6 * sizeof(unsigned long long), 0));
-        memset(dbg, 0, 256 * 8 * 6 * sizeof(unsigned long long));
-        if (a.nslots * a.cchunks <= 256) a.dbg = dbg;
-    }
-#endif
+    // kernel arguments, not constants: folding them into the kernels changes their code
+    a.dephase = 1;
+    a.walk = 1;
     // (the MX variant never runs four sub-tiles per wave -- gconv_pick_th: it would spill -- so that kernel is not even instantiated)
     if (a.th == 8) {
         if constexpr (WS != 2 && !XS) AVL_GCONV_LAUNCH(4);
@@ -609,17 +578,6 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
     else AVL_GCONV_LAUNCH(1);
 #undef AVL_GCONV_LAUNCH
     AVL_LAUNCH_CHECK();
-#ifdef AVL_EXPERIMENTS
-    if (a.dbg) {
-        AVL_HIP_CHECK(hipStreamSynchronize(s));
-        double sum[6] = {};
-        for (int i = 0; i < a.nslots * a.cchunks * 8; ++i)
-            for (int k = 0; k < 6; ++k) sum[k] += (double)dbg[i * 6 + k];
-        const double n = sum[5] > 0 ? sum[5] : 1;
-        fprintf(stderr, "[gconv probe] C %d dil %d stride %d th %d WS %d tiles/wg %.1f: cycles per tile: stage %.0f | MFMA phase %.0f | landing wait + zeroing %.0f | epilogue %.0f | barrier %.0f\n",
-                a.C, a.dil, a.stride, a.th, WS, n / (a.nslots * a.cchunks * 8), sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n, sum[4] / n);
-    }
-#endif
     return AVL_OK;
 }
 

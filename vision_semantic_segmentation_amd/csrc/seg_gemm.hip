@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm(GemmArgs p) {
 // STAGES = weight tiles in the ring (the producer runs STAGES - 1 sub-steps ahead); AST = activation tiles in the ring:
 // = STAGES for the plain GEMM; 2 is enough for NSUB = 2 at any depth because an activation tile lives for two sub-steps
 // (256 x 256 tile: 2 x 32 KB + 3 x 32 KB = the whole 160 KB of LDS, two sub-steps of DMA in flight instead of one).
-template <typename H, int WM, int WN, int MI, int STAGES, int PROBE = 0, int NSUB = 1, int IO = 0, int AST = STAGES>
+template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES>
 __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtiles) {
     typedef typename Half16<H>::v8 v8;
     constexpr int NW = WM * WN, BM = WM * MI * 16, BN = WN * 64;
@@ -395,12 +395,6 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
             const bool feed = pt < total;                  // sub-step g+STAGES-1 -> the slots consumed in step g-1
             const char* abase = lds + (ca % AST) * A_BYTES;
             const char* wbase = lds + (g % STAGES) * W_BYTES;
-            if (PROBE == 1) { if (feed) issue_part(0, 1, jn); continue; }      // DMA only
-            // PROBE 2: LDS reads + MFMAs, no DMA;  PROBE 3: DMA + LDS reads, no MFMAs (timing experiments, results are garbage)
-            auto mm = [&](const v8& w_, const v8& a_, const f32x4& c_) -> f32x4 {
-                if constexpr (PROBE == 3) { asm volatile("" ::"v"(w_), "v"(a_)); return c_; }
-                else return Half16<H>::mfma(w_, a_, c_);
-            };
             auto rd_w = [&](int kk, int nj) { return *reinterpret_cast<const v8*>(wbase + w_off[nj] + (((kk * 4 + kq) ^ w_key[nj]) << 4)); };
             auto rd_a = [&](int kk, int mi) { return *reinterpret_cast<const v8*>(abase + a_off[mi] + (((kk * 4 + kq) ^ a_key[mi]) << 4)); };
             // The step is cut into 4 MFMA groups; the next stage's DMA instructions and the second K-half's fragment
@@ -411,7 +405,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
             // half in the middle, so that on every SIMD one wave is in an MFMA group while its partner pays the
             // (100+ cycle per instruction) LDS-DMA issue cost, instead of both doing the same thing at the same time.
             const bool early = MI == 8 && NW >= 8 && wave >= NW / 2;      // measured: +4-7 % on 256x256 tiles, -4 % on 256x128
-            if (feed && early && PROBE != 2) { issue_part(0, 2, jn); issue_part(1, 2, jn); }
+            if (feed && early) { issue_part(0, 2, jn); issue_part(1, 2, jn); }
             v8 wa[4], wb[4], af[MI];
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj) wa[nj] = rd_w(0, nj);
@@ -421,25 +415,25 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
 #pragma unroll
             for (int mi = 0; mi < HALF; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = mm(wa[nj], af[mi], acc[mi][nj]);
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<H>::mfma(wa[nj], af[mi], acc[mi][nj]);
             __builtin_amdgcn_sched_barrier(0);
-            if (feed && !early && PROBE != 2) issue_part(0, 2, jn);
+            if (feed && !early) issue_part(0, 2, jn);
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj) wb[nj] = rd_w(1, nj);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mi = HALF; mi < MI; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = mm(wa[nj], af[mi], acc[mi][nj]);
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<H>::mfma(wa[nj], af[mi], acc[mi][nj]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mi = 0; mi < HALF; ++mi) af[mi] = rd_a(1, mi);
-            if (feed && !early && PROBE != 2) issue_part(1, 2, jn);
+            if (feed && !early) issue_part(1, 2, jn);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mi = 0; mi < HALF; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = mm(wb[nj], af[mi], acc[mi][nj]);
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<H>::mfma(wb[nj], af[mi], acc[mi][nj]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int mi = HALF; mi < MI; ++mi) af[mi] = rd_a(1, mi);
@@ -447,7 +441,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
 #pragma unroll
             for (int mi = HALF; mi < MI; ++mi)
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = mm(wb[nj], af[mi], acc[mi][nj]);
+                for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<H>::mfma(wb[nj], af[mi], acc[mi][nj]);
         }
         // ---- epilogue of tile t (the next tile's first stages are already in flight).  All residual loads
         // are issued before the first one is consumed, so their latency is paid once per tile, not per sub-tile.
@@ -534,28 +528,14 @@ int launch_ring(const GemmArgs& a0, int M, hipStream_t s) {
     constexpr int BM = WM * MI * 16, BN = WN * 64, LDS = (AST * BM + STAGES * BN) * 128;
     static_assert(LDS <= 160 * 1024, "ring does not fit LDS");
     // set on every launch: the attribute is per device and this may be called from several threads / for several devices
-    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, 0, NSUB, IO, AST>),
+    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     GemmArgs a = a0;
     a.ntiles = (a.N + BN - 1) / BN;
     const int mtiles = (M + BM - 1) / BM;
     const int total = mtiles * a.ntiles;
     const int grid = total < 256 ? total : 256;
-#ifdef AVL_EXPERIMENTS
-    const int probe = AVL_EXP_INT("AVL_GEMM_PROBE", 0);     // timing experiments only: the results are garbage
-    if (probe >= 1 && probe <= 3 && NSUB == 1 && IO == 0) {
-#define AVL_PROBE_LAUNCH(P)                                                                                                                     \
-    do {                                                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, P>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-        hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, P>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles);                         \
-    } while (0)
-        if (probe == 1) AVL_PROBE_LAUNCH(1);
-        else if (probe == 2) AVL_PROBE_LAUNCH(2);
-        else AVL_PROBE_LAUNCH(3);
-#undef AVL_PROBE_LAUNCH
-    } else
-#endif
-        hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, 0, NSUB, IO, AST>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles);
+    hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
@@ -612,9 +592,7 @@ struct MxArgs {
     const char* Aq2[2];
     const char* As2[2];
     long long a_srows2;
-    int stagger;                // 1: waves 0-3 issue their LDS-DMAs after the first K half of a sub-step (A/B switch)
-    unsigned long long* dbg;    // AVL_MX_PROBE=3 only: per-wave cycle sums (host-visible memory), else NULL
-    int same_tile;              // AVL_MX_PROBE=3 + AVL_MX_SAMETILE=1 (experiments): all workgroups load tile (0, 0): what would an all-hits K loop take?
+    int stagger;                // 1: waves 0-3 issue their LDS-DMAs after the first K half of a sub-step
 };
 
 // 16 values of one lane + the 16 of its partner (lane ^ 16) form one MX block: shared E8M0 scale, e2m1 elements.
@@ -974,7 +952,7 @@ __global__ void __launch_bounds__(512) k_gemm_ring_mx(MxArgs q, int mtiles) {
 //   * one sub-step's DMA is therefore two bursts of 4 instructions per wave (weights; activations + the scale blocks of an FP4
 //     sub-step), and the bursts of the two waves of a SIMD are COMPLEMENTARY: waves 4-7 send theirs right behind EW / EV, waves 0-3
 //     one event later (right in front of EV / of the next EW), so that one wave of every SIMD issues MFMAs while the other pays
-//     the ~150 cycles per LDS-DMA instruction (s_memtime stamps, AVL_MX_PROBE=3: a 4-instruction burst takes ~600 cycles: the 16
+//     the ~150 cycles per LDS-DMA instruction (s_memtime stamps: a 4-instruction burst takes ~600 cycles: the 16
 //     instructions of the four waves that burst together queue in the CU's one vector-memory path).
 // What bounds it now (stamps): 64 KB per sub-step through that path at ~27 B/clk = ~2400 cycles, against 2048 cycles of MFMA
 // issue per SIMD: the 256 x 256 tile is L2 -> LDS bound on this chip; the stream runs at ~3500 cycles per sub-step (was ~4000).
@@ -985,11 +963,7 @@ __global__ void __launch_bounds__(512) k_gemm_ring_mx(MxArgs q, int mtiles) {
 // are issued behind the last weight read (step 4: one fragment, plus its scale byte in an FP4 sub-step).
 // Sub-step kinds (f16 / FP4) alternate inside the stream; the fragments carried across a boundary are plain 128-bit values.
 // MI = 4 (128 x 256 tiles): one event (both slots) in front of step 5 of 8, vmcnt(0).
-// PROBE (timing experiments, results are garbage): 1 = no DMA after the prologue, 2 = no MFMAs, 3 = s_memtime stamps around the
-// events and the DMA bursts, per-wave sums -> q.dbg (each stamp drains the LDS queue: read the SHARES, not the totals),
-// 4 = no weight-fragment LDS reads after the first two sub-steps (a third of the LDS read bytes), 5 = every other activation
-// fragment not read (another third), 6 = every other DMA instruction not sent (half the staging bytes: throughput- or latency-bound?)
-template <int IO, int MI, int LATE, int PROBE = 0, int SPREAD = 0>
+template <int IO, int MI, int LATE>
 __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     typedef f16 H;
     typedef typename Half16<H>::v8 v8;
@@ -1001,10 +975,7 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     constexpr int S_BYTES = 4096;
     constexpr int A_INSTR = BM / 8 / NW, W_INSTR = BN / 8 / NW;
     constexpr int NS = 2 * MI, D = 3, EV = NS - D;              // steps per sub-step; fragments are read D steps ahead; the (main) event sits in front of step EV
-    constexpr int EW = (MI == 8 && SPREAD != 5) ? 5 : EV;        // ... and the weight-slot event (MI = 4: one event for both slots; SPREAD = 5: experiment, one event for MI = 8 too)
-    constexpr bool SPR = SPREAD == 1 || SPREAD == 2, PIN = SPREAD != 0;     // experiments: DMA schedules 1 / 2; 3 = the release schedule with pinned MFMAs
-    constexpr bool ONE = SPREAD == 5;       // experiment: ONE event per sub-step (step 13, both slots); waves 4-7 send both tiles right behind it, waves 0-3 at step 5
-    constexpr bool MID = SPREAD == 4;       // experiment: waves 0-3 send their bursts in the MIDDLE between two events (steps 1 / 9) instead of in front of the next one
+    constexpr int EW = MI == 8 ? 5 : EV;                         // ... and the weight-slot event (MI = 4: one event for both slots)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const GemmArgs& p = q.g;
 
@@ -1062,9 +1033,8 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
         pmbl = 0;
     };
     auto set_tile = [&]() __attribute__((always_inline)) {                  // rare: once per tile
-        int nt_ = pt % ntiles;
+        const int nt_ = pt % ntiles;
         p_mt = pt / ntiles;
-        if (PROBE == 3 && q.same_tile) { nt_ = 0; p_mt = 0; }   // probe (results garbage): every workgroup streams THE SAME tiles = all L2 hits
         cur_w16 = static_cast<const char*>(p.W) + (long long)nt_ * BN * p.K * 2;
         cur_wq = q.Wq[0] + (long long)nt_ * BN * (p.K / 2);
         cur_ws = q.Ws[0] + (long long)nt_ * BN * 8;
@@ -1073,8 +1043,7 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     };
     // One sub-step's DMA is issued in two bursts (see the events below): the weight tile, then the activation tile (+ the scale
     // blocks of an FP4 sub-step, so that a weight burst is W_INSTR instructions for EVERY wave: the hand count at the event).
-    // piece i of a burst = its i-th DMA instruction (1 KB per wave); `i < 0`: the whole burst
-    auto issue_w = [&](int only = -1) __attribute__((always_inline)) {
+    auto issue_w = [&]() __attribute__((always_inline)) {
         const unsigned wbase = lds_base + W_REGION + (issued & 1) * W_BYTES + wave * 1024;
         // weight row of instruction i: r = (i * 8 + wave) * 8 + srow; its swizzle key ((r >> 1) & 1) | (((r >> 4) & 3) << 1) =
         // ((srow >> 1) & 1) | (((wave >> 1) & 3) << 1) does not depend on i
@@ -1085,17 +1054,17 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
             const unsigned wl = wr0 * (unsigned)(p.K * 2) + cw;
 #pragma unroll
             for (int i = 0; i < W_INSTR; ++i)
-                if ((only < 0 || only == i) && !(PROBE == 6 && (i & 1))) glds16_saddr(sw + (long long)i * (NW * 8) * p.K * 2, wl, wbase + i * NW * 1024);
+                glds16_saddr(sw + (long long)i * (NW * 8) * p.K * 2, wl, wbase + i * NW * 1024);
         } else {
             const char* sw = cur_wq + (pj == 4 ? 0 : cur_wps) + (long long)pmb * 128;
             const unsigned wl = wr0 * (unsigned)(p.K / 2) + cw;
 #pragma unroll
             for (int i = 0; i < W_INSTR; ++i)
-                if ((only < 0 || only == i) && !(PROBE == 6 && (i & 1))) glds16_saddr(sw + (long long)i * (NW * 8) * (p.K / 2), wl, wbase + i * NW * 1024);
+                glds16_saddr(sw + (long long)i * (NW * 8) * (p.K / 2), wl, wbase + i * NW * 1024);
         }
     };
     // (the last piece also brings the scale blocks of an FP4 sub-step and moves the producer on to the next sub-step)
-    auto issue_a = [&](int only = -1) __attribute__((always_inline)) {
+    auto issue_a = [&]() __attribute__((always_inline)) {
         const unsigned abase = lds_base + (issued & 1) * A_BYTES + wave * 1024;
         const unsigned l = lane_now(), srow = l >> 3, ct = ((l & 7u) ^ srow) << 4;        // activation rows: key = r & 7 = srow
         if (pj < 4) {
@@ -1103,22 +1072,21 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
             const unsigned al = srow * (unsigned)cur_rowb16 + ct;
 #pragma unroll
             for (int i = 0; i < A_INSTR; ++i)
-                if ((only < 0 || only == i) && !(PROBE == 6 && (i & 1))) glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowb16, al, abase + i * NW * 1024);
+                glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowb16, al, abase + i * NW * 1024);
         } else {
             const long long ta = pj == 4 ? 0 : cur_aps, tw = pj == 4 ? 0 : cur_wps;     // which correction pass
             const char* sa = cur_aq + ta + (long long)pmbl * 128;
             const unsigned a_lq = srow * (unsigned)cur_rowbq + ct;
 #pragma unroll
             for (int i = 0; i < A_INSTR; ++i)
-                if ((only < 0 || only == i) && !(PROBE == 6 && (i & 1))) glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowbq, a_lq, abase + i * NW * 1024);
+                glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowbq, a_lq, abase + i * NW * 1024);
             // scales: BM x 8 bytes for the activation rows (waves 0, 1: one KB each), 2 KB for the weight rows (waves 2, 3)
-            if ((only < 0 || only == A_INSTR - 1) && wave < 4 && (wave >= 2 || wave * 128 < BM)) {
+            if (wave < 4 && (wave >= 2 || wave * 128 < BM)) {
                 const char* ss = wave < 2 ? cur_as + ta + (long long)pmbl * cur_asrows * 8 + wave * 1024
                                           : cur_ws + tw + (long long)pmb * q.w_srows * 8 + (wave - 2) * 1024;
                 glds16_saddr(ss, l * 16u, lds_base + S_REGION + (issued & 1) * S_BYTES + wave * 1024);
             }
         }
-        if (only >= 0 && only != A_INSTR - 1) return;
         ++issued;
         if (++pj == nsub) {
             pj = 0;
@@ -1173,12 +1141,6 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     auto rdWs = [&](const char* slot) { return *reinterpret_cast<const uint2*>(slot + sw_v); };
 
     int g = 0;                                                   // sub-steps consumed so far (ring position)
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;      // PROBE 3: cycles in [0] sub-steps [1] EW wait [2] W burst [3] EV wait [4] A burst
-    auto stamp = [&]() __attribute__((always_inline)) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        return t;
-    };
     bool w_sent = false;                                         // this wave has issued the weight burst of the current sub-step
     // KIND: 0 = f16 sub-step (K = 64), 1 = FP4 sub-step (K = 256, block scales); next_q: the sub-step that follows is an FP4 one
     // (run-time, uniform: it only decides whether scales are read ahead with the fragments -- TWO loop bodies in all, as in
@@ -1201,128 +1163,58 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
             Af[t] = rdA(abn, t / MI, t % MI);
             As[t] = rdAs(sbn, t / MI, t % MI);                   // (unconditional: see Wsn below)
         };
-        if (PROBE == 3 && S == 0) { const unsigned long long t = stamp(); if (tlast) tsum[0] += t - tlast; tlast = t; tsum[5] += 1; }
         if (EW != EV && S == EW) {
             // complementary bursts: waves 0-3 send the ACTIVATION tile of the sub-step after next here, one event after waves 4-7
             // did (its slot was released at the previous main event; not in the very first sub-step: that tile is already in flight)
-            if (!SPR && !MID && LATE == 0 && !early && g > 0 && PROBE != 1 && pt < total) {
-                unsigned long long t1 = 0;
-                if (PROBE == 3) t1 = stamp();
-                issue_a();
-                if (PROBE == 3) tsum[4] += stamp() - t1;
-            }
-            unsigned long long t0 = 0;
-            if (PROBE == 3) t0 = stamp();
+            if (LATE == 0 && !early && g > 0 && pt < total) issue_a();
             // weight-slot event: the last weight fragment of this slot was read at step 3, in front of at least one younger LDS
             // read (step 4: one fragment, and its scale byte in an FP4 sub-step), so lgkmcnt(1 / 2) retires every weight read
             if (KIND == 0) asm volatile("s_waitcnt lgkmcnt(1)\n\ts_barrier" ::: "memory");
             else asm volatile("s_waitcnt lgkmcnt(2)\n\ts_barrier" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            unsigned long long t1 = 0;
-            if (PROBE == 3) { t1 = stamp(); tsum[1] += t1 - t0; }
-            if (!SPR && PROBE != 1 && early && pt < total) { issue_w(); w_sent = true; }
-            if (PROBE == 3) tsum[2] += stamp() - t1;
+            if (early && pt < total) { issue_w(); w_sent = true; }
         }
-        if (!SPR && EW != EV && LATE != 0 && !early && S == EW + LATE && PROBE != 1 && pt < total) {
-            unsigned long long t1 = 0;
-            if (PROBE == 3) t1 = stamp();
+        if (EW != EV && LATE != 0 && !early && S == EW + LATE && pt < total) {
             issue_w();
             w_sent = true;
-            if (PROBE == 3) tsum[2] += stamp() - t1;
         }
         if (S == EV) {
             // every read of this slot was issued >= 2 steps ago.  DMA: the only operations this wave may still have in flight
             // are the W_INSTR of the weight burst it issued a few steps ago (for the sub-step after next); everything older
             // -- both tiles of the next sub-step, epilogue stores -- is waited for
-            if (!SPR && !MID && EW != EV && LATE == 0 && !early && PROBE != 1 && pt < total) {
-                unsigned long long t1 = 0;
-                if (PROBE == 3) t1 = stamp();
+            if (EW != EV && LATE == 0 && !early && pt < total) {
                 issue_w();
                 w_sent = true;
-                if (PROBE == 3) tsum[2] += stamp() - t1;
             }
             // (no weight burst once the work has run out: then nothing may stay in flight)
-            unsigned long long t0 = 0;
-            if (PROBE == 3) t0 = stamp();
-            if (EW != EV && w_sent) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(PROBE == 6 ? W_INSTR / 2 : W_INSTR) : "memory");
+            if (EW != EV && w_sent) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(W_INSTR) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             w_sent = false;
             __builtin_amdgcn_sched_barrier(0);
-            unsigned long long t1 = 0;
-            if (PROBE == 3) { t1 = stamp(); tsum[3] += t1 - t0; }
-            if (!SPR && PROBE != 1 && early && pt < total) { if (EW == EV) issue_w(); issue_a(); }
-            if (PROBE == 3) tsum[4] += stamp() - t1;
-            if (PROBE != 4 || g < 2) {
+            if (early && pt < total) { if (EW == EV) issue_w(); issue_a(); }
 #pragma unroll
-                for (int nj = 0; nj < 4; ++nj) Wf[0][nj] = rdW(wbn, 0, nj);
-            }
+            for (int nj = 0; nj < 4; ++nj) Wf[0][nj] = rdW(wbn, 0, nj);
             // Scales are read ahead whether or not the next sub-step is an FP4 one (then they are whatever the slot holds and nothing
             // uses them): a read under the run-time flag would keep Wsn / Wsc / As[0 .. 2] LIVE through every f16 sub-step (seven
             // registers hipcc spilled to scratch and reloaded inside the hand-counted stream); four LDS reads per sub-step are free.
             Wsn = rdWs(sbn);
             readAn(0);
         }
-        if (!SPR && !ONE && PROBE != 1 && !early && (EW == EV || LATE != 0) && S == EV + LATE && pt < total) {
-            unsigned long long t1 = 0;
-            if (PROBE == 3) t1 = stamp();
+        if (!early && (EW == EV || LATE != 0) && S == EV + LATE && pt < total) {
             if (EW == EV) issue_w();
             issue_a();
-            if (PROBE == 3) tsum[4] += stamp() - t1;
-        }
-        if constexpr (ONE) {
-            if constexpr (S == 5) { if (!early && g > 0 && pt < total) { issue_w(); issue_a(); } }
-        }
-        if constexpr (MID) {
-            // whole bursts, four steps behind those of waves 4-7 (which send right behind the events at steps 5 / 13): the weight tile of
-            // sub-step g + 2 at step 9 (its slot was released at EW, step 5), the activation tile of sub-step g + 1 at step 1 (slot
-            // released at the previous EV).  Same order per wave (weights, activations), so the counts at the events stand.
-            static_assert(MI == 8 && EV == 13, "MID: 16-step sub-steps only");
-            if constexpr (S == 9) { if (!early && pt < total) { issue_w(); w_sent = true; } }
-            if constexpr (S == 1) { if (!early && g > 0 && pt < total) issue_a(); }
-        }
-        if constexpr (SPR) {
-            // SPREAD: no bursts.  Every step, one wave of each SIMD sends ONE DMA instruction: waves 4-7 on the odd steps, waves 0-3
-            // on the even ones -- the weight tile of sub-step g + 2 in steps 5 .. 12 (behind EW, which releases its slot), its
-            // activation tile in steps 13 .. 15 (behind EV) and 0 .. 4 of the next sub-step.  Four 1 KB instructions per step and CU
-            // instead of sixteen at an event: the CU's vector-memory path takes one every ~37 cycles, so a burst made each of its
-            // waves wait ~600 cycles at the issue (stamps) while this keeps the queue short.  The counts at the events stand: at EV the
-            // four youngest operations of a wave are exactly its weight pieces of steps 5 .. 12, everything older (the activation
-            // pieces of the tile that is certified there included, the last of them issued at step 3 / 4) is waited for.
-            static_assert(MI == 8 && EW == 5 && EV == 13, "SPREAD: 16-step sub-steps only");
-            if constexpr (SPREAD == 1) {
-                if constexpr (S >= 5 && S <= 12) {
-                    if (early == ((S & 1) == 1) && pt < total) { issue_w((S - 5) / 2); w_sent = true; }
-                }
-                constexpr int pa_e = S == 13 ? 0 : S == 15 ? 1 : S == 1 ? 2 : S == 3 ? 3 : -1;
-                constexpr int pa_l = S == 14 ? 0 : S == 0 ? 1 : S == 2 ? 2 : S == 4 ? 3 : -1;
-                // (g == 0: the prologue has sent sub-steps 0 and 1 whole)
-                if constexpr (pa_e >= 0) { if (early && pt < total && (S >= 13 || g > 0)) issue_a(pa_e); }
-                if constexpr (pa_l >= 0) { if (!early && pt < total && (S >= 13 || g > 0)) issue_a(pa_l); }
-            } else {
-                // SPREAD = 2: half bursts (two instructions) at four points of the sub-step; waves 4-7 at steps 5 / 9 (weights) and
-                // 13 / 1 (activations), waves 0-3 two steps later
-                constexpr int pw_e = S == 5 ? 0 : S == 9 ? 2 : -1, pw_l = S == 7 ? 0 : S == 11 ? 2 : -1;
-                constexpr int pa_e = S == 13 ? 0 : S == 1 ? 2 : -1, pa_l = S == 15 ? 0 : S == 3 ? 2 : -1;
-                if constexpr (pw_e >= 0) { if (early && pt < total) { issue_w(pw_e); issue_w(pw_e + 1); w_sent = true; } }
-                if constexpr (pw_l >= 0) { if (!early && pt < total) { issue_w(pw_l); issue_w(pw_l + 1); w_sent = true; } }
-                if constexpr (pa_e >= 0) { if (early && pt < total && (S >= 13 || g > 0)) { issue_a(pa_e); issue_a(pa_e + 1); } }
-                if constexpr (pa_l >= 0) { if (!early && pt < total && (S >= 13 || g > 0)) { issue_a(pa_l); issue_a(pa_l + 1); } }
-            }
         }
         // activation fragments: D steps ahead, one per step -- the last one of the slot at step EV - 1, the first of the next slot
         // right behind the event
-        if (S + D < NS && (PROBE != 5 || g < 2 || ((S + D) & 1) == 0)) readA(S + D);
+        if (S + D < NS) readA(S + D);
         if (S >= EV && S + 1 < NS) readAn(S - EV + 1);
         // weight fragments of the second K half
-        if constexpr (MI == 8 && S < 4) if (PROBE != 4 || g < 2) Wf[1][S] = rdW(wb, 1, S);
+        if constexpr (MI == 8 && S < 4) Wf[1][S] = rdW(wb, 1, S);
         if constexpr (MI == 4 && S < 2) { Wf[1][2 * S] = rdW(wb, 1, 2 * S); Wf[1][2 * S + 1] = rdW(wb, 1, 2 * S + 1); }
         if (KIND == 0) {
             const v8 af = __builtin_bit_cast(v8, Af[S]);
 #pragma unroll
-            for (int nj = 0; nj < 4; ++nj) {
-                if (PROBE == 2) asm volatile("" ::"v"(Wf[kk][nj].x), "v"(Wf[kk][nj].w), "v"(Af[S].x), "v"(Af[S].w));
-                else acc[mi][nj] = Half16<H>::mfma(__builtin_bit_cast(v8, Wf[kk][nj]), af, acc[mi][nj]);
-            }
+            for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = Half16<H>::mfma(__builtin_bit_cast(v8, Wf[kk][nj]), af, acc[mi][nj]);
         } else {
             const v8i xa = {Af[S].x, Af[S].y, Af[S].z, Af[S].w, 0, 0, 0, 0};
             const int as = (int)As[S];
@@ -1330,18 +1222,10 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     do {                                                                                                                           \
         const v8i wa = {Wf[kk][NJ].x, Wf[kk][NJ].y, Wf[kk][NJ].z, Wf[kk][NJ].w, 0, 0, 0, 0};                                       \
         const int ws = (int)((NJ) < 2 ? Wsc.x : Wsc.y);                                                                            \
-        if (PROBE == 2) asm volatile("" ::"v"(Wf[kk][NJ].x), "v"(Wf[kk][NJ].w), "v"(Af[S].x), "v"(Af[S].w), "v"(ws), "v"(as));     \
-        else acc[mi][NJ] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa, xa, acc[mi][NJ], 4, 4, ((NJ) & 1) * 2 + kk, ws, 0, as); \
+        acc[mi][NJ] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa, xa, acc[mi][NJ], 4, 4, ((NJ) & 1) * 2 + kk, ws, 0, as);      \
     } while (0)
             AVL_QMFMA(0); AVL_QMFMA(1); AVL_QMFMA(2); AVL_QMFMA(3);
 #undef AVL_QMFMA
-        }
-        if constexpr (PIN) {
-            // with a (uniform) branch in every step hipcc sinks the MFMAs of all sixteen steps below the last branch of the
-            // sub-step (one block of 64 MFMAs, every fragment live: 45 spilled registers): an empty volatile asm that "touches" the
-            // step's accumulators keeps them in their step
-#pragma unroll
-            for (int nj = 0; nj < 4; ++nj) asm volatile("" : "+v"(acc[mi][nj]));
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -1375,101 +1259,29 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
             for (int j = 0; j < 4; ++j) substep(F16(), j == 3);
             for (int u = 0; u < nmx; ++u) substep(FP4(), u + 1 < nmx);
         }
-        unsigned long long te0 = 0;
-        if (PROBE == 3) te0 = stamp();
         mx_epilogue<IO, MI>(q, acc, nt, mt, wm, wn, fr, kq);
         if (t + nwg < total) init_acc(t + nwg);
-        if (PROBE == 3) { tsum[6] += stamp() - te0; tsum[7] += 1; tlast = 0; }      // (the epilogue is not part of the sub-step sums: [6] / [7] = cycles per epilogue)
-    }
-    if (PROBE == 3 && q.dbg && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q.dbg[((size_t)blockIdx.x * 8 + wave) * 8 + i] = tsum[i];
     }
 }
-
-#ifdef AVL_EXPERIMENTS
-#include "experiments/seg_gemm_mx_pp.inc"      // k_gemm_mx_pp (ping-pong schedule experiment): not part of the release translation unit
-#endif  // AVL_EXPERIMENTS
 
 template <int IO, int MI>
 int launch_ring_mx_t(const MxArgs& a0, hipStream_t s) {
     constexpr int BM = 2 * MI * 16, LDS = 2 * (BM + 256) * 128 + 2 * 4096;
     MxArgs a = a0;
-    a.stagger = AVL_EXP_INT("AVL_MX_STAGGER", 1);
-    a.same_tile = 0;
+    a.stagger = 1;          // a kernel argument, not a constant: folding it into the kernels changes their code (SGPR spills)
     a.g.ntiles = a.g.N / 256;
     const int mtiles = (a.g.M + BM - 1) / BM;
     const int total = mtiles * a.g.ntiles;
-    int grid = total < 256 ? total : 256;
-#ifdef AVL_EXPERIMENTS
-    { const int gl = AVL_EXP_INT("AVL_MX_GRID", 0); if (gl > 0 && gl < grid) grid = gl; }      // fewer workgroups: is a phase chip- or CU-bound?
-#endif
+    const int grid = total < 256 ? total : 256;
     // Which main loop: the software-pipelined stream wins where the K loop is long (K >= 1024: -2...-9 % on layer4 / layer3 conv1
     // and conv3 + downsample), the round-2 kernel (two plain barriers per sub-step, a cheaper tile switch) where a tile is only 1-2 K
     // macro-blocks (K = 256 / 512: layer2, layer3 conv3, the decoder's pointwise convs: the stream is +2...+19 % there);
-    // profiles/r03/gemm_mx_pipe_vs_ring_ab.log.  AVL_MX_PIPE = 0 / 1 forces one of them (A/B experiments).
-#ifdef AVL_EXPERIMENTS
-    if (MI == 8) {
-        const int pp = AVL_EXP_INT("AVL_MX_PP", 0);        // 1: ping-pong kernel for every 256-row-tile MX GEMM, 2: only where K >= 1024
-        if (pp == 1 || (pp == 2 && a.g.K >= 1024)) {
-            AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pp<IO>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            hipLaunchKernelGGL((k_gemm_mx_pp<IO>), dim3(grid), dim3(512), LDS, s, a, mtiles);
-            AVL_LAUNCH_CHECK();
-            return AVL_OK;
-        }
-    }
-#endif
-    const int pipe_env = AVL_EXP_INT("AVL_MX_PIPE", -1);
-    const bool pipe = pipe_env >= 0 ? pipe_env != 0 : a.g.K >= 1024;
-    if (pipe) {
+    // profiles/r03/gemm_mx_pipe_vs_ring_ab.log.
+    if (a.g.K >= 1024) {
         // LATE: how many steps behind the event(s) waves 0-3 issue their bursts (waves 4-7: right behind them)
-        constexpr int L0 = MI == 8 ? 0 : 1;
-#define AVL_PIPE_LAUNCH(...)                                                                                                                   \
-    do {                                                                                                                                       \
-        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pipe<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-        hipLaunchKernelGGL((k_gemm_mx_pipe<__VA_ARGS__>), dim3(grid), dim3(512), LDS, s, a, mtiles);                                           \
-    } while (0)
-#ifdef AVL_EXPERIMENTS
-        constexpr int L1 = 2;
-        const int late_env = AVL_EXP_INT("AVL_MX_LATE", -1);
-        const int probe = AVL_EXP_INT("AVL_MX_PROBE", 0);       // timing experiments only (256-row tiles): 1, 2, 4, 5 give garbage results
-        if (MI == 8 && probe == 1) AVL_PIPE_LAUNCH(IO, 8, 0, 1);
-        else if (MI == 8 && probe == 2) AVL_PIPE_LAUNCH(IO, 8, 0, 2);
-        else if (MI == 8 && probe == 4) AVL_PIPE_LAUNCH(IO, 8, 0, 4);
-        else if (MI == 8 && probe == 5) AVL_PIPE_LAUNCH(IO, 8, 0, 5);
-        else if (MI == 8 && probe == 6) AVL_PIPE_LAUNCH(IO, 8, 0, 6);
-        else if (MI == 8 && probe == 3) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            AVL_HIP_CHECK(hipStreamIsCapturing(s, &cap));
-            AVL_REQUIRE(cap == hipStreamCaptureStatusNone, "AVL_MX_PROBE=3 synchronises the stream: not while it is being captured (MODEL.HIP_GRAPH = False)");
-            static unsigned long long* dbg = nullptr;
-            if (!dbg) AVL_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dbg), 256 * 8 * 8 * sizeof(unsigned long long), 0));
-            memset(dbg, 0, 256 * 8 * 8 * sizeof(unsigned long long));
-            a.dbg = dbg;
-            a.same_tile = AVL_EXP_INT("AVL_MX_SAMETILE", 0);
-            AVL_PIPE_LAUNCH(IO, 8, 0, 3);
-            AVL_HIP_CHECK(hipStreamSynchronize(s));
-            double sum[2][8] = {};
-            for (int b = 0; b < grid; ++b)
-                for (int w = 0; w < 8; ++w)
-                    for (int i = 0; i < 8; ++i) sum[w >= 4][i] += (double)dbg[(b * 8 + w) * 8 + i];
-            for (int e = 0; e < 2; ++e) {
-                const double n = sum[e][5] > 0 ? sum[e][5] : 1;
-                fprintf(stderr, "[mx probe] M %d N %d K %d nmx %d %s waves: cycles per sub-step %.0f | EW wait+barrier %.0f | W burst %.0f | EV wait+barrier %.0f | A burst %.0f | epilogue %.0f (x %.1f per wave)\n",
-                        a.g.M, a.g.N, a.g.K, a.nmx, e ? "early (4-7)" : "late (0-3)", sum[e][0] / n, sum[e][1] / n, sum[e][2] / n, sum[e][3] / n, sum[e][4] / n,
-                        sum[e][7] > 0 ? sum[e][6] / sum[e][7] : 0., sum[e][7] / (4.0 * grid));
-            }
-        }
-        else if (late_env == L1) AVL_PIPE_LAUNCH(IO, MI, L1);
-        else if (MI == 8 && AVL_EXP_INT("AVL_MX_SPREAD", 0) == 1) AVL_PIPE_LAUNCH(IO, 8, 0, 0, 1);
-        else if (MI == 8 && AVL_EXP_INT("AVL_MX_SPREAD", 0) == 2) AVL_PIPE_LAUNCH(IO, 8, 0, 0, 2);
-        else if (MI == 8 && AVL_EXP_INT("AVL_MX_SPREAD", 0) == 3) AVL_PIPE_LAUNCH(IO, 8, 0, 0, 3);
-        else if (MI == 8 && AVL_EXP_INT("AVL_MX_SPREAD", 0) == 4) AVL_PIPE_LAUNCH(IO, 8, 0, 0, 4);
-        else if (MI == 8 && AVL_EXP_INT("AVL_MX_SPREAD", 0) == 5) AVL_PIPE_LAUNCH(IO, 8, 0, 0, 5);
-        else
-#endif
-            AVL_PIPE_LAUNCH(IO, MI, L0);
-#undef AVL_PIPE_LAUNCH
+        constexpr int LATE = MI == 8 ? 0 : 1;
+        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pipe<IO, MI, LATE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        hipLaunchKernelGGL((k_gemm_mx_pipe<IO, MI, LATE>), dim3(grid), dim3(512), LDS, s, a, mtiles);
     } else {
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring_mx<IO, MI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         hipLaunchKernelGGL((k_gemm_ring_mx<IO, MI>), dim3(grid), dim3(512), LDS, s, a, mtiles);
@@ -1481,9 +1293,8 @@ int launch_ring_mx_t(const MxArgs& a0, hipStream_t s) {
 int launch_ring_mx(const MxArgs& a, int m_image, bool quantize_out, hipStream_t s) {
     // 128-row tiles when 256-row tiles would leave more than a quarter of the 256 CUs idle (or give a ragged second wave); counted on ONE
     // image's rows (m_image), so that a batch runs the kernel its batch-1 plan runs
-    const int force = AVL_EXP_INT("AVL_MX_TILE", 0);       // 128 / 256: experiments
     const long long t256 = (long long)((m_image + 255) / 256) * (a.g.N / 256);
-    const bool small = force ? force == 128 : (t256 < 192 || (t256 > 256 && t256 < 384));
+    const bool small = t256 < 192 || (t256 > 256 && t256 < 384);
     if (small) return quantize_out ? launch_ring_mx_t<1, 4>(a, s) : launch_ring_mx_t<0, 4>(a, s);
     return quantize_out ? launch_ring_mx_t<1, 8>(a, s) : launch_ring_mx_t<0, 8>(a, s);
 }
@@ -1591,10 +1402,6 @@ int validate_gemm(const avl_seg_op& op) {
     return AVL_OK;
 }
 
-#ifdef AVL_EXPERIMENTS
-int launch_gemm_w4(const avl_seg_op& op, hipStream_t s);      // seg_gemm_w4.hip: one-wave-per-SIMD experiment (w_layout = 5)
-#endif
-
 int launch_gemm(const avl_seg_op& op, hipStream_t s) {
     if (op.bias_per_image && op_batch(op) > 1) {
         for (int n = 0; n < op.batch; ++n) {
@@ -1603,12 +1410,7 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
         }
         return AVL_OK;
     }
-#ifdef AVL_EXPERIMENTS
-    AVL_REQUIRE(op.w_layout != 5 || op_batch(op) == 1, "GEMM w_layout 5 (k_gemm_w4) takes one image");
-    if (op.w_layout == 5) return launch_gemm_w4(op, s);
-#else
-    AVL_REQUIRE(op.w_layout != 5, "GEMM w_layout 5 (k_gemm_w4) exists in the experiments build only (make experiments)");
-#endif
+    AVL_REQUIRE(op.w_layout != 5, "GEMM w_layout 5 is not supported");
     GemmArgs a;
     a.A = op.in; a.W = op.weight; a.bias = op.bias; a.R = op.in2; a.C = op.out;
     a.lda = op.in_ld; a.ldr = op.in2_ld; a.ldc = op.out_ld;
@@ -1681,8 +1483,7 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
         int v = op.w_layout;
         if (v == 0) v = (can256 && ((m_image + 255) / 256) * (a.N / 256) >= 192) ? 3 : 2;
         if (a.nsub == 2) {
-            const int deep = AVL_EXP_INT("AVL_GEMM_DEEP", 1);      // A/B: 0 = 2 + 2 tiles, one sub-step ahead
-            if (v == 3 && can256) return deep ? launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s) : launch_ring<f16, 2, 4, 8, 2, 2, 1>(a, a.M, s);
+            if (v == 3 && can256) return launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s);
             return launch_ring<f16, 4, 2, 4, 3, 2, 1>(a, a.M, s);
         }
         if (a.nsub == 3) {

@@ -248,7 +248,7 @@ int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, 
  * rows actually allocated (GEMM tiles read whole 128-row tiles, so M is padded up by the caller and
  * the plan checks it). */
 
-#define AVL_OP_STEM 1        /* uint8 RGB [H][W][3] -> normalise (semantic_segmentation.py:35-39) -> 7x7 s2 p3 conv +bias+ReLU */
+#define AVL_OP_STEM 1        /* uint8 RGB [H][W][3] (or fp32 [3][H][W]: in_format) -> normalise (semantic_segmentation.py:35-39) -> 7x7 s2 p3 conv +bias+ReLU */
 #define AVL_OP_MAXPOOL 2     /* 3x3 s2 p1 (torchvision ResNet.maxpool)                                          */
 #define AVL_OP_GEMM 3        /* 1x1 conv: out[m][n] = act(sum_k in[row(m)][k] w[n][k] + bias[n] (+ in2[m][n])) */
 #define AVL_OP_GCONV 4       /* grouped or dense 3x3 conv, stride 1|2, dilation d, pad d, +bias+ReLU (Bottleneck.conv2; w_layout) */
@@ -293,7 +293,7 @@ int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, 
 typedef struct avl_seg_op {
     int32_t kind;            /* AVL_OP_*                                                        */
     int32_t dtype;           /* activation type of in/in2/out: AVL_BF16, AVL_F16 or AVL_F32      */
-    const void* in;          /* input activation (STEM: uint8 image; GEMV/GAP-out: fp32)       */
+    const void* in;          /* input activation (STEM: uint8 image, or fp32 planes: in_format; GEMV/GAP-out: fp32) */
     const void* in2;         /* GEMM: residual added before the ReLU, or NULL; GAP: fp32 scratch [256][C];
                                 DWCONV: 32 zero bytes (what a tap outside the image reads);
                                 STEM: NULL, or the camera block of a pre-processing stem (avl_stem_camera_set) */
@@ -376,7 +376,16 @@ typedef struct avl_seg_op {
      * bias comes from each image's pooling branch).  Such a GEMM runs as one launch per image, so in_rows must cover the last image's
      * whole row tiles: in_rows >= (batch - 1) * out_h * out_w + round_up(out_h * out_w, 256).  Not with the MX GEMM (w_split 2). */
     int32_t bias_per_image;
+    /* STEM only (AVL_IN_*): the form of `in`.  AVL_IN_U8_HWC (0) = uint8 RGB [batch][in_h][in_w][3], normalised by the stem.
+     * AVL_IN_F32_CHW = fp32 [batch][3][in_h][in_w], already normalised by the caller ((x / 255 - mean) / std): image n starts at
+     * float n * 3 * in_h * in_w, each channel plane is in_h * in_w floats, in_rows = batch * in_h * in_w.  The stem converts each value
+     * as it converts the fp32 value its uint8 table holds, so a float input equal to that value gives the u8 path's bits.  Not with a
+     * pre-processing stem (in2 set); other ops must leave it 0. */
+    int32_t in_format;
 } avl_seg_op;
+
+#define AVL_IN_U8_HWC 0
+#define AVL_IN_F32_CHW 1
 
 #define AVL_MX_IN_LO 1
 #define AVL_MX_RES_LO 2

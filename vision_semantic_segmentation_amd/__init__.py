@@ -2,7 +2,8 @@
 
 Public names mirror the reference: ``SemanticSegmentation`` (src/semantic_segmentation.py),
 ``SemanticMapping`` (src/mapping.py), ``VisionSemanticSegmentationNode``
-(src/vision_semantic_segmentation_node.py), ``get_cfg_defaults`` (src/config/base_cfg.py).
+(src/vision_semantic_segmentation_node.py), ``get_cfg_defaults`` (src/config/base_cfg.py), ``DeepLabV3Plus`` and
+``build_model`` (src/network/deeplab_v3_plus/models).
 Heavy imports are deferred so that ``import vision_semantic_segmentation_amd`` works without a GPU.
 """
 __version__ = "0.1.0"
@@ -12,6 +13,8 @@ _LAZY = {
     "SemanticSegmentation": ("semantic_segmentation", "SemanticSegmentation"),
     "VisionSemanticSegmentationNode": ("vision_semantic_segmentation_node", "VisionSemanticSegmentationNode"),
     "get_cfg_defaults": ("config", "get_cfg_defaults"),
+    "DeepLabV3Plus": ("models", "DeepLabV3Plus"),
+    "build_model": ("models", "build_model"),
     "camera_setup_1": ("camera", "camera_setup_1"),
     "camera_setup_6": ("camera", "camera_setup_6"),
 }

@@ -17,13 +17,14 @@ constexpr int kThreads = 256;
 // ResNet.conv1 (7x7, stride 2, pad 3, 3->64) + folded bn1 + ReLU.  Zero padding applies to the
 // NORMALISED image, so normalisation cannot be folded into the weights at the border.
 // weight: float [7][7][3][64]; one lane = one output pixel x 64 channels.
-template <typename T>
+// F32IN (AVL_IN_F32_CHW): `img` is fp32 [3][H][W] planes the caller has normalised; the tap order and the fmaf chain stay the same.
+template <typename T, bool F32IN = false>
 __global__ void __launch_bounds__(kThreads) k_stem(const unsigned char* __restrict__ img, int H, int W,
                                                   const float* __restrict__ w, const float* __restrict__ bias,
                                                   T* __restrict__ out, int OH, int OW, int out_ld) {
     const int idx = blockIdx.x * kThreads + threadIdx.x;
     if (idx >= OH * OW) return;
-    img = image_base(img, (long long)H * W, 3);
+    img = image_base(img, (long long)H * W, F32IN ? 3 * (int)sizeof(float) : 3);
     out = image_base(out, (long long)OH * OW, out_ld);
     const int oy = idx / OW, ox = idx % OW;
     float acc[64];
@@ -38,7 +39,11 @@ __global__ void __launch_bounds__(kThreads) k_stem(const unsigned char* __restri
             const unsigned char* px = img + 3ll * ((long long)(in ? iy : 0) * W + (in ? ix : 0));
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci) {
-                const float x = in ? ((float)px[ci] / 255.0f - mean[ci]) / stdv[ci] : 0.0f;
+                float x;
+                if constexpr (F32IN)
+                    x = in ? reinterpret_cast<const float*>(img)[(long long)ci * H * W + (long long)iy * W + ix] : 0.0f;
+                else
+                    x = in ? ((float)px[ci] / 255.0f - mean[ci]) / stdv[ci] : 0.0f;
                 const float* wr = w + ((ky * 7 + kx) * 3 + ci) * 64;
 #pragma unroll
                 for (int c = 0; c < 64; ++c) acc[c] = fmaf(x, wr[c], acc[c]);
@@ -662,6 +667,12 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
     const unsigned nimg = (unsigned)op_batch(op);       // grid z = image (image_base)
     switch (op.kind) {
         case AVL_OP_STEM:
+            if (op.in_format == AVL_IN_F32_CHW) {
+                hipLaunchKernelGGL((k_stem<T, true>), dim3(blocks_for((long long)op.out_h * op.out_w), 1, nimg), dim3(kThreads), 0, s,
+                                   static_cast<const unsigned char*>(op.in), op.in_h, op.in_w, w, op.bias, out, op.out_h, op.out_w,
+                                   op.out_ld);
+                break;
+            }
             hipLaunchKernelGGL(k_stem<T>, dim3(blocks_for((long long)op.out_h * op.out_w), 1, nimg), dim3(kThreads), 0, s,
                                static_cast<const unsigned char*>(op.in), op.in_h, op.in_w, w, op.bias, out, op.out_h, op.out_w,
                                op.out_ld);

@@ -17,6 +17,10 @@ int validate(const avl_seg_op& op, int index) {
     int rc;
     if (op.batch < 0) rc = set_error(AVL_E_ARG, "batch %d (0 or 1 = one image)", op.batch);
     else if (op.bias_per_image && op.kind != AVL_OP_GEMM) rc = set_error(AVL_E_ARG, "bias_per_image is a GEMM field");
+    else if (op.in_format != AVL_IN_U8_HWC && op.in_format != AVL_IN_F32_CHW) rc = set_error(AVL_E_ARG, "in_format %d is not an AVL_IN_* value", op.in_format);
+    else if (op.in_format != AVL_IN_U8_HWC && op.kind != AVL_OP_STEM) rc = set_error(AVL_E_ARG, "in_format %d is a stem field (other ops leave it 0)", op.in_format);
+    else if (op.in_format == AVL_IN_F32_CHW && op.in2)
+        rc = set_error(AVL_E_UNSUPPORTED, "in_format AVL_IN_F32_CHW with a pre-processing stem (in2 set): that stem reads the raw uint8 frame");
     else if (op.kind == AVL_OP_GEMM) rc = validate_gemm(op);
     else if (op.kind == AVL_OP_DWPW) rc = validate_dwpw(op);
     else if (op.kind == AVL_OP_BOTTLENECK) rc = validate_bottleneck(op);
@@ -56,7 +60,8 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
     switch (op.kind) {
         case AVL_OP_STEM:
             flops = 2.0 * out_pix * 64 * 147;
-            bytes = (op.in2 ? (double)op.in_rows : in_pix) * 3 + out_pix * 64 * es;      // in2: the raw camera frame is what is read
+            // in2: the raw camera frame is what is read; AVL_IN_F32_CHW: three fp32 values per pixel instead of three bytes
+            bytes = (op.in2 ? (double)op.in_rows : in_pix) * (op.in_format == AVL_IN_F32_CHW ? 12 : 3) + out_pix * 64 * es;
             break;
         case AVL_OP_GEMM:
             flops = 2.0 * out_pix * op.out_c * (op.in_c + (op.in3 ? op.in3_c : 0));

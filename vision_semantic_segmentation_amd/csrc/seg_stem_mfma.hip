@@ -13,6 +13,10 @@
 // preprocessed_rgb() of seg_preprocess.h -- the function k_preprocess applies -- so the RGB network input is never written
 // to memory or re-read.  The 5-pixel halo of a tile is recomputed (x1.41 pixels), which costs less than
 // the round trip: the undistortion is ~60 double-precision flops per source pixel.
+//
+// F32IN = an input already normalised by the caller (AVL_IN_F32_CHW: fp32 [3][H][W] planes, DeepLabV3Plus.forward's tensor): the
+// loader reads it plane by plane, coalesced along x, and writes (HT)v (SPLIT: and (HT)(v - (float)(HT)v) into tile_lo) -- the
+// conversion the uint8 table applies to its fp32 value, so a float equal to that value fills the same tile bits.
 #include "seg_types.h"
 #include "seg_preprocess.h"
 
@@ -37,7 +41,7 @@ struct StemArgs {
 
 // SPLIT (the complete hi + lo pipeline): the NORMALISED image is kept as two f16 tiles (value = hi + lo), the weights are
 // f16 pairs, the product runs Wh.xh + Wl.xh + Wh.xl and the result leaves as hi + lo planes: no f16-class rounding anywhere.
-template <typename HT, bool PRE, bool SPLIT = false>
+template <typename HT, bool PRE, bool SPLIT = false, bool F32IN = false>
 __global__ void __launch_bounds__(256) k_stem_mfma(StemArgs<HT> p) {
     typedef typename Half16<HT>::v8 v8;
     __shared__ __attribute__((aligned(16))) HT tile[(IN_TH + 1) * ROW];
@@ -49,7 +53,7 @@ __global__ void __launch_bounds__(256) k_stem_mfma(StemArgs<HT> p) {
     const int tx = blockIdx.x % p.tiles_x, ty = blockIdx.x / p.tiles_x;
     const int oy0 = ty * S_TH, ox0 = tx * S_TW;
     if constexpr (!PRE) {       // batch: image blockIdx.z (a pre-processing stem takes one frame)
-        p.img = image_base(p.img, (long long)p.H * p.W, 3);
+        p.img = image_base(p.img, (long long)p.H * p.W, F32IN ? 3 * (int)sizeof(float) : 3);     // (F32IN: `img` is the fp32 planes)
         p.out = image_base(p.out, (long long)p.OH * p.OW, p.out_ld);
         p.out_lo = image_base(p.out_lo, (long long)p.OH * p.OW, p.out_ld);
     }
@@ -82,6 +86,41 @@ __global__ void __launch_bounds__(256) k_stem_mfma(StemArgs<HT> p) {
                 HT* tl = tile_lo + ly * ROW + lx * 3;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) tl[c] = ok ? lut_lo[c * 256 + rgb[c]] : (HT)0.f;
+            }
+        }
+    } else if constexpr (F32IN) {
+        // element e of the 3 x 21 x 69 input values: channel plane, then row, then column (consecutive lanes read consecutive floats
+        // of one image row); all of a lane's loads are issued before the first conversion, as below
+        constexpr int NV = IN_TH * IN_TW, NF = (3 * NV + 255) / 256;
+        const float* src = reinterpret_cast<const float*>(p.img);
+        const long long plane = (long long)p.H * p.W;
+        float v[NF];
+        unsigned okmask = 0;
+    #pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int e = tid + i * 256;
+            const int c = e / NV, r = e - c * NV;
+            const int ly = r / IN_TW, lx = r - ly * IN_TW;
+            const int iy = iy0 + ly, ix = ix0 + lx;
+            const bool ok = e < 3 * NV && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+            const int cy = min(max(iy, 0), p.H - 1), cx = min(max(ix, 0), p.W - 1);      // unconditional load, masked below
+            v[i] = src[min(c, 2) * plane + (long long)cy * p.W + cx];
+            okmask |= (ok ? 1u : 0u) << i;
+        }
+        // the slack of every row and the extra row (read by the zero-weight pad taps)
+        for (int e = tid; e < (IN_TH + 1) * ROW; e += 256) {
+            const int ly = e / ROW, lc = e - ly * ROW;
+            if (ly >= IN_TH || lc >= IN_TW * 3) { tile[e] = (HT)0.f; if constexpr (SPLIT) tile_lo[e] = (HT)0.f; }
+        }
+    #pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int e = tid + i * 256;
+            if (e < 3 * NV) {
+                const int c = e / NV, r = e - c * NV;
+                const int ly = r / IN_TW, lx = r - ly * IN_TW;
+                const float x = ((okmask >> i) & 1u) ? v[i] : 0.f;       // padding applies to the normalised image: 0
+                tile[ly * ROW + lx * 3 + c] = (HT)x;
+                if constexpr (SPLIT) tile_lo[ly * ROW + lx * 3 + c] = (HT)(x - (float)(HT)x);
             }
         }
     } else {
@@ -220,7 +259,15 @@ int launch_stem_typed(const avl_seg_op& op, hipStream_t s) {
     a.srcW = op.in2_ld;
     a.srcH = op.in2_ld > 0 ? op.in_rows / op.in2_ld : 0;
     a.factor = op.in_w > 0 ? a.srcW / op.in_w : 1;
-    if (op.w_split) {
+    const dim3 grid(a.tiles_x * tiles_y, 1, op_batch(op));
+    if (op.in_format == AVL_IN_F32_CHW) {       // (validated: never with in2)
+        if (op.w_split) {
+            if (!op.out_lo) return set_error(AVL_E_ARG, "split stem (w_split = 1): out_lo is NULL");
+            hipLaunchKernelGGL((k_stem_mfma<HT, false, true, true>), grid, dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((k_stem_mfma<HT, false, false, true>), grid, dim3(256), 0, s, a);
+        }
+    } else if (op.w_split) {
         if (!op.out_lo) return set_error(AVL_E_ARG, "split stem (w_split = 1): out_lo is NULL");
         if (op.in2)
             hipLaunchKernelGGL((k_stem_mfma<HT, true, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);

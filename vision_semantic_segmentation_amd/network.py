@@ -46,7 +46,13 @@ class AvlSegOp(C.Structure):
         ("w_mx", C.c_void_p), ("in_mx", C.c_void_p), ("out_mx", C.c_void_p), ("in2_mx", C.c_void_p),
         ("in3", C.c_void_p), ("in3_mx", C.c_void_p), ("in3_c", C.c_int32), ("in3_ld", C.c_int32),
         ("batch", C.c_int32), ("bias_per_image", C.c_int32),
+        ("in_format", C.c_int32),
     ]
+
+
+AVL_IN_U8_HWC, AVL_IN_F32_CHW = 0, 1
+# SegNet(input_format=...): the plan's input tensor
+INPUT_FORMATS = {"u8_hwc": AVL_IN_U8_HWC, "f32_nchw": AVL_IN_F32_CHW}
 
 
 AVL_MX_IN_LO, AVL_MX_RES_LO, AVL_MX_OUT_LO = 1, 2, 4
@@ -562,13 +568,21 @@ class SegNet(object):
     MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier")    # keyword switches of the "mixed" mode
 
     def __init__(self, state, height, width, precision="bf16", device=None, num_classes=19, output_stride=8, fuse_dwpw=True, raw_frame=None,
-                 part=None, backbone=DEFAULT_BACKBONE, batch=1, **mixed_opts):
+                 part=None, backbone=DEFAULT_BACKBONE, batch=1, input_format="u8_hwc", **mixed_opts):
         """raw_frame = (src_h, src_w): the plan's input is the RAW BGR camera frame and the node's pre-processing
         (vision_semantic_segmentation_node.py:83-98: BGR->RGB, undistort, INTER_AREA by src_w // width) runs inside the stem's loader
         (16-bit precisions); ``set_camera`` chooses the camera model, ``forward`` takes the raw frame.
         batch = N: the plan runs N images of height x width at once (DeepLabV3Plus.forward on an N x 3 x H x W batch); every op takes
         them packed densely, image n at pixel rows [n h w, (n + 1) h w) of each activation, and computes for each exactly what the
-        batch-1 plan computes."""
+        batch-1 plan computes.
+        input_format: "u8_hwc" = uint8 RGB frames [N,H,W,3] that the stem normalises; "f32_nchw" = the reference model's input, fp32
+        [N,3,H,W] ([3,H,W] for a batch of one) already normalised by the caller (AVL_IN_F32_CHW).  Not with raw_frame or part."""
+        if input_format not in INPUT_FORMATS:
+            raise ValueError("SegNet: input_format %r (known: %s)" % (input_format, ", ".join(INPUT_FORMATS)))
+        if input_format != "u8_hwc" and (raw_frame is not None or part is not None):
+            raise NotImplementedError("SegNet: input_format %r is the network input itself; a raw_frame plan (pre-processing stem) or a "
+                                      "sub-plan (part) takes no such input" % input_format)
+        self.input_format = input_format
         batch = int(batch)
         if batch < 1:
             raise ValueError("SegNet: batch %d < 1" % batch)
@@ -876,8 +890,10 @@ class SegNet(object):
         H, W = self.H, self.W
         dev = self.device
         # the plan's input: the RGB network input, or the raw BGR camera frame when the stem pre-processes
-        shape = (H, W, 3) if self.raw_frame is None else self.raw_frame + (3,)
-        self.image = torch.zeros(((self.batch,) if self.batch > 1 else ()) + shape, dtype=torch.uint8, device=dev)
+        # (or, input_format "f32_nchw", the normalised fp32 planes)
+        f32_in = self.input_format == "f32_nchw"
+        shape = (3, H, W) if f32_in else ((H, W, 3) if self.raw_frame is None else self.raw_frame + (3,))
+        self.image = torch.zeros(((self.batch,) if self.batch > 1 else ()) + shape, dtype=torch.float32 if f32_in else torch.uint8, device=dev)
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=dev)          # what a depthwise tap outside the image reads
         self.camera_block = torch.zeros(64, dtype=torch.uint8, device=dev)       # AVL_STEM_CAMERA_BYTES: zeros = no undistortion
         self._keep += [self.image, self.zero_page, self.camera_block]
@@ -898,7 +914,7 @@ class SegNet(object):
         self._op("backbone.conv1", OP_STEM, in_=self.image.data_ptr(), out=stem.hi.data_ptr(), weight=w_stem.data_ptr(),
                  bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.numel() // 3, out_h=h2, out_w=w2,
                  out_c=64, out_ld=64, out_rows=stem.shape[0], ksize=7, stride=2, pad=3, dil=1, groups=1, relu=1, w_layout=stem_layout,
-                 w_split=int(self.full_split), out_lo=self._lo(stem), **raw)
+                 w_split=int(self.full_split), out_lo=self._lo(stem), in_format=INPUT_FORMATS[self.input_format], **raw)
         h4, w4 = (h2 + 2 - 3) // 2 + 1, (w2 + 2 - 3) // 2 + 1
         x = self._act(h4 * w4, 64, split=self.full_split)
         self._spatial("backbone.maxpool", OP_MAXPOOL, stem, (h2, w2), 64, x, (h4, w4), 64, ksize=3, stride=2, pad=1, dil=1,
@@ -1260,12 +1276,19 @@ class SegNet(object):
 
     def forward(self, image_u8=None, stream=None):
         """image_u8: CUDA/CPU uint8 [H,W,3] RGB ([N,H,W,3] for a plan of batch N > 1) -- or, for a raw_frame plan, the
-        [src_h,src_w,3] BGR camera frame -- (copied into the plan's input buffer) or None to reuse it."""
+        [src_h,src_w,3] BGR camera frame -- (copied into the plan's input buffer) or None to reuse it.
+        An input_format "f32_nchw" plan takes a float tensor [3,H,W] ([N,3,H,W]) instead: another float dtype is converted and a CPU
+        tensor copied, both by the copy into the plan's fp32 input buffer."""
         if image_u8 is not None:
             assert self.part is None, "a sub-plan takes its inputs through set_feature / set_low"
             if not isinstance(image_u8, torch.Tensor):
                 image_u8 = torch.from_numpy(np.ascontiguousarray(image_u8))
-            assert tuple(image_u8.shape) == tuple(self.image.shape) and image_u8.dtype == torch.uint8
+            if self.input_format == "f32_nchw":
+                if tuple(image_u8.shape) != tuple(self.image.shape) or not image_u8.dtype.is_floating_point:
+                    raise ValueError("this plan takes a float tensor of shape %s, not %s %s" % (tuple(self.image.shape), image_u8.dtype,
+                                                                                               tuple(image_u8.shape)))
+            else:
+                assert tuple(image_u8.shape) == tuple(self.image.shape) and image_u8.dtype == torch.uint8
             self.image.copy_(image_u8, non_blocking=True)
         s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
         _lib.check(_lib.lib().avl_seg_plan_run(self._plan, C.c_void_p(s)), "avl_seg_plan_run")

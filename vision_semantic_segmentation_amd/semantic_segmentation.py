@@ -77,14 +77,17 @@ class SemanticSegmentation(object):
 
     LADDER = ("mixed", "mixed+lo", "split16", "f32")
 
-    def net_for(self, h, w, raw_frame=None, batch=1):
-        """The compiled plan for a batch of `batch` h x w network inputs (built on first use, kept per size and batch).  raw_frame =
-        (src_h, src_w): the plan that takes the raw BGR camera frame and pre-processes inside its first kernel (one frame only).
-        The mixed self-check runs once, on h x w frames of a batch of one; the rung it picks serves every batch."""
+    def net_for(self, h, w, raw_frame=None, batch=1, input_format="u8_hwc"):
+        """The compiled plan for a batch of `batch` h x w network inputs (built on first use, kept per size, batch and input format).
+        raw_frame = (src_h, src_w): the plan that takes the raw BGR camera frame and pre-processes inside its first kernel (one frame only).
+        input_format "f32_nchw": the plan takes normalised fp32 [N,3,h,w] tensors (SegNet); "u8_hwc" (default): uint8 RGB frames.
+        The mixed self-check runs once, on h x w frames of a batch of one; the rung it picks serves every batch and input format."""
         batch = int(batch)
         if batch > 1 and raw_frame is not None:
             raise NotImplementedError("a raw_frame plan (pre-processing stem) takes one camera frame, not a batch of %d" % batch)
         key = (int(h), int(w), batch) + (() if raw_frame is None else (int(raw_frame[0]), int(raw_frame[1])))
+        if input_format != "u8_hwc":
+            key += (input_format,)
         if key not in self._nets:
             if self._self_check and self.precision == "mixed" and self.mixed_check is None:
                 self.check_mixed_against_f32(key[0], key[1])
@@ -92,16 +95,16 @@ class SemanticSegmentation(object):
             if rung == "f32" and raw_frame is not None:
                 raise NotImplementedError("the self-check fell back to the fp32 plan, which has no pre-processing stem: "
                                           "use preprocess_device() + segmentation_device()")
-            net = self._build(key[0], key[1], rung, raw_frame, batch)
+            net = self._build(key[0], key[1], rung, raw_frame, batch, input_format)
             if getattr(self.cfg.MODEL, "HIP_GRAPH", True):
                 net.capture_graph()
             self._nets[key] = net
         return self._nets[key]
 
-    def _build(self, h, w, rung, raw_frame=None, batch=1):
+    def _build(self, h, w, rung, raw_frame=None, batch=1, input_format="u8_hwc"):
         """rung: a plan of the ladder ("mixed", "mixed+lo", "split16") or a plain precision ("f32", "f16", "bf16")"""
         kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride, backbone=self.backbone,
-                  batch=batch)
+                  batch=batch, input_format=input_format)
         if rung in ("f32", "f16", "bf16"):
             return SegNet(self.state, h, w, precision=rung, **kw)
         if rung == "split16":
@@ -277,6 +280,31 @@ class SemanticSegmentation(object):
         if head.logits is None:
             head.logits = torch.empty((self.num_classes, h, w), dtype=torch.float32, device=self.device)
         return seg_head.upsample_logits(net.logits, h, w, out=head.logits)
+
+    def forward_tensor(self, x, upsample_pred=True):
+        """DeepLabV3Plus.forward(x, upsample_pred) (deeplab_v3_plus.py:51-71) on the reference's own input: x = float [N,3,h,w],
+        normalised as ToTensor + Normalize leave it (any float dtype; a CPU tensor is copied to the device).  Runs the plan of the rung
+        the ladder picked, with the fp32-input stem (SegNet(input_format="f32_nchw")).  Returns a NEW fp32 tensor: the logits
+        [N,K,h',w'], or [N,K,h,w] with upsample_pred (F.interpolate(..., align_corners=True), seg_head.upsample_logits per image).
+        An unbatched x [3,h,w] gives [K,h',w'] ([K,h,w]), as torch's convolutions treat an unbatched input."""
+        if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or x.shape[-3] != 3 or not x.dtype.is_floating_point:
+            raise ValueError("expected a float tensor [N, 3, h, w] or [3, h, w], got %s" % (
+                "%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
+        unbatched = x.dim() == 3
+        xb = x.unsqueeze(0) if unbatched else x
+        n, h, w = int(xb.shape[0]), int(xb.shape[2]), int(xb.shape[3])
+        if n < 1:
+            raise ValueError("an empty batch")
+        net = self.net_for(h, w, batch=n, input_format="f32_nchw")
+        net.forward(xb[0] if n == 1 else xb)
+        logits = net.logits if n > 1 else net.logits.unsqueeze(0)          # [N, h', w', K]
+        if not upsample_pred:
+            out = logits.permute(0, 3, 1, 2).contiguous()
+        else:
+            out = torch.empty((n, self.num_classes, h, w), dtype=torch.float32, device=self.device)
+            for i in range(n):
+                seg_head.upsample_logits(logits[i], h, w, out=out[i])
+        return out[0] if unbatched else out
 
     def validate_step(self, image_in, label, metric=None):
         """The reference's validation step for a batch of one (train.py:138-141: preds = model(x); loss = loss_fn(preds, label);

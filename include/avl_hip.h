@@ -252,7 +252,10 @@ int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, 
 #define AVL_OP_MAXPOOL 2     /* 3x3 s2 p1 (torchvision ResNet.maxpool)                                          */
 #define AVL_OP_GEMM 3        /* 1x1 conv: out[m][n] = act(sum_k in[row(m)][k] w[n][k] + bias[n] (+ in2[m][n])) */
 #define AVL_OP_GCONV 4       /* grouped or dense 3x3 conv, stride 1|2, dilation d, pad d, +bias+ReLU (Bottleneck.conv2; w_layout) */
-#define AVL_OP_DWCONV 5      /* depthwise 3x3 conv, dilation d, pad p, +bias+ReLU (core/nn/modules/conv.py:131)  */
+#define AVL_OP_DWCONV 5      /* depthwise conv +bias+ReLU (core/nn/modules/conv.py:131); weight fp32 [ksize*ksize][C].
+                                ksize 3: dilation d, pad p (ASPP, decoder).  ksize 1, 2, 4..7 (MODEL.DECODER.REFINE_KERNEL_SIZE,
+                                seg_dwconv_k.hip): the decoder's geometry only -- stride 1, dil 1, pad 0, out = in - (ksize - 1),
+                                no out_mx, in_lo / out_lo both set (split f16) or both unset, in2 unused                    */
 #define AVL_OP_BILINEAR 6    /* F.interpolate(mode='bilinear', align_corners=True) (aspp.py:88, decoder.py:47)   */
 #define AVL_OP_GAP 7         /* AdaptiveAvgPool2d((1,1)) -> fp32 [C] (aspp.py:69)                                */
 #define AVL_OP_GEMV 8        /* out[n] = act(sum_k w[n][k] in[k] + bias[n]) on fp32 vectors (pooled branch)      */
@@ -295,7 +298,7 @@ typedef struct avl_seg_op {
     int32_t dtype;           /* activation type of in/in2/out: AVL_BF16, AVL_F16 or AVL_F32      */
     const void* in;          /* input activation (STEM: uint8 image, or fp32 planes: in_format; GEMV/GAP-out: fp32) */
     const void* in2;         /* GEMM: residual added before the ReLU, or NULL; GAP: fp32 scratch [256][C];
-                                DWCONV: 32 zero bytes (what a tap outside the image reads);
+                                DWCONV (ksize 3): 32 zero bytes (what a tap outside the image reads);
                                 STEM: NULL, or the camera block of a pre-processing stem (avl_stem_camera_set) */
     void* out;
     const void* weight;      /* packed by the host, layout per kind (see network.py)            */

@@ -698,6 +698,7 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
             break;
         }
         case AVL_OP_DWCONV: {
+            if (op.ksize != 3) return launch_dwconv_k(op, s);      // the decoder's k x k refine blocks (seg_dwconv_k.hip)
             if ((op.in_lo == nullptr) != (op.out_lo == nullptr) && !op.out_mx) {      // one side split only: the simple kernel
                 hipLaunchKernelGGL(k_dwconv_split<T>, dim3(blocks_for((long long)op.out_h * op.out_w * (op.in_c / 8)), 1, nimg), dim3(kThreads), 0, s,
                                    in, static_cast<const T*>(op.in_lo), w, op.bias, out, static_cast<T*>(op.out_lo), op.in_h, op.in_w,
@@ -825,7 +826,7 @@ int validate_conv_op(const avl_seg_op& op) {
     AVL_REQUIRE(op.in_ld >= op.in_c && op.out_ld >= op.out_c, "op %d: leading dims", op.kind);
     AVL_REQUIRE((op.in_ld * es) % 16 == 0 && (op.out_ld * es) % 16 == 0, "op %d: row strides must be 16-byte multiples", op.kind);
     AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.in) | reinterpret_cast<uintptr_t>(op.out)) % 16 == 0, "op %d: unaligned buffers", op.kind);
-    if (op.out_mx && op.kind == AVL_OP_DWCONV) {
+    if (op.out_mx && op.kind == AVL_OP_DWCONV && op.ksize == 3) {
         AVL_REQUIRE(op.dtype == AVL_F16 && op.in_lo && op.out_c % 256 == 0 && op.out_ld == op.out_c && (op.in_c / 8) % 4 == 0,
                     "dwconv: out_mx needs the split f16 form, channels %% 256 == 0 and a dense output");
         AVL_REQUIRE(!(op.mx_flags & AVL_MX_OUT_LO) || !op.out_lo, "dwconv: AVL_MX_OUT_LO together with out_lo");
@@ -854,6 +855,7 @@ int validate_conv_op(const avl_seg_op& op) {
             break;
         }
         case AVL_OP_DWCONV:
+            if (op.ksize != 3) return validate_dwconv_k(op);
             AVL_REQUIRE(op.weight && op.bias && op.out_c == op.in_c && op.ksize == 3 && op.stride == 1 && op.dil >= 1 && op.pad >= 0, "dwconv geometry");
             AVL_REQUIRE(op.in2 && reinterpret_cast<uintptr_t>(op.in2) % 16 == 0, "dwconv needs in2 = a 32-byte zero page (taps outside the image read it)");
             AVL_REQUIRE(op.out_h == op.in_h + 2 * op.pad - 2 * op.dil && op.out_w == op.in_w + 2 * op.pad - 2 * op.dil, "dwconv output size");

@@ -81,7 +81,7 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
             bytes += (double)op.out_c * (op.in_c / op.groups) * 9 * es * (op.w_split ? 2.0 : 1.0);
             break;
         case AVL_OP_DWCONV:
-            flops = 2.0 * out_pix * op.out_c * 9;
+            flops = 2.0 * out_pix * op.out_c * op.ksize * op.ksize;
             break;
         case AVL_OP_DWPW:
             flops = 2.0 * out_pix * op.in_c * 9 + 2.0 * out_pix * op.out_c * op.in_c;

@@ -7,18 +7,20 @@ N x 3 x H x W tensors run unchanged on the evaluation path.
     model.load_state_dict(torch.load(path)["model"])          # 'module.' keys, as the reference saves them
     model.eval()
     with torch.no_grad():
-        logits = model(x)                                      # fp32 [N, K, H, W]; upsample_pred=False: [N, K, H/4-4, W/4-4]
+        logits = model(x)                                      # fp32 [N, K, H, W]; upsample_pred=False: [N, K, H', W']
 
 The weights are BUFFERS named as the reference checkpoint's keys (plus one ``num_batches_tracked`` per BatchNorm, accepted and
 unused), so ``state_dict()``, strict ``load_state_dict``, ``.cuda()`` / ``.to()`` and the ``module.`` prefix of a one-GPU
-``nn.DataParallel`` behave as in the reference.  Inference only: a forward in train() mode raises NotImplementedError.
+``nn.DataParallel`` behave as in the reference.  H' x W' (upsample_pred=False) is the low-level map (H/4 x W/4) less sum(k_i - 1)
+over the refine blocks' depthwise kernel sizes (decoder_cfg.REFINE_KERNEL_SIZE, padding 0): H/4-4 x W/4-4 for the default [3, 3].
+Inference only: a forward in train() mode raises NotImplementedError.
 """
 import torch
 import torch.nn as nn
 
 from . import metrics
 from .config import get_network_cfg_defaults
-from .network import random_state_dict, state_spec
+from .network import random_state_dict, refine_kernel_sizes, state_spec
 from .semantic_segmentation import SemanticSegmentation
 
 # build-specific MODEL.* settings build_model() hands on when the configuration has them (config.py)
@@ -61,6 +63,7 @@ class DeepLabV3Plus(nn.Module):
         m.ASPP.ATROUS_CHANNELS = list(_get(aspp_cfg, "ATROUS_CHANNELS", m.ASPP.ATROUS_CHANNELS))
         m.DECODER.LOW_LEVEL_OUT_CHANNELS = int(_get(decoder_cfg, "LOW_LEVEL_OUT_CHANNELS", m.DECODER.LOW_LEVEL_OUT_CHANNELS))
         m.DECODER.REFINE_CHANNELS = list(_get(decoder_cfg, "REFINE_CHANNELS", m.DECODER.REFINE_CHANNELS))
+        m.DECODER.REFINE_KERNEL_SIZE = list(refine_kernel_sizes(_get(decoder_cfg, "REFINE_KERNEL_SIZE", None), m.DECODER.REFINE_CHANNELS))
         m.PRECISION, m.MIXED_ON_FAIL = precision, on_fail
         for k, v in (model_options or {}).items():
             if k not in MODEL_OPTIONS:
@@ -68,7 +71,8 @@ class DeepLabV3Plus(nn.Module):
             m[k] = v
         self._spec_kw = dict(num_classes=self.out_channels, in_channels=self.in_channels, aspp_out=m.ASPP.OUT_CHANNELS,
                              atrous_channels=tuple(m.ASPP.ATROUS_CHANNELS), low_level_out=m.DECODER.LOW_LEVEL_OUT_CHANNELS,
-                             refine_channels=tuple(m.DECODER.REFINE_CHANNELS), backbone=m.BACKBONE)
+                             refine_channels=tuple(m.DECODER.REFINE_CHANNELS), backbone=m.BACKBONE,
+                             refine_kernel_size=tuple(m.DECODER.REFINE_KERNEL_SIZE))
         self._keys = [k for k, _ in state_spec(**self._spec_kw)]          # (NotImplementedError for an unsupported backbone)
         init = random_state_dict(seed=0, **self._spec_kw)
         for k in self._keys:
@@ -127,7 +131,7 @@ class DeepLabV3Plus(nn.Module):
 
     def forward(self, x, upsample_pred=True):
         """x: normalised float [N, 3, H, W] -> fp32 logits [N, K, H, W] (upsample_pred=True, F.interpolate with align_corners=True)
-        or [N, K, H/4-4, W/4-4], in a new tensor without grad_fn."""
+        or [N, K, H', W'] (H/4 - sum(k_i - 1), module docstring), in a new tensor without grad_fn."""
         if self.training:
             raise NotImplementedError("DeepLabV3Plus here is inference only: call .eval() first (no training or backward)")
         if getattr(self, "_is_replica", False):

@@ -107,15 +107,40 @@ def backbone_arch(name):
     raise NotImplementedError("MODEL.BACKBONE %r is not supported; supported: %s" % (name, ", ".join(sorted(BACKBONES))))
 
 
+# depthwise kernel sizes of the decoder's refine blocks that have a kernel: 3 (k_dwconv / k_dwpw*) and the k x k op (seg_dwconv_k.hip)
+REFINE_KERNEL_SIZES = (1, 2, 3, 4, 5, 6, 7)
+
+
+def refine_kernel_sizes(refine_kernel_size, refine_channels):
+    """MODEL.DECODER.REFINE_KERNEL_SIZE -> a tuple with one size per refine block.  None = 3 everywhere.  The reference asserts one size
+    per block (decoder.py:20); a list of 3s of another length still means "3 everywhere" (what this build did before it read the key).
+    ValueError for another length or for a size outside REFINE_KERNEL_SIZES."""
+    n = len(refine_channels)
+    if refine_kernel_size is None:
+        return (3,) * n
+    ks = tuple(int(k) for k in refine_kernel_size)
+    if len(ks) != n:
+        if all(k == 3 for k in ks):
+            return (3,) * n
+        raise ValueError("MODEL.DECODER.REFINE_KERNEL_SIZE %s has %d entries, REFINE_CHANNELS %d: one kernel size per refine block "
+                         "(decoder.py:20)" % (list(ks), len(ks), n))
+    bad = [k for k in ks if k not in REFINE_KERNEL_SIZES]
+    if bad:
+        raise ValueError("MODEL.DECODER.REFINE_KERNEL_SIZE %s: depthwise kernels are built for sizes %s" % (list(ks), ", ".join(map(str, REFINE_KERNEL_SIZES))))
+    return ks
+
+
 def _bn_keys(prefix, c):
     return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)),
             (prefix + ".running_var", (c,))]
 
 
 def state_spec(num_classes=19, in_channels=3, aspp_out=256, atrous_channels=(256, 256, 256, 256), low_level_out=256,
-               refine_channels=(256, 256), backbone=DEFAULT_BACKBONE):
+               refine_channels=(256, 256), backbone=DEFAULT_BACKBONE, refine_kernel_size=None):
     """[(key, shape)] of DeepLabV3Plus.state_dict() for MODEL.BACKBONE = `backbone` (keys as
-    saved by the reference, without the DataParallel 'module.' prefix)."""
+    saved by the reference, without the DataParallel 'module.' prefix).  refine_kernel_size: the depthwise kernel size of each
+    refine block (MODEL.DECODER.REFINE_KERNEL_SIZE, decoder.py:16-36); None = 3 for every block."""
+    refine_kernel_size = refine_kernel_sizes(refine_kernel_size, refine_channels)
     layers, groups, wpg = backbone_arch(backbone)
     spec = [("backbone.conv1.weight", (64, in_channels, 7, 7))] + _bn_keys("backbone.bn1", 64)
     inplanes = 64
@@ -141,7 +166,8 @@ def state_spec(num_classes=19, in_channels=3, aspp_out=256, atrous_channels=(256
     cin = low_level_out + aspp_out
     for i, rc in enumerate(refine_channels):
         p = "decoder.refine_layers.%d" % i
-        spec += [(p + ".depthwise_cnn.conv.weight", (cin, 1, 3, 3))] + _bn_keys(p + ".depthwise_cnn.bn", cin)
+        k = refine_kernel_size[i]
+        spec += [(p + ".depthwise_cnn.conv.weight", (cin, 1, k, k))] + _bn_keys(p + ".depthwise_cnn.bn", cin)
         spec += [(p + ".pointwise_cnn.conv.weight", (rc, cin, 1, 1))] + _bn_keys(p + ".pointwise_cnn.bn", rc)
         cin = rc
     p = "decoder.refine_layers.%d" % len(refine_channels)
@@ -654,6 +680,7 @@ class SegNet(object):
         # the HIP kernels with the reference MODULES' outputs (tests/golden/net_aspp256.pt, net_decoder256.pt)
         self.part = part
         if part is None:
+            self._check_decoder_size(state)
             self._build(state)
         else:
             self._build_part(state)
@@ -666,6 +693,23 @@ class SegNet(object):
                 _lib.lib().avl_seg_plan_destroy(self._plan)
         except Exception:
             pass
+
+    def _check_decoder_size(self, state):
+        """ValueError when the refine blocks' k x k depthwise convs (padding 0: each shrinks the map by k - 1) leave nothing of the
+        low-level map (h/4 x w/4) -- before any buffer is made.  Names the smallest input size that works."""
+        shrink, i = 0, 0
+        while ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % i) in state:
+            shrink += state["decoder.refine_layers.%d.depthwise_cnn.conv.weight" % i].shape[-1] - 1
+            i += 1
+        low = lambda n: ((n + 6 - 7) // 2 + 1 + 2 - 3) // 2 + 1          # stem (7x7 s2 p3), max-pool (3x3 s2 p1)
+        if min(low(self.H), low(self.W)) - shrink >= 1:
+            return
+        need = 1
+        while low(need) - shrink < 1:
+            need += 1
+        raise ValueError("SegNet: a %dx%d input is too small for the decoder: its low-level map is %dx%d and the refine blocks' depthwise "
+                         "convs take %d pixels off each side; the smallest input that works is %dx%d"
+                         % (self.H, self.W, low(self.H), low(self.W), shrink, max(need, self.H), max(need, self.W)))
 
     # -------------------------------------------------------------------------------- buffers
     def _act(self, rows, ch, split=False, mx=False, lo_fp4=False):
@@ -1186,8 +1230,9 @@ class SegNet(object):
         k = 0
         while ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % k) in st:
             p = "decoder.refine_layers.%d" % k
-            ohw = (hw[0] - 2, hw[1] - 2)                                # padding 0 (decoder.py:33-36 default)
             w, b = fold_bn(st, p + ".depthwise_cnn.conv.weight", p + ".depthwise_cnn.bn")
+            ks = w.shape[-1]                                            # MODEL.DECODER.REFINE_KERNEL_SIZE[k]
+            ohw = (hw[0] - (ks - 1), hw[1] - (ks - 1))                  # padding 0 (decoder.py:33-36 default)
             w2, b2 = fold_bn(st, p + ".pointwise_cnn.conv.weight", p + ".pointwise_cnn.bn")
             if k == 0 and w.shape[0] != cin:             # the padded low-level channels (see above)
                 npad = cin - w.shape[0]
@@ -1197,7 +1242,7 @@ class SegNet(object):
             last = ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % (k + 1)) not in st
             fused_mixed = self.mixed and self.mixed_fuse_decoder and self.mixed_dw_exact
             # the last refine block also carries the classifier (decoder.py:42-43) and the arg-max in its epilogue: its 256-channel result never goes to memory
-            if (last and fused_mixed and self.mixed_fuse_classifier and self.half and self.fuse_dwpw and cin % 64 == 0 and w2.shape[0] == 256
+            if (ks == 3 and last and fused_mixed and self.mixed_fuse_classifier and self.half and self.fuse_dwpw and cin % 64 == 0 and w2.shape[0] == 256
                     and self.num_classes <= 32 and x.lo is not None):
                 pc = "decoder.refine_layers.%d" % (k + 1)
                 wc, bc = fold_bn(st, pc + ".conv.weight", None)
@@ -1215,16 +1260,18 @@ class SegNet(object):
             # tools/precision_study.py).  fuse_decoder (default): one k_dwpw_xs launch per block -- split input, depthwise weights as
             # f16 pairs, the depthwise result as a split tile in LDS, three MFMA passes, split output; off: the split depthwise
             # kernel (fp32 weights) -> HBM -> an MX / three-pass GEMM
-            if self.half and self.fuse_dwpw and cin % 64 == 0 and cin <= 2048 and (not self.mixed or (self.mixed_fuse_decoder and self.mixed_dw_exact)):
+            if (ks == 3 and self.half and self.fuse_dwpw and cin % 64 == 0 and cin <= 2048
+                    and (not self.mixed or (self.mixed_fuse_decoder and self.mixed_dw_exact))):
                 self._dwpw(p, x, hw, cin, w, b, w2, b2, y, 0, 1, padding=0)
                 self._release(x)
             else:
-                wd_, bd_ = self._dev(w.reshape(cin, 9).t().reshape(-1), torch.float32), self._dev(b, torch.float32)
-                # mixed: the depthwise output feeds an MX GEMM where shapes allow (f16 plane + FP4 copies, lo part as FP4 only)
-                t_fp4 = self.mixed_mx and self.mixed_trunk_fp4 and cin % 256 == 0 and w2.shape[0] % 256 == 0 and x.lo is not None
+                wd_, bd_ = self._dev(w.reshape(cin, ks * ks).t().reshape(-1), torch.float32), self._dev(b, torch.float32)     # [tap][C]
+                # mixed: the 3x3 depthwise output feeds an MX GEMM where shapes allow (f16 plane + FP4 copies, lo part as FP4 only); the k x k op
+                # (ks != 3, seg_dwconv_k.hip) writes no FP4 copy: its split output feeds the three-pass GEMM
+                t_fp4 = ks == 3 and self.mixed_mx and self.mixed_trunk_fp4 and cin % 256 == 0 and w2.shape[0] % 256 == 0 and x.lo is not None
                 t = self._act(ohw[0] * ohw[1], cin, split=self.mixed, mx=t_fp4, lo_fp4=t_fp4)
-                self._spatial(p + ".depthwise_cnn", OP_DWCONV, x, hw, cin, t, ohw, cin, wd_, bd_, ksize=3, stride=1, pad=0, dil=1, groups=cin, relu=1,
-                              in2=self.zero_page.data_ptr())
+                self._spatial(p + ".depthwise_cnn", OP_DWCONV, x, hw, cin, t, ohw, cin, wd_, bd_, ksize=ks, stride=1, pad=0, dil=1, groups=cin, relu=1,
+                              in2=self.zero_page.data_ptr() if ks == 3 else 0)
                 self._release(x)
                 self._gemm(p + ".pointwise_cnn", t, ohw, cin, w2, b2, y)
                 self._release(t)

@@ -2,8 +2,11 @@
 on the HIP conv stack.
 
     seg = SemanticSegmentation(cfg.VISION_SEM_SEG.SEM_SEG_NETWORK)
-    labels = seg.segmentation(image_rgb_u8)        # int64 ndarray [h/4-4, w/4-4], as the reference returns
-    labels = seg.segmentation(np.stack(frames))    # a batch [N, h, w, 3] -> [N, h/4-4, w/4-4], one plan for all N
+    labels = seg.segmentation(image_rgb_u8)        # int64 ndarray [h', w'], as the reference returns
+    labels = seg.segmentation(np.stack(frames))    # a batch [N, h, w, 3] -> [N, h', w'], one plan for all N
+
+h' x w' is the low-level map (h/4 x w/4, rounded as the stem and max-pool round) less sum(k_i - 1) over the refine blocks'
+depthwise kernel sizes k_i (MODEL.DECODER.REFINE_KERNEL_SIZE; padding 0): h/4-4 x w/4-4 for the default [3, 3].
 
 Differences by design: weights come from a LOCAL checkpoint (``MODEL.WEIGHT``) in the reference's
 format or, when that is empty, from a seeded random init -- the reference's
@@ -15,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, seg_head
-from .network import BACKBONES, SegNet, backbone_arch, check_state_dict, load_checkpoint, random_state_dict
+from .network import BACKBONES, SegNet, backbone_arch, check_state_dict, load_checkpoint, random_state_dict, refine_kernel_sizes
 
 
 def _strict_bool(v, what):
@@ -46,7 +49,11 @@ class SemanticSegmentation(object):
         self.precision = getattr(cfg.MODEL, "PRECISION", "mixed")
         kw = dict(num_classes=self.num_classes, in_channels=cfg.DATASET.IN_CHANNELS, aspp_out=cfg.MODEL.ASPP.OUT_CHANNELS,
                   atrous_channels=tuple(cfg.MODEL.ASPP.ATROUS_CHANNELS), low_level_out=cfg.MODEL.DECODER.LOW_LEVEL_OUT_CHANNELS,
-                  refine_channels=tuple(cfg.MODEL.DECODER.REFINE_CHANNELS), backbone=self.backbone)
+                  refine_channels=tuple(cfg.MODEL.DECODER.REFINE_CHANNELS), backbone=self.backbone,
+                  refine_kernel_size=refine_kernel_sizes(getattr(cfg.MODEL.DECODER, "REFINE_KERNEL_SIZE", None),
+                                                         cfg.MODEL.DECODER.REFINE_CHANNELS))
+        # (every plan, those of the self-check ladder included, takes each refine block's kernel size from its depthwise weight)
+        self.refine_kernel_size = kw["refine_kernel_size"]
         if state_dict is not None:
             self.state = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         elif cfg.MODEL.WEIGHT:
@@ -220,11 +227,11 @@ class SemanticSegmentation(object):
         return t
 
     def segmentation_device(self, image_in, upsample_pred=False):
-        """uint8 RGB [h,w,3] (ndarray or CUDA tensor) -> uint8 CUDA tensor [h/4-4, w/4-4].
+        """uint8 RGB [h,w,3] (ndarray or CUDA tensor) -> uint8 CUDA tensor [h', w'] (module docstring).
         upsample_pred=True: labels at the input's size [h, w] -- the arg-max of model(x, upsample_pred=True) (deeplab_v3_plus.py:67-69),
         from the fused full-resolution kernel (the upsampled logits are never written).  A view of a buffer owned per input size: the
         next call of the same size overwrites it.
-        A batch [N,h,w,3] runs through one plan of batch N -> [N, h/4-4, w/4-4] ([N, h, w] with upsample_pred: the full-resolution
+        A batch [N,h,w,3] runs through one plan of batch N -> [N, h', w'] ([N, h, w] with upsample_pred: the full-resolution
         kernel once per image, on that image's logits)."""
         net, n, h, w = self._run(image_in)
         if n is None:

@@ -159,7 +159,9 @@ int avl_preprocess_image_area(const uint8_t* bgr, int h, int w, const double* K_
  * in_rows = src_h * src_w of the raw frame; the integer factor is src_w / in_w (in_h == src_h / factor is checked).
  * `in2` points at AVL_STEM_CAMERA_BYTES of DEVICE memory holding the camera model, written by avl_stem_camera_set()
  * (stream-ordered: a plan captured into a hipGraph serves camera1 and camera6 alike; K_host / dist_host as above, both NULL
- * = no undistortion). */
+ * = no undistortion).  Every activation type has such a stem: AVL_BF16 / AVL_F16 with w_layout 1 (the MFMA stem) and AVL_F32 with
+ * w_layout 0 (the fp32 stem, same [ky][kx][ci][co] weights and fmaf chain as the plain one); a 16-bit stem with w_layout 0 is refused,
+ * as are in_format AVL_IN_F32_CHW and batch > 1 (one raw frame). */
 #define AVL_STEM_CAMERA_BYTES 64
 int avl_stem_camera_set(void* camera_dev, const double* K_host, const double* dist_host, void* stream);
 
@@ -299,7 +301,8 @@ typedef struct avl_seg_op {
     const void* in;          /* input activation (STEM: uint8 image, or fp32 planes: in_format; GEMV/GAP-out: fp32) */
     const void* in2;         /* GEMM: residual added before the ReLU, or NULL; GAP: fp32 scratch [256][C];
                                 DWCONV (ksize 3): 32 zero bytes (what a tap outside the image reads);
-                                STEM: NULL, or the camera block of a pre-processing stem (avl_stem_camera_set) */
+                                STEM: NULL, or the camera block of a pre-processing stem (avl_stem_camera_set; any dtype,
+                                AVL_F32 with w_layout 0, AVL_BF16 / AVL_F16 with w_layout 1) */
     void* out;
     const void* weight;      /* packed by the host, layout per kind (see network.py)            */
     const float* bias;       /* fp32 [out_c padded], or NULL                                    */

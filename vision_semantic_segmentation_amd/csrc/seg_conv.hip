@@ -795,7 +795,9 @@ int validate_conv_op(const avl_seg_op& op) {
             AVL_REQUIRE(op.out_rows >= out_pix && op.out_ld >= 64 && (op.out_ld * es) % 16 == 0, "stem output buffer");
             AVL_REQUIRE(op.w_layout == 0 || (op.w_layout == 1 && is_half(op.dtype)), "stem weight layout %d", op.w_layout);
             if (op.in2) {      // pre-processing in the loader: `in` is the raw BGR frame [in_rows / in2_ld][in2_ld][3], in2 the camera block
-                AVL_REQUIRE(op.w_layout == 1, "the pre-processing stem is the MFMA kernel (w_layout 1)");
+                AVL_REQUIRE(is_half(op.dtype) ? op.w_layout == 1 : (op.dtype == AVL_F32 && op.w_layout == 0),
+                            "a pre-processing stem is the MFMA kernel (16-bit, w_layout 1) or the fp32 kernel (AVL_F32, w_layout 0): dtype %d, w_layout %d",
+                            op.dtype, op.w_layout);
                 AVL_REQUIRE(reinterpret_cast<uintptr_t>(op.in2) % 4 == 0, "stem camera block alignment");
                 AVL_REQUIRE(op.in2_ld > 0 && op.in_rows > 0 && op.in_rows % op.in2_ld == 0, "stem raw frame: in_rows = src_h * src_w, in2_ld = src_w");
                 const int src_w = op.in2_ld, src_h = op.in_rows / op.in2_ld, f = src_w / op.in_w;
@@ -905,6 +907,7 @@ int launch_conv_op(const avl_seg_op& op, hipStream_t s) {
     if (op.kind == AVL_OP_GCONV && op.w_layout == 1) return launch_gconv_mfma(op, s);
     if (op.kind == AVL_OP_GCONV && op.w_layout == 2) return launch_conv3x3(op, s);
     if (op.kind == AVL_OP_STEM && op.w_layout == 1) return launch_stem_mfma(op, s);
+    if (op.kind == AVL_OP_STEM && op.in2) return launch_stem_pre_f32(op, s);
     if (op.kind == AVL_OP_GEMV) {
         hipLaunchKernelGGL(k_gemv, dim3((op.out_c + 3) / 4, 1, op_batch(op)), dim3(kThreads), 0, s, static_cast<const float*>(op.in),
                            static_cast<const float*>(op.weight), op.bias, static_cast<float*>(op.out), op.out_c, op.in_c, op.relu, op.in_ld, op.out_ld);

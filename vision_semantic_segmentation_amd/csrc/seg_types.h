@@ -169,6 +169,7 @@ int validate_gconv_mfma(const avl_seg_op& op);
 int launch_conv3x3(const avl_seg_op& op, hipStream_t s);
 int validate_conv3x3(const avl_seg_op& op);
 int launch_stem_mfma(const avl_seg_op& op, hipStream_t s);
+int launch_stem_pre_f32(const avl_seg_op& op, hipStream_t s);
 int launch_dwconv_k(const avl_seg_op& op, hipStream_t s);
 int validate_dwconv_k(const avl_seg_op& op);
 int launch_dwpw(const avl_seg_op& op, hipStream_t s);

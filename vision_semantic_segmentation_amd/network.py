@@ -597,7 +597,8 @@ class SegNet(object):
                  part=None, backbone=DEFAULT_BACKBONE, batch=1, input_format="u8_hwc", **mixed_opts):
         """raw_frame = (src_h, src_w): the plan's input is the RAW BGR camera frame and the node's pre-processing
         (vision_semantic_segmentation_node.py:83-98: BGR->RGB, undistort, INTER_AREA by src_w // width) runs inside the stem's loader
-        (16-bit precisions); ``set_camera`` chooses the camera model, ``forward`` takes the raw frame.
+        (every precision: the MFMA stem, or k_stem_pre_f32 for "f32"); ``set_camera`` chooses the camera model, ``forward`` takes the
+        raw frame.
         batch = N: the plan runs N images of height x width at once (DeepLabV3Plus.forward on an N x 3 x H x W batch); every op takes
         them packed densely, image n at pixel rows [n h w, (n + 1) h w) of each activation, and computes for each exactly what the
         batch-1 plan computes.
@@ -627,8 +628,8 @@ class SegNet(object):
         self.raw_frame = None if raw_frame is None else (int(raw_frame[0]), int(raw_frame[1]))
         if self.raw_frame is not None:
             f = self.raw_frame[1] // self.W
-            if precision == "f32" or f < 1 or (self.raw_frame[0] // f, self.raw_frame[1] // f) != (self.H, self.W):
-                raise ValueError("raw_frame %r does not scale to %dx%d by an integer factor (or precision is f32)" % (self.raw_frame, self.H, self.W))
+            if f < 1 or (self.raw_frame[0] // f, self.raw_frame[1] // f) != (self.H, self.W):
+                raise ValueError("raw_frame %r does not scale to %dx%d by an integer factor" % (self.raw_frame, self.H, self.W))
         self.precision = precision
         # "mixed": f16 MFMA with split operands where the error analysis (tools/precision_study.py)
         # says a single f16 rounding is too coarse: every weight is an f16 pair hi + lo, the residual trunk, the ASPP

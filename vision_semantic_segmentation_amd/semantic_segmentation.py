@@ -99,9 +99,6 @@ class SemanticSegmentation(object):
             if self._self_check and self.precision == "mixed" and self.mixed_check is None:
                 self.check_mixed_against_f32(key[0], key[1])
             rung = self._rung if self.precision == "mixed" else self.precision
-            if rung == "f32" and raw_frame is not None:
-                raise NotImplementedError("the self-check fell back to the fp32 plan, which has no pre-processing stem: "
-                                          "use preprocess_device() + segmentation_device()")
             net = self._build(key[0], key[1], rung, raw_frame, batch, input_format)
             if getattr(self.cfg.MODEL, "HIP_GRAPH", True):
                 net.capture_graph()
@@ -252,9 +249,7 @@ class SemanticSegmentation(object):
         """The node's chain from the camera frame on (vision_semantic_segmentation_node.py:83-102) in the network's own kernels:
         uint8 BGR [H,W,3] (ndarray or CUDA tensor) -> BGR->RGB, cv2.undistort(K, dist) (skipped when None), INTER_AREA by the integer
         `factor`, normalise, network, arg-max -> uint8 CUDA tensor.  Same labels as preprocess_device() + segmentation_device(), without
-        the RGB frame in between."""
-        if self.precision == "f32":
-            raise NotImplementedError("the pre-processing stem is a 16-bit MFMA kernel; use preprocess_device() with PRECISION f32")
+        the RGB frame in between.  Every precision and every rung of the self-check's ladder has such a stem (fp32: k_stem_pre_f32)."""
         H, W = int(bgr.shape[0]), int(bgr.shape[1])
         net = self.net_for(H // factor, W // factor, raw_frame=(H, W))
         net.set_camera(K, dist)

@@ -156,8 +156,6 @@ class VisionSemanticSegmentationNode(object):
             factor = self._downscale_factor(h, w)
             if factor is None:                                   # any other IMAGE_SCALE: OpenCV's general area resize as a stand-alone kernel
                 labels = self.seg.segmentation_device(preprocess_area_device(bgr, cam, int(h * self.image_scale), int(w * self.image_scale)))
-            elif self.seg.precision == "f32":                    # no 16-bit stem: stand-alone pre-processing kernel, then the network
-                labels = self.seg.segmentation_device(preprocess_device(bgr, cam, factor))
             else:                                                # pre-processing inside the stem's loader (no RGB frame in between)
                 labels = self.seg.segmentation_device_raw(bgr, None if cam is None else cam.K, None if cam is None else cam.dist, factor)
             self.last_labels = labels

@@ -328,7 +328,8 @@ typedef struct avl_seg_op {
                                 STEM:  0 = float [7][7][3][64] (direct kernel), 1 = bf16 [4][6][16][32] (MFMA kernel)
                                 GEMM:  0 = the library picks the kernel; 1 .. 4 force one tile configuration of the 16-bit
                                        kernels (tools/bench_gemm.py: 1 = 128 x 128 two-buffer kernel, 2 = 256 x 128 ring,
-                                       3 = 256 x 256 ring, 4 = 256 x 128 on four waves); 5 is refused */
+                                       3 = 256 x 256 ring, 4 = 256 x 128 on four waves); avl_seg_plan_create
+                                       refuses any other value, and 1 .. 4 on an AVL_F32 GEMM */
     int32_t w_split;         /* "mixed" precision (AVL_F16 only): 1 = `weight` holds each folded weight as an f16 pair
                                 hi = f16(w), lo = f16(w - hi), packed per 64-wide K block in the order the kernel
                                 walks it (GEMM/DWPW: [n][K/64][hi 64 | lo 64], or [hi | lo | hi] when the input is

@@ -101,7 +101,8 @@ def test_split_gemm(case, cuda_device):
         assert torch.all(out[1] == 7.0)                                  # the low plane is not touched
 
 
-@pytest.mark.parametrize("case", [(23, 45, 128, 1, 1), (23, 45, 256, 2, 1), (30, 41, 512, 1, 2), (19, 67, 1024, 1, 4)])
+@pytest.mark.parametrize("case", [(23, 45, 128, 1, 1), (23, 45, 256, 2, 1), (30, 41, 512, 1, 2), (19, 67, 1024, 1, 4),
+                                  (23, 45, 256, 2, 2)])      # stride 2 + dilation 2: the 2-row tile (NJ = 1)
 @pytest.mark.parametrize("out_split", [False, True])
 def test_split_grouped_conv(case, out_split, cuda_device):
     import torch
@@ -628,6 +629,8 @@ def _unbundle(buf, rows, c, half):
     (17000, 1024, 1024, "fp4", "fp4", "fp4", True, True),     # trunk form, more tiles than CUs, 256-row tiles
     (34000, 1024, 256, True, None, False, False, True),       # both corrections, 128-row tiles
     (9000, 1280, 512, False, True, True, True, True),         # odd number of K macro-blocks, split residual and output
+    # 256-row tiles without an FP4 copy of the output (192 .. 256 tiles of 256 x 256): both main loops
+    (12100, 512, 1024, False, None, False, False, True), (12100, 1024, 1024, True, None, True, False, True),
 ])
 def test_mx_gemm(case, cuda_device):
     """w_split = 2: main product on f16 hi parts, corrections Q4(W lo) x Q4(x hi) [+ Q4(W hi) x Q4(x lo)] on the block-scaled

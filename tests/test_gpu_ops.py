@@ -101,6 +101,7 @@ def test_depthwise_conv(case, precision, cuda_device):
 @pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
 @pytest.mark.parametrize("case", [  # (H, W, width, stride, dilation)   groups = 32
     (23, 45, 128, 1, 1), (23, 45, 256, 2, 1), (30, 41, 512, 1, 2), (19, 67, 1024, 1, 4), (8, 8, 128, 1, 1), (5, 33, 256, 1, 4),
+    (23, 45, 256, 2, 2),           # stride 2 + dilation 2: the MFMA kernel's 2-row tile (NJ = 1)
 ])
 def test_grouped_conv(case, precision, cuda_device):
     import torch
@@ -132,6 +133,114 @@ def test_grouped_conv(case, precision, cuda_device):
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= tol * 2, "grouped conv %s %s: %.3e" % (case, precision, err)
     assert torch.all(dst[OH * OW:] == 7.0)
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("cg", [2, 4, 8, 16, 32])
+def test_grouped_conv_direct_kernel(cg, precision, cuda_device):
+    """w_layout 0 (fp32 weights [group][tap][ci][co]) in every activation type: the direct k_gconv<T, channels per group> the MFMA
+    windows replace in the 16-bit networks; stride 1 and 2, dilation 1 and 3, images that end mid-block."""
+    import torch
+    import torch.nn.functional as F
+    from vision_semantic_segmentation_amd.network import OP_GCONV
+    G = 16
+    width = G * cg
+    tdt, did, tol = _dt(precision)
+    for H, W, s, d in ((13, 21, 1, 1), (11, 17, 2, 3)):
+        g = torch.Generator().manual_seed(cg * 100 + H + s)
+        x = torch.randn((1, width, H, W), generator=g).to(tdt)
+        w = torch.randn((width, cg, 3, 3), generator=g) * (2.0 / (cg * 9)) ** 0.5
+        b = torch.randn(width, generator=g) * 0.1
+        OH, OW = (H - 1) // s + 1, (W - 1) // s + 1
+        ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=d, dilation=d, groups=G))
+        src = _nhwc_rows(x).to(cuda_device)
+        dst = torch.full(((OH * OW + 255) // 256 * 256, width), 7.0, dtype=tdt, device=cuda_device)
+        wd = w.reshape(G, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).reshape(-1).contiguous().to(cuda_device)      # [g][ky][kx][ci][co]
+        bd = b.to(cuda_device)
+        _run_plan([_spatial_op(OP_GCONV, did, src, (H, W), width, dst, (OH, OW), width, weight=wd.data_ptr(), bias=bd.data_ptr(),
+                               ksize=3, stride=s, pad=d, dil=d, groups=G, relu=1, w_layout=0)])
+        got = _from_rows(dst.cpu().double(), OH, OW, width)
+        err = float((got - ref).abs().max() / ref.abs().max())
+        assert err <= tol * 2, "direct grouped conv cg=%d %s (%d, %d, s%d, d%d): %.3e" % (cg, precision, H, W, s, d, err)
+        assert torch.all(dst[OH * OW:] == 7.0)
+
+
+@pytest.mark.parametrize("precision", ["bf16", "f16"])
+@pytest.mark.parametrize("in_format", ["u8", "f32"])
+def test_stem_direct_kernel_16bit(in_format, precision, cuda_device):
+    """The direct stem (w_layout 0: fp32 weights [7][7][3][64], fp32 FMA chain) writing a 16-bit plane, from uint8 RGB and from
+    normalised fp32 planes (AVL_IN_F32_CHW), batch 2: only the final rounding to the 16-bit type differs from float64."""
+    import torch
+    import torch.nn.functional as F
+    from vision_semantic_segmentation_amd.network import AVL_IN_F32_CHW, AVL_IN_U8_HWC, OP_STEM, AvlSegOp
+    H, W, B = 37, 50, 2
+    tdt, did, tol = _dt(precision)
+    g = torch.Generator().manual_seed(H * W)
+    img = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
+    w = torch.randn((64, 3, 7, 7), generator=g) * (2.0 / 147) ** 0.5
+    b = torch.randn(64, generator=g) * 0.1
+    mean = torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
+    xn = (img.permute(0, 3, 1, 2).float() / 255 - mean) / std                   # fp32, as the kernel normalises
+    ref = F.relu(F.conv2d(xn.double(), w.double(), b.double(), stride=2, padding=3))
+    h2, w2 = ref.shape[2:]
+    src = (img if in_format == "u8" else xn.contiguous()).to(cuda_device)
+    out = torch.full((B * h2 * w2 + 8, 64), 7.0, dtype=tdt, device=cuda_device)
+    wd, bd = w.permute(2, 3, 1, 0).reshape(-1).contiguous().to(cuda_device), b.to(cuda_device)
+    op = AvlSegOp()
+    op.kind, op.dtype, op.batch = OP_STEM, did, B
+    op.in_format = AVL_IN_U8_HWC if in_format == "u8" else AVL_IN_F32_CHW
+    op.in_, op.out, op.weight, op.bias = src.data_ptr(), out.data_ptr(), wd.data_ptr(), bd.data_ptr()
+    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = H, W, 3, 3, B * H * W
+    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = h2, w2, 64, 64, B * h2 * w2
+    op.ksize, op.stride, op.pad, op.dil, op.groups, op.relu, op.w_layout = 7, 2, 3, 1, 1, 1, 0
+    _run_plan([op])
+    oc = out.cpu()
+    got = oc[:B * h2 * w2].double().reshape(B, h2, w2, 64).permute(0, 3, 1, 2)
+    err = float((got - ref).abs().max() / ref.abs().max())
+    assert err <= tol * 2, "direct stem %s %s: %.3e" % (in_format, precision, err)
+    assert torch.all(oc[B * h2 * w2:] == 7.0)
+
+
+@pytest.mark.parametrize("side", ["in_lo", "out_lo"])
+def test_depthwise_one_side_split(side, cuda_device):
+    """AVL_OP_DWCONV 3x3 (f16) with a split input and a single-plane output, or the reverse: k_dwconv_split, against float64 of
+    what it reads (hi + lo) -- a single-plane output carries the f16 rounding, a split one keeps ~22 bits."""
+    import torch
+    import torch.nn.functional as F
+    from vision_semantic_segmentation_amd import _lib
+    from vision_semantic_segmentation_amd.network import OP_DWCONV
+    H, W, Cc, d, B = 19, 27, 128, 2, 2
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn((B, Cc, H, W), generator=g, dtype=torch.float64)
+    hi = x.to(torch.float16)
+    lo = (x - hi.double()).to(torch.float16) if side == "in_lo" else torch.zeros_like(hi)
+    w = torch.randn((Cc, 1, 3, 3), generator=g) * 0.3
+    b = torch.randn(Cc, generator=g) * 0.1
+    ref = F.relu(F.conv2d(hi.double() + lo.double(), w.double(), b.double(), padding=d, dilation=d, groups=Cc))
+    rows_in, rows_out = B * H * W, B * H * W
+    src = torch.cat([_nhwc_rows(hi[i:i + 1], 1) for i in range(B)]).to(cuda_device)
+    src_lo = torch.cat([_nhwc_rows(lo[i:i + 1], 1) for i in range(B)]).to(cuda_device)
+    dst = torch.full((2, rows_out + 16, Cc), 7.0, dtype=torch.float16, device=cuda_device)
+    wd = w.reshape(Cc, 9).t().contiguous().reshape(-1).to(cuda_device)
+    bd = b.to(cuda_device)
+    zero = torch.zeros(64, dtype=torch.uint8, device=cuda_device)
+    op = _spatial_op(OP_DWCONV, _lib.AVL_F16, src, (H, W), Cc, dst[0], (H, W), Cc, weight=wd.data_ptr(), bias=bd.data_ptr(),
+                     in2=zero.data_ptr(), ksize=3, stride=1, pad=d, dil=d, groups=Cc, relu=1, batch=B)
+    op.in_rows, op.out_rows = rows_in, rows_out
+    if side == "in_lo":
+        op.in_lo = src_lo.data_ptr()
+    else:
+        op.out_lo = dst[1].data_ptr()
+    _run_plan([op])
+    oc = dst.cpu().double()
+    got = oc[0, :rows_out] + (oc[1, :rows_out] if side == "out_lo" else 0.0)
+    got = got.reshape(B, H, W, Cc).permute(0, 3, 1, 2)
+    err = float((got - ref).abs().max() / ref.abs().max())
+    assert err <= (2 ** -11 * 1.5 if side == "in_lo" else 1e-6), "one-side split depthwise (%s): %.3e" % (side, err)
+    assert torch.all(dst[0, rows_out:] == 7.0) and torch.all(dst[1, rows_out:] == 7.0)
+    if side == "in_lo":
+        assert torch.all(dst[1] == 7.0)                                              # no low plane written
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
@@ -203,20 +312,36 @@ def test_bilinear_align_corners(case, precision, cuda_device):
     assert float(dst[:, Cc:].abs().max()) == 0.0                     # the neighbouring columns are untouched
 
 
-# w_layout 0: the library picks the kernel by shape (1 .. 4 force one tile configuration: tools/bench_gemm.py)
-@pytest.mark.parametrize("layout", [0])
+def _create_rc(ops):
+    """avl_seg_plan_create's return code (the plan, if any, is destroyed at once) and the library's message"""
+    from vision_semantic_segmentation_amd import _lib
+    from vision_semantic_segmentation_amd.network import AvlSegOp
+    plan = C.c_void_p()
+    rc = _lib.lib().avl_seg_plan_create((AvlSegOp * len(ops))(*ops), len(ops), C.byref(plan))
+    if rc == 0:
+        _lib.lib().avl_seg_plan_destroy(plan)
+    return rc, _lib.last_error()
+
+
+# w_layout 0: the library picks the kernel by shape; 1 .. 4 force one tile configuration of the 16-bit kernels (tools/bench_gemm.py):
+# 1 = k_gemm<T, 2, 2>, 2 = ring 256 x 128, 3 = ring 256 x 256 (N % 256 == 0), 4 = ring 256 x 128 on four waves.  The fp32 GEMM has
+# one configuration per shape: a forced layout is refused by avl_seg_plan_create.
+@pytest.mark.parametrize("layout", [0, 1, 2, 3, 4])
 @pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
-@pytest.mark.parametrize("case", [  # (M, K, N, residual, relu)
+@pytest.mark.parametrize("case", [  # (M, K, N, residual, relu[, rows padded to])
     (1000, 64, 128, False, True), (777, 256, 64, False, True), (2600, 128, 256, True, True), (50000, 512, 256, False, False),
     (300, 2048, 1024, True, True), (4097, 1024, 512, False, True), (65, 64, 19, False, False),
+    (1000, 64, 192, True, True),            # N > 64, N % 128 != 0: the two-buffer 128 x 128 kernel by shape
+    (300, 256, 256, False, True, 128),      # rows padded to 128 only (384 < 512): not the ring
 ])
 def test_pointwise_gemm(case, precision, layout, cuda_device):
     import torch
     from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
-    M, K, N, res, relu = case
+    M, K, N, res, relu = case[:5]
+    rows_pad = case[5] if len(case) > 5 else 256
     tdt, did, tol = _dt(precision)
     g = torch.Generator().manual_seed(M + K + N)
-    Mp, Np = (M + 255) // 256 * 256, (N + 255) // 256 * 256
+    Mp, Np = (M + rows_pad - 1) // rows_pad * rows_pad, (N + 255) // 256 * 256
     a = torch.zeros((Mp, K), dtype=tdt)
     a[:M] = torch.randn((M, K), generator=g).to(tdt)
     w = torch.zeros((Np, K), dtype=tdt)
@@ -225,13 +350,13 @@ def test_pointwise_gemm(case, precision, layout, cuda_device):
     b[:N] = torch.randn(N, generator=g)
     r = torch.randn((Mp, N), generator=g).to(tdt) if res else None
     out_f32 = N == 19                                   # the classifier writes fp32 logits
-    ref = a[:M].float() @ w[:N].float().t() + b[:N]
+    ref = a[:M].double() @ w[:N].double().t() + b[:N].double()
     if res:
-        ref = ref + r[:M].float()
+        ref = ref + r[:M].double()
     if relu:
         ref = torch.relu(ref)
     ad, wd, bd = a.to(cuda_device), w.to(cuda_device), b.to(cuda_device)
-    out = torch.full((Mp, N), 7.0, dtype=torch.float32 if out_f32 else tdt, device=cuda_device)
+    out = torch.full((Mp + 16, N), 7.0, dtype=torch.float32 if out_f32 else tdt, device=cuda_device)
     op = AvlSegOp()
     op.kind, op.dtype = OP_GEMM, did
     op.in_, op.out, op.weight, op.bias = ad.data_ptr(), out.data_ptr(), wd.data_ptr(), bd.data_ptr()
@@ -242,12 +367,94 @@ def test_pointwise_gemm(case, precision, layout, cuda_device):
     if res:
         rd = r.to(cuda_device)
         op.in2, op.in2_ld = rd.data_ptr(), N
+    if precision == "f32" and layout:
+        rc, msg = _create_rc([op])
+        assert rc != 0 and "w_layout" in msg, (rc, msg)
+        return
     _run_plan([op])
-    got = out[:M].cpu().float()
+    got = out[:M].cpu().double()
     err = float((got - ref).abs().max() / ref.abs().max())
     bar = 2e-6 * max(1, K // 64) if precision == "f32" else (tol if not out_f32 else 1e-5)
-    assert err <= bar, "gemm %s %s: %.3e" % (case, precision, err)
+    assert err <= bar, "gemm %s %s layout %d: %.3e" % (case, precision, layout, err)
     assert torch.all(out[M:] == 7.0)                    # rows past M stay untouched
+
+
+@pytest.mark.parametrize("precision,layout", [("f32", 0)] + [(p, l) for p in ("bf16", "f16") for l in range(5)])
+def test_pointwise_gemm_strided_slices(precision, layout, cuda_device):
+    """The network's GEMMs read and write channel slices of concatenation buffers: in_ld > K, out_ld > N at a column offset, a
+    residual with in2_ld > N.  Sentinel columns on both sides of the output slice and rows past M must survive."""
+    import torch
+    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
+    M, K, N = 777, 256, 256
+    in_ld, in_off, out_ld, out_off, r_ld = K + 96, 64, N + 128, 64, N + 32
+    tdt, did, tol = _dt(precision)
+    g = torch.Generator().manual_seed(11)
+    Mp = 1024
+    a = torch.full((Mp, in_ld), float("nan"), dtype=tdt)   # poison outside the input slice (rows past M are read: zeros there)
+    a[:, in_off:in_off + K] = 0
+    a[:M, in_off:in_off + K] = torch.randn((M, K), generator=g).to(tdt)
+    w = (torch.randn((N, K), generator=g) / K ** 0.5).to(tdt)
+    b = torch.randn(N, generator=g)
+    r = torch.full((Mp, r_ld), float("nan"), dtype=tdt)
+    r[:M, :N] = torch.randn((M, N), generator=g).to(tdt)
+    ref = torch.relu(a[:M, in_off:in_off + K].double() @ w.double().t() + b.double() + r[:M, :N].double())
+    ad, wd, bd, rd = a.to(cuda_device), w.to(cuda_device), b.to(cuda_device), r.to(cuda_device)
+    out = torch.full((Mp, out_ld), 7.0, dtype=tdt, device=cuda_device)
+    es = a.element_size()
+    op = AvlSegOp()
+    op.kind, op.dtype = OP_GEMM, did
+    op.in_, op.out, op.weight, op.bias = ad.data_ptr() + in_off * es, out.data_ptr() + out_off * es, wd.data_ptr(), bd.data_ptr()
+    op.in2, op.in2_ld = rd.data_ptr(), r_ld
+    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = 1, M, K, in_ld, Mp
+    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = 1, M, N, out_ld, Mp
+    op.relu, op.w_rows, op.ksize, op.stride, op.dil, op.groups, op.w_layout = 1, N, 1, 1, 1, 1, layout
+    _run_plan([op])
+    oc = out.cpu()
+    got = oc[:M, out_off:out_off + N].double()
+    err = float((got - ref).abs().max() / ref.abs().max())
+    bar = 2e-6 * (K // 64) if precision == "f32" else tol
+    assert err <= bar, "strided gemm %s layout %d: %.3e" % (precision, layout, err)
+    assert torch.all(oc[:, :out_off] == 7.0) and torch.all(oc[:, out_off + N:] == 7.0) and torch.all(oc[M:] == 7.0)
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("hw", [(13, 29), (16, 16)])
+def test_gemm_bias_per_image(hw, precision, cuda_device):
+    """bias_per_image (the ASPP projection, whose bias is each image's pooling branch): batch 3, a distinct bias per image, checked
+    per image against float64; the op runs one launch per image, so in_rows must cover the last image's whole 256-row tiles and
+    avl_seg_plan_create refuses an input one tile short."""
+    import torch
+    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
+    h, w = hw
+    m, batch, K, N = h * w, 3, 256, 256
+    rows = (batch - 1) * m + (m + 255) // 256 * 256
+    tdt, did, tol = _dt(precision)
+    g = torch.Generator().manual_seed(m + K)
+    a = torch.zeros((rows, K), dtype=tdt)
+    a[:batch * m] = torch.randn((batch * m, K), generator=g).to(tdt)
+    wt = (torch.randn((N, K), generator=g) / K ** 0.5).to(tdt)
+    bias = torch.randn((batch, N), generator=g) * 2.0
+    ad, wd, bd = a.to(cuda_device), wt.to(cuda_device), bias.to(cuda_device)
+    out = torch.full((rows + 16, N), 7.0, dtype=tdt, device=cuda_device)
+    op = AvlSegOp()
+    op.kind, op.dtype, op.batch, op.bias_per_image = OP_GEMM, did, batch, 1
+    op.in_, op.out, op.weight, op.bias = ad.data_ptr(), out.data_ptr(), wd.data_ptr(), bd.data_ptr()
+    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = h, w, K, K, rows
+    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = h, w, N, N, rows
+    op.relu, op.w_rows, op.ksize, op.stride, op.dil, op.groups = 1, N, 1, 1, 1, 1
+    short = AvlSegOp.from_buffer_copy(op)
+    short.in_rows = rows - 256
+    rc, msg = _create_rc([short])
+    assert rc != 0 and "per-image bias" in msg, (rc, msg)
+    _run_plan([op])
+    oc = out.cpu()
+    for n in range(batch):
+        ref = torch.relu(a[n * m:(n + 1) * m].double() @ wt.double().t() + bias[n].double())
+        got = oc[n * m:(n + 1) * m].double()
+        err = float((got - ref).abs().max() / ref.abs().max())
+        bar = 2e-6 * (K // 64) if precision == "f32" else tol
+        assert err <= bar, "bias_per_image image %d %s %s: %.3e" % (n, hw, precision, err)
+    assert torch.all(oc[batch * m:] == 7.0)
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f16"])

@@ -48,7 +48,10 @@ FORMS = [("f32", torch.float32), ("f16", torch.float16), ("bf16", torch.bfloat16
 OP_BAR = {"f32": 1e-5, "split": 1e-5, "f16": 1e-3, "bf16": 8e-3}
 
 
-def _run_op(form, ks, h, w, c, batch, dev, seed):
+def _run_op(form, ks, h, w, c, batch, dev, seed, in_pad=0, in_off=0, out_pad=0, out_off=0):
+    """the op alone on [batch][h][w][c] (optionally a column slice at in_off / out_off of rows in_ld = c + in_pad / out_ld = c + out_pad);
+    NaN sentinels in the output columns outside the slice and in the rows past the output, NaN poison in the input's other columns
+    and in rows past the last image.  Returns (got, ref) as float64 [batch][oh][ow][c]."""
     from vision_semantic_segmentation_amd import _lib
     from vision_semantic_segmentation_amd.network import AvlSegOp, OP_DWCONV
     dt = dict(FORMS)[form]
@@ -62,19 +65,27 @@ def _run_op(form, ks, h, w, c, batch, dev, seed):
     xin = hi.double() + (lo.double() if lo is not None else 0.0)                 # what the kernel reads
     ref = torch.relu(F.conv2d(xin.permute(0, 3, 1, 2), wt.double(), b.double(), groups=c)).permute(0, 2, 3, 1)
     rows_in, rows_out = batch * h * w, batch * oh * ow
-    d_in = hi.reshape(rows_in, c).to(dev)
-    d_in_lo = lo.reshape(rows_in, c).to(dev) if lo is not None else None
-    d_out = torch.full((rows_out, c), float("nan"), dtype=dt, device=dev)
-    d_out_lo = torch.full((rows_out, c), float("nan"), dtype=dt, device=dev) if lo is not None else None
+    in_ld, out_ld = c + in_pad, c + out_pad
+    tail = 5                                                                      # sentinel rows past the output / poison past the input
+
+    def plane(t):
+        buf = torch.full((rows_in + tail, in_ld), float("nan"), dtype=dt)
+        buf[:rows_in, in_off:in_off + c] = t.reshape(rows_in, c)
+        return buf.to(dev)
+    d_in = plane(hi)
+    d_in_lo = plane(lo) if lo is not None else None
+    d_out = torch.full((rows_out + tail, out_ld), float("nan"), dtype=dt, device=dev)
+    d_out_lo = torch.full((rows_out + tail, out_ld), float("nan"), dtype=dt, device=dev) if lo is not None else None
     d_w = wt.reshape(c, ks * ks).t().contiguous().to(dev)                         # [tap][C]
     d_b = b.to(dev)
+    es = d_in.element_size()
     op = AvlSegOp()
     op.kind, op.dtype, op.batch = OP_DWCONV, {"f32": _lib.AVL_F32, "bf16": _lib.AVL_BF16}.get(form, _lib.AVL_F16), batch
-    op.in_, op.out, op.weight, op.bias = d_in.data_ptr(), d_out.data_ptr(), d_w.data_ptr(), d_b.data_ptr()
+    op.in_, op.out, op.weight, op.bias = d_in.data_ptr() + in_off * es, d_out.data_ptr() + out_off * es, d_w.data_ptr(), d_b.data_ptr()
     if lo is not None:
-        op.in_lo, op.out_lo = d_in_lo.data_ptr(), d_out_lo.data_ptr()
-    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = h, w, c, c, rows_in
-    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = oh, ow, c, c, rows_out
+        op.in_lo, op.out_lo = d_in_lo.data_ptr() + in_off * es, d_out_lo.data_ptr() + out_off * es
+    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = h, w, c, in_ld, rows_in
+    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = oh, ow, c, out_ld, rows_out
     op.ksize, op.stride, op.pad, op.dil, op.groups, op.relu = ks, 1, 0, 1, c, 1
     plan = C.c_void_p()
     _lib.check(_lib.lib().avl_seg_plan_create((AvlSegOp * 1)(op), 1, C.byref(plan)), "avl_seg_plan_create")
@@ -83,12 +94,19 @@ def _run_op(form, ks, h, w, c, batch, dev, seed):
         torch.cuda.synchronize(dev)
     finally:
         _lib.lib().avl_seg_plan_destroy(plan)
-    got = d_out.double() + (d_out_lo.double() if lo is not None else 0.0)
+    for o in (d_out, d_out_lo):
+        if o is None:
+            continue
+        oc = o.cpu()
+        assert bool(oc[rows_out:].isnan().all()), "rows past the output written (%s k=%d)" % (form, ks)
+        assert bool(oc[:, :out_off].isnan().all()) and bool(oc[:, out_off + c:].isnan().all()), "columns outside the slice written (%s k=%d)" % (form, ks)
+    sl = slice(out_off, out_off + c)
+    got = d_out[:rows_out, sl].double() + (d_out_lo[:rows_out, sl].double() if lo is not None else 0.0)
     return got.cpu().reshape(batch, oh, ow, c), ref
 
 
 @pytest.mark.parametrize("form", [f for f, _ in FORMS])
-@pytest.mark.parametrize("ks", [1, 2, 5, 7])
+@pytest.mark.parametrize("ks", [1, 2, 4, 5, 6, 7])
 def test_kxk_op_against_float64(form, ks, cuda_device):
     for (h, w), c, batch in (((13, 29), 64, 1), ((31, 47), 320, 3), ((13, 29), 320, 3), ((31, 47), 64, 1)):
         got, ref = _run_op(form, ks, h, w, c, batch, cuda_device, seed=ks * 100 + h + c + batch)
@@ -98,11 +116,31 @@ def test_kxk_op_against_float64(form, ks, cuda_device):
         assert rel <= OP_BAR[form], (form, ks, h, w, c, batch, rel)
 
 
+@pytest.mark.parametrize("form", [f for f, _ in FORMS])
+@pytest.mark.parametrize("ks", [2, 4, 6, 7])
+def test_kxk_op_tile_edges_and_slices(form, ks, cuda_device):
+    """Geometry at the 32 x 8 output tile's edges: a 1 x 1 output, an output one pixel past a tile in both directions, a channel slice
+    of wider rows at column offsets, and a batch of 3 whose images end mid-tile (the halo must stay inside each image)."""
+    cases = (  # (out_h, out_w, c, batch, in_pad, in_off, out_pad, out_off)
+        (1, 1, 64, 1, 0, 0, 0, 0),
+        (9, 33, 64, 1, 0, 0, 0, 0),
+        (9, 33, 128, 1, 64, 64, 128, 64),
+        (11, 45, 64, 3, 64, 0, 128, 128),
+        (1, 1, 64, 3, 64, 32, 128, 64),
+    )
+    for oh, ow, c, batch, ip, io, op_, oo in cases:
+        h, w = oh + ks - 1, ow + ks - 1
+        got, ref = _run_op(form, ks, h, w, c, batch, cuda_device, seed=ks * 1000 + oh * 50 + ow + batch, in_pad=ip, in_off=io, out_pad=op_, out_off=oo)
+        assert bool(torch.isfinite(got).all()), (form, ks, oh, ow, c, batch)
+        rel = float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+        assert rel <= OP_BAR[form], (form, ks, oh, ow, c, batch, rel)
+
+
 # ------------------------------------------------------------------------------------------------ whole networks
 NET_BAR = {"f32": 1e-3, "split16": 1e-3, "mixed": 1e-3, "f16": 4e-3, "bf16": 4e-2}
 
 
-@pytest.mark.parametrize("ks", [(5, 5), (7, 7), (5, 3)], ids=["5-5", "7-7", "5-3"])
+@pytest.mark.parametrize("ks", [(5, 5), (7, 7), (5, 3), (4, 4), (6, 6), (4, 6)], ids=["5-5", "7-7", "5-3", "4-4", "6-6", "4-6"])
 def test_network_against_oracle(ks, cuda_device):
     from oracle import network_oracle as no
     st = _state(ks)
@@ -140,6 +178,18 @@ def test_batch3_equals_batch1_bit_for_bit(precision, cuda_device):
     frames = np.random.default_rng(4).integers(0, 256, size=(3, 97, 131, 3), dtype=np.uint8)
     batch = seg.logits(frames).clone()
     assert tuple(batch.shape) == (3, 19, _low(97) - 8, _low(131) - 8)
+    for i in range(3):
+        one = seg.logits(frames[i])
+        assert torch.equal(batch[i], one), (precision, i)
+
+
+@pytest.mark.parametrize("precision", ["mixed", "f32"])
+def test_batch3_equals_batch1_even_kernel(precision, cuda_device):
+    ks = (6, 6)
+    seg = _seg(precision, ks, cuda_device)
+    frames = np.random.default_rng(8).integers(0, 256, size=(3, 97, 131, 3), dtype=np.uint8)
+    batch = seg.logits(frames).clone()
+    assert tuple(batch.shape) == (3, 19, _low(97) - 10, _low(131) - 10)
     for i in range(3):
         one = seg.logits(frames[i])
         assert torch.equal(batch[i], one), (precision, i)

@@ -808,15 +808,19 @@ int validate_conv_op(const avl_seg_op& op) {
             }
             return AVL_OK;
         case AVL_OP_GEMV:
+            AVL_REQUIRE(op.dtype == AVL_F32, "gemv reads and writes fp32 vectors: dtype %d", op.dtype);
             AVL_REQUIRE(op.weight && op.in_c > 0 && op.out_c > 0, "gemv shapes");
             AVL_REQUIRE(op_batch(op) == 1 || (op.in_ld >= op.in_c && op.out_ld >= op.out_c), "batched gemv: vector strides in_ld %d / out_ld %d", op.in_ld, op.out_ld);
             return AVL_OK;
         case AVL_OP_ARGMAX:
+            AVL_REQUIRE(op.dtype == AVL_F32, "argmax reads fp32 logits: dtype %d", op.dtype);
             AVL_REQUIRE(op.in_c > 0 && op.in_c <= 256 && op.in_ld >= op.in_c && op.in_rows >= in_pix && op.out_rows >= in_pix, "argmax shapes");
             return AVL_OK;
         case AVL_OP_GAP:
+            AVL_REQUIRE(is_half(op.dtype) || op.dtype == AVL_F32, "gap dtype %d", op.dtype);
             AVL_REQUIRE(op.in2 && op.in_c % 8 == 0 && op.in_rows >= in_pix && op.in_ld >= op.in_c, "gap shapes / scratch");
             AVL_REQUIRE((op.in_ld * es) % 16 == 0, "gap in_ld");
+            AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.in) | reinterpret_cast<uintptr_t>(op.in2)) % 16 == 0, "gap input / scratch not 16-byte aligned");
             AVL_REQUIRE(op_batch(op) == 1 || op.out_ld >= op.in_c, "batched gap: out_ld %d", op.out_ld);
             return AVL_OK;
         default:

@@ -1338,6 +1338,9 @@ int validate_gemm(const avl_seg_op& op) {
     const int es = elem_size(op.dtype);
     AVL_REQUIRE(is_half(op.dtype) || op.dtype == AVL_F32, "GEMM dtype %d", op.dtype);
     AVL_REQUIRE(op.in && op.out && op.weight && op.bias, "GEMM has NULL buffers");
+    // (checked here, not only at launch: a plan that cannot run is refused when it is created)
+    AVL_REQUIRE(op.w_layout >= 0 && op.w_layout <= 4, "GEMM w_layout %d (0 = by shape, 1 .. 4 = a forced 16-bit tile configuration)", op.w_layout);
+    AVL_REQUIRE(op.w_layout == 0 || is_half(op.dtype), "GEMM w_layout %d forces a tile configuration of the 16-bit kernels: dtype %d", op.w_layout, op.dtype);
     if (op.bias_per_image && op_batch(op) > 1) {
         AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: a per-image bias is not supported by the MX GEMM");
         for (int n = 0; n < op.batch; ++n) {

@@ -293,7 +293,12 @@ int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, 
                                 weight = conv1 [n 8][ks in_c/32], in2 = the 3x3 as block-diagonal 16-channel windows [window 8][ks 5]
                                 (K = 32 = two taps x 16 channels), in3 = conv3 [wave 8][ks 4 (+ in_c/32 downsample steps)][nj 2];
                                 in3_c = 128 (the width); bias = fp32 [b1 128 | b2 128 | b3 256 (+ downsample bias)].
-                                w_split = 1 (in_c = 64 only): conv1's result keeps a lo plane in LDS (conv2 runs a third pass). */
+                                w_split = 1 (in_c = 64 only): conv1's result keeps a lo plane in LDS (conv2 runs a third pass).
+                                in_c = 512: an identity block of layer2 (width 256 -> 512 channels; in3_c = 256, w_layout = w_split = 0,
+                                weight [n 16][ks 16], in2 [window 16][ks 5], in3 [wave 8][ks 8][nj 4]; bias [b1 256 | b2 256 | b3 512]),
+                                the trunk in the MX form on both sides: in + in_mx (lo part only as FP4, in_lo NULL), out + out_mx (both
+                                halves, out_lo NULL), mx_flags = AVL_MX_IN_LO | AVL_MX_OUT_LO, in_ld = out_ld = 512.  A conv1 result beyond
+                                f16's range makes the whole tile's output non-finite (the plan's non-finite screen then names the block). */
 
 typedef struct avl_seg_op {
     int32_t kind;            /* AVL_OP_*                                                        */

@@ -595,30 +595,6 @@ struct MxArgs {
     int stagger;                // 1: waves 0-3 issue their LDS-DMAs after the first K half of a sub-step
 };
 
-// 16 values of one lane + the 16 of its partner (lane ^ 16) form one MX block: shared E8M0 scale, e2m1 elements.
-// Returns the scale byte; q[0..1] = the lane's 16 values packed (element 2i in the low nibble of byte i).
-__device__ __forceinline__ unsigned quantize_fp4_block(const float (&v)[16], unsigned (&q)[2]) {
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    {
-        // partner = lane ^ 16, i.e. the neighbouring 16-lane row: v_permlane16_swap exchanges odd and even rows at VALU speed
-        // ([0] holds rows (0,0,2,2), [1] rows (1,1,3,3)); non-negative floats order as unsigned integers
-        const unsigned ab = __float_as_uint(amax);
-        const auto r16 = __builtin_amdgcn_permlane16_swap(ab, ab, false, false);
-        amax = __uint_as_float(max(r16[0], r16[1]));
-    }
-    const unsigned sbyte = mx_fp4_scale_byte(amax);
-    const float scale = __uint_as_float(sbyte << 23);
-    q[0] = q[1] = 0u;
-#define AVL_FP4_PAIR(i)                                                                                  \
-    q[0] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q[0], v[2 * (i)], v[2 * (i) + 1], scale, (i));        \
-    q[1] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(q[1], v[8 + 2 * (i)], v[8 + 2 * (i) + 1], scale, (i))
-    AVL_FP4_PAIR(0); AVL_FP4_PAIR(1); AVL_FP4_PAIR(2); AVL_FP4_PAIR(3);
-#undef AVL_FP4_PAIR
-    return sbyte;
-}
-
 // The epilogue of an MX GEMM tile (shared by k_gemm_ring_mx and k_gemm_mx_pipe): bias is in the accumulators; residual (one or two
 // planes), ReLU, f16 hi [+ lo] planes, and the FP4 planes + scales the next MX GEMM reads.
 template <int IO, int MI>

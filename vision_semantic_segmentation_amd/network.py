@@ -429,13 +429,14 @@ def pack_bottleneck(w1, w2, w3, wd, groups):
       conv2  float64 [width][width/groups][3][3] -> block-diagonal 16-channel windows, K = 32 = two taps x 16 input channels:
              [window width/16][ks 5][hi, lo][lane][8]; K value 8 kq + j of step ks is tap 2 ks + (kq >> 1) (the tenth is zero),
              input channel (kq & 1) * 8 + j of the window
-      conv3  float64 [cout][width] (+ downsample [cout][cin] or None as extra K steps) -> [wave cout/32][ks][nj 2][hi, lo][lane][8];
-             MFMA row i of n-tile nj is output channel 32 wave + (i >> 2) * 8 + nj * 4 + (i & 3) (a lane then owns 8 consecutive channels)
+      conv3  float64 [cout][width] (+ downsample [cout][cin] or None as extra K steps) -> [wave 8][ks][nj][hi, lo][lane][8] with
+             NJ = cout / 128 n-tiles per wave (2 in layer1, 4 in layer2): MFMA row i of n-tile nj is output channel
+             16 NJ wave + (i >> 2) * 4 NJ + nj * 4 + (i & 3) (a lane then owns 4 NJ consecutive channels)
     -> three flat float16 tensors."""
     width, cin = w1.shape
     cout = w3.shape[0]
     cg = width // groups
-    assert width % 16 == 0 and cin % 32 == 0 and cout % 32 == 0 and 16 % cg == 0
+    assert width % 16 == 0 and cin % 32 == 0 and cout in (256, 512) and 16 % cg == 0
 
     def pair(m):          # [.., lane, 8] hi and lo fragments interleaved as [..][2][lane][8]
         hi, lo = split_f16(m)
@@ -452,13 +453,14 @@ def pack_bottleneck(w1, w2, w3, wd, groups):
     for ci in range(cg):
         dense[win, col, :9, gbase + ci] = wt[co, ci, :]
     p2 = pair(dense.reshape(nwin * 16, 160))                                          # K = tap * 16 + in: step ks = taps 2 ks, 2 ks + 1
-    # conv3 (+ downsample): rows permuted per 32-channel wave block
+    # conv3 (+ downsample): rows permuted per wave block of 16 NJ channels
     w3k = w3.to(torch.float64) if wd is None else torch.cat([w3.to(torch.float64), wd.to(torch.float64)], dim=1)
     i = torch.arange(16)
-    rows = torch.cat([32 * wv + (i >> 2) * 8 + nj * 4 + (i & 3) for wv in range(cout // 32) for nj in range(2)])
-    p3 = pair(w3k[rows])                                                              # [wave * 2 + nj][ks][2][64][8]
+    nj_ = cout // 128
+    rows = torch.cat([16 * nj_ * wv + (i >> 2) * 4 * nj_ + nj * 4 + (i & 3) for wv in range(8) for nj in range(nj_)])
+    p3 = pair(w3k[rows])                                                              # [wave * NJ + nj][ks][2][64][8]
     ks3 = w3k.shape[1] // 32
-    p3 = p3.reshape(cout // 32, 2, ks3, 2, 64, 8).permute(0, 2, 1, 3, 4, 5)            # [wave][ks][nj][2][64][8]
+    p3 = p3.reshape(8, nj_, ks3, 2, 64, 8).permute(0, 2, 1, 3, 4, 5)                  # [wave][ks][nj][2][64][8]
     return p1.reshape(-1).contiguous(), p2.reshape(-1).contiguous(), p3.reshape(-1).contiguous()
 
 
@@ -857,7 +859,11 @@ class SegNet(object):
         bias = self._dev(torch.cat([b1, b2, b3]), torch.float32)
         ip, ild, irows = self._view(x)
         op_, old, orows = self._view(y)
-        self._op(p, OP_BOTTLENECK, in_=ip, in_lo=self._lo(x), out=op_, out_lo=self._lo(y), weight=p1.data_ptr(), in2=p2.data_ptr(), in3=p3.data_ptr(),
+        mx = {}
+        if cin == 512:         # layer2: the MX trunk in and out (the lo parts only as FP4)
+            mx = dict(in_mx=x.mx.data_ptr(), out_mx=y.mx.data_ptr(), mx_flags=AVL_MX_IN_LO | AVL_MX_OUT_LO)
+            y.mx_valid = True
+        self._op(p, OP_BOTTLENECK, **mx, in_=ip, in_lo=self._lo(x), out=op_, out_lo=self._lo(y), weight=p1.data_ptr(), in2=p2.data_ptr(), in3=p3.data_ptr(),
                  in3_c=width, bias=bias.data_ptr(), in_h=hw[0], in_w=hw[1], in_c=cin, in_ld=ild, in_rows=irows, out_h=hw[0], out_w=hw[1],
                  out_c=cout, out_ld=old, out_rows=orows, ksize=3, stride=1, pad=1, dil=1, groups=self.groups, relu=1, w_layout=int(wd is not None),
                  w_split=int(wd is not None))
@@ -998,6 +1004,16 @@ class SegNet(object):
                     self._bottleneck(p, st, x, hw, cin, width, cout, y)
                     if x is not low:
                         self._release(x)
+                    x, hw, cin = y, ohw, cout
+                    continue
+                # layer2's identity blocks of ResNeXt-50 32x4d (width 256, 8 channels per group): one kernel each, the trunk in and out in
+                # the MX form (hi plane + FP4 copies of hi and lo) that the MX GEMMs around them write and read
+                if (self.mixed_fuse_block and li == 2 and bi > 0 and s == 1 and d == 1 and width == 256 and cout == 512 and cin == 512
+                        and groups == 32 and cg == 8 and (p + ".downsample.0.weight") not in st and x.hi.shape[1] == cin and x.lo is None
+                        and x.mx is not None and x.mx_valid and x.lo_fp4):
+                    y = self._act(ohw[0] * ohw[1], cout, split=True, mx=True, lo_fp4=True)
+                    self._bottleneck(p, st, x, hw, cin, width, cout, y)
+                    self._release(x)
                     x, hw, cin = y, ohw, cout
                     continue
                 # conv1 1x1 + bn1 + relu

@@ -17,7 +17,9 @@ Two graph-level rewrites, both exact in real arithmetic:
     (aspp.py:86-89), so its share of the 1280->256 projection is a per-channel constant:
     it becomes a bias vector computed per frame by two small GEMVs.
 """
+import collections
 import ctypes as C
+import hashlib
 import math
 
 import numpy as np
@@ -537,24 +539,22 @@ def pack_mx_weights(w):
 
 # Packed weights are a pure function of (the state dict's content, the op, the packing variant): building the plan for another image size,
 # or the five plans of the load-time self-check, repeats the float64 folding and -- far slower -- the host-side FP4 quantisation of the MX
-# bundles.  Cached on the host, keyed by a fingerprint of the state dict (not its id(): that can be reused after a free), bounded in bytes.
+# bundles.  Cached on the host, keyed by a digest of the state dict's bytes (not its id(): that can be reused after a free), bounded in bytes.
 _PACK_CACHE = {}
 _PACK_CACHE_BYTES = [0]
 PACK_CACHE_LIMIT = 3 << 30
 
 
-def state_fingerprint(state):
-    """(sum, sum of squares, number of elements) over all tensors, float64: two different weight sets do not share it"""
-    s1 = s2 = 0.0
-    n = 0
+def state_digest(state):
+    """blake2b over every floating-point tensor's key, dtype, shape and bytes, in key order: two weight sets share it only when equal
+    (a sum-based fingerprint does not tell permuted channels apart)"""
+    h = hashlib.blake2b(digest_size=16)
     for k in sorted(state):
         t = state[k]
         if torch.is_tensor(t) and t.is_floating_point():
-            t64 = t.detach().to(torch.float64)
-            s1 += float(t64.sum())
-            s2 += float((t64 * t64).sum()) * (1.0 + 1e-3 * (hash(k) % 97))
-            n += t.numel()
-    return (s1, s2, n)
+            h.update(("%s %s %s;" % (k, t.dtype, tuple(t.shape))).encode())
+            h.update(t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy())
+    return h.hexdigest()
 
 
 def _cached_pack(key, fn):
@@ -580,12 +580,29 @@ class Act(object):
     def __init__(self, hi, lo=None, pool_key=None, mx=None):
         self.hi, self.lo, self.pool_key = hi, lo, pool_key
         self.mx = mx               # uint8 MX bundle (FP4 copies + scales of hi [and lo]) for the next MX GEMM, or None
-        self.mx_valid = False      # set by the op that fills it
+        self.mx_valid = False      # set by the op that fills it (SegNet._writes_mx)
         self.lo_fp4 = False        # the lo part exists ONLY as the FP4 half of the bundle (no f16 lo plane)
 
     @property
     def shape(self):
         return self.hi.shape
+
+    def mx_ready(self, ch):
+        """holds a valid MX bundle of exactly `ch` columns: an MX GEMM can read it"""
+        return self.mx is not None and self.mx_valid and self.hi.shape[1] == ch
+
+
+def _zero_pad(t, n, dim=0):
+    """float64 t with zeros appended along `dim` up to n entries: weights and biases widened to a kernel's granule (zero output
+    channels, zero GEMM rows up to w_rows, zero input columns)"""
+    shape = list(t.shape)
+    shape[dim] = n - shape[dim]
+    return torch.cat([t.to(torch.float64), torch.zeros(shape, dtype=torch.float64)], dim=dim)
+
+
+# one Bottleneck of the layer walk: its state-dict prefix, input and output sizes, channels (in, conv1/conv2 width, out), conv2's
+# stride and dilation, whether it has a downsample, and whether its output keeps the lo plane ("mixed")
+Block = collections.namedtuple("Block", "p hw ohw cin width cout s d has_ds trunk_lo")
 
 
 class SegNet(object):
@@ -677,7 +694,7 @@ class SegNet(object):
         self.ops = []
         self.op_names = []
         self._plan = C.c_void_p()
-        self._fp = state_fingerprint(state)
+        self._fp = state_digest(state)
         # part = None: the whole network.  ("aspp", C): height x width is the FEATURE map, `state` an ASPP module's state dict ("aspp." keys);
         # ("decoder", C_feature, C_low): height x width the feature map, the low-level map twice that -- sub-plans for the tests that compare
         # the HIP kernels with the reference MODULES' outputs (tests/golden/net_aspp256.pt, net_decoder256.pt)
@@ -772,41 +789,46 @@ class SegNet(object):
         """pointer to column `col` of an Act's low plane (0 = the activation is a single plane)"""
         return 0 if (not isinstance(a, Act) or a.lo is None) else a.lo.data_ptr() + col * a.lo.element_size()
 
-    def _gemm(self, name, src, hw, cin, w, b, dst, dst_col=0, relu=True, res=None, out_f32=False, src_col=0, bias_dev=None,
+    def _mx_gemm(self, src, cin, cout):
+        """Does a 1x1 conv of cin -> cout channels run as an MX GEMM (the f16 product plus its corrections on the block-scaled FP4 matrix
+        cores)?  It does in the MX mode, for K and N multiples of 256, when its input `src` holds a valid MX bundle of exactly cin columns.
+        src = None asks ahead of time, for an input still to be written: would it, given the bundle?"""
+        return self.mixed_mx and cin % 256 == 0 and cout % 256 == 0 and (src is None or (isinstance(src, Act) and src.mx_ready(cin)))
+
+    @staticmethod
+    def _writes_mx(dst, cout, dst_col=0, flags=0):
+        """mx_flags (`flags`: the op's other AVL_MX_* bits) and out_mx of an op able to fill an MX bundle that writes cout columns of dst
+        from column dst_col: where dst has a bundle of exactly those columns the op fills it, which makes it valid for the next MX GEMM"""
+        if isinstance(dst, Act) and dst.mx is not None and dst_col == 0 and dst.hi.shape[1] == cout:
+            dst.mx_valid = True
+            return dict(out_mx=dst.mx.data_ptr(), mx_flags=flags | (AVL_MX_OUT_LO if dst.lo_fp4 else 0))
+        return dict(mx_flags=flags)
+
+    def _gemm(self, name, src, hw, cin, w, b, dst, dst_col=0, relu=True, res=None, out_f32=False, bias_dev=None,
               read_lo=True, src2=None, w2=None, b2=None, labels=None, bias_per_image=False):
         """1x1 conv.  w float64 [cout][cin] (BN folded), b float64 [cout].  "mixed": weights become f16 pairs; the low
         plane of `src` is read if it has one (unless read_lo = False), `res` and `dst` are used with all the planes they have."""
         h, wd = hw
         cout = w.shape[0]
         w_rows = _round_up(cout, 256)
-        wp = torch.zeros((w_rows, cin), dtype=torch.float64)
-        wp[:cout] = w.reshape(cout, cin)
+        wp = _zero_pad(w.reshape(cout, cin), w_rows)
         if src2 is not None:          # a second input appended along K (MX GEMM only): conv3 + downsample in one product
-            cin2 = w2.shape[1]
-            wp2 = torch.zeros((w_rows, cin2), dtype=torch.float64)
-            wp2[:cout] = w2.reshape(cout, cin2)
-            wp = torch.cat([wp, wp2], dim=1)
+            wp = torch.cat([wp, _zero_pad(w2, w_rows)], dim=1)
             b = b + b2
-        in_lo = self._lo(src, src_col) if (self.mixed and read_lo) else 0
-        use_mx = (self.mixed_mx and isinstance(src, Act) and src.mx is not None and src.mx_valid and src_col == 0 and not out_f32
-                  and cin % 256 == 0 and cout % 256 == 0 and src.hi.shape[1] == cin)
+        in_lo = self._lo(src) if (self.mixed and read_lo) else 0
+        use_mx = not out_f32 and self._mx_gemm(src, cin, cout)
         assert src2 is None or use_mx, "%s: a second input needs the MX GEMM" % name
-        w_mx = None
         if use_mx:
             whi, bundle = _cached_pack((self._fp, self.backbone, name, "mx", tuple(wp.shape)), lambda: pack_mx_weights(wp))
-            wdev = self._dev(whi, torch.float16)
-            w_mx = bundle.to(self.device)
-            self._keep.append(w_mx)
+            wdev, w_mx = self._dev(whi, torch.float16), self._dev(bundle, torch.uint8)
         elif self.mixed:
             nsub = 3 if in_lo else 2
             wdev = self._dev(_cached_pack((self._fp, self.backbone, name, "split", nsub, tuple(wp.shape)), lambda: pack_split_rows(wp, nsub)), torch.float16)
         else:
             wdev = self._dev(wp, self.act_dtype)
         if bias_dev is None:
-            bp = torch.zeros(w_rows, dtype=torch.float64)
-            bp[:cout] = b
-            bias_dev = self._dev(bp, torch.float32)
-        ip, ild, irows = self._view(src, src_col)
+            bias_dev = self._dev(_zero_pad(b, w_rows), torch.float32)
+        ip, ild, irows = self._view(src)
         op_, old, orows = self._view(dst, dst_col)
         f = dict(in_=ip, out=op_, weight=wdev.data_ptr(), bias=bias_dev.data_ptr(), in_h=h, in_w=wd, in_c=cin, in_ld=ild,
                  in_rows=irows, out_h=h, out_w=wd, out_c=cout, out_ld=old, out_rows=orows, relu=int(relu), out_f32=int(out_f32),
@@ -815,28 +837,21 @@ class SegNet(object):
             rp, rld, _ = self._view(res)
             f.update(in2=rp, in2_ld=rld)
         if self.mixed:
-            f.update(w_split=1, in_lo=in_lo, out_lo=self._lo(dst, dst_col), in2_lo=self._lo(res) if res is not None else 0)
-        flags = 0
+            f.update(w_split=1, in_lo=in_lo, out_lo=self._lo(dst, dst_col), in2_lo=self._lo(res))
         if use_mx:
+            flags = AVL_MX_IN_LO if (src.lo_fp4 and read_lo) else 0
             f.update(w_split=2, w_mx=w_mx.data_ptr(), in_mx=src.mx.data_ptr())
-            if src.lo_fp4 and read_lo:
-                flags |= AVL_MX_IN_LO
             if src2 is not None:
-                assert src2.mx_valid and src2.lo_fp4 == src.lo_fp4 and src2.lo is None and src.lo is None
+                assert src2.mx_ready(w2.shape[1]) and src2.lo_fp4 == src.lo_fp4 and src2.lo is None and src.lo is None
                 f.update(in3=src2.hi.data_ptr(), in3_mx=src2.mx.data_ptr(), in3_c=src2.hi.shape[1], in3_ld=src2.hi.shape[1])
             if isinstance(res, Act) and res.lo_fp4:
                 f.update(in2_mx=res.mx.data_ptr())
                 flags |= AVL_MX_RES_LO
-            if isinstance(dst, Act) and dst.mx is not None and dst_col == 0 and dst.hi.shape[1] == cout:
-                f.update(out_mx=dst.mx.data_ptr())
-                dst.mx_valid = True
-                if dst.lo_fp4:
-                    flags |= AVL_MX_OUT_LO
+            f.update(self._writes_mx(dst, cout, dst_col, flags))
         else:
             for t_, what in ((src if read_lo else None, "input"), (res, "residual"), (dst, "output")):
                 if isinstance(t_, Act) and t_.lo_fp4:
                     raise RuntimeError("%s: the %s keeps its lo part as FP4 only, which needs the MX GEMM" % (name, what))
-        f["mx_flags"] = flags
         if labels is not None:
             assert out_f32 and not use_mx and res is None and not relu
             f["out_mx"] = labels.data_ptr()
@@ -845,13 +860,15 @@ class SegNet(object):
             f["bias_per_image"] = 1
         self._op(name, OP_GEMM, **f)
 
-    def _bottleneck(self, p, st, x, hw, cin, width, cout, y):
-        """One Bottleneck (stride 1, dilation 1) as AVL_OP_BOTTLENECK: BN folded, weights as f16 pairs in fragment order."""
+    def _bottleneck(self, st, blk, x, y):
+        """One Bottleneck (stride 1, dilation 1) as AVL_OP_BOTTLENECK: BN folded, weights as f16 pairs in fragment order.  A trunk in the
+        MX form (layer2: the lo part only as FP4) is read and written in that form."""
+        p, cin, width, cout = blk.p, blk.cin, blk.width, blk.cout
         w1, b1 = fold_bn(st, p + ".conv1.weight", p + ".bn1")
         w2, b2 = fold_bn(st, p + ".conv2.weight", p + ".bn2")
         w3, b3 = fold_bn(st, p + ".conv3.weight", p + ".bn3")
         wd = None
-        if (p + ".downsample.0.weight") in st:
+        if blk.has_ds:
             wd, bd = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
             wd, b3 = wd.reshape(cout, cin), b3 + bd
         p1, p2, p3 = (self._dev(t, torch.float16) for t in _cached_pack(
@@ -859,12 +876,9 @@ class SegNet(object):
         bias = self._dev(torch.cat([b1, b2, b3]), torch.float32)
         ip, ild, irows = self._view(x)
         op_, old, orows = self._view(y)
-        mx = {}
-        if cin == 512:         # layer2: the MX trunk in and out (the lo parts only as FP4)
-            mx = dict(in_mx=x.mx.data_ptr(), out_mx=y.mx.data_ptr(), mx_flags=AVL_MX_IN_LO | AVL_MX_OUT_LO)
-            y.mx_valid = True
+        mx = dict(in_mx=x.mx.data_ptr(), **self._writes_mx(y, cout, flags=AVL_MX_IN_LO)) if x.lo_fp4 else {}
         self._op(p, OP_BOTTLENECK, **mx, in_=ip, in_lo=self._lo(x), out=op_, out_lo=self._lo(y), weight=p1.data_ptr(), in2=p2.data_ptr(), in3=p3.data_ptr(),
-                 in3_c=width, bias=bias.data_ptr(), in_h=hw[0], in_w=hw[1], in_c=cin, in_ld=ild, in_rows=irows, out_h=hw[0], out_w=hw[1],
+                 in3_c=width, bias=bias.data_ptr(), in_h=blk.hw[0], in_w=blk.hw[1], in_c=cin, in_ld=ild, in_rows=irows, out_h=blk.hw[0], out_w=blk.hw[1],
                  out_c=cout, out_ld=old, out_rows=orows, ksize=3, stride=1, pad=1, dil=1, groups=self.groups, relu=1, w_layout=int(wd is not None),
                  w_split=int(wd is not None))
 
@@ -877,12 +891,9 @@ class SegNet(object):
         oh, ow = h + 2 * padding - 2 * dilation, wd + 2 * padding - 2 * dilation
         cout = w_pw.shape[0]
         w_rows = _round_up(cout, 256)
-        wp = torch.zeros((w_rows, cin), dtype=torch.float64)
-        wp[:cout] = w_pw.reshape(cout, cin)
-        bp = torch.zeros(w_rows, dtype=torch.float64)
-        bp[:cout] = b_pw
+        wp = _zero_pad(w_pw.reshape(cout, cin), w_rows)
         wdev = self._dev(pack_split_rows(wp, 2), torch.float16) if self.mixed else self._dev(wp, self.act_dtype)
-        bdev = self._dev(bp, torch.float32)
+        bdev = self._dev(_zero_pad(b_pw, w_rows), torch.float32)
         exact = self.mixed and self.mixed_dw_exact
         # exact: fp32 depthwise weights (w_split 3), the depthwise result as a split tile; a split input (hi + lo planes) exists in this form
         # only (k_dwpw_xs), its stride-1 case (the decoder) walks 8 x 16-pixel blocks
@@ -892,52 +903,69 @@ class SegNet(object):
         params = torch.cat([dwp, dwpw_block_order(oh, ow) if blocks else dwpw_tile_order(oh, ow, dilation)]).to(self.device)
         self._keep.append(params)
         ip, ild, irows = self._view(src)
+        f = dict(in_=ip, in_lo=in_lo, in2=params.data_ptr(), weight=wdev.data_ptr(), bias=bdev.data_ptr(), in_h=h, in_w=wd, in_c=cin, in_ld=ild,
+                 in_rows=irows, out_h=oh, out_w=ow, out_c=cout, relu=1, w_rows=w_rows, ksize=3, stride=1, pad=padding, dil=dilation, groups=cin,
+                 w_split=(3 if exact else int(self.mixed)), w_layout=int(blocks))
         if classifier is not None:
             wc, bc, logits, labels = classifier
             ncls = wc.shape[0]
             assert in_lo and cout == 256 and ncls <= 32 and wc.shape[1] == cout
-            wc32 = torch.zeros((32, cout), dtype=torch.float64)
-            wc32[:ncls] = wc
-            bc32 = torch.zeros(32, dtype=torch.float64)
-            bc32[:ncls] = bc
-            wcd = self._dev(torch.stack(split_f16(wc32)), torch.float16)           # [hi | lo][32][cout]
-            bcd = self._dev(bc32, torch.float32)
-            self._op(name, OP_DWPW, in_=ip, in_lo=in_lo, in2=params.data_ptr(), in2_lo=bcd.data_ptr(), in3=wcd.data_ptr(), in3_c=ncls, out=logits.data_ptr(),
-                     out_mx=labels.data_ptr(), out_f32=1, weight=wdev.data_ptr(), bias=bdev.data_ptr(), in_h=h, in_w=wd, in_c=cin, in_ld=ild, in_rows=irows,
-                     out_h=oh, out_w=ow, out_c=cout, out_ld=ncls, out_rows=logits.shape[0], relu=1, w_rows=w_rows, ksize=3, stride=1, pad=padding,
-                     dil=dilation, groups=cin, w_split=3, w_layout=int(blocks))
-            return
-        op_, old, orows = self._view(dst, dst_col)
-        self._op(name, OP_DWPW, in_=ip, in_lo=in_lo, in2=params.data_ptr(), out=op_, weight=wdev.data_ptr(), bias=bdev.data_ptr(), in_h=h, in_w=wd,
-                 in_c=cin, in_ld=ild, in_rows=irows, out_h=oh, out_w=ow, out_c=cout, out_ld=old, out_rows=orows, relu=1, w_rows=w_rows,
-                 ksize=3, stride=1, pad=padding, dil=dilation, groups=cin, w_split=(3 if exact else int(self.mixed)), w_layout=int(blocks),
-                 out_lo=self._lo(dst, dst_col) if self.mixed else 0)
+            wcd = self._dev(torch.stack(split_f16(_zero_pad(wc, 32))), torch.float16)           # [hi | lo][32][cout]
+            bcd = self._dev(_zero_pad(bc, 32), torch.float32)
+            f.update(in2_lo=bcd.data_ptr(), in3=wcd.data_ptr(), in3_c=ncls, out=logits.data_ptr(), out_mx=labels.data_ptr(), out_f32=1, out_ld=ncls,
+                     out_rows=logits.shape[0])
+        else:
+            op_, old, orows = self._view(dst, dst_col)
+            f.update(out=op_, out_ld=old, out_rows=orows, out_lo=self._lo(dst, dst_col) if self.mixed else 0)
+        self._op(name, OP_DWPW, **f)
 
-    def _spatial(self, name, kind, src, in_hw, cin, dst, out_hw, cout, weight=None, bias=None, dst_col=0, **extra):
+    def _spatial(self, name, kind, src, in_hw, cin, dst, out_hw, cout, weight=None, bias=None, **extra):
+        """an op from src to dst (Acts -- their hi planes -- or tensors); `extra`: its other fields, lo planes and MX fields included"""
         ip, ild, irows = self._view(src)
-        op_, old, orows = self._view(dst, dst_col)
+        op_, old, orows = self._view(dst)
         f = dict(in_=ip, out=op_, in_h=in_hw[0], in_w=in_hw[1], in_c=cin, in_ld=ild, in_rows=irows, out_h=out_hw[0],
                  out_w=out_hw[1], out_c=cout, out_ld=old, out_rows=orows)
         if weight is not None:
             f["weight"] = weight.data_ptr()
         if bias is not None:
             f["bias"] = bias.data_ptr()
-        if self.mixed and kind in (OP_BILINEAR, OP_DWCONV, OP_GCONV):
-            f["out_lo"] = self._lo(dst, dst_col)
-            if kind != OP_GCONV:
-                f["in_lo"] = self._lo(src)
-            if (isinstance(dst, Act) and dst.mx is not None and dst_col == 0
-                    and ((kind == OP_GCONV and extra.get("w_layout") == 1) or (kind == OP_DWCONV and f.get("in_lo")))):
-                f["out_mx"] = dst.mx.data_ptr()
-                dst.mx_valid = True
-                if dst.lo_fp4:
-                    f["mx_flags"] = AVL_MX_OUT_LO
-        f["mx_flags"] = f.get("mx_flags", 0) | extra.pop("mx_flags", 0)
         f.update(extra)
         self._op(name, kind, **f)
 
     # -------------------------------------------------------------------------------- the network
     def _build(self, st):
+        x, hw = self._emit_stem(st)
+        # ---- layer1..4 (torchvision _make_layer); replace_stride_with_dilation (backbone/build.py:11-16): OS8 (False, True, True),
+        # OS16 (False, False, True)
+        dilated = (False, False, True, True) if self.output_stride == 8 else (False, False, False, True)
+        cin, dilation, low = 64, 1, None
+        for li, (planes, nblocks, stride, dilate) in enumerate(zip(PLANES, self.layers, (1, 2, 2, 2), dilated), start=1):
+            width = int(planes * (self.width_per_group / 64.0)) * self.groups
+            cg = width // self.groups
+            # conv2 routes by channels per group: <= 32 and dividing 32 -> the block-diagonal window kernels (w_layout 1, or the direct
+            # fp32 kernel); a multiple of 64 -> the dense implicit-GEMM kernel (w_layout 2, every precision, no MX-FP4 variant)
+            assert cg % 64 == 0 or (cg <= 32 and 32 % cg == 0), "%s: %d channels per group" % (self.backbone, cg)
+            previous_dilation = dilation
+            if dilate:
+                dilation, stride = dilation * stride, 1
+            for bi in range(nblocks):
+                s, d = (stride, previous_dilation) if bi == 0 else (1, dilation)
+                p = "backbone.layer%d.%d" % (li, bi)
+                ohw = ((hw[0] - 1) // s + 1, (hw[1] - 1) // s + 1)              # conv2: 3x3, pad = dilation
+                # layer1_lo = False: of layer1's blocks only the last keeps the lo plane of its output
+                trunk_lo = self.mixed_layer1_lo or li != 1 or bi == nblocks - 1
+                blk = Block(p, hw, ohw, cin, width, planes * EXPANSION, s, d, (p + ".downsample.0.weight") in st, trunk_lo)
+                y = self._emit_block(st, blk, x)
+                if x is not low:              # layer1's output stays alive for the decoder
+                    self._release(x)
+                x, hw, cin = y, ohw, blk.cout
+            if li == 1:
+                low, low_hw, low_c = x, hw, cin           # low_features = layer1 output (resnet.py:33-34)
+        aspp, aspp_out = self._emit_aspp(st, x, hw, cin)
+        self._emit_decoder(st, aspp, hw, aspp_out, low, low_hw, low_c)
+
+    def _emit_stem(self, st):
+        """the plan's input buffers, conv1 7x7 s2 + bn1 + relu (resnet.py:25-27) and the max-pool (:28) -> (output Act, its size)"""
         H, W = self.H, self.W
         dev = self.device
         # the plan's input: the RGB network input, or the raw BGR camera frame when the stem pre-processes
@@ -949,7 +977,6 @@ class SegNet(object):
         self.camera_block = torch.zeros(64, dtype=torch.uint8, device=dev)       # AVL_STEM_CAMERA_BYTES: zeros = no undistortion
         self._keep += [self.image, self.zero_page, self.camera_block]
 
-        # ---- stem: conv1 7x7 s2 + bn1 + relu (resnet.py:25-27), maxpool (:28)
         h2, w2 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         w, b = fold_bn(st, "backbone.conv1.weight", "backbone.bn1")
         if self.full_split:         # f16 pairs: the hi parts' fragments, then the lo parts'
@@ -969,165 +996,142 @@ class SegNet(object):
         h4, w4 = (h2 + 2 - 3) // 2 + 1, (w2 + 2 - 3) // 2 + 1
         x = self._act(h4 * w4, 64, split=self.full_split)
         self._spatial("backbone.maxpool", OP_MAXPOOL, stem, (h2, w2), 64, x, (h4, w4), 64, ksize=3, stride=2, pad=1, dil=1,
-                      **(dict(in_lo=self._lo(stem), out_lo=self._lo(x)) if self.full_split else {}))
+                      in_lo=self._lo(stem), out_lo=self._lo(x))
         self._release(stem)
+        return x, (h4, w4)
 
-        # ---- layer1..4 (torchvision _make_layer, replace_stride_with_dilation = (False, True, True))
-        hw, cin = (h4, w4), 64
-        dilation = 1
-        low = None
-        # replace_stride_with_dilation (backbone/build.py:11-16): OS8 (False, True, True), OS16 (False, False, True)
-        dilated = (False, False, True, True) if self.output_stride == 8 else (False, False, False, True)
-        groups = self.groups
-        for li, (planes, nblocks, stride0, dilate) in enumerate(zip(PLANES, self.layers, (1, 2, 2, 2), dilated), start=1):
-            width = int(planes * (self.width_per_group / 64.0)) * groups
+    def _emit_block(self, st, blk, x):
+        """one Bottleneck -> its output Act (the caller releases x)"""
+        route = self._fused_route(blk, x)
+        if route is None:
+            return self._emit_block_unfused(st, blk, x)
+        # layer2's form keeps the trunk in the MX form (hi plane + FP4 copies of hi and lo) that the MX GEMMs around it write and read
+        mx = route == "layer2"
+        y = self._act(blk.ohw[0] * blk.ohw[1], blk.cout, split=blk.trunk_lo, mx=mx, lo_fp4=mx)
+        self._bottleneck(st, blk, x, y)
+        return y
+
+    def _fused_route(self, blk, x):
+        """Which form of AVL_OP_BOTTLENECK (the whole block as one kernel, both intermediates in LDS) runs the block, for ResNeXt-50 32x4d:
+        "layer1" (width 128, 256 output channels; the input a single f16 plane, or the split trunk), "layer2" (its identity blocks: width 256,
+        cin = cout = 512; the trunk in and out in the MX form), or None: the three-launch form."""
+        if not (self.mixed_fuse_block and blk.s == 1 and blk.d == 1 and self.groups == 32 and x.hi.shape[1] == blk.cin):
+            return None
+        cg = blk.width // self.groups
+        if (blk.width == 128 and blk.cout == 256 and blk.cin in (64, 256) and 16 % cg == 0 and blk.has_ds == (blk.cin == 64)
+                and (blk.cin == 256 or x.lo is None)):
+            return "layer1"
+        if blk.width == 256 and blk.cout == 512 and blk.cin == 512 and cg == 8 and not blk.has_ds and x.lo_fp4 and x.mx_ready(blk.cin):
+            return "layer2"
+        return None
+
+    def _emit_block_unfused(self, st, blk, x):
+        """one Bottleneck as three launches -- conv1 1x1, conv2 grouped 3x3, conv3 1x1 + the identity path -- -> its output Act"""
+        p, hw, ohw, cin, width, cout = blk.p, blk.hw, blk.ohw, blk.cin, blk.width, blk.cout
+        dense = (width // self.groups) % 64 == 0
+        # conv1 1x1 + bn1 + relu.  A split GEMM output needs N % 128 (the ring GEMM): the 64-wide conv1 of the ResNets' layer1 writes 64 zero
+        # channels more, which conv2 does not read (its input is a channel slice of t1)
+        w, b = fold_bn(st, p + ".conv1.weight", p + ".bn1")
+        t1_c = _round_up(width, 128) if self.full_split else width
+        # where conv1 runs as an MX GEMM its output keeps FP4 copies of both parts (the lo part only so): the grouped conv
+        # then corrects for the rounding of conv1's output too -- the largest single error term otherwise
+        conv1_mx = self.mixed_gconv_mx and not dense and self._mx_gemm(x, cin, t1_c)
+        t1 = self._act(hw[0] * hw[1], t1_c, split=self.full_split, mx=conv1_mx, lo_fp4=conv1_mx)
+        self._gemm(p + ".conv1", x, hw, cin, _zero_pad(w, t1_c), _zero_pad(b, t1_c), t1, read_lo=self.mixed_conv1_split)
+        # conv2 3x3 grouped + bn2 + relu
+        wg, bg, conv2 = self._conv2_weights(st, blk, t1, dense)
+        # (conv3 as an MX GEMM reads the 3x3 output's lo part only through its FP4 copy: no f16 lo plane then)
+        t2_fp4 = self.mixed_conv2_split and self.mixed_trunk_fp4 and conv2["w_layout"] == 1 and self._mx_gemm(None, width, cout)
+        # (the dense kernel writes no MX bundle: conv3 then takes the non-MX split GEMM, as in full_split)
+        t2 = self._act(ohw[0] * ohw[1], width, split=self.mixed_conv2_split, mx=not dense, lo_fp4=t2_fp4)
+        conv2.update(ksize=3, pad=blk.d, dil=blk.d, groups=self.groups, relu=1, in_lo=self._lo(t1))
+        if self.full_split:
+            assert conv2["w_layout"] in (1, 2) and conv2["w_split"] == 1 and t1.lo is not None, "full_split needs the MFMA grouped conv with split weights"
+        if self.full_split and blk.s != 1 and not dense:
+            # The window kernel keeps two input tiles in LDS; at stride 2 they do not fit with a lo plane beside the hi plane.  So the one
+            # strided window conv of full_split (layer2.0) runs at stride 1 and its result is sub-sampled (pad 1: out(y, x) = out1(2 y, 2 x)).
+            t2f = self._act(hw[0] * hw[1], width, split=True)
+            self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2f, hw, width, wg, bg, stride=1, out_lo=self._lo(t2f), **conv2)
+            self._spatial(p + ".conv2.sub", OP_SUBSAMPLE, t2f, hw, width, t2, ohw, width, stride=blk.s)
+            self._spatial(p + ".conv2.sub[lo]", OP_SUBSAMPLE, t2f.lo, hw, width, t2.lo, ohw, width, stride=blk.s)
+            self._release(t2f)
+        else:
+            conv2.update(self._writes_mx(t2, width, flags=conv2.get("mx_flags", 0)))
+            self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2, ohw, width, wg, bg, stride=blk.s, out_lo=self._lo(t2), **conv2)
+        self._release(t1)
+        idn = self._emit_identity(st, blk, x, t2)
+        # conv3 1x1 + bn3 + residual + relu.  Where it runs as an MX GEMM the trunk keeps its lo part only as FP4 (3 instead of 5 bytes per
+        # element move through conv3's epilogue, which is what bounds it: the 10 % error of FP4 hits a term that is 2^-11 of the sum)
+        w, b = fold_bn(st, p + ".conv3.weight", p + ".bn3")
+        trunk_fp4 = self.mixed_trunk_fp4 and self._mx_gemm(t2, width, cout)
+        y = self._act(ohw[0] * ohw[1], cout, split=self.mixed and blk.trunk_lo, mx=True, lo_fp4=trunk_fp4)
+        if idn is None:
+            wd, bd = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
+            self._gemm(p + ".conv3+downsample", t2, ohw, width, w, b, y, relu=True, src2=x, w2=wd.reshape(cout, cin), b2=bd)
+        else:
+            self._gemm(p + ".conv3", t2, ohw, width, w, b, y, relu=True, res=idn)
+        self._release(t2)
+        if idn is not x and idn is not None:
+            self._release(idn)
+        return y
+
+    def _conv2_weights(self, st, blk, t1, dense):
+        """conv2 (grouped 3x3 + bn2) of a three-launch block -> (packed weights, bias, the op's w_layout / w_split and MX fields):
+          dense (>= 64 channels per group)  the implicit-GEMM kernel (w_layout 2); "mixed": f16 pairs
+          t1 holds an MX bundle             block-diagonal windows, f16 hi fragments + FP4 corrections of weights and input (w_split 2)
+          16-bit activations                block-diagonal windows (w_layout 1); "mixed": 18 taps = 9 hi + 9 lo per window and n-tile
+          otherwise                         the direct fp32 kernel (w_layout 0)"""
+        p, width, groups = blk.p, blk.width, self.groups
+        w, b = fold_bn(st, p + ".conv2.weight", p + ".bn2")
+        key = (self._fp, self.backbone, p + ".conv2")
+        f = dict(w_split=int(self.mixed))
+        if dense:
+            if self.mixed:
+                wg = self._dev(_cached_pack(key + ("dense_split",), lambda: pack_conv3x3(w, groups, 8, split=True)), torch.float16)
+            else:
+                wg = self._dev(_cached_pack(key + ("dense", self.half), lambda: pack_conv3x3(w, groups, 8 if self.half else 4)), self.act_dtype)
+            f["w_layout"] = 2
+        elif t1.mx_ready(width):
+            frag_hi, bundle = _cached_pack(key + ("gconv_mx",), lambda: pack_gconv_mx(w, groups))
+            wg, wb = self._dev(frag_hi.reshape(-1), torch.float16), self._dev(bundle, torch.uint8)
+            f.update(w_layout=1, w_split=2, w_mx=wb.data_ptr(), in_mx=t1.mx.data_ptr(), mx_flags=AVL_MX_IN_LO)
+        elif self.half and width % 64 == 0:
+            if self.mixed:
+                nwin = width // 32
+                wg = self._dev(torch.cat([pack_gconv_windows(part.to(torch.float64), groups).reshape(nwin, 2, 9, 16, 32) for part in split_f16(w)],
+                                         dim=2).reshape(-1), torch.float16)
+            else:
+                wg = self._dev(pack_gconv_windows(w, groups), self.act_dtype)
+            f["w_layout"] = 1
+        else:
             cg = width // groups
-            # conv2 routes by channels per group: <= 32 and dividing 32 -> the block-diagonal window kernels (w_layout 1, or the direct
-            # fp32 kernel); a multiple of 64 -> the dense implicit-GEMM kernel (w_layout 2, every precision, no MX-FP4 variant)
-            dense = cg % 64 == 0
-            assert dense or (cg <= 32 and 32 % cg == 0), "%s: %d channels per group" % (self.backbone, cg)
-            cout = planes * EXPANSION
-            previous_dilation = dilation
-            stride = stride0
-            if dilate:
-                dilation *= stride
-                stride = 1
-            for bi in range(nblocks):
-                p = "backbone.layer%d.%d" % (li, bi)
-                trunk_lo = self.mixed_layer1_lo or li != 1 or bi == nblocks - 1      # does this block's output keep its lo plane
-                s = stride if bi == 0 else 1
-                d = previous_dilation if bi == 0 else dilation
-                ohw = ((hw[0] + 2 * d - 2 * d - 1) // s + 1, (hw[1] + 2 * d - 2 * d - 1) // s + 1)
-                if (self.mixed_fuse_block and s == 1 and d == 1 and width == 128 and cout == 256 and cin in (64, 256) and groups == 32 and 16 % cg == 0
-                        and ((p + ".downsample.0.weight") in st) == (cin == 64) and x.hi.shape[1] == cin and (cin == 256 or x.lo is None)):
-                    y = self._act(ohw[0] * ohw[1], cout, split=trunk_lo)
-                    self._bottleneck(p, st, x, hw, cin, width, cout, y)
-                    if x is not low:
-                        self._release(x)
-                    x, hw, cin = y, ohw, cout
-                    continue
-                # layer2's identity blocks of ResNeXt-50 32x4d (width 256, 8 channels per group): one kernel each, the trunk in and out in
-                # the MX form (hi plane + FP4 copies of hi and lo) that the MX GEMMs around them write and read
-                if (self.mixed_fuse_block and li == 2 and bi > 0 and s == 1 and d == 1 and width == 256 and cout == 512 and cin == 512
-                        and groups == 32 and cg == 8 and (p + ".downsample.0.weight") not in st and x.hi.shape[1] == cin and x.lo is None
-                        and x.mx is not None and x.mx_valid and x.lo_fp4):
-                    y = self._act(ohw[0] * ohw[1], cout, split=True, mx=True, lo_fp4=True)
-                    self._bottleneck(p, st, x, hw, cin, width, cout, y)
-                    self._release(x)
-                    x, hw, cin = y, ohw, cout
-                    continue
-                # conv1 1x1 + bn1 + relu
-                w, b = fold_bn(st, p + ".conv1.weight", p + ".bn1")
-                # where conv1 runs as an MX GEMM its output keeps FP4 copies of both parts (the lo part only so): the grouped conv
-                # then corrects for the rounding of conv1's output too -- the largest single error term otherwise
-                conv1_mx = (self.mixed_mx and self.mixed_gconv_mx and x.mx is not None and x.mx_valid and x.hi.shape[1] == cin
-                            and cin % 256 == 0 and width % 256 == 0 and not dense and 32 % cg == 0)
-                # a split GEMM output needs N % 128 (the ring GEMM): the 64-wide conv1 of the ResNets' layer1 writes 64 zero channels more,
-                # which conv2 does not read (its input is a channel slice of t1)
-                t1_c = _round_up(width, 128) if self.full_split else width
-                if t1_c != width:
-                    w = torch.cat([w, torch.zeros((t1_c - width,) + tuple(w.shape[1:]), dtype=w.dtype)])
-                    b = torch.cat([b, torch.zeros(t1_c - width, dtype=b.dtype)])
-                t1 = self._act(hw[0] * hw[1], t1_c, split=self.full_split, mx=conv1_mx, lo_fp4=conv1_mx)
-                self._gemm(p + ".conv1", x, hw, cin, w, b, t1, read_lo=self.mixed_conv1_split)
-                # conv2 3x3 grouped + bn2 + relu
-                w, b = fold_bn(st, p + ".conv2.weight", p + ".bn2")
-                gconv_mx = self.mixed and t1.mx is not None and t1.mx_valid and t1.lo_fp4 and not dense
-                wsplit = int(self.mixed)
-                extra_g = {}
-                if dense:
-                    if self.mixed:
-                        wg_d = self._dev(_cached_pack((self._fp, self.backbone, p + ".conv2", "dense_split"),
-                                                      lambda: pack_conv3x3(w, groups, 8, split=True)), torch.float16)
-                    else:
-                        wg_d = self._dev(_cached_pack((self._fp, self.backbone, p + ".conv2", "dense", self.half),
-                                                      lambda: pack_conv3x3(w, groups, 8 if self.half else 4)), self.act_dtype)
-                    layout = 2
-                elif gconv_mx:
-                    frag_hi, bundle = _cached_pack((self._fp, self.backbone, p + ".conv2", "gconv_mx"), lambda: pack_gconv_mx(w, groups))
-                    wg_d, layout, wsplit = self._dev(frag_hi.reshape(-1), torch.float16), 1, 2
-                    wb = bundle.to(self.device)
-                    self._keep.append(wb)
-                    extra_g = dict(w_mx=wb.data_ptr(), in_mx=t1.mx.data_ptr(), mx_flags=AVL_MX_IN_LO)
-                elif self.half and width % 64 == 0 and 32 % cg == 0:
-                    if self.mixed:       # f16 pairs: 18 "taps" = 9 hi + 9 lo per window and n-tile
-                        nwin = width // 32
-                        whi, wlo = split_f16(w)
-                        packed = torch.cat([pack_gconv_windows(whi.to(torch.float64), groups).reshape(nwin, 2, 9, 16, 32),
-                                            pack_gconv_windows(wlo.to(torch.float64), groups).reshape(nwin, 2, 9, 16, 32)], dim=2)
-                        wg_d, layout = self._dev(packed.reshape(-1), torch.float16), 1
-                    else:
-                        wg_d, layout = self._dev(pack_gconv_windows(w, groups), self.act_dtype), 1
-                else:
-                    wg = w.reshape(groups, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).reshape(-1)   # [g][ky][kx][ci][co]
-                    wg_d, layout = self._dev(wg, torch.float32), 0
-                bg_d = self._dev(b, torch.float32)
-                # (conv3 as an MX GEMM reads the 3x3 output's lo part only through its FP4 copy: no f16 lo plane then)
-                t2_fp4 = self.mixed_conv2_split and self.mixed_trunk_fp4 and width % 256 == 0 and cout % 256 == 0 and layout == 1
-                # (the dense kernel writes no MX bundle: conv3 then takes the non-MX split GEMM, as in full_split)
-                t2 = self._act(ohw[0] * ohw[1], width, split=self.mixed_conv2_split, mx=not dense, lo_fp4=t2_fp4)
-                if self.full_split:
-                    assert layout in (1, 2) and wsplit == 1 and t1.lo is not None, "full_split needs the MFMA grouped conv with split weights"
-                    extra_g = dict(in_lo=self._lo(t1))
-                if self.full_split and s != 1 and not dense:
-                    # two tile buffers of a stride-2 tile do not fit the LDS with a lo plane beside the hi plane: the one strided 3x3 of the
-                    # network (layer2.0) runs at stride 1 and its result is sub-sampled (pad 1: out(y, x) = out1(2 y, 2 x))
-                    t2f = self._act(hw[0] * hw[1], width, split=True)
-                    self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2f, hw, width, wg_d, bg_d, ksize=3, stride=1, pad=d, dil=d,
-                                  groups=groups, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
-                    self._spatial(p + ".conv2.sub", OP_SUBSAMPLE, t2f, hw, width, t2, ohw, width, stride=s)
-                    self._spatial(p + ".conv2.sub[lo]", OP_SUBSAMPLE, t2f.lo, hw, width, t2.lo, ohw, width, stride=s)
-                    self._release(t2f)
-                else:
-                    self._spatial(p + ".conv2", OP_GCONV, t1, hw, width, t2, ohw, width, wg_d, bg_d, ksize=3, stride=s, pad=d, dil=d,
-                                  groups=groups, relu=1, w_layout=layout, w_split=wsplit, **extra_g)
-                self._release(t1)
-                # identity / downsample.  Stride-1 downsamples (layer3.0, layer4.0) whose input and the 3x3 output both carry MX
-                # bundles are folded into conv3 as a second input along K: the identity tensor never exists
-                fuse_ds = ((p + ".downsample.0.weight") in st and s == 1 and self.mixed_mx and self.mixed_fuse_ds and x.mx is not None
-                           and x.mx_valid and x.hi.shape[1] == cin and cin % 256 == 0 and t2.mx is not None and t2.mx_valid
-                           and width % 256 == 0 and cout % 256 == 0 and t2.lo_fp4 and x.lo_fp4)
-                if fuse_ds:
-                    idn = None
-                elif (p + ".downsample.0.weight") in st:
-                    w, b = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
-                    src = x
-                    if s != 1:
-                        keep_lo = self.mixed_conv1_split and x.lo is not None
-                        sub = self._act(ohw[0] * ohw[1], cin, split=keep_lo)
-                        self._spatial(p + ".downsample.sub", OP_SUBSAMPLE, x, hw, cin, sub, ohw, cin, stride=s)
-                        if keep_lo:
-                            self._spatial(p + ".downsample.sub[lo]", OP_SUBSAMPLE, x.lo, hw, cin, sub.lo, ohw, cin, stride=s)
-                        src = sub
-                    idn = self._act(ohw[0] * ohw[1], cout, split=self.mixed and trunk_lo)
-                    self._gemm(p + ".downsample", src, ohw, cin, w, b, idn, relu=False, read_lo=self.mixed_conv1_split)
-                    if s != 1:
-                        self._release(sub)
-                else:
-                    idn = x
-                # conv3 1x1 + bn3 + residual + relu
-                w, b = fold_bn(st, p + ".conv3.weight", p + ".bn3")
-                # where conv3 runs as an MX GEMM the trunk keeps its lo part only as FP4 (3 instead of 5 bytes per element move
-                # through conv3's epilogue, which is what bounds it: the 10 % error of FP4 hits a term that is 2^-11 of the sum)
-                trunk_fp4 = (self.mixed_mx and self.mixed_trunk_fp4 and t2.mx is not None and t2.mx_valid and width % 256 == 0
-                             and cout % 256 == 0 and t2.hi.shape[1] == width)
-                y = self._act(ohw[0] * ohw[1], cout, split=self.mixed and trunk_lo, mx=True, lo_fp4=trunk_fp4)
-                if fuse_ds:
-                    wd_, bd_ = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
-                    self._gemm(p + ".conv3+downsample", t2, ohw, width, w, b, y, relu=True, src2=x, w2=wd_.reshape(cout, cin), b2=bd_)
-                else:
-                    self._gemm(p + ".conv3", t2, ohw, width, w, b, y, relu=True, res=idn)
-                self._release(t2)
-                if idn is not x and idn is not None:
-                    self._release(idn)
-                if x is not low:              # layer1's output stays alive for the decoder
-                    self._release(x)
-                x, hw, cin = y, ohw, cout
-            if li == 1:
-                low, low_hw, low_c = x, hw, cin           # low_features = layer1 output (resnet.py:33-34)
+            wg = self._dev(w.reshape(groups, cg, cg, 3, 3).permute(0, 3, 4, 2, 1).reshape(-1), torch.float32)   # [g][ky][kx][ci][co]
+            f["w_layout"] = 0
+        return wg, self._dev(b, torch.float32), f
 
-        aspp, aspp_out = self._emit_aspp(st, x, hw, cin)
-        self._emit_decoder(st, aspp, hw, aspp_out, low, low_hw, low_c)
+    def _emit_identity(self, st, blk, x, t2):
+        """the block's identity path -> the Act that conv3 adds: x itself, or the downsample 1x1 of x (sub-sampled first where it strides).
+        None: the downsample folds into conv3 as a second input along K of its MX GEMM (stride 1, x and t2 both in the MX form), and the
+        identity tensor never exists."""
+        p, ohw, cin, cout = blk.p, blk.ohw, blk.cin, blk.cout
+        if not blk.has_ds:
+            return x
+        if (blk.s == 1 and self.mixed_fuse_ds and x.lo_fp4 and t2.lo_fp4 and self._mx_gemm(x, cin, cout)
+                and self._mx_gemm(t2, blk.width, cout)):
+            return None
+        w, b = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
+        src = x
+        if blk.s != 1:
+            keep_lo = self.mixed_conv1_split and x.lo is not None
+            src = self._act(ohw[0] * ohw[1], cin, split=keep_lo)
+            self._spatial(p + ".downsample.sub", OP_SUBSAMPLE, x, blk.hw, cin, src, ohw, cin, stride=blk.s)
+            if keep_lo:
+                self._spatial(p + ".downsample.sub[lo]", OP_SUBSAMPLE, x.lo, blk.hw, cin, src.lo, ohw, cin, stride=blk.s)
+        idn = self._act(ohw[0] * ohw[1], cout, split=self.mixed and blk.trunk_lo)
+        self._gemm(p + ".downsample", src, ohw, cin, w, b, idn, relu=False, read_lo=self.mixed_conv1_split)
+        if src is not x:
+            self._release(src)
+        return idn
 
     def _part_input(self, rows, ch):
         """a sub-plan's input activation (hi [+ lo] planes of the activation type) -> (Act, setter(float tensor [ch, h, w]))"""
@@ -1145,12 +1149,11 @@ class SegNet(object):
         H, W = self.H, self.W
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=self.device)
         self._keep.append(self.zero_page)
+        feat, self.set_feature = self._part_input(H * W, self.part[1])
         if self.part[0] == "aspp":
-            feat, self.set_feature = self._part_input(H * W, self.part[1])
             self.part_out, self.part_out_c = self._emit_aspp(st, feat, (H, W), self.part[1])
             self.out_h, self.out_w = H, W
         else:
-            feat, self.set_feature = self._part_input(H * W, self.part[1])
             low, self.set_low = self._part_input(4 * H * W, self.part[2])
             self._emit_decoder(st, feat, (H, W), self.part[1], low, (2 * H, 2 * W), self.part[2])
 
@@ -1166,7 +1169,7 @@ class SegNet(object):
         """ASPP (aspp.py:79-95), dilations forced to 1,12,24,36 for OS8 (deeplab_v3_plus.py:33-34) -> (output Act, its channels)"""
         dev = self.device
         M = fhw[0] * fhw[1]
-        dil = (1, 12, 24, 36) if getattr(self, "output_stride", 8) == 8 else (1, 6, 12, 18)
+        dil = (1, 12, 24, 36) if self.output_stride == 8 else (1, 6, 12, 18)
         branches = []
         i = 0
         while ("aspp.module_pyramid.%d.conv.weight" % i) in st or ("aspp.module_pyramid.%d.depthwise_cnn.conv.weight" % i) in st:
@@ -1190,7 +1193,7 @@ class SegNet(object):
                 wd_, bd_ = self._dev(w.reshape(fc, 9).t().reshape(-1), torch.float32), self._dev(b, torch.float32)    # [tap][C]
                 t = self._act(M, fc, split=self.mixed)
                 self._spatial(p + ".depthwise_cnn", OP_DWCONV, feat, fhw, fc, t, fhw, fc, wd_, bd_, ksize=3, stride=1, pad=dil[k],
-                              dil=dil[k], groups=fc, relu=1, in2=self.zero_page.data_ptr())
+                              dil=dil[k], groups=fc, relu=1, in2=self.zero_page.data_ptr(), in_lo=self._lo(feat), out_lo=self._lo(t))
                 self._gemm(p + ".pointwise_cnn", t, fhw, fc, w2, b2, cat, dst_col=col)
                 self._release(t)
             col += bch[k]
@@ -1227,20 +1230,14 @@ class SegNet(object):
 
     def _emit_decoder(self, st, aspp, fhw, aspp_out, low, low_hw, low_c):
         """decoder (decoder.py:45-51) -> logits_buf / labels_buf"""
-        dev = self.device
         w, b = fold_bn(st, "decoder.low_level_conv.conv.weight", "decoder.low_level_conv.bn")
         # MODEL.DECODER.LOW_LEVEL_OUT_CHANNELS other than the reference's 256 (48 in the DeepLabV3+ paper): the low-level branch is padded with
         # zero channels to the kernels' granule (zero rows of this conv, zero depthwise taps and zero pointwise columns in the first refine
         # block): ReLU(0) = 0 contributes exactly nothing
-        low_true = w.shape[0]
-        low_out = _round_up(low_true, 128 if self.mixed else 64)
-        if low_out != low_true:
-            w = torch.cat([w, torch.zeros((low_out - low_true,) + tuple(w.shape[1:]), dtype=w.dtype)])
-            b = torch.cat([b, torch.zeros(low_out - low_true, dtype=b.dtype)])
-        Ml = low_hw[0] * low_hw[1]
-        cat2 = self._act(Ml, aspp_out + low_out, split=self.mixed)
-        self._gemm("decoder.low_level_conv", low, low_hw, low_c, w, b, cat2, dst_col=aspp_out)
-        self._spatial("decoder.interpolate", OP_BILINEAR, aspp, fhw, aspp_out, cat2, low_hw, aspp_out)
+        low_out = _round_up(w.shape[0], 128 if self.mixed else 64)
+        cat2 = self._act(low_hw[0] * low_hw[1], aspp_out + low_out, split=self.mixed)
+        self._gemm("decoder.low_level_conv", low, low_hw, low_c, _zero_pad(w, low_out), _zero_pad(b, low_out), cat2, dst_col=aspp_out)
+        self._spatial("decoder.interpolate", OP_BILINEAR, aspp, fhw, aspp_out, cat2, low_hw, aspp_out, in_lo=self._lo(aspp), out_lo=self._lo(cat2))
         self._release(aspp)
         self._release(low)
         x, hw, cin = cat2, low_hw, aspp_out + low_out
@@ -1251,63 +1248,58 @@ class SegNet(object):
             ks = w.shape[-1]                                            # MODEL.DECODER.REFINE_KERNEL_SIZE[k]
             ohw = (hw[0] - (ks - 1), hw[1] - (ks - 1))                  # padding 0 (decoder.py:33-36 default)
             w2, b2 = fold_bn(st, p + ".pointwise_cnn.conv.weight", p + ".pointwise_cnn.bn")
-            if k == 0 and w.shape[0] != cin:             # the padded low-level channels (see above)
-                npad = cin - w.shape[0]
-                w = torch.cat([w, torch.zeros((npad,) + tuple(w.shape[1:]), dtype=w.dtype)])
-                b = torch.cat([b, torch.zeros(npad, dtype=b.dtype)])
-                w2 = torch.cat([w2, torch.zeros((w2.shape[0], npad) + tuple(w2.shape[2:]), dtype=w2.dtype)], dim=1)
-            last = ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % (k + 1)) not in st
-            fused_mixed = self.mixed and self.mixed_fuse_decoder and self.mixed_dw_exact
-            # the last refine block also carries the classifier (decoder.py:42-43) and the arg-max in its epilogue: its 256-channel result never goes to memory
-            if (ks == 3 and last and fused_mixed and self.mixed_fuse_classifier and self.half and self.fuse_dwpw and cin % 64 == 0 and w2.shape[0] == 256
-                    and self.num_classes <= 32 and x.lo is not None):
-                pc = "decoder.refine_layers.%d" % (k + 1)
-                wc, bc = fold_bn(st, pc + ".conv.weight", None)
-                self.out_h, self.out_w = ohw
-                Mo = ohw[0] * ohw[1]
-                self.logits_buf = torch.zeros((_round_up(Mo * self.batch, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
-                self.labels_buf = torch.zeros(_round_up(Mo * self.batch, self.ROW_PAD), dtype=torch.uint8, device=dev)
-                self._keep += [self.logits_buf, self.labels_buf]
-                self._dwpw(p + "+classifier", x, hw, cin, w, b, w2, b2, None, 0, 1, padding=0,
-                           classifier=(wc.reshape(self.num_classes, w2.shape[0]), bc, self.logits_buf, self.labels_buf))
-                self._release(x)
-                return
-            y = self._act(ohw[0] * ohw[1], w2.shape[0], split=self.mixed)
+            if k == 0:             # the padded low-level channels (see above)
+                w, b, w2 = _zero_pad(w, cin), _zero_pad(b, cin), _zero_pad(w2, cin, dim=1)
+            cout = w2.shape[0]
             # "mixed": the decoder keeps every activation as hi + lo (the logits are most sensitive to roundings here:
             # tools/precision_study.py).  fuse_decoder (default): one k_dwpw_xs launch per block -- split input, depthwise weights as
             # f16 pairs, the depthwise result as a split tile in LDS, three MFMA passes, split output; off: the split depthwise
             # kernel (fp32 weights) -> HBM -> an MX / three-pass GEMM
-            if (ks == 3 and self.half and self.fuse_dwpw and cin % 64 == 0 and cin <= 2048
-                    and (not self.mixed or (self.mixed_fuse_decoder and self.mixed_dw_exact))):
+            fused = (ks == 3 and self.half and self.fuse_dwpw and cin % 64 == 0 and cin <= 2048
+                     and (not self.mixed or (self.mixed_fuse_decoder and self.mixed_dw_exact)))
+            # the last refine block also carries the classifier (decoder.py:42-43) and the arg-max in its epilogue: its 256-channel result never goes to memory
+            last = ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % (k + 1)) not in st
+            if fused and last and self.mixed_fuse_classifier and x.lo is not None and cout == 256 and self.num_classes <= 32:
+                wc, bc = fold_bn(st, "decoder.refine_layers.%d.conv.weight" % (k + 1), None)
+                self._outputs(ohw)
+                self._dwpw(p + "+classifier", x, hw, cin, w, b, w2, b2, None, 0, 1, padding=0,
+                           classifier=(wc.reshape(self.num_classes, cout), bc, self.logits_buf, self.labels_buf))
+                self._release(x)
+                return
+            y = self._act(ohw[0] * ohw[1], cout, split=self.mixed)
+            if fused:
                 self._dwpw(p, x, hw, cin, w, b, w2, b2, y, 0, 1, padding=0)
                 self._release(x)
             else:
                 wd_, bd_ = self._dev(w.reshape(cin, ks * ks).t().reshape(-1), torch.float32), self._dev(b, torch.float32)     # [tap][C]
                 # mixed: the 3x3 depthwise output feeds an MX GEMM where shapes allow (f16 plane + FP4 copies, lo part as FP4 only); the k x k op
                 # (ks != 3, seg_dwconv_k.hip) writes no FP4 copy: its split output feeds the three-pass GEMM
-                t_fp4 = ks == 3 and self.mixed_mx and self.mixed_trunk_fp4 and cin % 256 == 0 and w2.shape[0] % 256 == 0 and x.lo is not None
+                t_fp4 = ks == 3 and self.mixed_trunk_fp4 and x.lo is not None and self._mx_gemm(None, cin, cout)
                 t = self._act(ohw[0] * ohw[1], cin, split=self.mixed, mx=t_fp4, lo_fp4=t_fp4)
                 self._spatial(p + ".depthwise_cnn", OP_DWCONV, x, hw, cin, t, ohw, cin, wd_, bd_, ksize=ks, stride=1, pad=0, dil=1, groups=cin, relu=1,
-                              in2=self.zero_page.data_ptr() if ks == 3 else 0)
+                              in2=self.zero_page.data_ptr() if ks == 3 else 0, in_lo=self._lo(x), out_lo=self._lo(t), **self._writes_mx(t, cin))
                 self._release(x)
                 self._gemm(p + ".pointwise_cnn", t, ohw, cin, w2, b2, y)
                 self._release(t)
-            w = w2
-            x, hw, cin = y, ohw, w.shape[0]
+            x, hw, cin = y, ohw, cout
             k += 1
-        p = "decoder.refine_layers.%d" % k
-        w, b = fold_bn(st, p + ".conv.weight", None)
-        self.out_h, self.out_w = hw
-        Mo = hw[0] * hw[1]
-        self.logits_buf = torch.zeros((_round_up(Mo * self.batch, self.ROW_PAD), self.num_classes), dtype=torch.float32, device=dev)
-        self.labels_buf = torch.zeros(_round_up(Mo * self.batch, self.ROW_PAD), dtype=torch.uint8, device=dev)
-        self._keep += [self.logits_buf, self.labels_buf]
+        w, b = fold_bn(st, "decoder.refine_layers.%d.conv.weight" % k, None)
+        self._outputs(hw)
         # the arg-max (semantic_segmentation.py:56) rides in the classifier's epilogue: the 19 logits of a pixel sit in two lanes' registers there
-        self._gemm(p, x, hw, cin, w, b, Act(self.logits_buf), relu=False, out_f32=True, labels=self.labels_buf if self.num_classes <= 32 else None)
+        self._gemm("decoder.refine_layers.%d" % k, x, hw, cin, w, b, Act(self.logits_buf), relu=False, out_f32=True,
+                   labels=self.labels_buf if self.num_classes <= 32 else None)
         if self.num_classes > 32:
             self._op("argmax", OP_ARGMAX, dtype=_lib.AVL_F32, in_=self.logits_buf.data_ptr(), out=self.labels_buf.data_ptr(), in_h=hw[0], in_w=hw[1],
                      in_c=self.num_classes, in_ld=self.num_classes, in_rows=self.logits_buf.shape[0], out_h=hw[0], out_w=hw[1], out_c=1,
                      out_ld=1, out_rows=self.labels_buf.shape[0])
+
+    def _outputs(self, hw):
+        """the plan's outputs for an out_h x out_w map: logits_buf (fp32 [rows][classes]) and labels_buf (uint8 [rows])"""
+        self.out_h, self.out_w = hw
+        rows = _round_up(hw[0] * hw[1] * self.batch, self.ROW_PAD)
+        self.logits_buf = torch.zeros((rows, self.num_classes), dtype=torch.float32, device=self.device)
+        self.labels_buf = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        self._keep += [self.logits_buf, self.labels_buf]
 
     # -------------------------------------------------------------------------------- running
     @property

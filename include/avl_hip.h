@@ -132,6 +132,19 @@ int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_
                     const uint32_t* lut_host, const uint8_t* label_colors_host,
                     const double* cm_host, uint32_t bonus_classes, void* stream);
 
+/* The vote / apply path avl_fused_frame takes for a cloud of n points on grid g (host only: looks at sizes and pointer
+ * values, never at memory).  AVL_E_ARG for a grid or n that avl_fused_frame refuses.
+ *   path  vote mask                         apply                      chosen when
+ *   0     32-bit, one touched list          list of touched cells      sparse cloud, byte mask not usable
+ *   1     32-bit                            sweep of the whole mask    dense cloud, byte mask not usable
+ *   2     byte                              sweep of the byte mask     dense cloud, byte mask usable
+ *   3     byte, 64 partitioned lists        the 64 lists               sparse cloud, byte mask usable
+ * The byte mask is usable when C + popcount(bonus_classes) <= 8, Hm*Wm % 16 == 0 and cell_mask is 16-byte aligned.
+ * Path 3: counter_len >= 132, touched_cap >= 64 x (list capacity of n), n <= 250000 and 2n <= Hm*Wm.  Otherwise a sweep
+ * (path 2 or 1) when Hm*Wm % 4 == 0, cell_mask is 16-byte aligned and n * (1024 with the byte mask, else 128) >= Hm*Wm;
+ * path 0 when not. */
+int avl_fused_frame_path(const avl_grid* g, int n, uint32_t bonus_classes);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

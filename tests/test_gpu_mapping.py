@@ -82,18 +82,23 @@ def test_fused_mapping_matches_golden(path, cuda_device):
 
 
 def test_device_grid_f32_and_device_tensors(cuda_device):
-    """float32 grid + CUDA-tensor inputs: identity CM gives exact small integers in fp32."""
+    """float32 grid + CUDA-tensor inputs, bit for bit against the oracle on a float32 array: NumPy's `map[idx] += cm[:, i]`
+    adds in float64 and rounds once to float32, as the apply kernel's (MapT)(v + cm) does; two updates accumulate."""
     import torch
+    from oracle import mapping_oracle as mo
     g = np.load(CASES[0])
     boundary, res = g["boundary"].tolist(), float(g["resolution"])
     sm = make_sm(boundary, res, g["cm"], g["use_intensity"], cuda_device, grid_dtype="f32")
-    mp = torch.from_numpy(g["masked_pcd"]).to(cuda_device)
-    lab = torch.from_numpy(g["label"]).to(cuda_device)
-    out = sm.update_map(sm.map_dev, mp, lab)
-    assert out.dtype == torch.float32 and out.is_cuda
-    ref = dense(g["map_idx"], g["map_val"], tuple(out.shape))
-    tol = 1e-3 * max(1.0, np.abs(ref).max())          # north_star: grid log-odds within 1e-3
-    assert np.max(np.abs(out.cpu().numpy().astype(np.float64) - ref)) <= tol
+    want = np.zeros((sm.map_height, sm.map_width, sm.map_depth), dtype=np.float32)
+    for pcd, label in ((g["masked_pcd"], g["label"]), (g["masked_pcd2"], g["label2"])):
+        mp = torch.from_numpy(pcd).to(cuda_device)
+        lab = torch.from_numpy(label).to(cuda_device)
+        out = sm.update_map(sm.map_dev, mp, lab)
+        assert out.dtype == torch.float32 and out.is_cuda
+        mo.update_map(want, pcd, label, boundary, res, mo.LABELS_NAMES, mo.LABEL_COLORS, np.asarray(g["cm"]), bool(g["use_intensity"]))
+        assert np.array_equal(out.cpu().numpy(), want)
+    ref = dense(g["map2_idx"], g["map2_val"], tuple(out.shape))
+    assert np.max(np.abs(want.astype(np.float64) - ref)) <= 1e-3 * max(1.0, np.abs(ref).max())   # the f32 oracle itself: within 1e-3 of f64
 
 
 def test_classmap_source_equals_colour_image_path(cuda_device):

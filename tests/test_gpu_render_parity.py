@@ -1,0 +1,157 @@
+"""The GPU renderer (avl_render_bev_map, avl_render_bev_map_thresholds, avl_grid_box_filter) against oracle/renderer_oracle.py run
+on the same array in the same dtype, bit for bit, at class counts on both sides of NumPy's 8-accumulator pairwise sum.
+
+Which cells render black depends on np.sum(map, axis=2) == 0, so the rows here include cancellations whose sum is zero in NumPy's
+summation order and not in a plain left fold (and the other way round), in float32 and float64; shares that equal their
+threshold exactly after rounding to the map's type; ties; NaN and infinite rows; all-zero rows; a non-identity priority."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+CLASS_COUNTS = [1, 5, 7, 8, 9, 16]
+DTYPES = [np.float32, np.float64]
+
+
+def colors(c):
+    return [[(37 * i + 11) % 256, (91 * i + 5) % 256, (53 * i + 200) % 256] for i in range(c)]
+
+
+def pad(row, c):
+    row = list(row)[:c]
+    return row + [0.0] * (c - len(row))
+
+
+def constructed_rows(c, dtype):
+    """rows whose zero test or share depends on the order and type of the channel sum (the ones named in the issue first)"""
+    big = 1e8 if dtype == np.float32 else 1e16
+    rows = [
+        [1e8, 1, -1e8, 0, 0],                       # f32: NumPy's sum is 0, a float64 sum is 1
+        [0, 1e16, 1, 0, -1e16, 0, -1, 0],           # f64, C = 8: NumPy's pairwise sum is 0, a left fold -1
+        [1, 0, 1e8, 0, -1e8, 0, 0, -1],             # f32, C = 8: pairwise 0, a left fold not
+        [big, 1, -big, -1, 0, 0, 0, 0, 1, -1],
+        [1, big, 0, 0, 0, -big, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
+        [big, 0, 0, 0, 0, 0, 0, 0, -big, 1, 0, 0, 0, 0, 0, 0],
+        [1, 99],                                    # share of class 0: exactly float32(0.01) / 0.01
+        [99, 1, 0, 0, 0, 0, 0, 0, 0],
+        [1, 2], [2, 1, 0, 0, 0, 0, 0, 3],           # shares of exactly 1/3 and 1/2 in the map's type
+        [3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3],   # ties everywhere: the first channel wins
+        [-1, 5, 5, -9],
+    ]
+    return [pad(r, c) for r in rows]
+
+
+def special_rows(c, rng):
+    rows = [[0.0] * c, [-0.0] * c]
+    for k in {0, c // 2, c - 1}:
+        r = list(rng.normal(size=c))
+        r[k] = np.nan
+        rows.append(r)
+        r = list(rng.normal(size=c))
+        r[k] = np.inf
+        rows.append(r)
+        r = [0.0] * c
+        r[k] = -np.inf
+        rows.append(r)
+    rows.append([np.nan] * c)
+    rows.append([np.inf if i % 2 else -np.inf for i in range(c)])
+    return rows
+
+
+def cancellation_rows(c, dtype, rng, n=3000):
+    """random rows of 0, +-1, +-2, +-big: many have sums that differ between summation orders"""
+    big = 1e8 if dtype == np.float32 else 1e16
+    vals = np.array([0.0, 0.0, 1.0, -1.0, 2.0, -2.0, big, -big, big / 2, -big / 2])
+    return vals[rng.integers(0, vals.size, size=(n, c))].tolist()
+
+
+def make_map(c, dtype, seed, width=64):
+    rng = np.random.default_rng(seed)
+    rows = constructed_rows(c, dtype) + special_rows(c, rng) + cancellation_rows(c, dtype, rng)
+    rows += (rng.normal(size=(2000, c)) * 4).tolist()                      # random log-odds
+    rows += np.round(rng.normal(size=(300, c)) * 2).tolist()               # small integers: ties and exact shares
+    rows += (np.abs(rng.normal(size=(300, c))) * rng.integers(0, 2, size=(300, c))).tolist()   # non-negative, sparse
+    h = (len(rows) + width - 1) // width
+    rows += [[0.0] * c] * (h * width - len(rows))
+    return np.array(rows, dtype=dtype).reshape(h, width, c)
+
+
+def thresholds_for(c):
+    base = [0.01, 1.0 / 3.0, 0.5, 0.01, 0.25, 0.1, 0.01, 0.75, 1.0 / 3.0, 0.01, 0.2, 0.5, 0.01, 0.3, 0.05, 0.01]
+    return base[:c]
+
+
+def _ids(v):
+    return v.__name__ if isinstance(v, type) else str(v)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
+@pytest.mark.parametrize("c", CLASS_COUNTS)
+def test_render_bev_map_matches_oracle(c, dtype, cuda_device):
+    from oracle import renderer_oracle as ro
+    from vision_semantic_segmentation_amd import renderer as rr
+    m = make_map(c, dtype, seed=c)
+    col = colors(c)
+    with np.errstate(all="ignore"):
+        want = ro.render_bev_map(m, col)
+    got = rr.render_bev_map(m, col)
+    assert np.array_equal(got, want), "%d of %d cells differ" % (int((got != want).any(axis=2).sum()), m.shape[0] * m.shape[1])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
+@pytest.mark.parametrize("c", CLASS_COUNTS)
+def test_render_thresholds_matches_oracle(c, dtype, cuda_device):
+    from oracle import renderer_oracle as ro
+    from vision_semantic_segmentation_amd import renderer as rr
+    m = make_map(c, dtype, seed=100 + c)
+    col = colors(c)
+    priorities = [None, list(range(c))[::-1], [(3 * k + 1) % c for k in range(c)] if c % 3 else list(range(1, c)) + [0]]
+    assert all(p is None or sorted(p) == list(range(c)) for p in priorities)
+    for prio in priorities:
+        for thr in ([0.01] * c, thresholds_for(c)):
+            with np.errstate(all="ignore"):
+                want = ro.render_bev_map_with_thresholds(m, col, prio, thr)
+            got = rr.render_bev_map_with_thresholds(m, col, prio, thr)
+            assert np.array_equal(got, want), "priority %s thresholds %s: %d cells differ" % (prio, thr, int((got != want).any(axis=2).sum()))
+    if c <= 5:                              # the reference's default thresholds
+        with np.errstate(all="ignore"):
+            want = ro.render_bev_map_with_thresholds(m, col)
+        assert np.array_equal(rr.render_bev_map_with_thresholds(m, col), want)
+
+
+def test_share_equal_to_float32_threshold(cuda_device):
+    """[1, 99, 0, 0, 0] in float32: the share of class 0 is float32(0.01), which NumPy compares with the threshold in float32
+    (drawn), while float64(float32(0.01)) < 0.01."""
+    from oracle import renderer_oracle as ro
+    from vision_semantic_segmentation_amd import renderer as rr
+    col = colors(5)
+    m = np.array([[[1, 99, 0, 0, 0]]], dtype=np.float32)
+    want = ro.render_bev_map_with_thresholds(m, col, [1, 2, 3, 4, 0], [0.5, 0.5, 0.5, 0.5, 0.01])
+    assert want[0, 0].tolist() == col[0]
+    assert np.array_equal(rr.render_bev_map_with_thresholds(m, col, [1, 2, 3, 4, 0], [0.5, 0.5, 0.5, 0.5, 0.01]), want)
+
+
+def test_too_few_thresholds_raise(cuda_device):
+    from oracle import renderer_oracle as ro
+    from vision_semantic_segmentation_amd import renderer as rr
+    m = np.ones((4, 4, 7))
+    with pytest.raises(IndexError):
+        ro.render_bev_map_with_thresholds(m, colors(7))
+    with pytest.raises(IndexError):
+        rr.render_bev_map_with_thresholds(m, colors(7))
+    assert np.array_equal(rr.render_bev_map_with_thresholds(m, colors(7), thresholds=[0.01] * 8),
+                          ro.render_bev_map_with_thresholds(m, colors(7), thresholds=[0.01] * 8))
+
+
+@pytest.mark.parametrize("c", [1, 5, 16])
+def test_box_filter_float32_exact(c, cuda_device):
+    """apply_filter on a float32 map: double accumulation of float32(1/9) * value in kernel row order, rounded once to float32."""
+    from oracle import renderer_oracle as ro
+    from vision_semantic_segmentation_amd import renderer as rr
+    rng = np.random.default_rng(c)
+    src = (rng.normal(size=(37, 53, c)) * 10.0 ** rng.integers(-3, 9, size=(37, 53, c))).astype(np.float32)
+    src[rng.random(src.shape) < 0.3] = 0
+    src[5, 7, 0] = np.nan
+    got = rr.apply_filter(src)
+    assert got.dtype == np.float32
+    assert np.array_equal(got, ro.apply_filter(src).astype(np.float32), equal_nan=True)

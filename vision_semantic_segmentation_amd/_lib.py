@@ -43,6 +43,7 @@ _SIGNATURES = {
     "avl_grid_apply": (_i, [C.POINTER(AvlGrid), _vp, _vp, _i, _vp]),
     "avl_fused_frame": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
                              _vp, _vp, _vp, C.c_uint32, _vp]),
+    "avl_fused_frame_path": (_i, [C.POINTER(AvlGrid), _i, C.c_uint32]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -604,6 +604,30 @@ struct RenderParams {
     double thresholds[AVL_MAX_MAP_CLASSES];
 };
 
+// np.sum(map, axis=2) of one contiguous row, in the map's own type and in NumPy's order (pairwise_sum in NumPy's
+// umath/loops_utils.h.src; C <= 16 stays below its 128-element block): fewer than 8 values are a left fold from 0; from 8 up,
+// eight accumulators r[j] = a[j], r[j] += a[i + j] for every further whole group of 8, then
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then a left fold of the remainder.  Which cells count as empty (sum == 0)
+// and the shares of the thresholds renderer depend on this rounding.
+template <typename MapT>
+__device__ __forceinline__ MapT numpy_row_sum(const MapT* row, int C) {
+    if (C < 8) {
+        MapT s = (MapT)0;
+        for (int c = 0; c < C; ++c) s = s + row[c];
+        return s;
+    }
+    MapT r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = row[j];
+    int i = 8;
+    for (; i + 8 <= C; i += 8)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + row[i + j];
+    MapT s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < C; ++i) s = s + row[i];
+    return s;
+}
+
 // render_bev_map (renderer.py:32-59): colour of np.argmax (first maximum wins), black where the channel sum is 0
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_render_bev(const MapT* __restrict__ map, long long ncell, int C, RenderParams rp,
@@ -611,33 +635,32 @@ __global__ void __launch_bounds__(kBlock) k_render_bev(const MapT* __restrict__ 
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= ncell) return;
     const MapT* row = map + i * C;
-    double best = (double)row[0], sum = 0.0;
+    MapT best = row[0];
     int bi = 0;
-    for (int c = 0; c < C; ++c) {
-        const double v = (double)row[c];
-        sum = sum + v;                                            // np.sum over 5 contiguous values: sequential from 0
-        if (c > 0 && (v > best || (v != v && best == best))) { best = v; bi = c; }
+    for (int c = 1; c < C; ++c) {
+        const MapT v = row[c];
+        if (v > best || (v != v && best == best)) { best = v; bi = c; }
     }
     unsigned char r = rp.colors[3 * bi], g = rp.colors[3 * bi + 1], b = rp.colors[3 * bi + 2];
-    if (sum == 0.0) r = g = b = 0;
+    if (numpy_row_sum(row, C) == (MapT)0) r = g = b = 0;
     out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
 }
 
-// render_bev_map_with_thresholds (renderer.py:131-172): later priorities overwrite earlier ones
+// render_bev_map_with_thresholds (renderer.py:131-172): later priorities overwrite earlier ones.  The share is a MapT quotient
+// and is compared with the threshold in MapT: NumPy compares a float32 array with a Python float in float32.
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_render_thresholds(const MapT* __restrict__ map, long long ncell, int C, RenderParams rp,
                                                               unsigned char* __restrict__ out) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= ncell) return;
     const MapT* row = map + i * C;
-    MapT s = (MapT)0;
-    for (int c = 0; c < C; ++c) s = s + row[c];
+    const MapT s = numpy_row_sum(row, C);
     unsigned char r = 0, g = 0, b = 0;
     if (s != (MapT)0) {
         for (int k = 0; k < C; ++k) {
             const int ch = rp.priority[k];
             const MapT pn = row[ch] / s;                          // np.divide(map, channel_sum), same element type as the map
-            if ((double)pn >= rp.thresholds[k]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
+            if (pn >= (MapT)rp.thresholds[k]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
         }
     }
     out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
@@ -921,6 +944,16 @@ extern "C" int avl_update_map(const avl_grid* g, const double* pcd, const uint8_
     return launch_apply(g, cm_host, nullptr, 0, avl::as_stream(stream));
 }
 
+extern "C" int avl_fused_frame_path(const avl_grid* g, int n, uint32_t bonus_classes) {
+    GridParams gp;
+    int rc;
+    if ((rc = fill_grid(gp, g, nullptr, bonus_classes))) return rc;
+    AVL_REQUIRE(n >= 0, "n = %d", n);
+    if (use_lists(g, n, bonus_classes)) return 3;
+    if (!use_scan(g, n, bonus_classes)) return 0;
+    return byte_mask_ok(g, bonus_classes) ? 2 : 1;
+}
+
 extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride,
                                int64_t comp_stride, const double* P_host, const double* T_host, double range_max,
                                int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
@@ -948,8 +981,8 @@ extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dt
     AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     hipStream_t s = avl::as_stream(stream);
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool scan = use_scan(g, n, bonus_classes);
-    const int mode = use_lists(g, n, bonus_classes) ? 3 : !scan ? 0 : (byte_mask_ok(g, bonus_classes) ? 2 : 1);
+    const int mode = avl_fused_frame_path(g, n, bonus_classes);
+    if (mode < 0) return mode;
     if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
     const int list_cap = list_geom(n).cap;
 #define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, pv, pp, gp, src, src_w, src_h, lut, g->cell_mask, g->touched, g->counter, list_cap)

@@ -46,13 +46,17 @@ def render_bev_map(map, label_colors):
 
 def render_bev_map_with_thresholds(map, label_colors, priority=None, thresholds=(0.01, 0.01, 0.01, 0.01, 0.01)):
     """renderer.py:131-172: a label is drawn where its normalised share reaches its threshold; `priority` lists the
-    labels from low to high, higher ones overwrite lower ones."""
+    labels from low to high, higher ones overwrite lower ones.  Fewer thresholds than channels raise IndexError, as the
+    reference's `thresholds[i]` does."""
+    thresholds = list(thresholds)
+    if len(thresholds) < int(map.shape[-1]):
+        raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), int(map.shape[-1])))
     t, is_np, dt = _prep(map)
     h, w, c = t.shape
     if priority is not None and len(priority) != c:
         raise ValueError("Each channel should have a priority.")
     pr = (C.c_int32 * c)(*[int(p) for p in (priority if priority is not None else range(c))])
-    th = (C.c_double * c)(*[float(x) for x in list(thresholds)[:c]])
+    th = (C.c_double * c)(*[float(x) for x in thresholds[:c]])
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
     _lib.check(_lib.lib().avl_render_bev_map_thresholds(C.c_void_p(t.data_ptr()), dt, h, w, c, _colors(label_colors, c), pr, th,
                                                         C.c_void_p(out.data_ptr()), _stream(t)), "avl_render_bev_map_thresholds")

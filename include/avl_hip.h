@@ -248,6 +248,28 @@ int64_t avl_seg_eval_scratch_bytes(int H, int W);
 int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, int H, int W, const uint8_t* gt, int ignore_index,
                           uint8_t* labels_out, unsigned long long* confusion, double* loss_out, unsigned long long* counts_out,
                           void* scratch, void* stream);
+/* The two above for a batch of n images in ONE launch each (two with the loss: eval + finalize); the image index is blockIdx.z.
+ * logits: image i starts image_rows rows (of ld floats) after image i-1; image_rows >= h * w, and = h * w for a batched plan's logits
+ * buffer.  n >= 1.  gt and labels_out are uint8 [n][H][W], out is fp32 [n][K][H][W]; every size, K and ld are those of ONE image, and
+ * the limits are the single-image ones (K <= 256 for the up-sample, K <= 64 for the eval).
+ *   out[i], labels_out[i]: bit for bit what avl_upsample_logits / avl_seg_eval_full_res give on image i alone.
+ *   confusion uint64 [K][K]: ONE matrix, += the counts of all n images (MeanIOU.evaluate on a batch).
+ *   loss: CrossEntropyLoss's reduction='mean' over the BATCH.  The per-workgroup fp64 partials go to a slab [n][groups]; the finalize
+ *       kernel sums image i's partials in exactly the single-image order, then adds the n image sums in image order 0 .. n-1 in fp64
+ *       (no float atomics; bitwise reproducible).  loss_out = {that sum, sum / contributing pixels of the batch (NaN when there is
+ *       none; NOT the mean of the images' means)}, counts_out = {contributing pixels, invalid ground-truth values} of the batch.
+ *   image_loss_out double [n][2], image_counts_out uint64 [n][2] (both or neither; they need the loss trio): {sum, mean} and the two
+ *       counts per image; image_loss_out[i][0] is bit-identical to loss_out[0] of avl_seg_eval_full_res on image i alone, and
+ *       loss_out[0] is their left-to-right fp64 sum.
+ *   scratch: avl_seg_eval_scratch_bytes_batch(n, H, W) bytes (= n times the single-image figure).
+ * Arguments are checked before anything touches the device. */
+int avl_upsample_logits_batch(const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, float* out, int H, int W,
+                              void* stream);
+int64_t avl_seg_eval_scratch_bytes_batch(int n, int H, int W);
+int avl_seg_eval_full_res_batch(const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, int H, int W,
+                                const uint8_t* gt, int ignore_index, uint8_t* labels_out, unsigned long long* confusion, double* loss_out,
+                                unsigned long long* counts_out, double* image_loss_out, unsigned long long* image_counts_out,
+                                void* scratch, void* stream);
 
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *

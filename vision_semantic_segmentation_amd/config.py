@@ -113,6 +113,9 @@ def get_network_cfg_defaults():
                                         # (keep the best finite 16-bit plan)
     C.MODEL.SEED = 0               # seed of the random weights used when MODEL.WEIGHT == ""
     C.MODEL.HIP_GRAPH = True       # replay the ~90-kernel plan as one hipGraph launch per frame
+    C.MODEL.VALIDATE_BATCH = False # SemanticSegmentation.validate_step also takes a batch [N, h, w, 3] with labels [N, h, w] (one batch-N forward and
+                                   # one fused full-resolution pass).  Off by default: validate_step has always refused anything but one image with
+                                   # NotImplementedError, and callers that rely on that keep it.  DeepLabV3Plus.validate_step takes batches regardless
     return C
 
 

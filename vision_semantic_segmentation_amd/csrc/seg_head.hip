@@ -9,6 +9,10 @@
 // One workgroup = a 16 x 64 tile of output pixels; lane (x = tid & 63, row group tid >> 6) owns the four pixels of its column in rows
 // r, r + 4, r + 8, r + 12, so every store of a wave is 64 consecutive x.  The low-res window the tile reads (about 6 x 18 source pixels x K
 // at 266 x 476 -> 1080 x 1920) is staged in LDS when it fits (32 KB), otherwise (strong down-sampling) the corners are read from global.
+// A batch of n images is one launch: the image index is blockIdx.z, and at entry a workgroup moves its 64-bit base pointers (logits, gt,
+// labels, planes) to its image and writes its loss partial into its image's row of the slab; every per-lane offset stays that of one
+// image, so each image computes exactly what a launch on it alone computes.  The confusion matrix is one for the batch;
+// k_eval_finalize sums each image's partials in the single-image order and then the image sums in image order.
 #include <algorithm>
 
 #include "seg_types.h"
@@ -29,6 +33,7 @@ struct Geo {
     int H, W;
     float sy, sx;
     int win_cap;                       // floats of LDS for the staged window (window_capacity(); 0 = read the corners from global)
+    long long image_stride;            // floats between two images' logits (image_rows * ld); blockIdx.z = image
 };
 
 // The product is rounded before the corner and weight are taken from it: torch rounds it too, and the tile's window below must see the
@@ -120,8 +125,14 @@ __device__ __forceinline__ void upsample_pixel(const Geo& g, const Window& win, 
     for (int k = 0; k < g.K; ++k) dst[k * plane] = lerp4(src, o, c, k);
 }
 
+// BATCH: gridDim.z images (a launch for one image is the <false> kernel, which has no image arithmetic at all)
+template <bool BATCH>
 __global__ void __launch_bounds__(kThreads) k_upsample_logits(Geo g, float* __restrict__ out) {
     extern __shared__ float lds[];                              // [g.win_cap]
+    if (BATCH) {
+        g.logits += (long long)blockIdx.z * g.image_stride;
+        out += (long long)blockIdx.z * g.K * g.H * g.W;
+    }
     const int oy0 = blockIdx.y * kTileH, ox0 = blockIdx.x * kTileW;
     const Window win = stage_window(g, oy0, ox0, lds);
     const int ox = ox0 + (threadIdx.x & (kTileW - 1));
@@ -136,13 +147,12 @@ __global__ void __launch_bounds__(kThreads) k_upsample_logits(Geo g, float* __re
 }
 
 struct EvalOut {
-    const unsigned char* gt;           // uint8 [H][W] or NULL
+    const unsigned char* gt;           // uint8 [n][H][W] or NULL
     int ignore_index;
-    unsigned char* labels;             // uint8 [H][W] or NULL
-    unsigned long long* confusion;     // [K][K] (ground truth, prediction), accumulated; NULL = none
-    double* slab_sum;                  // [blocks] loss partials, NULL = no loss
-    unsigned* slab_cnt;                // [blocks] pixels that contributed to the loss
-    unsigned* slab_inv;                // [blocks] ground-truth values neither in [0, K) nor ignore_index
+    unsigned char* labels;             // uint8 [n][H][W] or NULL
+    unsigned long long* confusion;     // [K][K] (ground truth, prediction), accumulated over the batch; NULL = none
+    double* slab;                      // NULL = no loss; double [n][blocks] loss partials, then unsigned [n][blocks] pixels that contributed
+                                       // to the loss, then unsigned [n][blocks] ground-truth values neither in [0, K) nor ignore_index
 };
 
 // One output pixel: K interpolated logits -> arg-max (first maximal index wins, a NaN counts as maximal: AVL_OP_ARGMAX) and, with LOSS and a
@@ -195,6 +205,7 @@ __device__ __forceinline__ LossPart eval_tile(const Geo& g, const EvalOut& e, co
     return lp;
 }
 
+template <bool BATCH>
 __global__ void __launch_bounds__(kThreads) k_full_res_eval(Geo g, EvalOut e) {
     extern __shared__ unsigned smem[];                          // [K * K histogram bins when e.confusion][g.win_cap window floats]
     unsigned* hist = smem;
@@ -202,13 +213,19 @@ __global__ void __launch_bounds__(kThreads) k_full_res_eval(Geo g, EvalOut e) {
     __shared__ double red_sum[kThreads / 64];
     __shared__ unsigned red_cnt[kThreads / 64], red_inv[kThreads / 64];
     const int KK = g.K * g.K;
+    if (BATCH) {   // this workgroup's image
+        const long long img = blockIdx.z, pixels = (long long)g.H * g.W;
+        g.logits += img * g.image_stride;
+        if (e.gt) e.gt += img * pixels;
+        if (e.labels) e.labels += img * pixels;
+    }
     if (e.confusion)
         for (int i = threadIdx.x; i < KK; i += kThreads) hist[i] = 0u;
     const int oy0 = blockIdx.y * kTileH, ox0 = blockIdx.x * kTileW;
     const Window win = stage_window(g, oy0, ox0, lds);          // (its barrier also orders the histogram's zeroing)
     const int ox = ox0 + (threadIdx.x & (kTileW - 1));
     LossPart lp = {0.0, 0u, 0u};
-    if (ox < g.W) lp = e.slab_sum ? eval_tile<true>(g, e, win, lds, hist, oy0, ox) : eval_tile<false>(g, e, win, lds, hist, oy0, ox);
+    if (ox < g.W) lp = e.slab ? eval_tile<true>(g, e, win, lds, hist, oy0, ox) : eval_tile<false>(g, e, win, lds, hist, oy0, ox);
     double lsum = lp.sum;
     unsigned cnt = lp.cnt, inv = lp.inv;
     if (e.confusion) {
@@ -218,7 +235,7 @@ __global__ void __launch_bounds__(kThreads) k_full_res_eval(Geo g, EvalOut e) {
             if (v) atomicAdd(&e.confusion[i], (unsigned long long)v);
         }
     }
-    if (e.slab_sum) {
+    if (e.slab) {
         // fixed-order reduction: a shuffle tree inside each wave, then the four waves in order
         for (int d = 32; d > 0; d >>= 1) {
             lsum += __shfl_down(lsum, d);
@@ -232,55 +249,86 @@ __global__ void __launch_bounds__(kThreads) k_full_res_eval(Geo g, EvalOut e) {
             double sum = 0.0;
             unsigned c = 0u, n = 0u;
             for (int i = 0; i < kThreads / 64; ++i) { sum += red_sum[i]; c += red_cnt[i]; n += red_inv[i]; }
-            const int b = blockIdx.y * gridDim.x + blockIdx.x;
-            e.slab_sum[b] = sum;
-            e.slab_cnt[b] = c;
-            e.slab_inv[b] = n;
+            const long long blocks = (long long)gridDim.x * gridDim.y * (BATCH ? gridDim.z : 1u);
+            const long long b = ((long long)(BATCH ? blockIdx.z : 0u) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+            unsigned* slab_cnt = reinterpret_cast<unsigned*>(e.slab + blocks);
+            e.slab[b] = sum;
+            slab_cnt[b] = c;
+            slab_cnt[blocks + b] = n;
         }
     }
 }
 
-// loss_out[0] = sum of the terms, loss_out[1] = their mean (NaN when no pixel contributed, as torch's cross_entropy);
-// counts_out[0] = contributing pixels, counts_out[1] = invalid ground-truth values.  One workgroup, fixed order: bitwise reproducible.
+// Per image (in order): its nb partials summed by one workgroup in a fixed order (a strided pass, then a tree) -> image_loss[i] = {sum,
+// mean (NaN when no pixel contributed, as torch's cross_entropy)}, image_counts[i] = {contributing pixels, invalid ground-truth values}
+// (both optional).  Then the batch: loss_out[0] = the image sums added in image order 0 .. n-1 in fp64, loss_out[1] = that sum over the
+// batch's contributing pixels (torch's reduction='mean' over the batch; NaN when there is none), counts_out = the counts' totals.
+// Bitwise reproducible, and image i's words are those of a launch on image i alone.
 __global__ void __launch_bounds__(kThreads) k_eval_finalize(const double* __restrict__ slab_sum, const unsigned* __restrict__ slab_cnt,
-                                                           const unsigned* __restrict__ slab_inv, int nb, double* __restrict__ loss_out,
-                                                           unsigned long long* __restrict__ counts_out) {
+                                                           const unsigned* __restrict__ slab_inv, int nb, int n, double* __restrict__ loss_out,
+                                                           unsigned long long* __restrict__ counts_out, double* __restrict__ image_loss,
+                                                           unsigned long long* __restrict__ image_counts) {
     __shared__ double s_sum[kThreads];
     __shared__ unsigned long long s_cnt[kThreads], s_inv[kThreads];
-    double sum = 0.0;
-    unsigned long long cnt = 0, inv = 0;
-    for (int i = threadIdx.x; i < nb; i += kThreads) { sum += slab_sum[i]; cnt += slab_cnt[i]; inv += slab_inv[i]; }
-    s_sum[threadIdx.x] = sum;
-    s_cnt[threadIdx.x] = cnt;
-    s_inv[threadIdx.x] = inv;
-    __syncthreads();
-    for (int d = kThreads / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) {
-            s_sum[threadIdx.x] += s_sum[threadIdx.x + d];
-            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + d];
-            s_inv[threadIdx.x] += s_inv[threadIdx.x + d];
-        }
+    double total = 0.0;
+    unsigned long long total_cnt = 0, total_inv = 0;
+#pragma unroll 1
+    for (int img = 0; img < n; ++img) {
+        const long long base = (long long)img * nb;
+        double sum = 0.0;
+        unsigned long long cnt = 0, inv = 0;
+        for (int i = threadIdx.x; i < nb; i += kThreads) { sum += slab_sum[base + i]; cnt += slab_cnt[base + i]; inv += slab_inv[base + i]; }
+        s_sum[threadIdx.x] = sum;
+        s_cnt[threadIdx.x] = cnt;
+        s_inv[threadIdx.x] = inv;
         __syncthreads();
+        for (int d = kThreads / 2; d > 0; d >>= 1) {
+            if (threadIdx.x < d) {
+                s_sum[threadIdx.x] += s_sum[threadIdx.x + d];
+                s_cnt[threadIdx.x] += s_cnt[threadIdx.x + d];
+                s_inv[threadIdx.x] += s_inv[threadIdx.x + d];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            if (image_loss) {
+                image_loss[2 * img] = s_sum[0];
+                image_loss[2 * img + 1] = s_cnt[0] ? s_sum[0] / (double)s_cnt[0] : __builtin_nan("");
+                image_counts[2 * img] = s_cnt[0];
+                image_counts[2 * img + 1] = s_inv[0];
+            }
+            total = img ? total + s_sum[0] : s_sum[0];
+            total_cnt += s_cnt[0];
+            total_inv += s_inv[0];
+        }
+        __syncthreads();                                        // s_* are rewritten by the next image
     }
     if (threadIdx.x == 0) {
-        loss_out[0] = s_sum[0];
-        loss_out[1] = s_cnt[0] ? s_sum[0] / (double)s_cnt[0] : __builtin_nan("");
-        counts_out[0] = s_cnt[0];
-        counts_out[1] = s_inv[0];
+        loss_out[0] = total;
+        loss_out[1] = total_cnt ? total / (double)total_cnt : __builtin_nan("");
+        counts_out[0] = total_cnt;
+        counts_out[1] = total_inv;
     }
 }
 
 bool aligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
 
-int make_geo(const float* logits, int h, int w, int K, int64_t ld, int H, int W, Geo& g, const char* what) {
+constexpr int kMaxBatch = 65535;           // gridDim.z
+
+int make_geo(const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, int H, int W, Geo& g, const char* what) {
     AVL_REQUIRE(logits, "%s: logits is NULL", what);
     AVL_REQUIRE(aligned(logits, 4), "%s: logits is not 4-byte aligned", what);
+    AVL_REQUIRE(n >= 1 && n <= kMaxBatch, "%s: n = %d images (1 .. %d)", what, n, kMaxBatch);
     AVL_REQUIRE(h > 0 && w > 0 && H > 0 && W > 0, "%s: sizes %d x %d -> %d x %d", what, h, w, H, W);
     AVL_REQUIRE((long long)H * W <= (1ll << 31) - 1 && (long long)h * w <= (1ll << 31) - 1, "%s: image too large", what);
     AVL_REQUIRE(K > 0, "%s: K = %d", what, K);
     AVL_REQUIRE(ld >= K, "%s: row stride %lld < K %d", what, (long long)ld, K);
+    AVL_REQUIRE(image_rows >= (int64_t)h * w, "%s: image_rows %lld < h * w = %lld", what, (long long)image_rows, (long long)h * w);
+    AVL_REQUIRE(image_rows <= (1ll << 61) / ld / n, "%s: n * image_rows * row stride (%d * %lld * %lld) too large", what, n,
+                (long long)image_rows, (long long)ld);
     g.logits = logits;
     g.h = h; g.w = w; g.K = K; g.ld = ld; g.H = H; g.W = W;
+    g.image_stride = (long long)image_rows * ld;
     g.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
     g.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
     // A tile's window spans floor(s * (tile - 1)) + 3 source rows / columns, one more where the rounded products straddle an integer;
@@ -293,60 +341,98 @@ int make_geo(const float* logits, int h, int w, int K, int64_t ld, int H, int W,
     return AVL_OK;
 }
 
-dim3 tiles(int H, int W) { return dim3((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH)); }
+dim3 tiles(int H, int W, int n = 1) { return dim3((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH), (unsigned)n); }
+
+int upsample(const char* what, const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, float* out, int H, int W,
+             void* stream) {
+    Geo g;
+    if (int rc = make_geo(logits, n, image_rows, h, w, K, ld, H, W, g, what)) return rc;
+    if (K > 256) return set_error(AVL_E_UNSUPPORTED, "%s: K = %d > 256 classes", what, K);
+    AVL_REQUIRE(out, "%s: out is NULL", what);
+    AVL_REQUIRE(aligned(out, 4), "%s: out is not 4-byte aligned", what);
+    if (n > 1) hipLaunchKernelGGL(k_upsample_logits<true>, tiles(H, W, n), dim3(kThreads), g.win_cap * sizeof(float), as_stream(stream), g, out);
+    else hipLaunchKernelGGL(k_upsample_logits<false>, tiles(H, W), dim3(kThreads), g.win_cap * sizeof(float), as_stream(stream), g, out);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+int64_t scratch_bytes(const char* what, int n, int H, int W) {
+    if (n < 1 || n > kMaxBatch) return set_error(AVL_E_ARG, "%s: n = %d images (1 .. %d)", what, n, kMaxBatch);
+    if (H <= 0 || W <= 0) return set_error(AVL_E_ARG, "%s: size %d x %d", what, H, W);
+    const dim3 t = tiles(H, W);
+    return (int64_t)n * t.x * t.y * (sizeof(double) + 2 * sizeof(unsigned));
+}
+
+int eval(const char* what, const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, int H, int W, const uint8_t* gt,
+         int ignore_index, uint8_t* labels_out, unsigned long long* confusion, double* loss_out, unsigned long long* counts_out,
+         double* image_loss_out, unsigned long long* image_counts_out, void* scratch, void* stream) {
+    Geo g;
+    if (int rc = make_geo(logits, n, image_rows, h, w, K, ld, H, W, g, what)) return rc;
+    if (K > kMaxEvalClasses)
+        return set_error(AVL_E_UNSUPPORTED, "%s: K = %d > %d classes (LDS confusion histogram, uint8 labels)", what, K, kMaxEvalClasses);
+    const bool loss = loss_out || counts_out || scratch;
+    AVL_REQUIRE(!loss || (loss_out && counts_out && scratch), "%s: loss_out, counts_out and scratch go together", what);
+    AVL_REQUIRE(!image_loss_out == !image_counts_out, "%s: image_loss_out and image_counts_out go together", what);
+    AVL_REQUIRE(!image_loss_out || loss, "%s: image_loss_out and image_counts_out need loss_out, counts_out and scratch", what);
+    AVL_REQUIRE(labels_out || confusion || loss, "%s: nothing to compute (no labels_out, confusion or loss_out)", what);
+    AVL_REQUIRE(gt || (!confusion && !loss), "%s: the confusion matrix and the loss need a ground truth (gt is NULL)", what);
+    AVL_REQUIRE(!confusion || aligned(confusion, 8), "%s: confusion is not 8-byte aligned", what);
+    AVL_REQUIRE(!loss || (aligned(loss_out, 8) && aligned(counts_out, 8) && aligned(scratch, 8)),
+                "%s: loss_out, counts_out and scratch must be 8-byte aligned", what);
+    AVL_REQUIRE(!image_loss_out || (aligned(image_loss_out, 8) && aligned(image_counts_out, 8)),
+                "%s: image_loss_out and image_counts_out must be 8-byte aligned", what);
+    const dim3 grid = tiles(H, W, n);
+    const int nb = (int)(grid.x * grid.y);
+    const long long slabs = (long long)n * nb;
+    EvalOut e;
+    e.gt = gt;
+    e.ignore_index = ignore_index;
+    e.labels = labels_out;
+    e.confusion = confusion;
+    e.slab = loss ? static_cast<double*>(scratch) : nullptr;
+    hipStream_t s = as_stream(stream);
+    const size_t lds_bytes = ((confusion ? K * K : 0) + g.win_cap) * sizeof(float);
+    if (n > 1) hipLaunchKernelGGL(k_full_res_eval<true>, grid, dim3(kThreads), lds_bytes, s, g, e);
+    else hipLaunchKernelGGL(k_full_res_eval<false>, grid, dim3(kThreads), lds_bytes, s, g, e);
+    AVL_LAUNCH_CHECK();
+    if (loss) {
+        const unsigned* slab_cnt = reinterpret_cast<const unsigned*>(e.slab + slabs);
+        hipLaunchKernelGGL(k_eval_finalize, dim3(1), dim3(kThreads), 0, s, e.slab, slab_cnt, slab_cnt + slabs, nb, n, loss_out, counts_out,
+                           image_loss_out, image_counts_out);
+        AVL_LAUNCH_CHECK();
+    }
+    return AVL_OK;
+}
 
 }  // namespace
 }  // namespace avl
 
 extern "C" int avl_upsample_logits(const float* logits, int h, int w, int K, int64_t ld, float* out, int H, int W, void* stream) {
-    avl::Geo g;
-    if (int rc = avl::make_geo(logits, h, w, K, ld, H, W, g, "avl_upsample_logits")) return rc;
-    if (K > 256) return avl::set_error(AVL_E_UNSUPPORTED, "avl_upsample_logits: K = %d > 256 classes", K);
-    AVL_REQUIRE(out, "avl_upsample_logits: out is NULL");
-    AVL_REQUIRE(avl::aligned(out, 4), "avl_upsample_logits: out is not 4-byte aligned");
-    hipLaunchKernelGGL(avl::k_upsample_logits, avl::tiles(H, W), dim3(avl::kThreads), g.win_cap * sizeof(float), avl::as_stream(stream), g, out);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return avl::upsample("avl_upsample_logits", logits, 1, (int64_t)h * w, h, w, K, ld, out, H, W, stream);
 }
 
-extern "C" int64_t avl_seg_eval_scratch_bytes(int H, int W) {
-    if (H <= 0 || W <= 0) return avl::set_error(AVL_E_ARG, "avl_seg_eval_scratch_bytes: size %d x %d", H, W);
-    const dim3 t = avl::tiles(H, W);
-    return (int64_t)t.x * t.y * (sizeof(double) + 2 * sizeof(unsigned));
+extern "C" int avl_upsample_logits_batch(const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, float* out, int H,
+                                         int W, void* stream) {
+    return avl::upsample("avl_upsample_logits_batch", logits, n, image_rows, h, w, K, ld, out, H, W, stream);
+}
+
+extern "C" int64_t avl_seg_eval_scratch_bytes(int H, int W) { return avl::scratch_bytes("avl_seg_eval_scratch_bytes", 1, H, W); }
+
+extern "C" int64_t avl_seg_eval_scratch_bytes_batch(int n, int H, int W) {
+    return avl::scratch_bytes("avl_seg_eval_scratch_bytes_batch", n, H, W);
 }
 
 extern "C" int avl_seg_eval_full_res(const float* logits, int h, int w, int K, int64_t ld, int H, int W, const uint8_t* gt,
                                      int ignore_index, uint8_t* labels_out, unsigned long long* confusion, double* loss_out,
                                      unsigned long long* counts_out, void* scratch, void* stream) {
-    avl::Geo g;
-    if (int rc = avl::make_geo(logits, h, w, K, ld, H, W, g, "avl_seg_eval_full_res")) return rc;
-    if (K > avl::kMaxEvalClasses)
-        return avl::set_error(AVL_E_UNSUPPORTED, "avl_seg_eval_full_res: K = %d > %d classes (LDS confusion histogram, uint8 labels)", K,
-                              avl::kMaxEvalClasses);
-    const bool loss = loss_out || counts_out || scratch;
-    AVL_REQUIRE(!loss || (loss_out && counts_out && scratch), "avl_seg_eval_full_res: loss_out, counts_out and scratch go together");
-    AVL_REQUIRE(labels_out || confusion || loss, "avl_seg_eval_full_res: nothing to compute (no labels_out, confusion or loss_out)");
-    AVL_REQUIRE(gt || (!confusion && !loss), "avl_seg_eval_full_res: the confusion matrix and the loss need a ground truth (gt is NULL)");
-    AVL_REQUIRE(!confusion || avl::aligned(confusion, 8), "avl_seg_eval_full_res: confusion is not 8-byte aligned");
-    AVL_REQUIRE(!loss || (avl::aligned(loss_out, 8) && avl::aligned(counts_out, 8) && avl::aligned(scratch, 8)),
-                "avl_seg_eval_full_res: loss_out, counts_out and scratch must be 8-byte aligned");
-    const dim3 grid = avl::tiles(H, W);
-    const int nb = (int)(grid.x * grid.y);
-    avl::EvalOut e;
-    e.gt = gt;
-    e.ignore_index = ignore_index;
-    e.labels = labels_out;
-    e.confusion = confusion;
-    e.slab_sum = loss ? static_cast<double*>(scratch) : nullptr;
-    e.slab_cnt = loss ? reinterpret_cast<unsigned*>(e.slab_sum + nb) : nullptr;
-    e.slab_inv = loss ? e.slab_cnt + nb : nullptr;
-    hipStream_t s = avl::as_stream(stream);
-    const size_t lds_bytes = ((confusion ? K * K : 0) + g.win_cap) * sizeof(float);
-    hipLaunchKernelGGL(avl::k_full_res_eval, grid, dim3(avl::kThreads), lds_bytes, s, g, e);
-    AVL_LAUNCH_CHECK();
-    if (loss) {
-        hipLaunchKernelGGL(avl::k_eval_finalize, dim3(1), dim3(avl::kThreads), 0, s, e.slab_sum, e.slab_cnt, e.slab_inv, nb, loss_out, counts_out);
-        AVL_LAUNCH_CHECK();
-    }
-    return AVL_OK;
+    return avl::eval("avl_seg_eval_full_res", logits, 1, (int64_t)h * w, h, w, K, ld, H, W, gt, ignore_index, labels_out, confusion, loss_out,
+                     counts_out, nullptr, nullptr, scratch, stream);
+}
+
+extern "C" int avl_seg_eval_full_res_batch(const float* logits, int n, int64_t image_rows, int h, int w, int K, int64_t ld, int H, int W,
+                                           const uint8_t* gt, int ignore_index, uint8_t* labels_out, unsigned long long* confusion,
+                                           double* loss_out, unsigned long long* counts_out, double* image_loss_out,
+                                           unsigned long long* image_counts_out, void* scratch, void* stream) {
+    return avl::eval("avl_seg_eval_full_res_batch", logits, n, image_rows, h, w, K, ld, H, W, gt, ignore_index, labels_out, confusion,
+                     loss_out, counts_out, image_loss_out, image_counts_out, scratch, stream);
 }

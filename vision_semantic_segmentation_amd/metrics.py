@@ -2,7 +2,7 @@
 matrix kept as an int64 tensor on the device until it is read.
 
     metric = MeanIOU(num_class)
-    loss = seg.validate_step(image, label, metric)     # the fused HIP path adds the frame's counts (batch of one)
+    loss = seg.validate_step(image, label, metric)     # the fused HIP path adds the counts of the frame, or of a batch [N, h, w, 3]
     metric.evaluate(preds, labels)                     # or: full-res logits [B, K, H, W] through torch ops (not the hot path)
     metric.synchronize_between_processes()
     print(metric.global_avg)

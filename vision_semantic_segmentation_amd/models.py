@@ -8,6 +8,7 @@ N x 3 x H x W tensors run unchanged on the evaluation path.
     model.eval()
     with torch.no_grad():
         logits = model(x)                                      # fp32 [N, K, H, W]; upsample_pred=False: [N, K, H', W']
+    loss = net.validate_step(x, label, val_metric)             # the validation step for the batch, fused (no [N, K, H, W] tensor)
 
 The weights are BUFFERS named as the reference checkpoint's keys (plus one ``num_batches_tracked`` per BatchNorm, accepted and
 unused), so ``state_dict()``, strict ``load_state_dict``, ``.cuda()`` / ``.to()`` and the ``module.`` prefix of a one-GPU
@@ -24,7 +25,7 @@ from .network import random_state_dict, refine_kernel_sizes, state_spec
 from .semantic_segmentation import SemanticSegmentation
 
 # build-specific MODEL.* settings build_model() hands on when the configuration has them (config.py)
-MODEL_OPTIONS = ("MIXED_GCONV_MX", "MIXED_TRUNK_FP4", "MIXED_CONV2_SPLIT", "MIXED_LAYER1_LO", "HIP_GRAPH")
+MODEL_OPTIONS = ("MIXED_GCONV_MX", "MIXED_TRUNK_FP4", "MIXED_CONV2_SPLIT", "MIXED_LAYER1_LO", "HIP_GRAPH", "VALIDATE_BATCH")
 PRECISIONS = ("mixed", "split16", "f32", "f16", "bf16")
 
 
@@ -132,6 +133,12 @@ class DeepLabV3Plus(nn.Module):
     def forward(self, x, upsample_pred=True):
         """x: normalised float [N, 3, H, W] -> fp32 logits [N, K, H, W] (upsample_pred=True, F.interpolate with align_corners=True)
         or [N, K, H', W'] (H/4 - sum(k_i - 1), module docstring), in a new tensor without grad_fn."""
+        self._check_call(x)
+        with torch.no_grad():
+            return self.segmentation().forward_tensor(x, upsample_pred=upsample_pred)
+
+    def _check_call(self, *tensors):
+        """what forward and validate_step refuse: train() mode, a DataParallel replica, tensors on another GPU than the buffers"""
         if self.training:
             raise NotImplementedError("DeepLabV3Plus here is inference only: call .eval() first (no training or backward)")
         if getattr(self, "_is_replica", False):
@@ -139,10 +146,20 @@ class DeepLabV3Plus(nn.Module):
         dev = self._device()
         if self._seg is not None and self._seg.device != dev:
             raise RuntimeError("DeepLabV3Plus: this module's plans live on %s, its buffers on %s (a DataParallel replica?)" % (self._seg.device, dev))
-        if isinstance(x, torch.Tensor) and x.is_cuda and x.device != dev:
-            raise RuntimeError("DeepLabV3Plus: input on %s, model on %s" % (x.device, dev))
+        for x in tensors:
+            if isinstance(x, torch.Tensor) and x.is_cuda and x.device != dev:
+                raise RuntimeError("DeepLabV3Plus: input on %s, model on %s" % (x.device, dev))
+
+    def validate_step(self, x, label, metric=None):
+        """The reference's validation step (train.py:138-141: preds = model(x); loss = loss_fn(preds, label); metric.evaluate(preds,
+        label)) for a batch, fused: x normalised float [N, 3, H, W] as forward takes it, label integer [N, H, W] (255 = ignored).
+        One forward of the batch plan, then one kernel at H x W that interpolates the logits, takes the arg-max, adds MeanIOU's
+        counts into `metric` (a metrics.MeanIOU, or None) and sums CrossEntropyLoss(ignore_index=255) in fp64; the up-sampled logits
+        are never written.  Returns the batch loss as a float (reduction='mean' over every counted pixel; NaN when all are 255).
+        Labels outside [0, K) and not 255 raise ValueError, as torch's cross_entropy does, and leave `metric` unchanged."""
+        self._check_call(x, label)
         with torch.no_grad():
-            return self.segmentation().forward_tensor(x, upsample_pred=upsample_pred)
+            return self.segmentation().validate_step_tensor(x, label, metric)
 
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):

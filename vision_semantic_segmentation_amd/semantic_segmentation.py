@@ -62,7 +62,7 @@ class SemanticSegmentation(object):
             self.state = random_state_dict(seed=getattr(cfg.MODEL, "SEED", 0), **kw)
         check_state_dict(self.state, **kw)
         self._nets = {}
-        self._heads = {}                   # (h, w) -> _FullResBuffers of the upsample_pred / validate_step paths
+        self._heads = {}                   # (h, w) or (h, w, N) -> _FullResBuffers of the upsample_pred / validate_step paths
         self._batch_out = {}               # ("labels" | "logits", h, w, N) -> full-resolution output of a batch
         # "mixed" self-check: the logits error of the mixed mode follows the WEIGHTS and was measured on seeded
         # draws only, so a real checkpoint is checked once, before its first plan, against the fp32-input HIP path (itself 2e-6 from
@@ -81,6 +81,7 @@ class SemanticSegmentation(object):
         if self.on_fail not in ("f32", "raise", "warn"):
             raise ValueError("MODEL.MIXED_ON_FAIL must be 'f32', 'raise' or 'warn', not %r" % self.on_fail)
         self.mixed_check = None            # {"size", "rel_err", "rung", "tried", ...} once the check has run
+        self.validate_batch = bool(getattr(cfg.MODEL, "VALIDATE_BATCH", False))      # validate_step also takes [N, h, w, 3]
 
     LADDER = ("mixed", "mixed+lo", "split16", "f32")
 
@@ -228,8 +229,8 @@ class SemanticSegmentation(object):
         upsample_pred=True: labels at the input's size [h, w] -- the arg-max of model(x, upsample_pred=True) (deeplab_v3_plus.py:67-69),
         from the fused full-resolution kernel (the upsampled logits are never written).  A view of a buffer owned per input size: the
         next call of the same size overwrites it.
-        A batch [N,h,w,3] runs through one plan of batch N -> [N, h', w'] ([N, h, w] with upsample_pred: the full-resolution
-        kernel once per image, on that image's logits)."""
+        A batch [N,h,w,3] runs through one plan of batch N -> [N, h', w'] ([N, h, w] with upsample_pred: one launch of the
+        full-resolution kernel for the batch, each image from its own logits)."""
         net, n, h, w = self._run(image_in)
         if n is None:
             if not upsample_pred:
@@ -241,8 +242,7 @@ class SemanticSegmentation(object):
         if not upsample_pred:
             return net.labels if n > 1 else net.labels.unsqueeze(0)
         out = self._batch_buffer("labels", (n, h, w), torch.uint8)
-        for i in range(n):
-            seg_head.full_res_eval(logits[i], h, w, labels_out=out[i])
+        seg_head.full_res_eval(logits, h, w, labels_out=out)
         return out
 
     def segmentation_device_raw(self, bgr, K=None, dist=None, factor=1):
@@ -273,9 +273,7 @@ class SemanticSegmentation(object):
             if not upsample_pred:
                 return logits.permute(0, 3, 1, 2)
             out = self._batch_buffer("logits", (n, self.num_classes, h, w), torch.float32)
-            for i in range(n):
-                seg_head.upsample_logits(logits[i], h, w, out=out[i])
-            return out
+            return seg_head.upsample_logits(logits, h, w, out=out)
         if not upsample_pred:
             return net.logits.permute(2, 0, 1)
         head = self._full_res(h, w)
@@ -287,46 +285,73 @@ class SemanticSegmentation(object):
         """DeepLabV3Plus.forward(x, upsample_pred) (deeplab_v3_plus.py:51-71) on the reference's own input: x = float [N,3,h,w],
         normalised as ToTensor + Normalize leave it (any float dtype; a CPU tensor is copied to the device).  Runs the plan of the rung
         the ladder picked, with the fp32-input stem (SegNet(input_format="f32_nchw")).  Returns a NEW fp32 tensor: the logits
-        [N,K,h',w'], or [N,K,h,w] with upsample_pred (F.interpolate(..., align_corners=True), seg_head.upsample_logits per image).
+        [N,K,h',w'], or [N,K,h,w] with upsample_pred (F.interpolate(..., align_corners=True), one seg_head.upsample_logits for the batch).
         An unbatched x [3,h,w] gives [K,h',w'] ([K,h,w]), as torch's convolutions treat an unbatched input."""
+        logits, unbatched, n, h, w = self._run_tensor(x)
+        if not upsample_pred:
+            out = logits.permute(0, 3, 1, 2).contiguous()
+        else:
+            out = seg_head.upsample_logits(logits, h, w)
+        return out[0] if unbatched else out
+
+    @staticmethod
+    def _tensor_geometry(x):
+        """x = float [N,3,h,w] or [3,h,w] -> (unbatched, N, h, w)"""
         if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or x.shape[-3] != 3 or not x.dtype.is_floating_point:
             raise ValueError("expected a float tensor [N, 3, h, w] or [3, h, w], got %s" % (
                 "%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
         unbatched = x.dim() == 3
-        xb = x.unsqueeze(0) if unbatched else x
-        n, h, w = int(xb.shape[0]), int(xb.shape[2]), int(xb.shape[3])
+        n = 1 if unbatched else int(x.shape[0])
         if n < 1:
             raise ValueError("an empty batch")
+        return unbatched, n, int(x.shape[-2]), int(x.shape[-1])
+
+    def _run_tensor(self, x):
+        """one forward of the "f32_nchw" plan for x (_tensor_geometry) -> (its logits as [N,h',w',K], unbatched, N, h, w)"""
+        unbatched, n, h, w = self._tensor_geometry(x)
         net = self.net_for(h, w, batch=n, input_format="f32_nchw")
-        net.forward(xb[0] if n == 1 else xb)
+        net.forward(x if unbatched or n > 1 else x[0])
         logits = net.logits if n > 1 else net.logits.unsqueeze(0)          # [N, h', w', K]
-        if not upsample_pred:
-            out = logits.permute(0, 3, 1, 2).contiguous()
-        else:
-            out = torch.empty((n, self.num_classes, h, w), dtype=torch.float32, device=self.device)
-            for i in range(n):
-                seg_head.upsample_logits(logits[i], h, w, out=out[i])
-        return out[0] if unbatched else out
+        return logits, unbatched, n, h, w
 
     def validate_step(self, image_in, label, metric=None):
-        """The reference's validation step for a batch of one (train.py:138-141: preds = model(x); loss = loss_fn(preds, label);
+        """The reference's validation step (train.py:138-141: preds = model(x); loss = loss_fn(preds, label);
         metric.evaluate(preds, label)) on the current plan: one forward, then ONE fused kernel at the input's resolution that
         interpolates the logits, takes the arg-max, adds MeanIOU's counts into `metric` (a metrics.MeanIOU, or None) and sums
         CrossEntropyLoss(ignore_index=255) in fp64.  image_in: uint8 RGB [h, w, 3]; label: int64 or uint8 [h, w] (ndarray or tensor).
         Returns the frame's loss (NaN when every label is 255).  Labels outside [0, K) and not 255 raise ValueError, as torch's
-        cross_entropy does, and then leave `metric` unchanged."""
-        if image_in.ndim != 3:
-            raise NotImplementedError("validate_step takes one image [h, w, 3], not shape %s" % (tuple(image_in.shape),))
-        h, w = int(image_in.shape[0]), int(image_in.shape[1])
-        head = self._full_res(h, w)
-        head.gt.copy_(self._label_u8(label, h, w), non_blocking=True)
-        net = self.net_for(h, w)
-        net.forward(image_in)
+        cross_entropy does, and then leave `metric` unchanged.
+        With MODEL.VALIDATE_BATCH = True also a batch: image_in [N, h, w, 3] with label [N, h, w] ([1, h, w, 3] is a batch of one) ->
+        one forward of the batch-N plan and one fused pass over the batch; the loss is the mean over every counted pixel of the
+        batch (reduction='mean'), and an invalid label in any image raises and leaves `metric` unchanged.  Without it (the default)
+        anything but one image raises NotImplementedError, as it always has."""
+        if image_in.ndim != 3 and not self.validate_batch:
+            raise NotImplementedError("validate_step takes one image [h, w, 3], not shape %s (MODEL.VALIDATE_BATCH = True lets it take a "
+                                      "batch [N, h, w, 3])" % (tuple(image_in.shape),))
+        n, h, w = self._geometry(image_in)
+        head = self._full_res(h, w, n)
+        head.gt.copy_(self._label_u8(label, h, w, n), non_blocking=True)
+        net = self.net_for(h, w, batch=n or 1)
+        net.forward(image_in[0] if n == 1 else image_in)
+        logits = net.logits.unsqueeze(0) if n == 1 else net.logits
+        return self._eval_into(head, logits, h, w, metric)
+
+    def validate_step_tensor(self, x, label, metric=None):
+        """validate_step on the reference's own input: x = normalised float [N, 3, h, w] (forward_tensor's) with label [N, h, w], or
+        one image [3, h, w] with [h, w].  One forward of the "f32_nchw" plan and one fused pass over the batch; returns the batch loss."""
+        unbatched, n, h, w = self._tensor_geometry(x)
+        head = self._full_res(h, w, None if unbatched else n)
+        head.gt.copy_(self._label_u8(label, h, w, None if unbatched else n), non_blocking=True)
+        logits = self._run_tensor(x)[0]
+        return self._eval_into(head, logits[0] if unbatched else logits, h, w, metric)
+
+    def _eval_into(self, head, logits, h, w, metric):
+        """the fused pass of validate_step: head.gt against `logits`; the counts go to `metric` only after the labels' check"""
         if metric is not None:
             if metric.num_class != self.num_classes:
                 raise ValueError("the metric counts %d classes, the network has %d" % (metric.num_class, self.num_classes))
             head.confusion.zero_()
-        seg_head.full_res_eval(net.logits, h, w, gt=head.gt, confusion=head.confusion if metric is not None else None,
+        seg_head.full_res_eval(logits, h, w, gt=head.gt, confusion=head.confusion if metric is not None else None,
                                workspace=head.workspace)
         res = head.workspace.result()
         if res["invalid"]:
@@ -336,11 +361,14 @@ class SemanticSegmentation(object):
             metric.add_confusion(head.confusion)
         return res["loss"]
 
-    def _label_u8(self, label, h, w):
-        """ground truth [h, w] (int64 / uint8 ndarray or tensor) -> uint8 tensor; values that uint8 cannot hold raise ValueError"""
+    def _label_u8(self, label, h, w, n=None):
+        """ground truth [h, w] ([n, h, w] for a batch of n) (int64 / uint8 ndarray or tensor) -> uint8 tensor; values that uint8 cannot
+        hold raise ValueError"""
         t = label if isinstance(label, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(label))
-        if tuple(t.shape) != (h, w):
+        if n is None and tuple(t.shape) != (h, w):
             raise ValueError("label has shape %s, the image is %d x %d" % (tuple(t.shape), h, w))
+        if n is not None and tuple(t.shape) != (n, h, w):
+            raise ValueError("label has shape %s, the batch is %d images of %d x %d" % (tuple(t.shape), n, h, w))
         if t.dtype == torch.uint8:
             return t
         if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
@@ -350,20 +378,21 @@ class SemanticSegmentation(object):
                              % (self.num_classes, seg_head.IGNORE_INDEX, int(t.min()), int(t.max())))
         return t.to(torch.uint8)
 
-    def _full_res(self, h, w):
-        """the buffers of the full-resolution paths for an h x w input (made on first use, kept per size)"""
-        key = (int(h), int(w))
+    def _full_res(self, h, w, n=None):
+        """the buffers of the full-resolution paths for an h x w input, or a batch of n (made on first use, kept per size and batch)"""
+        key = (int(h), int(w)) + (() if n is None else (int(n),))
         head = self._heads.get(key)
         if head is None:
-            head = _FullResBuffers(self.device, h, w, self.num_classes)
+            head = _FullResBuffers(self.device, h, w, self.num_classes, n)
             self._heads[key] = head
         return head
 
 
 class _FullResBuffers(object):
-    def __init__(self, device, h, w, num_classes):
+    def __init__(self, device, h, w, num_classes, n=None):
+        lead = () if n is None else (n,)   # a batch of n: validate_step's buffers only (its labels / logits outputs: _batch_buffer)
         self.logits = None                 # fp32 [K, h, w], allocated by the first logits(upsample_pred=True)
-        self.labels = torch.empty((h, w), dtype=torch.uint8, device=device)
-        self.gt = torch.empty((h, w), dtype=torch.uint8, device=device)
+        self.labels = torch.empty((h, w), dtype=torch.uint8, device=device) if n is None else None
+        self.gt = torch.empty(lead + (h, w), dtype=torch.uint8, device=device)
         self.confusion = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=device)
-        self.workspace = seg_head.EvalWorkspace(h, w, device)
+        self.workspace = seg_head.EvalWorkspace(h, w, device, batch=n or 1)

@@ -145,6 +145,39 @@ int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_
  * path 0 when not. */
 int avl_fused_frame_path(const avl_grid* g, int n, uint32_t bonus_classes);
 
+/* ---- a9v: several synchronised cameras against one cloud ------------------------------------ */
+
+/* The reference's mapper listens to /camera1/semantic and /camera6/semantic (src/mapping.py:57-58); image_callback picks the
+ * calibration by frame_id (:273-276) and looks the cloud and the pose up by the message's stamp (:280-285), so cameras
+ * triggered together project the SAME cloud with the SAME pose, once each.  This entry maps n_views such views in one pass:
+ * the result equals n_views calls of avl_fused_frame in view order (view v: P_host + 12 v, src_host[v]) on the same cloud --
+ * bit for bit, for AVL_F32 and AVL_F64 maps.  A point is loaded, moved by T_host and range-tested (:371,:378) once, and its grid
+ * cell (:403-409, from the ORIGINAL coordinates, the same for every camera) is computed once; it is then projected through
+ * every view's P (:375, float64, the truncation rules of avl_fused_frame) and that view's label is fetched as avl_fused_frame
+ * fetches it.  The 32-bit word of cell_mask holds one vote byte per view (bit i = class i seen, bit C + r = lane bonus of the
+ * r-th class of bonus_classes), OR-ed with one atomic per point; each touched cell is then updated once, view 0's votes first,
+ * inside a view class i (+= CM[:, i], :424) and then its bonus (+2, :437), rounding to the map type after every addition.
+ * Limits: 1 <= n_views <= AVL_MAX_VIEWS, and for n_views >= 2 also C + popcount(bonus_classes) <= 8 (AVL_E_ARG otherwise).
+ * Source and image sizes are shared by the views (a batched plan has one size); src_host is a HOST array of n_views device
+ * pointers.  n_views == 1 forwards to avl_fused_frame.  The scratch contract of avl_grid holds: cell_mask and counter[4 ..) are
+ * all zero on return, so single-view and multi-view calls may alternate on one grid. */
+#define AVL_MAX_VIEWS 4
+int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                          int n_views, const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
+                          int src_kind, const uint8_t* const* src_host /* n_views device pointers */,
+                          int src_w, int src_h, int img_w, int img_h,
+                          const uint32_t* lut_host, const uint8_t* label_colors_host,
+                          const double* cm_host, uint32_t bonus_classes, void* stream);
+
+/* The path avl_fused_frame_views takes (host only: sizes and pointer values).  AVL_E_ARG for what the call itself refuses of
+ * g, n, n_views and bonus_classes.
+ *   n_views == 1: the value of avl_fused_frame_path (0 .. 3).
+ *   n_views >= 2:
+ *   4     word mask, 64 partitioned lists   the 64 lists               counter_len >= 132, touched_cap >= 64 x (list capacity
+ *                                                                      of n), n <= 250000 and 2n <= Hm*Wm
+ *   5     word mask                         sweep of the whole mask    everything else (any grid size, any alignment) */
+int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views, uint32_t bonus_classes);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

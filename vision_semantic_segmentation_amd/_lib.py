@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("AVL_HIP_LIB", os.path.join(_HERE, "libavl_hip.so"))  
 AVL_F32, AVL_F64, AVL_BF16, AVL_F16 = 0, 1, 2, 3
 AVL_SRC_RGB, AVL_SRC_CLASSMAP = 0, 1
 AVL_MAX_MAP_CLASSES = 16
+AVL_MAX_VIEWS = 4               # views of one avl_fused_frame_views call
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
 
 _lib = None
@@ -44,6 +45,9 @@ _SIGNATURES = {
     "avl_fused_frame": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
                              _vp, _vp, _vp, C.c_uint32, _vp]),
     "avl_fused_frame_path": (_i, [C.POINTER(AvlGrid), _i, C.c_uint32]),
+    "avl_fused_frame_views": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
+                                   _vp, _vp, _vp, C.c_uint32, _vp]),
+    "avl_fused_frame_views_path": (_i, [C.POINTER(AvlGrid), _i, _i, C.c_uint32]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -597,6 +597,223 @@ __global__ void __launch_bounds__(kBlock) k_grid_sweep_bytes(MapT* __restrict__ 
     }
 }
 
+// ================================================================ several cameras, one cloud (avl_fused_frame_views)
+// V synchronised cameras project the SAME cloud with the SAME pose (src/mapping.py:273-285), and the grid cell of a point comes
+// from its original coordinates (:403-409), not from the camera: every view of a point votes into one cell.  So one lane per
+// point loads it, applies T, tests the range and computes the cell ONCE, then projects through each view's P, fetches that
+// view's label and builds that view's vote byte (encode_vote_byte); the 32-bit word of cell_mask holds byte v for view v and
+// takes the votes of all views with one atomicOr.  The apply pass replays the bytes view by view (apply_views_word), which is
+// what V sequential frames do to the cell.
+constexpr int kMaxViews = AVL_MAX_VIEWS;
+static_assert(kMaxViews * 8 == 32, "one vote byte per view in the 32-bit mask word");
+
+struct ViewsParams {
+    double P[kMaxViews][12];
+    double T[16];
+    const unsigned char* src[kMaxViews];
+    double range_max;
+    int has_T, n_views, img_w, img_h;
+};
+
+// Word mask + partitioned touched lists: cast_vote_byte_lists with the whole word as the cell's mask.
+__device__ __forceinline__ void cast_vote_word_lists(unsigned* cell_mask, int* touched, int* counter, int cap, int cell, unsigned word) {
+    __shared__ int wg_count, wg_base;
+    if (threadIdx.x == 0) wg_count = 0;
+    __syncthreads();
+    bool first = false;
+    if (cell >= 0 && word != 0u) first = atomicOr(&cell_mask[cell], word) == 0u;   // this lane turned the word non-zero: it lists the cell
+    const unsigned long long m = __ballot(first);
+    const int lane = threadIdx.x & 63;
+    int wave_off = 0;
+    if (m != 0ull && lane == 0) wave_off = atomicAdd(&wg_count, __builtin_popcountll(m));
+    wave_off = __shfl(wave_off, 0);
+    __syncthreads();
+    const int list = blockIdx.x % kLists;
+    if (threadIdx.x == 0 && wg_count > 0) wg_base = atomicAdd(&counter[kListBase + list], wg_count);
+    __syncthreads();
+    // bounded like cast_vote_byte_lists: an entry past cap is dropped, never written outside the list
+    const int slot = wg_base + wave_off + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    if (first && slot < cap) touched[(long long)list * cap + slot] = cell;
+}
+
+// LISTS: 1 = word mask + partitioned lists (k_views_apply_lists), 0 = word mask only (k_views_sweep_words)
+template <int SRC, int LISTS>
+__global__ void __launch_bounds__(kBlock) k_views_vote(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LutParams lut,
+                                                       unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                       int* __restrict__ counter, int list_cap) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned word = 0;
+    if (k < pv.n) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        double v0 = x, v1 = y, v2 = z, v3 = 1.0;
+        if (vp.has_T) {
+            v0 = dot4(vp.T + 0, x, y, z, 1.0);
+            v1 = dot4(vp.T + 4, x, y, z, 1.0);
+            v2 = dot4(vp.T + 8, x, y, z, 1.0);
+            v3 = dot4(vp.T + 12, x, y, z, 1.0);
+        }
+        if ((0.0 < v0) && (v0 < vp.range_max)) cell = grid_cell(g, x, y, z);      // :378 and :404-411: the same for every view
+        if (cell >= 0) {
+            for (int v = 0; v < vp.n_views; ++v) {
+                const double p0 = dot4(vp.P[v] + 0, v0, v1, v2, v3);
+                const double p1 = dot4(vp.P[v] + 4, v0, v1, v2, v3);
+                const double p2 = dot4(vp.P[v] + 8, v0, v1, v2, v3);
+                const double rp2 = refine_rcp(p2);
+                const int ix = div_i32_numpy(p0, p2, rp2);
+                const int iy = div_i32_numpy(p1, p2, rp2);
+                if (ix < 0 || ix >= vp.img_w || iy < 0 || iy >= vp.img_h) continue;   // this view does not see the point
+                unsigned vote;
+                if (SRC == AVL_SRC_RGB) {
+                    const unsigned char* px = vp.src[v] + 3ll * ((long long)iy * src_w + ix);
+                    vote = vote_from_rg(g, px[0], px[1]);
+                } else {
+                    int sx = ix, sy = iy;                                              // the index rule of k_fused_vote
+                    if (src_w != vp.img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)vp.img_w)), src_w - 1);
+                    if (src_h != vp.img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)vp.img_h)), src_h - 1);
+                    vote = lut.lut[vp.src[v][(long long)sy * src_w + sx]];
+                }
+                vote = add_bonus(vote, g.bonus_classes, it);
+                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
+            }
+        }
+    }
+    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
+    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);                // fire and forget, as cast_vote_nolist
+}
+
+// One cell's word -> its grid row: view 0's votes, then view 1's, ...; inside a view class i adds CM[:, i], then its bonus +2,
+// and every addition is rounded to the map type -- the sequence V calls of avl_fused_frame run on the cell, so the row ends
+// bit-identical to theirs (a store to MapT and a reload between two views changes nothing: the value is already a MapT).
+template <typename MapT>
+__device__ __forceinline__ void apply_views_word(MapT* row, unsigned word, int C, unsigned bonus_classes, const CmParams& cm) {
+    double vals[AVL_MAX_MAP_CLASSES];
+#pragma unroll
+    for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+        if (c < C) vals[c] = (double)row[c];
+    for (; word != 0u; word >>= 8) {
+        const unsigned m = word & 0xffu;
+        if (m == 0u) continue;
+        int r = 0;
+        for (int i = 0; i < C; ++i) {
+            if (m & (1u << i)) {
+#pragma unroll
+                for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+                    if (c < C) vals[c] = (double)(MapT)(vals[c] + cm.cm[c * C + i]);
+            }
+            if ((bonus_classes >> i) & 1u) {
+                if (m & (1u << (C + r))) {
+#pragma unroll
+                    for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+                        if (c == i) vals[c] = (double)(MapT)(vals[c] + 2.0);
+                }
+                ++r;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+        if (c < C) row[c] = (MapT)vals[c];
+}
+
+// Partitioned lists -> grid: k_grid_apply_lists on mask words (same list geometry, same tickets).
+template <typename MapT>
+__global__ void __launch_bounds__(kBlock) k_views_apply_lists(MapT* __restrict__ map, int C, unsigned bonus_classes, CmParams cm,
+                                                              unsigned* __restrict__ mask, const int* __restrict__ touched,
+                                                              int* __restrict__ counter, int cap, int wgs_per_list) {
+    const int k = blockIdx.x % kLists, j = blockIdx.x / kLists;
+    const int n = min(counter[kListBase + k], cap);
+    const int* list = touched + (long long)k * cap;
+    for (int e = j * kBlock + threadIdx.x; e < n; e += wgs_per_list * kBlock) {
+        const int cell = list[e];
+        const unsigned m = mask[cell];
+        mask[cell] = 0u;
+        apply_views_word(map + (long long)cell * C, m, C, bonus_classes, cm);
+    }
+    __syncthreads();                  // every lane of this workgroup has read n
+    if (threadIdx.x == 0) {
+        const int t = atomicAdd(&counter[kListBase + kLists + k], 1);
+        if (t == wgs_per_list - 1) {
+            counter[kListBase + k] = 0;
+            counter[kListBase + kLists + k] = 0;
+        }
+    }
+}
+
+// Sweep of the word mask (dense clouds), built like k_grid_sweep_bytes: a workgroup takes kViewsSweepCells cells per round with
+// kViewsSweepVec independent 16-byte loads per lane in flight, compacts the non-zero words into an LDS list (local cell, word),
+// clears them, and then all lanes apply one listed cell each.  `vec` = the mask is 16-byte aligned; a last partial vector and
+// an unaligned mask go through bounds-checked dword accesses.
+constexpr int kViewsSweepVec = 4;
+constexpr int kViewsSweepCells = kBlock * kViewsSweepVec * 4;
+template <typename MapT>
+__global__ void __launch_bounds__(kBlock) k_views_sweep_words(MapT* __restrict__ map, int C, unsigned bonus_classes, CmParams cm,
+                                                              unsigned* __restrict__ mask, long long ncell, int vec) {
+    __shared__ unsigned short lcell[kViewsSweepCells];
+    __shared__ unsigned lword[kViewsSweepCells];
+    __shared__ int count;
+    const long long rounds = (ncell + kViewsSweepCells - 1) / kViewsSweepCells;
+    for (long long rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
+        if (threadIdx.x == 0) count = 0;
+        __syncthreads();
+        const long long base = rd * kViewsSweepCells;
+        uint4 v[kViewsSweepVec];
+#pragma unroll
+        for (int u = 0; u < kViewsSweepVec; ++u) {
+            const long long c0 = base + ((long long)u * kBlock + threadIdx.x) * 4;
+            if (vec && c0 + 4 <= ncell) v[u] = *reinterpret_cast<const uint4*>(mask + c0);
+            else v[u] = make_uint4(c0 < ncell ? mask[c0] : 0u, c0 + 1 < ncell ? mask[c0 + 1] : 0u, c0 + 2 < ncell ? mask[c0 + 2] : 0u,
+                                   c0 + 3 < ncell ? mask[c0 + 3] : 0u);
+        }
+        int mine = 0;
+#pragma unroll
+        for (int u = 0; u < kViewsSweepVec; ++u) mine += (v[u].x != 0u) + (v[u].y != 0u) + (v[u].z != 0u) + (v[u].w != 0u);
+        const int lane = threadIdx.x & 63;
+        int incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        int wave_base = 0;
+        if (lane == 63 && incl > 0) wave_base = atomicAdd(&count, incl);
+        wave_base = __shfl(wave_base, 63);
+        int slot = wave_base + incl - mine;
+        if (mine > 0) {
+#pragma unroll
+            for (int u = 0; u < kViewsSweepVec; ++u) {
+                if ((v[u].x | v[u].y | v[u].z | v[u].w) == 0u) continue;
+                const int local0 = (u * kBlock + threadIdx.x) * 4;
+                const long long c0 = base + local0;
+                auto take = [&](unsigned x, int j) {
+                    if (x != 0u) {
+                        lcell[slot] = (unsigned short)(local0 + j);
+                        lword[slot] = x;
+                        ++slot;
+                    }
+                };
+                take(v[u].x, 0);
+                take(v[u].y, 1);
+                take(v[u].z, 2);
+                take(v[u].w, 3);
+                if (vec && c0 + 4 <= ncell) *reinterpret_cast<uint4*>(mask + c0) = make_uint4(0u, 0u, 0u, 0u);
+                else {
+                    if (v[u].x != 0u) mask[c0] = 0u;
+                    if (v[u].y != 0u) mask[c0 + 1] = 0u;
+                    if (v[u].z != 0u) mask[c0 + 2] = 0u;
+                    if (v[u].w != 0u) mask[c0 + 3] = 0u;
+                }
+            }
+        }
+        __syncthreads();
+        const int n = count;
+        for (int k = threadIdx.x; k < n; k += kBlock)
+            apply_views_word(map + (base + lcell[k]) * C, lword[k], C, bonus_classes, cm);
+        __syncthreads();
+    }
+}
+
 // ================================================================ end-of-run rendering (src/renderer.py), SURVEY 8f row 3
 struct RenderParams {
     unsigned char colors[AVL_MAX_MAP_CLASSES * 3];
@@ -854,6 +1071,29 @@ bool use_scan(const avl_grid* g, int n, unsigned bonus) {
     return (long long)n * (byte_mask_ok(g, bonus) ? 1024 : 128) >= cells;
 }
 
+// ---- avl_fused_frame_views: lists (sparse) or sweep (dense) of the word mask
+// The lists cost what the cloud costs (a returning atomic per point that votes, one row visit per touched cell) and are paid once
+// per call, not once per view: the crossover of use_lists is kept.  The sweep reads Hm*Wm*4 bytes whatever the cloud and takes
+// any grid: it is the path for everything else.
+bool views_use_lists(const avl_grid* g, int n) {
+    if (g->counter_len < kListBase + 2 * kLists) return false;
+    if ((long long)list_geom(n).cap * kLists > g->touched_cap) return false;
+    return n <= 250000 && (long long)n * 2 <= (long long)g->Hm * g->Wm;
+}
+int views_check(int n_views, const uint8_t* const* src_host) {
+    if (n_views < 1) return avl::set_error(AVL_E_ARG, "n_views = %d (at least one view)", n_views);
+    if (n_views > kMaxViews) return avl::set_error(AVL_E_ARG, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    if (!src_host) return avl::set_error(AVL_E_ARG, "src_host is NULL");
+    for (int v = 0; v < n_views; ++v)
+        if (!src_host[v]) return avl::set_error(AVL_E_ARG, "view %d: semantic source is NULL", v);
+    return AVL_OK;
+}
+int views_bits_check(const avl_grid* g, uint32_t bonus) {
+    const int bits = g->C + __builtin_popcount(bonus);
+    if (bits > 8) return avl::set_error(AVL_E_ARG, "C + popcount(bonus_classes) = %d vote bits per view, the views mask holds 8", bits);
+    return AVL_OK;
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -999,6 +1239,97 @@ extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dt
     }
     if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
     return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
+}
+
+extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views, uint32_t bonus_classes) {
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    if (n_views == 1) return avl_fused_frame_path(g, n, bonus_classes);
+    GridParams gp;
+    int rc;
+    if ((rc = fill_grid(gp, g, nullptr, bonus_classes))) return rc;
+    if ((rc = views_bits_check(g, bonus_classes))) return rc;
+    AVL_REQUIRE(n >= 0, "n = %d", n);
+    return views_use_lists(g, n) ? 4 : 5;
+}
+
+extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                     int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                                     const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                     const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                     uint32_t bonus_classes, void* stream) {
+    int rc;
+    if ((rc = views_check(n_views, src_host))) return rc;
+    if (n_views == 1)
+        return avl_fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h,
+                               img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, stream);
+    PtsView pv;
+    ProjParams pp;
+    GridParams gp;
+    LutParams lut;
+    if ((rc = fill_pts(pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = fill_grid(gp, g, label_colors_host, bonus_classes))) return rc;
+    if ((rc = views_bits_check(g, bonus_classes))) return rc;
+    AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
+    AVL_REQUIRE(src_w > 0 && src_h > 0, "bad semantic source");
+    AVL_REQUIRE(cm_host, "cm_host is NULL");
+    memset(&lut, 0, sizeof(lut));
+    if (src_kind == AVL_SRC_RGB) {
+        AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
+        AVL_REQUIRE(src_w == img_w && src_h == img_h, "RGB source must be %dx%d", img_w, img_h);
+    } else {
+        AVL_REQUIRE(lut_host, "lut_host is NULL");
+        memcpy(lut.lut, lut_host, sizeof(lut.lut));
+    }
+    if (n == 0) return AVL_OK;
+    AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
+    ViewsParams vp;
+    memset(&vp, 0, sizeof(vp));
+    memcpy(vp.P, P_host, sizeof(double) * 12 * n_views);
+    memcpy(vp.T, pp.T, sizeof(vp.T));
+    for (int v = 0; v < n_views; ++v) vp.src[v] = src_host[v];
+    vp.range_max = range_max;
+    vp.has_T = pp.has_T;
+    vp.n_views = n_views;
+    vp.img_w = img_w;
+    vp.img_h = img_h;
+    CmParams cm;
+    memset(&cm, 0, sizeof(cm));
+    memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
+    hipStream_t s = avl::as_stream(stream);
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const bool lists = views_use_lists(g, n);
+    const ListGeom lg = list_geom(n);
+#define AVL_VV(SRC, LISTS) hipLaunchKernelGGL((k_views_vote<SRC, LISTS>), grid, block, 0, s, pv, vp, gp, src_w, src_h, lut, g->cell_mask, g->touched, g->counter, lg.cap)
+    if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VV(AVL_SRC_RGB, 1); else AVL_VV(AVL_SRC_RGB, 0); }
+    else { if (lists) AVL_VV(AVL_SRC_CLASSMAP, 1); else AVL_VV(AVL_SRC_CLASSMAP, 0); }
+#undef AVL_VV
+    AVL_LAUNCH_CHECK();
+    if (lists) {
+        if (g->map_dtype == AVL_F64)
+            hipLaunchKernelGGL(k_views_apply_lists<double>, dim3(lg.apply_wgs), block, 0, s, static_cast<double*>(g->map), g->C, bonus_classes, cm,
+                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
+        else
+            hipLaunchKernelGGL(k_views_apply_lists<float>, dim3(lg.apply_wgs), block, 0, s, static_cast<float*>(g->map), g->C, bonus_classes, cm,
+                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
+        // as in avl_fused_frame: only the apply kernel returns the list cursors to zero
+        if (hipGetLastError() != hipSuccess) {
+            (void)hipMemsetAsync(g->counter + kListBase, 0, 2 * kLists * sizeof(int), s);
+            return avl::set_error(AVL_E_HIP, "k_views_apply_lists did not launch");
+        }
+        return AVL_OK;
+    }
+    const long long ncell = (long long)g->Hm * g->Wm;
+    const long long rounds = (ncell + kViewsSweepCells - 1) / kViewsSweepCells;
+    const unsigned blocks = (unsigned)(rounds < 8192 ? rounds : 8192);
+    const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
+    if (g->map_dtype == AVL_F64)
+        hipLaunchKernelGGL(k_views_sweep_words<double>, dim3(blocks), block, 0, s, static_cast<double*>(g->map), g->C, bonus_classes, cm, g->cell_mask, ncell, vec);
+    else
+        hipLaunchKernelGGL(k_views_sweep_words<float>, dim3(blocks), block, 0, s, static_cast<float*>(g->map), g->C, bonus_classes, cm, g->cell_mask, ncell, vec);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
 }
 
 extern "C" int avl_colorize_labels(const uint8_t* labels, int lw, int lh, const uint8_t* palette_host, uint8_t* out,

@@ -382,6 +382,34 @@ class SemanticMapping(object):
             self.pose, self.pose_time = self.update_pose(msg.header.stamp)
             self.mapping(image_in, self.pose, camera_calibration)
 
+    def _camera_for(self, frame_id):
+        if frame_id == "camera1":
+            return self.cam1
+        if frame_id == "camera6":
+            return self.cam6
+        raise ValueError("cannot find camera for frame_id %s" % frame_id)
+
+    def image_callback_views(self, msgs):
+        """V semantic images of one trigger (mapping.py:261-290 once per message, with the stamps equal): every message names its
+        camera by frame_id (:273-276); the cloud and the pose are looked up once, by the first message's stamp -- V calls of
+        image_callback with one stamp pick the same pair V times (:280-285) -- and mapping_views() maps all of them in one pass."""
+        msgs = list(msgs)
+        if not msgs:
+            raise ValueError("image_callback_views needs at least one message")
+        stamp = msgs[0].header.stamp
+        self.logger.log("Mapping %d images at: %d.%09ds" % (len(msgs), stamp.secs, stamp.nsecs))
+        images = [m.data if isinstance(getattr(m, "data", None), (np.ndarray, torch.Tensor)) else _imgmsg_to_array(m) for m in msgs]
+        cameras = [self._camera_for(m.header.frame_id) for m in msgs]
+        with self._lock:
+            if self.depth_method in ["points_map", "points_raw"]:
+                if len(self.pcd_header_queue) == 0:
+                    return
+                self.pcd, self.pcd_time = self.update_pcd(stamp)
+            if len(self.pose_queue) == 0:
+                return
+            self.pose, self.pose_time = self.update_pose(stamp)
+            self.mapping_views(images, self.pose, cameras)
+
     # ------------------------------------------------------------------ per-frame hot path
     def mapping(self, semantic_image, pose, camera_calibration):
         """mapping.py:292-321 for the LiDAR depth methods: one fused project+vote+apply on the GPU.
@@ -399,6 +427,30 @@ class SemanticMapping(object):
             img = self._as_device_u8(semantic_image)
             self.frame_device(self.pcd, self.pcd_frame_id, img, pose, camera_calibration, src_kind="rgb")
         if self.save_map_to_file:                                                # mapping.py:323-345, both depth modes
+            self.save_map_to_file = False
+            self.finish_run()
+
+    def mapping_views(self, semantic_images, pose, cameras):
+        """mapping() for V colour images of one trigger: what V mapping() calls in view order do to the grid (bit for bit), to
+        input_list (one record per view, mapping.py:309-313) and to the save_map_to_file branch (:323-345), which the first of V
+        calls would run before the later views are in -- here it runs once, after the last view."""
+        semantic_images, cameras = list(semantic_images), list(cameras)
+        if len(semantic_images) != len(cameras) or not cameras:
+            raise ValueError("mapping_views needs one camera per semantic image, got %d and %d" % (len(semantic_images), len(cameras)))
+        if self.depth_method not in ["points_map", "points_raw"]:                 # planar mode has no cloud to share
+            for img, cam in zip(semantic_images, cameras):
+                self.update_map_planar(self.map_dev, self._as_device_u8(img), cam)
+                self.frames_mapped += 1
+        else:
+            if self.pcd is None:
+                return
+            if self.record_inputs:
+                for img in semantic_images:
+                    self.input_list.append({"pcd": np.array(_to_numpy(self.pcd)), "pcd_frame_id": self.pcd_frame_id,
+                                            "semantic_image": np.array(_to_numpy(img)), "pose": pose})
+            self.frame_device_views(self.pcd, self.pcd_frame_id, [self._as_device_u8(img) for img in semantic_images], pose, cameras,
+                                    src_kind="rgb")
+        if self.save_map_to_file:
             self.save_map_to_file = False
             self.finish_run()
 
@@ -464,6 +516,63 @@ class SemanticMapping(object):
         _lib.check(rc, "avl_fused_frame")
         self._map_host = None
         self.frames_mapped += 1
+
+    def frame_device_views(self, pcd, pcd_frame_id, semantics, pose, cameras, src_kind="classmap", image_size=None,
+                           net_palette=PALETTE_19, stream=None):
+        """V cameras on one cloud in one fused pass (avl_fused_frame_views): the grid ends bit-identical to V frame_device calls
+        in view order.  ``semantics``: a uint8 CUDA tensor [V,h,w] of class maps (a batched plan's label buffer goes in as it is)
+        or [V,H,W,3] of colour images (src_kind="rgb"), or a list of V such tensors of one size; ``cameras``: V calibrations.
+        More than AVL_MAX_VIEWS views, or more vote bits than a view's byte of the mask holds (classes + lane classes > 8), are
+        mapped by sequential frame_device calls."""
+        cameras = list(cameras)
+        V = len(cameras)
+        if V < 1:
+            raise ValueError("frame_device_views needs at least one camera")
+        want_dim = 3 if src_kind == "rgb" else 2
+        if isinstance(semantics, torch.Tensor):
+            if semantics.dim() != want_dim + 1 or int(semantics.shape[0]) != V:
+                raise ValueError("semantics has shape %s for %d %s views" % (tuple(semantics.shape), V, src_kind))
+            views = [semantics[v] for v in range(V)]
+        else:
+            views = list(semantics)
+            if len(views) != V:
+                raise ValueError("%d semantic sources for %d cameras" % (len(views), V))
+        shape = tuple(views[0].shape)
+        for t in views:
+            if tuple(t.shape) != shape or t.dtype != torch.uint8 or not t.is_cuda:
+                raise ValueError("the views' semantic sources must be uint8 CUDA tensors of one size")
+        if src_kind == "rgb":
+            assert len(shape) == 3 and shape[2] == 3
+            sh, sw = int(shape[0]), int(shape[1])
+            ih, iw = sh, sw
+            kind, lut = _lib.AVL_SRC_RGB, None
+        else:
+            assert len(shape) == 2
+            sh, sw = int(shape[0]), int(shape[1])
+            ih, iw = (sh, sw) if image_size is None else (int(image_size[0]), int(image_size[1]))
+            kind = _lib.AVL_SRC_CLASSMAP
+            lut = self._lut_host(net_palette)
+        bonus = self._bonus_classes()
+        if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
+            for t, cam in zip(views, cameras):
+                self.frame_device(pcd, pcd_frame_id, t, pose, cam, src_kind=src_kind, image_size=image_size, net_palette=net_palette,
+                                  stream=stream)
+            return
+        pts, n, dtype, pstride, cstride = self._points_view(pcd)
+        T = self._origin_to_velodyne(pose) if pcd_frame_id != "velodyne" else None
+        g = self.grid
+        g.ensure_capacity(n)
+        gs = g.struct()
+        views = [t.contiguous() for t in views]
+        src = (C.c_void_p * V)(*[t.data_ptr() for t in views])
+        P = _dbl(np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]))
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        rc = _lib.lib().avl_fused_frame_views(C.byref(gs), pts, n, dtype, pstride, cstride, V, P, _dbl(T) if T is not None else None,
+                                              float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut, self._colors_host(),
+                                              _dbl(self.confusion_matrix), bonus, C.c_void_p(s))
+        _lib.check(rc, "avl_fused_frame_views")
+        self._map_host = None
+        self.frames_mapped += V
 
     def project_pcd(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """mapping.py:357-389.  NumPy in, NumPy out: (pcd[:, mask] float64[4,M], label uint8[3,M]).

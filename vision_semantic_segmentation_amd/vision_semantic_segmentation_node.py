@@ -166,3 +166,47 @@ class VisionSemanticSegmentationNode(object):
         if self._ros_image_cls is not None:
             self._publish_ros(out, msg.header)
         return out
+
+    def image_callback_views(self, msgs):
+        """V raw frames of one trigger through ONE batched plan: each frame is pre-processed by preprocess_device with its own
+        camera's model (:83-98) into one [V, h, w, 3] buffer, a single segmentation_device call labels the batch, and every view
+        is colourised and published as image_callback does it.  Returns the plan's [V, h', w'] label tensor (CUDA uint8; also in
+        ``last_labels``), which SemanticMapping.frame_device_views takes as it is.  Frames of different sizes raise ValueError."""
+        msgs = list(msgs)
+        if not msgs:
+            raise ValueError("image_callback_views needs at least one message")
+        frames = []
+        for msg in msgs:
+            if isinstance(msg.data, (np.ndarray, torch.Tensor)):
+                bgr = msg.data
+            else:
+                from .mapping import _imgmsg_to_array
+                bgr = _imgmsg_to_array(msg)
+                if bgr.ndim != 3:
+                    raise ValueError("image_callback_views needs 3-channel images, got encoding %r" % (msg.encoding,))
+            frames.append(bgr)
+        h, w = int(frames[0].shape[0]), int(frames[0].shape[1])
+        for bgr in frames:
+            if (int(bgr.shape[0]), int(bgr.shape[1])) != (h, w):
+                raise ValueError("the frames of one trigger must have one size: %dx%d and %dx%d" % (h, w, int(bgr.shape[0]), int(bgr.shape[1])))
+        with self._lock:
+            factor = self._downscale_factor(h, w)
+            batch = None
+            for v, (msg, bgr) in enumerate(zip(msgs, frames)):
+                cam = {"camera1": self.cam1, "camera6": self.cam6}.get(msg.header.frame_id) if self.undistort else None
+                if factor is None:
+                    rgb = preprocess_area_device(bgr, cam, int(h * self.image_scale), int(w * self.image_scale))
+                else:
+                    rgb = preprocess_device(bgr, cam, factor)
+                if batch is None:
+                    batch = torch.empty((len(msgs),) + tuple(rgb.shape), dtype=torch.uint8, device=rgb.device)
+                batch[v].copy_(rgb)
+            labels = self.seg.segmentation_device(batch)
+            self.last_labels = labels
+            outs = [colorize_labels_device(labels[v], h, w, self.seg_color_ref).cpu().numpy() for v in range(len(msgs))]
+        for msg, out in zip(msgs, outs):
+            if self.publish is not None:
+                self.publish(msg.header.frame_id, out, msg.header)
+            if self._ros_image_cls is not None:
+                self._publish_ros(out, msg.header)
+        return labels

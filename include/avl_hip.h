@@ -207,7 +207,16 @@ int avl_preprocess_image_area(const uint8_t* bgr, int h, int w, const double* K_
  * (stream-ordered: a plan captured into a hipGraph serves camera1 and camera6 alike; K_host / dist_host as above, both NULL
  * = no undistortion).  Every activation type has such a stem: AVL_BF16 / AVL_F16 with w_layout 1 (the MFMA stem) and AVL_F32 with
  * w_layout 0 (the fp32 stem, same [ky][kx][ci][co] weights and fmaf chain as the plain one); a 16-bit stem with w_layout 0 is refused,
- * as are in_format AVL_IN_F32_CHW and batch > 1 (one raw frame). */
+ * as is in_format AVL_IN_F32_CHW.
+ * Two forms.  raw_batch = 0: ONE raw frame and one camera block; batch > 1 is refused (AVL_E_UNSUPPORTED).  raw_batch = 1: every image
+ * of the batch is a raw frame of the same size with a camera model of its own -- `in` = uint8 [batch][src_h][src_w][3],
+ * in_rows = batch * src_h * src_w, in2_ld = src_w, `in2` = batch camera blocks of AVL_STEM_CAMERA_BYTES each, block n for image n;
+ * in_h x in_w stays the network input of one image and the integer factor is checked per image.  Image n's result is bit for bit
+ * what the one-frame form gives on frame n with camera n; a block of all zeros means no undistortion for that image only, so one
+ * batch may mix undistorted and plain views.
+ * avl_stem_camera_set writes ONE block at camera_dev, which may be any 4-byte aligned device address: block n of a raw batch is
+ * (char*)in2 + n * AVL_STEM_CAMERA_BYTES.  It is stream-ordered in both forms, so a captured plan can get new cameras, for one image
+ * or for all, between two replays. */
 #define AVL_STEM_CAMERA_BYTES 64
 int avl_stem_camera_set(void* camera_dev, const double* K_host, const double* dist_host, void* stream);
 
@@ -375,7 +384,7 @@ typedef struct avl_seg_op {
     const void* in2;         /* GEMM: residual added before the ReLU, or NULL; GAP: fp32 scratch [256][C];
                                 DWCONV (ksize 3): 32 zero bytes (what a tap outside the image reads);
                                 STEM: NULL, or the camera block of a pre-processing stem (avl_stem_camera_set; any dtype,
-                                AVL_F32 with w_layout 0, AVL_BF16 / AVL_F16 with w_layout 1) */
+                                AVL_F32 with w_layout 0, AVL_BF16 / AVL_F16 with w_layout 1); `batch` blocks with raw_batch */
     void* out;
     const void* weight;      /* packed by the host, layout per kind (see network.py)            */
     const float* bias;       /* fp32 [out_c padded], or NULL                                    */
@@ -449,8 +458,8 @@ typedef struct avl_seg_op {
      * MX bundles keep their layout: image n's FP4 rows and scales sit at row offset n * h * w inside each plane and each C/256 slab,
      * the slab stride stays the total row count.  GAP: in2 = fp32 scratch [batch][256][C], out = fp32 [batch][out_ld]; GEMV: in and out
      * are [batch] vectors with strides in_ld / out_ld.  Every spatial kernel keeps its halo inside its own image, and every image
-     * computes exactly what a batch-1 op on it computes (bit for bit).  A pre-processing stem (in2 set) takes one image only
-     * (AVL_E_UNSUPPORTED otherwise). */
+     * computes exactly what a batch-1 op on it computes (bit for bit).  A pre-processing stem (in2 set) takes one image
+     * (AVL_E_UNSUPPORTED otherwise) unless it asks for a batch of raw frames with raw_batch = 1 (below). */
     int32_t batch;
     /* GEMM only: `bias` is fp32 [batch][w_rows] and output row r uses image r / (out_h * out_w)'s vector (the ASPP projection, whose
      * bias comes from each image's pooling branch).  Such a GEMM runs as one launch per image, so in_rows must cover the last image's
@@ -462,6 +471,12 @@ typedef struct avl_seg_op {
      * as it converts the fp32 value its uint8 table holds, so a float input equal to that value gives the u8 path's bits.  Not with a
      * pre-processing stem (in2 set); other ops must leave it 0. */
     int32_t in_format;
+    /* STEM with in2 only (a pre-processing stem); other ops must leave it 0.  0 = `in` is ONE raw BGR frame [src_h][src_w][3] and in2
+     * one camera block; batch > 1 is refused.  1 = every image of the batch is a raw frame: `in` = uint8 [batch][src_h][src_w][3],
+     * in_rows = batch * src_h * src_w, in2_ld = src_w, in2 = `batch` camera blocks of AVL_STEM_CAMERA_BYTES each (block n for image n,
+     * 4-byte aligned); in_h x in_w = the network input of one image.  batch 0 or 1 with raw_batch = 1 is one frame.  Not with
+     * AVL_IN_F32_CHW.  Any other value is AVL_E_ARG. */
+    int32_t raw_batch;
 } avl_seg_op;
 
 #define AVL_IN_U8_HWC 0

@@ -14,6 +14,7 @@ AVL_SRC_RGB, AVL_SRC_CLASSMAP = 0, 1
 AVL_MAX_MAP_CLASSES = 16
 AVL_MAX_VIEWS = 4               # views of one avl_fused_frame_views call
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
+AVL_STEM_CAMERA_BYTES = 64      # one camera block of a pre-processing stem (avl_stem_camera_set); a raw batch has one per image
 
 _lib = None
 _lock = threading.Lock()

@@ -788,19 +788,24 @@ int validate_conv_op(const avl_seg_op& op) {
     const long long in_pix = (long long)op.in_h * op.in_w * op_batch(op), out_pix = (long long)op.out_h * op.out_w * op_batch(op);
     switch (op.kind) {
         case AVL_OP_STEM:
-            if (op.in2 && op_batch(op) > 1)
-                return set_error(AVL_E_UNSUPPORTED, "a pre-processing stem (in2 = camera block) takes one raw frame: batch %d", op.batch);
+            if (op.in2 && op_batch(op) > 1 && !op.raw_batch)
+                return set_error(AVL_E_UNSUPPORTED, "a pre-processing stem (in2 = camera block) takes one raw frame unless raw_batch = 1: batch %d",
+                                 op.batch);
             AVL_REQUIRE(op.weight && op.bias && op.out_c == 64 && op.in_c == 3, "stem expects 3 -> 64 channels");
             AVL_REQUIRE(op.out_h == (op.in_h + 6 - 7) / 2 + 1 && op.out_w == (op.in_w + 6 - 7) / 2 + 1, "stem output size");
             AVL_REQUIRE(op.out_rows >= out_pix && op.out_ld >= 64 && (op.out_ld * es) % 16 == 0, "stem output buffer");
             AVL_REQUIRE(op.w_layout == 0 || (op.w_layout == 1 && is_half(op.dtype)), "stem weight layout %d", op.w_layout);
-            if (op.in2) {      // pre-processing in the loader: `in` is the raw BGR frame [in_rows / in2_ld][in2_ld][3], in2 the camera block
+            if (op.in2) {      // pre-processing in the loader: `in` is the raw BGR frame [src_h][in2_ld][3] (raw_batch: [batch] of them), in2 the camera block(s)
                 AVL_REQUIRE(is_half(op.dtype) ? op.w_layout == 1 : (op.dtype == AVL_F32 && op.w_layout == 0),
                             "a pre-processing stem is the MFMA kernel (16-bit, w_layout 1) or the fp32 kernel (AVL_F32, w_layout 0): dtype %d, w_layout %d",
                             op.dtype, op.w_layout);
-                AVL_REQUIRE(reinterpret_cast<uintptr_t>(op.in2) % 4 == 0, "stem camera block alignment");
-                AVL_REQUIRE(op.in2_ld > 0 && op.in_rows > 0 && op.in_rows % op.in2_ld == 0, "stem raw frame: in_rows = src_h * src_w, in2_ld = src_w");
-                const int src_w = op.in2_ld, src_h = op.in_rows / op.in2_ld, f = src_w / op.in_w;
+                AVL_REQUIRE(reinterpret_cast<uintptr_t>(op.in2) % 4 == 0, "stem camera block alignment: in2 (one block, or `batch` blocks of "
+                            "AVL_STEM_CAMERA_BYTES with raw_batch) must be 4-byte aligned");
+                // raw_batch: `batch` frames back to back, each src_h x src_w (op_batch is 1 otherwise: a batch was refused above)
+                const int nb = op_batch(op);
+                AVL_REQUIRE(op.in2_ld > 0 && op.in_rows > 0 && op.in_rows % nb == 0 && (op.in_rows / nb) % op.in2_ld == 0,
+                            "stem raw frame: in_rows %d is not batch %d * src_h * src_w for an integer src_h (in2_ld = src_w = %d)", op.in_rows, nb, op.in2_ld);
+                const int src_w = op.in2_ld, src_h = op.in_rows / nb / op.in2_ld, f = src_w / op.in_w;
                 AVL_REQUIRE(f >= 1 && op.in_w == src_w / f && op.in_h == src_h / f, "stem raw frame %dx%d does not scale to %dx%d by an integer factor",
                             src_h, src_w, op.in_h, op.in_w);
             } else {
@@ -899,9 +904,10 @@ int launch_preprocess_area(const unsigned char* bgr, int H, int W, const double*
 
 __global__ void k_set_camera(PreCamera q, PreCamera* out) { *out = q; }
 
-// writes the camera block a pre-processing stem reads (stream-ordered, so a captured plan can switch cameras between frames)
+// writes ONE camera block a pre-processing stem reads (stream-ordered, so a captured plan can switch cameras between frames);
+// image n of a raw batch reads the block at cam_dev + n * AVL_STEM_CAMERA_BYTES
 int launch_set_camera(void* cam_dev, const double* K, const double* dist, hipStream_t s) {
-    static_assert(sizeof(PreCamera) <= 64, "AVL_STEM_CAMERA_BYTES");
+    static_assert(sizeof(PreCamera) <= AVL_STEM_CAMERA_BYTES && AVL_STEM_CAMERA_BYTES % alignof(PreCamera) == 0, "AVL_STEM_CAMERA_BYTES");
     hipLaunchKernelGGL(k_set_camera, dim3(1), dim3(1), 0, s, make_pre_camera(K, dist), static_cast<PreCamera*>(cam_dev));
     AVL_LAUNCH_CHECK();
     return AVL_OK;

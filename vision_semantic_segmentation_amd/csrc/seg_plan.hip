@@ -20,7 +20,11 @@ int validate(const avl_seg_op& op, int index) {
     else if (op.in_format != AVL_IN_U8_HWC && op.in_format != AVL_IN_F32_CHW) rc = set_error(AVL_E_ARG, "in_format %d is not an AVL_IN_* value", op.in_format);
     else if (op.in_format != AVL_IN_U8_HWC && op.kind != AVL_OP_STEM) rc = set_error(AVL_E_ARG, "in_format %d is a stem field (other ops leave it 0)", op.in_format);
     else if (op.in_format == AVL_IN_F32_CHW && op.in2)
-        rc = set_error(AVL_E_UNSUPPORTED, "in_format AVL_IN_F32_CHW with a pre-processing stem (in2 set): that stem reads the raw uint8 frame");
+        rc = set_error(AVL_E_UNSUPPORTED, op.raw_batch ? "in_format AVL_IN_F32_CHW with raw_batch = 1: a batch of raw frames is uint8 [batch][src_h][src_w][3]"
+                                                       : "in_format AVL_IN_F32_CHW with a pre-processing stem (in2 set): that stem reads the raw uint8 frame");
+    else if (op.raw_batch != 0 && op.raw_batch != 1) rc = set_error(AVL_E_ARG, "raw_batch %d (0 = one raw frame, 1 = every image of the batch is a raw frame)", op.raw_batch);
+    else if (op.raw_batch && op.kind != AVL_OP_STEM) rc = set_error(AVL_E_ARG, "raw_batch is a stem field (other ops leave it 0)");
+    else if (op.raw_batch && !op.in2) rc = set_error(AVL_E_ARG, "raw_batch needs a pre-processing stem: in2 (the camera blocks) is NULL");
     else if (op.kind == AVL_OP_GEMM) rc = validate_gemm(op);
     else if (op.kind == AVL_OP_DWPW) rc = validate_dwpw(op);
     else if (op.kind == AVL_OP_BOTTLENECK) rc = validate_bottleneck(op);
@@ -60,7 +64,7 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
     switch (op.kind) {
         case AVL_OP_STEM:
             flops = 2.0 * out_pix * 64 * 147;
-            // in2: the raw camera frame is what is read; AVL_IN_F32_CHW: three fp32 values per pixel instead of three bytes
+            // in2: the raw camera frames are what is read (in_rows counts every frame of a raw batch); AVL_IN_F32_CHW: three fp32 values per pixel instead of three bytes
             bytes = (op.in2 ? (double)op.in_rows : in_pix) * (op.in_format == AVL_IN_F32_CHW ? 12 : 3) + out_pix * 64 * es;
             break;
         case AVL_OP_GEMM:

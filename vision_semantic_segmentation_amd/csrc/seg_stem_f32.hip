@@ -8,6 +8,7 @@
 // lane computes one output pixel x 64 channels with k_stem's fmaf chain: bias first, taps in [ky][kx][ci] order, the same
 // [ky][kx][ci][co] weights (wave-uniform addresses: scalar loads, v_fmac with an SGPR operand), ReLU, fp32 store.  The result is
 // therefore the same bits as avl_preprocess_image followed by the plain fp32 stem, without the RGB frame in between.
+// A batch of raw frames (avl_seg_op.raw_batch): image blockIdx.z, each with a camera block of its own, as in k_stem_mfma<PRE>.
 #include "seg_types.h"
 #include "seg_preprocess.h"
 
@@ -18,11 +19,15 @@ constexpr int F_TH = 8, F_TW = 32;                               // outputs per 
 constexpr int F_IH = 2 * F_TH + 5, F_IW = 2 * F_TW + 5;         // 21 x 69 input pixels
 constexpr int F_ROW = F_IW * 3;                                 // floats per LDS row
 
-__global__ void __launch_bounds__(256) k_stem_pre_f32(const unsigned char* __restrict__ bgr, int srcH, int srcW, int factor,
+__global__ void __launch_bounds__(256) k_stem_pre_f32(const unsigned char* __restrict__ bgr0, int srcH, int srcW, int factor,
                                                      const PreCamera* __restrict__ cam_dev, int H, int W,
                                                      const float* __restrict__ w, const float* __restrict__ bias,
-                                                     float* __restrict__ out, int OH, int OW, int out_ld, int tiles_x) {
+                                                     float* __restrict__ out0, int OH, int OW, int out_ld, int tiles_x) {
     __shared__ float tile[F_IH * F_ROW];
+    // batch of raw frames (raw_batch): frame blockIdx.z, its output rows and ITS camera block (AVL_STEM_CAMERA_BYTES apart)
+    const unsigned char* __restrict__ bgr = image_base(bgr0, (long long)srcH * srcW, 3);
+    float* __restrict__ out = image_base(out0, (long long)OH * OW, out_ld);
+    cam_dev = reinterpret_cast<const PreCamera*>(reinterpret_cast<const char*>(cam_dev) + (long long)blockIdx.z * AVL_STEM_CAMERA_BYTES);
     const int tid = threadIdx.x;
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
     const int oy0 = ty * F_TH, ox0 = tx * F_TW;
@@ -76,11 +81,12 @@ __global__ void __launch_bounds__(256) k_stem_pre_f32(const unsigned char* __res
 
 }  // namespace
 
-// (validated by validate_conv_op: AVL_F32, w_layout 0, one raw frame, in_rows = src_h * src_w, in2_ld = src_w, integer factor)
+// (validated by validate_conv_op: AVL_F32, w_layout 0, in_rows = batch * src_h * src_w -- batch > 1 only with raw_batch --, in2_ld = src_w,
+// integer factor)
 int launch_stem_pre_f32(const avl_seg_op& op, hipStream_t s) {
-    const int srcW = op.in2_ld, srcH = op.in_rows / op.in2_ld, factor = srcW / op.in_w;
+    const int srcW = op.in2_ld, srcH = op.in_rows / op_batch(op) / op.in2_ld, factor = srcW / op.in_w;
     const int tiles_x = (op.out_w + F_TW - 1) / F_TW, tiles_y = (op.out_h + F_TH - 1) / F_TH;
-    hipLaunchKernelGGL(k_stem_pre_f32, dim3(tiles_x * tiles_y), dim3(256), 0, s, static_cast<const unsigned char*>(op.in), srcH, srcW,
+    hipLaunchKernelGGL(k_stem_pre_f32, dim3(tiles_x * tiles_y, 1, op_batch(op)), dim3(256), 0, s, static_cast<const unsigned char*>(op.in), srcH, srcW,
                        factor, static_cast<const PreCamera*>(op.in2), op.in_h, op.in_w, static_cast<const float*>(op.weight), op.bias,
                        static_cast<float*>(op.out), op.out_h, op.out_w, op.out_ld, tiles_x);
     AVL_LAUNCH_CHECK();

@@ -12,7 +12,9 @@
 // integer factor) happens in the loader: `img` is then the RAW camera frame and every pixel of the LDS tile is
 // preprocessed_rgb() of seg_preprocess.h -- the function k_preprocess applies -- so the RGB network input is never written
 // to memory or re-read.  The 5-pixel halo of a tile is recomputed (x1.41 pixels), which costs less than
-// the round trip: the undistortion is ~60 double-precision flops per source pixel.
+// the round trip: the undistortion is ~60 double-precision flops per source pixel.  A batch of raw frames (avl_seg_op.raw_batch): image
+// blockIdx.z, whose frame, output rows and CAMERA BLOCK (AVL_STEM_CAMERA_BYTES apart) the workgroup moves to at entry; a one-frame
+// launch has z = 0.
 //
 // F32IN = an input already normalised by the caller (AVL_IN_F32_CHW: fp32 [3][H][W] planes, DeepLabV3Plus.forward's tensor): the
 // loader reads it plane by plane, coalesced along x, and writes (HT)v (SPLIT: and (HT)(v - (float)(HT)v) into tile_lo) -- the
@@ -35,7 +37,7 @@ struct StemArgs {
     HT* out;
     HT* out_lo;            // SPLIT: the result's lo plane
     int H, W, OH, OW, out_ld, tiles_x;
-    const PreCamera* cam;      // PRE: device memory (one captured graph serves both cameras)
+    const PreCamera* cam;      // PRE: device memory (one captured graph serves both cameras); one block per image of a batch
     int srcH, srcW, factor;    // PRE: the raw frame; H = srcH / factor, W = srcW / factor
 };
 
@@ -52,10 +54,15 @@ __global__ void __launch_bounds__(256) k_stem_mfma(StemArgs<HT> p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tx = blockIdx.x % p.tiles_x, ty = blockIdx.x / p.tiles_x;
     const int oy0 = ty * S_TH, ox0 = tx * S_TW;
-    if constexpr (!PRE) {       // batch: image blockIdx.z (a pre-processing stem takes one frame)
+    if constexpr (!PRE) {       // batch: image blockIdx.z
         p.img = image_base(p.img, (long long)p.H * p.W, F32IN ? 3 * (int)sizeof(float) : 3);     // (F32IN: `img` is the fp32 planes)
         p.out = image_base(p.out, (long long)p.OH * p.OW, p.out_ld);
         p.out_lo = image_base(p.out_lo, (long long)p.OH * p.OW, p.out_ld);
+    } else {                    // batch of raw frames (raw_batch): frame blockIdx.z, and ITS camera block (AVL_STEM_CAMERA_BYTES apart)
+        p.img = image_base(p.img, (long long)p.srcH * p.srcW, 3);
+        p.out = image_base(p.out, (long long)p.OH * p.OW, p.out_ld);
+        p.out_lo = image_base(p.out_lo, (long long)p.OH * p.OW, p.out_ld);
+        p.cam = reinterpret_cast<const PreCamera*>(reinterpret_cast<const char*>(p.cam) + (long long)blockIdx.z * AVL_STEM_CAMERA_BYTES);
     }
     const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
@@ -257,7 +264,7 @@ int launch_stem_typed(const avl_seg_op& op, hipStream_t s) {
     const int tiles_y = (op.out_h + S_TH - 1) / S_TH;
     a.cam = static_cast<const PreCamera*>(op.in2);
     a.srcW = op.in2_ld;
-    a.srcH = op.in2_ld > 0 ? op.in_rows / op.in2_ld : 0;
+    a.srcH = op.in2_ld > 0 ? op.in_rows / op_batch(op) / op.in2_ld : 0;      // (in_rows counts the frames of a raw batch)
     a.factor = op.in_w > 0 ? a.srcW / op.in_w : 1;
     const dim3 grid(a.tiles_x * tiles_y, 1, op_batch(op));
     if (op.in_format == AVL_IN_F32_CHW) {       // (validated: never with in2)
@@ -270,11 +277,11 @@ int launch_stem_typed(const avl_seg_op& op, hipStream_t s) {
     } else if (op.w_split) {
         if (!op.out_lo) return set_error(AVL_E_ARG, "split stem (w_split = 1): out_lo is NULL");
         if (op.in2)
-            hipLaunchKernelGGL((k_stem_mfma<HT, true, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((k_stem_mfma<HT, true, true>), grid, dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((k_stem_mfma<HT, false, true>), dim3(a.tiles_x * tiles_y, 1, op_batch(op)), dim3(256), 0, s, a);
     } else if (op.in2)
-        hipLaunchKernelGGL((k_stem_mfma<HT, true>), dim3(a.tiles_x * tiles_y), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_stem_mfma<HT, true>), grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL((k_stem_mfma<HT, false>), dim3(a.tiles_x * tiles_y, 1, op_batch(op)), dim3(256), 0, s, a);
     AVL_LAUNCH_CHECK();

@@ -49,6 +49,7 @@ class AvlSegOp(C.Structure):
         ("in3", C.c_void_p), ("in3_mx", C.c_void_p), ("in3_c", C.c_int32), ("in3_ld", C.c_int32),
         ("batch", C.c_int32), ("bias_per_image", C.c_int32),
         ("in_format", C.c_int32),
+        ("raw_batch", C.c_int32),
     ]
 
 
@@ -613,11 +614,15 @@ class SegNet(object):
     MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier")    # keyword switches of the "mixed" mode
 
     def __init__(self, state, height, width, precision="bf16", device=None, num_classes=19, output_stride=8, fuse_dwpw=True, raw_frame=None,
-                 part=None, backbone=DEFAULT_BACKBONE, batch=1, input_format="u8_hwc", **mixed_opts):
+                 part=None, backbone=DEFAULT_BACKBONE, batch=1, input_format="u8_hwc", raw_batch=False, **mixed_opts):
         """raw_frame = (src_h, src_w): the plan's input is the RAW BGR camera frame and the node's pre-processing
         (vision_semantic_segmentation_node.py:83-98: BGR->RGB, undistort, INTER_AREA by src_w // width) runs inside the stem's loader
         (every precision: the MFMA stem, or k_stem_pre_f32 for "f32"); ``set_camera`` chooses the camera model, ``forward`` takes the
         raw frame.
+        raw_batch = True (with raw_frame): every image of the batch is a raw frame of that size with a camera model of its own (the
+        frames of several cameras triggered together) -- ``forward`` takes uint8 [N,src_h,src_w,3] and ``set_camera(..., image=n)``
+        writes image n's model; image n's logits are bit for bit those of the one-frame raw plan on frame n with camera n.  Without it a
+        raw_frame plan takes one frame (batch > 1 is refused); every other op is what the plain batch = N plan emits.
         batch = N: the plan runs N images of height x width at once (DeepLabV3Plus.forward on an N x 3 x H x W batch); every op takes
         them packed densely, image n at pixel rows [n h w, (n + 1) h w) of each activation, and computes for each exactly what the
         batch-1 plan computes.
@@ -632,8 +637,15 @@ class SegNet(object):
         batch = int(batch)
         if batch < 1:
             raise ValueError("SegNet: batch %d < 1" % batch)
-        if batch > 1 and raw_frame is not None:
-            raise NotImplementedError("SegNet: a raw_frame plan (pre-processing stem) takes one camera frame; batch %d" % batch)
+        self.raw_batch = bool(raw_batch)
+        if self.raw_batch and raw_frame is None:
+            raise ValueError("SegNet: raw_batch=True asks for a batch of raw camera frames and needs raw_frame=(src_h, src_w)")
+        if self.raw_batch and (part is not None or input_format != "u8_hwc"):
+            raise NotImplementedError("SegNet: raw_batch=True takes uint8 camera frames through the whole network; not with part=%r or "
+                                      "input_format %r" % (part, input_format))
+        if batch > 1 and raw_frame is not None and not self.raw_batch:
+            raise NotImplementedError("SegNet: a raw_frame plan (pre-processing stem) takes one camera frame unless raw_batch=True; "
+                                      "batch %d" % batch)
         if batch > 1 and part is not None:
             raise NotImplementedError("SegNet: sub-plans (part=%r) take one image; batch %d" % (part, batch))
         self.batch = batch
@@ -974,7 +986,8 @@ class SegNet(object):
         shape = (3, H, W) if f32_in else ((H, W, 3) if self.raw_frame is None else self.raw_frame + (3,))
         self.image = torch.zeros(((self.batch,) if self.batch > 1 else ()) + shape, dtype=torch.float32 if f32_in else torch.uint8, device=dev)
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=dev)          # what a depthwise tap outside the image reads
-        self.camera_block = torch.zeros(64, dtype=torch.uint8, device=dev)       # AVL_STEM_CAMERA_BYTES: zeros = no undistortion
+        # AVL_STEM_CAMERA_BYTES per camera model, zeros = no undistortion; a raw batch has one block per image
+        self.camera_block = torch.zeros(_lib.AVL_STEM_CAMERA_BYTES * (self.batch if self.raw_batch else 1), dtype=torch.uint8, device=dev)
         self._keep += [self.image, self.zero_page, self.camera_block]
 
         h2, w2 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
@@ -988,7 +1001,7 @@ class SegNet(object):
             w_stem, stem_layout = self._dev(w.permute(2, 3, 1, 0).reshape(-1), torch.float32), 0   # [ky][kx][ci][co]
         b_stem = self._dev(b, torch.float32)
         stem = self._act(h2 * w2, 64, split=self.full_split)
-        raw = {} if self.raw_frame is None else dict(in2=self.camera_block.data_ptr(), in2_ld=self.raw_frame[1])
+        raw = {} if self.raw_frame is None else dict(in2=self.camera_block.data_ptr(), in2_ld=self.raw_frame[1], raw_batch=int(self.raw_batch))
         self._op("backbone.conv1", OP_STEM, in_=self.image.data_ptr(), out=stem.hi.data_ptr(), weight=w_stem.data_ptr(),
                  bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.numel() // 3, out_h=h2, out_w=w2,
                  out_c=64, out_ld=64, out_rows=stem.shape[0], ksize=7, stride=2, pad=3, dil=1, groups=1, relu=1, w_layout=stem_layout,
@@ -1318,21 +1331,31 @@ class SegNet(object):
             return self.logits_buf[:self.batch * n].view(self.batch, self.out_h, self.out_w, self.num_classes)
         return self.logits_buf[:n].view(self.out_h, self.out_w, self.num_classes)
 
-    def set_camera(self, K=None, dist=None, stream=None):
+    def set_camera(self, K=None, dist=None, stream=None, image=None):
         """raw_frame plans: the camera model the stem undistorts with (3x3 K, k1 k2 p1 p2 k3); None = no undistortion.
-        Stream-ordered, so it may change between two forwards of a captured plan."""
+        Stream-ordered, so it may change between two forwards of a captured plan.
+        A raw_batch plan keeps one model per image: image = n writes image n's, image = None writes every image's (one camera for all)."""
         assert self.raw_frame is not None, "set_camera needs a plan built with raw_frame"
         assert (K is None) == (dist is None)
+        blocks = self.camera_block.numel() // _lib.AVL_STEM_CAMERA_BYTES
+        if image is None:
+            which = range(blocks)
+        else:
+            if not 0 <= int(image) < blocks:
+                raise IndexError("set_camera: image %d of a plan with %d camera block(s)" % (image, blocks))
+            which = (int(image),)
         k = d = None
         if K is not None:
             k = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).ravel().tolist())
             d = (C.c_double * 5)(*np.asarray(dist, dtype=np.float64).ravel()[:5].tolist())
         s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-        _lib.check(_lib.lib().avl_stem_camera_set(C.c_void_p(self.camera_block.data_ptr()), k, d, C.c_void_p(s)), "avl_stem_camera_set")
+        for n in which:
+            _lib.check(_lib.lib().avl_stem_camera_set(C.c_void_p(self.camera_block.data_ptr() + n * _lib.AVL_STEM_CAMERA_BYTES), k, d, C.c_void_p(s)),
+                       "avl_stem_camera_set")
 
     def forward(self, image_u8=None, stream=None):
         """image_u8: CUDA/CPU uint8 [H,W,3] RGB ([N,H,W,3] for a plan of batch N > 1) -- or, for a raw_frame plan, the
-        [src_h,src_w,3] BGR camera frame -- (copied into the plan's input buffer) or None to reuse it.
+        [src_h,src_w,3] BGR camera frame ([N,src_h,src_w,3] with raw_batch) -- (copied into the plan's input buffer) or None to reuse it.
         An input_format "f32_nchw" plan takes a float tensor [3,H,W] ([N,3,H,W]) instead: another float dtype is converted and a CPU
         tensor copied, both by the copy into the plan's fp32 input buffer."""
         if image_u8 is not None:
@@ -1344,6 +1367,8 @@ class SegNet(object):
                     raise ValueError("this plan takes a float tensor of shape %s, not %s %s" % (tuple(self.image.shape), image_u8.dtype,
                                                                                                tuple(image_u8.shape)))
             else:
+                if self.raw_batch and self.batch == 1 and image_u8.dim() == 4:        # a raw batch of one frame
+                    image_u8 = image_u8[0]
                 assert tuple(image_u8.shape) == tuple(self.image.shape) and image_u8.dtype == torch.uint8
             self.image.copy_(image_u8, non_blocking=True)
         s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream

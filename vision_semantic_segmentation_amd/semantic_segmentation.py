@@ -85,31 +85,38 @@ class SemanticSegmentation(object):
 
     LADDER = ("mixed", "mixed+lo", "split16", "f32")
 
-    def net_for(self, h, w, raw_frame=None, batch=1, input_format="u8_hwc"):
+    def net_for(self, h, w, raw_frame=None, batch=1, input_format="u8_hwc", raw_batch=False):
         """The compiled plan for a batch of `batch` h x w network inputs (built on first use, kept per size, batch and input format).
-        raw_frame = (src_h, src_w): the plan that takes the raw BGR camera frame and pre-processes inside its first kernel (one frame only).
+        raw_frame = (src_h, src_w): the plan that takes the raw BGR camera frame and pre-processes inside its first kernel (one frame,
+        unless raw_batch=True: `batch` raw frames, each with a camera model of its own -- SegNet(raw_batch=True); its key ends in
+        "raw_batch", so it is neither the plain (h, w, N) plan nor the one-frame raw plan (h, w, 1, src_h, src_w)).
         input_format "f32_nchw": the plan takes normalised fp32 [N,3,h,w] tensors (SegNet); "u8_hwc" (default): uint8 RGB frames.
         The mixed self-check runs once, on h x w frames of a batch of one; the rung it picks serves every batch and input format."""
         batch = int(batch)
-        if batch > 1 and raw_frame is not None:
-            raise NotImplementedError("a raw_frame plan (pre-processing stem) takes one camera frame, not a batch of %d" % batch)
+        if raw_batch and raw_frame is None:
+            raise ValueError("raw_batch=True asks for a batch of raw camera frames and needs raw_frame=(src_h, src_w)")
+        if batch > 1 and raw_frame is not None and not raw_batch:
+            raise NotImplementedError("a raw_frame plan (pre-processing stem) takes one camera frame, not a batch of %d (raw_batch=True "
+                                      "builds the plan for a batch of raw frames)" % batch)
         key = (int(h), int(w), batch) + (() if raw_frame is None else (int(raw_frame[0]), int(raw_frame[1])))
         if input_format != "u8_hwc":
             key += (input_format,)
+        if raw_batch:
+            key += ("raw_batch",)
         if key not in self._nets:
             if self._self_check and self.precision == "mixed" and self.mixed_check is None:
                 self.check_mixed_against_f32(key[0], key[1])
             rung = self._rung if self.precision == "mixed" else self.precision
-            net = self._build(key[0], key[1], rung, raw_frame, batch, input_format)
+            net = self._build(key[0], key[1], rung, raw_frame, batch, input_format, raw_batch)
             if getattr(self.cfg.MODEL, "HIP_GRAPH", True):
                 net.capture_graph()
             self._nets[key] = net
         return self._nets[key]
 
-    def _build(self, h, w, rung, raw_frame=None, batch=1, input_format="u8_hwc"):
+    def _build(self, h, w, rung, raw_frame=None, batch=1, input_format="u8_hwc", raw_batch=False):
         """rung: a plan of the ladder ("mixed", "mixed+lo", "split16") or a plain precision ("f32", "f16", "bf16")"""
         kw = dict(device=self.device, num_classes=self.num_classes, raw_frame=raw_frame, output_stride=self.output_stride, backbone=self.backbone,
-                  batch=batch, input_format=input_format)
+                  batch=batch, input_format=input_format, raw_batch=raw_batch)
         if rung in ("f32", "f16", "bf16"):
             return SegNet(self.state, h, w, precision=rung, **kw)
         if rung == "split16":
@@ -254,6 +261,45 @@ class SemanticSegmentation(object):
         net = self.net_for(H // factor, W // factor, raw_frame=(H, W))
         net.set_camera(K, dist)
         return net.forward(bgr)
+
+    def segmentation_device_raw_batch(self, frames, Ks=None, dists=None, factor=1):
+        """segmentation_device_raw for the V frames of one trigger, each with its own camera, in ONE plan (net_for(raw_batch=True)):
+        frames = uint8 BGR [V,H,W,3] (ndarray or CUDA tensor) or a list of V equal-sized [H,W,3] frames; Ks[v] / dists[v] = view v's
+        3x3 K and (k1 k2 p1 p2 k3), None (per view, or Ks = dists = None for all) = that view is not undistorted.  Every frame is
+        copied straight into the plan's input buffer and pre-processed inside the stem's loader with its own camera block, so view
+        v's labels are bit for bit segmentation_device_raw(frames[v], Ks[v], dists[v], factor).  Returns the plan's uint8 CUDA labels
+        [V, h', w'] (V = 1 included).  The mixed self-check and its fall-back ladder apply as for every other plan."""
+        if isinstance(frames, (list, tuple)):
+            views = list(frames)
+        else:
+            if frames.ndim != 4:
+                raise ValueError("expected BGR frames [V, H, W, 3] or a list of [H, W, 3] frames, got shape %s" % (tuple(frames.shape),))
+            views = [frames[v] for v in range(int(frames.shape[0]))]
+        V = len(views)
+        if V < 1:
+            raise ValueError("an empty batch")
+        H, W = int(views[0].shape[0]), int(views[0].shape[1])
+        for f in views:
+            if tuple(f.shape) != (H, W, 3):
+                raise ValueError("the frames of one batch must have one size: %s and %s" % ((H, W, 3), tuple(f.shape)))
+        Ks = [None] * V if Ks is None else list(Ks)
+        dists = [None] * V if dists is None else list(dists)
+        if len(Ks) != V or len(dists) != V:
+            raise ValueError("%d frames, %d camera matrices, %d distortion vectors" % (V, len(Ks), len(dists)))
+        net = self.net_for(H // factor, W // factor, raw_frame=(H, W), batch=V, raw_batch=True)
+        for v in range(V):
+            net.set_camera(Ks[v], dists[v], image=v)
+        if isinstance(frames, (list, tuple)):
+            slots = net.image.view(V, H, W, 3)
+            for v, f in enumerate(views):
+                t = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))
+                if t.dtype != torch.uint8:
+                    raise ValueError("camera frames are uint8, not %s" % t.dtype)
+                slots[v].copy_(t, non_blocking=True)
+            labels = net.forward()
+        else:
+            labels = net.forward(frames)
+        return labels if V > 1 else labels.unsqueeze(0)
 
     def segmentation(self, image_in, upsample_pred=False):
         """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map ([h, w] with upsample_pred=True); a batch

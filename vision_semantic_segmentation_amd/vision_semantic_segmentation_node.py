@@ -168,9 +168,11 @@ class VisionSemanticSegmentationNode(object):
         return out
 
     def image_callback_views(self, msgs):
-        """V raw frames of one trigger through ONE batched plan: each frame is pre-processed by preprocess_device with its own
-        camera's model (:83-98) into one [V, h, w, 3] buffer, a single segmentation_device call labels the batch, and every view
-        is colourised and published as image_callback does it.  Returns the plan's [V, h', w'] label tensor (CUDA uint8; also in
+        """V raw frames of one trigger through ONE batched plan.  With an integer INTER_AREA factor (IMAGE_SCALE 1.0, 0.5, ...) the raw
+        frames go straight into the batched raw-frame plan (segmentation_device_raw_batch): each is pre-processed inside the stem's
+        loader with its own camera's model (:83-98), as image_callback does it for one frame.  Any other IMAGE_SCALE: each frame goes
+        through preprocess_area_device into one [V, h, w, 3] buffer and a single segmentation_device call labels the batch.  Every
+        view is colourised and published as image_callback does it.  Returns the plan's [V, h', w'] label tensor (CUDA uint8; also in
         ``last_labels``), which SemanticMapping.frame_device_views takes as it is.  Frames of different sizes raise ValueError."""
         msgs = list(msgs)
         if not msgs:
@@ -191,17 +193,18 @@ class VisionSemanticSegmentationNode(object):
                 raise ValueError("the frames of one trigger must have one size: %dx%d and %dx%d" % (h, w, int(bgr.shape[0]), int(bgr.shape[1])))
         with self._lock:
             factor = self._downscale_factor(h, w)
-            batch = None
-            for v, (msg, bgr) in enumerate(zip(msgs, frames)):
-                cam = {"camera1": self.cam1, "camera6": self.cam6}.get(msg.header.frame_id) if self.undistort else None
-                if factor is None:
+            cams = [{"camera1": self.cam1, "camera6": self.cam6}.get(msg.header.frame_id) if self.undistort else None for msg in msgs]
+            if factor is None:                                   # any other IMAGE_SCALE: the general area resize, one stand-alone kernel per view
+                batch = None
+                for v, (cam, bgr) in enumerate(zip(cams, frames)):
                     rgb = preprocess_area_device(bgr, cam, int(h * self.image_scale), int(w * self.image_scale))
-                else:
-                    rgb = preprocess_device(bgr, cam, factor)
-                if batch is None:
-                    batch = torch.empty((len(msgs),) + tuple(rgb.shape), dtype=torch.uint8, device=rgb.device)
-                batch[v].copy_(rgb)
-            labels = self.seg.segmentation_device(batch)
+                    if batch is None:
+                        batch = torch.empty((len(msgs),) + tuple(rgb.shape), dtype=torch.uint8, device=rgb.device)
+                    batch[v].copy_(rgb)
+                labels = self.seg.segmentation_device(batch)
+            else:                                                # pre-processing inside the batched stem's loader, one camera block per view
+                labels = self.seg.segmentation_device_raw_batch(frames, [None if c is None else c.K for c in cams],
+                                                                [None if c is None else c.dist for c in cams], factor)
             self.last_labels = labels
             outs = [colorize_labels_device(labels[v], h, w, self.seg_color_ref).cpu().numpy() for v in range(len(msgs))]
         for msg, out in zip(msgs, outs):

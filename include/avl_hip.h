@@ -427,6 +427,10 @@ typedef struct avl_seg_op {
     /* w_split = 2 (GEMM on gfx950's block-scaled matrix cores): `weight` is the plain f16 hi part [w_rows][K]; the correction
      * products run on MX-FP4 copies (OCP e2m1 elements, element 2i in the low nibble of byte i, one E8M0 scale per 32 values
      * along K) at 4x the f16 rate: Q4(W lo) x Q4(in hi) and, when in_lo is set, Q4(W hi) x Q4(in lo).
+     * The MX GEMM multiplies exactly what it is passed: `in` x `weight` in f16, the hi half of in_mx x the first half of w_mx, the
+     * lo half of in_mx x the second half of w_mx.  It reads the input's lo part from the BUNDLE's lo half only: in_lo (like
+     * AVL_MX_IN_LO) merely switches the second correction pass on, the plane it points to is never read (a NaN-filled plane gives
+     * the same bytes: tests/test_gpu_gemm_exact.py).
      * An "MX bundle" of a [rows][C] tensor (C % 256 == 0, dense rows) is laid out
      *     [FP4 plane of the hi part: rows x C/2 bytes][its scales: C/256 x rows x 8 bytes][the same two for the lo part]
      * w_mx: bundle of the weights (rows = w_rows; first Q4(W lo), then Q4(W hi)); in_mx: bundle of the input (rows = in_rows);

@@ -618,18 +618,35 @@ def _unbundle(buf, rows, c, half):
     return q, s, mx_dequant_fp4(q, s)
 
 
+def _unbundle_raw(buf, rows, c, half):
+    """(FP4 plane, scales) of one half of a bundle, not decoded"""
+    from vision_semantic_segmentation_amd.network import mx_bundle_bytes
+    hb = mx_bundle_bytes(rows, c)
+    b = buf[half * hb:(half + 1) * hb]
+    return b[:rows * (c // 2)].reshape(rows, c // 2), b[rows * (c // 2):].reshape(c // 256, rows, 8)
+
+
+def _unbundle_rows(buf, rows, c, half, r0, r1):
+    """the values of rows r0 .. r1 - 1 of one half of a bundle (decoding a whole load-test bundle takes longer than the test)"""
+    from vision_semantic_segmentation_amd.network import mx_dequant_fp4
+    q, s = _unbundle_raw(buf, rows, c, half)
+    return mx_dequant_fp4(q[r0:r1], s[:, r0:r1])
+
+
 @pytest.mark.parametrize("case", [  # (M, K, N, A split, residual split, out split, quantise output, relu)
-    (2600, 256, 512, False, None, False, False, True),
-    (2600, 256, 512, True, None, True, True, True),
-    (17000, 512, 1024, False, True, True, True, True),        # conv3-like: split residual and output, FP4 copy of the output
-    (34000, 512, 256, True, None, False, False, True),        # conv1-like: both corrections (128-row tiles: 266 of them)
-    (300, 2048, 2048, True, False, True, True, False),        # fewer rows than one tile, single-plane residual
-    (9000, 512, 1024, "fp4", "fp4", "fp4", True, True),       # the trunk form: every lo part only as FP4 (mx_flags)
+    # t256 = ceil(M / 256) * N / 256; launch_ring_mx takes 128-row tiles iff t256 < 192 or 256 < t256 < 384, 256-row tiles otherwise.  Every
+    # case that writes out_mx runs 128-row tiles; the quantising epilogue on 256-row tiles is checked in test_gpu_gemm_exact.py
+    (2600, 256, 512, False, None, False, False, True),        # t256 = 22: 128-row tiles
+    (2600, 256, 512, True, None, True, True, True),           # t256 = 22: 128-row tiles
+    (17000, 512, 1024, False, True, True, True, True),        # conv3-like: split residual and output, FP4 copy of the output (t256 = 268: 128-row tiles)
+    (34000, 512, 256, True, None, False, False, True),        # conv1-like: both corrections (t256 = 133: 128-row tiles, 266 of them)
+    (300, 2048, 2048, True, False, True, True, False),        # fewer rows than one 256-row tile, single-plane residual (t256 = 16: 128-row tiles)
+    (9000, 512, 1024, "fp4", "fp4", "fp4", True, True),       # the trunk form: every lo part only as FP4 (mx_flags) (t256 = 144: 128-row tiles)
     # K >= 1024 runs the software-pipelined stream (k_gemm_mx_pipe), K < 1024 the two-barrier kernel (k_gemm_ring_mx): the same forms again
-    (17000, 1024, 1024, "fp4", "fp4", "fp4", True, True),     # trunk form, more tiles than CUs, 256-row tiles
-    (34000, 1024, 256, True, None, False, False, True),       # both corrections, 128-row tiles
-    (9000, 1280, 512, False, True, True, True, True),         # odd number of K macro-blocks, split residual and output
-    # 256-row tiles without an FP4 copy of the output (192 .. 256 tiles of 256 x 256): both main loops
+    (17000, 1024, 1024, "fp4", "fp4", "fp4", True, True),     # trunk form, more tiles than CUs (t256 = 268: 128-row tiles, 532 of them)
+    (34000, 1024, 256, True, None, False, False, True),       # both corrections (t256 = 133: 128-row tiles)
+    (9000, 1280, 512, False, True, True, True, True),         # odd number of K macro-blocks, split residual and output (t256 = 72: 128-row tiles)
+    # 256-row tiles without an FP4 copy of the output (t256 = 48 * 4 = 192 tiles of 256 x 256): both main loops
     (12100, 512, 1024, False, None, False, False, True), (12100, 1024, 1024, True, None, True, False, True),
 ])
 def test_mx_gemm(case, cuda_device):
@@ -701,6 +718,24 @@ def test_mx_gemm(case, cuda_device):
         err = float((got + v_lo[:M] - ref).abs().max() / ref.abs().max())
         assert err <= 2 ** -11 * 0.3, "mx gemm %s: %.3e" % (case, err)
         assert float((v_hi[:M] - got).abs().max() / ref.abs().max()) <= 0.3      # the FP4 copy of the hi plane is a 2-3 bit image of it
+        # ... namely the host quantiser's image of the plane the kernel wrote, byte for byte, scales included
+        q_hi, s_hi = _unbundle_raw(out_mx.cpu(), Mp, N, 0)
+        q_ref, s_ref = mx_quant_fp4(out[0, :M].cpu().double())
+        assert torch.equal(s_hi[:, :M], s_ref), "trunk form: scales of Q4(hi) differ"
+        assert torch.equal(q_hi[:M], q_ref), "trunk form: Q4(hi) differs"
+        # Q4(lo) per 32-block (the rows carry scales from 2^-3 to 2^3, a bound on the global maximum says nothing about the small rows):
+        # the block maximum lands in [3.25, 6.5] scale units, where e2m1's widest step is 2 (4 .. 6), so an element is off by at most a
+        # quarter of ITS block's maximum.  The kernel quantises lo' = v' - hi with v' its fp32 sum: lo' - want_lo = v' - ref = d, the fp32
+        # accumulation error (<= TOL of max|ref|, the bar of every split-output case above), which also moves the block maximum by at most
+        # d: |Q4(lo') - want_lo| <= amax(lo') / 4 + d <= amax(want_lo) / 4 + 1.25 d
+        blk_amax = want_lo.reshape(M, N // 32, 32).abs().amax(dim=2, keepdim=True).expand(-1, -1, 32).reshape(M, N)
+        over = float(((v_lo[:M] - want_lo).abs() - 0.25 * blk_amax).clamp_min(0).max() / ref.abs().max())
+        assert over <= 1.25 * TOL, "trunk form: Q4(lo) is %.3e of max|ref| beyond a quarter of its block maximum" % over
+        # rows past M: the plane, and both FP4 planes and both scale slabs of the bundle, are untouched
+        assert torch.all(out[0, M:] == 7.0)
+        for half in (0, 1):
+            q_dev, s_dev = _unbundle_raw(out_mx.cpu(), Mp, N, half)
+            assert torch.all(q_dev[M:] == 0xEE) and torch.all(s_dev[:, M:] == 0xEE), "trunk form: bundle rows past M, half %d" % half
         return
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= (TOL if o_split else 2 ** -11 * 1.5), "mx gemm %s: %.3e" % (case, err)
@@ -718,11 +753,12 @@ def test_mx_gemm(case, cuda_device):
 @pytest.mark.parametrize("shape", [  # (M, K, N, correction passes, K of a second input appended along K or 0)
     # (round 5: sizes cut to ~40 % -- the host-side FP4 packing of the operands was most of this test's 85 s; every case still gives
     # each CU several tiles)
-    (256 * 300, 1024, 512, 2, 0),            # 256-row tiles, 2.3 tiles per CU
-    (256 * 140 + 77, 1024, 256, 1, 0),       # 128-row tiles (k_gemm_mx_pipe<., 4, ...>), weights-only correction, ragged last tile
-    (256 * 180, 512, 512, 2, 1024),          # conv3 + downsample form: the stream switches inputs at K macro-block 2 of 6 (set_input)
-    (256 * 140, 1024, 256, 2, 512),          # the same on 128-row tiles
-    (256 * 300, 512, 512, 2, 0),             # K < 1024: the two-barrier kernel k_gemm_ring_mx (kept: it runs the short-K layers)
+    # t256 = ceil(M / 256) * N / 256: 128-row tiles iff t256 < 192 or 256 < t256 < 384
+    (256 * 300, 1024, 512, 2, 0),            # t256 = 600: 256-row tiles, 2.3 tiles per CU
+    (256 * 140 + 77, 1024, 256, 1, 0),       # t256 = 141: 128-row tiles (k_gemm_mx_pipe<., 4, ...>), weights-only correction, ragged last tile
+    (256 * 180, 512, 512, 2, 1024),          # conv3 + downsample form: the stream switches inputs at K macro-block 2 of 6 (set_input); t256 = 360: 128-row tiles
+    (256 * 140, 1024, 256, 2, 512),          # the same at t256 = 140: 128-row tiles as well
+    (256 * 300, 512, 512, 2, 0),             # K < 1024: the two-barrier kernel k_gemm_ring_mx (kept: it runs the short-K layers); t256 = 600: 256-row tiles
 ])
 def test_mx_gemm_repeats_under_load(shape, cuda_device):
     """Race screen for the software-pipelined MX GEMM (k_gemm_mx_pipe, every case with K >= 1024: LDS slots re-filled by inline-asm
@@ -788,8 +824,10 @@ def test_mx_gemm_repeats_under_load(shape, cuda_device):
                 want = want + xb.double() @ w_hi[:, K:].double().t() + deq(xb) @ deq(w_lo[:, K:]).t() + deq(xbl) @ deq(w_hi[:, K:]).t()
             rr = r_hi[lo_:lo_ + want.shape[0]].double() + deq(r_lo[lo_:lo_ + want.shape[0]])
             want = torch.relu(want + rr)[:hi_ - lo_]
-            got = ref[lo_:hi_].cpu().double()
-            assert float((got - want).abs().max() / want.abs().max()) <= 2 ** -11 * 1.5
+            # value = f16 plane + the FP4 lo half of the bundle (AVL_MX_OUT_LO): the trunk bar of test_mx_gemm, inside which a dropped
+            # correction pass (~1e-4 of max|ref| on these operands) shows
+            got = ref[lo_:hi_].cpu().double() + _unbundle_rows(ref_mx.cpu(), Mp, N, 1, lo_, hi_)
+            assert float((got - want).abs().max() / want.abs().max()) <= 2 ** -11 * 0.3
         outs = [(torch.zeros_like(out), torch.zeros_like(out_mx)) for _ in range(4)]
         for i in range(60):
             _lib.lib().avl_seg_plan_run(plan, s)
@@ -840,7 +878,8 @@ def test_grouped_conv_writes_the_mx_bundle(case, cuda_device):
 def test_mx_gemm_with_a_second_input_along_k(ks, cuda_device):
     """conv3 + stride-1 downsample as ONE MX GEMM: out = relu(W3 . t2 + Wd . x + b3 + bd), both inputs with FP4-only lo parts
     (in3 / in3_mx of include/avl_hip.h).  Reference: float64 on the operands the kernel is given.  K1 + K2 < 1024 runs
-    k_gemm_ring_mx, the others the software-pipelined k_gemm_mx_pipe (256-row tiles; third case: 128-row tiles)."""
+    k_gemm_ring_mx, the others the software-pipelined k_gemm_mx_pipe.  t256 = ceil(M / 256) * N / 256 = 144, 268, 47, 72: all four run
+    128-row tiles (t256 < 192 or 256 < t256 < 384); the 256-row tiles with a second input are in test_gpu_gemm_exact.py."""
     import torch
     from vision_semantic_segmentation_amd import _lib
     from vision_semantic_segmentation_amd.network import (AVL_MX_IN_LO, AVL_MX_OUT_LO, OP_GEMM, AvlSegOp, mx_bundle_bytes, mx_dequant_fp4,
@@ -868,7 +907,7 @@ def test_mx_gemm_with_a_second_input_along_k(ks, cuda_device):
     dev = [(_pad_rows(hi, Mp).to(cuda_device), _bundle(hi, lo, Mp).to(cuda_device)) for hi, lo in ins]
     wd, wmx, bd = w_hi16.to(cuda_device), wbundle.to(cuda_device), b.to(cuda_device)
     out = torch.full((Mp, N), 7.0, dtype=torch.float16, device=cuda_device)
-    out_mx = torch.zeros(2 * mx_bundle_bytes(Mp, N), dtype=torch.uint8, device=cuda_device)
+    out_mx = torch.full((2 * mx_bundle_bytes(Mp, N),), 0xEE, dtype=torch.uint8, device=cuda_device)
     op = AvlSegOp()
     op.kind, op.dtype = OP_GEMM, _lib.AVL_F16
     op.in_, op.out, op.weight, op.bias = dev[0][0].data_ptr(), out.data_ptr(), wd.data_ptr(), bd.data_ptr()
@@ -884,6 +923,13 @@ def test_mx_gemm_with_a_second_input_along_k(ks, cuda_device):
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= 2 ** -11 * 0.3, "mx gemm with a second input: %.3e" % err
     assert torch.all(out[M:] == 7.0)
+    # Q4(hi): the host quantiser's bytes of the plane the kernel wrote; rows past M of both halves keep the sentinel
+    q_hi, s_hi = _unbundle_raw(out_mx.cpu(), Mp, N, 0)
+    q_ref, s_ref = mx_quant_fp4(out[:M].cpu().double())
+    assert torch.equal(s_hi[:, :M], s_ref) and torch.equal(q_hi[:M], q_ref), "Q4(hi) differs from the host quantiser"
+    for half in (0, 1):
+        q_dev, s_dev = _unbundle_raw(out_mx.cpu(), Mp, N, half)
+        assert torch.all(q_dev[M:] == 0xEE) and torch.all(s_dev[:, M:] == 0xEE), "bundle rows past M, half %d" % half
 
 
 @pytest.mark.parametrize("case", [(37, 53, 256, 1, 0), (20, 31, 512, 1, 0)])

@@ -313,6 +313,40 @@ int avl_seg_eval_full_res_batch(const float* logits, int n, int64_t image_rows, 
                                 unsigned long long* counts_out, double* image_loss_out, unsigned long long* image_counts_out,
                                 void* scratch, void* stream);
 
+/* ---- semantic extraction: per-class connected components and convex hulls (src/semantic_convex_hull.py:17-91, called from
+ * vision_semantic_segmentation_node.py:138-152; csrc/seg_hull.hip) ------------------------------------------------------------
+ * maps uint8 [n][h][w] label maps on the device; classes int32[n_classes] on the HOST, each 1 .. 255 (0 is the background, as in the
+ * reference, :33-35), n_classes 1 .. 64.  A plane is one (map, class) pair: plane p = image * n_classes + class position, P =
+ * n * n_classes <= 65535 planes run in the same launches.  Any h, w >= 1 with h * w < 2^31 - 1, h < 2^20, w < 2^21.
+ * Per plane: mask = (label == class) (:36-37); erode != 0: 3x3 erosion (:40-45), pixels outside the image do not erode (cv2.erode's
+ * default border; cv2 is absent where this was built, so that border is an assumption, not a pinned fact); erode = 0: the mask is
+ * taken as it is.  8-connected components (skimage.measure.label(connectivity=ndim), :51).
+ * Everything runs on `stream` without host synchronisation, and results are bit-for-bit reproducible (integers only).
+ * Argument errors (a NULL pointer, class 0 or above 255, top_number outside 1 .. 8, h or w below 1) return AVL_E_ARG before
+ * anything touches the device.  The library keeps no pointer after a call. */
+/* bytes of scratch avl_class_hulls needs (0 for sizes it refuses) */
+int64_t avl_hull_scratch_bytes(int h, int w, int planes, int top_number);
+/* labels_out int32 [P][h][w]: 0 = background, otherwise 1 + the smallest linear index y * w + x of the pixel's component.  skimage
+ * numbers components 1, 2, ... in raster order of their first pixel (unpinned: skimage is absent); these labels have the same order.
+ * scratch is not used by this entry point and may be NULL. */
+int avl_label_components(const uint8_t* maps, int n, int h, int w, const int32_t* classes, int n_classes, int erode, int32_t* labels_out,
+                         void* scratch, void* stream);
+/* :59-76 for every plane: the top_number (1 .. 8) largest components ordered by (area descending, label ascending) -- the order of
+ * Counter.most_common, which keeps first-seen (raster) order among equal counts -- of which those with area > area_threshold
+ * (strict, :60) get a convex hull.  Slot k of plane p:
+ *   roots int32 [P][top]      the component's label, 0 = no such component or area <= area_threshold;
+ *   areas int32 [P][top]      its pixel count (0 likewise);
+ *   n_vertices int32 [P][top] number of hull vertices, 0 for an empty slot;
+ *   vertices int32 [P][top][2h+1][2]  (x = column, y = row), strict vertices only (no collinear points), starting at the smallest
+ *       (x, then y) and running with positive cross products on (x, y) as stored: counter-clockwise for x right, y up, the lower
+ *       chain of a monotone chain first.  cv2.convexHull's start and direction are unpinned (cv2 is absent).
+ * drop_first != 0 (the reference): the raster-first pixel of the component -- the one whose index + 1 is the label -- is left out of
+ * the hull (crosswalk_pts[1:], :71) though it counts for the area; a component of one pixel then has n_vertices 0.  One or two
+ * remaining points, or collinear ones, give 1 or 2 vertices.  scratch: avl_hull_scratch_bytes(h, w, P, top_number) bytes, 8-aligned. */
+int avl_class_hulls(const uint8_t* maps, int n, int h, int w, const int32_t* classes, int n_classes, int erode, int top_number,
+                    int area_threshold, int drop_first, int32_t* vertices, int32_t* n_vertices, int32_t* areas, int32_t* roots,
+                    void* scratch, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

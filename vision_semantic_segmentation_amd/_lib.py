@@ -66,6 +66,9 @@ _SIGNATURES = {
     "avl_upsample_logits_batch": (_i, [_vp, _i, _i64, _i, _i, _i, _i64, _vp, _i, _i, _vp]),
     "avl_seg_eval_scratch_bytes_batch": (_i64, [_i, _i, _i]),
     "avl_seg_eval_full_res_batch": (_i, [_vp, _i, _i64, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_hull_scratch_bytes": (_i64, [_i, _i, _i, _i]),
+    "avl_label_components": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "avl_class_hulls": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

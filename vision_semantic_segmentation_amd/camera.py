@@ -1,6 +1,8 @@
 """Pinhole camera and the two hard-coded calibrations of the reference (src/camera.py:21-35,102-135).
 
-Host-side float64 setup only: the kernels receive ``Camera.P`` (3x4, row-major) by value.
+Host-side float64 setup only: the kernels receive ``Camera.P`` (3x4, row-major) by value.  ``pixel_to_ray`` /
+``pixel_to_ray_vec`` (src/camera.py:37-72) back-project the few hundred hull vertices of a frame on the host, in the reference's
+float64 arithmetic.
 """
 import numpy as np
 
@@ -21,6 +23,24 @@ class Camera(object):
         self.C_world_inhomo = np.matmul(-R.T, t)
         self.imSize = imSize
         self.dist = dist
+
+    def pixel_to_ray(self, Ix, Iy, world=True):
+        """src/camera.py:37-56: the 3-D line of the points that project to pixel (Ix, Iy), as (unit direction [3,1], point on the
+        line [3,1]).  world=True: in the velodyne frame, through the camera centre, direction signed so that its x is positive;
+        world=False: in the camera frame, through the origin, z positive.  Same float64 operations in the same order."""
+        pixel = np.array([[Ix, Iy, 1.0]]).T
+        if not world:
+            ray_cam = np.matmul(self.K_inv, pixel)
+            return ray_cam / np.sign(ray_cam[2, 0]) / np.linalg.norm(ray_cam), np.zeros([3, 1])
+        point_world = np.matmul(self.R.T, (np.matmul(self.K_inv, pixel) - self.t))
+        ray = point_world - self.C_world_inhomo
+        return ray / np.sign(ray[0, 0]) / np.linalg.norm(ray), self.C_world_inhomo
+
+    def pixel_to_ray_vec(self, pts):
+        """src/camera.py:58-72: pts [2, n] pixels -> (unit directions [3, n] in the velodyne frame, each signed so that its x is
+        positive; the camera centre [3, 1])."""
+        rays = np.matmul(self.R.T, np.matmul(self.K_inv, np.vstack((pts, np.ones((1, pts.shape[1]))))))
+        return rays / np.sign(rays[0, :]) / np.linalg.norm(rays, axis=0), self.C_world_inhomo
 
     def get_image_coordinate(self, X):
         """src/camera.py:87-91: image coordinates of 3xN world points."""

@@ -149,5 +149,9 @@ def get_cfg_defaults():
     C.MAPPING.GRID_DTYPE = "f64"
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
+    # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground
+    # plane (vision_semantic_segmentation_node.py:104-106, commented out in the reference: [2, 1] is what those two lines ask for).
+    # [] = off: the hull code is never touched
+    C.VISION_SEM_SEG.CONVEX_HULL_CLASSES = []
     C.VISION_SEM_SEG.SEM_SEG_NETWORK = get_network_cfg_defaults()
     return C

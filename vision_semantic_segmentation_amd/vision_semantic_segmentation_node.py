@@ -6,8 +6,13 @@ image_callback keeps the reference's sequence (:74-136): BGR->RGB, cv2.undistort
 colouring, publish.  Pre-processing runs inside the network's first kernel (the stem's loader applies BGR->RGB, undistort and
 INTER_AREA per pixel while it fills its LDS tile; avl_preprocess_image is the same function as a stand-alone kernel), the
 upscale + colouring is one more kernel (avl_colorize_labels); the frame is uploaded once and only the colour image comes back.
+
+Semantic extraction (:104-106, :138-201) is the node's second product: with VISION_SEM_SEG.CONVEX_HULL_CLASSES set, the convex
+hulls of the listed classes are taken from the frame's device labels in one call (semantic_convex_hull.class_hulls_device), only the
+vertices come to the host, and they are back-projected onto the ground plane of plane_callback in the reference's float64 arithmetic.
 """
 import ctypes as C
+import logging
 import threading
 
 import numpy as np
@@ -16,6 +21,11 @@ import torch
 from . import _lib
 from .camera import camera_setup_1, camera_setup_6
 from .labels import get_labels
+
+_log = logging.getLogger(__name__)
+
+# the topic cam_back_project_convex_hull publishes a class's hulls on (:194-197), and the marker look (:178-183)
+CROSSWALK_HULL_TOPIC, ROAD_HULL_TOPIC = "/crosswalk_convex_hull_rviz", "/road_convex_hull_rviz"
 
 
 def _palette_host(labels):
@@ -81,7 +91,7 @@ def colorize_labels_device(labels_small, out_h, out_w, labels=None, stream=None)
 class VisionSemanticSegmentationNode(object):
     """Reference class: src/vision_semantic_segmentation_node.py:41."""
 
-    def __init__(self, cfg, seg=None, use_ros=False, publish=None, undistort=True):
+    def __init__(self, cfg, seg=None, use_ros=False, publish=None, undistort=True, publish_markers=None):
         if cfg.VISION_SEM_SEG.IMAGE_SCALE < 0 or cfg.VISION_SEM_SEG.IMAGE_SCALE > 1:
             raise ValueError("image scale should be in the range of [0, 1]")       # :43-44
         network_cfg = cfg.VISION_SEM_SEG.SEM_SEG_NETWORK
@@ -96,6 +106,14 @@ class VisionSemanticSegmentationNode(object):
         self.publish = publish          # callable(frame_id, colour image, header) or None
         self.undistort = undistort      # the reference always undistorts camera1 / camera6 frames (:84-87)
         self.last_labels = None         # CUDA uint8 [h', w'] of the last frame (feeds the fused mapping path)
+        self.publish_markers = publish_markers       # callable(topic, list of marker dicts) or None
+        self.hull_classes = [int(c) for c in cfg.VISION_SEM_SEG.CONVEX_HULL_CLASSES]   # [] = no semantic extraction (:105-106 stay off)
+        self.plane = None               # Plane3D of the last plane_callback (:65)
+        self.hull_id = 0                # :70
+        self._hull_workspace = None
+        self._warned_no_plane = False
+        self._marker_msgs = None        # (Marker, MarkerArray, Point) once ROS markers are wanted
+        self.pub_crosswalk_markers = self.pub_road_markers = None
         # rospy runs each subscription's callback on its own thread, and both cameras share one compiled plan (fixed
         # input / activation / label buffers on one stream): one frame at a time through upload -> net -> colour -> download
         self._lock = threading.Lock()
@@ -112,6 +130,13 @@ class VisionSemanticSegmentationNode(object):
         self.image_pub_cam1 = rospy.Publisher("/camera1/semantic", Image, queue_size=1)
         self.image_pub_cam6 = rospy.Publisher("/camera6/semantic", Image, queue_size=1)
         self._ros_image_cls = Image
+        from shape_msgs.msg import Plane
+        from visualization_msgs.msg import Marker, MarkerArray
+        from geometry_msgs.msg import Point
+        self.plane_sub = rospy.Subscriber("/estimated_plane", Plane, self.plane_callback)                       # :51
+        self.pub_crosswalk_markers = rospy.Publisher(CROSSWALK_HULL_TOPIC, MarkerArray, queue_size=10)          # :56-57
+        self.pub_road_markers = rospy.Publisher(ROAD_HULL_TOPIC, MarkerArray, queue_size=10)
+        self._marker_msgs = (Marker, MarkerArray, Point)
 
     def _publish_ros(self, colored, header):
         """:118-134 -- the colour image as an 8UC3 sensor_msgs/Image (cv_bridge's "passthrough" of a uint8 H x W x 3 array)
@@ -138,6 +163,109 @@ class VisionSemanticSegmentationNode(object):
             return None
         return f
 
+    # ------------------------------------------------------------------------------------------ semantic extraction
+    def plane_callback(self, msg):
+        """:199-201 -- shape_msgs/Plane: msg.coef[0..3] = a, b, c, d of the estimated ground plane."""
+        from .plane_3d import Plane3D
+        self.plane = Plane3D(msg.coef[0], msg.coef[1], msg.coef[2], msg.coef[3])
+
+    def _camera_of(self, cam_frame_id):
+        return {"camera1": self.cam1, "camera6": self.cam6}.get(cam_frame_id)
+
+    def generate_and_publish_convex_hull(self, image, cam_frame_id, index_care_about=1):
+        """:138-152 -- hulls of class index_care_about in the label map `image` (ndarray or the device labels), scaled from the
+        network's output size to the camera's image size, back-projected and published.  Returns the markers."""
+        from .semantic_convex_hull import generate_convex_hull
+        cam = self._camera_of(cam_frame_id)
+        if cam is None:
+            raise ValueError("no camera model for frame id %r" % (cam_frame_id,))      # the reference fails on its unbound `cam`
+        vertice_list = generate_convex_hull(image, index_care_about=index_care_about, vis=False)
+        vertice_list = self._scale_to_camera(cam, vertice_list, int(image.shape[0]), int(image.shape[1]))
+        markers = self.cam_back_project_convex_hull(cam, vertice_list, index_care_about=index_care_about)
+        self._send_markers([(index_care_about, markers)])
+        return markers
+
+    @staticmethod
+    def _scale_to_camera(cam, vertice_list, h, w):
+        scale = np.array([[float(cam.imSize[0]) / w, float(cam.imSize[1]) / h]]).T                              # :147-150
+        return [v * scale for v in vertice_list]
+
+    def cam_back_project_convex_hull(self, cam, vertice_list, index_care_about=1):
+        """:154-197 -- every hull's pixels [2, n] become rays (Camera.pixel_to_ray_vec) that are cut with the ground plane
+        (Plane3D.plane_ray_intersection_vec); one line-strip marker per hull in the "velodyne" frame, ids counted in ``hull_id``.
+        Returns the list of marker dicts (id, frame_id, type, scale, color, lifetime, points [n, 3]); nothing is sent from here."""
+        markers = []
+        if len(vertice_list) == 0:
+            return markers
+        if self.plane is None:
+            raise RuntimeError("cam_back_project_convex_hull needs a ground plane: no plane_callback yet")
+        for vertices in vertice_list:
+            d_vec, C_vec = cam.pixel_to_ray_vec(vertices)
+            intersection_vec = self.plane.plane_ray_intersection_vec(d_vec, C_vec)
+            self.hull_id += 1
+            if index_care_about == 1:
+                color, vis_time = [0.8, 0., 0., 0.8], 10.0
+            else:
+                color, vis_time = [0.0, 0, 0.8, 0.8], 3.0
+            markers.append({"id": self.hull_id, "frame_id": "velodyne", "type": "line_strip", "scale": 0.1, "color": color,
+                            "lifetime": vis_time, "points": intersection_vec.T})
+        return markers
+
+    def _extract_hulls(self, labels, frame_ids):
+        """Under the lock, between segmentation and colourising (:104-106): ONE class_hulls_device call for every view and every
+        listed class, one copy of the vertices to the host, then the host-side back-projection.  labels [h', w'] or [V, h', w'].
+        Returns [(class index, markers)] in view order, classes in the configured order."""
+        if not self.hull_classes:
+            return []
+        if self.plane is None:
+            if not self._warned_no_plane:
+                _log.warning("no ground plane received yet (plane_callback): semantic extraction is skipped until one arrives")
+                self._warned_no_plane = True
+            return []
+        from .semantic_convex_hull import class_hulls_device, hull_workspace_bytes
+        batch = labels if labels.dim() == 3 else labels[None]
+        V, h, w = (int(v) for v in batch.shape)
+        need = hull_workspace_bytes(h, w, V * len(self.hull_classes), 1)
+        if self._hull_workspace is None or self._hull_workspace.numel() < need or self._hull_workspace.device != batch.device:
+            self._hull_workspace = torch.empty(need, dtype=torch.uint8, device=batch.device)
+        polygons = class_hulls_device(batch, self.hull_classes, workspace=self._hull_workspace).polygons()
+        out = []
+        for v, frame_id in enumerate(frame_ids):
+            cam = self._camera_of(frame_id)
+            if cam is None:
+                continue                                         # no model to back-project with (:139-142 know two cameras)
+            for k, index in enumerate(self.hull_classes):
+                vertice_list = self._scale_to_camera(cam, polygons[v][k], h, w)
+                out.append((index, self.cam_back_project_convex_hull(cam, vertice_list, index_care_about=index)))
+        return out
+
+    def _send_markers(self, hulls):
+        for index, markers in hulls:
+            if not markers:
+                continue                                         # :155-157: nothing is published for an empty list
+            topic = CROSSWALK_HULL_TOPIC if index == 1 else ROAD_HULL_TOPIC                                     # :194-197
+            if self.publish_markers is not None:
+                self.publish_markers(topic, markers)
+            if self._marker_msgs is not None:
+                self._publish_markers_ros(index, markers)
+
+    def _publish_markers_ros(self, index, markers):
+        """The marker dicts as a visualization_msgs/MarkerArray of LINE_STRIP markers (src/vis.py:19-107)."""
+        import rospy
+        Marker, MarkerArray, Point = self._marker_msgs
+        array = MarkerArray()
+        for m in markers:
+            mk = Marker()
+            mk.header.frame_id, mk.header.stamp = m["frame_id"], rospy.get_rostime()
+            mk.action, mk.id, mk.type = 0, m["id"], Marker.LINE_STRIP
+            mk.lifetime.secs, mk.lifetime.nsecs = int(m["lifetime"]), int(m["lifetime"] % 1.0 * 1e9)
+            mk.color.r, mk.color.g, mk.color.b, mk.color.a = m["color"]
+            mk.scale.x = mk.scale.y = mk.scale.z = m["scale"]
+            for p in m["points"]:
+                mk.points.append(Point(x=float(p[0]), y=float(p[1]), z=float(p[2])))
+            array.markers.append(mk)
+        (self.pub_crosswalk_markers if index == 1 else self.pub_road_markers).publish(array)
+
     def image_callback(self, msg):
         """:74-136.  msg.data: uint8[H,W,3] BGR (as the camera driver publishes it).  The whole chain runs on the GPU:
         pre-processing (:83-98), segmentation (:101-102), nearest upscale + palette (:109-116); only the published
@@ -159,8 +287,10 @@ class VisionSemanticSegmentationNode(object):
             else:                                                # pre-processing inside the stem's loader (no RGB frame in between)
                 labels = self.seg.segmentation_device_raw(bgr, None if cam is None else cam.K, None if cam is None else cam.dist, factor)
             self.last_labels = labels
+            hulls = self._extract_hulls(labels, [msg.header.frame_id])
             colored = colorize_labels_device(labels, h, w, self.seg_color_ref)
             out = colored.cpu().numpy()
+        self._send_markers(hulls)
         if self.publish is not None:
             self.publish(msg.header.frame_id, out, msg.header)                     # :129-134
         if self._ros_image_cls is not None:
@@ -206,7 +336,9 @@ class VisionSemanticSegmentationNode(object):
                 labels = self.seg.segmentation_device_raw_batch(frames, [None if c is None else c.K for c in cams],
                                                                 [None if c is None else c.dist for c in cams], factor)
             self.last_labels = labels
+            hulls = self._extract_hulls(labels, [msg.header.frame_id for msg in msgs])
             outs = [colorize_labels_device(labels[v], h, w, self.seg_color_ref).cpu().numpy() for v in range(len(msgs))]
+        self._send_markers(hulls)
         for msg, out in zip(msgs, outs):
             if self.publish is not None:
                 self.publish(msg.header.frame_id, out, msg.header)

@@ -101,3 +101,40 @@ def test_fused_frame_path_refuses_what_the_frame_refuses():
     for g, n, bonus, msg in cases:
         assert path(g, n, bonus) == -1
         assert msg in _lib.last_error(), (msg, _lib.last_error())
+
+
+# ---------------------------------------------------------------- cm_host is checked before the empty cloud returns
+# one grid per path, from CASES (every one with 6 vote bits, so that two views take it as well)
+EMPTY_CLOUD_GRIDS = [("odd_cells_sparse", 0), ("cells_mod16_4_dense", 1), ("counter_len_131", 2), ("c5_one_lane_6_bits", 3)]
+
+
+def _empty_frame(g, bonus, cm, n_views=None):
+    """avl_fused_frame (or avl_fused_frame_views with n_views views) on an EMPTY cloud: n = 0 returns before any HIP call, so the fake
+    pointers are never handed to a device.  -> (rc, message)"""
+    from vision_semantic_segmentation_amd import _lib
+    L = _lib.lib()
+    P = (C.c_double * (12 * (n_views or 1)))()
+    lut, colors = (C.c_uint32 * 256)(), (C.c_uint8 * 48)()
+    cm_c = (C.c_double * 256)() if cm else None
+    head = (C.byref(g), 0x7f0000500000, 0, _lib.AVL_F32, 16, 4)
+    tail = (640, 480, 640, 480, lut, colors, cm_c, bonus, None)
+    if n_views is None:
+        rc = L.avl_fused_frame(*head, P, None, 100.0, _lib.AVL_SRC_CLASSMAP, 0x7f0000600000, *tail)
+    else:
+        src = (C.c_void_p * n_views)(*[0x7f0000600000 + 0x100000 * v for v in range(n_views)])
+        rc = L.avl_fused_frame_views(*head, n_views, P, None, 100.0, _lib.AVL_SRC_CLASSMAP, src, *tail)
+    return rc, _lib.last_error()
+
+
+@pytest.mark.parametrize("case_id,want_path", EMPTY_CLOUD_GRIDS, ids=["path%d" % p for _, p in EMPTY_CLOUD_GRIDS])
+@pytest.mark.parametrize("n_views", [None, 2], ids=["single", "two_views"])
+def test_null_cm_host_is_refused_on_every_path(case_id, want_path, n_views):
+    """a NULL cm_host is AVL_E_ARG from both fused entry points whatever path the grid would take (path 3 used to read through it),
+    and a valid one still maps the empty cloud"""
+    kw, n, bonus, want = {c[0]: c[1:] for c in CASES}[case_id]
+    assert want == want_path and path(grid(**kw), n, bonus) == want_path
+    rc, err = _empty_frame(grid(**kw), bonus, cm=False, n_views=n_views)
+    assert rc == -1, (rc, err)
+    assert "cm_host is NULL" in err, err
+    rc, err = _empty_frame(grid(**kw), bonus, cm=True, n_views=n_views)
+    assert rc == 0, (rc, err)

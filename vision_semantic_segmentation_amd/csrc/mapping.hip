@@ -969,55 +969,67 @@ int fill_grid(GridParams& gp, const avl_grid* g, const uint8_t* colors, uint32_t
     return AVL_OK;
 }
 
-int launch_apply(const avl_grid* g, const double* cm_host, void* rows, int rows_dtype, hipStream_t s) {
+int fill_cm(CmParams& cm, const avl_grid* g, const double* cm_host) {
     if (!cm_host) return avl::set_error(AVL_E_ARG, "cm_host is NULL");
-    const int dt = rows ? rows_dtype : g->map_dtype;
-    if (dt != AVL_F32 && dt != AVL_F64) return avl::set_error(AVL_E_ARG, "rows dtype %d", dt);
-    CmParams cm;
     memset(&cm, 0, sizeof(cm));
     memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
+    return AVL_OK;
+}
+
+// The map's element type: launch(float()) or launch(double()) starts the kernel of that type, the launch check follows.  Every
+// kernel that is a template over MapT goes through here.
+template <typename Launch>
+int launch_map_typed(int map_dtype, Launch&& launch) {
+    if (map_dtype == AVL_F64) launch(double());
+    else launch(float());
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+// workgroups of a sweep over the whole grid, each round of one taking `wg_cells` cells
+unsigned sweep_blocks(long long ncell, int wg_cells) {
+    const long long rounds = (ncell + wg_cells - 1) / wg_cells;
+    return (unsigned)(rounds < 8192 ? rounds : 8192);
+}
+
+int launch_apply(const avl_grid* g, const double* cm_host, void* rows, int rows_dtype, hipStream_t s) {
+    CmParams cm;
+    int rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
+    const int dt = rows ? rows_dtype : g->map_dtype;
+    if (dt != AVL_F32 && dt != AVL_F64) return avl::set_error(AVL_E_ARG, "rows dtype %d", dt);
     const int cap = g->touched_cap;
     int blocks = (cap + kBlock - 1) / kBlock;
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    if (dt == AVL_F64)
-        hipLaunchKernelGGL(k_grid_apply<double>, dim3(blocks), dim3(kBlock), 0, s, static_cast<double*>(g->map),
-                           static_cast<double*>(rows), g->C, cm, g->cell_mask, g->touched, g->counter);
-    else
-        hipLaunchKernelGGL(k_grid_apply<float>, dim3(blocks), dim3(kBlock), 0, s, static_cast<float*>(g->map),
-                           static_cast<float*>(rows), g->C, cm, g->cell_mask, g->touched, g->counter);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(dt, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_grid_apply<T>, dim3(blocks), dim3(kBlock), 0, s, static_cast<T*>(g->map), static_cast<T*>(rows), g->C, cm,
+                           g->cell_mask, g->touched, g->counter);
+    });
 }
 
 int launch_apply_scan(const avl_grid* g, const double* cm_host, hipStream_t s) {
-    if (!cm_host) return avl::set_error(AVL_E_ARG, "cm_host is NULL");
     CmParams cm;
-    memset(&cm, 0, sizeof(cm));
-    memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
+    int rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
     const long long ncell4 = (long long)g->Hm * g->Wm / 4;
-    if (g->map_dtype == AVL_F64)
-        hipLaunchKernelGGL(k_grid_apply_scan<double>, dim3(2048), dim3(kBlock), 0, s, static_cast<double*>(g->map), g->C, cm, g->cell_mask, ncell4);
-    else
-        hipLaunchKernelGGL(k_grid_apply_scan<float>, dim3(2048), dim3(kBlock), 0, s, static_cast<float*>(g->map), g->C, cm, g->cell_mask, ncell4);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_grid_apply_scan<T>, dim3(2048), dim3(kBlock), 0, s, static_cast<T*>(g->map), g->C, cm, g->cell_mask, ncell4);
+    });
 }
 
 int launch_sweep_bytes(const avl_grid* g, const double* cm_host, unsigned bonus, hipStream_t s) {
-    if (!cm_host) return avl::set_error(AVL_E_ARG, "cm_host is NULL");
     CmParams cm;
-    memset(&cm, 0, sizeof(cm));
-    memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
+    int rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
     const long long ncell = (long long)g->Hm * g->Wm;
     unsigned char* mask = reinterpret_cast<unsigned char*>(g->cell_mask);
-    const long long rounds = (ncell + kSweepCells - 1) / kSweepCells;
-    const unsigned blocks = (unsigned)(rounds < 8192 ? rounds : 8192);
-    if (g->map_dtype == AVL_F64)
-        hipLaunchKernelGGL(k_grid_sweep_bytes<double>, dim3(blocks), dim3(kBlock), 0, s, static_cast<double*>(g->map), g->C, bonus, cm, mask, ncell);
-    else
-        hipLaunchKernelGGL(k_grid_sweep_bytes<float>, dim3(blocks), dim3(kBlock), 0, s, static_cast<float*>(g->map), g->C, bonus, cm, mask, ncell);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_grid_sweep_bytes<T>, dim3(sweep_blocks(ncell, kSweepCells)), dim3(kBlock), 0, s, static_cast<T*>(g->map), g->C,
+                           bonus, cm, mask, ncell);
+    });
 }
 
 // byte mask usable: class bits + bonus bits fit a byte, whole 16-byte vectors, aligned scratch
@@ -1037,28 +1049,34 @@ ListGeom list_geom(int n) {
     lg.apply_wgs = lg.wgs_per_list * kLists;
     return lg;
 }
-// MODE 3 needs the big counter block, room for kLists x cap entries and a byte mask.  Its cost grows with the cloud (returning
-// atomics in the vote, rows visited in point order -- no locality -- in the apply), the sweep's is ~15 us whatever the cloud:
-// measured 17 vs 22 us per frame at 120 k points on 4 M cells (config C), 54 vs 38 us at 1 M points on 16 M cells (config E).
-bool use_lists(const avl_grid* g, int n, unsigned bonus) {
-    if (g->counter_len < kListBase + 2 * kLists || !byte_mask_ok(g, bonus)) return false;
+// The lists need the big counter block and room for kLists x cap entries.  Their cost grows with the cloud (returning atomics in
+// the vote, rows visited in point order -- no locality -- in the apply), the sweep's is ~15 us whatever the cloud: measured 17 vs
+// 22 us per frame at 120 k points on 4 M cells (config C), 54 vs 38 us at 1 M points on 16 M cells (config E).  With several views
+// the lists are paid once per call, not once per view, so avl_fused_frame_views keeps the same crossover.
+bool lists_fit(const avl_grid* g, int n) {
+    if (g->counter_len < kListBase + 2 * kLists) return false;
     if ((long long)list_geom(n).cap * kLists > g->touched_cap) return false;
     return n <= 250000 && (long long)n * 2 <= (long long)g->Hm * g->Wm;
 }
+// MODE 3 reads the byte mask as well
+bool use_lists(const avl_grid* g, int n, unsigned bonus) { return byte_mask_ok(g, bonus) && lists_fit(g, n); }
+// Only the apply kernels return the list cursors to zero: if one did not launch (rc), reset them here so that the next frame's vote
+// appends from the start of each list again.
+int lists_applied(const avl_grid* g, int rc, hipStream_t s) {
+    if (rc != AVL_OK) (void)hipMemsetAsync(g->counter + kListBase, 0, 2 * kLists * sizeof(int), s);
+    return rc;
+}
 int launch_apply_lists(const avl_grid* g, const double* cm_host, unsigned bonus, int n, hipStream_t s) {
     CmParams cm;
-    memset(&cm, 0, sizeof(cm));
-    for (int i = 0; i < g->C * g->C; ++i) cm.cm[i] = cm_host[i];
+    int rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
     const ListGeom lg = list_geom(n);
     unsigned char* mask = reinterpret_cast<unsigned char*>(g->cell_mask);
-    if (g->map_dtype == AVL_F64)
-        hipLaunchKernelGGL(k_grid_apply_lists<double>, dim3(lg.apply_wgs), dim3(kBlock), 0, s, static_cast<double*>(g->map), g->C, bonus, cm,
-                           mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-    else
-        hipLaunchKernelGGL(k_grid_apply_lists<float>, dim3(lg.apply_wgs), dim3(kBlock), 0, s, static_cast<float*>(g->map), g->C, bonus, cm,
-                           mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_grid_apply_lists<T>, dim3(lg.apply_wgs), dim3(kBlock), 0, s, static_cast<T*>(g->map), g->C, bonus, cm, mask,
+                           g->touched, g->counter, lg.cap, lg.wgs_per_list);
+    });
 }
 
 // list (sparse) vs sweep (dense) apply: the sweep reads Hm*Wm*4 bytes whatever the cloud; the list costs a
@@ -1071,15 +1089,8 @@ bool use_scan(const avl_grid* g, int n, unsigned bonus) {
     return (long long)n * (byte_mask_ok(g, bonus) ? 1024 : 128) >= cells;
 }
 
-// ---- avl_fused_frame_views: lists (sparse) or sweep (dense) of the word mask
-// The lists cost what the cloud costs (a returning atomic per point that votes, one row visit per touched cell) and are paid once
-// per call, not once per view: the crossover of use_lists is kept.  The sweep reads Hm*Wm*4 bytes whatever the cloud and takes
-// any grid: it is the path for everything else.
-bool views_use_lists(const avl_grid* g, int n) {
-    if (g->counter_len < kListBase + 2 * kLists) return false;
-    if ((long long)list_geom(n).cap * kLists > g->touched_cap) return false;
-    return n <= 250000 && (long long)n * 2 <= (long long)g->Hm * g->Wm;
-}
+// ---- avl_fused_frame_views: lists (sparse, lists_fit) or sweep (dense) of the word mask.  The sweep reads Hm*Wm*4 bytes whatever
+// the cloud and takes any grid: it is the path for everything else.
 int views_check(int n_views, const uint8_t* const* src_host) {
     if (n_views < 1) return avl::set_error(AVL_E_ARG, "n_views = %d (at least one view)", n_views);
     if (n_views > kMaxViews) return avl::set_error(AVL_E_ARG, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
@@ -1091,6 +1102,32 @@ int views_check(int n_views, const uint8_t* const* src_host) {
 int views_bits_check(const avl_grid* g, uint32_t bonus) {
     const int bits = g->C + __builtin_popcount(bonus);
     if (bits > 8) return avl::set_error(AVL_E_ARG, "C + popcount(bonus_classes) = %d vote bits per view, the views mask holds 8", bits);
+    return AVL_OK;
+}
+
+
+// What avl_fused_frame and avl_fused_frame_views take alike, validated and in kernel-argument form (`src`: the only or first view's
+// semantic source).  Everything here is refused before the empty cloud returns; touched_cap matters only to a cloud that votes.
+struct FrameArgs { PtsView pv; ProjParams pp; GridParams gp; LutParams lut; };
+int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+               const double* P_host, const double* T_host, double range_max, int src_kind, const uint8_t* src, int src_w, int src_h,
+               int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus) {
+    int rc;
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = fill_grid(f.gp, g, label_colors_host, bonus))) return rc;
+    AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
+    AVL_REQUIRE(src && src_w > 0 && src_h > 0, "bad semantic source");
+    AVL_REQUIRE(cm_host, "cm_host is NULL");
+    memset(&f.lut, 0, sizeof(f.lut));
+    if (src_kind == AVL_SRC_RGB) {
+        AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
+        AVL_REQUIRE(src_w == img_w && src_h == img_h, "RGB source must be %dx%d", img_w, img_h);
+    } else {
+        AVL_REQUIRE(lut_host, "lut_host is NULL");
+        memcpy(f.lut.lut, lut_host, sizeof(f.lut.lut));
+    }
+    if (n > 0) AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     return AVL_OK;
 }
 
@@ -1199,44 +1236,24 @@ extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dt
                                int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
                                const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
                                uint32_t bonus_classes, void* stream) {
-    PtsView pv;
-    ProjParams pp;
-    GridParams gp;
-    LutParams lut;
+    FrameArgs f;
     int rc;
-    if ((rc = fill_pts(pv, pts, n, dtype, point_stride, comp_stride))) return rc;
-    if ((rc = fill_proj(pp, P_host, T_host, range_max, img_w, img_h))) return rc;
-    if ((rc = fill_grid(gp, g, label_colors_host, bonus_classes))) return rc;
-    AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
-    AVL_REQUIRE(src && src_w > 0 && src_h > 0, "bad semantic source");
-    memset(&lut, 0, sizeof(lut));
-    if (src_kind == AVL_SRC_RGB) {
-        AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
-        AVL_REQUIRE(src_w == img_w && src_h == img_h, "RGB source must be %dx%d", img_w, img_h);
-    } else {
-        AVL_REQUIRE(lut_host, "lut_host is NULL");
-        memcpy(lut.lut, lut_host, sizeof(lut.lut));
-    }
+    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
+                         lut_host, label_colors_host, cm_host, bonus_classes)))
+        return rc;
     if (n == 0) return AVL_OK;
-    AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     hipStream_t s = avl::as_stream(stream);
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
     const int mode = avl_fused_frame_path(g, n, bonus_classes);
     if (mode < 0) return mode;
     if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
     const int list_cap = list_geom(n).cap;
-#define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, pv, pp, gp, src, src_w, src_h, lut, g->cell_mask, g->touched, g->counter, list_cap)
+#define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap)
     if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FV(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FV(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FV(AVL_SRC_RGB, 1); else AVL_FV(AVL_SRC_RGB, 0); }
     else { if (mode == 3) AVL_FV(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FV(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FV(AVL_SRC_CLASSMAP, 1); else AVL_FV(AVL_SRC_CLASSMAP, 0); }
 #undef AVL_FV
     AVL_LAUNCH_CHECK();
-    if (mode == 3) {
-        rc = launch_apply_lists(g, cm_host, bonus_classes, n, s);
-        // only the apply kernel returns the list cursors to zero: if it did not launch, reset them here so that the next frame's
-        // vote appends from the start of each list again
-        if (rc != AVL_OK) (void)hipMemsetAsync(g->counter + kListBase, 0, 2 * kLists * sizeof(int), s);
-        return rc;
-    }
+    if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
     if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
     return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
 }
@@ -1250,7 +1267,7 @@ extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views,
     if ((rc = fill_grid(gp, g, nullptr, bonus_classes))) return rc;
     if ((rc = views_bits_check(g, bonus_classes))) return rc;
     AVL_REQUIRE(n >= 0, "n = %d", n);
-    return views_use_lists(g, n) ? 4 : 5;
+    return lists_fit(g, n) ? 4 : 5;
 }
 
 extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
@@ -1263,73 +1280,46 @@ extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, 
     if (n_views == 1)
         return avl_fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h,
                                img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, stream);
-    PtsView pv;
-    ProjParams pp;
-    GridParams gp;
-    LutParams lut;
-    if ((rc = fill_pts(pv, pts, n, dtype, point_stride, comp_stride))) return rc;
-    if ((rc = fill_proj(pp, P_host, T_host, range_max, img_w, img_h))) return rc;
-    if ((rc = fill_grid(gp, g, label_colors_host, bonus_classes))) return rc;
+    FrameArgs f;
+    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h, img_w,
+                         img_h, lut_host, label_colors_host, cm_host, bonus_classes)))
+        return rc;
     if ((rc = views_bits_check(g, bonus_classes))) return rc;
-    AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
-    AVL_REQUIRE(src_w > 0 && src_h > 0, "bad semantic source");
-    AVL_REQUIRE(cm_host, "cm_host is NULL");
-    memset(&lut, 0, sizeof(lut));
-    if (src_kind == AVL_SRC_RGB) {
-        AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
-        AVL_REQUIRE(src_w == img_w && src_h == img_h, "RGB source must be %dx%d", img_w, img_h);
-    } else {
-        AVL_REQUIRE(lut_host, "lut_host is NULL");
-        memcpy(lut.lut, lut_host, sizeof(lut.lut));
-    }
     if (n == 0) return AVL_OK;
-    AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     ViewsParams vp;
     memset(&vp, 0, sizeof(vp));
     memcpy(vp.P, P_host, sizeof(double) * 12 * n_views);
-    memcpy(vp.T, pp.T, sizeof(vp.T));
+    memcpy(vp.T, f.pp.T, sizeof(vp.T));
     for (int v = 0; v < n_views; ++v) vp.src[v] = src_host[v];
     vp.range_max = range_max;
-    vp.has_T = pp.has_T;
+    vp.has_T = f.pp.has_T;
     vp.n_views = n_views;
     vp.img_w = img_w;
     vp.img_h = img_h;
     CmParams cm;
-    memset(&cm, 0, sizeof(cm));
-    memcpy(cm.cm, cm_host, sizeof(double) * g->C * g->C);
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
     hipStream_t s = avl::as_stream(stream);
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool lists = views_use_lists(g, n);
+    const bool lists = lists_fit(g, n);
     const ListGeom lg = list_geom(n);
-#define AVL_VV(SRC, LISTS) hipLaunchKernelGGL((k_views_vote<SRC, LISTS>), grid, block, 0, s, pv, vp, gp, src_w, src_h, lut, g->cell_mask, g->touched, g->counter, lg.cap)
+#define AVL_VV(SRC, LISTS) hipLaunchKernelGGL((k_views_vote<SRC, LISTS>), grid, block, 0, s, f.pv, vp, f.gp, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, lg.cap)
     if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VV(AVL_SRC_RGB, 1); else AVL_VV(AVL_SRC_RGB, 0); }
     else { if (lists) AVL_VV(AVL_SRC_CLASSMAP, 1); else AVL_VV(AVL_SRC_CLASSMAP, 0); }
 #undef AVL_VV
     AVL_LAUNCH_CHECK();
-    if (lists) {
-        if (g->map_dtype == AVL_F64)
-            hipLaunchKernelGGL(k_views_apply_lists<double>, dim3(lg.apply_wgs), block, 0, s, static_cast<double*>(g->map), g->C, bonus_classes, cm,
+    if (lists)
+        return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
+            typedef decltype(t) T;
+            hipLaunchKernelGGL(k_views_apply_lists<T>, dim3(lg.apply_wgs), block, 0, s, static_cast<T*>(g->map), g->C, bonus_classes, cm,
                                g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-        else
-            hipLaunchKernelGGL(k_views_apply_lists<float>, dim3(lg.apply_wgs), block, 0, s, static_cast<float*>(g->map), g->C, bonus_classes, cm,
-                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-        // as in avl_fused_frame: only the apply kernel returns the list cursors to zero
-        if (hipGetLastError() != hipSuccess) {
-            (void)hipMemsetAsync(g->counter + kListBase, 0, 2 * kLists * sizeof(int), s);
-            return avl::set_error(AVL_E_HIP, "k_views_apply_lists did not launch");
-        }
-        return AVL_OK;
-    }
+        }), s);
     const long long ncell = (long long)g->Hm * g->Wm;
-    const long long rounds = (ncell + kViewsSweepCells - 1) / kViewsSweepCells;
-    const unsigned blocks = (unsigned)(rounds < 8192 ? rounds : 8192);
     const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
-    if (g->map_dtype == AVL_F64)
-        hipLaunchKernelGGL(k_views_sweep_words<double>, dim3(blocks), block, 0, s, static_cast<double*>(g->map), g->C, bonus_classes, cm, g->cell_mask, ncell, vec);
-    else
-        hipLaunchKernelGGL(k_views_sweep_words<float>, dim3(blocks), block, 0, s, static_cast<float*>(g->map), g->C, bonus_classes, cm, g->cell_mask, ncell, vec);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
+                           bonus_classes, cm, g->cell_mask, ncell, vec);
+    });
 }
 
 extern "C" int avl_colorize_labels(const uint8_t* labels, int lw, int lh, const uint8_t* palette_host, uint8_t* out,
@@ -1433,10 +1423,10 @@ extern "C" int avl_planar_update(void* map, int map_dtype, int Hm, int Wm, int C
     }
     const long long n = (long long)Hm * Wm;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_planar_update<double>, grid, block, 0, avl::as_stream(stream), static_cast<double*>(map), Hm, Wm, image, pp);
-    else hipLaunchKernelGGL(k_planar_update<float>, grid, block, 0, avl::as_stream(stream), static_cast<float*>(map), Hm, Wm, image, pp);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_planar_update<T>, grid, block, 0, avl::as_stream(stream), static_cast<T*>(map), Hm, Wm, image, pp);
+    });
 }
 
 namespace {
@@ -1503,10 +1493,10 @@ extern "C" int avl_render_bev_map(const void* map, int map_dtype, int Hm, int Wm
     AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
     const long long n = (long long)Hm * Wm;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_render_bev<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(map), n, C, rp, out);
-    else hipLaunchKernelGGL(k_render_bev<float>, grid, block, 0, avl::as_stream(stream), static_cast<const float*>(map), n, C, rp, out);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_render_bev<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(map), n, C, rp, out);
+    });
 }
 
 extern "C" int avl_render_bev_map_thresholds(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host,
@@ -1518,10 +1508,10 @@ extern "C" int avl_render_bev_map_thresholds(const void* map, int map_dtype, int
     AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
     const long long n = (long long)Hm * Wm;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_render_thresholds<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(map), n, C, rp, out);
-    else hipLaunchKernelGGL(k_render_thresholds<float>, grid, block, 0, avl::as_stream(stream), static_cast<const float*>(map), n, C, rp, out);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_render_thresholds<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(map), n, C, rp, out);
+    });
 }
 
 // ---- end-of-run evaluation (test/test_semantic_mapping.py: convert_labels :6-19, Test.iou :127-161) -----------------
@@ -1580,8 +1570,8 @@ extern "C" int avl_grid_box_filter(const void* src, void* dst, int map_dtype, in
     AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
     const long long n = (long long)Hm * Wm * C;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_box_filter3<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(src), static_cast<double*>(dst), Hm, Wm, C);
-    else hipLaunchKernelGGL(k_box_filter3<float>, grid, block, 0, avl::as_stream(stream), static_cast<const float*>(src), static_cast<float*>(dst), Hm, Wm, C);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
+    return launch_map_typed(map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_box_filter3<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(src), static_cast<T*>(dst), Hm, Wm, C);
+    });
 }

@@ -738,11 +738,10 @@ int launch_typed(const avl_seg_op& op, hipStream_t s) {
                     MxOut mx;
                     memset(&mx, 0, sizeof(mx));
                     if (op.out_mx) {
-                        char* b = static_cast<char*>(op.out_mx);
-                        const long long rows = op.out_rows, P = rows * (op.out_c / 2), S = (long long)(op.out_c / 256) * rows * 8;
-                        mx.q[0] = b; mx.s[0] = b + P;
-                        if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.q[1] = b + P + S; mx.s[1] = b + 2 * P + S; }
-                        mx.srows = rows; mx.ldq = op.out_c / 2;
+                        const auto o = mx_bundle(op.out_mx, op.out_rows, op.out_c);
+                        mx.q[0] = o.q[0]; mx.s[0] = o.s[0];
+                        if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.q[1] = o.q[1]; mx.s[1] = o.s[1]; }
+                        mx.srows = o.srows; mx.ldq = o.ldq;
                     }
                     hipLaunchKernelGGL((k_dwconv<T, true>), dim3(nblk, 1, nimg), dim3(kThreads), 0, s, in, w, op.bias, out,
                                        static_cast<const T*>(op.in2), g, static_cast<const T*>(op.in_lo), static_cast<T*>(op.out_lo), mx);

@@ -528,10 +528,9 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
     a.oq[0] = a.oq[1] = a.os[0] = a.os[1] = nullptr;
     a.o_srows = op.out_rows;
     if (op.out_mx) {
-        char* b = static_cast<char*>(op.out_mx);
-        const long long rows = op.out_rows, P = rows * (op.out_c / 2), S = (long long)(op.out_c / 256) * rows * 8;
-        a.oq[0] = b; a.os[0] = b + P;
-        if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { a.oq[1] = b + P + S; a.os[1] = b + 2 * P + S; }
+        const auto o = mx_bundle(op.out_mx, op.out_rows, op.out_c);
+        a.oq[0] = o.q[0]; a.os[0] = o.s[0];
+        if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { a.oq[1] = o.q[1]; a.os[1] = o.s[1]; }
     }
     a.H = op.in_h; a.W = op.in_w; a.in_ld = op.in_ld; a.OH = op.out_h; a.OW = op.out_w; a.out_ld = op.out_ld; a.C = op.in_c;
     a.stride = op.stride; a.dil = op.dil;
@@ -545,10 +544,9 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
         const long long nwin = op.in_c / 32;
         a.w4 = static_cast<const char*>(op.w_mx);
         a.w4s = a.w4 + nwin * (2 * 2 * 3 * 64 * 16);
-        const char* b = static_cast<const char*>(op.in_mx);
-        const long long rows = op.in_rows, P = rows * (op.in_c / 2), S = (long long)(op.in_c / 256) * rows * 8;
-        a.xq[0] = b; a.xs[0] = b + P;
-        if (op.mx_flags & AVL_MX_IN_LO) { a.xq[1] = b + P + S; a.xs[1] = b + 2 * P + S; }
+        const auto x = mx_bundle(op.in_mx, op.in_rows, op.in_c);
+        a.xq[0] = x.q[0]; a.xs[0] = x.s[0];
+        if (op.mx_flags & AVL_MX_IN_LO) { a.xq[1] = x.q[1]; a.xs[1] = x.s[1]; }
     }
     {
         const int d = a.comb ? 1 : op.dil;

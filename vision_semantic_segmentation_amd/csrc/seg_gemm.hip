@@ -1405,45 +1405,33 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
         mx.g = a;
         // (with a second input appended along K: K1 = op.in_c comes from `in`, the rest from in3; weights span the whole K)
         const long long K1 = op.in_c, K2 = op.in3 ? op.in3_c : 0;
-        auto abundle = [&](const void* base, long long rows, long long kk, const char** plane, const char** scales) {
-            const char* b = static_cast<const char*>(base);
-            const long long P = rows * (kk / 2), S = (kk / 256) * rows * 8;
-            plane[0] = b; scales[0] = b + P; plane[1] = b + P + S; scales[1] = b + 2 * P + S;
-        };
-        abundle(op.in_mx, op.in_rows, K1, mx.Aq, mx.As);
+        const auto x = mx_bundle(op.in_mx, op.in_rows, K1);
+        mx.Aq[0] = x.q[0]; mx.As[0] = x.s[0]; mx.Aq[1] = x.q[1]; mx.As[1] = x.s[1];
+        mx.ldaq = x.ldq; mx.a_srows = x.srows;
         mx.nmb1 = (int)(K1 / 256);
-        mx.lda2 = mx.g.lda; mx.ldaq2 = (int)(K1 / 2);
+        mx.lda2 = mx.g.lda; mx.ldaq2 = x.ldq;
         if (K2) {
             a.K = (int)(K1 + K2);
             mx.g.K = a.K;
-            mx.A2 = op.in3; mx.lda2 = op.in3_ld; mx.ldaq2 = (int)(K2 / 2);
-            abundle(op.in3_mx, op.in_rows, K2, mx.Aq2, mx.As2);
-            mx.a_srows2 = op.in_rows;
+            const auto x2 = mx_bundle(op.in3_mx, op.in_rows, K2);
+            mx.A2 = op.in3; mx.lda2 = op.in3_ld; mx.ldaq2 = x2.ldq;
+            mx.Aq2[0] = x2.q[0]; mx.As2[0] = x2.s[0]; mx.Aq2[1] = x2.q[1]; mx.As2[1] = x2.s[1];
+            mx.a_srows2 = x2.srows;
         }
-        {
-            const long long KT = K1 + K2;
-            const char* b = static_cast<const char*>(op.w_mx);
-            const long long P = (long long)op.w_rows * (KT / 2), S = (KT / 256) * op.w_rows * 8;
-            mx.Wq[0] = b; mx.Ws[0] = b + P; mx.Wq[1] = b + P + S; mx.Ws[1] = b + 2 * P + S;
-        }
-        mx.ldaq = (int)(K1 / 2);
-        mx.a_srows = op.in_rows;
-        mx.w_srows = op.w_rows;
+        const auto w = mx_bundle(op.w_mx, op.w_rows, K1 + K2);
+        mx.Wq[0] = w.q[0]; mx.Ws[0] = w.s[0]; mx.Wq[1] = w.q[1]; mx.Ws[1] = w.s[1];
+        mx.w_srows = w.srows;
         mx.nmx = (op.in_lo || (op.mx_flags & AVL_MX_IN_LO)) ? 2 : 1;
         if (op.mx_flags & AVL_MX_RES_LO) {
-            const char* b = static_cast<const char*>(op.in2_mx);
-            const long long rows = op.out_rows, P = rows * (a.N / 2), S = (long long)(a.N / 256) * rows * 8;
-            mx.Rq = b + P + S; mx.Rs = b + 2 * P + S;
-            mx.ldrq = a.N / 2;
-            mx.r_srows = rows;
+            const auto r = mx_bundle(op.in2_mx, op.out_rows, a.N);
+            mx.Rq = r.q[1]; mx.Rs = r.s[1];
+            mx.ldrq = r.ldq; mx.r_srows = r.srows;
         }
         if (op.out_mx) {
-            char* b = static_cast<char*>(op.out_mx);
-            const long long rows = op.out_rows, P = rows * (a.N / 2), S = (long long)(a.N / 256) * rows * 8;
-            mx.Cq[0] = b; mx.Cs[0] = b + P;
-            if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.Cq[1] = b + P + S; mx.Cs[1] = b + 2 * P + S; }
-            mx.ldcq = a.N / 2;
-            mx.c_srows = rows;
+            const auto c = mx_bundle(op.out_mx, op.out_rows, a.N);
+            mx.Cq[0] = c.q[0]; mx.Cs[0] = c.s[0];
+            if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.Cq[1] = c.q[1]; mx.Cs[1] = c.s[1]; }
+            mx.ldcq = c.ldq; mx.c_srows = c.srows;
         }
         return launch_ring_mx(mx, m_image, op.out_mx != nullptr, s);
     }

@@ -183,6 +183,24 @@ __device__ __forceinline__ T* image_base(T* p, long long pixels, long long ld) {
 }
 inline bool is_half(int dtype) { return dtype == AVL_BF16 || dtype == AVL_F16; }
 
+// The MX bundle of a dense [rows][channels] activation or weight (avl_hip.h; network.mx_bundle_bytes sizes it): FP4 plane
+// [rows][channels / 2], E8M0 scales [channels / 256][rows][8], then the same pair for the lo part.  The one host statement of that
+// layout: q / s[0] = hi part, [1] = lo part; a launcher that has no lo part leaves the second pair of its kernel arguments NULL.
+template <typename C>      // char or const char
+struct MxBundle {
+    C* q[2];               // FP4 planes
+    C* s[2];               // their scales
+    int ldq;               // bytes per FP4 row
+    long long srows;       // rows per 256-channel slab of the scales
+};
+template <typename C>
+inline MxBundle<C> mx_bundle_at(C* b, long long rows, long long channels) {
+    const long long P = rows * (channels / 2), S = (channels / 256) * rows * 8;
+    return {{b, b + P + S}, {b + P, b + 2 * P + S}, (int)(channels / 2), rows};
+}
+inline MxBundle<char> mx_bundle(void* base, long long rows, long long channels) { return mx_bundle_at(static_cast<char*>(base), rows, channels); }
+inline MxBundle<const char> mx_bundle(const void* base, long long rows, long long channels) { return mx_bundle_at(static_cast<const char*>(base), rows, channels); }
+
 // launchers implemented in seg_gemm.hip / seg_conv.hip; each validates its op and returns AVL_*
 int launch_gemm(const avl_seg_op& op, hipStream_t s);
 int validate_gemm(const avl_seg_op& op);

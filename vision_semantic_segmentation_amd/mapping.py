@@ -488,31 +488,12 @@ class SemanticMapping(object):
         reference layout) or [N,4] float32 (AoS); ``semantic``: CUDA uint8 tensor, either the colour
         image [H,W,3] (src_kind="rgb") or a class-id map [h,w] (src_kind="classmap", sampled as the
         nearest-upscaled image of size ``image_size`` = (H, W))."""
-        pts, n, dtype, pstride, cstride = self._points_view(pcd)
-        T = self._origin_to_velodyne(pose) if pcd_frame_id != "velodyne" else None
-        g = self.grid
-        g.ensure_capacity(n)
-        gs = g.struct()
-        P = _dbl(camera_calibration.P)
-        Tc = _dbl(T) if T is not None else None
-        cm = _dbl(self.confusion_matrix)
-        colors = self._colors_host()
-        bonus = self._bonus_classes()
-        if src_kind == "rgb":
-            assert semantic.dim() == 3 and semantic.shape[2] == 3 and semantic.dtype == torch.uint8
-            sh, sw = int(semantic.shape[0]), int(semantic.shape[1])
-            ih, iw = sh, sw
-            kind, lut = _lib.AVL_SRC_RGB, None
-        else:
-            assert semantic.dim() == 2 and semantic.dtype == torch.uint8
-            sh, sw = int(semantic.shape[0]), int(semantic.shape[1])
-            ih, iw = (sh, sw) if image_size is None else (int(image_size[0]), int(image_size[1]))
-            kind = _lib.AVL_SRC_CLASSMAP
-            lut = self._lut_host(net_palette)
+        assert semantic.dtype == torch.uint8
+        sh, sw, ih, iw, kind, lut = self._semantic_source(semantic.shape, src_kind, image_size, net_palette)
+        view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, camera_calibration.P, stream)
         semantic = semantic.contiguous()
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-        rc = _lib.lib().avl_fused_frame(C.byref(gs), pts, n, dtype, pstride, cstride, P, Tc, float(self.pcd_range_max),
-                                        kind, _ptr(semantic), sw, sh, iw, ih, lut, colors, cm, bonus, C.c_void_p(s))
+        rc = _lib.lib().avl_fused_frame(C.byref(gs), *view, P, T, float(self.pcd_range_max), kind, _ptr(semantic), sw, sh, iw, ih, lut,
+                                        self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), s)
         _lib.check(rc, "avl_fused_frame")
         self._map_host = None
         self.frames_mapped += 1
@@ -541,35 +522,18 @@ class SemanticMapping(object):
         for t in views:
             if tuple(t.shape) != shape or t.dtype != torch.uint8 or not t.is_cuda:
                 raise ValueError("the views' semantic sources must be uint8 CUDA tensors of one size")
-        if src_kind == "rgb":
-            assert len(shape) == 3 and shape[2] == 3
-            sh, sw = int(shape[0]), int(shape[1])
-            ih, iw = sh, sw
-            kind, lut = _lib.AVL_SRC_RGB, None
-        else:
-            assert len(shape) == 2
-            sh, sw = int(shape[0]), int(shape[1])
-            ih, iw = (sh, sw) if image_size is None else (int(image_size[0]), int(image_size[1]))
-            kind = _lib.AVL_SRC_CLASSMAP
-            lut = self._lut_host(net_palette)
+        sh, sw, ih, iw, kind, lut = self._semantic_source(shape, src_kind, image_size, net_palette)
         bonus = self._bonus_classes()
         if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
             for t, cam in zip(views, cameras):
                 self.frame_device(pcd, pcd_frame_id, t, pose, cam, src_kind=src_kind, image_size=image_size, net_palette=net_palette,
                                   stream=stream)
             return
-        pts, n, dtype, pstride, cstride = self._points_view(pcd)
-        T = self._origin_to_velodyne(pose) if pcd_frame_id != "velodyne" else None
-        g = self.grid
-        g.ensure_capacity(n)
-        gs = g.struct()
+        view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]), stream)
         views = [t.contiguous() for t in views]
         src = (C.c_void_p * V)(*[t.data_ptr() for t in views])
-        P = _dbl(np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]))
-        s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-        rc = _lib.lib().avl_fused_frame_views(C.byref(gs), pts, n, dtype, pstride, cstride, V, P, _dbl(T) if T is not None else None,
-                                              float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut, self._colors_host(),
-                                              _dbl(self.confusion_matrix), bonus, C.c_void_p(s))
+        rc = _lib.lib().avl_fused_frame_views(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
+                                              self._colors_host(), _dbl(self.confusion_matrix), bonus, s)
         _lib.check(rc, "avl_fused_frame_views")
         self._map_host = None
         self.frames_mapped += V
@@ -586,10 +550,10 @@ class SemanticMapping(object):
     def project_pcd_device(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """avl_project_pcd: returns CUDA tensors (out_pcd f64[4,N], out_label u8[3,N], count int32[1]);
         only the first `count` columns are meaningful."""
-        pts, n, dtype, pstride, cstride = self._points_view(pcd)
+        view, T, _, P, s = self._frame_args(pcd, pcd_frame_id, pose, camera_calibration.P, grid=False)
         img = self._as_device_u8(image)
         assert img.dim() == 3 and img.shape[2] == 3
-        T = self._origin_to_velodyne(pose) if pcd_frame_id != "velodyne" else None
+        n = view[1]
         ld = max(n, 1)
         out_pcd = torch.empty((4, ld), dtype=torch.float64, device=self.device)
         out_label = torch.empty((3, ld), dtype=torch.uint8, device=self.device)
@@ -597,11 +561,8 @@ class SemanticMapping(object):
         need = int(_lib.lib().avl_project_pcd_scratch_bytes(n))
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        rc = _lib.lib().avl_project_pcd(pts, n, dtype, pstride, cstride, _dbl(camera_calibration.P),
-                                        _dbl(T) if T is not None else None, float(self.pcd_range_max),
-                                        _ptr(img), int(img.shape[1]), int(img.shape[0]),
-                                        _ptr(out_pcd), _ptr(out_label), ld, _ptr(count), _ptr(self._scratch), C.c_void_p(s))
+        rc = _lib.lib().avl_project_pcd(*view, P, T, float(self.pcd_range_max), _ptr(img), int(img.shape[1]), int(img.shape[0]),
+                                        _ptr(out_pcd), _ptr(out_label), ld, _ptr(count), _ptr(self._scratch), s)
         _lib.check(rc, "avl_project_pcd")
         return out_pcd, out_label, count[:1]
 
@@ -784,6 +745,30 @@ class SemanticMapping(object):
         a = np.ascontiguousarray(a)
         assert a.dtype == np.uint8, "semantic images / labels must be uint8"
         return torch.from_numpy(a).to(self.device)
+
+    def _semantic_source(self, shape, src_kind, image_size, net_palette):
+        """-> (sh, sw, ih, iw, kind, lut) of a semantic source of ``shape``: a colour image [H,W,3] is its own image; a class map
+        [h,w] stands for the image of ``image_size`` (its own size if None) and votes through the palette's LUT."""
+        if src_kind == "rgb":
+            assert len(shape) == 3 and shape[2] == 3
+            sh, sw = int(shape[0]), int(shape[1])
+            return sh, sw, sh, sw, _lib.AVL_SRC_RGB, None
+        assert len(shape) == 2
+        sh, sw = int(shape[0]), int(shape[1])
+        ih, iw = (sh, sw) if image_size is None else (int(image_size[0]), int(image_size[1]))
+        return sh, sw, ih, iw, _lib.AVL_SRC_CLASSMAP, self._lut_host(net_palette)
+
+    def _frame_args(self, pcd, pcd_frame_id, pose, P, stream=None, grid=True):
+        """What every frame call hands the library alike -> (points view, T or None, grid struct grown to the cloud or None,
+        P, stream), each in its ctypes form."""
+        view = self._points_view(pcd)
+        T = _dbl(self._origin_to_velodyne(pose)) if pcd_frame_id != "velodyne" else None
+        gs = None
+        if grid:
+            self.grid.ensure_capacity(view[1])
+            gs = self.grid.struct()
+        s = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        return view, T, gs, _dbl(P), C.c_void_p(s)
 
     def _points_view(self, pcd):
         """-> (ctypes ptr, n, avl dtype, point_stride, comp_stride) and keeps the tensor alive."""

@@ -1,0 +1,121 @@
+"""The operands of test_gpu_exact_ops.py, checked without a GPU (tests/_exact_operands.py builds them and asserts, while it does,
+that the float32 and float64 host evaluations agree, that every expected output is finite, that >= 20 % of the 16-bit outputs
+round and that exact ties round in both directions), and the teeth of the comparison: for one case of each op a subtly wrong host
+result -- another rounding rule, one product dropped, two taps swapped, a K block skipped in the last row tile, the residual
+added after the ReLU -- is not torch.equal to the expected tensor."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _exact_operands as X
+
+PRECS = ["f32", "bf16", "f16"]
+
+
+@pytest.mark.parametrize("case", X.GEMM_CASES + [X.GEMM_RING256], ids=str)
+def test_gemm_operands(case):
+    for prec in PRECS:
+        c = X.gemm_case(case, prec)
+        assert c["want"].shape == (case[0], case[2])
+
+
+@pytest.mark.parametrize("case", X.GEMM_ARGMAX, ids=str)
+def test_classifier_operands_hold_ties(case):
+    c = X.gemm_case(case, "f16")
+    assert c["tied_rows"] > 0 and c["want"].dtype == torch.float32
+
+
+@pytest.mark.parametrize("case", X.CONV3X3_CASES, ids=str)
+def test_dense_conv_operands(case):
+    H, W, cg, G, s, d = case
+    for prec in PRECS:
+        X.conv_case(H, W, cg * G, G, 3, s, d, d, prec)
+    X.conv_split_case(H, W, cg * G, G, s, d, True)
+
+
+def test_dense_conv_split_operands_without_lo_plane():
+    for (H, W, cg, G, s, d), with_lo in X.CONV3X3_SPLIT:
+        if not with_lo:
+            X.conv_split_case(H, W, cg * G, G, s, d, False)
+
+
+def test_grouped_and_depthwise_operands():
+    for H, W, cg, s, d in X.GCONV_MFMA_CASES:
+        for prec in ("bf16", "f16"):
+            X.conv_case(H, W, 32 * cg, 32, 3, s, d, d, prec)
+    for cg in X.GCONV_DIRECT_CG:
+        for H, W, s, d in X.GCONV_DIRECT_SHAPES:
+            for prec in PRECS:
+                X.conv_case(H, W, 16 * cg, 16, 3, s, d, d, prec)
+    for H, W, Cc, d, pad, relu in X.DW3_CASES:
+        for prec in PRECS:
+            X.conv_case(H, W, Cc, Cc, 3, 1, pad, d, prec, relu=relu)
+    for ks in X.DWK_KS:
+        for H, W, Cc, batch in X.DWK_SHAPES:
+            for prec in PRECS:
+                X.conv_case(H, W, Cc, Cc, ks, 1, 0, 1, prec, relu=bool(ks & 1), batch=batch)
+
+
+@pytest.mark.parametrize("hw", X.STEM_SIZES, ids=str)
+def test_stem_operands(hw):
+    for prec in PRECS:
+        for fmt in ("f32", "u8"):
+            X.stem_case(hw[0], hw[1], fmt, "direct", prec)
+            if prec != "f32":
+                X.stem_case(hw[0], hw[1], fmt, "mfma", prec)
+
+
+def test_dwpw_operands():
+    for H, W, K, N, d, pad, relu in X.DWPW_CASES:
+        for prec in ("bf16", "f16"):
+            X.dwpw_case(H, W, K, N, d, pad, prec, relu)
+
+
+def test_the_evaluator_is_the_convolution():
+    """the im2col evaluator against F.conv2d in float64: dense, grouped, depthwise, strided, dilated past the image"""
+    for H, W, Cc, G, k, s, pad, d in ((9, 14, 64, 1, 3, 1, 2, 2), (11, 17, 64, 16, 3, 2, 2, 2), (5, 7, 64, 64, 3, 1, 12, 12), (13, 9, 64, 64, 5, 1, 0, 1)):
+        c = X.conv_case(H, W, Cc, G, k, s, pad, d, "f32", tag=1)
+        cg = Cc // G
+        w = c["W4"].reshape(Cc, k, k, cg).permute(0, 3, 1, 2).double()
+        ref = F.relu(F.conv2d(c["x"].permute(0, 3, 1, 2).double(), w, c["bias"].double(), stride=s, padding=pad, dilation=d, groups=G))
+        assert torch.equal(ref[0].permute(1, 2, 0).reshape(-1, Cc), c["v"])
+
+
+def _teeth_cases():
+    return {
+        "gemm": X.gemm_case((777, 2048, 512, True, True, "slices"), "bf16"),
+        "gemm_f16": X.gemm_case((777, 256, 128, True, False, None), "f16"),
+        "conv3x3": X.conv_case(13, 21, 256, 1, 3, 1, 2, 2, "f16"),
+        "gconv_mfma": X.conv_case(23, 45, 256, 32, 3, 2, 2, 2, "bf16"),
+        "gconv_direct": X.conv_case(13, 21, 64, 16, 3, 1, 1, 1, "f16"),
+        "dwconv3": X.conv_case(17, 23, 128, 128, 3, 1, 12, 12, "bf16", relu=False),
+        "dwconv_k": X.conv_case(13, 29, 64, 64, 5, 1, 0, 1, "f16"),
+        "stem": X.stem_case(33, 47, "f32", "mfma", "bf16"),
+        "stem_u8": X.stem_case(33, 47, "u8", "mfma", "f16"),
+        "dwpw": X.dwpw_case(19, 27, 128, 256, 12, 12, "f16", True),
+    }
+
+
+def test_every_mutation_is_caught():
+    caught = {m: 0 for m in X.MUTATIONS}
+    for name, c in _teeth_cases().items():
+        assert torch.equal(X.evaluate(c), c["want"]), name                      # the evaluator reproduces the expected tensor ...
+        for mut in X.MUTATIONS:
+            if X.applicable(c, mut):
+                assert not torch.equal(X.evaluate(c, mut), c["want"]), (name, mut)      # ... and no mutation of it does
+                caught[mut] += 1
+    assert all(caught.values()), caught
+    # the depthwise stage of the fused op: two swapped taps
+    a, b = X.dwpw_case(19, 27, 128, 256, 12, 12, "f16", True), X.dwpw_case(19, 27, 128, 256, 12, 12, "f16", True, dw_mut="swap_taps")
+    assert not torch.equal(a["want"], b["want"])
+
+
+def test_rounding_mutations_differ_only_where_they_should():
+    v = torch.tensor([257.0, 259.0, -257.0, -259.0, 258.0, 300.5], dtype=torch.float64)
+    assert X.round_toward_zero(v, "bf16").tolist() == [256.0, 258.0, -256.0, -258.0, 258.0, 300.0]
+    assert X.round_half_away(v, "bf16").tolist() == [258.0, 260.0, -258.0, -260.0, 258.0, 300.0]
+    assert v.to(torch.bfloat16).tolist() == [256.0, 260.0, -256.0, -260.0, 258.0, 300.0]
+    v = torch.tensor([2049.0, 2051.0, -2049.0, -2051.0, 2050.0], dtype=torch.float64)
+    assert X.round_toward_zero(v, "f16").tolist() == [2048.0, 2050.0, -2048.0, -2050.0, 2050.0]
+    assert X.round_half_away(v, "f16").tolist() == [2050.0, 2052.0, -2050.0, -2052.0, 2050.0]
+    assert v.to(torch.float16).tolist() == [2048.0, 2052.0, -2048.0, -2052.0, 2050.0]

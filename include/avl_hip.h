@@ -347,6 +347,42 @@ int avl_class_hulls(const uint8_t* maps, int n, int h, int w, const int32_t* cla
                     int area_threshold, int drop_first, int32_t* vertices, int32_t* n_vertices, int32_t* areas, int32_t* roots,
                     void* scratch, void* stream);
 
+/* ---- ground plane from the cloud: RANSAC around the reference's plane model (src/plane_3d.py; csrc/seg_plane.hip) ---------------
+ * The reference has the model only: Plane3D.fit(data, "min") (plane_3d.py:45-63), normalize (:98-107), eval (:65-80) and
+ * distance_to_plane (:82-88); its node receives the plane from another package (vision_semantic_segmentation_node.py:199-201).
+ * One call hypothesises, scores, selects and sums the winner's moments on `stream` without host synchronisation; the library keeps
+ * no pointer after it.  Integer atomics and fixed-order sums only: two runs give the same bits.
+ * Argument errors (a NULL pointer, n < 3 or above 2^27, n_hyp outside 1 .. AVL_PLANE_MAX_HYP, norm not 1 or 2, tolerance <= 0, a bad dtype or
+ * stride) return AVL_E_ARG before anything touches the device. */
+#define AVL_PLANE_W_NONE 0             /* weight method "none" (plane_3d.py:76-77) */
+#define AVL_PLANE_W_XNORM 1            /* weight method "x norm" (plane_3d.py:66-75) */
+#define AVL_PLANE_MAX_HYP 1024
+#define AVL_PLANE_RESULT_WORDS 24      /* 8-byte words, layout below */
+/* bytes of scratch avl_plane_ransac needs (0 for sizes it refuses) */
+int64_t avl_plane_scratch_bytes(int n, int n_hyp);
+/* Points are addressed as in avl_project_points (f32 or f64, any strides, widened to double); with T_host (row-major 4x4) the fitted
+ * frame is Xv = T [x, y, z, 1].  roi_host = xmin, xmax, ymin, ymax, zmin, zmax in the fitted frame (bounds included), or NULL.
+ *  1. A point is USED when its three fitted coordinates are finite and inside the roi; the others take no part in anything (a
+ *     departure: in the reference one NaN turns np.max of plane_3d.py:74, and with it every weight, into NaN).  For
+ *     AVL_PLANE_W_XNORM recip_i = 1 / (|x_i - x0|^norm + 1) (plane_3d.py:67-73) and its maximum over the used points (:74, exact).
+ *  2. Hypothesis h = Plane3D.fit of the points triples[h][0..2] (plane_3d.py:47-51) followed by normalize (:99-106), in float64 with
+ *     the reference's expressions.  It is invalid -- plane (0, 0, 0, 0), count 0 -- when an index is outside [0, n), a point of the
+ *     triple is not used, data[0] == data[1] (:47), s == 0 (:100) or, after normalisation, c < min_c (the cosine of the largest
+ *     tilt the caller accepts).
+ *  3. count[h] = number of used points with eval < tolerance (plane_3d.py:65-80):
+ *     |a x + b y + c z + d| / sqrt(a^2 + b^2 + c^2) * w_i, w_i = recip_i / max recip (AVL_PLANE_W_XNORM) or 1 (AVL_PLANE_W_NONE).
+ *  4. best = the hypothesis with the largest count, the lowest index among equals; -1 when every count is 0.
+ *  5. Moments of the winner's inliers about p0 = the first point of its triple, delta = p - p0, in float64.
+ * planes_out double [n_hyp][4] (32-byte aligned) and counts_out int32 [n_hyp] on the device, either may be NULL.
+ * result, on the device, AVL_PLANE_RESULT_WORDS 8-byte words: 0 best (int64), 1 inlier count (int64), 2 used points (int64),
+ * 3 valid hypotheses (int64), 4-7 the winner's plane a, b, c, d (double, as all that follow), 8-10 p0, 11 the moments' n,
+ * 12-14 sum(delta), 15-20 sum(delta delta^T) as xx, xy, xz, yy, yz, zz, 21-23 zero.  best = -1: words 4-20 are zero.
+ * scratch: avl_plane_scratch_bytes(n, n_hyp) bytes, 32-byte aligned. */
+int avl_plane_ransac(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* T_host,
+                     const double* roi_host, const int32_t* triples /* DEVICE int32 [n_hyp][3], point indices */, int n_hyp,
+                     int weight_method, double x0, int norm /* 1 | 2 */, double tolerance, double min_c, double* planes_out,
+                     int32_t* counts_out, void* result, void* scratch, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

@@ -14,6 +14,9 @@ AVL_SRC_RGB, AVL_SRC_CLASSMAP = 0, 1
 AVL_MAX_MAP_CLASSES = 16
 AVL_MAX_VIEWS = 4               # views of one avl_fused_frame_views call
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
+AVL_PLANE_W_NONE, AVL_PLANE_W_XNORM = 0, 1
+AVL_PLANE_MAX_HYP = 1024
+AVL_PLANE_RESULT_WORDS = 24     # 8-byte words of avl_plane_ransac's result block
 AVL_STEM_CAMERA_BYTES = 64      # one camera block of a pre-processing stem (avl_stem_camera_set); a raw batch has one per image
 
 _lib = None
@@ -69,6 +72,8 @@ _SIGNATURES = {
     "avl_hull_scratch_bytes": (_i64, [_i, _i, _i, _i]),
     "avl_label_components": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "avl_class_hulls": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_plane_scratch_bytes": (_i64, [_i, _i]),
+    "avl_plane_ransac": (_i, [_vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -124,3 +129,27 @@ def host_array(values, ctype):
     """A ctypes array holding `values` (flattened); keep the return value alive across the call."""
     flat = [v for v in values]
     return (ctype * len(flat))(*flat)
+
+
+def points_view(pcd, device):
+    """A point cloud [4, N] (the reference's layout) or [N, 4], ndarray or tensor, as avl_project_points addresses it ->
+    (tensor on `device` that must outlive the call, n, avl dtype, point_stride, comp_stride).  float32 and float64 are kept,
+    anything else becomes float64."""
+    import numpy as np
+    import torch
+    if not isinstance(pcd, torch.Tensor):
+        a = np.asarray(pcd)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        pcd = torch.from_numpy(np.ascontiguousarray(a))
+    if pcd.dtype not in (torch.float32, torch.float64):
+        pcd = pcd.to(torch.float64)
+    t = pcd.to(device).contiguous()
+    es = t.element_size()
+    dtype = AVL_F64 if t.dtype == torch.float64 else AVL_F32
+    if t.dim() == 2 and t.shape[0] == 4:            # SoA [4,N]: the reference layout
+        n = int(t.shape[1])
+        return t, n, dtype, es, es * max(n, 1)
+    if t.dim() == 2 and t.shape[1] == 4:            # AoS [N,4]
+        return t, int(t.shape[0]), dtype, 4 * es, es
+    raise ValueError("point cloud must be [4,N] or [N,4], got %s" % (tuple(t.shape),))

@@ -153,5 +153,19 @@ def get_cfg_defaults():
     # plane (vision_semantic_segmentation_node.py:104-106, commented out in the reference: [2, 1] is what those two lines ask for).
     # [] = off: the hull code is never touched
     C.VISION_SEM_SEG.CONVEX_HULL_CLASSES = []
+    # build-specific: where the ground plane of the extraction comes from.  "callback" = plane_callback only (the reference: another
+    # package publishes /estimated_plane); nothing below is touched.  "cloud" = VisionSemanticSegmentationNode.cloud_callback estimates
+    # it from the LiDAR cloud on the GPU (ground_plane.estimate_ground_plane_device; plane_callback keeps working).  The values
+    # are this project's choices -- the reference has the plane model but no RANSAC driver
+    C.VISION_SEM_SEG.GROUND_PLANE = CfgNode()
+    C.VISION_SEM_SEG.GROUND_PLANE.SOURCE = "callback"
+    C.VISION_SEM_SEG.GROUND_PLANE.HYPOTHESES = 256
+    C.VISION_SEM_SEG.GROUND_PLANE.SEED = 0
+    C.VISION_SEM_SEG.GROUND_PLANE.TOLERANCE = 0.1         # on Plane3D.eval's cost: metres at x = WEIGHT_X0, looser further out
+    C.VISION_SEM_SEG.GROUND_PLANE.MAX_TILT_DEG = 30.0     # hypotheses whose normal is further from +z are dropped
+    C.VISION_SEM_SEG.GROUND_PLANE.WEIGHT_X0 = 0.0         # Plane3D's "x norm" weight (plane_3d.py:19): x0 and the norm, 1 or 2
+    C.VISION_SEM_SEG.GROUND_PLANE.WEIGHT_NORM = 1
+    C.VISION_SEM_SEG.GROUND_PLANE.REFINE = True           # least-squares plane of the winner's inliers instead of the winner itself
+    C.VISION_SEM_SEG.GROUND_PLANE.ROI = []                # [xmin, xmax, ymin, ymax, zmin, zmax] in the velodyne frame; [] = none
     C.VISION_SEM_SEG.SEM_SEG_NETWORK = get_network_cfg_defaults()
     return C

@@ -221,10 +221,7 @@ class SemanticMapping(object):
 
     def set_velodyne_to_baselink(self):
         """mapping.py:165-170"""
-        T = euler_matrix(0., 0.140, 0.)
-        t = np.array([[2.64, 0, 1.98]]).T
-        T[0:3, -1::] = t
-        return T
+        return velodyne_to_baselink()
 
     # ------------------------------------------------------------------ the grid
     @property
@@ -710,8 +707,22 @@ class SemanticMapping(object):
     # ------------------------------------------------------------------ helpers
     def _origin_to_velodyne(self, pose):
         """mapping.py:368-369 (host, float64 4x4)."""
-        T_base_to_origin = get_transform_from_pose(pose)
-        return np.linalg.inv(np.matmul(T_base_to_origin, self.T_velodyne_to_basklink))
+        return origin_to_velodyne(pose, self.T_velodyne_to_basklink)
+
+    def estimate_ground_plane(self, pose=None, **kw):
+        """The ground plane of the current cloud (``self.pcd`` in ``self.pcd_frame_id``) in the velodyne frame, estimated on the GPU:
+        ground_plane.estimate_ground_plane_device with its keyword arguments.  A cloud that is not in the velodyne frame needs the
+        pose (the transform of project_pcd, mapping.py:368-373).  Returns the GroundPlaneResult (asynchronous until ``.host()``)."""
+        from .ground_plane import estimate_ground_plane_device
+        with self._lock:
+            if self.pcd is None:
+                raise RuntimeError("estimate_ground_plane needs a point cloud: no pcd yet")
+            T = None
+            if self.pcd_frame_id != "velodyne":
+                if pose is None:
+                    raise ValueError("a cloud in frame %r needs the pose to reach the velodyne frame" % (self.pcd_frame_id,))
+                T = self._origin_to_velodyne(pose)
+            return estimate_ground_plane_device(self.pcd, T=T, device=self.device, **kw)
 
     def _colors_host(self):
         c = np.ascontiguousarray(self.label_colors, dtype=np.uint8).ravel()
@@ -772,23 +783,23 @@ class SemanticMapping(object):
 
     def _points_view(self, pcd):
         """-> (ctypes ptr, n, avl dtype, point_stride, comp_stride) and keeps the tensor alive."""
-        if not isinstance(pcd, torch.Tensor):
-            a = np.asarray(pcd)
-            if a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float64)
-            pcd = torch.from_numpy(np.ascontiguousarray(a))
-        if pcd.dtype not in (torch.float32, torch.float64):
-            pcd = pcd.to(torch.float64)
-        t = pcd.to(self.device).contiguous()
+        t, n, dtype, point_stride, comp_stride = _lib.points_view(pcd, self.device)
         self._pcd_dev = t
-        es = t.element_size()
-        dtype = _lib.AVL_F64 if t.dtype == torch.float64 else _lib.AVL_F32
-        if t.dim() == 2 and t.shape[0] == 4:            # SoA [4,N]: the reference layout
-            n = int(t.shape[1])
-            return _ptr(t), n, dtype, es, es * max(n, 1)
-        if t.dim() == 2 and t.shape[1] == 4:            # AoS [N,4]
-            return _ptr(t), int(t.shape[0]), dtype, 4 * es, es
-        raise ValueError("point cloud must be [4,N] or [N,4], got %s" % (tuple(t.shape),))
+        return _ptr(t), n, dtype, point_stride, comp_stride
+
+
+def velodyne_to_baselink():
+    """mapping.py:165-170 (host, float64 4x4)."""
+    T = euler_matrix(0., 0.140, 0.)
+    t = np.array([[2.64, 0, 1.98]]).T
+    T[0:3, -1::] = t
+    return T
+
+
+def origin_to_velodyne(pose, T_velodyne_to_baselink):
+    """mapping.py:368-369 (host, float64 4x4)."""
+    T_base_to_origin = get_transform_from_pose(pose)
+    return np.linalg.inv(np.matmul(T_base_to_origin, T_velodyne_to_baselink))
 
 
 def _to_numpy(a):

@@ -10,10 +10,12 @@ upscale + colouring is one more kernel (avl_colorize_labels); the frame is uploa
 Semantic extraction (:104-106, :138-201) is the node's second product: with VISION_SEM_SEG.CONVEX_HULL_CLASSES set, the convex
 hulls of the listed classes are taken from the frame's device labels in one call (semantic_convex_hull.class_hulls_device), only the
 vertices come to the host, and they are back-projected onto the ground plane of plane_callback in the reference's float64 arithmetic.
+With VISION_SEM_SEG.GROUND_PLANE.SOURCE = "cloud" that plane can also come from the LiDAR cloud (cloud_callback, ground_plane.py).
 """
 import ctypes as C
 import logging
 import threading
+import types
 
 import numpy as np
 import torch
@@ -112,6 +114,12 @@ class VisionSemanticSegmentationNode(object):
         self.hull_id = 0                # :70
         self._hull_workspace = None
         self._warned_no_plane = False
+        self.ground_plane_cfg = cfg.VISION_SEM_SEG.GROUND_PLANE
+        if self.ground_plane_cfg.SOURCE not in ("callback", "cloud"):
+            raise ValueError("VISION_SEM_SEG.GROUND_PLANE.SOURCE must be \"callback\" or \"cloud\", got %r" % (self.ground_plane_cfg.SOURCE,))
+        self._plane_workspace = None
+        self._plane_lock = threading.Lock()
+        self._warned_no_cloud_plane = False
         self._marker_msgs = None        # (Marker, MarkerArray, Point) once ROS markers are wanted
         self.pub_crosswalk_markers = self.pub_road_markers = None
         # rospy runs each subscription's callback on its own thread, and both cameras share one compiled plan (fixed
@@ -168,6 +176,44 @@ class VisionSemanticSegmentationNode(object):
         """:199-201 -- shape_msgs/Plane: msg.coef[0..3] = a, b, c, d of the estimated ground plane."""
         from .plane_3d import Plane3D
         self.plane = Plane3D(msg.coef[0], msg.coef[1], msg.coef[2], msg.coef[3])
+
+    def cloud_callback(self, points, pcd_frame_id="velodyne", pose=None):
+        """With GROUND_PLANE.SOURCE == "cloud": estimates the ground plane from the cloud (ndarray or tensor, [4, N] or [N, 4]) on the
+        GPU and sets ``self.plane`` exactly as plane_callback does, from the plane's four coefficients.  A cloud that is not in the
+        velodyne frame is taken there with the pose (SemanticMapping._origin_to_velodyne, mapping.py:368-373).  When no hypothesis
+        has an inlier the previous plane stays and one warning is logged.  With SOURCE == "callback" this does nothing.  Returns the
+        GroundPlaneResult, or None when nothing was estimated."""
+        gp = self.ground_plane_cfg
+        if gp.SOURCE != "cloud":
+            return None
+        from .ground_plane import GroundPlaneWorkspace, estimate_ground_plane_device
+        T = None
+        if pcd_frame_id != "velodyne":
+            if pose is None:
+                raise ValueError("a cloud in frame %r needs the pose to reach the velodyne frame" % (pcd_frame_id,))
+            from .mapping import origin_to_velodyne, velodyne_to_baselink
+            T = origin_to_velodyne(pose, velodyne_to_baselink())
+        device = points.device if isinstance(points, torch.Tensor) and points.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        points, n = _lib.points_view(points, device)[:2]
+        # its own lock: the workspace is shared between calls and a result refers to it until host() has read it.  The frame lock is
+        # not taken, so image callbacks go on while the estimate runs; plane_callback takes no lock (one attribute store)
+        with self._plane_lock:
+            ws = self._plane_workspace
+            if ws is None or not ws.fits(n, int(gp.HYPOTHESES), device):
+                ws = self._plane_workspace = GroundPlaneWorkspace(n, int(gp.HYPOTHESES), device)
+            weight = {'method': "x norm", 'param': {'x0': float(gp.WEIGHT_X0), 'norm': int(gp.WEIGHT_NORM)}}
+            result = estimate_ground_plane_device(points, hypotheses=int(gp.HYPOTHESES), seed=int(gp.SEED), tolerance=float(gp.TOLERANCE),
+                                                  weight=weight, max_tilt_deg=float(gp.MAX_TILT_DEG), roi=list(gp.ROI) or None, T=T,
+                                                  refine=bool(gp.REFINE), workspace=ws, device=device).host()
+        if result.plane is None:
+            if not self._warned_no_cloud_plane:
+                _log.warning("no ground plane in the cloud (%d points used, %d valid hypotheses): the previous plane stays",
+                             result.used, result.valid)
+                self._warned_no_cloud_plane = True
+            return result
+        p = result.plane
+        self.plane_callback(types.SimpleNamespace(coef=[p.a, p.b, p.c, p.d]))
+        return result
 
     def _camera_of(self, cam_frame_id):
         return {"camera1": self.cam1, "camera6": self.cam6}.get(cam_frame_id)

@@ -258,6 +258,41 @@ int avl_render_bev_map_thresholds(const void* map, int map_dtype, int Hm, int Wm
                                   const int32_t* priority_host, const double* thresholds_host, uint8_t* out, void* stream);
 /* apply_filter (renderer.py:175-189): 3x3 mean, kernel float32(1/9), BORDER_REFLECT_101; dst != src */
 int avl_grid_box_filter(const void* src, void* dst, int map_dtype, int Hm, int Wm, int C, void* stream);
+
+/* ---- live vehicle-centred map: the renderer's remaining functions, fused over a window of the grid ----------------------------
+ * The reference publishes its map once, at shutdown (pub_semantic_local_map, src/mapping.py:350); fill_black / resume_color
+ * (src/renderer.py:62-105), fill_edge (:192-196, plain slicing in renderer.py) and add_car_to_map (src/mapping.py:490-526)
+ * have no caller there.  avl_live_map writes out uint8[h][w][3], the window whose first cell is grid cell (x0, y0); the window
+ * may lie partly or wholly outside the grid.  The result is DEFINED as the crop of this chain over the whole grid:
+ *   F = avl_grid_box_filter(map) rounded to map_dtype (AVL_LIVE_FILTER; reflect-101 at the GRID's edge), else map;
+ *   R = avl_render_bev_map(F), or avl_render_bev_map_thresholds(F, priority_host, thresholds_host) with AVL_LIVE_THRESHOLDS
+ *       (priority_host NULL = 0..C-1; thresholds_host is required then);
+ *   B = R, or with AVL_LIVE_FILL fill_black(R) as avl_fill_black computes it with colors_host and fill_priority_host
+ *       [n_fill_priority], put back into an Hm x Wm frame with a one-cell black ring;
+ *   out[i][j] = B[x0 + i][y0 + j] inside the grid, black outside;
+ *   then, with car_host != NULL, the ego car: car_host = double[AVL_LIVE_CAR_DOUBLES] {cx, cy, cos yaw, sin yaw, u_lo, u_hi,
+ *   v_lo, v_hi} in CELLS (cx, cy = the vehicle's un-truncated grid position).  Pixel (i, j) takes car_color_host (NULL =
+ *   255, 0, 0) when, with gx = x0 + i, gy = y0 + j, dx = (gx + 0.5) - cx, dy = (gy + 0.5) - cy, u = c*dx + s*dy,
+ *   v = c*dy - s*dx (float64, no contraction): u_lo <= u < u_hi and v_lo <= v < v_hi.  The car goes last: its red has the
+ *   lane's R value and fill_black matches on R.  add_car_to_map's dimensions (4.0 m x 1.8 m), reference point (a quarter
+ *   length from the rear: u_lo = -L/(4 res), u_hi = 3L/(4 res), v = -+W/(2 res)) and colour are the caller's to pass; its
+ *   forward scatter of truncated pixels (holes under rotation, marked untested by its authors) is not reproduced.
+ * The grid is only read.  1 <= h, w <= 32768; C <= AVL_MAX_MAP_CLASSES; the filter needs Hm, Wm >= 2, the fill Hm, Wm >= 3. */
+#define AVL_LIVE_FILTER 1
+#define AVL_LIVE_THRESHOLDS 2
+#define AVL_LIVE_FILL 4
+#define AVL_LIVE_CAR_DOUBLES 8
+int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int x0, int y0, int h, int w,
+                 int flags, const int32_t* priority_host, const double* thresholds_host, const int32_t* fill_priority_host,
+                 int n_fill_priority, const double* car_host, const uint8_t* car_color_host, uint8_t* out, void* stream);
+/* fill_black (src/renderer.py:62-98) with resume_color (:101-105), reproduced as written: img uint8[X][Y][3] (device) ->
+ * out uint8[X-2][Y-2][3].  EVERY interior pixel, black or not (:91 is commented out), looks at the R channel of its 3 x 3
+ * neighbourhood; label i is present if a neighbour's R equals colors_host[i][0]; the last present label of priority_host
+ * [n_priority] (low to high; the reference's is 0, 3, 4, 2, 1) gives the pixel's R, none present gives 0; resume_color maps
+ * that R to the colour of the LAST label with it (black if there is none).  Matching is on R only.  X, Y >= 3;
+ * n_colors, n_priority <= AVL_MAX_MAP_CLASSES. */
+int avl_fill_black(const uint8_t* img, int X, int Y, const uint8_t* colors_host, int n_colors, const int32_t* priority_host,
+                   int n_priority, uint8_t* out, void* stream);
 /* End-of-run evaluation (test/test_semantic_mapping.py, called at src/mapping.py:341-344): convert_labels (:6-19) and the
  * counting part of Test.iou (:127-161) in one pass over the rendered colour map.
  *   color_map uint8[H][W][3]; mask uint8[>=H][mask_ld] (0 = invalid) or NULL;

@@ -147,6 +147,22 @@ def get_cfg_defaults():
     C.MAPPING.PLANAR_MATCH = "reference"
     # build-specific: element type of the grid on the GPU ("f64" = the reference's, "f32")
     C.MAPPING.GRID_DTYPE = "f64"
+    # build-specific: the live vehicle-centred map (SemanticMapping.live_map; the reference renders its map once, at shutdown).  With
+    # ENABLED, mapping() / mapping_views() render the window around the vehicle after every EVERY-th mapped frame into
+    # SemanticMapping.live_map_image (device) and live_map_host (pinned, valid once the stream is synchronised) and publish it on
+    # pub_semantic_local_map under ROS.  The live path only reads the grid.  On several GPUs it shows the rank's private grid
+    C.MAPPING.LIVE_MAP = CfgNode()
+    C.MAPPING.LIVE_MAP.ENABLED = False
+    C.MAPPING.LIVE_MAP.SIZE_M = [60.0, 60.0]              # window in metres along the grid's x, y; cells = int(size / RESOLUTION)
+    C.MAPPING.LIVE_MAP.EVERY = 1
+    C.MAPPING.LIVE_MAP.FILTER = True                      # renderer.apply_filter
+    C.MAPPING.LIVE_MAP.RENDER = "argmax"                  # render_bev_map; "thresholds": render_bev_map_with_thresholds
+    C.MAPPING.LIVE_MAP.PRIORITY = None
+    C.MAPPING.LIVE_MAP.THRESHOLDS = None
+    C.MAPPING.LIVE_MAP.FILL_BLACK = False                 # renderer.fill_black
+    C.MAPPING.LIVE_MAP.FILL_PRIORITY = [0, 3, 4, 2, 1]    # low to high (renderer.py:67)
+    C.MAPPING.LIVE_MAP.DRAW_CAR = True
+    C.MAPPING.LIVE_MAP.CAR_SIZE = [4.0, 1.8]              # length, width in metres (src/mapping.py:502-503)
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

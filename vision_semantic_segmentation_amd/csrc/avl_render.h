@@ -1,0 +1,61 @@
+// Device arithmetic that the end-of-run renderer (mapping.hip) and the live-map kernel (seg_livemap.hip) share, so that a window of
+// the live map is bit-equal to a crop of apply_filter + render_bev_map.  Both translation units are built with -ffp-contract=off.
+#pragma once
+#include "avl_common.h"
+
+namespace avl {
+
+struct RenderParams {
+    unsigned char colors[AVL_MAX_MAP_CLASSES * 3];
+    int priority[AVL_MAX_MAP_CLASSES];
+    double thresholds[AVL_MAX_MAP_CLASSES];
+};
+
+// np.sum(map, axis=2) of one contiguous row, in the map's own type and in NumPy's order (pairwise_sum in NumPy's
+// umath/loops_utils.h.src; C <= 16 stays below its 128-element block): fewer than 8 values are a left fold from 0; from 8 up,
+// eight accumulators r[j] = a[j], r[j] += a[i + j] for every further whole group of 8, then
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then a left fold of the remainder.  Which cells count as empty (sum == 0)
+// and the shares of the thresholds renderer depend on this rounding.  `at(c)` yields element c of the row.
+template <typename MapT, typename At>
+__device__ __forceinline__ MapT numpy_row_sum_of(int C, At at) {
+    if (C < 8) {
+        MapT s = (MapT)0;
+        for (int c = 0; c < C; ++c) s = s + at(c);
+        return s;
+    }
+    MapT r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = at(j);
+    int i = 8;
+    for (; i + 8 <= C; i += 8)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + at(i + j);
+    MapT s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < C; ++i) s = s + at(i);
+    return s;
+}
+
+template <typename MapT>
+__device__ __forceinline__ MapT numpy_row_sum(const MapT* row, int C) {
+    return numpy_row_sum_of<MapT>(C, [row](int c) { return row[c]; });
+}
+
+// apply_filter (renderer.py:175-189) at cell (y, x), channel c of src [Hm][Wm][C]: cv2.filter2D with ones(3,3,float32)/9,
+// BORDER_REFLECT_101 at the grid's edge, the nine products accumulated in double (dy outer, dx inner); the caller rounds to MapT.
+template <typename MapT>
+__device__ __forceinline__ double box_filter3_taps(const MapT* __restrict__ src, int Hm, int Wm, int C, int y, int x, int c) {
+    const double k = (double)(1.0f / 9.0f);
+    double acc = 0.0;
+    for (int dy = -1; dy <= 1; ++dy) {
+        int yy = y + dy;
+        yy = yy < 0 ? -yy : (yy >= Hm ? 2 * Hm - 2 - yy : yy);
+        for (int dx = -1; dx <= 1; ++dx) {
+            int xx = x + dx;
+            xx = xx < 0 ? -xx : (xx >= Wm ? 2 * Wm - 2 - xx : xx);
+            acc = acc + k * (double)src[((long long)yy * Wm + xx) * C + c];
+        }
+    }
+    return acc;
+}
+
+}  // namespace avl

@@ -12,6 +12,7 @@
 // Kernels are HBM/latency bound integer + f64 work: one point per lane, coalesced 16 B (f32 AoS)
 // or 8 B (f64 SoA) loads, a label gather served by L2, and an idempotent atomicOr per point.
 #include "avl_common.h"
+#include "avl_render.h"
 
 #include <climits>
 #include <cstdlib>
@@ -815,35 +816,10 @@ __global__ void __launch_bounds__(kBlock) k_views_sweep_words(MapT* __restrict__
 }
 
 // ================================================================ end-of-run rendering (src/renderer.py), SURVEY 8f row 3
-struct RenderParams {
-    unsigned char colors[AVL_MAX_MAP_CLASSES * 3];
-    int priority[AVL_MAX_MAP_CLASSES];
-    double thresholds[AVL_MAX_MAP_CLASSES];
-};
-
-// np.sum(map, axis=2) of one contiguous row, in the map's own type and in NumPy's order (pairwise_sum in NumPy's
-// umath/loops_utils.h.src; C <= 16 stays below its 128-element block): fewer than 8 values are a left fold from 0; from 8 up,
-// eight accumulators r[j] = a[j], r[j] += a[i + j] for every further whole group of 8, then
-// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then a left fold of the remainder.  Which cells count as empty (sum == 0)
-// and the shares of the thresholds renderer depend on this rounding.
-template <typename MapT>
-__device__ __forceinline__ MapT numpy_row_sum(const MapT* row, int C) {
-    if (C < 8) {
-        MapT s = (MapT)0;
-        for (int c = 0; c < C; ++c) s = s + row[c];
-        return s;
-    }
-    MapT r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = row[j];
-    int i = 8;
-    for (; i + 8 <= C; i += 8)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + row[i + j];
-    MapT s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < C; ++i) s = s + row[i];
-    return s;
-}
+// RenderParams, numpy_row_sum (np.sum(map, axis=2) in NumPy's order) and the filter's tap loop are in avl_render.h: the live-map kernel
+// (seg_livemap.hip) computes the same values from them.
+using avl::RenderParams;
+using avl::numpy_row_sum;
 
 // render_bev_map (renderer.py:32-59): colour of np.argmax (first maximum wins), black where the channel sum is 0
 template <typename MapT>
@@ -892,18 +868,7 @@ __global__ void __launch_bounds__(kBlock) k_box_filter3(const MapT* __restrict__
     const int c = (int)(i % C);
     const long long cell = i / C;
     const int x = (int)(cell % Wm), y = (int)(cell / Wm);
-    const double k = (double)(1.0f / 9.0f);
-    double acc = 0.0;
-    for (int dy = -1; dy <= 1; ++dy) {
-        int yy = y + dy;
-        yy = yy < 0 ? -yy : (yy >= Hm ? 2 * Hm - 2 - yy : yy);
-        for (int dx = -1; dx <= 1; ++dx) {
-            int xx = x + dx;
-            xx = xx < 0 ? -xx : (xx >= Wm ? 2 * Wm - 2 - xx : xx);
-            acc = acc + k * (double)src[((long long)yy * Wm + xx) * C + c];
-        }
-    }
-    dst[i] = (MapT)acc;
+    dst[i] = (MapT)avl::box_filter3_taps(src, Hm, Wm, C, y, x, c);
 }
 
 __global__ void __launch_bounds__(kBlock) k_colorize(const unsigned char* __restrict__ labels, int lw, int lh,

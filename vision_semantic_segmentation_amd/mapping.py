@@ -18,6 +18,9 @@ What differs from the reference, by design:
   * ``mapping()`` is fused: points are projected, labelled, voted and applied without the
     intermediate masked point list; ``frame_device()`` does the same for inputs already in HBM
     (e.g. the argmax label map straight from SemanticSegmentation).
+  * ``live_map()`` renders the window of the grid around the vehicle (filter, renderer, hole fill, ego car) in one kernel; with
+    MAPPING.LIVE_MAP.ENABLED ``mapping()`` / ``mapping_views()`` do so after the grid update.  The reference renders once, at
+    shutdown.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -34,7 +37,7 @@ from .camera import camera_setup_1, camera_setup_6
 from .config import get_cfg_defaults
 from .data.confusion_matrix import ConfusionMatrix
 from .labels import PALETTE_19, vote_lut
-from .utils.utils_ros import euler_matrix, get_transform_from_pose
+from .utils.utils_ros import euler_matrix, get_transform_from_pose, quaternion_matrix
 from .utils.logger import MyLogger
 
 # src/mapping.py:404 (= minus the global_map pose of :232-233)
@@ -181,6 +184,15 @@ class SemanticMapping(object):
         self.record_inputs = cfg.MAPPING.INPUT_DIR != ""
         self.frames_mapped = 0
 
+        # live vehicle-centred map (MAPPING.LIVE_MAP); off by default
+        self.live_cfg = cfg.MAPPING.LIVE_MAP
+        self.live_map_image = None             # uint8 [h, w, 3] on the device, the last live map
+        self.live_map_host = None              # the same in pinned host memory, valid once the stream is synchronised
+        self.live_map_origin = None            # grid cell of live_map_image[0, 0]
+        self.live_map_ready = None             # event recorded behind the copy into live_map_host
+        self.pub_semantic_local_map = getattr(self, "pub_semantic_local_map", None)
+        self._live_pose = None
+
         # device-side caches
         self._scratch = None
         self._pcd_dev = None
@@ -197,6 +209,8 @@ class SemanticMapping(object):
         self.sub_pose = rospy.Subscriber("/current_pose", PoseStamped, self.pose_callback)
         self.image_sub_cam1 = rospy.Subscriber("/camera1/semantic", Image, self.image_callback)
         self.image_sub_cam6 = rospy.Subscriber("/camera6/semantic", Image, self.image_callback)
+        self.pub_semantic_local_map = rospy.Publisher("/semantic_local_map", Image, queue_size=5)     # mapping.py:69
+        self._ros_image_cls = Image
         if self.depth_method == "points_map":
             self.sub_pcd = rospy.Subscriber("/reduced_map", PointCloud2, self.pcd_callback)
         elif self.depth_method == "points_raw":
@@ -411,6 +425,8 @@ class SemanticMapping(object):
     def mapping(self, semantic_image, pose, camera_calibration):
         """mapping.py:292-321 for the LiDAR depth methods: one fused project+vote+apply on the GPU.
         semantic_image: uint8[H,W,3] colourised labels (NumPy or a CUDA tensor)."""
+        if pose is not None:
+            self._live_pose = pose                                               # live_map(pose=None): the last pose mapped
         if self.depth_method not in ["points_map", "points_raw"]:                 # mapping.py:320-321
             img = self._as_device_u8(semantic_image)
             self.update_map_planar(self.map_dev, img, camera_calibration)
@@ -423,6 +439,8 @@ class SemanticMapping(object):
                                         "semantic_image": np.array(_to_numpy(semantic_image)), "pose": pose})
             img = self._as_device_u8(semantic_image)
             self.frame_device(self.pcd, self.pcd_frame_id, img, pose, camera_calibration, src_kind="rgb")
+        if self.live_cfg.ENABLED:
+            self._live_map_step(pose)
         if self.save_map_to_file:                                                # mapping.py:323-345, both depth modes
             self.save_map_to_file = False
             self.finish_run()
@@ -434,6 +452,8 @@ class SemanticMapping(object):
         semantic_images, cameras = list(semantic_images), list(cameras)
         if len(semantic_images) != len(cameras) or not cameras:
             raise ValueError("mapping_views needs one camera per semantic image, got %d and %d" % (len(semantic_images), len(cameras)))
+        if pose is not None:
+            self._live_pose = pose
         if self.depth_method not in ["points_map", "points_raw"]:                 # planar mode has no cloud to share
             for img, cam in zip(semantic_images, cameras):
                 self.update_map_planar(self.map_dev, self._as_device_u8(img), cam)
@@ -447,6 +467,8 @@ class SemanticMapping(object):
                                             "semantic_image": np.array(_to_numpy(img)), "pose": pose})
             self.frame_device_views(self.pcd, self.pcd_frame_id, [self._as_device_u8(img) for img in semantic_images], pose, cameras,
                                     src_kind="rgb")
+        if self.live_cfg.ENABLED:
+            self._live_map_step(pose)
         if self.save_map_to_file:
             self.save_map_to_file = False
             self.finish_run()
@@ -478,6 +500,69 @@ class SemanticMapping(object):
         if self.ground_truth_dir != "":                                          # :342-345
             Test(ground_truth_dir=self.ground_truth_dir, logger=self.logger).test_single_map(color_dev)
         return color_map
+
+    # ------------------------------------------------------------------ live vehicle-centred map
+    def live_map_window(self, pose, size_cells=None):
+        """-> ((x0, y0), (h, w), (cx, cy)): the live map's window for `pose`.  The vehicle's cell is
+        trunc((pose.xy + PCD_ORIGIN_OFFSET.xy - boundary minimum) / resolution), the expression that puts points on the grid
+        (mapping.py:404-409); the window's first cell is that cell minus size // 2; (cx, cy) is the un-truncated position in cells."""
+        if size_cells is None:
+            size_cells = [int(float(v) / self.resolution) for v in self.live_cfg.SIZE_M]
+        h, w = int(size_cells[0]), int(size_cells[1])
+        xy = np.array(_pose_to_array(pose)[:2], dtype=np.float64)
+        cxy = (xy + np.array(PCD_ORIGIN_OFFSET[:2]) - np.array([self.map_boundary[0][0], self.map_boundary[1][0]], dtype=np.float64)) / self.resolution
+        with np.errstate(invalid="ignore"):
+            centre = cxy.astype(np.int32)
+        return (int(centre[0]) - h // 2, int(centre[1]) - w // 2), (h, w), (float(cxy[0]), float(cxy[1]))
+
+    def live_map(self, pose=None, size_cells=None, out=None, stream=None):
+        """The map around the vehicle as a uint8 CUDA tensor [h, w, 3], rendered by one kernel (renderer.render_window with
+        MAPPING.LIVE_MAP's settings): out[i, j] is grid cell (x0 + i, y0 + j) in the global map's orientation (no heading-up
+        rotation), black where the window leaves the grid, the ego footprint painted last.  ``pose`` None = the last pose mapped;
+        ``size_cells`` None = LIVE_MAP.SIZE_M.  Reads the grid only -- unlike finish_run, which replaces it by its filtered self.
+        On several GPUs this is the rank's private grid, not global_map()."""
+        from . import renderer
+        lc = self.live_cfg
+        pose = self._live_pose if pose is None else pose
+        if pose is None:
+            raise RuntimeError("live_map needs a pose: none was given and no frame has been mapped with one")
+        origin, size, (cx, cy) = self.live_map_window(pose, size_cells)
+        car = None
+        if lc.DRAW_CAR:
+            c, s = pose_heading(pose)
+            car = renderer.car_block(cx, cy, c, s, self.resolution, lc.CAR_SIZE)
+        if lc.RENDER not in ("argmax", "thresholds"):
+            raise ValueError("MAPPING.LIVE_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (lc.RENDER,))
+        thresholds = None
+        if lc.RENDER == "thresholds":
+            thresholds = lc.THRESHOLDS if lc.THRESHOLDS is not None else [0.01] * self.map_depth
+        img = renderer.render_window(self.map_dev, self.label_colors, origin, size, filter=bool(lc.FILTER), thresholds=thresholds,
+                                     priority=lc.PRIORITY if lc.RENDER == "thresholds" else None, fill=bool(lc.FILL_BLACK),
+                                     fill_priority=lc.FILL_PRIORITY, car=car, out=out, stream=stream)
+        self.live_map_origin = origin
+        return img
+
+    def _live_map_step(self, pose):
+        """mapping()'s live branch: on every EVERY-th call (the first included) render the window, keep it, start its copy into pinned memory and --
+        under ROS -- publish it (sensor_msgs/Image, 8UC3, as mapping.py:349-350 does with the end-of-run map)."""
+        self._live_frames = getattr(self, "_live_frames", 0) + 1
+        if self._live_pose is None or (self._live_frames - 1) % max(int(self.live_cfg.EVERY), 1) != 0:
+            return
+        img = self.live_map()
+        self.live_map_image = img
+        if self.live_map_host is None or self.live_map_host.shape != img.shape:
+            self.live_map_host = torch.empty(tuple(img.shape), dtype=torch.uint8).pin_memory()
+            self.live_map_ready = torch.cuda.Event()
+        self.live_map_host.copy_(img, non_blocking=True)      # stream-ordered behind the kernel and behind the previous copy
+        self.live_map_ready.record(torch.cuda.current_stream(self.device))
+        if self._ros is not None and self.pub_semantic_local_map is not None:
+            self.live_map_ready.synchronize()
+            msg = self._ros_image_cls()
+            msg.height, msg.width = int(img.shape[0]), int(img.shape[1])
+            msg.encoding, msg.is_bigendian, msg.step = "8UC3", 0, int(img.shape[1]) * 3
+            msg.data = self.live_map_host.numpy().tobytes()
+            msg.header.frame_id = "semantic_local_map"
+            self.pub_semantic_local_map.publish(msg)
 
     def frame_device(self, pcd, pcd_frame_id, semantic, pose, camera_calibration, src_kind="rgb",
                      image_size=None, net_palette=PALETTE_19, stream=None):
@@ -802,11 +887,23 @@ def origin_to_velodyne(pose, T_velodyne_to_baselink):
     return np.linalg.inv(np.matmul(T_base_to_origin, T_velodyne_to_baselink))
 
 
+def pose_heading(pose):
+    """(cos yaw, sin yaw) of the vehicle's x axis in the map's x, y plane, from the pose quaternion (host float64): the first column
+    of its rotation matrix, projected on the plane and normalised; (1, 0) for a vertical one."""
+    q = _pose_to_array(pose)[3:7]
+    R = quaternion_matrix(q)
+    c, s = float(R[0, 0]), float(R[1, 0])
+    n = float(np.hypot(c, s))
+    return (c / n, s / n) if n > 0.0 else (1.0, 0.0)
+
+
 def _to_numpy(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 def _pose_to_array(pose):
+    if not hasattr(pose, "position"):
+        return np.asarray(pose, dtype=np.float64)[:7]
     p, o = pose.position, pose.orientation
     return np.array([p.x, p.y, p.z, o.x, o.y, o.z, o.w], dtype=np.float64)
 

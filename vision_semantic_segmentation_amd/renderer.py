@@ -2,6 +2,11 @@
 render_bev_map_with_thresholds :131-172, apply_filter :175-189), which the reference runs once at shutdown
 (src/mapping.py:332-334).  Same function names and argument meaning; inputs may be NumPy arrays (results come
 back as NumPy) or CUDA tensors (results stay on the GPU), so a live map can be rendered every frame.
+
+The renderer's remaining functions are here too: fill_black with resume_color (:62-105) and fill_edge (:192-196), which the reference
+defines and never calls, and render_window, the per-frame front end: filter, renderer, hole fill and the ego car
+(src/mapping.py:490-526) over a window of the grid in one kernel (avl_live_map), bit-equal to a crop of the chain of the functions
+above.
 """
 import ctypes as C
 
@@ -9,6 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from .labels import LABEL_COLORS
+
+FILL_PRIORITY = (0, 3, 4, 2, 1)          # renderer.py:67, from low to high
+CAR_SIZE = (4.0, 1.8)                    # src/mapping.py:502-503: length, width in metres
+CAR_COLOR = (255, 0, 0)                  # src/mapping.py:525
 
 
 def _prep(map_):
@@ -71,3 +81,82 @@ def apply_filter(src):
     _lib.check(_lib.lib().avl_grid_box_filter(C.c_void_p(t.data_ptr()), C.c_void_p(dst.data_ptr()), dt, h, w, c, _stream(t)),
                "avl_grid_box_filter")
     return dst.cpu().numpy() if is_np else dst
+
+
+def fill_black(img, label_colors=LABEL_COLORS, priority_list=FILL_PRIORITY):
+    """renderer.py:62-98 with resume_color (:101-105), as written: EVERY pixel of the interior, black or not, takes the colour of the
+    highest-priority label whose R value occurs among the R values of its 3 x 3 neighbourhood (black if none does).  Matching is
+    on R only.  img uint8 [X, Y, 3] -> [X - 2, Y - 2, 3]; the colours and the priority list (low to high) are module constants in
+    the reference and arguments here.  NumPy in gives NumPy out, a CUDA tensor stays on the device."""
+    is_np = not isinstance(img, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(img)).cuda() if is_np else img.contiguous()
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("fill_black takes a uint8 [X, Y, 3] colour image")
+    x, y = int(t.shape[0]), int(t.shape[1])
+    lc = np.asarray(label_colors)
+    prio = [int(p) for p in priority_list]
+    out = torch.empty((max(x - 2, 0), max(y - 2, 0), 3), dtype=torch.uint8, device=t.device)
+    _lib.check(_lib.lib().avl_fill_black(C.c_void_p(t.data_ptr()), x, y, _colors(lc, len(lc)), len(lc), (C.c_int32 * max(len(prio), 1))(*prio),
+                                         len(prio), C.c_void_p(out.data_ptr()), _stream(t)), "avl_fill_black")
+    return out.cpu().numpy() if is_np else out
+
+
+def fill_edge(color_map):
+    """renderer.py:192-196: 250 on the outer ring, 254 in the 5 x 5 corner; in place (array or tensor) and returned."""
+    color_map[0, :, :] = 250
+    color_map[-1, :, :] = 250
+    color_map[:, 0, :] = 250
+    color_map[:, -1, :] = 250
+    color_map[0:5, 0:5] = 254
+    return color_map
+
+
+def car_block(cx, cy, cos_yaw, sin_yaw, resolution, size=CAR_SIZE):
+    """avl_live_map's car block: the vehicle at the un-truncated grid position (cx, cy) cells, heading (cos, sin) in the grid's x, y
+    axes, footprint `size` = (length, width) metres with the reference point a quarter length from the rear
+    (src/mapping.py:502-511)."""
+    length, width, res = float(size[0]), float(size[1]), float(resolution)
+    return (float(cx), float(cy), float(cos_yaw), float(sin_yaw),
+            -length / (4.0 * res), 3.0 * length / (4.0 * res), -width / (2.0 * res), width / (2.0 * res))
+
+
+def render_window(map, label_colors, origin, size, filter=True, thresholds=None, priority=None, fill=False,
+                  fill_priority=FILL_PRIORITY, car=None, car_color=CAR_COLOR, out=None, stream=None):
+    """The window of `size` = (h, w) cells whose first cell is grid cell `origin` = (x0, y0), uint8 [h, w, 3]: what
+    ``render_bev_map(apply_filter(map).astype(map.dtype), label_colors)[x0:x0 + h, y0:y0 + w]`` gives (bit for bit), black where the
+    window leaves the grid -- in one kernel, reading about nine windows' worth of the grid and writing no temporary.
+    filter=False skips apply_filter; `thresholds` (with `priority`, low to high) picks render_bev_map_with_thresholds; fill=True
+    applies fill_black (label_colors, fill_priority) over the grid's interior, with a one-cell black ring where its output is
+    smaller than the grid; `car` = car_block(...) paints the ego footprint last.  The grid is only read."""
+    t, is_np, dt = _prep(map)
+    hm, wm, c = t.shape
+    h, w = int(size[0]), int(size[1])
+    colors = _colors(label_colors, c)
+    flags = (_lib.AVL_LIVE_FILTER if filter else 0) | (_lib.AVL_LIVE_THRESHOLDS if thresholds is not None else 0) | \
+            (_lib.AVL_LIVE_FILL if fill else 0)
+    pr = th = None
+    if thresholds is not None:
+        thresholds = list(thresholds)
+        if len(thresholds) < c:
+            raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), c))
+        th = (C.c_double * c)(*[float(x) for x in thresholds[:c]])
+    if priority is not None:
+        if len(priority) != c:
+            raise ValueError("Each channel should have a priority.")
+        pr = (C.c_int32 * c)(*[int(p) for p in priority])
+    fp = [int(p) for p in fill_priority] if fill else []
+    car_c = col_c = None
+    if car is not None:
+        if len(car) != _lib.AVL_LIVE_CAR_DOUBLES:
+            raise ValueError("car is car_block(...): %d numbers" % _lib.AVL_LIVE_CAR_DOUBLES)
+        car_c = (C.c_double * _lib.AVL_LIVE_CAR_DOUBLES)(*[float(v) for v in car])
+        col_c = (C.c_uint8 * 3)(*[int(v) for v in car_color])
+    if out is None:
+        out = torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=t.device)
+    elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (h, w, t.device))
+    s = _stream(t) if stream is None else C.c_void_p(int(stream))
+    _lib.check(_lib.lib().avl_live_map(C.c_void_p(t.data_ptr()), dt, hm, wm, c, colors, int(origin[0]), int(origin[1]), h, w,
+                                       flags, pr, th, (C.c_int32 * max(len(fp), 1))(*fp), len(fp), car_c, col_c,
+                                       C.c_void_p(out.data_ptr()), s), "avl_live_map")
+    return out.cpu().numpy() if is_np else out

@@ -432,7 +432,9 @@ int avl_plane_ransac(const void* pts, int n, int dtype, int64_t point_stride, in
  * rows actually allocated (GEMM tiles read whole 128-row tiles, so M is padded up by the caller and
  * the plan checks it). */
 
-#define AVL_OP_STEM 1        /* uint8 RGB [H][W][3] (or fp32 [3][H][W]: in_format) -> normalise (semantic_segmentation.py:35-39) -> 7x7 s2 p3 conv +bias+ReLU */
+#define AVL_OP_STEM 1        /* uint8 RGB [H][W][3] (or fp32 [3][H][W]: in_format) -> normalise (semantic_segmentation.py:35-39) -> 7x7 s2 p3 conv +bias+ReLU.
+                                stride = 4 (16-bit MFMA stem, w_layout 1, not w_split): AVL_OP_MAXPOOL runs in the epilogue and out_h x out_w is the
+                                POOLED size -- the bits of stem -> max-pool, the conv map never written */
 #define AVL_OP_MAXPOOL 2     /* 3x3 s2 p1 (torchvision ResNet.maxpool)                                          */
 #define AVL_OP_GEMM 3        /* 1x1 conv: out[m][n] = act(sum_k in[row(m)][k] w[n][k] + bias[n] (+ in2[m][n])) */
 #define AVL_OP_GCONV 4       /* grouped or dense 3x3 conv, stride 1|2, dilation d, pad d, +bias+ReLU (Bottleneck.conv2; w_layout) */
@@ -586,6 +588,18 @@ typedef struct avl_seg_op {
      * 4-byte aligned); in_h x in_w = the network input of one image.  batch 0 or 1 with raw_batch = 1 is one frame.  Not with
      * AVL_IN_F32_CHW.  Any other value is AVL_E_ARG. */
     int32_t raw_batch;
+    /* GEMM on the 16-bit ring kernel only (not w_split = 2, not AVL_F32, not w_layout 1 or 4, no residual): a SECOND destination.
+     * out2 != NULL: `weight` / `bias` hold the rows of two 1x1 convs of the same input one after the other, out_c = both widths together;
+     * output columns [0, n_split) go to out (+ out_lo, row stride out_ld), columns [n_split, out_c) to out2 (+ out2_lo, row stride
+     * out2_ld; out2 points at the column of its buffer where column n_split lands).  n_split is a multiple of the N tile the op runs with
+     * (256 where out_c % 256 == 0 and the shape takes the 256 x 256 tile, else 128), so an output tile belongs to one destination; each
+     * value is what the conv alone computes, bit for bit.  out_rows counts the rows of the shorter of the two buffers.
+     * A ring GEMM also takes stride = s > 1 (Bottleneck.downsample of a striding block): in_h x in_w is then the UN-sampled input image,
+     * out_h x out_w = ((in_h - 1) / s + 1) x ((in_w - 1) / s + 1), and output row (oy, ox) of image n reads input pixel
+     * n * in_h * in_w + oy * s * in_w + ox * s -- AVL_OP_SUBSAMPLE without its launch and its copy; in_rows >= batch * in_h * in_w. */
+    void* out2;
+    void* out2_lo;
+    int32_t out2_ld, n_split;
 } avl_seg_op;
 
 #define AVL_IN_U8_HWC 0

@@ -59,7 +59,8 @@ def main():
     ends = {}
     for i, n in enumerate(net.op_names):
         for key in ref:
-            if n == key or n in (key + ".conv3", key + ".conv3+downsample"):
+            # (fuse_passes: the max-pool's output is the pooled stem's)
+            if n == key or n in (key + ".conv3", key + ".conv3+downsample") or (key, n) == ("backbone.maxpool", "backbone.conv1+maxpool"):
                 ends[key] = i
         if n.startswith("decoder.refine_layers.") and net.ops[i].out_f32:
             ends["logits"] = i

@@ -791,7 +791,16 @@ int validate_conv_op(const avl_seg_op& op) {
                 return set_error(AVL_E_UNSUPPORTED, "a pre-processing stem (in2 = camera block) takes one raw frame unless raw_batch = 1: batch %d",
                                  op.batch);
             AVL_REQUIRE(op.weight && op.bias && op.out_c == 64 && op.in_c == 3, "stem expects 3 -> 64 channels");
-            AVL_REQUIRE(op.out_h == (op.in_h + 6 - 7) / 2 + 1 && op.out_w == (op.in_w + 6 - 7) / 2 + 1, "stem output size");
+            if (op.stride == 4) {      // the max-pool (3x3 s2 p1) in the MFMA stem's epilogue: out is the pooled map
+                const int ch = (op.in_h + 6 - 7) / 2 + 1, cw = (op.in_w + 6 - 7) / 2 + 1;
+                AVL_REQUIRE(is_half(op.dtype) && op.w_layout == 1, "a pooled stem (stride 4) is the MFMA kernel (16-bit, w_layout 1): dtype %d, w_layout %d",
+                            op.dtype, op.w_layout);
+                AVL_REQUIRE(!op.w_split && !op.out_lo, "a pooled stem (stride 4) writes one plane: w_split %d with%s out_lo", op.w_split, op.out_lo ? "" : "out");
+                AVL_REQUIRE(op.out_h == (ch + 2 - 3) / 2 + 1 && op.out_w == (cw + 2 - 3) / 2 + 1, "pooled stem output size %d x %d (conv %d x %d)",
+                            op.out_h, op.out_w, ch, cw);
+                AVL_REQUIRE(reinterpret_cast<uintptr_t>(op.out) % 16 == 0, "pooled stem: unaligned output");
+            } else
+                AVL_REQUIRE(op.out_h == (op.in_h + 6 - 7) / 2 + 1 && op.out_w == (op.in_w + 6 - 7) / 2 + 1, "stem output size");
             AVL_REQUIRE(op.out_rows >= out_pix && op.out_ld >= 64 && (op.out_ld * es) % 16 == 0, "stem output buffer");
             AVL_REQUIRE(op.w_layout == 0 || (op.w_layout == 1 && is_half(op.dtype)), "stem weight layout %d", op.w_layout);
             if (op.in2) {      // pre-processing in the loader: `in` is the raw BGR frame [src_h][in2_ld][3] (raw_batch: [batch] of them), in2 the camera block(s)

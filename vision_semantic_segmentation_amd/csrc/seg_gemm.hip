@@ -51,6 +51,19 @@ struct GemmArgs {
     // kernel argument in SGPRs.)
 };
 
+// What k_gemm_ring<..., EXT = true> takes beside GemmArgs (not fields of GemmArgs: MxArgs embeds that struct, and the MX kernels keep
+// their argument layout).  Both parts are optional at run time.
+struct RingExt {
+    // pixel map of the A rows (s = 0: none): row m of the product = pixel (oy * s, ox * s) of image m / ohw, (oy, ox) = its place in the
+    // ow-wide output image; w, hw = input image width and pixel count.  A stride-s 1x1 conv without the sub-sampled copy of its input.
+    int s, ow, ohw, w, hw;
+    // second destination (C2 = NULL: none): tiles whose first column is >= n_split write C2 (+ C2_lo) with row stride ldc2, column
+    // n_split landing at C2's first.  n_split is a multiple of BN, so a tile has one destination.
+    int n_split, ldc2;
+    void* C2;
+    void* C2_lo;
+};
+
 // which sub-steps of a K block bring a NEW activation tile (the others reuse the tile already in LDS)
 template <int NSUB> __device__ __forceinline__ bool sub_needs_a(int j) { return NSUB == 1 || j == 0 || (NSUB == 3 && j == 2); }
 
@@ -272,8 +285,10 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm(GemmArgs p) {
 // STAGES = weight tiles in the ring (the producer runs STAGES - 1 sub-steps ahead); AST = activation tiles in the ring:
 // = STAGES for the plain GEMM; 2 is enough for NSUB = 2 at any depth because an activation tile lives for two sub-steps
 // (256 x 256 tile: 2 x 32 KB + 3 x 32 KB = the whole 160 KB of LDS, two sub-steps of DMA in flight instead of one).
-template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES>
-__global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtiles) {
+// EXT: the loader may read its rows through a pixel map and the epilogue may write a second destination (RingExt); the plain
+// instantiations (EXT = false) never look at `x`.
+template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES, bool EXT = false>
+__global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtiles, RingExt x) {
     typedef typename Half16<H>::v8 v8;
     constexpr int NW = WM * WN, BM = WM * MI * 16, BN = WN * 64;
     constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128;
@@ -306,7 +321,14 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
 #pragma unroll
         for (int i = 0; i < A_INSTR; ++i) {
             const int r = (i * NW + wave) * 8 + srow;
-            a_src[i] = static_cast<const char*>(p.A) + (long long)(mt * BM + r) * p.lda * 2 + ((schunk ^ (r & 7)) << 4);
+            long long row = mt * BM + r;
+            if constexpr (EXT) {
+                if (x.s) {         // (rows at or past M, which the last tile reads and never stores, take row M - 1's pixel: inside the image)
+                    const int m = min(mt * BM + r, p.M - 1), img = m / x.ohw, rem = m - img * x.ohw, oy = rem / x.ow, ox = rem - oy * x.ow;
+                    row = (long long)img * x.hw + (long long)(oy * x.s) * x.w + ox * x.s;
+                }
+            }
+            a_src[i] = static_cast<const char*>(p.A) + row * p.lda * 2 + ((schunk ^ (r & 7)) << 4);
         }
 #pragma unroll
         for (int i = 0; i < W_INSTR; ++i) {
@@ -448,7 +470,19 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
         const int nbase = nt * BN + wn * 64 + kq * 16;
         const bool ncol_ok = nbase + 16 <= p.N;
         constexpr int EB = IO ? 2 : 4;              // sub-tiles per epilogue batch (residual registers: 8 (16 split) per sub-tile)
-        const bool rsplit = IO && p.R_lo != nullptr, csplit = IO && p.C_lo != nullptr;
+        // the tile's destination (wave-uniform): C2 takes the tiles from column n_split on
+        H* c_hi = static_cast<H*>(p.C);
+        H* c_lo = static_cast<H*>(p.C_lo);
+        int ldc = p.ldc, cbase = nbase;
+        if constexpr (EXT) {
+            if (x.C2 != nullptr && nt * BN >= x.n_split) {
+                c_hi = static_cast<H*>(x.C2);
+                c_lo = static_cast<H*>(x.C2_lo);
+                ldc = x.ldc2;
+                cbase = nbase - x.n_split;
+            }
+        }
+        const bool rsplit = IO && p.R_lo != nullptr, csplit = IO && c_lo != nullptr;
 #pragma unroll
         for (int b0 = 0; b0 < MI; b0 += EB) {
             v8 res[EB][2], resl[IO ? EB : 1][2];
@@ -501,7 +535,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
 #pragma unroll
                         for (int i = 0; i < 16; ++i) v[i] = fmaxf(v[i], 0.f);
                     }
-                    H* cp = static_cast<H*>(p.C) + (long long)m * p.ldc + nbase;
+                    H* cp = c_hi + (long long)m * ldc + cbase;
                     float lo[8], hi[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) { lo[i] = v[i]; hi[i] = v[8 + i]; }
@@ -511,7 +545,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
                         if (csplit) {              // low plane: what the rounding to the 16-bit type dropped
 #pragma unroll
                             for (int i = 0; i < 8; ++i) { lo[i] = v[i] - (float)(H)v[i]; hi[i] = v[8 + i] - (float)(H)v[8 + i]; }
-                            H* cl = static_cast<H*>(p.C_lo) + (long long)m * p.ldc + nbase;
+                            H* cl = c_lo + (long long)m * ldc + cbase;
                             Vec8<H>::store(cl, lo);
                             Vec8<H>::store(cl + 8, hi);
                         }
@@ -523,21 +557,28 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
     }
 }
 
-template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES>
-int launch_ring(const GemmArgs& a0, int M, hipStream_t s) {
+template <typename H, int WM, int WN, int MI, int STAGES, int NSUB, int IO, int AST, bool EXT>
+int launch_ring_t(const GemmArgs& a0, int M, hipStream_t s, const RingExt& x) {
     constexpr int BM = WM * MI * 16, BN = WN * 64, LDS = (AST * BM + STAGES * BN) * 128;
     static_assert(LDS <= 160 * 1024, "ring does not fit LDS");
     // set on every launch: the attribute is per device and this may be called from several threads / for several devices
-    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST>),
+    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     GemmArgs a = a0;
     a.ntiles = (a.N + BN - 1) / BN;
     const int mtiles = (M + BM - 1) / BM;
     const int total = mtiles * a.ntiles;
     const int grid = total < 256 ? total : 256;
-    hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles);
+    hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles, x);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
+}
+
+// x = NULL: the plain kernel; else the EXT instantiation of the same tile configuration
+template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES>
+int launch_ring(const GemmArgs& a, int M, hipStream_t s, const RingExt* x = nullptr) {
+    if (x) return launch_ring_t<H, WM, WN, MI, STAGES, NSUB, IO, AST, true>(a, M, s, *x);
+    return launch_ring_t<H, WM, WN, MI, STAGES, NSUB, IO, AST, false>(a, M, s, RingExt{});
 }
 
 template <typename T, int WM, int WN>
@@ -1285,6 +1326,20 @@ inline TileCfg pick_tile(const avl_seg_op& op) {
     if (op.out_c <= 64) return {256, 64};
     return {128, 128};
 }
+// The ring GEMM's tile configuration for a ring_eligible op (the values of w_layout: 2 = 256 x 128, 3 = 256 x 256, 4 = 256 x 128 on four
+// waves).  256 x 256 halves the L2->LDS bytes per flop (the measured limiter) but needs >= ~200 tiles to fill 256 CUs; it is counted on
+// ONE image's rows, so that a batch runs the kernel its batch-1 plan runs.
+// (network.py _emit_conv1_with_low_level mirrors this choice to pick an n_split the op can run with: change both together;
+// tests/test_fused_passes_cpu.py creates the merged op of several plans, so a mismatch fails there.)
+inline int ring_variant(const avl_seg_op& op) {
+    const bool can256 = op.out_c % 256 == 0 && op.w_rows % 256 == 0;
+    const int m_image = op.out_h * op.out_w;
+    int v = op.w_layout;
+    if (v == 0) v = (can256 && ((m_image + 255) / 256) * (op.out_c / 256) >= 192) ? 3 : 2;
+    if (v == 3 && !can256) v = 2;
+    return v;
+}
+inline bool ring_ext(const avl_seg_op& op) { return op.stride > 1 || op.out2 != nullptr || op.out2_lo != nullptr || op.n_split != 0; }
 
 }  // namespace
 
@@ -1319,6 +1374,8 @@ int validate_gemm(const avl_seg_op& op) {
     AVL_REQUIRE(op.w_layout == 0 || is_half(op.dtype), "GEMM w_layout %d forces a tile configuration of the 16-bit kernels: dtype %d", op.w_layout, op.dtype);
     if (op.bias_per_image && op_batch(op) > 1) {
         AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: a per-image bias is not supported by the MX GEMM");
+        // (gemm_image_op moves neither out2 nor a strided input to image n)
+        AVL_REQUIRE(!ring_ext(op), "GEMM: a per-image bias goes with neither strided input rows (stride %d) nor a second destination", op.stride);
         for (int n = 0; n < op.batch; ++n) {
             const avl_seg_op v = gemm_image_op(op, n);
             AVL_REQUIRE(v.in_rows >= (op.out_h * op.out_w + 255) / 256 * 256,
@@ -1330,10 +1387,35 @@ int validate_gemm(const avl_seg_op& op) {
     }
     const int M = op.out_h * op.out_w * op_batch(op), K = op.in_c, N = op.out_c;      // a batch is one long run of rows
     AVL_REQUIRE(M > 0 && N > 0 && K > 0, "GEMM M/N/K = %d/%d/%d", M, N, K);
-    AVL_REQUIRE(op.in_h * op.in_w == op.out_h * op.out_w, "GEMM in/out pixel counts differ (%d vs %d)", op.in_h * op.in_w, op.out_h * op.out_w);
+    if (ring_ext(op)) {     // strided input rows / a second destination: the ring GEMM of the 16-bit types only
+        AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: the MX GEMM takes neither strided input rows (stride %d) nor a second destination", op.stride);
+        AVL_REQUIRE(is_half(op.dtype) && !op.out_f32, "GEMM: strided input rows (stride %d) / a second destination need a 16-bit GEMM (dtype %d, out_f32 %d)",
+                    op.stride, op.dtype, op.out_f32);
+        AVL_REQUIRE(ring_eligible(op) && op.w_layout != 4, "GEMM: strided input rows (stride %d) / a second destination need the ring GEMM "
+                    "(N %% 128 == 0, N > 64, rows padded to 256, w_layout 0, 2 or 3): N %d, in_rows %d, w_layout %d", op.stride, N, op.in_rows, op.w_layout);
+    }
+    if (op.stride > 1) {
+        AVL_REQUIRE(op.out_h == (op.in_h - 1) / op.stride + 1 && op.out_w == (op.in_w - 1) / op.stride + 1,
+                    "GEMM stride %d: output %d x %d is not the sub-sampled %d x %d input", op.stride, op.out_h, op.out_w, op.in_h, op.in_w);
+        AVL_REQUIRE((long long)op.in_rows >= (long long)op.in_h * op.in_w * op_batch(op), "GEMM stride %d reads %lld rows, input has %d allocated",
+                    op.stride, (long long)op.in_h * op.in_w * op_batch(op), op.in_rows);
+    } else
+        AVL_REQUIRE(op.in_h * op.in_w == op.out_h * op.out_w, "GEMM in/out pixel counts differ (%d vs %d)", op.in_h * op.in_w, op.out_h * op.out_w);
     AVL_REQUIRE((K * es) % 128 == 0, "GEMM K = %d is not a multiple of %d", K, 128 / es);
     AVL_REQUIRE(op.in_ld >= K && (op.in_ld * es) % 16 == 0, "GEMM in_ld %d", op.in_ld);
-    AVL_REQUIRE(op.out_ld >= N, "GEMM out_ld %d < N %d", op.out_ld, N);
+    int n1 = N;             // columns that go to `out`
+    if (op.out2 || op.out2_lo || op.n_split) {
+        const int bn = ring_variant(op) == 3 ? 256 : 128;
+        AVL_REQUIRE(op.out2, "GEMM: n_split %d / out2_lo without a second destination (out2 is NULL)", op.n_split);
+        AVL_REQUIRE(op.n_split > 0 && op.n_split < N && op.n_split % bn == 0,
+                    "GEMM: n_split %d must be a multiple of the N tile (%d) inside (0, N = %d)", op.n_split, bn, N);
+        AVL_REQUIRE(!op.in2, "GEMM: a second destination takes no residual");
+        AVL_REQUIRE(op.out2_ld >= N - op.n_split && (op.out2_ld * es) % 16 == 0, "GEMM out2_ld %d (second destination of %d columns)", op.out2_ld, N - op.n_split);
+        AVL_REQUIRE(!op.out2_lo || (op.dtype == AVL_F16 && op.w_split == 1), "GEMM: out2_lo needs AVL_F16 activations and w_split = 1");
+        AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.out2) | reinterpret_cast<uintptr_t>(op.out2_lo)) % 16 == 0, "GEMM second destination must be 16-byte aligned");
+        n1 = op.n_split;
+    }
+    AVL_REQUIRE(op.out_ld >= n1, "GEMM out_ld %d < N %d", op.out_ld, n1);
     const TileCfg t = pick_tile(op);
     const int mtiles = (M + t.bm - 1) / t.bm, ntiles = (N + t.bn - 1) / t.bn;
     AVL_REQUIRE(op.in_rows >= mtiles * t.bm, "GEMM reads %d rows, input has %d allocated", mtiles * t.bm, op.in_rows);
@@ -1446,21 +1528,25 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
     // 2 = ring 256x128 x3 stages, 3 = ring 256x256 x2 stages, 4 = ring 256x128 (4 waves) x3 stages.
     // 256x256 halves the L2->LDS bytes per flop (the measured limiter) but needs >= ~200 tiles to fill 256 CUs.
     if (ring_eligible(op)) {
-        const bool can256 = a.N % 256 == 0 && op.w_rows % 256 == 0;
-        int v = op.w_layout;
-        if (v == 0) v = (can256 && ((m_image + 255) / 256) * (a.N / 256) >= 192) ? 3 : 2;
+        const int v = ring_variant(op);
+        // strided input rows and / or a second destination: the EXT instantiation of the same configuration (validate_gemm: not with v == 4)
+        RingExt ext;
+        memset(&ext, 0, sizeof(ext));
+        if (op.stride > 1) { ext.s = op.stride; ext.ow = op.out_w; ext.ohw = m_image; ext.w = op.in_w; ext.hw = op.in_h * op.in_w; }
+        if (op.out2) { ext.n_split = op.n_split; ext.ldc2 = op.out2_ld; ext.C2 = op.out2; ext.C2_lo = op.out2_lo; }
+        const RingExt* x = ring_ext(op) ? &ext : nullptr;
         if (a.nsub == 2) {
-            if (v == 3 && can256) return launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s);
-            return launch_ring<f16, 4, 2, 4, 3, 2, 1>(a, a.M, s);
+            if (v == 3) return launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s, x);
+            return launch_ring<f16, 4, 2, 4, 3, 2, 1>(a, a.M, s, x);
         }
         if (a.nsub == 3) {
-            if (v == 3 && can256) return launch_ring<f16, 2, 4, 8, 2, 3, 1>(a, a.M, s);
-            return launch_ring<f16, 4, 2, 4, 3, 3, 1>(a, a.M, s);
+            if (v == 3) return launch_ring<f16, 2, 4, 8, 2, 3, 1>(a, a.M, s, x);
+            return launch_ring<f16, 4, 2, 4, 3, 3, 1>(a, a.M, s, x);
         }
         const bool bf = op.dtype == AVL_BF16;
-        if (v == 3 && can256) return bf ? launch_ring<bf16, 2, 4, 8, 2>(a, a.M, s) : launch_ring<f16, 2, 4, 8, 2>(a, a.M, s);
-        if (v == 4) return bf ? launch_ring<bf16, 2, 2, 8, 3>(a, a.M, s) : launch_ring<f16, 2, 2, 8, 3>(a, a.M, s);
-        return bf ? launch_ring<bf16, 4, 2, 4, 3>(a, a.M, s) : launch_ring<f16, 4, 2, 4, 3>(a, a.M, s);
+        if (v == 3) return bf ? launch_ring<bf16, 2, 4, 8, 2>(a, a.M, s, x) : launch_ring<f16, 2, 4, 8, 2>(a, a.M, s, x);
+        if (v == 4) return bf ? launch_ring_t<bf16, 2, 2, 8, 3, 1, 0, 3, false>(a, a.M, s, ext) : launch_ring_t<f16, 2, 2, 8, 3, 1, 0, 3, false>(a, a.M, s, ext);
+        return bf ? launch_ring<bf16, 4, 2, 4, 3>(a, a.M, s, x) : launch_ring<f16, 4, 2, 4, 3>(a, a.M, s, x);
     }
     if (op.dtype == AVL_BF16) {
         if (t.bn == 64) return launch_cfg<bf16, 4, 1>(a, mtiles, s);

@@ -63,7 +63,8 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
     bytes = in_pix * op.in_c * e_in + out_pix * op.out_c * e_out;
     switch (op.kind) {
         case AVL_OP_STEM:
-            flops = 2.0 * out_pix * 64 * 147;
+            // (stride 4, the pooled stem: the conv's flops at ITS output size; the bytes are the pooled map's, which is all it writes)
+            flops = 2.0 * (op.stride == 4 ? nb * ((op.in_h - 1) / 2 + 1) * ((op.in_w - 1) / 2 + 1) : out_pix) * 64 * 147;
             // in2: the raw camera frames are what is read (in_rows counts every frame of a raw batch); AVL_IN_F32_CHW: three fp32 values per pixel instead of three bytes
             bytes = (op.in2 ? (double)op.in_rows : in_pix) * (op.in_format == AVL_IN_F32_CHW ? 12 : 3) + out_pix * 64 * es;
             break;
@@ -75,6 +76,10 @@ void work(const avl_seg_op& op, double& flops, double& bytes) {
                 const double e_res = act_bytes(es, op.in2_lo != nullptr, (op.mx_flags & AVL_MX_RES_LO) != 0, false);
                 bytes += (double)op.out_c * k_all * e_w + (op.in2 ? out_pix * op.out_c * e_res : 0.0) + (op.in3 ? in_pix * op.in3_c * e_in : 0.0);
             }
+            // strided input rows: only the rows of the sub-sampled pixels are read
+            if (op.stride > 1) bytes -= (in_pix - out_pix) * op.in_c * e_in;
+            // a second destination: the input counts once, the columns from n_split on are written with the planes out2 has
+            if (op.out2) bytes += out_pix * (op.out_c - op.n_split) * (act_bytes(es, op.out2_lo != nullptr, false, false) - e_out);
             if (op.out_f32) {
                 bytes += out_pix * op.out_c * (4 - es);
                 if (op.out_mx) bytes += out_pix - out_pix * op.out_c * (0.5 + 1.0 / 32.0);       // out_mx = the uint8 label map of the fused arg-max, not an MX bundle
@@ -256,10 +261,22 @@ extern "C" int avl_seg_plan_nonfinite(avl_seg_plan* plan, void* stream, unsigned
         const long long rows = (op.kind == AVL_OP_GAP || op.kind == AVL_OP_GEMV) ? avl::op_batch(op) : (long long)op.out_h * op.out_w * avl::op_batch(op);
         const bool f32 = op.dtype == AVL_F32 || op.out_f32 || op.kind == AVL_OP_GAP || op.kind == AVL_OP_GEMV;
         if (f32) avl::count_plane<float>(op.out, rows, (op.kind == AVL_OP_DWPW && op.out_f32) ? op.in3_c : op.out_c, op.out_ld, dev + i, s);
-        else if (op.dtype == AVL_F16) {
-            avl::count_plane<avl::f16>(op.out, rows, op.out_c, op.out_ld, dev + i, s);
-            avl::count_plane<avl::f16>(op.out_lo, rows, op.out_c, op.out_ld, dev + i, s);
-        } else avl::count_plane<avl::bf16>(op.out, rows, op.out_c, op.out_ld, dev + i, s);
+        else {
+            // (a GEMM with a second destination: columns [0, n_split) in out, the rest in out2)
+            const bool two = op.kind == AVL_OP_GEMM && op.out2 != nullptr;
+            const int c1 = two ? op.n_split : op.out_c, c2 = op.out_c - c1;
+            if (op.dtype == AVL_F16) {
+                avl::count_plane<avl::f16>(op.out, rows, c1, op.out_ld, dev + i, s);
+                avl::count_plane<avl::f16>(op.out_lo, rows, c1, op.out_ld, dev + i, s);
+                if (two) {
+                    avl::count_plane<avl::f16>(op.out2, rows, c2, op.out2_ld, dev + i, s);
+                    avl::count_plane<avl::f16>(op.out2_lo, rows, c2, op.out2_ld, dev + i, s);
+                }
+            } else {
+                avl::count_plane<avl::bf16>(op.out, rows, c1, op.out_ld, dev + i, s);
+                if (two) avl::count_plane<avl::bf16>(op.out2, rows, c2, op.out2_ld, dev + i, s);
+            }
+        }
         e = hipGetLastError();
     }
     if (rc == AVL_OK && e == hipSuccess) e = hipMemcpyAsync(counts_host, dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);

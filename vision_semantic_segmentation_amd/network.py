@@ -50,6 +50,7 @@ class AvlSegOp(C.Structure):
         ("batch", C.c_int32), ("bias_per_image", C.c_int32),
         ("in_format", C.c_int32),
         ("raw_batch", C.c_int32),
+        ("out2", C.c_void_p), ("out2_lo", C.c_void_p), ("out2_ld", C.c_int32), ("n_split", C.c_int32),
     ]
 
 
@@ -611,7 +612,7 @@ class SegNet(object):
     native plan.  ``forward(image_u8_cuda)`` runs it; ``labels`` / ``logits`` are views of its outputs."""
 
     ROW_PAD = 256        # GEMM tiles read whole 128/256-row tiles
-    MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier")    # keyword switches of the "mixed" mode
+    MIXED_OPTS = ("conv1_split", "conv2_split", "mx", "trunk_fp4", "fuse_ds", "gconv_mx", "dw_exact", "layer1_lo", "fuse_block", "full_split", "fuse_decoder", "fuse_classifier", "fuse_passes")    # keyword switches of the "mixed" mode (fuse_passes: of every 16-bit precision)
 
     def __init__(self, state, height, width, precision="bf16", device=None, num_classes=19, output_stride=8, fuse_dwpw=True, raw_frame=None,
                  part=None, backbone=DEFAULT_BACKBONE, batch=1, input_format="u8_hwc", raw_batch=False, **mixed_opts):
@@ -695,6 +696,15 @@ class SegNet(object):
             self.mixed_trunk_fp4 = False
             self.mixed_layer1_lo = True
             self.mixed_fuse_block = False        # (the fused layer1 block has no LDS for a t1 lo plane at 256 input channels)
+        # fuse_passes (default; every 16-bit precision, not full_split): passes that only move data ride in a neighbouring kernel -- the
+        # max-pool runs in the MFMA stem's epilogue (the stem's map is never written), a striding block's non-MX downsample 1x1 reads every
+        # s-th pixel itself (no sub-sample op, no compact copy), and decoder.low_level_conv runs in layer2.0.conv1's launch (two 1x1 convs
+        # of layer1's output: one op with two destinations, the input read from HBM once).  Every result keeps its bits.
+        # False builds the op list with the stand-alone ops.
+        self.fuse_passes = bool(mixed_opts.get("fuse_passes", True)) and precision != "f32" and not self.full_split
+        self._low_twin = None      # (layer1's output Act, its hw, its channels) while layer2's first block is emitted
+        self._cat2 = None          # the decoder's concat buffer, once the merged op has written its low-level columns
+        self.activation_bytes = 0  # bytes of all activation buffers the plan allocated (they are pooled, never freed: its peak)
         self.mixed_gconv_mx = mixed_opts.get("gconv_mx", True) and not self.full_split   # grouped conv with FP4 corrections for its weights AND for conv1's output (-10..-30 % logits error, -5 % frames/s)
         self.act_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "mixed": torch.float16}[precision]
         self.avl_dtype = {"bf16": _lib.AVL_BF16, "f16": _lib.AVL_F16, "f32": _lib.AVL_F32, "mixed": _lib.AVL_F16}[precision]
@@ -765,9 +775,11 @@ class SegNet(object):
             t = torch.zeros((prow, ch), dtype=self.act_dtype, device=self.device)
             a = Act(t, None, key)
         self._keep.append(t)
+        self.activation_bytes += t.numel() * t.element_size()
         if mx:
             a.mx = torch.zeros(2 * mx_bundle_bytes(prow, ch), dtype=torch.uint8, device=self.device)
             self._keep.append(a.mx)
+            self.activation_bytes += a.mx.numel()
         a.lo_fp4 = lo_fp4
         return a
 
@@ -817,10 +829,13 @@ class SegNet(object):
         return dict(mx_flags=flags)
 
     def _gemm(self, name, src, hw, cin, w, b, dst, dst_col=0, relu=True, res=None, out_f32=False, bias_dev=None,
-              read_lo=True, src2=None, w2=None, b2=None, labels=None, bias_per_image=False):
+              read_lo=True, src2=None, w2=None, b2=None, labels=None, bias_per_image=False, in_hw=None, stride=1, dst2=None, n_split=0):
         """1x1 conv.  w float64 [cout][cin] (BN folded), b float64 [cout].  "mixed": weights become f16 pairs; the low
-        plane of `src` is read if it has one (unless read_lo = False), `res` and `dst` are used with all the planes they have."""
+        plane of `src` is read if it has one (unless read_lo = False), `res` and `dst` are used with all the planes they have.
+        stride = s > 1 (ring GEMM): `src` is the un-sampled in_hw image and the GEMM reads every s-th pixel of every s-th row; hw is the output's.
+        dst2 (ring GEMM): w / b hold two convs' rows, the columns from n_split on go to dst2 (from its column 0)."""
         h, wd = hw
+        ih, iw = hw if in_hw is None else in_hw
         cout = w.shape[0]
         w_rows = _round_up(cout, 256)
         wp = _zero_pad(w.reshape(cout, cin), w_rows)
@@ -842,14 +857,20 @@ class SegNet(object):
             bias_dev = self._dev(_zero_pad(b, w_rows), torch.float32)
         ip, ild, irows = self._view(src)
         op_, old, orows = self._view(dst, dst_col)
-        f = dict(in_=ip, out=op_, weight=wdev.data_ptr(), bias=bias_dev.data_ptr(), in_h=h, in_w=wd, in_c=cin, in_ld=ild,
+        f = dict(in_=ip, out=op_, weight=wdev.data_ptr(), bias=bias_dev.data_ptr(), in_h=ih, in_w=iw, in_c=cin, in_ld=ild,
                  in_rows=irows, out_h=h, out_w=wd, out_c=cout, out_ld=old, out_rows=orows, relu=int(relu), out_f32=int(out_f32),
-                 w_rows=w_rows, ksize=1, stride=1, dil=1, groups=1)
+                 w_rows=w_rows, ksize=1, stride=stride, dil=1, groups=1)
+        assert (stride == 1 and dst2 is None) or (not use_mx and not out_f32 and self.half), "%s: strided rows / a second destination need the ring GEMM" % name
+        if dst2 is not None:
+            o2, old2, orows2 = self._view(dst2)
+            f.update(out2=o2, out2_ld=old2, n_split=n_split, out_rows=min(orows, orows2))
         if res is not None:
             rp, rld, _ = self._view(res)
             f.update(in2=rp, in2_ld=rld)
         if self.mixed:
             f.update(w_split=1, in_lo=in_lo, out_lo=self._lo(dst, dst_col), in2_lo=self._lo(res))
+            if dst2 is not None:
+                f.update(out2_lo=self._lo(dst2))
         if use_mx:
             flags = AVL_MX_IN_LO if (src.lo_fp4 and read_lo) else 0
             f.update(w_split=2, w_mx=w_mx.data_ptr(), in_mx=src.mx.data_ptr())
@@ -861,7 +882,7 @@ class SegNet(object):
                 flags |= AVL_MX_RES_LO
             f.update(self._writes_mx(dst, cout, dst_col, flags))
         else:
-            for t_, what in ((src if read_lo else None, "input"), (res, "residual"), (dst, "output")):
+            for t_, what in ((src if read_lo else None, "input"), (res, "residual"), (dst, "output"), (dst2, "second output")):
                 if isinstance(t_, Act) and t_.lo_fp4:
                     raise RuntimeError("%s: the %s keeps its lo part as FP4 only, which needs the MX GEMM" % (name, what))
         if labels is not None:
@@ -967,8 +988,11 @@ class SegNet(object):
                 # layer1_lo = False: of layer1's blocks only the last keeps the lo plane of its output
                 trunk_lo = self.mixed_layer1_lo or li != 1 or bi == nblocks - 1
                 blk = Block(p, hw, ohw, cin, width, planes * EXPANSION, s, d, (p + ".downsample.0.weight") in st, trunk_lo)
+                # layer2's first block may carry decoder.low_level_conv in its conv1's launch (_emit_block_unfused)
+                self._low_twin = (low, low_hw, low_c) if (li == 2 and bi == 0 and self.fuse_passes) else None
                 y = self._emit_block(st, blk, x)
-                if x is not low:              # layer1's output stays alive for the decoder
+                self._low_twin = None
+                if x is not low or self._cat2 is not None:      # layer1's output stays alive for the decoder, unless its conv has run already
                     self._release(x)
                 x, hw, cin = y, ohw, blk.cout
             if li == 1:
@@ -1000,13 +1024,21 @@ class SegNet(object):
         else:
             w_stem, stem_layout = self._dev(w.permute(2, 3, 1, 0).reshape(-1), torch.float32), 0   # [ky][kx][ci][co]
         b_stem = self._dev(b, torch.float32)
-        stem = self._act(h2 * w2, 64, split=self.full_split)
+        h4, w4 = (h2 + 2 - 3) // 2 + 1, (w2 + 2 - 3) // 2 + 1
         raw = {} if self.raw_frame is None else dict(in2=self.camera_block.data_ptr(), in2_ld=self.raw_frame[1], raw_batch=int(self.raw_batch))
+        if self.fuse_passes and stem_layout == 1:
+            # the max-pool in the MFMA stem's epilogue (stride 4 = the conv's 2 x the pool's 2): the conv map is never written
+            x = self._act(h4 * w4, 64)
+            self._op("backbone.conv1+maxpool", OP_STEM, in_=self.image.data_ptr(), out=x.hi.data_ptr(), weight=w_stem.data_ptr(),
+                     bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.numel() // 3, out_h=h4, out_w=w4,
+                     out_c=64, out_ld=64, out_rows=x.shape[0], ksize=7, stride=4, pad=3, dil=1, groups=1, relu=1, w_layout=stem_layout,
+                     in_format=INPUT_FORMATS[self.input_format], **raw)
+            return x, (h4, w4)
+        stem = self._act(h2 * w2, 64, split=self.full_split)
         self._op("backbone.conv1", OP_STEM, in_=self.image.data_ptr(), out=stem.hi.data_ptr(), weight=w_stem.data_ptr(),
                  bias=b_stem.data_ptr(), in_h=H, in_w=W, in_c=3, in_ld=3, in_rows=self.image.numel() // 3, out_h=h2, out_w=w2,
                  out_c=64, out_ld=64, out_rows=stem.shape[0], ksize=7, stride=2, pad=3, dil=1, groups=1, relu=1, w_layout=stem_layout,
                  w_split=int(self.full_split), out_lo=self._lo(stem), in_format=INPUT_FORMATS[self.input_format], **raw)
-        h4, w4 = (h2 + 2 - 3) // 2 + 1, (w2 + 2 - 3) // 2 + 1
         x = self._act(h4 * w4, 64, split=self.full_split)
         self._spatial("backbone.maxpool", OP_MAXPOOL, stem, (h2, w2), 64, x, (h4, w4), 64, ksize=3, stride=2, pad=1, dil=1,
                       in_lo=self._lo(stem), out_lo=self._lo(x))
@@ -1050,7 +1082,8 @@ class SegNet(object):
         # then corrects for the rounding of conv1's output too -- the largest single error term otherwise
         conv1_mx = self.mixed_gconv_mx and not dense and self._mx_gemm(x, cin, t1_c)
         t1 = self._act(hw[0] * hw[1], t1_c, split=self.full_split, mx=conv1_mx, lo_fp4=conv1_mx)
-        self._gemm(p + ".conv1", x, hw, cin, _zero_pad(w, t1_c), _zero_pad(b, t1_c), t1, read_lo=self.mixed_conv1_split)
+        if not self._emit_conv1_with_low_level(st, blk, x, t1, _zero_pad(w, t1_c), _zero_pad(b, t1_c)):
+            self._gemm(p + ".conv1", x, hw, cin, _zero_pad(w, t1_c), _zero_pad(b, t1_c), t1, read_lo=self.mixed_conv1_split)
         # conv2 3x3 grouped + bn2 + relu
         wg, bg, conv2 = self._conv2_weights(st, blk, t1, dense)
         # (conv3 as an MX GEMM reads the 3x3 output's lo part only through its FP4 copy: no f16 lo plane then)
@@ -1087,6 +1120,39 @@ class SegNet(object):
         if idn is not x and idn is not None:
             self._release(idn)
         return y
+
+    def _low_level_conv(self, st):
+        """decoder.low_level_conv (BN folded) -> (w, b, its output channels padded to the kernels' granule)"""
+        w, b = fold_bn(st, "decoder.low_level_conv.conv.weight", "decoder.low_level_conv.bn")
+        # MODEL.DECODER.LOW_LEVEL_OUT_CHANNELS other than the reference's 256 (48 in the DeepLabV3+ paper): the low-level branch is padded with
+        # zero channels to the kernels' granule (zero rows of this conv, zero depthwise taps and zero pointwise columns in the first refine
+        # block): ReLU(0) = 0 contributes exactly nothing
+        low_out = _round_up(w.shape[0], 128 if self.mixed else 64)
+        return _zero_pad(w, low_out), _zero_pad(b, low_out), low_out
+
+    def _emit_conv1_with_low_level(self, st, blk, x, t1, w1, b1):
+        """layer2's first conv1 and decoder.low_level_conv are 1x1 convs of the same tensor, layer1's output.  Where both are non-MX ring
+        GEMMs with the same passes and ReLU they run as ONE op with two destinations (the decoder's concat buffer, allocated here, and t1):
+        the second N half of a row tile finds the input in L2.  -> True when emitted; False: two ops as before."""
+        if self._low_twin is None or self._low_twin[0] is not x:
+            return False
+        low_hw, low_c = self._low_twin[1:]
+        wl, bl, low_out = self._low_level_conv(st)
+        t1_c = w1.shape[0]
+        n = low_out + t1_c
+        # the N tile the library runs the merged op with: n_split must be a multiple of it.  This MIRRORS ring_variant() of seg_gemm.hip (256 x 256
+        # tiles where N % 256 == 0 and one image gives >= 192 of them, else 256 x 128) -- change both together; a mismatch makes
+        # avl_seg_plan_create refuse the op with an n_split message (tests/test_fused_passes_cpu.py builds these plans)
+        bn = 256 if (n % 256 == 0 and ((low_hw[0] * low_hw[1] + 255) // 256) * (n // 256) >= 192) else 128
+        same_passes = not self.mixed or x.lo is None or self.mixed_conv1_split       # low_level_conv reads the lo plane whenever there is one
+        if not (low_hw == blk.hw and low_c == blk.cin and same_passes and low_out % bn == 0 and t1_c % 128 == 0 and x.hi.shape[1] == low_c
+                and not self._mx_gemm(x, low_c, t1_c) and not self._mx_gemm(x, low_c, low_out) and t1.lo is None and not t1.lo_fp4):
+            return False
+        aspp_out = st["aspp.conv.conv.weight"].shape[0]
+        self._cat2 = self._act(low_hw[0] * low_hw[1], aspp_out + low_out, split=self.mixed)
+        self._gemm(blk.p + ".conv1+decoder.low_level_conv", x, low_hw, low_c, torch.cat([wl.reshape(low_out, low_c), w1.reshape(t1_c, low_c)]),
+                   torch.cat([bl, b1]), self._cat2, dst_col=aspp_out, dst2=t1, n_split=low_out)
+        return True
 
     def _conv2_weights(self, st, blk, t1, dense):
         """conv2 (grouped 3x3 + bn2) of a three-launch block -> (packed weights, bias, the op's w_layout / w_split and MX fields):
@@ -1134,6 +1200,12 @@ class SegNet(object):
             return None
         w, b = fold_bn(st, p + ".downsample.0.weight", p + ".downsample.1")
         src = x
+        idn_split = self.mixed and blk.trunk_lo
+        if blk.s != 1 and self.fuse_passes and self.half and not self._mx_gemm(x, cin, cout) and cout % 128 == 0 and x.hi.shape[1] == cin:
+            # the non-MX ring GEMM reads every s-th pixel of every s-th row itself: no sub-sample op, no compact copy
+            idn = self._act(ohw[0] * ohw[1], cout, split=idn_split)
+            self._gemm(p + ".downsample", x, ohw, cin, w, b, idn, relu=False, read_lo=self.mixed_conv1_split, in_hw=blk.hw, stride=blk.s)
+            return idn
         if blk.s != 1:
             keep_lo = self.mixed_conv1_split and x.lo is not None
             src = self._act(ohw[0] * ohw[1], cin, split=keep_lo)
@@ -1243,16 +1315,16 @@ class SegNet(object):
 
     def _emit_decoder(self, st, aspp, fhw, aspp_out, low, low_hw, low_c):
         """decoder (decoder.py:45-51) -> logits_buf / labels_buf"""
-        w, b = fold_bn(st, "decoder.low_level_conv.conv.weight", "decoder.low_level_conv.bn")
-        # MODEL.DECODER.LOW_LEVEL_OUT_CHANNELS other than the reference's 256 (48 in the DeepLabV3+ paper): the low-level branch is padded with
-        # zero channels to the kernels' granule (zero rows of this conv, zero depthwise taps and zero pointwise columns in the first refine
-        # block): ReLU(0) = 0 contributes exactly nothing
-        low_out = _round_up(w.shape[0], 128 if self.mixed else 64)
-        cat2 = self._act(low_hw[0] * low_hw[1], aspp_out + low_out, split=self.mixed)
-        self._gemm("decoder.low_level_conv", low, low_hw, low_c, _zero_pad(w, low_out), _zero_pad(b, low_out), cat2, dst_col=aspp_out)
+        w, b, low_out = self._low_level_conv(st)
+        cat2 = self._cat2          # the low-level columns are there already when the conv ran in layer2.0.conv1's launch (and `low` is released)
+        merged = cat2 is not None
+        if not merged:
+            cat2 = self._act(low_hw[0] * low_hw[1], aspp_out + low_out, split=self.mixed)
+            self._gemm("decoder.low_level_conv", low, low_hw, low_c, w, b, cat2, dst_col=aspp_out)
         self._spatial("decoder.interpolate", OP_BILINEAR, aspp, fhw, aspp_out, cat2, low_hw, aspp_out, in_lo=self._lo(aspp), out_lo=self._lo(cat2))
         self._release(aspp)
-        self._release(low)
+        if not merged:
+            self._release(low)
         x, hw, cin = cat2, low_hw, aspp_out + low_out
         k = 0
         while ("decoder.refine_layers.%d.depthwise_cnn.conv.weight" % k) in st:
@@ -1399,7 +1471,8 @@ class SegNet(object):
         """float32 CPU tensor [out_h * out_w, out_c] of what op i wrote (hi + lo planes) -- valid right after a run of ops 0 .. i only (later ops
         recycle the buffers): diagnostics and tests (tools/layer_error_trace.py)."""
         op = self.ops[i]
-        rows, cols = op.out_h * op.out_w * self.batch, (op.in3_c if (op.kind == OP_DWPW and op.out_f32) else op.out_c)     # (the fused classifier writes in3_c logits per pixel)
+        # (the fused classifier writes in3_c logits per pixel; a GEMM with a second destination: the columns of its first one)
+        rows, cols = op.out_h * op.out_w * self.batch, (op.in3_c if (op.kind == OP_DWPW and op.out_f32) else (op.n_split if op.out2 else op.out_c))
         dt = torch.float32 if (op.out_f32 or op.dtype == _lib.AVL_F32) else self.act_dtype
 
         def plane(ptr):

@@ -119,3 +119,59 @@ def test_rounding_mutations_differ_only_where_they_should():
     assert X.round_toward_zero(v, "f16").tolist() == [2048.0, 2050.0, -2048.0, -2050.0, 2050.0]
     assert X.round_half_away(v, "f16").tolist() == [2050.0, 2052.0, -2050.0, -2052.0, 2050.0]
     assert v.to(torch.float16).tolist() == [2048.0, 2052.0, -2048.0, -2052.0, 2050.0]
+
+
+# ------------------------------------------------------------------------- the ring GEMM's EXT forms (tests/_ring_ext_operands.py)
+import _ring_ext_operands as R  # noqa: E402
+
+
+@pytest.mark.parametrize("c", R.SMALL_CASES + R.MULTI_TILE_CASES, ids=R.case_id)
+def test_ring_ext_operands(c):
+    """every case: the exactness bound, float32 product == float64 product, >= 20 % of the outputs round, ties in both directions,
+    non-zero lo planes (R.want asserts them); sentinels survive outside the written slices"""
+    g = R.geometry(c)
+    v, bufs = R.want(c, check64=True)
+    assert v.shape == (g["M"], c.N)
+    assert bool((bufs["out"][:, g["M"]:] == R.FILL).all()) and bool((bufs["out"][:, :, :R.COL] == R.FILL).all())
+    assert bool((bufs["out"][:, :, R.COL + g["n1"]:] == R.FILL).all()) and bool((bufs["out2"][:, g["M"]:] == R.FILL).all())
+    assert bool((bufs["out"][1] == R.FILL).all()) != bool(c.lo1) and bool((bufs["out2"][1] == R.FILL).all()) != bool(c.lo2)
+    assert bool((bufs["out2"][0] == R.FILL).all()) != bool(c.n_split)
+    a = R.device_input(c)
+    rows = R.row_map(c)
+    assert bool(torch.isfinite(a[:, rows, :R.K].float()).all()) and int(torch.isfinite(a.float()).sum()) == a.shape[0] * g["M"] * R.K
+
+
+def test_ring_ext_cases_reach_what_they_claim():
+    """all eight EXT instantiations among the small cases of each form; every multi-tile case has more tiles than the grid's cap"""
+    for cases in (R.SMALL_STRIDED, R.SMALL_TWIN, R.SMALL_BOTH):
+        assert {(c.mode, R.variant(c)) for c in cases} == set(R.INSTANTIATION)
+    assert {(c.mode, R.variant(c)) for c in R.MULTI_TILE_CASES} == set(R.INSTANTIATION)
+    for c in R.MULTI_TILE_CASES:
+        mt, nt = R.tiles(c)
+        assert mt in (86, 171) and mt * nt > 256 and R.geometry(c)["M"] % 256 != 0, R.case_id(c)
+        assert (256 % nt != 0) == (c.N != 512)
+        if c.s > 1:
+            assert (R.geometry(c)["M"] // c.B) % 256 != 0          # the image boundary falls inside a row tile
+    assert any(c.s == 3 and c.B == 2 and c.extra and c.ih % 3 and c.iw % 3 for c in R.SMALL_STRIDED)
+    assert any(c.n_split and c.s > 1 for c in R.MULTI_TILE_CASES)
+    assert any(R.tiles(c)[0] * R.tiles(c)[1] > 512 and c.n_split for c in R.MULTI_TILE_CASES)      # every workgroup walks two tiles
+
+
+@pytest.mark.parametrize("c", [R.SMALL_STRIDED[6], R.SMALL_STRIDED[8], R.SMALL_TWIN[6], R.SMALL_TWIN[9], R.SMALL_BOTH[6], R.SMALL_BOTH[7],
+                               R.SMALL_BOTH[0], R.MULTI_TILE_CASES[12]], ids=R.case_id)
+def test_ring_ext_mutations_are_caught(c):
+    """each deliberately wrong host evaluation differs from the expectation in at least one stored element"""
+    _, bufs = R.want(c)
+    assert R.same(R.stored(c, R.exact_v(c)), bufs)
+    n = 0
+    for mut in R.MUTATIONS:
+        if R.applicable(c, mut):
+            assert not R.same(R.mutated(c, mut), bufs), (R.case_id(c), mut)
+            n += 1
+    assert n >= 2
+
+
+def test_ring_ext_every_mutation_applies_somewhere():
+    cases = [R.SMALL_STRIDED[8], R.SMALL_TWIN[6], R.SMALL_BOTH[6]]
+    assert all(any(R.applicable(c, m) for c in cases) for m in R.MUTATIONS)
+    assert all(R.applicable(R.SMALL_BOTH[6], m) for m in R.MUTATIONS)

@@ -6,7 +6,10 @@ stand-alone ops it replaces, then the whole plan with the keyword on against off
   second destination  two 1x1 convs of one input in one launch; reference = the two single-destination GEMMs.
 
 Nothing is rounded differently: the same products are accumulated in the same order, so every comparison is torch.equal on whole
-buffers -- the fill pattern of rows and columns the op must not touch included."""
+buffers -- the fill pattern of rows and columns the op must not touch included.
+
+(tests/test_gpu_ring_ext_exact.py compares the same forms with a float64 host reference, at sizes where a workgroup walks several
+tiles.)  The whole-plan tests also compare the per-op non-finite counts, op by op, and the flops / bytes SegNet.profile() reports."""
 import ctypes as C
 
 import pytest
@@ -166,7 +169,30 @@ def test_twin_gemm_equals_two_gemms(case, cuda_device):
     assert bool((ref2[M:] == FILL).all())
 
 
-@pytest.mark.parametrize("case", [("mixed", 97, 131), ("mixed", 192, 256), ("f16", 97, 131)])
+MERGED, POOLED_STEM, DOWNSAMPLE = "backbone.layer2.0.conv1+decoder.low_level_conv", "backbone.conv1+maxpool", "backbone.layer2.0.downsample"
+# what each fused op replaces in the plan built with fuse_passes=False
+REPLACES = {MERGED: ("backbone.layer2.0.conv1", "decoder.low_level_conv"), POOLED_STEM: ("backbone.conv1", "backbone.maxpool"),
+            DOWNSAMPLE: (DOWNSAMPLE + ".sub", DOWNSAMPLE + ".sub[lo]", DOWNSAMPLE)}
+
+
+def _unfused_view(counts):
+    """per-op non-finite counts of an unfused plan under the fused plan's op names: a merged op's outputs are those of the two
+    ops it replaces; the pooled stem writes the max-pool's map only; the sub-sampled copies do not exist"""
+    d = dict(counts)
+    merged = d.pop("backbone.layer2.0.conv1", 0) + d.pop("decoder.low_level_conv", 0)
+    if merged:
+        d[MERGED] = merged
+    d.pop("backbone.conv1", None)
+    if d.get("backbone.maxpool"):
+        d[POOLED_STEM] = d["backbone.maxpool"]
+    d.pop("backbone.maxpool", None)
+    d.pop(DOWNSAMPLE + ".sub", None)
+    d.pop(DOWNSAMPLE + ".sub[lo]", None)
+    return d
+
+
+# ("mixed", 512, 516): layer1's output is 128 x 129 = 16 512 rows, so the merged op itself has 65 row tiles x 4 N tiles = 260 > 256
+@pytest.mark.parametrize("case", [("mixed", 97, 131), ("mixed", 192, 256), ("f16", 97, 131), ("bf16", 97, 131), ("mixed", 512, 516)])
 def test_whole_plan_is_unchanged_by_fuse_passes(case, cuda_device):
     import torch
     from vision_semantic_segmentation_amd.network import SegNet, random_state_dict
@@ -176,15 +202,71 @@ def test_whole_plan_is_unchanged_by_fuse_passes(case, cuda_device):
     outs = []
     for fuse in (True, False):
         net = SegNet(st, H, W, precision=precision, device=cuda_device, fuse_passes=fuse)
-        assert ("backbone.layer2.0.conv1+decoder.low_level_conv" in net.op_names) == fuse
+        assert (MERGED in net.op_names) == fuse
         assert ("backbone.layer2.0.downsample.sub" in net.op_names) != fuse
+        if (H, W) == (512, 516):
+            op = net.ops[net.op_names.index(MERGED if fuse else "backbone.layer2.0.conv1")]
+            assert op.out_h * op.out_w == 16512 and (not fuse or (op.out2 and (16512 + 255) // 256 * (op.out_c // 128) > 256))
         net.forward(img)
         torch.cuda.synchronize()
-        outs.append((net.logits.clone(), net.labels.clone(), sum(net.nonfinite_counts().values())))
+        outs.append((net.logits.clone(), net.labels.clone(), net.nonfinite_counts()))
     assert bool(torch.isfinite(outs[0][0]).all())
     assert torch.equal(outs[0][0], outs[1][0]), "%r: logits differ" % (case,)
     assert torch.equal(outs[0][1], outs[1][1]), "%r: labels differ" % (case,)
-    assert outs[0][2] == outs[1][2]
+    assert outs[0][2] == _unfused_view(outs[1][2]), (outs[0][2], outs[1][2])         # per-op counts, as dictionaries
+
+
+@pytest.mark.parametrize("precision", ["f16", "bf16"])
+def test_whole_plan_counts_an_overflow_in_the_same_ops(precision, cuda_device):
+    """the comparison above on counts that are NOT zero: a checkpoint whose folded BN bias is +Inf on one channel of
+    decoder.low_level_conv (the merged op's first destination) and one of layer2.0.conv1 (its second), both under a ReLU.  The
+    merged op counts one value per pixel and poisoned channel -- known from the operands -- and every op behind it counts what its
+    unfused twin counts."""
+    import torch
+    from vision_semantic_segmentation_amd.network import SegNet, random_state_dict
+    H, W = 97, 131
+    st = {k: v.clone() for k, v in random_state_dict(seed=0).items()}
+    st["decoder.low_level_conv.bn.bias"][5] = float("inf")
+    st["backbone.layer2.0.bn1.bias"][3] = float("inf")
+    img = torch.randint(0, 256, (H, W, 3), generator=torch.Generator().manual_seed(1), dtype=torch.uint8).to(cuda_device)
+    counts = {}
+    for fuse in (True, False):
+        net = SegNet(st, H, W, precision=precision, device=cuda_device, fuse_passes=fuse)
+        net.forward(img)
+        torch.cuda.synchronize()
+        counts[fuse] = net.nonfinite_counts()
+        if fuse:
+            op = net.ops[net.op_names.index(MERGED)]
+            assert op.out2 and counts[fuse][MERGED] == 2 * op.out_h * op.out_w
+    assert "decoder.low_level_conv" in counts[False] and "backbone.layer2.0.conv1" in counts[False] and len(counts[True]) > 3
+    assert counts[True] == _unfused_view(counts[False]), (counts[True], counts[False])
+
+
+@pytest.mark.parametrize("precision", ["mixed", "bf16"])
+def test_profile_accounts_the_same_work_with_and_without_fuse_passes(precision, cuda_device):
+    """avl_seg_plan_profile's flops and bytes (the benchmark's roofline reads them through SegNet.profile()): a fused op does the
+    flops of the ops it replaces and moves no more bytes than they do.  No timing is asserted."""
+    from vision_semantic_segmentation_amd.network import SegNet, random_state_dict
+    st = random_state_dict(seed=0)
+    prof = {}
+    for fuse in (True, False):
+        net = SegNet(st, 97, 131, precision=precision, device=cuda_device, fuse_passes=fuse)
+        rows = net.profile()
+        assert len({r["name"] for r in rows}) == len(rows)
+        prof[fuse] = {r["name"]: r for r in rows}
+    on, off = prof[True], prof[False]
+    assert sum(r["flops"] for r in on.values()) == sum(r["flops"] for r in off.values()) > 0
+    for name, parts in REPLACES.items():
+        assert name in on and all(p in off for p in parts if not p.endswith("[lo]")), name
+        old = [off[p] for p in parts if p in off]
+        assert on[name]["flops"] == sum(r["flops"] for r in old) > 0, name
+        assert 0 < on[name]["bytes"] <= sum(r["bytes"] for r in old), (name, on[name]["bytes"], [r["bytes"] for r in old])
+    assert on[MERGED]["flops"] == off["backbone.layer2.0.conv1"]["flops"] + off["decoder.low_level_conv"]["flops"]
+    assert on[DOWNSAMPLE]["flops"] == off[DOWNSAMPLE]["flops"]                    # the sub-sampled copies do no flops
+    assert on[POOLED_STEM]["flops"] == off["backbone.conv1"]["flops"]              # nor does the max-pool
+    for name in on:                                                               # every other op is the same op
+        if name not in REPLACES:
+            assert on[name]["flops"] == off[name]["flops"] and on[name]["bytes"] == off[name]["bytes"], name
 
 
 # ------------------------------------------------------------------------------------------------ the stem with the max-pool in its epilogue

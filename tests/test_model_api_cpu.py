@@ -172,7 +172,8 @@ def test_strict_load_state_dict_and_the_dataparallel_prefix():
     other = {k: (v + 0.5 if v.is_floating_point() else v) for k, v in sd.items()}
     dp = nn.DataParallel(net, device_ids=[]) if not torch.cuda.is_available() else nn.DataParallel(net, device_ids=[0])
     dp.load_state_dict({"module." + k: v for k, v in other.items()})
-    assert torch.equal(net.backbone.conv1.weight, other["backbone.conv1.weight"])
+    # (.cpu(): where a GPU is present, DataParallel with one device id moves the module there)
+    assert torch.equal(net.backbone.conv1.weight.cpu(), other["backbone.conv1.weight"])
     assert net._loaded
     with pytest.raises(RuntimeError, match="Missing key"):
         dp.load_state_dict(sd)             # without the prefix

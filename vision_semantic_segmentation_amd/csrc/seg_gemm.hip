@@ -634,6 +634,9 @@ struct MxArgs {
     const char* As2[2];
     long long a_srows2;
     int stagger;                // 1: waves 0-3 issue their LDS-DMAs after the first K half of a sub-step
+    // k_gemm_mx_pipe reads of the INPUT side only A, A2, Aq[0], Aq2[0], W, Wq[0], K, nmb1, a_srows and w_srows: rows are dense
+    // (lda = K1, lda2 = K - K1, a_srows2 = a_srows) and the other planes lie where mx_bundle_at puts them behind Aq[0] / Aq2[0] /
+    // Wq[0]; launch_ring_mx_t checks exactly that.  k_gemm_ring_mx reads every field.
 };
 
 // The epilogue of an MX GEMM tile (shared by k_gemm_ring_mx and k_gemm_mx_pipe): bias is in the accumulators; residual (one or two
@@ -646,9 +649,15 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
     const GemmArgs& p = q.g;
     const int nbase = nt * BN + wn * 64 + kq * 16;
     const bool ncol_ok = nbase + 16 <= p.N;
-    const bool rsplit = p.R_lo != nullptr, csplit = p.C_lo != nullptr;
+    // The uniform decisions of the eight rounds -- which planes there are -- are taken ONCE, into one flag word that the compiler
+    // cannot see through: a round then tests a bit of one scalar register (s_bitcmp) where it used to compare a 64-bit pointer or
+    // keep a 64-bit lane mask per decision alive, which is what pushed the kernels' scalar registers into spills.
+    enum { F_RES = 1, F_RES_LO16 = 2, F_RES_LOQ = 4, F_OUT_LO16 = 8, F_RELU = 16, F_OUT_Q0 = 32, F_OUT_Q1 = 64 };
+    unsigned fl = (p.R ? F_RES : 0) | (p.R_lo ? F_RES_LO16 : 0) | (q.Rq ? F_RES_LOQ : 0) | (p.C_lo ? F_OUT_LO16 : 0) | (p.relu ? F_RELU : 0) |
+                  (q.Cq[0] ? F_OUT_Q0 : 0) | (q.Cq[1] ? F_OUT_Q1 : 0);
+    asm volatile("" : "+s"(fl));
     // The epilogue is VALU-issue bound (eight rounds of ~250 vector instructions per wave while the matrix pipe idles), so:
-    // every address is a 32-bit offset from a uniform plane base (validate_gemm bounds the planes to 2 GB), the result is
+    // every address is a 32-bit BYTE offset from a uniform plane base (validate_gemm bounds the planes to 2 GB), the result is
     // converted to f16 ONCE (the packed vector is stored and read back as hi), every lane stores its own 8 FP4 bytes.
     const unsigned m0 = (unsigned)(mt * BM + wm * (MI * 16) + fr);
     const unsigned sc_r = (unsigned)(nbase >> 8) * (unsigned)q.r_srows * 8u + (unsigned)((nbase >> 5) & 7);
@@ -660,11 +669,11 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
     unsigned nsb = 127u;
     auto load_res = [&](int mi) {
         const unsigned m = m0 + mi * 16;
-        if (p.R && (int)m < p.M && ncol_ok) {
-            const H* rp = static_cast<const H*>(p.R) + (m * (unsigned)p.ldr + (unsigned)nbase);
+        if ((fl & F_RES) && (int)m < p.M && ncol_ok) {
+            const H* rp = reinterpret_cast<const H*>(static_cast<const char*>(p.R) + (m * (unsigned)p.ldr + (unsigned)nbase) * 2u);
             nr0 = *reinterpret_cast<const v8*>(rp);
             nr1 = *reinterpret_cast<const v8*>(rp + 8);
-            if (q.Rq) {       // the lo part as FP4: 16 values = 8 bytes, one scale byte for the lane pair's 32-block
+            if (fl & F_RES_LOQ) {       // the lo part as FP4: 16 values = 8 bytes, one scale byte for the lane pair's 32-block
                 npk = *reinterpret_cast<const uint2*>(q.Rq + (m * (unsigned)q.ldrq + (unsigned)(nbase / 2)));
                 nsb = (unsigned char)q.Rs[sc_r + m * 8u];
             }
@@ -684,16 +693,16 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
         for (int nj = 0; nj < 4; ++nj)
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[nj * 4 + r] = acc[mi][nj][r];
-        if (p.R && live) {
+        if ((fl & F_RES) && live) {
             float rl[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) rl[i] = 0.f;
-            if (rsplit) {
-                const H* rlp = static_cast<const H*>(p.R_lo) + (m * (unsigned)p.ldr + (unsigned)nbase);
+            if (fl & F_RES_LO16) {
+                const H* rlp = reinterpret_cast<const H*>(static_cast<const char*>(p.R_lo) + (m * (unsigned)p.ldr + (unsigned)nbase) * 2u);
                 const v8 l0 = *reinterpret_cast<const v8*>(rlp), l1 = *reinterpret_cast<const v8*>(rlp + 8);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { rl[i] = (float)l0[i]; rl[8 + i] = (float)l1[i]; }
-            } else if (q.Rq) {
+            } else if (fl & F_RES_LOQ) {
                 typedef float v2f __attribute__((ext_vector_type(2)));
                 const float sc = __uint_as_float(sb << 23);
 #define AVL_FP4_DEC(w, sel, o) { const v2f d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc, sel); rl[o] = d.x; rl[o + 1] = d.y; }
@@ -705,7 +714,7 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
 #pragma unroll
             for (int i = 0; i < 8; ++i) { v[i] += (float)r0[i] + rl[i]; v[8 + i] += (float)r1[i] + rl[8 + i]; }
         }
-        if (p.relu) {
+        if (fl & F_RELU) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = fmaxf(v[i], 0.f);
         }
@@ -720,18 +729,18 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
             lo[i] = v[i] - hi[i];
             lo[8 + i] = v[8 + i] - hi[8 + i];
         }
-        const unsigned coff = m * (unsigned)p.ldc + (unsigned)nbase;
+        const unsigned coff = (m * (unsigned)p.ldc + (unsigned)nbase) * 2u;       // bytes
         if (live) {
-            H* cp = static_cast<H*>(p.C) + coff;
+            H* cp = reinterpret_cast<H*>(static_cast<char*>(p.C) + coff);
             *reinterpret_cast<v8*>(cp) = h0;
             *reinterpret_cast<v8*>(cp + 8) = h1;
         }
-        if (csplit) {          // a stored lo plane is f16: its FP4 copy is taken from what it holds
+        if (fl & F_OUT_LO16) { // a stored lo plane is f16: its FP4 copy is taken from what it holds
             v8 l0, l1;
 #pragma unroll
             for (int i = 0; i < 8; ++i) { l0[i] = (H)lo[i]; l1[i] = (H)lo[8 + i]; }
             if (live) {
-                H* cl = static_cast<H*>(p.C_lo) + coff;
+                H* cl = reinterpret_cast<H*>(static_cast<char*>(p.C_lo) + coff);
                 *reinterpret_cast<v8*>(cl) = l0;
                 *reinterpret_cast<v8*>(cl + 8) = l1;
             }
@@ -743,7 +752,7 @@ __device__ __forceinline__ void mx_epilogue(const MxArgs& q, f32x4 (&acc)[MI][4]
             // (the partner lane is the same row, so it is dead as well)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
-                if (q.Cq[pl] == nullptr) continue;
+                if (!(fl & (pl == 0 ? F_OUT_Q0 : F_OUT_Q1))) continue;
                 unsigned pq[2];
                 const unsigned sq = quantize_fp4_block(pl == 0 ? hi : lo, pq);
                 if (live) {
@@ -1015,10 +1024,11 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     // of a tile: the (i, wave) part is uniform and goes into the scalar base, the lane keeps srow * row_bytes + its swizzled chunk
     // ((r & 7) == srow for activation rows).  For weight rows the swizzle key ((r >> 1) & 1) | (((r >> 4) & 3) << 1) does not depend
     // on i either (i moves r by 64): ONE lane offset per plane kind.
-    // The hot path of issue() works on a handful of scalars (cur_*: the planes of the input the current K macro-block comes from, at
-    // this tile and wave) that are re-derived from the argument struct only where they change -- at a tile switch and where the K
-    // loop passes from the first input to the second (conv3 + downsample): no scalar (kernarg) loads inside the stream, where
-    // their out-of-order lgkmcnt would force `s_waitcnt lgkmcnt(0)` in front of every LDS fragment use.
+    // The hot path of issue_w / issue_a works on a handful of scalars (run_*: where the next burst reads each plane of the input the
+    // current K macro-block comes from, at this tile and wave) that are set anew only at a tile switch and where the K loop passes
+    // from the first input to the second (conv3 + downsample): no scalar (kernarg) loads inside the stream, where their
+    // out-of-order lgkmcnt would force `s_waitcnt lgkmcnt(0)` in front of every LDS fragment use, and no spilled scalar either
+    // (tests/test_abi_mx_pipe_scalars.py: no v_readlane / v_writelane between the first and the last MFMA).
     // The lane offsets are NOT kept in registers (the K loop has none to spare: hipcc spilled them to scratch, and a scratch reload is a
     // vector-memory operation in the middle of the hand-counted DMA stream): every burst re-derives them from the lane id, ~8 VALU
     // instructions beside 64 MFMAs.  The lane id comes out of a volatile asm so that the arithmetic is not hoisted back out.
@@ -1027,35 +1037,57 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
         return l;
     };
-    int pt = vb, pmb = 0, pj = 0, issued = 0, pmbl = 0;        // tile, K macro-block (global / inside its input), sub-step being issued next
-    long long cur_rowb16 = 0, cur_rowbq = 0, cur_asrows = 0;
-    const char *cur_a16 = nullptr, *cur_aq = nullptr, *cur_as = nullptr, *cur_w16 = nullptr, *cur_wq = nullptr, *cur_ws = nullptr;
-    long long cur_aps = 0, cur_wps = 0;                          // distance from correction plane 0 to plane 1 (activations / weights)
+    // The six source pointers RUN: they stand at the piece the next burst fetches and move on by a constant when a sub-step (f16
+    // planes: 128 bytes along K) or a K macro-block (FP4 planes: 128 bytes; scale arrays: one block of rows) has been issued, so a
+    // burst costs an add pair per instruction and no multiply chain from (tile, macro-block, sub-step) indices.
+    int pt = vb, pmb = 0, pj = 0, issued = 0;                   // tile, K macro-block, sub-step being issued next
+    // What a switch (to the next tile; from the first input to the second) starts from is kept small, because it stays in scalar
+    // registers all through the stream: per operand the f16 plane and the BASE of its MX bundle, the allocated rows and the K split.
+    // The input rows are dense (row bytes from the operand's own K) and a bundle's planes lie where mx_bundle_at (seg_types.h) puts
+    // them -- FP4 hi, scales hi, FP4 lo, scales lo -- so strides and plane distances are a few multiplies at the switch instead of a
+    // dozen more pointers held; launch_ring_mx_t refuses arguments that are laid out otherwise.
+    unsigned cur_rowb16 = 0;                                     // bytes per row of the f16 input plane (the FP4 plane: a quarter)
+    const char *run_a16 = nullptr, *run_aq = nullptr, *run_as = nullptr, *run_w16 = nullptr, *run_wq = nullptr, *run_ws = nullptr;
+    unsigned cur_aps = 0;                                        // distance from correction plane 0 to plane 1 of the input
+    // These few are what the stream holds of the argument struct.  They are read from the kernel-argument segment at entry AND again
+    // behind every epilogue (read_args, through a pointer the compiler cannot see through), so that they are dead while the epilogue
+    // runs: it needs the scalar registers for its own dozen planes and strides, which in turn are dead in the stream.
+    const char *c_A, *c_A2, *c_Aq, *c_Aq2, *c_W, *c_Wq;
+    unsigned K, K1, arows, wrows;
+    unsigned asb, wsb;                                           // bytes per K macro-block of the input's / the weights' scales
+    unsigned w_pb, wps;                                          // the weights' FP4 plane; distance from correction plane 0 to plane 1
+    auto read_args = [&]() __attribute__((always_inline)) {
+        auto ka = __builtin_amdgcn_kernarg_segment_ptr();        // `q` is the kernel's first argument: offset 0
+        asm volatile("" : "+s"(ka));
+        const MxArgs* a = (const MxArgs*)ka;
+        c_A = static_cast<const char*>(a->g.A); c_A2 = static_cast<const char*>(a->A2); c_Aq = a->Aq[0]; c_Aq2 = a->Aq2[0];
+        c_W = static_cast<const char*>(a->g.W); c_Wq = a->Wq[0];
+        K = (unsigned)a->g.K; K1 = (unsigned)a->nmb1 * 256u; arows = (unsigned)a->a_srows; wrows = (unsigned)a->w_srows;
+        // the values are used HERE: the wait for the scalar loads stands here and not at their first use inside the stream
+        asm volatile("" : "+s"(c_A), "+s"(c_A2), "+s"(c_Aq), "+s"(c_Aq2), "+s"(c_W), "+s"(c_Wq), "+s"(K), "+s"(K1), "+s"(arows), "+s"(wrows));
+        asb = arows * 8u; wsb = wrows * 8u;
+        w_pb = (unsigned)mx_plane_bytes(wrows, K); wps = w_pb + (unsigned)mx_scale_bytes(wrows, K);
+    };
+    read_args();
     int p_mt = 0;
     auto set_input = [&](bool second) __attribute__((always_inline)) {     // rare: tile switch, first -> second input
         const long long rows0 = (long long)p_mt * BM + wave * 8;
-        if (!second) {
-            cur_rowb16 = (long long)p.lda * 2; cur_rowbq = q.ldaq; cur_asrows = q.a_srows;
-            cur_a16 = static_cast<const char*>(p.A) + rows0 * cur_rowb16;
-            cur_aq = q.Aq[0] + rows0 * cur_rowbq;
-            cur_as = q.As[0] + (long long)p_mt * BM * 8;
-            cur_aps = q.Aq[1] - q.Aq[0];
-        } else {
-            cur_rowb16 = (long long)q.lda2 * 2; cur_rowbq = q.ldaq2; cur_asrows = q.a_srows2;
-            cur_a16 = static_cast<const char*>(q.A2) + rows0 * cur_rowb16;
-            cur_aq = q.Aq2[0] + rows0 * cur_rowbq;
-            cur_as = q.As2[0] + (long long)p_mt * BM * 8;
-            cur_aps = q.Aq2[1] - q.Aq2[0];
-        }
-        pmbl = 0;
+        const unsigned kin = second ? K - K1 : K1;                         // this input's share of K
+        const char* a16 = second ? c_A2 : c_A;
+        const char* aq = second ? c_Aq2 : c_Aq;
+        const unsigned a_pb = (unsigned)mx_plane_bytes(arows, kin);
+        cur_rowb16 = kin * 2u;
+        run_a16 = a16 + rows0 * cur_rowb16;
+        run_aq = aq + rows0 * (kin / 2u);
+        run_as = aq + a_pb + (unsigned)(p_mt * BM * 8);
+        cur_aps = a_pb + (unsigned)mx_scale_bytes(arows, kin);
     };
     auto set_tile = [&]() __attribute__((always_inline)) {                  // rare: once per tile
         const int nt_ = pt % ntiles;
         p_mt = pt / ntiles;
-        cur_w16 = static_cast<const char*>(p.W) + (long long)nt_ * BN * p.K * 2;
-        cur_wq = q.Wq[0] + (long long)nt_ * BN * (p.K / 2);
-        cur_ws = q.Ws[0] + (long long)nt_ * BN * 8;
-        cur_wps = q.Wq[1] - q.Wq[0];
+        run_w16 = c_W + (long long)nt_ * BN * K * 2;
+        run_wq = c_Wq + (long long)nt_ * BN * (K / 2u);
+        run_ws = c_Wq + w_pb + (unsigned)(nt_ * BN * 8);
         set_input(false);
     };
     // One sub-step's DMA is issued in two bursts (see the events below): the weight tile, then the activation tile (+ the scale
@@ -1066,18 +1098,19 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
         // ((srow >> 1) & 1) | (((wave >> 1) & 3) << 1) does not depend on i
         const unsigned l = lane_now(), srow = l >> 3, cw = ((l & 7u) ^ (((srow >> 1) & 1u) | (((unsigned)(wave >> 1) & 3u) << 1))) << 4;
         const unsigned wr0 = (unsigned)wave * 8u + srow;
+        // (instruction i + 1 reads NW * 8 rows further on: an unsigned add to the running pointer)
         if (pj < 4) {
-            const char* sw = cur_w16 + (long long)(pmb * 4 + pj) * 128;
-            const unsigned wl = wr0 * (unsigned)(p.K * 2) + cw;
+            const char* sw = run_w16;
+            const unsigned rb = K * 2u, wl = wr0 * rb + cw;
 #pragma unroll
-            for (int i = 0; i < W_INSTR; ++i)
-                glds16_saddr(sw + (long long)i * (NW * 8) * p.K * 2, wl, wbase + i * NW * 1024);
+            for (int i = 0; i < W_INSTR; ++i, sw += rb * (NW * 8))
+                glds16_saddr_m0(sw, wl, wbase + i * NW * 1024);
         } else {
-            const char* sw = cur_wq + (pj == 4 ? 0 : cur_wps) + (long long)pmb * 128;
-            const unsigned wl = wr0 * (unsigned)(p.K / 2) + cw;
+            const char* sw = run_wq + (pj == 4 ? 0u : wps);
+            const unsigned rb = K / 2u, wl = wr0 * rb + cw;
 #pragma unroll
-            for (int i = 0; i < W_INSTR; ++i)
-                glds16_saddr(sw + (long long)i * (NW * 8) * (p.K / 2), wl, wbase + i * NW * 1024);
+            for (int i = 0; i < W_INSTR; ++i, sw += rb * (NW * 8))
+                glds16_saddr_m0(sw, wl, wbase + i * NW * 1024);
         }
     };
     // (the last piece also brings the scale blocks of an FP4 sub-step and moves the producer on to the next sub-step)
@@ -1085,34 +1118,36 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
         const unsigned abase = lds_base + (issued & 1) * A_BYTES + wave * 1024;
         const unsigned l = lane_now(), srow = l >> 3, ct = ((l & 7u) ^ srow) << 4;        // activation rows: key = r & 7 = srow
         if (pj < 4) {
-            const char* sa = cur_a16 + (long long)(pmbl * 4 + pj) * 128;
-            const unsigned al = srow * (unsigned)cur_rowb16 + ct;
+            const char* sa = run_a16;
+            const unsigned al = srow * cur_rowb16 + ct;
 #pragma unroll
-            for (int i = 0; i < A_INSTR; ++i)
-                glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowb16, al, abase + i * NW * 1024);
+            for (int i = 0; i < A_INSTR; ++i, sa += cur_rowb16 * (NW * 8))
+                glds16_saddr_m0(sa, al, abase + i * NW * 1024);
+            run_a16 += 128;
+            run_w16 += 128;
         } else {
-            const long long ta = pj == 4 ? 0 : cur_aps, tw = pj == 4 ? 0 : cur_wps;     // which correction pass
-            const char* sa = cur_aq + ta + (long long)pmbl * 128;
-            const unsigned a_lq = srow * (unsigned)cur_rowbq + ct;
+            const unsigned ta = pj == 4 ? 0u : cur_aps, tw = pj == 4 ? 0u : wps;        // which correction pass
+            const char* sa = run_aq + ta;
+            const unsigned cur_rowbq = cur_rowb16 >> 2, a_lq = srow * cur_rowbq + ct;
 #pragma unroll
-            for (int i = 0; i < A_INSTR; ++i)
-                glds16_saddr(sa + (long long)i * (NW * 8) * cur_rowbq, a_lq, abase + i * NW * 1024);
+            for (int i = 0; i < A_INSTR; ++i, sa += cur_rowbq * (NW * 8))
+                glds16_saddr_m0(sa, a_lq, abase + i * NW * 1024);
             // scales: BM x 8 bytes for the activation rows (waves 0, 1: one KB each), 2 KB for the weight rows (waves 2, 3)
             if (wave < 4 && (wave >= 2 || wave * 128 < BM)) {
-                const char* ss = wave < 2 ? cur_as + ta + (long long)pmbl * cur_asrows * 8 + wave * 1024
-                                          : cur_ws + tw + (long long)pmb * q.w_srows * 8 + (wave - 2) * 1024;
-                glds16_saddr(ss, l * 16u, lds_base + S_REGION + (issued & 1) * S_BYTES + wave * 1024);
+                const char* ss = wave < 2 ? run_as + ta + wave * 1024 : run_ws + tw + (wave - 2) * 1024;
+                glds16_saddr_m0(ss, l * 16u, lds_base + S_REGION + (issued & 1) * S_BYTES + wave * 1024);
             }
         }
         ++issued;
         if (++pj == nsub) {
             pj = 0;
-            ++pmbl;
+            run_aq += 128; run_as += asb;                        // the next K macro-block
+            run_wq += 128; run_ws += wsb;
             if (++pmb == nmb) {
                 pmb = 0;
                 pt += nwg;
                 if (pt < total) set_tile();
-            } else if (pmb == q.nmb1) set_input(true);
+            } else if (pmb * 256u == K1) set_input(true);
         }
     };
     if (pt < total) set_tile();
@@ -1134,16 +1169,16 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     const unsigned sw_v = (unsigned)(S_REGION + 2048 + (wn * 4 + (fr >> 2)) * 128 + ((fr & 3) * 4 + kq) * 8);
 
     f32x4 acc[MI][4];
-    auto init_acc = [&](int t) {
+    auto init_acc = [&](const float* bias, int t) {
         const int nb = (t % ntiles) * BN + wn * 64 + kq * 16;
 #pragma unroll
         for (int nj = 0; nj < 4; ++nj) {
-            const float4 b = *reinterpret_cast<const float4*>(p.bias + nb + 4 * nj);
+            const float4 b = *reinterpret_cast<const float4*>(bias + nb + 4 * nj);
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) acc[mi][nj] = f32x4{b.x, b.y, b.z, b.w};
         }
     };
-    if (vb < total) init_acc(vb);
+    if (vb < total) init_acc(p.bias, vb);
 
     // fragments: step s of a sub-step uses Af[s] (and its scale byte As[s]) with the weight set Wf[s / MI]
     int4 Af[NS], Wf[2][4];
@@ -1276,8 +1311,20 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
             for (int j = 0; j < 4; ++j) substep(F16(), j == 3);
             for (int u = 0; u < nmx; ++u) substep(FP4(), u + 1 < nmx);
         }
-        mx_epilogue<IO, MI>(q, acc, nt, mt, wm, wn, fr, kq);
-        if (t + nwg < total) init_acc(t + nwg);
+        // What only the epilogue uses (output and residual planes, their FP4 planes, scale slabs and strides, the bias) is not held
+        // in scalar registers across the stream -- with the producer's state that is more than the 100-odd a wave has, and hipcc
+        // then keeps the excess in the lanes of two vector registers and reads them back one v_readlane at a time, inside the stream
+        // too.  The tile's epilogue reads the argument struct again, from the kernel-argument segment it was passed in (`q` is the
+        // kernel's first argument: offset 0), through a pointer the compiler cannot see through, so the scalar loads stay here,
+        // behind the last MFMA in program text (tests/test_abi.py forbids them inside the stream).
+        auto ka = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        // (a COPY, made here: every field the epilogue uses is loaded once per tile, in front of the eight rounds -- through the bare
+        // pointer hipcc may not read ahead of the rounds' conditions and would load fields again in every round)
+        const MxArgs qe = *(const MxArgs*)ka;
+        mx_epilogue<IO, MI>(qe, acc, nt, mt, wm, wn, fr, kq);
+        if (t + nwg < total) init_acc(qe.g.bias, t + nwg);
+        read_args();
     }
 }
 
@@ -1297,6 +1344,16 @@ int launch_ring_mx_t(const MxArgs& a0, hipStream_t s) {
     if (a.g.K >= 1024) {
         // LATE: how many steps behind the event(s) waves 0-3 issue their bursts (waves 4-7: right behind them)
         constexpr int LATE = MI == 8 ? 0 : 1;
+        // k_gemm_mx_pipe finds strides and planes from each operand's K and the base of its bundle (see its set_input / set_tile)
+        const long long K = a.g.K, K1 = (long long)a.nmb1 * 256, K2 = K - K1;
+        auto bundle_ok = [&](const char* const* bq, const char* const* bs, long long rows, long long ch) {
+            const long long P = mx_plane_bytes(rows, ch), S = mx_scale_bytes(rows, ch);
+            return bs[0] - bq[0] == P && (a.nmx < 2 || (bq[1] - bq[0] == P + S && bs[1] - bq[0] == 2 * P + S)) && 2 * (P + S) < (1LL << 32);
+        };
+        AVL_REQUIRE(a.g.lda == K1 && a.ldaq == K1 / 2 && bundle_ok(a.Aq, a.As, a.a_srows, K1), "MX GEMM: first input is not dense rows + a bundle");
+        AVL_REQUIRE(K2 == 0 || (a.lda2 == K2 && a.ldaq2 == K2 / 2 && a.a_srows2 == a.a_srows && bundle_ok(a.Aq2, a.As2, a.a_srows, K2)),
+                    "MX GEMM: second input is not dense rows + a bundle of the first input's rows");
+        AVL_REQUIRE(bundle_ok(a.Wq, a.Ws, a.w_srows, K), "MX GEMM: weights are not a bundle");
         AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pipe<IO, MI, LATE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         hipLaunchKernelGGL((k_gemm_mx_pipe<IO, MI, LATE>), dim3(grid), dim3(512), LDS, s, a, mtiles);
     } else {

@@ -119,6 +119,19 @@ __device__ __forceinline__ void glds16_saddr(const void* sbase, unsigned voff, u
         : "memory");
 }
 
+// The same without saving and restoring M0: the statement declares it clobbered.  hipcc reserves M0 (it draws "clobber list
+// contains reserved registers" for this) and writes it itself right in front of the few instructions of its own that read it,
+// so it keeps no value there across a statement; a kernel that uses this must still show no other M0 user in its disassembly.
+__device__ __forceinline__ void glds16_saddr_m0(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
+    asm volatile(
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %0, %1"
+        :
+        : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
+        : "memory", "m0");
+}
+
 // 4 bytes per lane (64 x 4 B = 256 B per wave-instruction)
 __device__ __forceinline__ void glds4_saddr(const void* sbase, unsigned voff, unsigned lds_byte_addr) {
     unsigned keep;
@@ -193,9 +206,12 @@ struct MxBundle {
     int ldq;               // bytes per FP4 row
     long long srows;       // rows per 256-channel slab of the scales
 };
+// (bytes of one FP4 plane / of one scale array: k_gemm_mx_pipe finds the planes of a bundle from its base with the same two functions)
+__host__ __device__ inline long long mx_plane_bytes(long long rows, long long channels) { return rows * (channels / 2); }
+__host__ __device__ inline long long mx_scale_bytes(long long rows, long long channels) { return (channels / 256) * rows * 8; }
 template <typename C>
 inline MxBundle<C> mx_bundle_at(C* b, long long rows, long long channels) {
-    const long long P = rows * (channels / 2), S = (channels / 256) * rows * 8;
+    const long long P = mx_plane_bytes(rows, channels), S = mx_scale_bytes(rows, channels);
     return {{b, b + P + S}, {b + P, b + 2 * P + S}, (int)(channels / 2), rows};
 }
 inline MxBundle<char> mx_bundle(void* base, long long rows, long long channels) { return mx_bundle_at(static_cast<char*>(base), rows, channels); }

@@ -592,7 +592,7 @@ typedef struct avl_seg_op {
      * out2 != NULL: `weight` / `bias` hold the rows of two 1x1 convs of the same input one after the other, out_c = both widths together;
      * output columns [0, n_split) go to out (+ out_lo, row stride out_ld), columns [n_split, out_c) to out2 (+ out2_lo, row stride
      * out2_ld; out2 points at the column of its buffer where column n_split lands).  n_split is a multiple of the N tile the op runs with
-     * (256 where out_c % 256 == 0 and the shape takes the 256 x 256 tile, else 128), so an output tile belongs to one destination; each
+     * (tile_n of avl_seg_gemm_route, which may be asked before the buffers exist), so an output tile belongs to one destination; each
      * value is what the conv alone computes, bit for bit.  out_rows counts the rows of the shorter of the two buffers.
      * A ring GEMM also takes stride = s > 1 (Bottleneck.downsample of a striding block): in_h x in_w is then the UN-sampled input image,
      * out_h x out_w = ((in_h - 1) / s + 1) x ((in_w - 1) / s + 1), and output row (oy, ox) of image n reads input pixel
@@ -627,6 +627,60 @@ int avl_seg_plan_num_ops(const avl_seg_plan* plan);
  * type's range into Inf in the producing op's epilogue; a later ReLU can hide that from the logits.  SemanticSegmentation's
  * load-time self-check (semantic_segmentation.py:28-32 loads real checkpoints) refuses a plan with a non-zero count. */
 int avl_seg_plan_nonfinite(avl_seg_plan* plan, void* stream, unsigned long long* counts_host);
+
+/* ---- which kernel an AVL_OP_GEMM runs -------------------------------------------------------- */
+#define AVL_GEMM_PLAIN 0     /* k_gemm<T, WM, WN>: two LDS buffers, tiles of WM * 64 rows x WN * 64 columns, one workgroup per tile */
+#define AVL_GEMM_RING 1      /* k_gemm_ring<T, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>: tiles of WM * MI * 16 rows x WN * 64 columns   */
+#define AVL_GEMM_RING_MX 2   /* k_gemm_ring_mx<IO, MI>: the MX GEMM (w_split 2), tiles of MI * 32 rows x 256 columns                   */
+#define AVL_GEMM_MX_PIPE 3   /* k_gemm_mx_pipe<IO, MI, LATE>: the MX GEMM with the software-pipelined main loop, same tiles           */
+
+/* What the launch of one AVL_OP_GEMM decides.  A template argument the kernel family does not have is 0. */
+typedef struct avl_gemm_route {
+    int32_t kernel;              /* AVL_GEMM_*                                                                          */
+    int32_t dtype;               /* element type the kernel is instantiated for (AVL_F32 / AVL_BF16 / AVL_F16)          */
+    int32_t tile_m, tile_n;      /* rows and columns of an output tile                                                  */
+    int32_t wm, wn;              /* PLAIN, RING: waves along M and N                                                    */
+    int32_t mi;                  /* RING, MX: 16-row MFMA blocks per wave along M                                       */
+    int32_t stages;              /* RING: LDS stages of the weight ring                                                  */
+    int32_t nsub;                /* RING (template argument NSUB), PLAIN (a kernel argument): passes per K block, 1 (w_split 0),
+                                    2 (w_split 1: weights split) or 3 (w_split 1 with in_lo: the input split too)        */
+    int32_t io;                  /* RING: 1 = split residual / output planes (with nsub > 1); MX: 1 = the epilogue also writes the
+                                    output's MX bundle (out_mx set)                                                     */
+    int32_t ast;                 /* RING: LDS stages of the activation tile                                             */
+    int32_t ext;                 /* the op asks for strided input rows or a second destination (stride > 1, out2, out2_lo or n_split set):
+                                    RING runs its EXT instantiation; no other kernel has one (avl_seg_plan_create refuses the op) */
+    int32_t late;                /* MX_PIPE: LATE                                                                       */
+    int32_t launches;            /* `batch` for an op with a per-image bias (each launch: one image as a batch-1 op), else 1 */
+    int32_t m_tiles, n_tiles;    /* of ONE launch: row tiles over all the rows of the batch (or the one image), column tiles */
+    int32_t workgroups;          /* of ONE launch: m_tiles * n_tiles for PLAIN, min(m_tiles * n_tiles, 256) for the others,
+                                    whose workgroups walk their tiles */
+} avl_gemm_route;
+
+/* The kernel avl_seg_plan_run launches for `op` (host only: looks at sizes, flags and whether pointer fields are NULL, never at
+ * memory), provided avl_seg_plan_create accepts the op; it does not run that validation, so the buffers need not exist yet.
+ * AVL_E_ARG for a NULL argument or an op that is not AVL_OP_GEMM.
+ *
+ * With M1 = out_h * out_w (the rows of ONE image: a batch runs the kernel its batch-1 plan runs), M = M1 * batch, N = out_c,
+ * K = in_c (+ in3_c with a second input) and t256 = ceil(M1 / 256) * (N / 256), the first row that applies:
+ *
+ *   condition                                            kernel     tile        template arguments
+ *   w_split 2 (the MX GEMM)                              MX_PIPE where K >= 1024, else RING_MX; IO = (out_mx set)
+ *     t256 < 192 or 256 < t256 < 384                                128 x 256   MI 4, LATE 1
+ *     otherwise                                                     256 x 256   MI 8, LATE 0
+ *   ring-eligible: a 16-bit dtype, w_layout != 1, N > 64, N % 128 == 0, out_f32 0 and in_rows >= M rounded up to 256
+ *                                                        RING; NSUB = nsub; IO = (NSUB > 1); T = f16 with NSUB > 1, else dtype;
+ *                                                        EXT = ext
+ *     v = 3                                                         256 x 256   WM 2, WN 4, MI 8, STAGES 3 with NSUB 2 else 2, AST 2
+ *     v = 4 and NSUB 1                                              256 x 128   WM 2, WN 2, MI 8, STAGES 3, AST 3 (four waves; no EXT form)
+ *     otherwise                                                     256 x 128   WM 4, WN 2, MI 4, STAGES 3, AST 3
+ *     where v = w_layout, or with w_layout 0: 3 if t256 >= 192 and N % 256 == 0 and w_rows % 256 == 0, else 2; a forced 3 falls back to
+ *     2 unless N % 256 == 0 and w_rows % 256 == 0
+ *   N <= 64                                              PLAIN      256 x 64    T = dtype, WM 4, WN 1
+ *   otherwise (AVL_F32, w_layout 1, out_f32, ...)        PLAIN      128 x 128   T = dtype, WM 2, WN 2
+ *
+ * m_tiles = ceil(M / tile_m), n_tiles = ceil(N / tile_n).  An op with bias_per_image and batch > 1 runs `batch` launches, each the
+ * route of one image (M = M1, that image's rows). */
+int avl_seg_gemm_route(const avl_seg_op* op, avl_gemm_route* out);
 
 #ifdef __cplusplus
 }

@@ -14,8 +14,9 @@ other element of both buffers' two planes keeps FILL.  stored() builds the WHOLE
 neighbouring columns and planes that are not written.  The device input (device_input) holds NaN in every row and column the op
 must not read: pixels a strided read skips, columns past K, rows past the last image.
 
-Which kernel a case reaches (launch_gemm / ring_variant in csrc/seg_gemm.hip): variant() mirrors ring_variant; the instantiation
-is k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT = true> as named by INSTANTIATION."""
+Which kernel a case reaches is asked of the library (route(): avl_seg_gemm_route on the case's op, whose header comment states the
+rule): k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT = true> with the arguments INSTANTIATION names for the case's mode and
+tile variant; tests/test_exact_operands_cpu.py checks every case's route against that table."""
 import collections
 import functools
 
@@ -56,19 +57,60 @@ def geometry(c):
                 w_rows=_up(c.N, 256), n1=n1, n2=c.N - n1, ld1=n1 + PAD1, ld2=c.N - n1 + PAD2)
 
 
-def variant(c):
-    """ring_variant of csrc/seg_gemm.hip: 2 = 256 x 128 tiles, 3 = 256 x 256"""
+def shape_op(c, ptr):
+    """the case's op with `ptr` (16-byte aligned) in every pointer field the case sets: what the library's validation and its
+    choice of kernel look at.  test_gpu_ring_ext_exact.py puts the device buffers in."""
+    from vision_semantic_segmentation_amd import _lib
+    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
     g = geometry(c)
-    can256 = c.N % 256 == 0 and g["w_rows"] % 256 == 0
-    v = c.wl
-    if v == 0:
-        v = 3 if can256 and _up(g["oh"] * g["ow"], 256) // 256 * (c.N // 256) >= 192 else 2
-    return 2 if v == 3 and not can256 else v
+    prec, nsub = MODES[c.mode]
+    op = AvlSegOp()
+    op.kind, op.dtype = OP_GEMM, _lib.AVL_BF16 if prec == "bf16" else _lib.AVL_F16
+    op.in_ = op.weight = op.bias = op.out = ptr
+    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = c.ih, c.iw, K, K + c.extra, g["in_rows"]
+    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = g["oh"], g["ow"], c.N, g["ld1"], g["out_rows"]
+    op.relu, op.w_rows, op.ksize, op.stride, op.dil, op.groups, op.batch = int(c.relu), g["w_rows"], 1, c.s, 1, 1, c.B
+    op.w_layout, op.w_split = c.wl, int(nsub > 1)
+    if nsub == 3:
+        op.in_lo = ptr
+    if c.lo1:
+        op.out_lo = ptr
+    if c.n_split:
+        op.out2, op.out2_ld, op.n_split = ptr, g["ld2"], c.n_split
+        if c.lo2:
+            op.out2_lo = ptr
+    return op
+
+
+def claimed_variant(c):
+    """the tile variant a case is written for (INSTANTIATION's second key): the one its w_layout forces (N is a multiple of 256 wherever
+    that is 3); the w_layout-0 cases here are small shapes of N = 384, which the library runs on 256 x 128 tiles"""
+    return c.wl or 2
+
+
+def route(c):
+    """the library's answer for the case's op (network.gemm_route)"""
+    from vision_semantic_segmentation_amd.network import gemm_route
+    return gemm_route(shape_op(c, 16))
+
+
+def variant(c):
+    """the tile variant the case runs with, in w_layout's numbering: 2 = 256 x 128 tiles, 3 = 256 x 256"""
+    return {128: 2, 256: 3}[route(c)["tile_n"]]
 
 
 def tiles(c):
-    """(mtiles, ntiles) of the launch: 256-row tiles, 128 or 256 columns"""
-    return _up(geometry(c)["M"], 256) // 256, _up(c.N, 256 if variant(c) == 3 else 128) // (256 if variant(c) == 3 else 128)
+    """(mtiles, ntiles) of the launch"""
+    r = route(c)
+    return r["m_tiles"], r["n_tiles"]
+
+
+def instantiation(r):
+    """a route of the ring kernel in INSTANTIATION's form"""
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name
+    name = gemm_kernel_name(r)
+    assert name.startswith("k_gemm_ring<"), name
+    return name[len("k_gemm_ring<"):-1]
 
 
 def row_map(c, wrong=None):

@@ -160,7 +160,7 @@ def test_mx_pipe_stream_holds_no_scalar_loads_and_no_scratch():
 def test_library_reads_no_environment_and_holds_only_launched_kernels():
     """VERDICT r3 / ADVICE r3: the library takes no A/B switch from the environment -- it must not even import getenv -- and
     holds no timing probe (results garbage by design) nor experiment kernel: k_gemm_mx_pipe is compiled for exactly the
-    <IO, MI, LATE> sets launch_ring_mx_t launches."""
+    <IO, MI, LATE> sets of GEMM_KERNELS (csrc/seg_gemm.hip), the table launch_gemm dispatches from."""
     import subprocess
     kn = _notes()
     undefined = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout

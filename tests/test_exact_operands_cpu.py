@@ -141,6 +141,29 @@ def test_ring_ext_operands(c):
     assert bool(torch.isfinite(a[:, rows, :R.K].float()).all()) and int(torch.isfinite(a.float()).sum()) == a.shape[0] * g["M"] * R.K
 
 
+_HOST = torch.zeros(1 << 12, dtype=torch.uint8)
+_PTR = (_HOST.data_ptr() + 255) // 256 * 256        # host memory: validation and the route look at values and alignment only
+
+
+@pytest.mark.parametrize("c", R.SMALL_CASES + R.MULTI_TILE_CASES, ids=R.case_id)
+def test_ring_ext_case_runs_the_instantiation_the_table_names(c):
+    """the library's route for the case's op (placeholder pointers: no GPU) is the row of R.INSTANTIATION the case claims, on the
+    256-row tiles of the ring kernel, and avl_seg_plan_create accepts that op"""
+    import ctypes as C
+    from vision_semantic_segmentation_amd import _lib
+    from vision_semantic_segmentation_amd.network import AvlSegOp, gemm_route
+    op = R.shape_op(c, _PTR)
+    r = gemm_route(op)
+    assert R.instantiation(r) == R.INSTANTIATION[(c.mode, R.claimed_variant(c))]
+    assert R.variant(c) == R.claimed_variant(c)
+    bn = {2: 128, 3: 256}[R.claimed_variant(c)]
+    assert (r["tile_m"], r["tile_n"], r["launches"]) == (256, bn, 1)
+    assert R.tiles(c) == ((R.geometry(c)["M"] + 255) // 256, (c.N + bn - 1) // bn) and r["workgroups"] == min(256, r["m_tiles"] * r["n_tiles"])
+    plan = C.c_void_p()
+    _lib.check(_lib.lib().avl_seg_plan_create((AvlSegOp * 1)(op), 1, C.byref(plan)), "avl_seg_plan_create")
+    _lib.lib().avl_seg_plan_destroy(plan)
+
+
 def test_ring_ext_cases_reach_what_they_claim():
     """all eight EXT instantiations among the small cases of each form; every multi-tile case has more tiles than the grid's cap"""
     for cases in (R.SMALL_STRIDED, R.SMALL_TWIN, R.SMALL_BOTH):

@@ -28,15 +28,9 @@ Operand design (tests/_exact_operands.py; test_exact_operands_cpu.py checks ever
     mirrors step by step (fma_chain).  These cases have no integer ties; they assert the 20 % condition only.
   * OP_DWPW: depthwise weights in {0, +-1}, bias within +-20: relu(depthwise) is an integer below 256, exact in both 16-bit types.
 
-Which kernel a case reaches (launch_gemm / pick_tile / ring_eligible in csrc/seg_gemm.hip and the launchers of the other files):
-  OP_GEMM, w_layout 0 (by shape), 16-bit: N <= 64 -> k_gemm<T, 4, 1> (256 x 64 tiles): (300, 64, 64), (65, 256, 64), N = 19;
-    N % 128 != 0 or rows padded to 128 only -> k_gemm<T, 2, 2>: (65, 2048, 192), (300, 256, 256 | pad128);
-    else the ring: 256 x 256 (k_gemm_ring<T, 2, 4, 8, 2>) iff N % 256 == 0 and ceil(M / 256) * N / 256 >= 192: (12288, 64, 1024)
-    = 48 * 4; 256 x 128 (k_gemm_ring<T, 4, 2, 4, 3>) otherwise: (777, 256, 128), (4097, 256, 256), (777, 2048, 512), per-image
-    bias (three launches of 377 rows).  fp32: k_gemm<float, 4, 1> for N <= 64, k_gemm<float, 2, 2> for the rest.
-  OP_GEMM, w_layout 1 .. 4 (16-bit, forced): 1 = k_gemm<T, 2, 2> (N > 64); where the shape is ring-eligible 2 = the 256 x 128
-    ring, 3 = the 256 x 256 ring when N % 256 == 0 (else as 2), 4 = k_gemm_ring<T, 2, 2, 8, 3>; shapes that are not eligible
-    (N <= 64, N = 192, pad128) run the kernel of layout 0 under every layout.
+Which kernel a case reaches (the launchers of csrc/):
+  OP_GEMM: GEMM_KERNELS below names the kernel of every case, type and w_layout; _run_gemm asserts it against the library's own answer
+    (avl_seg_gemm_route, whose comment in include/avl_hip.h states the rule) for the op that runs.
   OP_GCONV w_layout 2: k_conv3x3<T, 0, false, NQ> with NQ = 2 iff cg % 128 == 0 (cg 256, 1024), NQ = 1 for cg 64; split:
     k_conv3x3<f16, 1, XS, NQ>, XS = the input has a lo plane.  Stride 1 with dilation > 1 walks the d x d residue classes ("comb").
   OP_GCONV w_layout 1: k_gconv_mfma<T, 0, NJ, false>, NJ (tile height 2 NJ) picked by gconv_pick_th from the shape;
@@ -86,10 +80,29 @@ def _same(got, want, what):
 
 
 # ------------------------------------------------------------------------------------------------------------------- GEMM
+# The kernel of every GEMM case: (under fp32, [under a 16-bit type T with w_layout 0, 1, 2, 3, 4]).  k_gemm<T, WM, WN> has tiles of
+# WM * 64 x WN * 64, k_gemm_ring<T, WM, WN, MI, STAGES, NSUB, IO, AST, EXT> of 256 x WN * 64 (WM = MI = 2, 8: on four waves).
+_P64, _P128, _F64, _F128 = "k_gemm<T, 4, 1>", "k_gemm<T, 2, 2>", "k_gemm<float, 4, 1>", "k_gemm<float, 2, 2>"
+_R128, _R256, _R4W = ("k_gemm_ring<T, 4, 2, 4, 3, 1, 0, 3, false>", "k_gemm_ring<T, 2, 4, 8, 2, 1, 0, 2, false>",
+                      "k_gemm_ring<T, 2, 2, 8, 3, 1, 0, 3, false>")
+GEMM_KERNELS = {
+    (300, 64, 64, False, True, None): (_F64, [_P64] * 5),                                   # N = 64: the small-N kernel, whatever is forced
+    (65, 256, 64, True, False, None): (_F64, [_P64] * 5),
+    (777, 256, 128, True, False, None): (_F128, [_R128, _P128, _R128, _R128, _R4W]),        # N = 128: a forced 256 x 256 falls back
+    (65, 2048, 192, True, True, None): (_F128, [_P128] * 5),                                # N = 192 is no multiple of 128
+    (4097, 256, 256, False, False, "slices"): (_F128, [_R128, _P128, _R128, _R256, _R4W]),  # 17 tiles of 256 x 256: by shape 256 x 128
+    (777, 2048, 512, True, True, "slices"): (_F128, [_R128, _P128, _R128, _R256, _R4W]),
+    (300, 256, 256, False, True, "pad128"): (_F128, [_P128] * 5),                           # rows padded to 128 only
+    (1131, 256, 256, False, True, "per_image"): (_F128, [_R128]),                           # three launches of 377 rows
+    X.GEMM_RING256: (_F128, [_R256]),                                                       # 48 x 4 = 192 tiles of 256 x 256
+    X.GEMM_ARGMAX[0]: (_F64, [_P64]), X.GEMM_ARGMAX[1]: (_F64, [_P64]),                     # N = 19
+}
+
+
 def _run_gemm(case, prec, layout, dev):
     import torch
     from test_gpu_ops import _run_plan
-    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
+    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp, gemm_kernel_name, gemm_route
     M, K, N, res, relu, form = case
     c = X.gemm_case(case, prec)
     tdt, did = _types(prec)
@@ -133,6 +146,10 @@ def _run_gemm(case, prec, layout, dev):
     if argmax:
         labels = torch.full((Mp,), 99, dtype=torch.uint8, device=dev)
         op.out_mx = labels.data_ptr()
+    route = gemm_route(op)
+    f32_kernel, half_kernels = GEMM_KERNELS[case]
+    assert gemm_kernel_name(route) == (f32_kernel if prec == "f32" else half_kernels[layout].replace("T", prec)), (case, prec, layout)
+    assert route["launches"] == batch
     _run_plan([op])
     o = out.cpu()
     _same(o[:M, out_off:out_off + N], c["want"], "gemm %s %s layout %d" % (case, prec, layout))

@@ -35,6 +35,14 @@ def _gemm(did, src, src_lo, w, b, dst, dst_lo, in_hw, out_hw, n, in_ld, out_ld, 
     return op
 
 
+def _runs_ext_ring(op, mode, w_layout):
+    """the op runs the EXT instantiation of the ring kernel that tests/_ring_ext_operands.py names for its mode and tile variant
+    (w_layout 3 = 256 x 256 tiles; by shape these sizes run 256 x 128): asked of the library for the very op"""
+    import _ring_ext_operands as R
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name, gemm_route
+    assert gemm_kernel_name(gemm_route(op)) == "k_gemm_ring<%s>" % R.INSTANTIATION[(mode, w_layout or 2)]
+
+
 def _operands(mode, n, rows, ld, seed, cuda_device):
     """input planes [2 | 1][rows][ld] (NaN outside the K columns that are read), packed weights [round_up(n, 256)][..], bias"""
     import torch
@@ -101,7 +109,9 @@ def test_strided_gemm_equals_subsample_then_gemm(case, cuda_device):
     _run_plan(ops)
 
     got = torch.full((planes, out_rows, N), FILL, dtype=tdt, device=cuda_device)
-    _run_plan([_gemm(did, a[0].data_ptr(), lo(a), wd, bd, got[0].data_ptr(), lo(got), (ih, iw), (oh, ow), N, ld, N, in_rows, out_rows, B, stride=s, **kw)])
+    strided = _gemm(did, a[0].data_ptr(), lo(a), wd, bd, got[0].data_ptr(), lo(got), (ih, iw), (oh, ow), N, ld, N, in_rows, out_rows, B, stride=s, **kw)
+    _runs_ext_ring(strided, mode, kw.get("w_layout"))
+    _run_plan([strided])
     assert bool(torch.isfinite(ref[:, :B * oh * ow].float()).all()) and float(ref[0, :B * oh * ow].float().abs().max()) > 0
     for p in range(planes):
         assert torch.equal(got[p], ref[p]), "%r: plane %d differs from sub-sample -> GEMM" % (case, p)
@@ -155,6 +165,7 @@ def test_twin_gemm_equals_two_gemms(case, cuda_device):
     got1, got2 = new()
     twin = _gemm(did, a[0].data_ptr(), lo(a), wd, bd, got1[0, :, col:].data_ptr(), lo(got1, col), (1, M), (1, M), n1 + n2, K, 512, rows, rows, 1,
                  out2=got2.data_ptr(), out2_ld=256, n_split=n1, **kw)
+    _runs_ext_ring(twin, mode, kw.get("w_layout"))
     first = None
     for rep in range(3):           # a race screen: the same bytes every time
         _run_plan([twin])

@@ -30,11 +30,9 @@ mx_quant_fp4(out) byte for byte with its scales, lo half = mx_quant_fp4 of the f
 fp32 value v - out under AVL_MX_OUT_LO alone.  Rows past M keep their sentinel in every plane and scale slab; so do out_lo and
 the lo half of the bundle when the form does not write them.
 
-Which kernel a case reaches (launch_ring_mx / launch_gemm in csrc/seg_gemm.hip), with t256 = ceil(M / 256) * N / 256 counted on
-ONE image's rows:
-  * MX: 128-row tiles (MI = 4) iff t256 < 192 or 256 < t256 < 384, 256-row tiles (MI = 8) otherwise; k_gemm_mx_pipe iff the
-    total K >= 1024, else k_gemm_ring_mx; IO = 1 iff out_mx is set.
-  * split: the 256 x 256 ring iff N % 256 == 0 and t256 >= 192, else the 256 x 128 ring; NSUB = 3 iff in_lo is set.
+Which kernel a case reaches is part of the case (the last field of MX_CASES, SPLIT_KERNELS) and asserted against the library's own
+answer for the very op that runs (avl_seg_gemm_route, whose comment in include/avl_hip.h states the rule; t256 there = ceil(M / 256)
+* N / 256 on ONE image's rows); tests/test_gemm_route_cpu.py walks the same tables without a GPU.
 
 Hardware observation (MI355X): v_mfma_scale_f32_16x16x128_f8f6f4 and v_mfma_f32_16x16x32_f16 accumulate these dot products
 exactly -- every case below is bit-equal to the host's result."""
@@ -161,7 +159,7 @@ def _same_values(got, want):
     return got.shape == want.shape and bool(torch.equal(got, want))
 
 
-# (M, K, K2, N, form, relu): K2 = columns of a second input appended along K; forms
+# (M, K, K2, N, form, relu, the kernel the op runs): K2 = columns of a second input appended along K; forms
 #   plain = weights-only correction, no residual, one output plane                                   (IO 0)
 #   noq   = in_lo, single-plane residual, split output, no out_mx                                    (IO 0)
 #   split = in_lo, split f16 residual, split output, out_mx with both halves                         (IO 1)
@@ -169,52 +167,88 @@ def _same_values(got, want):
 #   trunk = AVL_MX_IN_LO | AVL_MX_RES_LO | AVL_MX_OUT_LO: every lo part only as FP4                  (IO 1)
 MX_CASES = [
     # 256-row tiles: N = 2048, M = 5900 -> 24 row tiles (the last holds 12 rows), t256 = 24 * 8 = 192
-    (5900, 256, 0, 2048, "plain", True),      # k_gemm_ring_mx<0, 8>: K < 1024, one macro-block
-    (5900, 256, 0, 2048, "split", False),     # k_gemm_ring_mx<1, 8>
-    (5900, 256, 0, 2048, "trunk", True),      # k_gemm_ring_mx<1, 8>
-    (5900, 1024, 0, 2048, "noq", False),      # k_gemm_mx_pipe<0, 8, 0>: K >= 1024
-    (5900, 1024, 0, 2048, "split", True),     # k_gemm_mx_pipe<1, 8, 0>
-    (5900, 1024, 0, 2048, "trunk", False),    # k_gemm_mx_pipe<1, 8, 0>
-    (5900, 1280, 0, 2048, "plain", False),    # k_gemm_mx_pipe<0, 8, 0>, odd macro-block count (5)
-    (5900, 1280, 0, 2048, "hiq", True),       # k_gemm_mx_pipe<1, 8, 0>
-    (5900, 1280, 0, 2048, "trunk", True),     # k_gemm_mx_pipe<1, 8, 0>
-    # more tiles than CUs, a workgroup walks several: M = 12100 -> t256 = 48 * 8 = 384 (not < 384): 256-row tiles, 384 of them
-    (12100, 1024, 0, 2048, "trunk", True),    # k_gemm_mx_pipe<1, 8, 0>
-    # 128-row tiles: t256 = 2 * 1 = 2 and 4 * 2 = 8, both < 192
-    (300, 256, 0, 256, "plain", False),       # k_gemm_ring_mx<0, 4>
-    (300, 1024, 0, 256, "split", True),       # k_gemm_mx_pipe<1, 4, 1>
-    (777, 256, 0, 512, "trunk", False),       # k_gemm_ring_mx<1, 4>
-    (777, 256, 0, 512, "split", True),        # k_gemm_ring_mx<1, 4>
-    (777, 1024, 0, 512, "noq", True),         # k_gemm_mx_pipe<0, 4, 1>
-    (777, 1024, 0, 512, "trunk", True),       # k_gemm_mx_pipe<1, 4, 1>
-    # 128-row tiles in the window 256 < t256 < 384: M = 8300 -> t256 = 33 * 8 = 264, 65 * 8 = 520 tiles of 128 rows on 256 workgroups
-    (8300, 256, 0, 2048, "trunk", True),      # k_gemm_ring_mx<1, 4>
+    (5900, 256, 0, 2048, "plain", True, "k_gemm_ring_mx<0, 8>"),      # one macro-block
+    (5900, 256, 0, 2048, "split", False, "k_gemm_ring_mx<1, 8>"),
+    (5900, 256, 0, 2048, "trunk", True, "k_gemm_ring_mx<1, 8>"),
+    (5900, 1024, 0, 2048, "noq", False, "k_gemm_mx_pipe<0, 8, 0>"),      # K = 1024
+    (5900, 1024, 0, 2048, "split", True, "k_gemm_mx_pipe<1, 8, 0>"),
+    (5900, 1024, 0, 2048, "trunk", False, "k_gemm_mx_pipe<1, 8, 0>"),
+    (5900, 1280, 0, 2048, "plain", False, "k_gemm_mx_pipe<0, 8, 0>"),      # odd macro-block count (5)
+    (5900, 1280, 0, 2048, "hiq", True, "k_gemm_mx_pipe<1, 8, 0>"),
+    (5900, 1280, 0, 2048, "trunk", True, "k_gemm_mx_pipe<1, 8, 0>"),
+    # more tiles than CUs, a workgroup walks several: M = 12100 -> t256 = 48 * 8 = 384: 256-row tiles, 384 of them
+    (12100, 1024, 0, 2048, "trunk", True, "k_gemm_mx_pipe<1, 8, 0>"),
+    # 128-row tiles: t256 = 2 * 1 = 2 and 4 * 2 = 8
+    (300, 256, 0, 256, "plain", False, "k_gemm_ring_mx<0, 4>"),
+    (300, 1024, 0, 256, "split", True, "k_gemm_mx_pipe<1, 4, 1>"),
+    (777, 256, 0, 512, "trunk", False, "k_gemm_ring_mx<1, 4>"),
+    (777, 256, 0, 512, "split", True, "k_gemm_ring_mx<1, 4>"),
+    (777, 1024, 0, 512, "noq", True, "k_gemm_mx_pipe<0, 4, 1>"),
+    (777, 1024, 0, 512, "trunk", True, "k_gemm_mx_pipe<1, 4, 1>"),
+    # 128-row tiles again above 256: M = 8300 -> t256 = 33 * 8 = 264, 65 * 8 = 520 tiles of 128 rows on 256 workgroups
+    (8300, 256, 0, 2048, "trunk", True, "k_gemm_ring_mx<1, 4>"),
     # a second input along K, 128-row tiles (t256 = 8)
-    (777, 256, 512, 512, "trunk", True),      # K1 + K2 = 768 < 1024: k_gemm_ring_mx<1, 4>, the input changes after macro-block 1 of 3
-    (777, 512, 512, 512, "trunk", False),     # K1 + K2 = 1024: k_gemm_mx_pipe<1, 4, 1>, the input changes in the middle of the stream
+    (777, 256, 512, 512, "trunk", True, "k_gemm_ring_mx<1, 4>"),      # K1 + K2 = 768: the input changes after macro-block 1 of 3
+    (777, 512, 512, 512, "trunk", False, "k_gemm_mx_pipe<1, 4, 1>"),      # K1 + K2 = 1024: the input changes in the middle of the stream
     # ... and 256-row tiles (t256 = 192)
-    (5900, 256, 512, 2048, "trunk", False),   # k_gemm_ring_mx<1, 8>
-    (5900, 512, 512, 2048, "trunk", True),    # k_gemm_mx_pipe<1, 8, 0>
-    (5900, 512, 768, 2048, "noq", True),      # k_gemm_mx_pipe<0, 8, 0>: plain in_lo is refused with a second input, so AVL_MX_IN_LO
+    (5900, 256, 512, 2048, "trunk", False, "k_gemm_ring_mx<1, 8>"),
+    (5900, 512, 512, 2048, "trunk", True, "k_gemm_mx_pipe<1, 8, 0>"),
+    (5900, 512, 768, 2048, "noq", True, "k_gemm_mx_pipe<0, 8, 0>"),      # plain in_lo is refused with a second input, so AVL_MX_IN_LO
 ]
+
+
+def _mx_form(form):
+    """-> (correction passes, the residual's form, split output, out_mx set, the bundle's lo half is written)"""
+    return (1 if form in ("plain", "hiq") else 2, {"plain": None, "hiq": None, "noq": "single", "split": "split", "trunk": "fp4"}[form],
+            form in ("noq", "split"), form in ("split", "hiq", "trunk"), form in ("split", "trunk"))
+
+
+def mx_shape_op(case, ptr, batch=0, hw=None):
+    """the case's op with `ptr` (16-byte aligned) in every pointer field its form sets: all that the library's validation and its
+    choice of kernel look at.  _run_mx puts the device buffers in; tests/test_gemm_route_cpu.py asks for the route as it stands."""
+    from vision_semantic_segmentation_amd.network import AVL_MX_IN_LO, AVL_MX_OUT_LO, AVL_MX_RES_LO
+    M, K1, K2, N, form, relu = case[:6]
+    nmx, res, o_split, quant, _ = _mx_form(form)
+    op = _gemm_op(M if not batch else hw[0] * hw[1], K1, N, (M + 255) // 256 * 256, relu, batch, hw)
+    op.in_ = op.out = op.weight = op.bias = op.w_mx = op.in_mx = ptr
+    op.w_rows, op.w_split = N, 2
+    flags = 0
+    if nmx == 2:
+        if form == "trunk" or K2:
+            flags |= AVL_MX_IN_LO
+        else:
+            op.in_lo = ptr                                       # switches the second pass on; its values are never read
+    if K2:
+        op.in3, op.in3_mx, op.in3_c, op.in3_ld = ptr, ptr, K2, K2
+    if o_split:
+        op.out_lo = ptr
+    if quant:
+        op.out_mx = ptr
+        if form == "trunk":
+            flags |= AVL_MX_OUT_LO
+    if res:
+        op.in2, op.in2_ld = ptr, N
+        if res == "split":
+            op.in2_lo = ptr
+        if res == "fp4":
+            op.in2_mx = ptr
+            flags |= AVL_MX_RES_LO
+    op.mx_flags = flags
+    return op
 
 
 def _run_mx(case, cuda_device, batch=0, hw=None):
     import torch
     from test_gpu_ops import _run_plan
-    from vision_semantic_segmentation_amd.network import AVL_MX_IN_LO, AVL_MX_OUT_LO, AVL_MX_RES_LO, mx_bundle_bytes, mx_quant_fp4
-    M, K1, K2, N, form, relu = case
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name, gemm_route, mx_bundle_bytes, mx_quant_fp4
+    M, K1, K2, N, form, relu, kernel = case
     K, Mp = K1 + K2, (M + 255) // 256 * 256
     assert 216 * K <= 2 ** 19                                   # the exactness bound of the module docstring
     seed = 1000 * (M % 97) + K1 + 3 * K2 + N
     _cache_scope((M, K1, K2, N))
     ins = [_act(M, K1, seed)] + ([_act(M, K2, seed + 50)] if K2 else [])
     Wh, Wl, Wh2, w16, wmx, bias = _mx_weights(N, K, seed + 100)
-    nmx = 1 if form in ("plain", "hiq") else 2
-    res = {"plain": None, "hiq": None, "noq": "single", "split": "split", "trunk": "fp4"}[form]
-    o_split = form in ("noq", "split")
-    quant = form in ("split", "hiq", "trunk")
-    lo_half = form in ("split", "trunk")                        # the bundle's lo half is written
+    nmx, res, o_split, quant, lo_half = _mx_form(form)
     # expected accumulator: one exact fp32 product over the concatenated K ranges
     cat = lambda i: torch.cat([t[i] for t in ins], dim=1)       # noqa: E731
     acc = cat(0) @ Wh.t() + cat(1) @ Wl.t() + bias
@@ -234,27 +268,21 @@ def _run_mx(case, cuda_device, batch=0, hw=None):
     out = torch.full((2, Mp, N), 7.0, dtype=torch.float16, device=cuda_device)
     hb = mx_bundle_bytes(Mp, N)
     out_mx = torch.full((2 * hb,), 0xEE, dtype=torch.uint8, device=cuda_device)
-    op = _gemm_op(M if not batch else hw[0] * hw[1], K1, N, Mp, relu, batch, hw)
-    op.in_, op.out, op.weight, op.bias, op.w_rows = dev[0][0].data_ptr(), out[0].data_ptr(), wd.data_ptr(), bd.data_ptr(), N
-    op.w_split, op.w_mx, op.in_mx = 2, wmxd.data_ptr(), dev[0][1].data_ptr()
-    flags = 0
-    if nmx == 2:
-        if form == "trunk" or K2:
-            flags |= AVL_MX_IN_LO
-        else:
-            nan_plane = torch.full((Mp, K1), float("nan"), dtype=torch.float16, device=cuda_device)
-            op.in_lo = nan_plane.data_ptr()                      # switches the second pass on; its values are never read
+    op = mx_shape_op(case, 16, batch, hw)                       # every pointer field the form sets, then the device buffers in them
+    op.in_, op.out, op.weight, op.bias = dev[0][0].data_ptr(), out[0].data_ptr(), wd.data_ptr(), bd.data_ptr()
+    op.w_mx, op.in_mx = wmxd.data_ptr(), dev[0][1].data_ptr()
+    if op.in_lo:
+        nan_plane = torch.full((Mp, K1), float("nan"), dtype=torch.float16, device=cuda_device)
+        op.in_lo = nan_plane.data_ptr()                          # switches the second pass on; its values are never read
     if K2:
-        op.in3, op.in3_mx, op.in3_c, op.in3_ld = dev[1][0].data_ptr(), dev[1][1].data_ptr(), K2, K2
+        op.in3, op.in3_mx = dev[1][0].data_ptr(), dev[1][1].data_ptr()
     if o_split:
         op.out_lo = out[1].data_ptr()
     if quant:
         op.out_mx = out_mx.data_ptr()
-        if form == "trunk":
-            flags |= AVL_MX_OUT_LO
     if res:
         rd = torch.stack([_pad(r_hi, Mp), _pad(r_lo, Mp)]).to(torch.float16).to(cuda_device)
-        op.in2, op.in2_ld = rd[0].data_ptr(), N
+        op.in2 = rd[0].data_ptr()
         if res == "split":
             op.in2_lo = rd[1].data_ptr()
         if res == "fp4":
@@ -262,8 +290,7 @@ def _run_mx(case, cuda_device, batch=0, hw=None):
             q, s = _q4(_pad(r_lo, Mp), "residual lo")
             r_mx = torch.cat([torch.randint(0, 256, (hb,), generator=g, dtype=torch.uint8), q.reshape(-1), s.reshape(-1)]).to(cuda_device)
             op.in2_mx = r_mx.data_ptr()                          # hi half: random bytes the kernel must not read
-            flags |= AVL_MX_RES_LO
-    op.mx_flags = flags
+    assert gemm_kernel_name(gemm_route(op)) == kernel, case     # the kernel this case is here for, on the op that runs
     _run_plan([op])
 
     o = out.cpu()
@@ -291,26 +318,50 @@ def _run_mx(case, cuda_device, batch=0, hw=None):
         assert torch.all(qd[M:] == 0xEE) and torch.all(sd[:, M:] == 0xEE)      # rows past M: plane and every scale slab
 
 
-@pytest.mark.parametrize("case", MX_CASES, ids=lambda c: "%d-%d+%d-%d-%s-%d" % c)
+@pytest.mark.parametrize("case", MX_CASES, ids=lambda c: "%d-%d+%d-%d-%s-%d" % c[:6])
 def test_mx_gemm_exact(case, cuda_device):
     _run_mx(case, cuda_device)
+
+
+BATCH_CASE = (778, 1024, 0, 512, "trunk", True, "k_gemm_mx_pipe<1, 4, 1>")
 
 
 def test_mx_gemm_exact_batch_of_two(cuda_device):
     """batch = 2, 389 pixels per image: the image boundary falls inside the fourth 128-row tile.  Images are packed densely and the
     bundles keep the plain layout (image n at row offset n * 389 of each plane and slab, slab stride = all rows: the BATCH paragraph
     of include/avl_hip.h), so the expected bytes are those of one 778-row GEMM.  t256 is counted on one image: 2 * 2 = 4,
-    128-row tiles, K = 1024: k_gemm_mx_pipe<1, 4, 1>."""
-    _run_mx((778, 1024, 0, 512, "trunk", True), cuda_device, batch=2, hw=(1, 389))
+    128-row tiles, K = 1024."""
+    _run_mx(BATCH_CASE, cuda_device, batch=2, hw=(1, 389))
 
 
 # (M, K, N, nsub, residual, split output, relu)
 SPLIT_CASES = [(M, K, N, nsub, res, osp, (i + nsub) % 2 == 0)
-               # t256 = 11 * 1 = 11 < 192: the 256 x 128 ring k_gemm_ring<f16, 4, 2, 4, 3, NSUB, 1>;
-               # t256 = 24 * 8 = 192: the 256 x 256 ring k_gemm_ring<f16, 2, 4, 8, ., NSUB, 1>.  K = 192: three 64-wide blocks
+               # t256 = 11 * 1 = 11: the 256 x 128 ring; t256 = 24 * 8 = 192: the 256 x 256 ring.  K = 192: three 64-wide blocks
                for M, K, N in ((2600, 192, 256), (5900, 192, 2048))
                for nsub in (2, 3)
                for i, (res, osp) in enumerate(((None, False), (None, True), ("single", True), ("split", False)))]
+
+
+# (N, nsub) -> the kernel a split case runs: <f16, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>
+SPLIT_KERNELS = {(256, 2): "k_gemm_ring<f16, 4, 2, 4, 3, 2, 1, 3, false>", (256, 3): "k_gemm_ring<f16, 4, 2, 4, 3, 3, 1, 3, false>",
+                 (2048, 2): "k_gemm_ring<f16, 2, 4, 8, 3, 2, 1, 2, false>", (2048, 3): "k_gemm_ring<f16, 2, 4, 8, 2, 3, 1, 2, false>"}
+
+
+def split_shape_op(case, ptr):
+    """the split case's op with `ptr` in every pointer field it sets (see mx_shape_op)"""
+    M, K, N, nsub, res, o_split, relu = case
+    op = _gemm_op(M, K, N, (M + 255) // 256 * 256, relu)
+    op.in_ = op.out = op.weight = op.bias = ptr
+    op.w_rows, op.w_split = N, 1
+    if nsub == 3:
+        op.in_lo = ptr
+    if o_split:
+        op.out_lo = ptr
+    if res:
+        op.in2, op.in2_ld = ptr, N
+        if res == "split":
+            op.in2_lo = ptr
+    return op
 
 
 def _split_weights(N, K, nsub, seed, rows):
@@ -326,6 +377,7 @@ def _split_weights(N, K, nsub, seed, rows):
 def test_split_gemm_exact(case, cuda_device):
     import torch
     from test_gpu_ops import _run_plan
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name, gemm_route
     M, K, N, nsub, res, o_split, relu = case
     Mp = (M + 255) // 256 * 256
     seed = 7000 + M + N + nsub
@@ -344,17 +396,18 @@ def test_split_gemm_exact(case, cuda_device):
     planes = torch.stack([_pad(A, Mp), _pad(A_lo, Mp)]).to(torch.float16).to(cuda_device)
     wd, bd = packed.to(cuda_device), bias.to(cuda_device)
     out = torch.full((2, Mp, N), 7.0, dtype=torch.float16, device=cuda_device)
-    op = _gemm_op(M, K, N, Mp, relu)
-    op.in_, op.out, op.weight, op.bias, op.w_rows, op.w_split = planes[0].data_ptr(), out[0].data_ptr(), wd.data_ptr(), bd.data_ptr(), N, 1
+    op = split_shape_op(case, 16)
+    op.in_, op.out, op.weight, op.bias = planes[0].data_ptr(), out[0].data_ptr(), wd.data_ptr(), bd.data_ptr()
     if nsub == 3:
         op.in_lo = planes[1].data_ptr()
     if o_split:
         op.out_lo = out[1].data_ptr()
     if res:
         rd = torch.stack([_pad(r_hi, Mp), _pad(r_lo, Mp)]).to(torch.float16).to(cuda_device)
-        op.in2, op.in2_ld = rd[0].data_ptr(), N
+        op.in2 = rd[0].data_ptr()
         if res == "split":
             op.in2_lo = rd[1].data_ptr()
+    assert gemm_kernel_name(gemm_route(op)) == SPLIT_KERNELS[(N, nsub)], case
     _run_plan([op])
     o = out.cpu()
     assert _same_values(o[0, :M], hi), "hi plane: %d of %d values differ" % (int((o[0, :M] != hi).sum()), hi.numel())
@@ -368,10 +421,11 @@ def test_split_gemm_exact(case, cuda_device):
 
 @pytest.mark.parametrize("M", [777, 300])
 def test_split_classifier_exact(M, cuda_device):
-    """The classifier form: N = 19, fp32 output, nsub 3, in the small-N kernel k_gemm<f16, 4, 1> (out_c <= 64).  Exact in fp32; the
+    """The classifier form: N = 19, fp32 output, nsub 3, in the small-N kernel (asserted below).  Exact in fp32; the
     45 weight rows past N hold values and reach nothing; out_ld = 19, so a stray column would land in the next row."""
     import torch
     from test_gpu_ops import _run_plan
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name, gemm_route
     K, N, rows = 256, 19, 64
     Mp = (M + 255) // 256 * 256
     seed = 9000 + M
@@ -387,6 +441,7 @@ def test_split_classifier_exact(M, cuda_device):
     op = _gemm_op(M, K, N, Mp, False)
     op.in_, op.in_lo, op.out, op.weight, op.bias = planes[0].data_ptr(), planes[1].data_ptr(), out.data_ptr(), wd.data_ptr(), bd.data_ptr()
     op.w_rows, op.w_split, op.out_f32 = rows, 1, 1
+    assert gemm_kernel_name(gemm_route(op)) == "k_gemm<f16, 4, 1>"
     _run_plan([op])
     o = out.cpu()
     assert torch.equal(o[:M].double(), want), "%d logits differ" % int((o[:M].double() != want).sum())

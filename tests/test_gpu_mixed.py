@@ -633,16 +633,51 @@ def _unbundle_rows(buf, rows, c, half, r0, r1):
     return mx_dequant_fp4(q[r0:r1], s[:, r0:r1])
 
 
-@pytest.mark.parametrize("case", [  # (M, K, N, A split, residual split, out split, quantise output, relu)
-    # t256 = ceil(M / 256) * N / 256; launch_ring_mx takes 128-row tiles iff t256 < 192 or 256 < t256 < 384, 256-row tiles otherwise.  Every
-    # case that writes out_mx runs 128-row tiles; the quantising epilogue on 256-row tiles is checked in test_gpu_gemm_exact.py
+def _runs(op, kernel):
+    """the op runs the kernel its case is here for (asked of the library, avl_seg_gemm_route, for the very op)"""
+    from vision_semantic_segmentation_amd.network import gemm_kernel_name, gemm_route
+    assert gemm_kernel_name(gemm_route(op)) == kernel
+
+
+# The kernel each MX case runs: k_gemm_ring_mx<IO, MI> or k_gemm_mx_pipe<IO, MI, LATE>, IO = 1 with out_mx, MI = 4: 128-row tiles,
+# 8: 256-row tiles (the rule: avl_seg_gemm_route's comment in include/avl_hip.h; t256 in the case comments = ceil(M / 256) * N / 256)
+MX_GEMM_KERNELS = {
+    (2600, 256, 512, False, None, False, False, True): "k_gemm_ring_mx<0, 4>",
+    (2600, 256, 512, True, None, True, True, True): "k_gemm_ring_mx<1, 4>",
+    (17000, 512, 1024, False, True, True, True, True): "k_gemm_ring_mx<1, 4>",
+    (34000, 512, 256, True, None, False, False, True): "k_gemm_ring_mx<0, 4>",
+    (300, 2048, 2048, True, False, True, True, False): "k_gemm_mx_pipe<1, 4, 1>",
+    (9000, 512, 1024, "fp4", "fp4", "fp4", True, True): "k_gemm_ring_mx<1, 4>",
+    (17000, 1024, 1024, "fp4", "fp4", "fp4", True, True): "k_gemm_mx_pipe<1, 4, 1>",
+    (34000, 1024, 256, True, None, False, False, True): "k_gemm_mx_pipe<0, 4, 1>",
+    (9000, 1280, 512, False, True, True, True, True): "k_gemm_mx_pipe<1, 4, 1>",
+    (12100, 512, 1024, False, None, False, False, True): "k_gemm_ring_mx<0, 8>",
+    (12100, 1024, 1024, True, None, True, False, True): "k_gemm_mx_pipe<0, 8, 0>",
+}
+MX_LOAD_KERNELS = {
+    (256 * 300, 1024, 512, 2, 0): "k_gemm_mx_pipe<1, 8, 0>",
+    (256 * 140 + 77, 1024, 256, 1, 0): "k_gemm_mx_pipe<1, 4, 1>",
+    (256 * 180, 512, 512, 2, 1024): "k_gemm_mx_pipe<1, 4, 1>",
+    (256 * 140, 1024, 256, 2, 512): "k_gemm_mx_pipe<1, 4, 1>",
+    (256 * 300, 512, 512, 2, 0): "k_gemm_ring_mx<1, 8>",
+}
+MX_TWO_INPUT_KERNELS = {
+    (9000, 512, 256, 1024): "k_gemm_ring_mx<1, 4>",
+    (17000, 512, 1024, 1024): "k_gemm_mx_pipe<1, 4, 1>",
+    (12000, 1024, 512, 256): "k_gemm_mx_pipe<1, 4, 1>",
+    (9000, 256, 1024, 512): "k_gemm_mx_pipe<1, 4, 1>",
+}
+
+
+@pytest.mark.parametrize("case", [  # (M, K, N, A split, residual split, out split, quantise output, relu); the kernels: MX_GEMM_KERNELS
+    # Every case that writes out_mx runs 128-row tiles; the quantising epilogue on 256-row tiles is checked in test_gpu_gemm_exact.py
     (2600, 256, 512, False, None, False, False, True),        # t256 = 22: 128-row tiles
     (2600, 256, 512, True, None, True, True, True),           # t256 = 22: 128-row tiles
     (17000, 512, 1024, False, True, True, True, True),        # conv3-like: split residual and output, FP4 copy of the output (t256 = 268: 128-row tiles)
     (34000, 512, 256, True, None, False, False, True),        # conv1-like: both corrections (t256 = 133: 128-row tiles, 266 of them)
     (300, 2048, 2048, True, False, True, True, False),        # fewer rows than one 256-row tile, single-plane residual (t256 = 16: 128-row tiles)
     (9000, 512, 1024, "fp4", "fp4", "fp4", True, True),       # the trunk form: every lo part only as FP4 (mx_flags) (t256 = 144: 128-row tiles)
-    # K >= 1024 runs the software-pipelined stream (k_gemm_mx_pipe), K < 1024 the two-barrier kernel (k_gemm_ring_mx): the same forms again
+    # the same forms again in the software-pipelined stream (k_gemm_mx_pipe; above: the two-barrier kernel k_gemm_ring_mx, but for K = 2048)
     (17000, 1024, 1024, "fp4", "fp4", "fp4", True, True),     # trunk form, more tiles than CUs (t256 = 268: 128-row tiles, 532 of them)
     (34000, 1024, 256, True, None, False, False, True),       # both corrections (t256 = 133: 128-row tiles)
     (9000, 1280, 512, False, True, True, True, True),         # odd number of K macro-blocks, split residual and output (t256 = 72: 128-row tiles)
@@ -707,6 +742,7 @@ def test_mx_gemm(case, cuda_device):
         from vision_semantic_segmentation_amd.network import AVL_MX_IN_LO, AVL_MX_OUT_LO, AVL_MX_RES_LO
         r_mx = _bundle(r_hi, r_lo, Mp).to(cuda_device)
         op.in2_mx, op.mx_flags = r_mx.data_ptr(), AVL_MX_IN_LO | AVL_MX_RES_LO | AVL_MX_OUT_LO
+    _runs(op, MX_GEMM_KERNELS[case])
     _run_plan([op])
     got = out[0, :M].cpu().double() + (out[1, :M].cpu().double() if o_split else 0)
     if fp4_only:
@@ -753,15 +789,15 @@ def test_mx_gemm(case, cuda_device):
 @pytest.mark.parametrize("shape", [  # (M, K, N, correction passes, K of a second input appended along K or 0)
     # (round 5: sizes cut to ~40 % -- the host-side FP4 packing of the operands was most of this test's 85 s; every case still gives
     # each CU several tiles)
-    # t256 = ceil(M / 256) * N / 256: 128-row tiles iff t256 < 192 or 256 < t256 < 384
+    # the kernels: MX_LOAD_KERNELS
     (256 * 300, 1024, 512, 2, 0),            # t256 = 600: 256-row tiles, 2.3 tiles per CU
-    (256 * 140 + 77, 1024, 256, 1, 0),       # t256 = 141: 128-row tiles (k_gemm_mx_pipe<., 4, ...>), weights-only correction, ragged last tile
+    (256 * 140 + 77, 1024, 256, 1, 0),       # t256 = 141: 128-row tiles, weights-only correction, ragged last tile
     (256 * 180, 512, 512, 2, 1024),          # conv3 + downsample form: the stream switches inputs at K macro-block 2 of 6 (set_input); t256 = 360: 128-row tiles
     (256 * 140, 1024, 256, 2, 512),          # the same at t256 = 140: 128-row tiles as well
-    (256 * 300, 512, 512, 2, 0),             # K < 1024: the two-barrier kernel k_gemm_ring_mx (kept: it runs the short-K layers); t256 = 600: 256-row tiles
+    (256 * 300, 512, 512, 2, 0),             # K = 512: the two-barrier kernel k_gemm_ring_mx (kept: it runs the short-K layers); t256 = 600: 256-row tiles
 ])
 def test_mx_gemm_repeats_under_load(shape, cuda_device):
-    """Race screen for the software-pipelined MX GEMM (k_gemm_mx_pipe, every case with K >= 1024: LDS slots re-filled by inline-asm
+    """Race screen for the software-pipelined MX GEMM (k_gemm_mx_pipe, every case but the last: LDS slots re-filled by inline-asm
     LDS-DMA behind a barrier that sits in the middle of the MFMA stream, fragments read ahead across it): conv3-like shapes with
     several tiles per CU, 256- and 128-row tiles, one and two correction passes, one and two inputs along K (no unit
     case used to drive the pipe kernel's input switch), FP4 residual and output, launched back to back with copies in between,
@@ -802,6 +838,7 @@ def test_mx_gemm_repeats_under_load(shape, cuda_device):
     op.mx_flags = (AVL_MX_IN_LO if nmx == 2 else 0) | AVL_MX_RES_LO | AVL_MX_OUT_LO
     if K2:
         op.in3, op.in3_mx, op.in3_c, op.in3_ld = b_d.data_ptr(), in3_mx.data_ptr(), K2, K2
+    _runs(op, MX_LOAD_KERNELS[shape])
     plan = C.c_void_p()
     _lib.check(_lib.lib().avl_seg_plan_create((AvlSegOp * 1)(op), 1, C.byref(plan)), "avl_seg_plan_create")
     try:
@@ -877,9 +914,10 @@ def test_grouped_conv_writes_the_mx_bundle(case, cuda_device):
 @pytest.mark.parametrize("ks", [(9000, 512, 256, 1024), (17000, 512, 1024, 1024), (12000, 1024, 512, 256), (9000, 256, 1024, 512)])
 def test_mx_gemm_with_a_second_input_along_k(ks, cuda_device):
     """conv3 + stride-1 downsample as ONE MX GEMM: out = relu(W3 . t2 + Wd . x + b3 + bd), both inputs with FP4-only lo parts
-    (in3 / in3_mx of include/avl_hip.h).  Reference: float64 on the operands the kernel is given.  K1 + K2 < 1024 runs
-    k_gemm_ring_mx, the others the software-pipelined k_gemm_mx_pipe.  t256 = ceil(M / 256) * N / 256 = 144, 268, 47, 72: all four run
-    128-row tiles (t256 < 192 or 256 < t256 < 384); the 256-row tiles with a second input are in test_gpu_gemm_exact.py."""
+    (in3 / in3_mx of include/avl_hip.h).  Reference: float64 on the operands the kernel is given.  The first case
+    (K1 + K2 = 768) runs k_gemm_ring_mx, the others the software-pipelined k_gemm_mx_pipe (MX_TWO_INPUT_KERNELS, asserted below).
+    t256 = ceil(M / 256) * N / 256 = 144, 268, 47, 72: all four run 128-row tiles; the 256-row tiles with a second input are in
+    test_gpu_gemm_exact.py."""
     import torch
     from vision_semantic_segmentation_amd import _lib
     from vision_semantic_segmentation_amd.network import (AVL_MX_IN_LO, AVL_MX_OUT_LO, OP_GEMM, AvlSegOp, mx_bundle_bytes, mx_dequant_fp4,
@@ -917,6 +955,7 @@ def test_mx_gemm_with_a_second_input_along_k(ks, cuda_device):
     op.w_split, op.w_mx, op.in_mx, op.out_mx = 2, wmx.data_ptr(), dev[0][1].data_ptr(), out_mx.data_ptr()
     op.in3, op.in3_mx, op.in3_c, op.in3_ld = dev[1][0].data_ptr(), dev[1][1].data_ptr(), K2, K2
     op.mx_flags = AVL_MX_IN_LO | AVL_MX_OUT_LO
+    _runs(op, MX_TWO_INPUT_KERNELS[ks])
     _run_plan([op])
     v_lo = _unbundle(out_mx.cpu(), Mp, N, 1)[2]
     got = out[:M].cpu().double() + v_lo[:M]

@@ -27,21 +27,16 @@ def _plan(c, cuda_device, fill=R.FILL, bias=None, more_ops=()):
     output, bias = another bias vector, more_ops = ops appended to the plan"""
     import torch
     from vision_semantic_segmentation_amd import _lib
-    from vision_semantic_segmentation_amd.network import OP_GEMM, AvlSegOp
+    from vision_semantic_segmentation_amd.network import AvlSegOp, gemm_route
     g = R.geometry(c)
-    prec, nsub = R.MODES[c.mode]
+    nsub = R.MODES[c.mode][1]
     a = R.device_input(c).to(cuda_device)
     w, b = (t.to(cuda_device) for t in R.device_weights(c, bias))
     dt = a.dtype
     out = torch.full((2, g["out_rows"], g["ld1"]), fill, dtype=dt, device=cuda_device)
     out2 = torch.full((2, g["out_rows"], g["ld2"]), fill, dtype=dt, device=cuda_device)
-    op = AvlSegOp()
-    op.kind, op.dtype = OP_GEMM, _lib.AVL_BF16 if prec == "bf16" else _lib.AVL_F16
+    op = R.shape_op(c, 16)
     op.in_, op.weight, op.bias = a[0].data_ptr(), w.data_ptr(), b.data_ptr()
-    op.in_h, op.in_w, op.in_c, op.in_ld, op.in_rows = c.ih, c.iw, R.K, R.K + c.extra, g["in_rows"]
-    op.out_h, op.out_w, op.out_c, op.out_ld, op.out_rows = g["oh"], g["ow"], c.N, g["ld1"], g["out_rows"]
-    op.relu, op.w_rows, op.ksize, op.stride, op.dil, op.groups, op.batch = int(c.relu), g["w_rows"], 1, c.s, 1, 1, c.B
-    op.w_layout, op.w_split = c.wl, int(nsub > 1)
     if nsub == 3:
         op.in_lo = a[1].data_ptr()
     op.out = out[0, :, R.COL:].data_ptr()
@@ -51,6 +46,8 @@ def _plan(c, cuda_device, fill=R.FILL, bias=None, more_ops=()):
         op.out2, op.out2_ld, op.n_split = out2[0].data_ptr(), g["ld2"], c.n_split
         if c.lo2:
             op.out2_lo = out2[1].data_ptr()
+    # the kernel the case is here for, asked of the library for the very op that runs (the table: R.INSTANTIATION)
+    assert R.instantiation(gemm_route(op)) == R.INSTANTIATION[(c.mode, R.claimed_variant(c))], R.case_id(c)
     ops = [op] + list(more_ops)
     plan = C.c_void_p()
     _lib.check(_lib.lib().avl_seg_plan_create((AvlSegOp * len(ops))(*ops), len(ops), C.byref(plan)), "avl_seg_plan_create")
@@ -99,7 +96,7 @@ def _run_case(c, cuda_device, repeats=0):
     del keep
 
 
-# Which instantiation a case reaches: k_gemm_ring<R.INSTANTIATION[(mode, R.variant(case))]>, from ring_variant / launch_gemm:
+# Which instantiation a case reaches: k_gemm_ring<R.INSTANTIATION[(mode, R.variant(case))]> (_plan asserts it on the op that runs):
 #   f16   wl2  k_gemm_ring<f16,  4, 2, 4, 3, 1, 0, 3, true>        f16   wl3  k_gemm_ring<f16,  2, 4, 8, 2, 1, 0, 2, true>
 #   bf16  wl2  k_gemm_ring<bf16, 4, 2, 4, 3, 1, 0, 3, true>        bf16  wl3  k_gemm_ring<bf16, 2, 4, 8, 2, 1, 0, 2, true>
 #   w2    wl2  k_gemm_ring<f16,  4, 2, 4, 3, 2, 1, 3, true>        w2    wl3  k_gemm_ring<f16,  2, 4, 8, 3, 2, 1, 2, true>  (AST = 2)

@@ -557,36 +557,25 @@ __global__ void __launch_bounds__(WM* WN * 64) k_gemm_ring(GemmArgs p, int mtile
     }
 }
 
+// The launchers take tile counts and the grid from the op's route (gemm_route below); a.ntiles is set by launch_gemm.
 template <typename H, int WM, int WN, int MI, int STAGES, int NSUB, int IO, int AST, bool EXT>
-int launch_ring_t(const GemmArgs& a0, int M, hipStream_t s, const RingExt& x) {
+int launch_ring(const GemmArgs& a, const avl_gemm_route& r, hipStream_t s, const RingExt& x) {
     constexpr int BM = WM * MI * 16, BN = WN * 64, LDS = (AST * BM + STAGES * BN) * 128;
     static_assert(LDS <= 160 * 1024, "ring does not fit LDS");
     // set on every launch: the attribute is per device and this may be called from several threads / for several devices
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    GemmArgs a = a0;
-    a.ntiles = (a.N + BN - 1) / BN;
-    const int mtiles = (M + BM - 1) / BM;
-    const int total = mtiles * a.ntiles;
-    const int grid = total < 256 ? total : 256;
-    hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>), dim3(grid), dim3(WM * WN * 64), LDS, s, a, mtiles, x);
+    hipLaunchKernelGGL((k_gemm_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, EXT>), dim3(r.workgroups), dim3(WM * WN * 64), LDS, s, a, r.m_tiles, x);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
 
-// x = NULL: the plain kernel; else the EXT instantiation of the same tile configuration
-template <typename H, int WM, int WN, int MI, int STAGES, int NSUB = 1, int IO = 0, int AST = STAGES>
-int launch_ring(const GemmArgs& a, int M, hipStream_t s, const RingExt* x = nullptr) {
-    if (x) return launch_ring_t<H, WM, WN, MI, STAGES, NSUB, IO, AST, true>(a, M, s, *x);
-    return launch_ring_t<H, WM, WN, MI, STAGES, NSUB, IO, AST, false>(a, M, s, RingExt{});
-}
-
 template <typename T, int WM, int WN>
-int launch_cfg(const GemmArgs& a, int mtiles, hipStream_t s) {
+int launch_plain(const GemmArgs& a, const avl_gemm_route& r, hipStream_t s, const RingExt&) {
     constexpr int LDS = 2 * (WM * 64 + WN * 64) * 128;
     AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm<T, WM, WN>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    hipLaunchKernelGGL((k_gemm<T, WM, WN>), dim3(mtiles * a.ntiles), dim3(WM * WN * 64), LDS, s, a);
+    hipLaunchKernelGGL((k_gemm<T, WM, WN>), dim3(r.workgroups), dim3(WM * WN * 64), LDS, s, a);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
@@ -636,7 +625,7 @@ struct MxArgs {
     int stagger;                // 1: waves 0-3 issue their LDS-DMAs after the first K half of a sub-step
     // k_gemm_mx_pipe reads of the INPUT side only A, A2, Aq[0], Aq2[0], W, Wq[0], K, nmb1, a_srows and w_srows: rows are dense
     // (lda = K1, lda2 = K - K1, a_srows2 = a_srows) and the other planes lie where mx_bundle_at puts them behind Aq[0] / Aq2[0] /
-    // Wq[0]; launch_ring_mx_t checks exactly that.  k_gemm_ring_mx reads every field.
+    // Wq[0]; launch_mx_pipe checks exactly that.  k_gemm_ring_mx reads every field.
 };
 
 // The epilogue of an MX GEMM tile (shared by k_gemm_ring_mx and k_gemm_mx_pipe): bias is in the accumulators; residual (one or two
@@ -1045,7 +1034,7 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     // registers all through the stream: per operand the f16 plane and the BASE of its MX bundle, the allocated rows and the K split.
     // The input rows are dense (row bytes from the operand's own K) and a bundle's planes lie where mx_bundle_at (seg_types.h) puts
     // them -- FP4 hi, scales hi, FP4 lo, scales lo -- so strides and plane distances are a few multiplies at the switch instead of a
-    // dozen more pointers held; launch_ring_mx_t refuses arguments that are laid out otherwise.
+    // dozen more pointers held; launch_mx_pipe refuses arguments that are laid out otherwise.
     unsigned cur_rowb16 = 0;                                     // bytes per row of the f16 input plane (the FP4 plane: a quarter)
     const char *run_a16 = nullptr, *run_aq = nullptr, *run_as = nullptr, *run_w16 = nullptr, *run_wq = nullptr, *run_ws = nullptr;
     unsigned cur_aps = 0;                                        // distance from correction plane 0 to plane 1 of the input
@@ -1328,81 +1317,38 @@ __global__ void __launch_bounds__(512) k_gemm_mx_pipe(MxArgs q, int mtiles) {
     }
 }
 
+template <int MI> constexpr int MX_LDS = 2 * (2 * MI * 16 + 256) * 128 + 2 * 4096;
+
 template <int IO, int MI>
-int launch_ring_mx_t(const MxArgs& a0, hipStream_t s) {
-    constexpr int BM = 2 * MI * 16, LDS = 2 * (BM + 256) * 128 + 2 * 4096;
-    MxArgs a = a0;
-    a.stagger = 1;          // a kernel argument, not a constant: folding it into the kernels changes their code (SGPR spills)
-    a.g.ntiles = a.g.N / 256;
-    const int mtiles = (a.g.M + BM - 1) / BM;
-    const int total = mtiles * a.g.ntiles;
-    const int grid = total < 256 ? total : 256;
-    // Which main loop: the software-pipelined stream wins where the K loop is long (K >= 1024: -2...-9 % on layer4 / layer3 conv1
-    // and conv3 + downsample), the round-2 kernel (two plain barriers per sub-step, a cheaper tile switch) where a tile is only 1-2 K
-    // macro-blocks (K = 256 / 512: layer2, layer3 conv3, the decoder's pointwise convs: the stream is +2...+19 % there);
-    // profiles/r03/gemm_mx_pipe_vs_ring_ab.log.
-    if (a.g.K >= 1024) {
-        // LATE: how many steps behind the event(s) waves 0-3 issue their bursts (waves 4-7: right behind them)
-        constexpr int LATE = MI == 8 ? 0 : 1;
-        // k_gemm_mx_pipe finds strides and planes from each operand's K and the base of its bundle (see its set_input / set_tile)
-        const long long K = a.g.K, K1 = (long long)a.nmb1 * 256, K2 = K - K1;
-        auto bundle_ok = [&](const char* const* bq, const char* const* bs, long long rows, long long ch) {
-            const long long P = mx_plane_bytes(rows, ch), S = mx_scale_bytes(rows, ch);
-            return bs[0] - bq[0] == P && (a.nmx < 2 || (bq[1] - bq[0] == P + S && bs[1] - bq[0] == 2 * P + S)) && 2 * (P + S) < (1LL << 32);
-        };
-        AVL_REQUIRE(a.g.lda == K1 && a.ldaq == K1 / 2 && bundle_ok(a.Aq, a.As, a.a_srows, K1), "MX GEMM: first input is not dense rows + a bundle");
-        AVL_REQUIRE(K2 == 0 || (a.lda2 == K2 && a.ldaq2 == K2 / 2 && a.a_srows2 == a.a_srows && bundle_ok(a.Aq2, a.As2, a.a_srows, K2)),
-                    "MX GEMM: second input is not dense rows + a bundle of the first input's rows");
-        AVL_REQUIRE(bundle_ok(a.Wq, a.Ws, a.w_srows, K), "MX GEMM: weights are not a bundle");
-        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pipe<IO, MI, LATE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        hipLaunchKernelGGL((k_gemm_mx_pipe<IO, MI, LATE>), dim3(grid), dim3(512), LDS, s, a, mtiles);
-    } else {
-        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring_mx<IO, MI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        hipLaunchKernelGGL((k_gemm_ring_mx<IO, MI>), dim3(grid), dim3(512), LDS, s, a, mtiles);
-    }
+int launch_ring_mx(const MxArgs& a, const avl_gemm_route& r, hipStream_t s) {
+    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_ring_mx<IO, MI>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_LDS<MI>));
+    hipLaunchKernelGGL((k_gemm_ring_mx<IO, MI>), dim3(r.workgroups), dim3(512), MX_LDS<MI>, s, a, r.m_tiles);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }
 
-int launch_ring_mx(const MxArgs& a, int m_image, bool quantize_out, hipStream_t s) {
-    // 128-row tiles when 256-row tiles would leave more than a quarter of the 256 CUs idle (or give a ragged second wave); counted on ONE
-    // image's rows (m_image), so that a batch runs the kernel its batch-1 plan runs
-    const long long t256 = (long long)((m_image + 255) / 256) * (a.g.N / 256);
-    const bool small = t256 < 192 || (t256 > 256 && t256 < 384);
-    if (small) return quantize_out ? launch_ring_mx_t<1, 4>(a, s) : launch_ring_mx_t<0, 4>(a, s);
-    return quantize_out ? launch_ring_mx_t<1, 8>(a, s) : launch_ring_mx_t<0, 8>(a, s);
+// LATE: how many steps behind the event(s) waves 0-3 issue their bursts (waves 4-7: right behind them)
+template <int IO, int MI, int LATE>
+int launch_mx_pipe(const MxArgs& a, const avl_gemm_route& r, hipStream_t s) {
+    // k_gemm_mx_pipe finds strides and planes from each operand's K and the base of its bundle (see its set_input / set_tile)
+    const long long K = a.g.K, K1 = (long long)a.nmb1 * 256, K2 = K - K1;
+    auto bundle_ok = [&](const char* const* bq, const char* const* bs, long long rows, long long ch) {
+        const long long P = mx_plane_bytes(rows, ch), S = mx_scale_bytes(rows, ch);
+        return bs[0] - bq[0] == P && (a.nmx < 2 || (bq[1] - bq[0] == P + S && bs[1] - bq[0] == 2 * P + S)) && 2 * (P + S) < (1LL << 32);
+    };
+    AVL_REQUIRE(a.g.lda == K1 && a.ldaq == K1 / 2 && bundle_ok(a.Aq, a.As, a.a_srows, K1), "MX GEMM: first input is not dense rows + a bundle");
+    AVL_REQUIRE(K2 == 0 || (a.lda2 == K2 && a.ldaq2 == K2 / 2 && a.a_srows2 == a.a_srows && bundle_ok(a.Aq2, a.As2, a.a_srows, K2)),
+                "MX GEMM: second input is not dense rows + a bundle of the first input's rows");
+    AVL_REQUIRE(bundle_ok(a.Wq, a.Ws, a.w_srows, K), "MX GEMM: weights are not a bundle");
+    AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_mx_pipe<IO, MI, LATE>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_LDS<MI>));
+    hipLaunchKernelGGL((k_gemm_mx_pipe<IO, MI, LATE>), dim3(r.workgroups), dim3(512), MX_LDS<MI>, s, a, r.m_tiles);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
 }
-
-struct TileCfg { int bm, bn; };
-inline TileCfg pick_tile(const avl_seg_op& op);
-inline bool ring_eligible(const avl_seg_op& op) {
-    const int M = op.out_h * op.out_w * op_batch(op);
-    return is_half(op.dtype) && op.w_layout != 1 && op.out_c > 64 && !op.out_f32 && op.out_c % 128 == 0 && op.in_rows >= (M + 255) / 256 * 256;
-}
-inline TileCfg pick_tile(const avl_seg_op& op) {
-    if (op.out_c <= 64) return {256, 64};
-    return {128, 128};
-}
-// The ring GEMM's tile configuration for a ring_eligible op (the values of w_layout: 2 = 256 x 128, 3 = 256 x 256, 4 = 256 x 128 on four
-// waves).  256 x 256 halves the L2->LDS bytes per flop (the measured limiter) but needs >= ~200 tiles to fill 256 CUs; it is counted on
-// ONE image's rows, so that a batch runs the kernel its batch-1 plan runs.
-// (network.py _emit_conv1_with_low_level mirrors this choice to pick an n_split the op can run with: change both together;
-// tests/test_fused_passes_cpu.py creates the merged op of several plans, so a mismatch fails there.)
-inline int ring_variant(const avl_seg_op& op) {
-    const bool can256 = op.out_c % 256 == 0 && op.w_rows % 256 == 0;
-    const int m_image = op.out_h * op.out_w;
-    int v = op.w_layout;
-    if (v == 0) v = (can256 && ((m_image + 255) / 256) * (op.out_c / 256) >= 192) ? 3 : 2;
-    if (v == 3 && !can256) v = 2;
-    return v;
-}
-inline bool ring_ext(const avl_seg_op& op) { return op.stride > 1 || op.out2 != nullptr || op.out2_lo != nullptr || op.n_split != 0; }
-
-}  // namespace
 
 // A GEMM with a per-image bias runs as one batch-1 GEMM per image: the op of image n (pointers at its first row, the rows that
 // follow it, its bias vector).
-static avl_seg_op gemm_image_op(const avl_seg_op& op, int n) {
+avl_seg_op gemm_image_op(const avl_seg_op& op, int n) {
     avl_seg_op v = op;
     const long long m = (long long)op.out_h * op.out_w * n;
     const int es = elem_size(op.dtype), oes = op.out_f32 ? 4 : es;
@@ -1422,17 +1368,130 @@ static avl_seg_op gemm_image_op(const avl_seg_op& op, int n) {
     return v;
 }
 
+inline bool per_image_launches(const avl_seg_op& op) { return op.bias_per_image && op_batch(op) > 1; }
+
+// Which kernel an op runs, on which tiles and grid: the ONE place that decides it.  validate_gemm and launch_gemm both start here,
+// avl_seg_gemm_route hands it out, and include/avl_hip.h states the rule as a table (keep the two in step).  Why the thresholds:
+//   * tile choices count ONE image's rows, so that a batch runs the kernel its batch-1 plan runs;
+//   * MX: 128-row tiles where 256-row tiles would leave more than a quarter of the 256 CUs idle or give a ragged second wave.  The
+//     software-pipelined stream wins where the K loop is long (K >= 1024: -2...-9 % on layer4 / layer3 conv1 and conv3 + downsample),
+//     the ring kernel (two plain barriers per sub-step, a cheaper tile switch) where a tile is only 1-2 K macro-blocks (K = 256 /
+//     512: layer2, layer3 conv3, the decoder's pointwise convs: the stream is +2...+19 % there); profiles/r03/gemm_mx_pipe_vs_ring_ab.log;
+//   * ring: 256 x 256 halves the L2->LDS bytes per flop (the measured limiter) but needs >= ~200 tiles to fill 256 CUs.
+avl_gemm_route gemm_route(const avl_seg_op& op0) {
+    const avl_seg_op op = per_image_launches(op0) ? gemm_image_op(op0, 0) : op0;
+    avl_gemm_route r;
+    memset(&r, 0, sizeof(r));
+    r.launches = per_image_launches(op0) ? op0.batch : 1;
+    r.ext = op.stride > 1 || op.out2 != nullptr || op.out2_lo != nullptr || op.n_split != 0;
+    const int m_image = op.out_h * op.out_w, M = m_image * op_batch(op), N = op.out_c;
+    const long long t256 = (long long)((m_image + 255) / 256) * (N / 256);
+    const bool can256 = N % 256 == 0 && op.w_rows % 256 == 0;
+    if (op.w_split != 2) r.nsub = op.w_split ? (op.in_lo ? 3 : 2) : 1;      // passes per K block: weights split, input split too
+    if (op.w_split == 2) {
+        const int K = op.in_c + (op.in3 ? op.in3_c : 0);
+        r.kernel = K >= 1024 ? AVL_GEMM_MX_PIPE : AVL_GEMM_RING_MX;
+        r.dtype = AVL_F16;
+        r.io = op.out_mx != nullptr;
+        r.mi = (t256 < 192 || (t256 > 256 && t256 < 384)) ? 4 : 8;
+        r.late = (r.kernel == AVL_GEMM_MX_PIPE && r.mi == 4) ? 1 : 0;
+        r.tile_m = r.mi * 32;
+        r.tile_n = 256;
+    } else if (is_half(op.dtype) && op.w_layout != 1 && N > 64 && !op.out_f32 && N % 128 == 0 && op.in_rows >= (M + 255) / 256 * 256) {
+        r.kernel = AVL_GEMM_RING;
+        r.io = r.nsub > 1;
+        r.dtype = r.nsub > 1 ? AVL_F16 : op.dtype;
+        int v = op.w_layout;        // 0 = by shape, 2 = 256 x 128, 3 = 256 x 256, 4 = 256 x 128 on four waves
+        if (v == 0) v = (can256 && t256 >= 192) ? 3 : 2;
+        if (v == 3) v = can256 ? 3 : 2;
+        if (v == 3) { r.wm = 2; r.wn = 4; r.mi = 8; r.stages = r.nsub == 2 ? 3 : 2; r.ast = 2; }
+        else if (v == 4 && r.nsub == 1) { r.wm = 2; r.wn = 2; r.mi = 8; r.stages = 3; r.ast = 3; }
+        else { r.wm = 4; r.wn = 2; r.mi = 4; r.stages = 3; r.ast = 3; }
+        r.tile_m = r.wm * r.mi * 16;
+        r.tile_n = r.wn * 64;
+    } else {
+        r.kernel = AVL_GEMM_PLAIN;
+        r.dtype = is_half(op.dtype) ? op.dtype : AVL_F32;
+        r.wm = N <= 64 ? 4 : 2;
+        r.wn = N <= 64 ? 1 : 2;
+        r.tile_m = r.wm * 64;
+        r.tile_n = r.wn * 64;
+    }
+    r.m_tiles = (M + r.tile_m - 1) / r.tile_m;
+    r.n_tiles = (N + r.tile_n - 1) / r.tile_n;
+    const long long total = (long long)r.m_tiles * r.n_tiles;
+    r.workgroups = (int)(r.kernel != AVL_GEMM_PLAIN && total > 256 ? 256 : total);
+    return r;
+}
+
+// Every instantiation the library holds, once: the route's kernel, element type and template arguments, and its launcher.  A ring
+// kernel stands with its EXT twin (strided input rows / a second destination), which the four-wave configuration does not have.
+// (The rows' order is the order hipcc lays the kernels out in the code object; it is the one they had before this table existed, so
+// that tools/device_code_diff.py shows the library's device code unmoved, the kernels' places in it included.)
+typedef int (*GemmLauncher)(const GemmArgs&, const avl_gemm_route&, hipStream_t, const RingExt&);
+typedef int (*MxLauncher)(const MxArgs&, const avl_gemm_route&, hipStream_t);
+struct GemmKernel {
+    int kernel, dtype, wm, wn, mi, stages, nsub, io, ast, late;
+    GemmLauncher launch, launch_ext;
+    MxLauncher launch_mx;
+};
+template <typename T> constexpr int DTYPE = std::is_same<T, float>::value ? AVL_F32 : std::is_same<T, bf16>::value ? AVL_BF16 : AVL_F16;
+template <typename H, int WM, int WN, int MI, int STAGES, int NSUB, int IO, int AST, bool TWIN>
+constexpr GemmKernel ring_kernel() {
+    GemmLauncher ext = nullptr;
+    if constexpr (TWIN) ext = &launch_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, true>;
+    return {AVL_GEMM_RING, DTYPE<H>, WM, WN, MI, STAGES, NSUB, IO, AST, 0, &launch_ring<H, WM, WN, MI, STAGES, NSUB, IO, AST, false>, ext, nullptr};
+}
+template <typename T, int WM, int WN>
+constexpr GemmKernel plain_kernel() { return {AVL_GEMM_PLAIN, DTYPE<T>, WM, WN, 0, 0, 0, 0, 0, 0, &launch_plain<T, WM, WN>, nullptr, nullptr}; }
+template <int IO, int MI>
+constexpr GemmKernel ring_mx_kernel() { return {AVL_GEMM_RING_MX, AVL_F16, 0, 0, MI, 0, 0, IO, 0, 0, nullptr, nullptr, &launch_ring_mx<IO, MI>}; }
+template <int IO, int MI, int LATE>
+constexpr GemmKernel mx_pipe_kernel() { return {AVL_GEMM_MX_PIPE, AVL_F16, 0, 0, MI, 0, 0, IO, 0, LATE, nullptr, nullptr, &launch_mx_pipe<IO, MI, LATE>}; }
+
+const GemmKernel GEMM_KERNELS[] = {
+    //             IO MI LATE                      IO MI
+    mx_pipe_kernel<1, 4, 1>(), ring_mx_kernel<1, 4>(), mx_pipe_kernel<0, 4, 1>(), ring_mx_kernel<0, 4>(),       // 128 x 256
+    mx_pipe_kernel<1, 8, 0>(), ring_mx_kernel<1, 8>(), mx_pipe_kernel<0, 8, 0>(), ring_mx_kernel<0, 8>(),       // 256 x 256
+    //          T     WM WN MI STAGES NSUB IO AST  EXT twin
+    ring_kernel<f16,  2, 4, 8, 3,     2,   1, 2,   true>(),     // split operands: 256 x 256 and 256 x 128, two passes, then three
+    ring_kernel<f16,  4, 2, 4, 3,     2,   1, 3,   true>(),
+    ring_kernel<f16,  2, 4, 8, 2,     3,   1, 2,   true>(),
+    ring_kernel<f16,  4, 2, 4, 3,     3,   1, 3,   true>(),
+    ring_kernel<bf16, 2, 4, 8, 2,     1,   0, 2,   true>(),     // one plane: 256 x 256
+    ring_kernel<f16,  2, 4, 8, 2,     1,   0, 2,   true>(),
+    ring_kernel<bf16, 2, 2, 8, 3,     1,   0, 3,   false>(),    // 256 x 128 on four waves
+    ring_kernel<f16,  2, 2, 8, 3,     1,   0, 3,   false>(),
+    ring_kernel<bf16, 4, 2, 4, 3,     1,   0, 3,   true>(),     // 256 x 128
+    ring_kernel<f16,  4, 2, 4, 3,     1,   0, 3,   true>(),
+    //           T      WM WN: 256 x 64, 128 x 128
+    plain_kernel<bf16,  4, 1>(), plain_kernel<bf16,  2, 2>(),
+    plain_kernel<f16,   4, 1>(), plain_kernel<f16,   2, 2>(),
+    plain_kernel<float, 4, 1>(), plain_kernel<float, 2, 2>(),
+};
+
+const GemmKernel* find_kernel(const avl_gemm_route& r) {
+    for (const GemmKernel& k : GEMM_KERNELS)
+        if (k.kernel == r.kernel && k.dtype == r.dtype && k.wm == r.wm && k.wn == r.wn && k.mi == r.mi && k.stages == r.stages &&
+            (k.kernel != AVL_GEMM_RING || k.nsub == r.nsub) && k.io == r.io && k.ast == r.ast && k.late == r.late && (!r.ext || k.launch_ext))
+            return &k;
+    return nullptr;
+}
+
+}  // namespace
+
 int validate_gemm(const avl_seg_op& op) {
     const int es = elem_size(op.dtype);
+    const avl_gemm_route route = gemm_route(op);
     AVL_REQUIRE(is_half(op.dtype) || op.dtype == AVL_F32, "GEMM dtype %d", op.dtype);
     AVL_REQUIRE(op.in && op.out && op.weight && op.bias, "GEMM has NULL buffers");
     // (checked here, not only at launch: a plan that cannot run is refused when it is created)
     AVL_REQUIRE(op.w_layout >= 0 && op.w_layout <= 4, "GEMM w_layout %d (0 = by shape, 1 .. 4 = a forced 16-bit tile configuration)", op.w_layout);
     AVL_REQUIRE(op.w_layout == 0 || is_half(op.dtype), "GEMM w_layout %d forces a tile configuration of the 16-bit kernels: dtype %d", op.w_layout, op.dtype);
-    if (op.bias_per_image && op_batch(op) > 1) {
+    if (per_image_launches(op)) {
         AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: a per-image bias is not supported by the MX GEMM");
         // (gemm_image_op moves neither out2 nor a strided input to image n)
-        AVL_REQUIRE(!ring_ext(op), "GEMM: a per-image bias goes with neither strided input rows (stride %d) nor a second destination", op.stride);
+        AVL_REQUIRE(!route.ext, "GEMM: a per-image bias goes with neither strided input rows (stride %d) nor a second destination", op.stride);
         for (int n = 0; n < op.batch; ++n) {
             const avl_seg_op v = gemm_image_op(op, n);
             AVL_REQUIRE(v.in_rows >= (op.out_h * op.out_w + 255) / 256 * 256,
@@ -1444,11 +1503,11 @@ int validate_gemm(const avl_seg_op& op) {
     }
     const int M = op.out_h * op.out_w * op_batch(op), K = op.in_c, N = op.out_c;      // a batch is one long run of rows
     AVL_REQUIRE(M > 0 && N > 0 && K > 0, "GEMM M/N/K = %d/%d/%d", M, N, K);
-    if (ring_ext(op)) {     // strided input rows / a second destination: the ring GEMM of the 16-bit types only
+    if (route.ext) {        // strided input rows / a second destination: the ring GEMM of the 16-bit types only
         AVL_REQUIRE(op.w_split != 2 && !op.in3, "GEMM: the MX GEMM takes neither strided input rows (stride %d) nor a second destination", op.stride);
         AVL_REQUIRE(is_half(op.dtype) && !op.out_f32, "GEMM: strided input rows (stride %d) / a second destination need a 16-bit GEMM (dtype %d, out_f32 %d)",
                     op.stride, op.dtype, op.out_f32);
-        AVL_REQUIRE(ring_eligible(op) && op.w_layout != 4, "GEMM: strided input rows (stride %d) / a second destination need the ring GEMM "
+        AVL_REQUIRE(route.kernel == AVL_GEMM_RING && op.w_layout != 4, "GEMM: strided input rows (stride %d) / a second destination need the ring GEMM "
                     "(N %% 128 == 0, N > 64, rows padded to 256, w_layout 0, 2 or 3): N %d, in_rows %d, w_layout %d", op.stride, N, op.in_rows, op.w_layout);
     }
     if (op.stride > 1) {
@@ -1462,7 +1521,7 @@ int validate_gemm(const avl_seg_op& op) {
     AVL_REQUIRE(op.in_ld >= K && (op.in_ld * es) % 16 == 0, "GEMM in_ld %d", op.in_ld);
     int n1 = N;             // columns that go to `out`
     if (op.out2 || op.out2_lo || op.n_split) {
-        const int bn = ring_variant(op) == 3 ? 256 : 128;
+        const int bn = route.tile_n;
         AVL_REQUIRE(op.out2, "GEMM: n_split %d / out2_lo without a second destination (out2 is NULL)", op.n_split);
         AVL_REQUIRE(op.n_split > 0 && op.n_split < N && op.n_split % bn == 0,
                     "GEMM: n_split %d must be a multiple of the N tile (%d) inside (0, N = %d)", op.n_split, bn, N);
@@ -1473,16 +1532,15 @@ int validate_gemm(const avl_seg_op& op) {
         n1 = op.n_split;
     }
     AVL_REQUIRE(op.out_ld >= n1, "GEMM out_ld %d < N %d", op.out_ld, n1);
-    const TileCfg t = pick_tile(op);
-    const int mtiles = (M + t.bm - 1) / t.bm, ntiles = (N + t.bn - 1) / t.bn;
-    AVL_REQUIRE(op.in_rows >= mtiles * t.bm, "GEMM reads %d rows, input has %d allocated", mtiles * t.bm, op.in_rows);
-    AVL_REQUIRE(op.w_rows >= ntiles * t.bn, "GEMM reads %d weight rows, %d allocated", ntiles * t.bn, op.w_rows);
+    const int rows_read = route.m_tiles * route.tile_m, w_rows_read = route.n_tiles * route.tile_n;
+    AVL_REQUIRE(op.in_rows >= rows_read, "GEMM reads %d rows, input has %d allocated", rows_read, op.in_rows);
+    AVL_REQUIRE(op.w_rows >= w_rows_read, "GEMM reads %d weight rows, %d allocated", w_rows_read, op.w_rows);
     AVL_REQUIRE(op.out_rows >= M, "GEMM writes %d rows, output has %d", M, op.out_rows);
     if (!op.out_f32) AVL_REQUIRE((op.out_ld * es) % 16 == 0 && N % 16 == 0, "GEMM out_ld %d / N %d not 16-aligned", op.out_ld, N);
     if (op.in2) AVL_REQUIRE(op.in2_ld >= N && (op.in2_ld * es) % 16 == 0, "GEMM residual ld %d", op.in2_ld);
     if (op.out_f32) AVL_REQUIRE(!op.out_lo, "GEMM: an fp32 output has no low plane");
     if (op.out_f32 && op.out_mx)      // the fused arg-max (labels through out_mx): the small-N kernel, plain logits
-        AVL_REQUIRE(N <= 32 && !op.in2 && !op.relu && op.w_split != 2 && t.bn == 64 && !ring_eligible(op),
+        AVL_REQUIRE(N <= 32 && !op.in2 && !op.relu && route.kernel == AVL_GEMM_PLAIN && route.tile_n == 64,
                     "GEMM: an arg-max output (out_f32 with out_mx = uint8 labels[rows]) needs N <= 32, no residual, no ReLU (N %d)", N);
     if (op.w_split == 2) {
         AVL_REQUIRE(op.dtype == AVL_F16 && op.w_mx && op.in_mx, "MX GEMM needs AVL_F16 activations and the w_mx / in_mx bundles");
@@ -1512,7 +1570,7 @@ int validate_gemm(const avl_seg_op& op) {
         AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.in_lo) | reinterpret_cast<uintptr_t>(op.in2_lo) | reinterpret_cast<uintptr_t>(op.out_lo)) % 16 == 0,
                     "GEMM low planes must be 16-byte aligned");
         if (op.in2_lo || op.out_lo)
-            AVL_REQUIRE(ring_eligible(op), "split residual / output need the ring GEMM (N %% 128 == 0, 16-bit output, rows padded to 256)");
+            AVL_REQUIRE(route.kernel == AVL_GEMM_RING, "split residual / output need the ring GEMM (N %% 128 == 0, 16-bit output, rows padded to 256)");
     }
     AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.in) | reinterpret_cast<uintptr_t>(op.weight) | reinterpret_cast<uintptr_t>(op.out) |
                  reinterpret_cast<uintptr_t>(op.bias) | reinterpret_cast<uintptr_t>(op.in2)) % 16 == 0,
@@ -1521,27 +1579,31 @@ int validate_gemm(const avl_seg_op& op) {
 }
 
 int launch_gemm(const avl_seg_op& op, hipStream_t s) {
-    if (op.bias_per_image && op_batch(op) > 1) {
+    if (per_image_launches(op)) {
         for (int n = 0; n < op.batch; ++n) {
             const int rc = launch_gemm(gemm_image_op(op, n), s);
             if (rc) return rc;
         }
         return AVL_OK;
     }
-    AVL_REQUIRE(op.w_layout != 5, "GEMM w_layout 5 is not supported");
+    const avl_gemm_route route = gemm_route(op);
+    const GemmKernel* kernel = find_kernel(route);
+    if (!kernel) return set_error(AVL_E_UNSUPPORTED, "GEMM: the library holds no kernel for this op's route (kernel %d, dtype %d, w_layout %d, ext %d)",
+                                  route.kernel, route.dtype, op.w_layout, route.ext);
     GemmArgs a;
     a.A = op.in; a.W = op.weight; a.bias = op.bias; a.R = op.in2; a.C = op.out;
     a.lda = op.in_ld; a.ldr = op.in2_ld; a.ldc = op.out_ld;
     a.M = op.out_h * op.out_w * op_batch(op); a.N = op.out_c; a.K = op.in_c;
     a.relu = op.relu; a.out_f32 = op.out_f32;
-    const int m_image = op.out_h * op.out_w;      // tile choices look at one image: a batch runs what its batch-1 plan runs
-    if (op.w_split == 2) {
+    a.ntiles = route.n_tiles;
+    if (kernel->launch_mx) {
         MxArgs mx;
         memset(&mx, 0, sizeof(mx));
         a.nsub = 1;
         a.a_lo_delta = 0;
         a.R_lo = op.in2_lo; a.C_lo = op.out_lo;
         mx.g = a;
+        mx.stagger = 1;     // a kernel argument, not a constant: folding it into the kernels changes their code (SGPR spills)
         // (with a second input appended along K: K1 = op.in_c comes from `in`, the rest from in3; weights span the whole K)
         const long long K1 = op.in_c, K2 = op.in3 ? op.in3_c : 0;
         const auto x = mx_bundle(op.in_mx, op.in_rows, K1);
@@ -1572,49 +1634,25 @@ int launch_gemm(const avl_seg_op& op, hipStream_t s) {
             if (op.out_lo || (op.mx_flags & AVL_MX_OUT_LO)) { mx.Cq[1] = c.q[1]; mx.Cs[1] = c.s[1]; }
             mx.ldcq = c.ldq; mx.c_srows = c.srows;
         }
-        return launch_ring_mx(mx, m_image, op.out_mx != nullptr, s);
+        return kernel->launch_mx(mx, route, s);
     }
-    a.nsub = op.w_split ? (op.in_lo ? 3 : 2) : 1;
+    a.nsub = route.nsub;
     a.a_lo_delta = op.in_lo ? static_cast<const char*>(op.in_lo) - static_cast<const char*>(op.in) : 0;
     a.R_lo = op.in2_lo;
     a.C_lo = op.out_f32 ? op.out_mx : op.out_lo;      // (out_f32 ops have neither a low plane nor an MX bundle: out_mx carries the label map)
-    const TileCfg t = pick_tile(op);
-    const int mtiles = (a.M + t.bm - 1) / t.bm;
-    a.ntiles = (a.N + t.bn - 1) / t.bn;
-    // 16-bit variants.  w_layout: 0 = pick by shape, 1 = v1 (128x128, 2 LDS buffers, 2 workgroups/CU),
-    // 2 = ring 256x128 x3 stages, 3 = ring 256x256 x2 stages, 4 = ring 256x128 (4 waves) x3 stages.
-    // 256x256 halves the L2->LDS bytes per flop (the measured limiter) but needs >= ~200 tiles to fill 256 CUs.
-    if (ring_eligible(op)) {
-        const int v = ring_variant(op);
-        // strided input rows and / or a second destination: the EXT instantiation of the same configuration (validate_gemm: not with v == 4)
-        RingExt ext;
-        memset(&ext, 0, sizeof(ext));
-        if (op.stride > 1) { ext.s = op.stride; ext.ow = op.out_w; ext.ohw = m_image; ext.w = op.in_w; ext.hw = op.in_h * op.in_w; }
-        if (op.out2) { ext.n_split = op.n_split; ext.ldc2 = op.out2_ld; ext.C2 = op.out2; ext.C2_lo = op.out2_lo; }
-        const RingExt* x = ring_ext(op) ? &ext : nullptr;
-        if (a.nsub == 2) {
-            if (v == 3) return launch_ring<f16, 2, 4, 8, 3, 2, 1, 2>(a, a.M, s, x);
-            return launch_ring<f16, 4, 2, 4, 3, 2, 1>(a, a.M, s, x);
-        }
-        if (a.nsub == 3) {
-            if (v == 3) return launch_ring<f16, 2, 4, 8, 2, 3, 1>(a, a.M, s, x);
-            return launch_ring<f16, 4, 2, 4, 3, 3, 1>(a, a.M, s, x);
-        }
-        const bool bf = op.dtype == AVL_BF16;
-        if (v == 3) return bf ? launch_ring<bf16, 2, 4, 8, 2>(a, a.M, s, x) : launch_ring<f16, 2, 4, 8, 2>(a, a.M, s, x);
-        if (v == 4) return bf ? launch_ring_t<bf16, 2, 2, 8, 3, 1, 0, 3, false>(a, a.M, s, ext) : launch_ring_t<f16, 2, 2, 8, 3, 1, 0, 3, false>(a, a.M, s, ext);
-        return bf ? launch_ring<bf16, 4, 2, 4, 3>(a, a.M, s, x) : launch_ring<f16, 4, 2, 4, 3>(a, a.M, s, x);
-    }
-    if (op.dtype == AVL_BF16) {
-        if (t.bn == 64) return launch_cfg<bf16, 4, 1>(a, mtiles, s);
-        return launch_cfg<bf16, 2, 2>(a, mtiles, s);
-    }
-    if (op.dtype == AVL_F16) {
-        if (t.bn == 64) return launch_cfg<f16, 4, 1>(a, mtiles, s);
-        return launch_cfg<f16, 2, 2>(a, mtiles, s);
-    }
-    if (t.bn == 64) return launch_cfg<float, 4, 1>(a, mtiles, s);
-    return launch_cfg<float, 2, 2>(a, mtiles, s);
+    // strided input rows and / or a second destination: the EXT twin of the same ring configuration
+    RingExt ext;
+    memset(&ext, 0, sizeof(ext));
+    if (op.stride > 1) { ext.s = op.stride; ext.ow = op.out_w; ext.ohw = op.out_h * op.out_w; ext.w = op.in_w; ext.hw = op.in_h * op.in_w; }
+    if (op.out2) { ext.n_split = op.n_split; ext.ldc2 = op.out2_ld; ext.C2 = op.out2; ext.C2_lo = op.out2_lo; }
+    return (route.ext ? kernel->launch_ext : kernel->launch)(a, route, s, ext);
 }
 
 }  // namespace avl
+
+extern "C" int avl_seg_gemm_route(const avl_seg_op* op, avl_gemm_route* out) {
+    AVL_REQUIRE(op && out, "avl_seg_gemm_route: NULL argument");
+    AVL_REQUIRE(op->kind == AVL_OP_GEMM, "avl_seg_gemm_route: op kind %d is not AVL_OP_GEMM", op->kind);
+    *out = avl::gemm_route(*op);
+    return AVL_OK;
+}

@@ -62,8 +62,39 @@ INPUT_FORMATS = {"u8_hwc": AVL_IN_U8_HWC, "f32_nchw": AVL_IN_F32_CHW}
 AVL_MX_IN_LO, AVL_MX_RES_LO, AVL_MX_OUT_LO = 1, 2, 4
 
 
+GEMM_KERNELS = ("k_gemm", "k_gemm_ring", "k_gemm_ring_mx", "k_gemm_mx_pipe")      # AVL_GEMM_* of include/avl_hip.h
+
+
+class AvlGemmRoute(C.Structure):
+    """struct avl_gemm_route of include/avl_hip.h"""
+    _fields_ = [(name, C.c_int32) for name in (
+        "kernel", "dtype", "tile_m", "tile_n", "wm", "wn", "mi", "stages", "nsub", "io", "ast", "ext", "late",
+        "launches", "m_tiles", "n_tiles", "workgroups")]
+
+
+def gemm_route(op):
+    """Which kernel the library runs an AVL_OP_GEMM op with (avl_seg_gemm_route: host only, the op's buffers need not exist) ->
+    the fields of avl_gemm_route by name, `kernel` as the kernel's name"""
+    r = AvlGemmRoute()
+    _lib.check(_lib.lib().avl_seg_gemm_route(C.byref(op), C.byref(r)), "avl_seg_gemm_route")
+    d = {name: getattr(r, name) for name, _ in AvlGemmRoute._fields_}
+    d["kernel"] = GEMM_KERNELS[r.kernel]
+    return d
+
+
+def gemm_kernel_name(route):
+    """a gemm_route() result as the instantiation's name in csrc/seg_gemm.hip, e.g. "k_gemm_mx_pipe<1, 8, 0>" """
+    t = {_lib.AVL_F32: "float", _lib.AVL_BF16: "bf16", _lib.AVL_F16: "f16"}[route["dtype"]]
+    args = {"k_gemm": [t, "wm", "wn"],
+            "k_gemm_ring": [t, "wm", "wn", "mi", "stages", "nsub", "io", "ast", "true" if route["ext"] else "false"],
+            "k_gemm_ring_mx": ["io", "mi"],
+            "k_gemm_mx_pipe": ["io", "mi", "late"]}[route["kernel"]]
+    return "%s<%s>" % (route["kernel"], ", ".join(str(route.get(a, a)) for a in args))
+
+
 _vp, _i = C.c_void_p, C.c_int
 _lib._register_seg({
+    "avl_seg_gemm_route": (_i, [C.POINTER(AvlSegOp), C.POINTER(AvlGemmRoute)]),
     "avl_seg_plan_create": (_i, [C.POINTER(AvlSegOp), _i, C.POINTER(C.c_void_p)]),
     "avl_seg_plan_destroy": (None, [_vp]),
     "avl_seg_plan_run": (_i, [_vp, _vp]),
@@ -1140,10 +1171,11 @@ class SegNet(object):
         wl, bl, low_out = self._low_level_conv(st)
         t1_c = w1.shape[0]
         n = low_out + t1_c
-        # the N tile the library runs the merged op with: n_split must be a multiple of it.  This MIRRORS ring_variant() of seg_gemm.hip (256 x 256
-        # tiles where N % 256 == 0 and one image gives >= 192 of them, else 256 x 128) -- change both together; a mismatch makes
-        # avl_seg_plan_create refuse the op with an n_split message (tests/test_fused_passes_cpu.py builds these plans)
-        bn = 256 if (n % 256 == 0 and ((low_hw[0] * low_hw[1] + 255) // 256) * (n // 256) >= 192) else 128
+        # the N tile the library would run the merged op with (n_split must be a multiple of it): asked of the library, for an op of the
+        # merged op's shape with a second destination (the buffers do not exist yet: the query looks at no memory)
+        probe = AvlSegOp(kind=OP_GEMM, dtype=self.avl_dtype, batch=self.batch, out_h=low_hw[0], out_w=low_hw[1], out_c=n, w_rows=_round_up(n, 256),
+                         in_rows=x.hi.shape[0], w_layout=0, w_split=int(self.mixed), in_lo=self._lo(x) if self.mixed else 0, out2=x.hi.data_ptr())
+        bn = gemm_route(probe)["tile_n"]
         same_passes = not self.mixed or x.lo is None or self.mixed_conv1_split       # low_level_conv reads the lo plane whenever there is one
         if not (low_hw == blk.hw and low_c == blk.cin and same_passes and low_out % bn == 0 and t1_c % 128 == 0 and x.hi.shape[1] == low_c
                 and not self._mx_gemm(x, low_c, t1_c) and not self._mx_gemm(x, low_c, low_out) and t1.lo is None and not t1.lo_fp4):

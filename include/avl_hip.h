@@ -178,6 +178,62 @@ int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, 
  *   5     word mask                         sweep of the whole mask    everything else (any grid size, any alignment) */
 int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views, uint32_t bonus_classes);
 
+/* ---- a9o: occlusion culling -- occluded points do not vote (not in the reference) --------------- */
+
+/* project_pcd keeps every point in front of the vehicle that lands inside the image (:378-383), so a map point behind a parked car
+ * or a wall takes the label of what hides it.  The calls below give every view a coarse depth buffer in image space and let a point
+ * vote only if it is not clearly behind the nearest point of its image neighbourhood.  THE RULE, for one view with a projection
+ * image of img_w x img_h (the size points are projected to, not that of a smaller class map), s = cell_px, R = radius,
+ * Wc = ceil(img_w / s), Hc = ceil(img_h / s):
+ *   1. candidate: a point that passes the test of :378-383 as avl_fused_frame computes it (0 < v0 < range_max, 0 <= ix < img_w,
+ *      0 <= iy < img_h).  Whether it falls on the grid plays no part: an off-grid wall hides what is behind it.
+ *   2. depth: p2, the third row of P . v (the divisor of :375); its key q = (float)p2, rounded to nearest.  A candidate whose key
+ *      is not finite and > 0 writes nothing to the buffer and is never culled.
+ *   3. buffer: depth[cy][cx] = the minimum key over the candidates with cx = ix / s, cy = iy / s, held as the key's bit pattern in
+ *      a uint32 (positive floats order as unsigned integers); an empty cell holds 0xFFFFFFFF.
+ *   4. m = the minimum of depth over the cells (cx + dx, cy + dy), |dx|, |dy| <= R, clipped to the buffer.
+ *   5. a candidate is culled iff (double)q > (double)m * k + abs_tol, k = 1.0 + rel_tol computed once on the host in double, the
+ *      product and the sum two separately rounded double operations.  The nearest point of a neighbourhood is never culled.
+ *   6. a culled candidate casts no vote in that view; everything else is avl_fused_frame's.
+ * The grid after a call equals, bit for bit, what the call without culling does with the cloud from which that view's culled points
+ * were removed.  Integer atomics only: the result does not depend on the order of the points.  Every call starts from an empty
+ * buffer (it resets depth and culled itself), so calls are independent and may share one scratch. */
+typedef struct avl_occlusion {
+    int32_t cell_px;       /* s: edge of a depth cell in pixels of the projection image, 1..64                       */
+    int32_t radius;        /* R: neighbourhood radius in cells, 0..2                                                 */
+    double rel_tol;        /* >= 0                                                                                   */
+    double abs_tol;        /* >= 0, in the unit of the depth (metres)                                                */
+    uint32_t* depth;       /* scratch uint32[depth_words], 4-byte aligned; any content on entry                      */
+    int64_t depth_words;   /* >= avl_occlusion_depth_words(img_w, img_h, cell_px, n_views)                           */
+    int32_t* culled;       /* int32[n_views]: receives the number of culled candidates of each view; may be NULL     */
+} avl_occlusion;
+
+/* words of depth scratch for n_views views: n_views * Hc * Wc (host only; 0 for sizes the calls refuse) */
+int64_t avl_occlusion_depth_words(int img_w, int img_h, int cell_px, int n_views);
+
+/* avl_fused_frame / avl_fused_frame_views with the rule above: a depth pass over the cloud (one atomicMin per candidate and view),
+ * then the vote with the cull test, then the same apply.  The path is avl_fused_frame_path's / avl_fused_frame_views_path's for n as
+ * passed in, not for the number of survivors.  AVL_E_ARG, before any GPU work, for what the plain calls refuse and for a NULL occl,
+ * cell_px outside 1..64, radius outside 0..2, a negative or NaN tolerance, a NULL, too short or misaligned depth scratch. */
+int avl_fused_frame_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride,
+                         int64_t comp_stride, const double* P_host, const double* T_host, double range_max,
+                         int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
+                         const uint32_t* lut_host, const uint8_t* label_colors_host,
+                         const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream);
+int avl_fused_frame_views_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                               int n_views, const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
+                               int src_kind, const uint8_t* const* src_host /* n_views device pointers */,
+                               int src_w, int src_h, int img_w, int img_h,
+                               const uint32_t* lut_host, const uint8_t* label_colors_host,
+                               const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream);
+
+/* The rule alone, for 1 <= n_views <= AVL_MAX_VIEWS views of one cloud (points addressed as in avl_project_points): state
+ * uint8[n_views][n] = 0 not a candidate of the view, 1 visible, 2 culled; key float[n_views][n] (or NULL) = the candidate's key,
+ * 0 for a point that is no candidate.  occl->culled, when given, receives the number of state-2 points per view. */
+int avl_occlusion_visibility(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                             const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
+                             int img_w, int img_h, const avl_occlusion* occl, uint8_t* state, float* key, void* stream);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

@@ -1,0 +1,432 @@
+"""Occlusion culling on the GPU (csrc/mapping.hip: k_occl_depth, k_fused_vote_occl, k_views_vote_occl, k_occl_visibility) against the
+NumPy restatement of the rule (tests/_occlusion_reference.py).
+
+States are compared point by point.  Grids are compared bit for bit with what the PLAIN calls do with the cloud from which the
+reference's culled points were removed (padded back to n with points that project nowhere, so that the same vote / apply path runs;
+the path is asserted).  The reference is fed with the float32 keys the GPU returns, after those were checked against the oracle's
+float64 depth to one float32 ulp.  Scenes are tiny (96 x 64 and 97 x 61 pixels, 1 .. 3000 points): the grids of 64 x 64 and 50 x 30
+cells put those clouds on all four single-view paths and both views paths."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _occlusion_reference as ref
+
+pytestmark = pytest.mark.gpu
+
+GRIDS = {"g64": (64, 64, 0.5), "g50x30": (50, 30, 0.6)}      # 4096 cells: byte mask; 1500 cells (% 16 != 0): 32-bit mask only
+# (grid, n, the path avl_fused_frame_path gives): 2n <= cells -> lists (3); dense, byte mask -> 2; no byte mask: sweep (1) from
+# n * 128 >= cells on, the single touched list (0) below
+FRAME_CASES = [("g64", 3000, 2), ("g64", 257, 3), ("g64", 63, 3), ("g64", 1, 3),
+               ("g50x30", 3000, 1), ("g50x30", 257, 1), ("g50x30", 63, 1), ("g50x30", 11, 0), ("g50x30", 1, 0)]
+# (grid, n, the path avl_fused_frame_views_path gives for V >= 2): lists (4) while 2n <= cells, else the word sweep (5)
+VIEWS_CASES = [("g64", 257, 4), ("g64", 3000, 5), ("g50x30", 257, 4), ("g50x30", 3000, 5)]
+# (map dtype, USE_INTENSITY, semantic source, cloud format, (s, R, rel, abs)): the defaults cull most of so small an image (an 8 px cell
+# with R = 1 spans 24 of its 64 rows), the other parameter sets leave several hundred voting points
+VARIANTS = {"f64_int_rgb_soa64": ("f64", True, "rgb", "soa64", (8, 1, 0.05, 0.5)), "f32_noint_cls_aos32": ("f32", False, "classmap", "aos32", (7, 0, 0.1, 1.0)),
+            "f32_int_rgb_aos32": ("f32", True, "rgb", "aos32", (1, 2, 0.05, 0.5)), "f64_noint_cls_soa64": ("f64", False, "classmap", "soa64", (4, 1, 0.1, 1.0))}
+
+
+def occl_cfg(par):
+    return dict(CELL_PX=par[0], RADIUS=par[1], REL_TOL=par[2], ABS_TOL=par[3])
+
+
+YAWS = [0.0, 0.35, -0.35]                 # the views see different parts of the scene
+S_R_TOL = [(s, R, tol) for s in (1, 7, 8) for R in (0, 1, 2) for tol in ((0.0, 0.0), (0.05, 0.5), (0.2, 0.0))]
+NOWHERE = np.array([-1.0, 0.0, 0.0, 0.0])   # behind the sensor: no candidate of any view
+
+
+class Cam(object):
+    def __init__(self, P):
+        self.P = P
+
+
+def cams(w, h, V):
+    return [Cam(ref.pinhole_P(w, h, yaw=YAWS[v % 3] + 0.1 * (v // 3))) for v in range(V)]
+
+
+def cloud_as(pcd, fmt):
+    """(what goes to the GPU, the float64 [4, n] cloud the oracle sees)"""
+    if fmt == "soa64":
+        return pcd, pcd
+    aos = np.ascontiguousarray(pcd.T.astype(np.float32))
+    return aos, np.ascontiguousarray(aos.T.astype(np.float64))
+
+
+def make_sm(grid, device, grid_dtype="f64", intensity=True, occl=None, boundary=None):
+    from vision_semantic_segmentation_amd import SemanticMapping, get_cfg_defaults, synthetic as syn
+    from vision_semantic_segmentation_amd.utils.logger import MyLogger
+    Hm, Wm, res = GRIDS[grid]
+    cfg = get_cfg_defaults()
+    cfg.MAPPING.BOUNDARY = ref.boundary(Hm, Wm, res) if boundary is None else boundary
+    cfg.MAPPING.RESOLUTION = res
+    cfg.MAPPING.PCD.USE_INTENSITY = intensity
+    cfg.MAPPING.GRID_DTYPE = grid_dtype
+    if occl is not None:
+        cfg.MAPPING.OCCLUSION.ENABLED = True
+        for k, v in occl.items():
+            cfg.MAPPING.OCCLUSION[k] = v
+    sm = SemanticMapping(cfg, device=device, logger=MyLogger("test", quiet=True))
+    sm.confusion_matrix = syn.log_confusion(5)
+    assert (sm.map_height, sm.map_width) == (Hm, Wm)
+    return sm
+
+
+def set_occl(sm, s, R, rel, abs_):
+    oc = sm.occlusion_cfg
+    oc.CELL_PX, oc.RADIUS, oc.REL_TOL, oc.ABS_TOL = s, R, rel, abs_
+
+
+def sources(seed, w, h, V, src_kind, device):
+    """V semantic sources on the device: colour images [h, w, 3], or class maps of half the projection size"""
+    import torch
+    from vision_semantic_segmentation_amd import synthetic as syn
+    rng = np.random.default_rng(seed)
+    ids = np.array([2, 1, 8, 10, 3, 0], dtype=np.uint8)            # the five map classes and one the map does not hold
+    out = []
+    for _ in range(V):
+        if src_kind == "rgb":
+            out.append(torch.from_numpy(syn.colorize(ids[syn.make_label_map(rng, h, w, num_classes=6, tile=5)])).to(device))
+        else:
+            out.append(torch.from_numpy(ids[syn.make_label_map(rng, h // 2, w // 2, num_classes=6, tile=3)]).to(device))
+    return out
+
+
+def frame_path(sm, n, V=1):
+    from vision_semantic_segmentation_amd import _lib
+    g = sm.grid
+    g.ensure_capacity(n)
+    gs = g.struct()
+    return _lib.lib().avl_fused_frame_views_path(C.byref(gs), n, V, sm._bonus_classes())
+
+
+def gpu_states(sm, gpu_cloud, host_cloud, camlist, w, h, check_keys=True, projs=None, frame_id="velodyne", pose=None, pose7=None):
+    """visibility_device -> (states uint8 [V, n], keys float32 [V, n], projections), the keys of the candidates checked against
+    the oracle's float64 depth to one float32 ulp and the candidate sets against the oracle's mask"""
+    state, key = sm.visibility_device(gpu_cloud, frame_id, pose, camlist, (h, w), return_keys=True)
+    state, key = state.cpu().numpy(), key.cpu().numpy()
+    projs = projs or [ref.Projection(host_cloud, c.P, w, h, frame_id=frame_id, pose7=pose7) for c in camlist]
+    for v, pr in enumerate(projs):
+        assert np.array_equal(state[v] != 0, pr.cand), "view %d: candidate set differs from the oracle's mask" % v
+        if check_keys:
+            p2 = pr.p2[pr.cand]
+            ulp = np.spacing(np.abs(p2).astype(np.float32)).astype(np.float64)
+            err = np.abs(key[v][pr.cand].astype(np.float64) - p2)
+            assert (err <= ulp).all(), "view %d: key off by %g ulp" % (v, float((err / ulp).max()))
+        assert not key[v][~pr.cand].any()
+    return state, key, projs
+
+
+def ref_states(projs, key, s, R, rel, abs_):
+    return np.stack([pr.states(key=key[v], s=s, R=R, rel=rel, abs_=abs_) for v, pr in enumerate(projs)])
+
+
+def removed(gpu_cloud, culled):
+    """the cloud without its culled points, padded back to n with points that project nowhere (same layout and dtype)"""
+    keep = ~culled
+    if gpu_cloud.shape[0] == 4 and gpu_cloud.dtype == np.float64:      # SoA [4, n]
+        out = np.tile(NOWHERE.reshape(4, 1), (1, gpu_cloud.shape[1]))
+        out[:, :int(keep.sum())] = gpu_cloud[:, keep]
+        return out
+    out = np.tile(NOWHERE.astype(np.float32), (gpu_cloud.shape[0], 1))
+    out[:int(keep.sum())] = gpu_cloud[keep]
+    return out
+
+
+def run_frame(sm, cloud, src, cam, src_kind, w, h):
+    sm.frame_device(cloud, "velodyne", src, None, cam, src_kind=src_kind, image_size=(h, w))
+
+
+def run_views(sm, cloud, srcs, camlist, src_kind, w, h):
+    sm.frame_device_views(cloud, "velodyne", srcs, None, camlist, src_kind=src_kind, image_size=(h, w))
+
+
+def same_grid(a, b, what):
+    import torch
+    assert a.map_dev.dtype == b.map_dev.dtype
+    assert torch.equal(a.map_dev, b.map_dev), "%s: %d values differ" % (what, int((a.map_dev != b.map_dev).sum()))
+    for sm in (a, b):
+        assert not bool(sm.grid.cell_mask.any()) and not bool(sm.grid.counter[4:].any()), "%s: scratch not cleared" % what
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. visibility
+@pytest.mark.parametrize("fmt", ["soa64", "aos32"])
+@pytest.mark.parametrize("sc", ref.scenes(), ids=[sc[0] for sc in ref.scenes()])
+def test_visibility_states_equal_the_rule(sc, fmt, cuda_device):
+    _, w, h, n, pcd, P = sc
+    gpu_cloud, host_cloud = cloud_as(pcd, fmt)
+    sm = make_sm("g64", cuda_device)
+    assert not sm.occlusion_enabled()                     # visibility_device works with the option off
+    cam = [Cam(P)]
+    culled_any, projs = 0, None
+    for k, (s, R, (rel, abs_)) in enumerate(S_R_TOL):
+        set_occl(sm, s, R, rel, abs_)
+        state, key, projs = gpu_states(sm, gpu_cloud, host_cloud, cam, w, h, check_keys=(k == 0), projs=projs)
+        want = ref_states(projs, key, s, R, rel, abs_)
+        assert np.array_equal(state, want), "s=%d R=%d rel=%g abs=%g: %d states differ" % (s, R, rel, abs_, int((state != want).sum()))
+        assert sm.last_culled.cpu().tolist() == [int((want[0] == 2).sum())]
+        culled_any += int((want == 2).sum())
+    if n == 3000:
+        assert culled_any > 27 * 50
+
+
+@pytest.mark.parametrize("size", ref.SIZES, ids=["%dx%d" % s for s in ref.SIZES])
+def test_visibility_of_three_views_in_one_call(size, cuda_device):
+    w, h = size
+    pcd = ref.make_cloud(7, 3000)
+    sm = make_sm("g64", cuda_device)
+    camlist = cams(w, h, 3)
+    for s, R, rel, abs_ in [(8, 1, 0.05, 0.5), (7, 2, 0.0, 0.0), (1, 0, 0.1, 0.1)]:
+        set_occl(sm, s, R, rel, abs_)
+        state, key, projs = gpu_states(sm, pcd, pcd, camlist, w, h)
+        want = ref_states(projs, key, s, R, rel, abs_)
+        assert np.array_equal(state, want)
+        assert sm.last_culled.cpu().tolist() == [int((want[v] == 2).sum()) for v in range(3)]
+    assert len({int(pr.cand.sum()) for pr in projs}) == 3 and all(int((want[v] == 2).sum()) > 50 for v in range(3))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. fused frame
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+@pytest.mark.parametrize("size", ref.SIZES, ids=["%dx%d" % s for s in ref.SIZES])
+@pytest.mark.parametrize("case", FRAME_CASES, ids=["%s_n%d_p%d" % c for c in FRAME_CASES])
+def test_fused_frame_equals_the_plain_frame_on_the_filtered_cloud(case, size, variant, cuda_device):
+    grid, n, path = case
+    w, h = size
+    dtype, intensity, src_kind, fmt, par = VARIANTS[variant]
+    gpu_cloud, host_cloud = cloud_as(ref.make_cloud(11 + n, n), fmt)
+    cam = Cam(ref.pinhole_P(w, h))
+    src = sources(n, w, h, 1, src_kind, cuda_device)[0]
+    culling = make_sm(grid, cuda_device, dtype, intensity, occl=occl_cfg(par))
+    plain = make_sm(grid, cuda_device, dtype, intensity)
+    assert frame_path(culling, n) == path and frame_path(plain, n) == path
+    state, key, projs = gpu_states(culling, gpu_cloud, host_cloud, [cam], w, h)
+    want = ref_states(projs, key, *par)[0]
+    assert np.array_equal(state[0], want)
+    run_frame(culling, gpu_cloud, src, cam, src_kind, w, h)
+    assert culling.last_culled.cpu().tolist() == [int((want == 2).sum())]
+    run_frame(plain, removed(gpu_cloud, want == 2), src, cam, src_kind, w, h)
+    same_grid(culling, plain, "culling frame vs plain frame on the filtered cloud")
+    if n == 3000:
+        assert (want == 2).sum() >= 150 and int(culling.map_dev.count_nonzero()) > 20
+        unfiltered = make_sm(grid, cuda_device, dtype, intensity)
+        run_frame(unfiltered, gpu_cloud, src, cam, src_kind, w, h)
+        assert not bool((unfiltered.map_dev == culling.map_dev).all()), "culling changed nothing: the case tests nothing"
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. views
+@pytest.mark.parametrize("variant", ["f64_int_rgb_soa64", "f32_noint_cls_aos32"])
+@pytest.mark.parametrize("V", [2, 3])
+@pytest.mark.parametrize("case", VIEWS_CASES, ids=["%s_n%d_p%d" % c for c in VIEWS_CASES])
+def test_views_equal_sequential_culling_frames_and_plain_frames_on_filtered_clouds(case, V, variant, cuda_device):
+    grid, n, path = case
+    w, h = ref.SIZES[V % 2]
+    dtype, intensity, src_kind, fmt, par = VARIANTS[variant]
+    gpu_cloud, host_cloud = cloud_as(ref.make_cloud(23 + n, n), fmt)
+    camlist = cams(w, h, V)
+    srcs = sources(n + V, w, h, V, src_kind, cuda_device)
+    fused = make_sm(grid, cuda_device, dtype, intensity, occl=occl_cfg(par))
+    assert frame_path(fused, n, V) == path
+    state, key, projs = gpu_states(fused, gpu_cloud, host_cloud, camlist, w, h)
+    want = ref_states(projs, key, *par)
+    run_views(fused, gpu_cloud, srcs, camlist, src_kind, w, h)
+    assert fused.last_culled.cpu().tolist() == [int((want[v] == 2).sum()) for v in range(V)]
+    seq = make_sm(grid, cuda_device, dtype, intensity, occl=occl_cfg(par))
+    plain = make_sm(grid, cuda_device, dtype, intensity)
+    for v in range(V):
+        run_frame(seq, gpu_cloud, srcs[v], camlist[v], src_kind, w, h)
+        assert seq.last_culled.cpu().tolist() == [int((want[v] == 2).sum())]
+        run_frame(plain, removed(gpu_cloud, want[v] == 2), srcs[v], camlist[v], src_kind, w, h)
+    same_grid(fused, seq, "views vs sequential culling frames")
+    same_grid(fused, plain, "views vs plain frames on the per-view filtered clouds")
+    if n == 3000:
+        assert int(fused.map_dev.count_nonzero()) > 20
+        assert all((want[v] == 2).sum() > 50 for v in range(V))
+
+
+def test_more_views_than_one_call_takes_fall_back_to_sequential_culling_frames(cuda_device):
+    w, h = ref.SIZES[1]
+    V, n = 5, 3000
+    pcd = ref.make_cloud(5, n)
+    camlist = cams(w, h, V)
+    srcs = sources(5, w, h, V, "classmap", cuda_device)
+    many = make_sm("g64", cuda_device, occl={})
+    state, key, projs = gpu_states(many, pcd, pcd, camlist, w, h)
+    want = ref_states(projs, key, 8, 1, 0.05, 0.5)
+    assert np.array_equal(state, want)
+    run_views(many, pcd, srcs, camlist, "classmap", w, h)
+    assert many.last_culled.cpu().tolist() == [int((want[v] == 2).sum()) for v in range(V)]
+    plain = make_sm("g64", cuda_device)
+    for v in range(V):
+        run_frame(plain, removed(pcd, want[v] == 2), srcs[v], camlist[v], "classmap", w, h)
+    same_grid(many, plain, "five views")
+
+
+WORLD_POSE = np.array([-1369.0496826171875 + 1369.3, -562.84814453125 + 563.1, 0.2, 0.0, 0.0, 0.0871557427, 0.9961946981])
+
+
+@pytest.mark.parametrize("case", VIEWS_CASES, ids=["%s_n%d_p%d" % c for c in VIEWS_CASES])
+def test_a_cloud_in_the_world_frame_is_moved_by_the_pose_once(case, cuda_device):
+    """the cloud in world coordinates with a pose (T_host is not NULL): states against the rule on the oracle's transformed projection,
+    one view and three, and the grids of the culling calls against the plain calls on the filtered clouds"""
+    from vision_semantic_segmentation_amd.utils import Pose
+    grid, n, path = case
+    Hm, Wm, res = GRIDS[grid]
+    w, h = ref.SIZES[1]
+    pose = Pose.from_array(WORLD_POSE)
+    cx, cy = WORLD_POSE[0] + 1369.0496826171875, WORLD_POSE[1] + 562.84814453125
+    boundary = [[cx - Hm * res / 2, cx + Hm * res / 2], [cy - Wm * res / 2, cy + Wm * res / 2]]      # centred on the vehicle
+    par = (7, 1, 0.1, 1.0)
+    fused = make_sm(grid, cuda_device, occl=occl_cfg(par), boundary=boundary)
+    plain = make_sm(grid, cuda_device, boundary=boundary)
+    vel = ref.make_cloud(81 + n, n)
+    pcd = vel.copy()
+    pcd[0:3] = (np.linalg.inv(fused._origin_to_velodyne(pose)) @ np.vstack([vel[0:3], np.ones((1, n))]))[0:3]
+    camlist = cams(w, h, 3)
+    srcs = sources(81, w, h, 3, "classmap", cuda_device)
+    state, key, projs = gpu_states(fused, pcd, pcd, camlist, w, h, frame_id="world", pose=pose, pose7=WORLD_POSE)
+    want = ref_states(projs, key, *par)
+    assert np.array_equal(state, want)
+    assert frame_path(fused, n, 3) == path
+    fused.frame_device_views(pcd, "world", srcs, pose, camlist, src_kind="classmap", image_size=(h, w))
+    fused.frame_device(pcd, "world", srcs[1], pose, camlist[1], src_kind="classmap", image_size=(h, w))
+    assert fused.last_culled.cpu().tolist() == [int((want[1] == 2).sum())]
+    for v in (0, 1, 2, 1):
+        plain.frame_device(removed(pcd, want[v] == 2), "world", srcs[v], pose, camlist[v], src_kind="classmap", image_size=(h, w))
+    same_grid(fused, plain, "world frame")
+    if n == 3000:
+        assert all((want[v] == 2).sum() > 50 for v in range(3)) and int(fused.map_dev.count_nonzero()) > 20
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. nothing culled
+@pytest.mark.parametrize("case", [("g64", 3000), ("g64", 257), ("g50x30", 3000), ("g50x30", 11)], ids=lambda c: "%s_n%d" % c)
+def test_a_huge_abs_tol_gives_the_plain_grids(case, cuda_device):
+    grid, n = case
+    w, h = ref.SIZES[1]
+    pcd = ref.make_cloud(31, n)
+    camlist = cams(w, h, 3)
+    srcs = sources(31, w, h, 3, "rgb", cuda_device)
+    culling, plain = make_sm(grid, cuda_device, occl=dict(ABS_TOL=1e30)), make_sm(grid, cuda_device)
+    run_frame(culling, pcd, srcs[0], camlist[0], "rgb", w, h)
+    run_frame(plain, pcd, srcs[0], camlist[0], "rgb", w, h)
+    same_grid(culling, plain, "one view")
+    assert culling.last_culled.cpu().tolist() == [0]
+    run_views(culling, pcd, srcs, camlist, "rgb", w, h)
+    run_views(plain, pcd, srcs, camlist, "rgb", w, h)
+    same_grid(culling, plain, "three views")
+    assert culling.last_culled.cpu().tolist() == [0, 0, 0]
+    assert n < 100 or int(plain.map_dev.count_nonzero()) > 50
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. independence
+@pytest.mark.parametrize("V", [1, 3])
+def test_calls_through_one_scratch_are_independent(V, cuda_device):
+    """scene A, scene B (nearer points in other cells), scene A again through one SemanticMapping and one depth scratch: each
+    step's grid and counts are those of a fresh object"""
+    w, h = ref.SIZES[0]
+    a, b = ref.make_cloud(41, 3000), ref.make_cloud(42, 3000)
+    b[0:2] *= 0.6                                          # nearer: leaves smaller depths in the buffer than scene A's
+    camlist = cams(w, h, V)
+    srcs = sources(41, w, h, V, "rgb", cuda_device)
+    one = make_sm("g64", cuda_device, occl={})
+    scratch = None
+    for step, pcd in enumerate((a, b, a)):
+        fresh = make_sm("g64", cuda_device, occl={})
+        one.map_dev.zero_()
+        for sm in (one, fresh):
+            if V == 1:
+                run_frame(sm, pcd, srcs[0], camlist[0], "rgb", w, h)
+            else:
+                run_views(sm, pcd, srcs, camlist, "rgb", w, h)
+        same_grid(one, fresh, "step %d" % step)
+        assert one.last_culled.cpu().tolist() == fresh.last_culled.cpu().tolist() and sum(one.last_culled.cpu().tolist()) > 50
+        assert len(one._occl_depth) == 1
+        ptr = next(iter(one._occl_depth.values())).data_ptr()
+        assert scratch in (None, ptr)
+        scratch = ptr
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6. edges
+def test_empty_cloud(cuda_device):
+    w, h = ref.SIZES[0]
+    cam = Cam(ref.pinhole_P(w, h))
+    src = sources(1, w, h, 1, "rgb", cuda_device)[0]
+    sm = make_sm("g64", cuda_device, occl={})
+    run_frame(sm, ref.make_cloud(1, 3000), src, cam, "rgb", w, h)
+    assert sm.last_culled.cpu().tolist()[0] > 50
+    before = sm.map_dev.clone()
+    empty = np.zeros((4, 0))
+    run_frame(sm, empty, src, cam, "rgb", w, h)
+    assert sm.last_culled.cpu().tolist() == [0] and bool((sm.map_dev == before).all())
+    run_views(sm, empty, [src, src], [cam, cam], "rgb", w, h)
+    assert sm.last_culled.cpu().tolist() == [0, 0] and bool((sm.map_dev == before).all())
+    state, key = sm.visibility_device(empty, "velodyne", None, [cam, cam], (h, w), return_keys=True)
+    assert tuple(state.shape) == (2, 0) and tuple(key.shape) == (2, 0)
+
+
+@pytest.mark.parametrize("fmt", ["soa64", "aos32"])
+def test_non_finite_coordinates_are_no_candidates(fmt, cuda_device):
+    w, h = ref.SIZES[1]
+    pcd = ref.make_cloud(51, 257)
+    bad = np.arange(0, 240, 3)
+    vals = [np.nan, np.inf, -np.inf]
+    for j, k in enumerate(bad):
+        pcd[j % 3, k] = vals[(j // 3) % 3]                 # x, y and z in turn, NaN, +Inf and -Inf in turn
+    pcd[3, 1:240:3] = np.array(vals)[np.arange(80) % 3]    # intensity alone: the point stays a candidate
+    gpu_cloud, host_cloud = cloud_as(pcd, fmt)
+    cam = Cam(ref.pinhole_P(w, h))
+    for grid in GRIDS:
+        sm, plain = make_sm(grid, cuda_device, occl={}), make_sm(grid, cuda_device)
+        state, key, projs = gpu_states(sm, gpu_cloud, host_cloud, [cam], w, h)
+        assert not state[0][bad].any() and state[0][1:240:3].any()
+        want = ref_states(projs, key, 8, 1, 0.05, 0.5)[0]
+        assert np.array_equal(state[0], want)
+        src = sources(51, w, h, 1, "rgb", cuda_device)[0]
+        run_frame(sm, gpu_cloud, src, cam, "rgb", w, h)
+        run_frame(plain, removed(gpu_cloud, want == 2), src, cam, "rgb", w, h)
+        same_grid(sm, plain, grid)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. wiring
+def test_enabled_through_mapping_and_mapping_views(cuda_device):
+    w, h = ref.SIZES[0]
+    n = 3000
+    pcd = ref.make_cloud(61, n)
+    camlist = cams(w, h, 3)
+    imgs = [t.cpu().numpy() for t in sources(61, w, h, 3, "rgb", cuda_device)]
+    sm = make_sm("g64", cuda_device, occl={})
+    state, key, projs = gpu_states(sm, pcd, pcd, camlist, w, h)
+    want = ref_states(projs, key, 8, 1, 0.05, 0.5)
+    sm.pcd, sm.pcd_frame_id = pcd, "velodyne"
+    sm.mapping(imgs[0], None, camlist[0])
+    assert sm.last_culled.cpu().tolist() == [int((want[0] == 2).sum())]
+    plain = make_sm("g64", cuda_device)
+    plain.pcd, plain.pcd_frame_id = removed(pcd, want[0] == 2), "velodyne"
+    plain.mapping(imgs[0], None, camlist[0])
+    same_grid(sm, plain, "mapping()")
+    sm.mapping_views(imgs, None, camlist)
+    assert sm.last_culled.cpu().tolist() == [int((want[v] == 2).sum()) for v in range(3)]
+    for v in range(3):
+        plain.pcd = removed(pcd, want[v] == 2)
+        plain.mapping(imgs[v], None, camlist[v])
+    same_grid(sm, plain, "mapping_views()")
+    assert sm.frames_mapped == 4
+
+
+def test_disabled_allocates_nothing_and_maps_like_the_oracle(cuda_device):
+    from oracle import mapping_oracle as mo
+    w, h = ref.SIZES[0]
+    pcd = ref.make_cloud(71, 3000)
+    cam = Cam(ref.pinhole_P(w, h))
+    img = sources(71, w, h, 1, "rgb", cuda_device)[0].cpu().numpy()
+    sm = make_sm("g64", cuda_device)
+    sm.pcd, sm.pcd_frame_id = pcd, "velodyne"
+    sm.mapping(img, None, cam)
+    sm.mapping_views([img, img], None, [cam, cam])
+    assert sm._occl_depth == {} and sm.last_culled is None
+    grid = np.zeros((64, 64, 5))
+    ocfg = dict(range_max=sm.pcd_range_max, boundary=sm.map_boundary, resolution=sm.resolution, label_names=mo.LABELS_NAMES,
+                label_colors=mo.LABEL_COLORS, confusion_matrix=sm.confusion_matrix, use_pcd_intensity=True)
+    for _ in range(3):
+        mo.mapping_frame(grid, pcd, "velodyne", img, None, cam.P, ocfg)
+    assert np.array_equal(sm.map, grid) and np.count_nonzero(grid) > 100

@@ -37,6 +37,14 @@ class AvlGrid(C.Structure):
     ]
 
 
+class AvlOcclusion(C.Structure):
+    """struct avl_occlusion of include/avl_hip.h"""
+    _fields_ = [
+        ("cell_px", C.c_int32), ("radius", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double),
+        ("depth", C.c_void_p), ("depth_words", C.c_int64), ("culled", C.c_void_p),
+    ]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
 _SIGNATURES = {
@@ -54,6 +62,12 @@ _SIGNATURES = {
     "avl_fused_frame_views": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
                                    _vp, _vp, _vp, C.c_uint32, _vp]),
     "avl_fused_frame_views_path": (_i, [C.POINTER(AvlGrid), _i, _i, C.c_uint32]),
+    "avl_occlusion_depth_words": (_i64, [_i, _i, _i, _i]),
+    "avl_fused_frame_occl": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
+                                  _vp, _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
+    "avl_fused_frame_views_occl": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
+                                        _vp, _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
+    "avl_occlusion_visibility": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlOcclusion), _vp, _vp, _vp]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

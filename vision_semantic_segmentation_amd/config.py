@@ -163,6 +163,18 @@ def get_cfg_defaults():
     C.MAPPING.LIVE_MAP.FILL_PRIORITY = [0, 3, 4, 2, 1]    # low to high (renderer.py:67)
     C.MAPPING.LIVE_MAP.DRAW_CAR = True
     C.MAPPING.LIVE_MAP.CAR_SIZE = [4.0, 1.8]              # length, width in metres (src/mapping.py:502-503)
+    # build-specific: occluded points do not vote (the reference lets a map point behind a wall take the wall's label).  Every view gets a
+    # depth buffer of CELL_PX x CELL_PX pixel cells of the projection image; a point is culled when its depth exceeds
+    # m * (1 + REL_TOL) + ABS_TOL, m the nearest depth within RADIUS cells (the rule: include/avl_hip.h, avl_occlusion).  Off by
+    # default: nothing of it runs and no scratch is allocated.  The defaults are reasoned, not tuned on a recorded drive: at 20 m, with
+    # the camera 2 m above the ground and f ~ 1000 px, the ground's depth changes by ~0.2 m per image row, so an 8 px cell spans ~8 %
+    # of its depth.  The planar mode ignores the option
+    C.MAPPING.OCCLUSION = CfgNode()
+    C.MAPPING.OCCLUSION.ENABLED = False
+    C.MAPPING.OCCLUSION.CELL_PX = 8                       # 1..64
+    C.MAPPING.OCCLUSION.RADIUS = 1                        # 0..2 cells
+    C.MAPPING.OCCLUSION.REL_TOL = 0.05
+    C.MAPPING.OCCLUSION.ABS_TOL = 0.5                     # metres
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

@@ -52,6 +52,14 @@ struct LutParams {
     unsigned lut[256];
 };
 
+// avl_occlusion in kernel-argument form (the culling kernels are at the end of this file)
+struct OcclParams {
+    unsigned* depth;     // [n_views][Hc][Wc]: bit pattern of the nearest candidate's float32 depth, 0xFFFFFFFF = empty cell
+    int* culled;         // [n_views] culled candidates, or NULL
+    double k, abs_tol;   // a candidate of depth q is culled iff (double)q > (double)m * k + abs_tol; k = 1 + rel_tol
+    int s, R, Wc, Hc;    // cell edge in pixels, neighbourhood radius in cells, buffer size
+};
+
 __device__ __forceinline__ void load_point(const PtsView& v, int k, double& x, double& y, double& z, double& it) {
     if (v.aos_f32) {
         const float4 p = *reinterpret_cast<const float4*>(v.base + (long long)k * 16);
@@ -112,7 +120,8 @@ __device__ __forceinline__ double dot4(const double* r, double a, double b, doub
     return s;
 }
 
-__device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy) {
+// `p2` = the third row of P . v, the divisor of :375: the depth the occlusion test compares (k_occl_depth, occl_culled)
+__device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy, double& p2) {
     double v0 = x, v1 = y, v2 = z, v3 = 1.0;
     if (pp.has_T) {
         v0 = dot4(pp.T + 0, x, y, z, 1.0);
@@ -122,12 +131,16 @@ __device__ __forceinline__ bool project(const ProjParams& pp, double x, double y
     }
     const double p0 = dot4(pp.P + 0, v0, v1, v2, v3);
     const double p1 = dot4(pp.P + 4, v0, v1, v2, v3);
-    const double p2 = dot4(pp.P + 8, v0, v1, v2, v3);
+    p2 = dot4(pp.P + 8, v0, v1, v2, v3);
     const double rp2 = refine_rcp(p2);
     ix = div_i32_numpy(p0, p2, rp2);
     iy = div_i32_numpy(p1, p2, rp2);
     const bool positive = (0.0 < v0) && (v0 < pp.range_max);
     return positive && ix >= 0 && ix < pp.img_w && iy >= 0 && iy < pp.img_h;
+}
+__device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy) {
+    double p2;
+    return project(pp, x, y, z, ix, iy, p2);
 }
 
 // grid cell of a point in its ORIGINAL frame (:404-411); -1 if off-grid / non-finite
@@ -1096,6 +1109,70 @@ int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtyp
     return AVL_OK;
 }
 
+// Occlusion culling (avl_fused_frame_occl and its kin): defined with the culling kernels at the end of this file.
+//   occl_fill: validates an avl_occlusion for n_views views of img_w x img_h (host only) and puts it into kernel-argument form
+//   occl_reset: every depth cell back to empty and the culled counts to zero (two memsets) -- what makes a call independent of the last
+//   launch_occl_depth: the depth pass;  launch_*_vote_occl: the culling twin of k_fused_vote<SRC, mode> / k_views_vote<SRC, lists>
+int occl_fill(OcclParams& oc, const avl_occlusion* occl, int img_w, int img_h, int n_views);
+int occl_reset(const OcclParams& oc, int n_views, bool depth, hipStream_t s);
+int launch_occl_depth(const PtsView& pv, const ViewsParams& vp, const OcclParams& oc, hipStream_t s);
+int launch_fused_vote_occl(const FrameArgs& f, int src_kind, int mode, const uint8_t* src, int src_w, int src_h, const avl_grid* g, int list_cap,
+                           const OcclParams& oc, hipStream_t s);
+int launch_views_vote_occl(const FrameArgs& f, const ViewsParams& vp, int src_kind, bool lists, int src_w, int src_h, const avl_grid* g,
+                           int list_cap, const OcclParams& oc, hipStream_t s);
+
+void fill_views(ViewsParams& vp, const FrameArgs& f, int n_views, const double* P_host, const uint8_t* const* src_host) {
+    memset(&vp, 0, sizeof(vp));
+    memcpy(vp.P, P_host, sizeof(double) * 12 * n_views);
+    memcpy(vp.T, f.pp.T, sizeof(vp.T));
+    for (int v = 0; v < n_views; ++v) vp.src[v] = src_host ? src_host[v] : nullptr;
+    vp.range_max = f.pp.range_max;
+    vp.has_T = f.pp.has_T;
+    vp.n_views = n_views;
+    vp.img_w = f.pp.img_w;
+    vp.img_h = f.pp.img_h;
+}
+
+// avl_fused_frame, and with `occl` avl_fused_frame_occl: the path is decided from n alike, the depth pass runs first and the vote
+// kernel is the culling twin; the apply and sweep kernels are the same.
+int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
+                const double* T_host, double range_max, int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
+                const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes,
+                const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    OcclParams oc;
+    int rc;
+    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
+                         lut_host, label_colors_host, cm_host, bonus_classes)))
+        return rc;
+    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, 1))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if (n == 0) return occl ? occl_reset(oc, 1, false, s) : AVL_OK;
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const int mode = avl_fused_frame_path(g, n, bonus_classes);
+    if (mode < 0) return mode;
+    if (occl) {
+        ViewsParams vp;
+        fill_views(vp, f, 1, P_host, nullptr);
+        if ((rc = occl_reset(oc, 1, true, s))) return rc;
+        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+    }
+    if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
+    const int list_cap = list_geom(n).cap;
+    if (occl) {
+        if ((rc = launch_fused_vote_occl(f, src_kind, mode, src, src_w, src_h, g, list_cap, oc, s))) return rc;
+    } else {
+#define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap)
+        if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FV(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FV(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FV(AVL_SRC_RGB, 1); else AVL_FV(AVL_SRC_RGB, 0); }
+        else { if (mode == 3) AVL_FV(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FV(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FV(AVL_SRC_CLASSMAP, 1); else AVL_FV(AVL_SRC_CLASSMAP, 0); }
+#undef AVL_FV
+        AVL_LAUNCH_CHECK();
+    }
+    if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
+    if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
+    return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1201,26 +1278,8 @@ extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dt
                                int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
                                const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
                                uint32_t bonus_classes, void* stream) {
-    FrameArgs f;
-    int rc;
-    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
-                         lut_host, label_colors_host, cm_host, bonus_classes)))
-        return rc;
-    if (n == 0) return AVL_OK;
-    hipStream_t s = avl::as_stream(stream);
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const int mode = avl_fused_frame_path(g, n, bonus_classes);
-    if (mode < 0) return mode;
-    if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
-    const int list_cap = list_geom(n).cap;
-#define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap)
-    if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FV(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FV(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FV(AVL_SRC_RGB, 1); else AVL_FV(AVL_SRC_RGB, 0); }
-    else { if (mode == 3) AVL_FV(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FV(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FV(AVL_SRC_CLASSMAP, 1); else AVL_FV(AVL_SRC_CLASSMAP, 0); }
-#undef AVL_FV
-    AVL_LAUNCH_CHECK();
-    if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
-    if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
-    return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
+    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
+                       lut_host, label_colors_host, cm_host, bonus_classes, nullptr, stream);
 }
 
 extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views, uint32_t bonus_classes) {
@@ -1235,43 +1294,45 @@ extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views,
     return lists_fit(g, n) ? 4 : 5;
 }
 
-extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                                     int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
-                                     const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
-                                     const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
-                                     uint32_t bonus_classes, void* stream) {
+namespace {
+// avl_fused_frame_views, and with `occl` avl_fused_frame_views_occl (as fused_frame: same path, depth pass first, culling vote twin)
+int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                      int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                      const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                      const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                      uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
     int rc;
     if ((rc = views_check(n_views, src_host))) return rc;
     if (n_views == 1)
-        return avl_fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h,
-                               img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, stream);
+        return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h,
+                           img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
     FrameArgs f;
+    OcclParams oc;
     if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h, img_w,
                          img_h, lut_host, label_colors_host, cm_host, bonus_classes)))
         return rc;
     if ((rc = views_bits_check(g, bonus_classes))) return rc;
-    if (n == 0) return AVL_OK;
+    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;
     ViewsParams vp;
-    memset(&vp, 0, sizeof(vp));
-    memcpy(vp.P, P_host, sizeof(double) * 12 * n_views);
-    memcpy(vp.T, f.pp.T, sizeof(vp.T));
-    for (int v = 0; v < n_views; ++v) vp.src[v] = src_host[v];
-    vp.range_max = range_max;
-    vp.has_T = f.pp.has_T;
-    vp.n_views = n_views;
-    vp.img_w = img_w;
-    vp.img_h = img_h;
+    fill_views(vp, f, n_views, P_host, src_host);
     CmParams cm;
     if ((rc = fill_cm(cm, g, cm_host))) return rc;
-    hipStream_t s = avl::as_stream(stream);
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
     const bool lists = lists_fit(g, n);
     const ListGeom lg = list_geom(n);
+    if (occl) {
+        if ((rc = occl_reset(oc, n_views, true, s))) return rc;
+        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+        if ((rc = launch_views_vote_occl(f, vp, src_kind, lists, src_w, src_h, g, lg.cap, oc, s))) return rc;
+    } else {
 #define AVL_VV(SRC, LISTS) hipLaunchKernelGGL((k_views_vote<SRC, LISTS>), grid, block, 0, s, f.pv, vp, f.gp, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, lg.cap)
-    if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VV(AVL_SRC_RGB, 1); else AVL_VV(AVL_SRC_RGB, 0); }
-    else { if (lists) AVL_VV(AVL_SRC_CLASSMAP, 1); else AVL_VV(AVL_SRC_CLASSMAP, 0); }
+        if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VV(AVL_SRC_RGB, 1); else AVL_VV(AVL_SRC_RGB, 0); }
+        else { if (lists) AVL_VV(AVL_SRC_CLASSMAP, 1); else AVL_VV(AVL_SRC_CLASSMAP, 0); }
 #undef AVL_VV
-    AVL_LAUNCH_CHECK();
+        AVL_LAUNCH_CHECK();
+    }
     if (lists)
         return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
             typedef decltype(t) T;
@@ -1285,6 +1346,16 @@ extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, 
         hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
                            bonus_classes, cm, g->cell_mask, ncell, vec);
     });
+}
+}  // namespace
+
+extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                     int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                                     const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                     const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                     uint32_t bonus_classes, void* stream) {
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src_kind, src_host, src_w, src_h,
+                             img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, nullptr, stream);
 }
 
 extern "C" int avl_colorize_labels(const uint8_t* labels, int lw, int lh, const uint8_t* palette_host, uint8_t* out,
@@ -1539,4 +1610,315 @@ extern "C" int avl_grid_box_filter(const void* src, void* dst, int map_dtype, in
         typedef decltype(t) T;
         hipLaunchKernelGGL(k_box_filter3<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(src), static_cast<T*>(dst), Hm, Wm, C);
     });
+}
+
+// ================================================================ occlusion culling (avl_fused_frame_occl, avl_fused_frame_views_occl)
+// A map point behind a wall projects onto the wall's pixels and takes its label.  Before the vote, every view gets a coarse depth
+// buffer in image space; a point votes only if it is not clearly behind the nearest point of its image neighbourhood.  The rule
+// (include/avl_hip.h states it in full):
+//   candidate: a point that passes project(): 0 < v0 < range_max and 0 <= ix < img_w, 0 <= iy < img_h, on the grid or not;
+//   key q = (float)p2, p2 the third row of P . v; only a finite key > 0 is written to the buffer or compared;
+//   depth[iy / s][ix / s] = min of the keys' bit patterns (positive floats order as unsigned integers), 0xFFFFFFFF = empty;
+//   m = min of depth over the (2R + 1)^2 cells around the candidate's, clipped to the buffer;
+//   culled iff (double)q > (double)m * k + abs_tol (a multiplication and an addition, each rounded: -ffp-contract=off).
+// Integer atomicMin and, for the counts, integer atomicAdd only: the result does not depend on the order of the points.
+namespace {
+
+// what k_views_vote computes per view, with the divisor: true when the pixel lies in the image
+__device__ __forceinline__ bool project_view(const double* P, double v0, double v1, double v2, double v3, int img_w, int img_h, int& ix,
+                                             int& iy, double& p2) {
+    const double p0 = dot4(P + 0, v0, v1, v2, v3);
+    const double p1 = dot4(P + 4, v0, v1, v2, v3);
+    p2 = dot4(P + 8, v0, v1, v2, v3);
+    const double rp2 = refine_rcp(p2);
+    ix = div_i32_numpy(p0, p2, rp2);
+    iy = div_i32_numpy(p1, p2, rp2);
+    return ix >= 0 && ix < img_w && iy >= 0 && iy < img_h;
+}
+
+// the key of depth p2 as its bit pattern; false for a key that is not finite and > 0 (it is neither written nor culled)
+__device__ __forceinline__ bool depth_key(double p2, unsigned& bits) {
+    const float q = (float)p2;
+    bits = __float_as_uint(q);
+    return q > 0.0f && q < __builtin_inff();
+}
+
+__device__ __forceinline__ long long depth_cell(const OcclParams& oc, int v, int ix, int iy) {
+    return ((long long)v * oc.Hc + iy / oc.s) * oc.Wc + ix / oc.s;
+}
+
+// the cull test of a candidate of view v with a valid key: its own cell is in the neighbourhood, so m <= bits and m is a key
+__device__ __forceinline__ bool occl_culled(const OcclParams& oc, int v, int ix, int iy, unsigned bits) {
+    const int cx = ix / oc.s, cy = iy / oc.s;
+    const int x0 = max(cx - oc.R, 0), x1 = min(cx + oc.R, oc.Wc - 1), y0 = max(cy - oc.R, 0), y1 = min(cy + oc.R, oc.Hc - 1);
+    const unsigned* depth = oc.depth + (long long)v * oc.Hc * oc.Wc;
+    unsigned m = 0xffffffffu;
+    for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) m = min(m, depth[y * oc.Wc + x]);
+    return (double)__uint_as_float(bits) > (double)__uint_as_float(m) * oc.k + oc.abs_tol;
+}
+
+// culled candidates of one view: one atomic per wave that has any.  Every lane of the wave must arrive here.
+__device__ __forceinline__ void count_culled(int* counts, int v, bool culled) {
+    if (!counts) return;
+    const unsigned long long m = __ballot(culled);
+    if (m != 0ull && (threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(&counts[v], __builtin_popcountll(m));
+}
+
+// the label fetch of k_fused_vote / k_views_vote at pixel (ix, iy) -> vote bits
+template <int SRC>
+__device__ __forceinline__ unsigned fetch_vote(const GridParams& g, const LutParams& lut, const unsigned char* __restrict__ src, int src_w,
+                                               int src_h, int img_w, int img_h, int ix, int iy) {
+    if (SRC == AVL_SRC_RGB) {
+        const unsigned char* px = src + 3ll * ((long long)iy * src_w + ix);
+        return vote_from_rg(g, px[0], px[1]);
+    }
+    int sx = ix, sy = iy;                                                  // cv2 INTER_NEAREST source index, as k_fused_vote
+    if (src_w != img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)img_w)), src_w - 1);
+    if (src_h != img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)img_h)), src_h - 1);
+    return lut.lut[src[(long long)sy * src_w + sx]];
+}
+
+// Depth pass, one view or several: one read of the cloud, T and the range test once per point, one atomicMin per candidate and
+// view (no return value: nothing waits for it).  Off-grid points take part: an off-grid wall hides what is behind it.
+__global__ void __launch_bounds__(kBlock) k_occl_depth(PtsView pv, ViewsParams vp, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= pv.n) return;
+    double x, y, z, it;
+    load_point(pv, k, x, y, z, it);
+    double v0 = x, v1 = y, v2 = z, v3 = 1.0;
+    if (vp.has_T) {
+        v0 = dot4(vp.T + 0, x, y, z, 1.0);
+        v1 = dot4(vp.T + 4, x, y, z, 1.0);
+        v2 = dot4(vp.T + 8, x, y, z, 1.0);
+        v3 = dot4(vp.T + 12, x, y, z, 1.0);
+    }
+    if (!((0.0 < v0) && (v0 < vp.range_max))) return;
+    for (int v = 0; v < vp.n_views; ++v) {
+        int ix, iy;
+        double p2;
+        unsigned bits;
+        if (project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2) && depth_key(p2, bits))
+            atomicMin(&oc.depth[depth_cell(oc, v, ix, iy)], bits);
+    }
+}
+
+// k_fused_vote<SRC, MODE> with the cull test between the projection and the vote
+template <int SRC, int MODE>
+__global__ void __launch_bounds__(kBlock) k_fused_vote_occl(PtsView pv, ProjParams pp, GridParams g,
+                                                            const unsigned char* __restrict__ src, int src_w, int src_h,
+                                                            LutParams lut, unsigned* __restrict__ cell_mask,
+                                                            int* __restrict__ touched, int* __restrict__ counter, int list_cap, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned vote = 0;
+    bool culled = false;
+    if (k < pv.n) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        int ix, iy;
+        double p2;
+        if (project(pp, x, y, z, ix, iy, p2)) {
+            unsigned bits;
+            culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
+            if (!culled) cell = grid_cell(g, x, y, z);
+            if (cell >= 0) {
+                vote = fetch_vote<SRC>(g, lut, src, src_w, src_h, pp.img_w, pp.img_h, ix, iy);
+                vote = add_bonus(vote, g.bonus_classes, it);
+            }
+        }
+    }
+    count_culled(oc.culled, 0, culled);
+    if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
+    else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
+    else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
+    else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
+}
+
+// k_views_vote<SRC, LISTS> with the cull test per view.  Off-grid points are projected as well: they cast no vote, but a culled one
+// counts like any other candidate (the counts are those of k_occl_visibility's state 2).
+template <int SRC, int LISTS>
+__global__ void __launch_bounds__(kBlock) k_views_vote_occl(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LutParams lut,
+                                                            unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                            int* __restrict__ counter, int list_cap, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned word = 0;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0;
+    if (k < pv.n) {
+        double x, y, z;
+        load_point(pv, k, x, y, z, it);
+        v0 = x; v1 = y; v2 = z;
+        if (vp.has_T) {
+            v0 = dot4(vp.T + 0, x, y, z, 1.0);
+            v1 = dot4(vp.T + 4, x, y, z, 1.0);
+            v2 = dot4(vp.T + 8, x, y, z, 1.0);
+            v3 = dot4(vp.T + 12, x, y, z, 1.0);
+        }
+        positive = (0.0 < v0) && (v0 < vp.range_max);
+        if (positive) cell = grid_cell(g, x, y, z);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {                                 // the same trip count in every lane: count_culled ballots
+        bool culled = false;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
+            unsigned bits;
+            culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
+            if (!culled && cell >= 0) {
+                unsigned vote = fetch_vote<SRC>(g, lut, vp.src[v], src_w, src_h, vp.img_w, vp.img_h, ix, iy);
+                vote = add_bonus(vote, g.bonus_classes, it);
+                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
+            }
+        }
+        count_culled(oc.culled, v, culled);
+    }
+    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
+    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);
+}
+
+// One state per point and view: 0 not a candidate, 1 visible, 2 culled; key (optional): the candidate's float32 depth, 0 for the rest.
+// Reads the depth buffer k_occl_depth filled.
+__global__ void __launch_bounds__(kBlock) k_occl_visibility(PtsView pv, ViewsParams vp, OcclParams oc, unsigned char* __restrict__ state,
+                                                            float* __restrict__ key) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = k < pv.n;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
+    if (live) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        v0 = x; v1 = y; v2 = z;
+        if (vp.has_T) {
+            v0 = dot4(vp.T + 0, x, y, z, 1.0);
+            v1 = dot4(vp.T + 4, x, y, z, 1.0);
+            v2 = dot4(vp.T + 8, x, y, z, 1.0);
+            v3 = dot4(vp.T + 12, x, y, z, 1.0);
+        }
+        positive = (0.0 < v0) && (v0 < vp.range_max);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {
+        unsigned char st = 0;
+        unsigned bits = 0u;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2))
+            st = (depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits)) ? 2 : 1;
+        if (live) {
+            state[(long long)v * pv.n + k] = st;
+            if (key) key[(long long)v * pv.n + k] = st ? __uint_as_float(bits) : 0.0f;
+        }
+        count_culled(oc.culled, v, st == 2);
+    }
+}
+
+long long occl_cells(int img_w, int img_h, int s) { return (long long)((img_w + s - 1) / s) * ((img_h + s - 1) / s); }
+
+int occl_fill(OcclParams& oc, const avl_occlusion* occl, int img_w, int img_h, int n_views) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    AVL_REQUIRE(occl->cell_px >= 1 && occl->cell_px <= 64, "occlusion cell_px = %d (1..64)", occl->cell_px);
+    AVL_REQUIRE(occl->radius >= 0 && occl->radius <= 2, "occlusion radius = %d (0..2)", occl->radius);
+    AVL_REQUIRE(occl->rel_tol >= 0.0, "occlusion rel_tol = %g (must be >= 0)", occl->rel_tol);     // a NaN fails the comparison too
+    AVL_REQUIRE(occl->abs_tol >= 0.0, "occlusion abs_tol = %g (must be >= 0)", occl->abs_tol);
+    AVL_REQUIRE(img_w > 0 && img_h > 0 && n_views >= 1 && n_views <= kMaxViews, "occlusion: %d views of %dx%d", n_views, img_w, img_h);
+    const long long words = occl_cells(img_w, img_h, occl->cell_px) * n_views;
+    AVL_REQUIRE(occl->depth, "occlusion depth scratch is NULL");
+    AVL_REQUIRE(occl->depth_words >= words, "occlusion depth scratch holds %lld words, %lld needed", (long long)occl->depth_words, words);
+    AVL_REQUIRE(words * 4 <= 0x7fffffffLL, "occlusion depth buffer of %lld words is too large", words);
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->depth) & 3) == 0, "occlusion depth scratch is not 4-byte aligned");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->culled) & 3) == 0, "occlusion culled counts are not 4-byte aligned");
+    oc.depth = occl->depth;
+    oc.culled = occl->culled;
+    oc.k = 1.0 + occl->rel_tol;
+    oc.abs_tol = occl->abs_tol;
+    oc.s = occl->cell_px;
+    oc.R = occl->radius;
+    oc.Wc = (img_w + oc.s - 1) / oc.s;
+    oc.Hc = (img_h + oc.s - 1) / oc.s;
+    return AVL_OK;
+}
+
+int occl_reset(const OcclParams& oc, int n_views, bool depth, hipStream_t s) {
+    if (depth) AVL_HIP_CHECK(hipMemsetAsync(oc.depth, 0xff, sizeof(unsigned) * (size_t)n_views * oc.Hc * oc.Wc, s));
+    if (oc.culled) AVL_HIP_CHECK(hipMemsetAsync(oc.culled, 0, sizeof(int) * n_views, s));
+    return AVL_OK;
+}
+
+int launch_occl_depth(const PtsView& pv, const ViewsParams& vp, const OcclParams& oc, hipStream_t s) {
+    hipLaunchKernelGGL(k_occl_depth, dim3((pv.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pv, vp, oc);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+int launch_fused_vote_occl(const FrameArgs& f, int src_kind, int mode, const uint8_t* src, int src_w, int src_h, const avl_grid* g, int list_cap,
+                           const OcclParams& oc, hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+#define AVL_FVO(SRC, MODE) hipLaunchKernelGGL((k_fused_vote_occl<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
+    if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FVO(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FVO(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FVO(AVL_SRC_RGB, 1); else AVL_FVO(AVL_SRC_RGB, 0); }
+    else { if (mode == 3) AVL_FVO(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FVO(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FVO(AVL_SRC_CLASSMAP, 1); else AVL_FVO(AVL_SRC_CLASSMAP, 0); }
+#undef AVL_FVO
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+int launch_views_vote_occl(const FrameArgs& f, const ViewsParams& vp, int src_kind, bool lists, int src_w, int src_h, const avl_grid* g,
+                           int list_cap, const OcclParams& oc, hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+#define AVL_VVO(SRC, LISTS) hipLaunchKernelGGL((k_views_vote_occl<SRC, LISTS>), grid, block, 0, s, f.pv, vp, f.gp, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
+    if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VVO(AVL_SRC_RGB, 1); else AVL_VVO(AVL_SRC_RGB, 0); }
+    else { if (lists) AVL_VVO(AVL_SRC_CLASSMAP, 1); else AVL_VVO(AVL_SRC_CLASSMAP, 0); }
+#undef AVL_VVO
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t avl_occlusion_depth_words(int img_w, int img_h, int cell_px, int n_views) {
+    if (img_w <= 0 || img_h <= 0 || cell_px < 1 || cell_px > 64 || n_views < 1) return 0;
+    return occl_cells(img_w, img_h, cell_px) * n_views;
+}
+
+extern "C" int avl_fused_frame_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                    const double* P_host, const double* T_host, double range_max, int src_kind, const uint8_t* src,
+                                    int src_w, int src_h, int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host,
+                                    const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
+                       lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
+}
+
+extern "C" int avl_fused_frame_views_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                          int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                                          const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                          const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                          uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src_kind, src_host, src_w, src_h,
+                             img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
+}
+
+extern "C" int avl_occlusion_visibility(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                                        const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
+                                        const avl_occlusion* occl, uint8_t* state, float* key, void* stream) {
+    FrameArgs f;
+    OcclParams oc;
+    int rc;
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    AVL_REQUIRE(n == 0 || state, "state is NULL");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(key) & 3) == 0, "key is not 4-byte aligned");
+    hipStream_t s = avl::as_stream(stream);
+    if (n == 0) return occl_reset(oc, n_views, false, s);
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    if ((rc = occl_reset(oc, n_views, true, s))) return rc;
+    if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+    hipLaunchKernelGGL(k_occl_visibility, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, oc, state, key);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
 }

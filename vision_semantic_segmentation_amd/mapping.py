@@ -21,6 +21,9 @@ What differs from the reference, by design:
   * ``live_map()`` renders the window of the grid around the vehicle (filter, renderer, hole fill, ego car) in one kernel; with
     MAPPING.LIVE_MAP.ENABLED ``mapping()`` / ``mapping_views()`` do so after the grid update.  The reference renders once, at
     shutdown.
+  * with MAPPING.OCCLUSION.ENABLED, points hidden behind nearer ones in a view's image do not vote (a per-view depth buffer, the
+    rule at struct avl_occlusion in include/avl_hip.h); ``visibility_device()`` returns the verdict per point.  The reference lets
+    every point that lands in the image vote.  Off by default.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -192,6 +195,11 @@ class SemanticMapping(object):
         self.live_map_ready = None             # event recorded behind the copy into live_map_host
         self.pub_semantic_local_map = getattr(self, "pub_semantic_local_map", None)
         self._live_pose = None
+
+        # occlusion culling (MAPPING.OCCLUSION); off by default: then nothing below is touched
+        self.occlusion_cfg = getattr(cfg.MAPPING, "OCCLUSION", None)
+        self.last_culled = None                # int32 CUDA tensor [V]: culled candidates per view of the last culling call (no sync to fill it)
+        self._occl_depth = {}                  # (V, Hc, Wc) -> the depth scratch of that shape
 
         # device-side caches
         self._scratch = None
@@ -564,19 +572,77 @@ class SemanticMapping(object):
             msg.header.frame_id = "semantic_local_map"
             self.pub_semantic_local_map.publish(msg)
 
+    # ------------------------------------------------------------------ occlusion culling (MAPPING.OCCLUSION)
+    def occlusion_enabled(self):
+        return self.occlusion_cfg is not None and bool(self.occlusion_cfg.ENABLED)
+
+    def _occlusion(self, V, ih, iw, culled=None):
+        """struct avl_occlusion for V views of an ih x iw projection image, from MAPPING.OCCLUSION.  The depth scratch is allocated on
+        first use per (V, Hc, Wc) and reused (every call resets it itself).  ``culled``: (int32 CUDA tensor, first element) that
+        receives the V counts; None = a fresh-or-reused ``self.last_culled`` of V elements."""
+        oc = self.occlusion_cfg
+        s = int(oc.CELL_PX)
+        words = int(_lib.lib().avl_occlusion_depth_words(int(iw), int(ih), s, int(V)))
+        if words <= 0:
+            raise ValueError("MAPPING.OCCLUSION.CELL_PX = %r (1..64) for %d views of %dx%d" % (oc.CELL_PX, V, iw, ih))
+        key = (int(V), -(-int(ih) // s), -(-int(iw) // s))
+        depth = self._occl_depth.get(key)
+        if depth is None:
+            depth = self._occl_depth[key] = torch.empty(words, dtype=torch.int32, device=self.device)
+        if culled is None:
+            if self.last_culled is None or int(self.last_culled.numel()) != V:
+                self.last_culled = torch.zeros(V, dtype=torch.int32, device=self.device)
+            culled = (self.last_culled, 0)
+        o = _lib.AvlOcclusion()
+        o.cell_px, o.radius = s, int(oc.RADIUS)
+        o.rel_tol, o.abs_tol = float(oc.REL_TOL), float(oc.ABS_TOL)
+        o.depth, o.depth_words = depth.data_ptr(), words
+        o.culled = culled[0].data_ptr() + 4 * int(culled[1])
+        return o
+
+    def visibility_device(self, pcd, pcd_frame_id, pose, cameras, image_size, return_keys=False):
+        """The occlusion rule alone (avl_occlusion_visibility, MAPPING.OCCLUSION's parameters whether ENABLED or not): for every
+        camera of ``cameras`` (one calibration or a list) and every point of ``pcd``, 0 = the point is no candidate of that view
+        (behind the vehicle, out of range or outside the ``image_size`` = (H, W) image), 1 = visible, 2 = culled.  Returns a uint8
+        CUDA tensor [V, N]; with ``return_keys`` also the float32 depth keys [V, N] (0 where the state is 0).  ``last_culled``
+        receives the per-view counts of state 2.  A caller who wants a culled semantic cloud filters project_pcd's input with it."""
+        cameras = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+        V = len(cameras)
+        if V < 1:
+            raise ValueError("visibility_device needs at least one camera")
+        ih, iw = int(image_size[0]), int(image_size[1])
+        n = int(_lib.points_view(pcd, self.device)[1])
+        state = torch.empty((V, n), dtype=torch.uint8, device=self.device)
+        keys = torch.empty((V, n), dtype=torch.float32, device=self.device) if return_keys else None
+        self.last_culled = torch.zeros(V, dtype=torch.int32, device=self.device)
+        for v0 in range(0, V, _lib.AVL_MAX_VIEWS):
+            cams = cameras[v0:v0 + _lib.AVL_MAX_VIEWS]
+            view, T, _, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(c.P, dtype=np.float64) for c in cams]), grid=False)
+            occ = self._occlusion(len(cams), ih, iw, culled=(self.last_culled, v0))
+            rc = _lib.lib().avl_occlusion_visibility(*view, len(cams), P, T, float(self.pcd_range_max), iw, ih, C.byref(occ),
+                                                     _ptr(state[v0:]), _ptr(keys[v0:]) if return_keys else None, s)
+            _lib.check(rc, "avl_occlusion_visibility")
+        return (state, keys) if return_keys else state
+
     def frame_device(self, pcd, pcd_frame_id, semantic, pose, camera_calibration, src_kind="rgb",
-                     image_size=None, net_palette=PALETTE_19, stream=None):
-        """Fused frame (avl_fused_frame).  ``pcd``: NumPy/torch [4,N] float64|float32 (SoA, the
-        reference layout) or [N,4] float32 (AoS); ``semantic``: CUDA uint8 tensor, either the colour
+                     image_size=None, net_palette=PALETTE_19, stream=None, _culled=None):
+        """Fused frame (avl_fused_frame; avl_fused_frame_occl with MAPPING.OCCLUSION.ENABLED).  ``pcd``: NumPy/torch [4,N]
+        float64|float32 (SoA, the reference layout) or [N,4] float32 (AoS); ``semantic``: CUDA uint8 tensor, either the colour
         image [H,W,3] (src_kind="rgb") or a class-id map [h,w] (src_kind="classmap", sampled as the
         nearest-upscaled image of size ``image_size`` = (H, W))."""
         assert semantic.dtype == torch.uint8
         sh, sw, ih, iw, kind, lut = self._semantic_source(semantic.shape, src_kind, image_size, net_palette)
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, camera_calibration.P, stream)
         semantic = semantic.contiguous()
-        rc = _lib.lib().avl_fused_frame(C.byref(gs), *view, P, T, float(self.pcd_range_max), kind, _ptr(semantic), sw, sh, iw, ih, lut,
-                                        self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), s)
-        _lib.check(rc, "avl_fused_frame")
+        if self.occlusion_enabled():
+            occ = self._occlusion(1, ih, iw, _culled)
+            rc = _lib.lib().avl_fused_frame_occl(C.byref(gs), *view, P, T, float(self.pcd_range_max), kind, _ptr(semantic), sw, sh, iw, ih, lut,
+                                                 self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), C.byref(occ), s)
+            _lib.check(rc, "avl_fused_frame_occl")
+        else:
+            rc = _lib.lib().avl_fused_frame(C.byref(gs), *view, P, T, float(self.pcd_range_max), kind, _ptr(semantic), sw, sh, iw, ih, lut,
+                                            self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), s)
+            _lib.check(rc, "avl_fused_frame")
         self._map_host = None
         self.frames_mapped += 1
 
@@ -606,17 +672,27 @@ class SemanticMapping(object):
                 raise ValueError("the views' semantic sources must be uint8 CUDA tensors of one size")
         sh, sw, ih, iw, kind, lut = self._semantic_source(shape, src_kind, image_size, net_palette)
         bonus = self._bonus_classes()
+        occlusion = self.occlusion_enabled()
         if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
-            for t, cam in zip(views, cameras):
+            culled = torch.zeros(V, dtype=torch.int32, device=self.device) if occlusion else None
+            for v, (t, cam) in enumerate(zip(views, cameras)):
                 self.frame_device(pcd, pcd_frame_id, t, pose, cam, src_kind=src_kind, image_size=image_size, net_palette=net_palette,
-                                  stream=stream)
+                                  stream=stream, _culled=(culled, v) if occlusion else None)
+            if occlusion:
+                self.last_culled = culled
             return
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]), stream)
         views = [t.contiguous() for t in views]
         src = (C.c_void_p * V)(*[t.data_ptr() for t in views])
-        rc = _lib.lib().avl_fused_frame_views(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
-                                              self._colors_host(), _dbl(self.confusion_matrix), bonus, s)
-        _lib.check(rc, "avl_fused_frame_views")
+        if occlusion:
+            occ = self._occlusion(V, ih, iw)
+            rc = _lib.lib().avl_fused_frame_views_occl(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
+                                                       self._colors_host(), _dbl(self.confusion_matrix), bonus, C.byref(occ), s)
+            _lib.check(rc, "avl_fused_frame_views_occl")
+        else:
+            rc = _lib.lib().avl_fused_frame_views(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
+                                                  self._colors_host(), _dbl(self.confusion_matrix), bonus, s)
+            _lib.check(rc, "avl_fused_frame_views")
         self._map_host = None
         self.frames_mapped += V
 

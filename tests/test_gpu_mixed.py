@@ -1065,7 +1065,7 @@ def test_mx_grouped_conv(case, in_lo, cuda_device):
                     rows_in).to(cuda_device)
     rows = (OH * OW + 255) // 256 * 256
     dst = torch.full((rows, width), 7.0, dtype=torch.float16, device=cuda_device)
-    out_mx = torch.zeros(2 * mx_bundle_bytes(rows, width), dtype=torch.uint8, device=cuda_device)
+    out_mx = torch.full((2 * mx_bundle_bytes(rows, width),), 0xA5, dtype=torch.uint8, device=cuda_device)
     frag, bundle = pack_gconv_mx(w64, G)
     wd, wb, bd = frag.reshape(-1).to(cuda_device), bundle.to(cuda_device), b.to(cuda_device)
     _run_plan([_spatial_op(OP_GCONV, _lib.AVL_F16, src, (H, W), width, dst, (OH, OW), width, weight=wd.data_ptr(), bias=bd.data_ptr(),
@@ -1078,3 +1078,11 @@ def test_mx_grouped_conv(case, in_lo, cuda_device):
     err = float((got - want).abs().max() / want.abs().max())
     assert err <= 2 ** -11 * 0.3, "mx grouped conv %s in_lo=%s: %.3e" % (case, in_lo, err)
     assert torch.all(dst[M:] == 7.0)
+    # the Q4(hi) half is the host's quantisation of the hi plane the kernel wrote, byte for byte; rows past M keep the fill in both
+    # halves' planes and scale slabs
+    q_hi, s_hi = _unbundle_raw(out_mx.cpu(), rows, width, 0)
+    q_ref, s_ref = mx_quant_fp4(dst[:M].cpu().double())
+    assert torch.equal(q_hi[:M], q_ref) and torch.equal(s_hi[:, :M], s_ref), "mx grouped conv %s in_lo=%s: Q4(hi) half" % (case, in_lo)
+    for half in (0, 1):
+        q, sc = _unbundle_raw(out_mx.cpu(), rows, width, half)
+        assert torch.all(q[M:] == 0xA5) and torch.all(sc[:, M:] == 0xA5), "mx grouped conv %s: half %d written past row M" % (case, half)

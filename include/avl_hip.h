@@ -234,6 +234,64 @@ int avl_occlusion_visibility(const void* pts, int n, int dtype, int64_t point_st
                              const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
                              int img_w, int img_h, const avl_occlusion* occl, uint8_t* state, float* key, void* stream);
 
+/* ---- a9p: points labelled from interpolated logits, with a confidence gate (not in the reference) ---------- */
+
+/* The class-map source gives a point the arg-max of the nearest pixel of the network's low-resolution output.  The reference model
+ * predicts more finely: DeepLabV3Plus.forward(x, upsample_pred=True) interpolates the logits bilinearly (align_corners=True) to the
+ * input's size and takes the arg-max there (deeplab_v3_plus.py:67-69).  The calls below read a plan's fp32 logits (h x w pixels of K
+ * classes, `ld` floats from one pixel to the next) and evaluate that prediction only at the pixels the points project to; they also
+ * know how sure the network was there and let a point abstain.  THE RULE, for one candidate point of one view (a candidate is a point
+ * that passes the test of :378-383 as avl_fused_frame computes it); every float32 operation below is rounded on its own (no fused
+ * multiply-add), which is what NumPy float32 arithmetic does:
+ *   1. (ix, iy): the pixel of the img_w x img_h projection image, as avl_fused_frame computes it.
+ *   2. (nx, ny): the pixel of the net_w x net_h network-input image that (ix, iy) stands for, by the cv2 INTER_NEAREST index rule of
+ *      the class-map source: nx = ix when net_w == img_w, else min((int)floor((double)ix * ((double)net_w / (double)img_w)), net_w - 1);
+ *      ny alike.
+ *   3. scales, computed once on the host as avl_seg_eval_full_res computes them: sy = net_h > 1 ? (float)(h - 1) / (float)(net_h - 1)
+ *      : 0, sx alike.  fy = sy * (float)ny and fx = sx * (float)nx, each rounded; y0 = min((int)fy, h - 1), y1 = y0 + (y0 < h - 1),
+ *      ly = fy - (float)y0, hy = 1 - ly; x0, x1, lx, hx alike.
+ *   4. z[k] = hy * (hx * a + lx * b) + ly * (hx * c + lx * d) for k = 0 .. K - 1, with a, b, c, d the logits of class k at
+ *      (y0, x0), (y0, x1), (y1, x0), (y1, x1): seven operations, seven roundings.
+ *   5. top = the first maximal index of z, a NaN counting as maximal (AVL_OP_ARGMAX's rule: k replaces the running best when
+ *      z[k] > best, or when z[k] is a NaN and best is not).  margin = z[top] - max(z[k], k != top) in float32; +inf when K = 1.
+ *   6. the point votes lut[top] iff !(margin < min_margin); otherwise it abstains: it casts no vote in that view, like a pixel of
+ *      label 255.  So min_margin = 0 gates nothing, and a NaN margin (a NaN logit, or inf - inf) votes.
+ * Everything else is avl_fused_frame's: the intensity bonus, the vote masks, the apply.  The grid after a call equals, bit for bit, what
+ * the class-map call does when fed the net_h x net_w label map of rule 3 - 6 at every pixel (255 where the pixel abstains). */
+typedef struct avl_point_logits {
+    const float* logits[AVL_MAX_VIEWS]; /* per view: device fp32 [h][w] pixels of `ld` floats, the first K the classes; 4-byte aligned */
+    int h, w, K;                        /* logits size; 1 <= K <= 254 (states 254 and 255 are taken)                                   */
+    int64_t ld;                         /* floats from one pixel to the next, >= K                                                     */
+    int net_h, net_w;                   /* the size the logits are interpolated to: the network's input                               */
+    float min_margin;                   /* >= 0; a point whose margin is below it abstains                                             */
+    int32_t* abstained;                 /* int32[n_views] or NULL: receives, per view, the abstentions of the call (below)            */
+} avl_point_logits;
+
+/* avl_fused_frame / avl_fused_frame_views with the logits as the semantic source, and with `occl` != NULL avl_fused_frame_occl /
+ * avl_fused_frame_views_occl's culling between the projection and the rule above (a culled candidate is not evaluated).  lut_host:
+ * uint32[256], network class -> vote bits.  The path is avl_fused_frame_path's / avl_fused_frame_views_path's for the same n; the
+ * apply and sweep kernels are the plain calls'.  abstained[v] receives the number of view v's candidates that fall on the grid, are
+ * not culled and abstain -- the votes the gate withheld; the call resets it itself (one integer atomic per wave that has any).
+ * AVL_E_ARG, before any GPU work, for what the plain calls refuse and for a NULL pl, a NULL or misaligned logits pointer of a view in
+ * use, K outside 1..254, ld < K, a non-positive size, a NaN or negative min_margin, a misaligned abstained, n_views outside
+ * 1..AVL_MAX_VIEWS, and what avl_fused_frame_occl refuses of a non-NULL occl. */
+int avl_fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                           const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl,
+                           int img_w, int img_h, const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes,
+                           const avl_occlusion* occl, void* stream);
+int avl_fused_frame_views_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                 int n_views, const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
+                                 const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host, const double* cm_host,
+                                 uint32_t bonus_classes, const avl_occlusion* occl, void* stream);
+
+/* The rule alone, for 1 <= n_views <= AVL_MAX_VIEWS views of one cloud (points addressed as in avl_project_points), on the grid or
+ * not: state uint8[n_views][n] = top for a candidate that votes, 254 for one that abstains, 255 for a point that is no candidate of
+ * the view; margin float[n_views][n] (or NULL) = the candidate's margin, 0 where the state is 255.  pl->abstained, when given,
+ * receives the number of state-254 points per view. */
+int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                     const double* P_host /* [n_views][12] */, const double* T_host, double range_max, int img_w, int img_h,
+                     const avl_point_logits* pl, uint8_t* state, float* margin, void* stream);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

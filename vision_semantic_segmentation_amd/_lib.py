@@ -13,6 +13,7 @@ AVL_F32, AVL_F64, AVL_BF16, AVL_F16 = 0, 1, 2, 3
 AVL_SRC_RGB, AVL_SRC_CLASSMAP = 0, 1
 AVL_MAX_MAP_CLASSES = 16
 AVL_MAX_VIEWS = 4               # views of one avl_fused_frame_views call
+AVL_LABEL_ABSTAINED, AVL_LABEL_NONE = 254, 255   # avl_point_labels' states beside the classes
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
 AVL_LIVE_FILTER, AVL_LIVE_THRESHOLDS, AVL_LIVE_FILL = 1, 2, 4   # avl_live_map's flags
 AVL_LIVE_CAR_DOUBLES = 8        # avl_live_map's car block
@@ -45,6 +46,14 @@ class AvlOcclusion(C.Structure):
     ]
 
 
+class AvlPointLogits(C.Structure):
+    """struct avl_point_logits of include/avl_hip.h"""
+    _fields_ = [
+        ("logits", C.c_void_p * AVL_MAX_VIEWS), ("h", C.c_int), ("w", C.c_int), ("K", C.c_int), ("ld", C.c_int64),
+        ("net_h", C.c_int), ("net_w", C.c_int), ("min_margin", C.c_float), ("abstained", C.c_void_p),
+    ]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
 _SIGNATURES = {
@@ -68,6 +77,11 @@ _SIGNATURES = {
     "avl_fused_frame_views_occl": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
                                         _vp, _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
     "avl_occlusion_visibility": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlOcclusion), _vp, _vp, _vp]),
+    "avl_fused_frame_logits": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _vp, _vp, _d, C.POINTER(AvlPointLogits), _i, _i,
+                                    _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
+    "avl_fused_frame_views_logits": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, C.POINTER(AvlPointLogits), _i, _i,
+                                          _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
+    "avl_point_labels": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlPointLogits), _vp, _vp, _vp]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -175,6 +175,12 @@ def get_cfg_defaults():
     C.MAPPING.OCCLUSION.RADIUS = 1                        # 0..2 cells
     C.MAPPING.OCCLUSION.REL_TOL = 0.05
     C.MAPPING.OCCLUSION.ABS_TOL = 0.5                     # metres
+    # build-specific: the confidence gate of the logits source (frame_device(..., src_kind="logits")).  A point takes the arg-max of the
+    # plan's logits interpolated at its pixel; when the top-1 minus top-2 margin (fp32 logit units) is below MIN_MARGIN it abstains
+    # instead of voting (the rule: include/avl_hip.h, avl_point_logits).  0.0 gates nothing.  A float >= 0 (SemanticMapping refuses
+    # anything else).  The other sources ignore it
+    C.MAPPING.CONFIDENCE = CfgNode()
+    C.MAPPING.CONFIDENCE.MIN_MARGIN = 0.0
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

@@ -1133,6 +1133,13 @@ void fill_views(ViewsParams& vp, const FrameArgs& f, int n_views, const double* 
     vp.img_h = f.pp.img_h;
 }
 
+// what follows the vote kernel of path `mode` (avl_fused_frame_path) for a cloud of n points
+int apply_frame(const avl_grid* g, const double* cm_host, uint32_t bonus_classes, int mode, int n, hipStream_t s) {
+    if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
+    if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
+    return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
+}
+
 // avl_fused_frame, and with `occl` avl_fused_frame_occl: the path is decided from n alike, the depth pass runs first and the vote
 // kernel is the culling twin; the apply and sweep kernels are the same.
 int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
@@ -1168,9 +1175,7 @@ int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t po
 #undef AVL_FV
         AVL_LAUNCH_CHECK();
     }
-    if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
-    if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
-    return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
+    return apply_frame(g, cm_host, bonus_classes, mode, n, s);
 }
 
 }  // namespace
@@ -1295,6 +1300,24 @@ extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views,
 }
 
 namespace {
+// what follows the views vote kernel: the lists' apply (path 4) or the sweep of the word mask (path 5)
+int apply_views(const avl_grid* g, const CmParams& cm, uint32_t bonus_classes, bool lists, const ListGeom& lg, hipStream_t s) {
+    const dim3 block(kBlock);
+    if (lists)
+        return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
+            typedef decltype(t) T;
+            hipLaunchKernelGGL(k_views_apply_lists<T>, dim3(lg.apply_wgs), block, 0, s, static_cast<T*>(g->map), g->C, bonus_classes, cm,
+                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
+        }), s);
+    const long long ncell = (long long)g->Hm * g->Wm;
+    const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
+                           bonus_classes, cm, g->cell_mask, ncell, vec);
+    });
+}
+
 // avl_fused_frame_views, and with `occl` avl_fused_frame_views_occl (as fused_frame: same path, depth pass first, culling vote twin)
 int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
                       int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
@@ -1333,19 +1356,7 @@ int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int6
 #undef AVL_VV
         AVL_LAUNCH_CHECK();
     }
-    if (lists)
-        return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
-            typedef decltype(t) T;
-            hipLaunchKernelGGL(k_views_apply_lists<T>, dim3(lg.apply_wgs), block, 0, s, static_cast<T*>(g->map), g->C, bonus_classes, cm,
-                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-        }), s);
-    const long long ncell = (long long)g->Hm * g->Wm;
-    const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
-    return launch_map_typed(g->map_dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
-                           bonus_classes, cm, g->cell_mask, ncell, vec);
-    });
+    return apply_views(g, cm, bonus_classes, lists, lg, s);
 }
 }  // namespace
 
@@ -1919,6 +1930,334 @@ extern "C" int avl_occlusion_visibility(const void* pts, int n, int dtype, int64
     if ((rc = occl_reset(oc, n_views, true, s))) return rc;
     if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
     hipLaunchKernelGGL(k_occl_visibility, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, oc, state, key);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+// ================================================================ points labelled from interpolated logits (avl_fused_frame_logits and its kin)
+// The class-map source hands a point the arg-max of the nearest low-resolution pixel.  These kernels read the plan's fp32 logits
+// instead and evaluate the reference model's full-resolution prediction (bilinear, align_corners=True, then arg-max:
+// deeplab_v3_plus.py:67-69) at the point's pixel alone, with the top-1 minus top-2 margin as a confidence: a point whose margin is
+// below min_margin abstains.  The rule is stated in full at struct avl_point_logits in include/avl_hip.h; the interpolation is that of
+// seg_head.hip (src_coord, corner, lerp4) with every float32 operation rounded on its own, which -ffp-contract=off gives here.
+// What a lane fetches: the K logits of four source pixels, each a run of K consecutive floats (76 bytes at K = 19, ld = K: 4-byte
+// aligned only, so no lane can count on a 16-byte boundary).  The loop takes four classes of each corner at a time -- sixteen
+// independent loads in flight before the first is used, which the compiler merges into dwordx4 / dwordx2 loads of 4-byte alignment
+// (gfx950 allows them on global memory) -- and keeps only the running best, second best and index.
+namespace {
+
+struct LogitsParams {
+    const float* logits[kMaxViews];
+    int* abstained;                   // [n_views] abstentions, or NULL
+    long long ld;
+    int h, w, K, net_h, net_w;
+    float sy, sx, min_margin;
+};
+
+// One more class for the running arg-max: the first maximal index wins and a NaN counts as maximal (AVL_OP_ARGMAX, eval_pixel of
+// seg_head.hip); `second` follows as the largest of the others.  best = second = -inf, top = 0 to start with.
+__device__ __forceinline__ void take_logit(float v, int k, float& best, float& second, int& top) {
+    if (v > best || (v != v && best == best)) { second = best; best = v; top = k; }
+    else if (v > second) second = v;
+}
+
+// rules 2 - 5 at pixel (ix, iy) of the img_w x img_h projection image: -> top, and the margin
+__device__ __forceinline__ int point_label(const LogitsParams& lp, const float* __restrict__ src, int img_w, int img_h, int ix, int iy,
+                                           float& margin) {
+    int nx = ix, ny = iy;                                                  // the index rule of fetch_vote, towards the network's input
+    if (lp.net_w != img_w) nx = min((int)__builtin_floor((double)ix * ((double)lp.net_w / (double)img_w)), lp.net_w - 1);
+    if (lp.net_h != img_h) ny = min((int)__builtin_floor((double)iy * ((double)lp.net_h / (double)img_h)), lp.net_h - 1);
+    const float fy = lp.sy * (float)ny, fx = lp.sx * (float)nx;
+    const int y0 = min((int)fy, lp.h - 1), x0 = min((int)fx, lp.w - 1);
+    const int y1 = y0 + (y0 < lp.h - 1 ? 1 : 0), x1 = x0 + (x0 < lp.w - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float* __restrict__ a = src + ((long long)y0 * lp.w + x0) * lp.ld;
+    const float* __restrict__ b = src + ((long long)y0 * lp.w + x1) * lp.ld;
+    const float* __restrict__ c = src + ((long long)y1 * lp.w + x0) * lp.ld;
+    const float* __restrict__ d = src + ((long long)y1 * lp.w + x1) * lp.ld;
+    float best = -__builtin_inff(), second = -__builtin_inff();
+    int top = 0, k = 0;
+    for (; k + 4 <= lp.K; k += 4) {
+        float va[4], vb[4], vc[4], vd[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { va[j] = a[k + j]; vb[j] = b[k + j]; vc[j] = c[k + j]; vd[j] = d[k + j]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) take_logit(hy * (hx * va[j] + lx * vb[j]) + ly * (hx * vc[j] + lx * vd[j]), k + j, best, second, top);
+    }
+    for (; k < lp.K; ++k) take_logit(hy * (hx * a[k] + lx * b[k]) + ly * (hx * c[k] + lx * d[k]), k, best, second, top);
+    margin = lp.K == 1 ? __builtin_inff() : best - second;
+    return top;
+}
+
+// k_fused_vote<AVL_SRC_CLASSMAP, MODE> with the label and its gate computed from the logits; OCCL: the cull test of k_fused_vote_occl
+// between the projection and the fetch (a culled candidate is not evaluated and does not count as an abstention)
+template <int MODE, int OCCL>
+__global__ void __launch_bounds__(kBlock) k_fused_vote_logits(PtsView pv, ProjParams pp, GridParams g, LogitsParams lp, LutParams lut,
+                                                              unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                              int* __restrict__ counter, int list_cap, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned vote = 0;
+    bool culled = false, abstains = false;
+    if (k < pv.n) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        int ix, iy;
+        double p2;
+        if (project(pp, x, y, z, ix, iy, p2)) {
+            if (OCCL) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
+            }
+            if (!culled) cell = grid_cell(g, x, y, z);
+            if (cell >= 0) {
+                float margin;
+                const int top = point_label(lp, lp.logits[0], pp.img_w, pp.img_h, ix, iy, margin);
+                abstains = margin < lp.min_margin;
+                if (!abstains) vote = add_bonus(lut.lut[top], g.bonus_classes, it);
+            }
+        }
+    }
+    if (OCCL) count_culled(oc.culled, 0, culled);
+    count_culled(lp.abstained, 0, abstains);
+    if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
+    else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
+    else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
+    else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
+}
+
+// k_views_vote<AVL_SRC_CLASSMAP, LISTS> with one logits image per view.  Without OCCL an off-grid point is not projected (as in
+// k_views_vote); with it, it is, because a culled off-grid candidate counts (k_views_vote_occl).  Every lane runs the loop over the
+// views: the counts ballot.
+template <int LISTS, int OCCL>
+__global__ void __launch_bounds__(kBlock) k_views_vote_logits(PtsView pv, ViewsParams vp, GridParams g, LogitsParams lp, LutParams lut,
+                                                              unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                              int* __restrict__ counter, int list_cap, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned word = 0;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0;
+    if (k < pv.n) {
+        double x, y, z;
+        load_point(pv, k, x, y, z, it);
+        v0 = x; v1 = y; v2 = z;
+        if (vp.has_T) {
+            v0 = dot4(vp.T + 0, x, y, z, 1.0);
+            v1 = dot4(vp.T + 4, x, y, z, 1.0);
+            v2 = dot4(vp.T + 8, x, y, z, 1.0);
+            v3 = dot4(vp.T + 12, x, y, z, 1.0);
+        }
+        positive = (0.0 < v0) && (v0 < vp.range_max);
+        if (positive) cell = grid_cell(g, x, y, z);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {
+        bool culled = false, abstains = false;
+        int ix, iy;
+        double p2;
+        if (positive && (OCCL || cell >= 0) && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
+            if (OCCL) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
+            }
+            if (!culled && cell >= 0) {
+                float margin;
+                const int top = point_label(lp, lp.logits[v], vp.img_w, vp.img_h, ix, iy, margin);
+                abstains = margin < lp.min_margin;
+                if (!abstains) {
+                    const unsigned vote = add_bonus(lut.lut[top], g.bonus_classes, it);
+                    word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
+                }
+            }
+        }
+        if (OCCL) count_culled(oc.culled, v, culled);
+        count_culled(lp.abstained, v, abstains);
+    }
+    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
+    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);
+}
+
+// The rule alone, per point and view, on the grid or not: state = top, 254 = abstained, 255 = no candidate of the view; margin
+// (optional) = the candidate's margin, 0 for the rest.
+__global__ void __launch_bounds__(kBlock) k_point_labels(PtsView pv, ViewsParams vp, LogitsParams lp, unsigned char* __restrict__ state,
+                                                         float* __restrict__ margin) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = k < pv.n;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
+    if (live) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        v0 = x; v1 = y; v2 = z;
+        if (vp.has_T) {
+            v0 = dot4(vp.T + 0, x, y, z, 1.0);
+            v1 = dot4(vp.T + 4, x, y, z, 1.0);
+            v2 = dot4(vp.T + 8, x, y, z, 1.0);
+            v3 = dot4(vp.T + 12, x, y, z, 1.0);
+        }
+        positive = (0.0 < v0) && (v0 < vp.range_max);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {
+        unsigned char st = 255;
+        float m = 0.f;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
+            const int top = point_label(lp, lp.logits[v], vp.img_w, vp.img_h, ix, iy, m);
+            st = m < lp.min_margin ? 254 : (unsigned char)top;
+        }
+        if (live) {
+            state[(long long)v * pv.n + k] = st;
+            if (margin) margin[(long long)v * pv.n + k] = m;
+        }
+        count_culled(lp.abstained, v, st == 254);
+    }
+}
+
+// validates an avl_point_logits for n_views views (host only) and puts it into kernel-argument form
+int logits_fill(LogitsParams& lp, const avl_point_logits* pl, int n_views) {
+    AVL_REQUIRE(pl, "avl_point_logits is NULL");
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    AVL_REQUIRE(pl->h > 0 && pl->w > 0, "logits of %dx%d pixels", pl->w, pl->h);
+    AVL_REQUIRE(pl->K >= 1 && pl->K <= 254, "logits K = %d (1..254)", pl->K);
+    AVL_REQUIRE(pl->ld >= pl->K, "logits ld = %lld < K = %d", (long long)pl->ld, pl->K);
+    AVL_REQUIRE(pl->ld <= (1ll << 61) / pl->h / pl->w, "logits of %dx%d pixels x ld %lld are too large", pl->w, pl->h, (long long)pl->ld);
+    AVL_REQUIRE(pl->net_h > 0 && pl->net_w > 0, "logits net size %dx%d", pl->net_w, pl->net_h);
+    AVL_REQUIRE(pl->min_margin >= 0.f, "logits min_margin = %g (must be >= 0)", (double)pl->min_margin);      // a NaN fails the comparison too
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->abstained) & 3) == 0, "logits abstained counts are not 4-byte aligned");
+    memset(&lp, 0, sizeof(lp));
+    for (int v = 0; v < n_views; ++v) {
+        AVL_REQUIRE(pl->logits[v], "view %d: logits are NULL", v);
+        AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->logits[v]) & 3) == 0, "view %d: logits are not 4-byte aligned", v);
+        lp.logits[v] = pl->logits[v];
+    }
+    lp.abstained = pl->abstained;
+    lp.ld = pl->ld;
+    lp.h = pl->h; lp.w = pl->w; lp.K = pl->K; lp.net_h = pl->net_h; lp.net_w = pl->net_w;
+    lp.sy = pl->net_h > 1 ? (float)(pl->h - 1) / (float)(pl->net_h - 1) : 0.f;          // as avl_seg_eval_full_res (seg_head.hip)
+    lp.sx = pl->net_w > 1 ? (float)(pl->w - 1) / (float)(pl->net_w - 1) : 0.f;
+    lp.min_margin = pl->min_margin;
+    return AVL_OK;
+}
+
+int logits_reset(const LogitsParams& lp, int n_views, hipStream_t s) {
+    if (lp.abstained) AVL_HIP_CHECK(hipMemsetAsync(lp.abstained, 0, sizeof(int) * n_views, s));
+    return AVL_OK;
+}
+
+// fill_frame for a logits source: the logits stand where the class map stands (its checks ask for a source and its size only)
+int fill_frame_logits(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                      const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl, int img_w, int img_h,
+                      const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes) {
+    return fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, AVL_SRC_CLASSMAP,
+                      reinterpret_cast<const uint8_t*>(pl->logits[0]), pl->w, pl->h, img_w, img_h, lut_host, nullptr, cm_host, bonus_classes);
+}
+
+// fused_frame with the logits as the source: the same path from n, the same depth pass and apply
+int fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
+                       const double* T_host, double range_max, const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
+                       const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    LogitsParams lp;
+    OcclParams oc;
+    int rc;
+    if ((rc = logits_fill(lp, pl, 1))) return rc;
+    if ((rc = fill_frame_logits(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
+                                bonus_classes)))
+        return rc;
+    memset(&oc, 0, sizeof(oc));
+    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, 1))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if ((rc = logits_reset(lp, 1, s))) return rc;
+    if (n == 0) return occl ? occl_reset(oc, 1, false, s) : AVL_OK;
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const int mode = avl_fused_frame_path(g, n, bonus_classes);
+    if (mode < 0) return mode;
+    if (occl) {
+        ViewsParams vp;
+        fill_views(vp, f, 1, P_host, nullptr);
+        if ((rc = occl_reset(oc, 1, true, s))) return rc;
+        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+    }
+    if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
+    const int list_cap = list_geom(n).cap;
+#define AVL_FVL(MODE, OCCL) hipLaunchKernelGGL((k_fused_vote_logits<MODE, OCCL>), grid, block, 0, s, f.pv, f.pp, f.gp, lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
+    if (occl) { if (mode == 3) AVL_FVL(3, 1); else if (mode == 2) AVL_FVL(2, 1); else if (mode == 1) AVL_FVL(1, 1); else AVL_FVL(0, 1); }
+    else { if (mode == 3) AVL_FVL(3, 0); else if (mode == 2) AVL_FVL(2, 0); else if (mode == 1) AVL_FVL(1, 0); else AVL_FVL(0, 0); }
+#undef AVL_FVL
+    AVL_LAUNCH_CHECK();
+    return apply_frame(g, cm_host, bonus_classes, mode, n, s);
+}
+
+}  // namespace
+
+extern "C" int avl_fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                      const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl,
+                                      int img_w, int img_h, const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes,
+                                      const avl_occlusion* occl, void* stream) {
+    return fused_frame_logits(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
+                              bonus_classes, occl, stream);
+}
+
+extern "C" int avl_fused_frame_views_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                            int n_views, const double* P_host, const double* T_host, double range_max,
+                                            const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
+                                            const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    LogitsParams lp;
+    OcclParams oc;
+    int rc;
+    if ((rc = logits_fill(lp, pl, n_views))) return rc;
+    if (n_views == 1)
+        return fused_frame_logits(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
+                                  bonus_classes, occl, stream);
+    if ((rc = fill_frame_logits(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
+                                bonus_classes)))
+        return rc;
+    if ((rc = views_bits_check(g, bonus_classes))) return rc;
+    memset(&oc, 0, sizeof(oc));
+    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if ((rc = logits_reset(lp, n_views, s))) return rc;
+    if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    CmParams cm;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const bool lists = lists_fit(g, n);
+    const ListGeom lg = list_geom(n);
+    if (occl) {
+        if ((rc = occl_reset(oc, n_views, true, s))) return rc;
+        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+    }
+#define AVL_VVL(LISTS, OCCL) hipLaunchKernelGGL((k_views_vote_logits<LISTS, OCCL>), grid, block, 0, s, f.pv, vp, f.gp, lp, f.lut, g->cell_mask, g->touched, g->counter, lg.cap, oc)
+    if (occl) { if (lists) AVL_VVL(1, 1); else AVL_VVL(0, 1); }
+    else { if (lists) AVL_VVL(1, 0); else AVL_VVL(0, 0); }
+#undef AVL_VVL
+    AVL_LAUNCH_CHECK();
+    return apply_views(g, cm, bonus_classes, lists, lg, s);
+}
+
+extern "C" int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                                const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
+                                const avl_point_logits* pl, uint8_t* state, float* margin, void* stream) {
+    FrameArgs f;
+    LogitsParams lp;
+    int rc;
+    if ((rc = logits_fill(lp, pl, n_views))) return rc;
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    AVL_REQUIRE(n == 0 || state, "state is NULL");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(margin) & 3) == 0, "margin is not 4-byte aligned");
+    hipStream_t s = avl::as_stream(stream);
+    if ((rc = logits_reset(lp, n_views, s))) return rc;
+    if (n == 0) return AVL_OK;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    hipLaunchKernelGGL(k_point_labels, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, lp, state, margin);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }

@@ -24,6 +24,10 @@ What differs from the reference, by design:
   * with MAPPING.OCCLUSION.ENABLED, points hidden behind nearer ones in a view's image do not vote (a per-view depth buffer, the
     rule at struct avl_occlusion in include/avl_hip.h); ``visibility_device()`` returns the verdict per point.  The reference lets
     every point that lands in the image vote.  Off by default.
+  * ``frame_device(..., src_kind="logits")`` labels the points from a plan's fp32 logits, interpolated at each point's pixel as the
+    reference model's full-resolution prediction is, and lets a point whose top-1 minus top-2 margin is below
+    MAPPING.CONFIDENCE.MIN_MARGIN abstain (the rule at struct avl_point_logits in include/avl_hip.h); ``point_labels_device()``
+    returns label and margin per point.  The reference votes the nearest low-resolution arg-max with full weight.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -66,6 +70,57 @@ def _dbl(a):
         hit = (C.c_double * a.size).from_buffer_copy(key)
         _DBL_CACHE[key] = hit
     return hit
+
+
+def confidence_min_margin(cfg):
+    """MAPPING.CONFIDENCE.MIN_MARGIN as a float (0.0 for a configuration without the node).  ValueError unless it is a number >= 0:
+    a bool, a string, a negative value and a NaN are refused."""
+    node = getattr(cfg.MAPPING, "CONFIDENCE", None)
+    v = 0.0 if node is None else node.MIN_MARGIN
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not float(v) >= 0.0:
+        raise ValueError("MAPPING.CONFIDENCE.MIN_MARGIN = %r (a float >= 0)" % (v,))
+    return float(v)
+
+
+def logits_views(semantics, n_views=None):
+    """The views of a logits source (src_kind="logits") -> (list of fp32 CUDA tensors [h', w', K], (h', w', K), ld).  ``semantics``:
+    one tensor [h', w', K] (n_views None), a tensor [V, h', w', K] or a list of V tensors [h', w', K] -- SegNet.logits of a plan or
+    a batched plan goes in as it is.  Every view's pixels lie ``ld`` >= K floats apart with the classes next to each other (a
+    contiguous tensor, or the first K columns of one), one ld for all views; K is 1..254.  ValueError otherwise."""
+    if n_views is None:
+        if not isinstance(semantics, torch.Tensor) or semantics.dim() != 3:
+            raise ValueError("a logits source is a tensor [h', w', K], got %s" % (
+                tuple(semantics.shape) if isinstance(semantics, torch.Tensor) else type(semantics).__name__,))
+        views = [semantics]
+    elif isinstance(semantics, torch.Tensor):
+        if semantics.dim() != 4 or int(semantics.shape[0]) != n_views:
+            raise ValueError("semantics has shape %s for %d logits views" % (tuple(semantics.shape), n_views))
+        views = [semantics[v] for v in range(n_views)]
+    else:
+        views = list(semantics)
+        if len(views) != n_views:
+            raise ValueError("%d semantic sources for %d cameras" % (len(views), n_views))
+    shape, ld = None, None
+    for t in views:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("logits must be float32 tensors, got %s" % (t.dtype if isinstance(t, torch.Tensor) else type(t).__name__,))
+        if t.dim() != 3 or min(t.shape) < 1:
+            raise ValueError("a logits view is [h', w', K], got %s" % (tuple(t.shape),))
+        h, w, K = (int(d) for d in t.shape)
+        if K > 254:
+            raise ValueError("logits of K = %d classes (1..254)" % K)
+        t_ld = int(t.stride(1)) if w > 1 else (int(t.stride(0)) if h > 1 else K)
+        if (K > 1 and t.stride(2) != 1) or t_ld < K or (h > 1 and int(t.stride(0)) != w * t_ld):
+            raise ValueError("logits view of shape %s has strides %s: its pixels must lie ld >= K floats apart, row after row" % (
+                tuple(t.shape), tuple(t.stride())))
+        if shape is None:
+            shape, ld = (h, w, K), t_ld
+        elif (h, w, K) != shape or t_ld != ld:
+            raise ValueError("the views' logits must have one shape and one row stride")
+    for t in views:
+        if not t.is_cuda:
+            raise ValueError("logits must be CUDA tensors")
+    return views, shape, ld
 
 
 class DeviceGrid(object):
@@ -200,6 +255,10 @@ class SemanticMapping(object):
         self.occlusion_cfg = getattr(cfg.MAPPING, "OCCLUSION", None)
         self.last_culled = None                # int32 CUDA tensor [V]: culled candidates per view of the last culling call (no sync to fill it)
         self._occl_depth = {}                  # (V, Hc, Wc) -> the depth scratch of that shape
+
+        # labels from interpolated logits (src_kind="logits") and their confidence gate (MAPPING.CONFIDENCE)
+        self.min_margin = confidence_min_margin(cfg)   # a point whose top-1 minus top-2 margin is below it abstains; 0 gates nothing
+        self.last_abstained = None             # int32 CUDA tensor [V]: votes the gate withheld per view in the last logits call (no sync)
 
         # device-side caches
         self._scratch = None
@@ -625,11 +684,17 @@ class SemanticMapping(object):
         return (state, keys) if return_keys else state
 
     def frame_device(self, pcd, pcd_frame_id, semantic, pose, camera_calibration, src_kind="rgb",
-                     image_size=None, net_palette=PALETTE_19, stream=None, _culled=None):
+                     image_size=None, net_palette=PALETTE_19, stream=None, _culled=None, net_size=None, _abstained=None):
         """Fused frame (avl_fused_frame; avl_fused_frame_occl with MAPPING.OCCLUSION.ENABLED).  ``pcd``: NumPy/torch [4,N]
         float64|float32 (SoA, the reference layout) or [N,4] float32 (AoS); ``semantic``: CUDA uint8 tensor, either the colour
         image [H,W,3] (src_kind="rgb") or a class-id map [h,w] (src_kind="classmap", sampled as the
-        nearest-upscaled image of size ``image_size`` = (H, W))."""
+        nearest-upscaled image of size ``image_size`` = (H, W)).  With src_kind="logits" ``semantic`` is a plan's fp32 logits
+        [h',w',K] (SegNet.logits): every point takes the arg-max of the logits interpolated to ``net_size`` = (h, w) (the network's
+        input; ``image_size`` by default) at its pixel, and abstains when the top-1 minus top-2 margin is below ``self.min_margin``
+        (MAPPING.CONFIDENCE.MIN_MARGIN); ``last_abstained`` receives the count (avl_fused_frame_logits)."""
+        if src_kind == "logits":
+            return self._frame_device_logits(pcd, pcd_frame_id, logits_views(semantic)[0], pose, [camera_calibration], image_size, net_size,
+                                             net_palette, stream, _culled, _abstained)
         assert semantic.dtype == torch.uint8
         sh, sw, ih, iw, kind, lut = self._semantic_source(semantic.shape, src_kind, image_size, net_palette)
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, camera_calibration.P, stream)
@@ -647,16 +712,20 @@ class SemanticMapping(object):
         self.frames_mapped += 1
 
     def frame_device_views(self, pcd, pcd_frame_id, semantics, pose, cameras, src_kind="classmap", image_size=None,
-                           net_palette=PALETTE_19, stream=None):
+                           net_palette=PALETTE_19, stream=None, net_size=None):
         """V cameras on one cloud in one fused pass (avl_fused_frame_views): the grid ends bit-identical to V frame_device calls
         in view order.  ``semantics``: a uint8 CUDA tensor [V,h,w] of class maps (a batched plan's label buffer goes in as it is)
-        or [V,H,W,3] of colour images (src_kind="rgb"), or a list of V such tensors of one size; ``cameras``: V calibrations.
-        More than AVL_MAX_VIEWS views, or more vote bits than a view's byte of the mask holds (classes + lane classes > 8), are
-        mapped by sequential frame_device calls."""
+        or [V,H,W,3] of colour images (src_kind="rgb"), or a list of V such tensors of one size; with src_kind="logits" an fp32
+        CUDA tensor [V,h',w',K] (a batched plan's logits) or a list of V tensors [h',w',K], ``net_size`` as in frame_device;
+        ``cameras``: V calibrations.  More than AVL_MAX_VIEWS views, or more vote bits than a view's byte of the mask holds
+        (classes + lane classes > 8), are mapped by sequential frame_device calls."""
         cameras = list(cameras)
         V = len(cameras)
         if V < 1:
             raise ValueError("frame_device_views needs at least one camera")
+        if src_kind == "logits":
+            return self._frame_device_logits(pcd, pcd_frame_id, logits_views(semantics, V)[0], pose, cameras, image_size, net_size,
+                                             net_palette, stream)
         want_dim = 3 if src_kind == "rgb" else 2
         if isinstance(semantics, torch.Tensor):
             if semantics.dim() != want_dim + 1 or int(semantics.shape[0]) != V:
@@ -695,6 +764,85 @@ class SemanticMapping(object):
             _lib.check(rc, "avl_fused_frame_views")
         self._map_host = None
         self.frames_mapped += V
+
+    # ------------------------------------------------------------------ labels from interpolated logits (MAPPING.CONFIDENCE)
+    def _point_logits(self, views, image_size, net_size, abstained=None):
+        """-> (struct avl_point_logits for the checked ``views`` of logits_views(), ih, iw): the points are projected to
+        ``image_size`` (``net_size``, else the logits' own size, when None) and the logits interpolated to ``net_size``
+        (``image_size`` when None).  ``abstained``: (int32 CUDA tensor, first element) that receives the counts, or None."""
+        _, (h, w, K), ld = logits_views(views, len(views))
+        size = image_size if image_size is not None else (net_size if net_size is not None else (h, w))
+        ih, iw = int(size[0]), int(size[1])
+        nh, nw = (ih, iw) if net_size is None else (int(net_size[0]), int(net_size[1]))
+        pl = _lib.AvlPointLogits()
+        for v, t in enumerate(views):
+            pl.logits[v] = t.data_ptr()
+        pl.h, pl.w, pl.K, pl.ld = h, w, K, ld
+        pl.net_h, pl.net_w = nh, nw
+        pl.min_margin = float(self.min_margin)
+        pl.abstained = None if abstained is None else abstained[0].data_ptr() + 4 * int(abstained[1])
+        return pl, ih, iw
+
+    def _frame_device_logits(self, pcd, pcd_frame_id, views, pose, cameras, image_size, net_size, net_palette, stream,
+                             _culled=None, _abstained=None):
+        """frame_device / frame_device_views for src_kind="logits": ``views`` are V checked logits tensors (logits_views)."""
+        V = len(cameras)
+        bonus = self._bonus_classes()
+        occlusion = self.occlusion_enabled()
+        if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
+            abstained = torch.zeros(V, dtype=torch.int32, device=self.device)
+            culled = torch.zeros(V, dtype=torch.int32, device=self.device) if occlusion else None
+            for v, (t, cam) in enumerate(zip(views, cameras)):
+                self._frame_device_logits(pcd, pcd_frame_id, [t], pose, [cam], image_size, net_size, net_palette, stream,
+                                          (culled, v) if occlusion else None, (abstained, v))
+            self.last_abstained = abstained
+            if occlusion:
+                self.last_culled = culled
+            return
+        if _abstained is None:
+            if self.last_abstained is None or int(self.last_abstained.numel()) != V:
+                self.last_abstained = torch.zeros(V, dtype=torch.int32, device=self.device)
+            _abstained = (self.last_abstained, 0)
+        pl, ih, iw = self._point_logits(views, image_size, net_size, _abstained)
+        view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]), stream)
+        occ = C.byref(self._occlusion(V, ih, iw, _culled)) if occlusion else None
+        lut, cm = self._lut_host(net_palette), _dbl(self.confusion_matrix)
+        if V == 1:
+            rc = _lib.lib().avl_fused_frame_logits(C.byref(gs), *view, P, T, float(self.pcd_range_max), C.byref(pl), iw, ih, lut, cm, bonus, occ, s)
+            _lib.check(rc, "avl_fused_frame_logits")
+        else:
+            rc = _lib.lib().avl_fused_frame_views_logits(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), C.byref(pl), iw, ih, lut, cm,
+                                                         bonus, occ, s)
+            _lib.check(rc, "avl_fused_frame_views_logits")
+        self._map_host = None
+        self.frames_mapped += V
+
+    def point_labels_device(self, pcd, pcd_frame_id, pose, cameras, logits, image_size, net_size=None):
+        """The logits rule alone (avl_point_labels; struct avl_point_logits in include/avl_hip.h), with ``self.min_margin``: for every
+        camera of ``cameras`` (one calibration or a list) and every point of ``pcd``, on the grid or not, the class the point takes
+        from that view's ``logits`` ([h',w',K], [V,h',w',K] or a list), 254 where it abstains and 255 where it is no candidate of the
+        view.  Returns (state uint8 CUDA [V, N], margin float32 CUDA [V, N], 0 where the state is 255).  ``last_abstained`` receives
+        the per-view counts of state 254."""
+        single = not isinstance(cameras, (list, tuple))
+        cameras = [cameras] if single else list(cameras)
+        V = len(cameras)
+        if V < 1:
+            raise ValueError("point_labels_device needs at least one camera")
+        if single and isinstance(logits, torch.Tensor) and logits.dim() == 3:
+            logits = [logits]
+        views = logits_views(logits, V)[0]
+        n = int(_lib.points_view(pcd, self.device)[1])
+        state = torch.empty((V, n), dtype=torch.uint8, device=self.device)
+        margin = torch.empty((V, n), dtype=torch.float32, device=self.device)
+        self.last_abstained = torch.zeros(V, dtype=torch.int32, device=self.device)
+        for v0 in range(0, V, _lib.AVL_MAX_VIEWS):
+            cams = cameras[v0:v0 + _lib.AVL_MAX_VIEWS]
+            pl, ih, iw = self._point_logits(views[v0:v0 + len(cams)], image_size, net_size, (self.last_abstained, v0))
+            view, T, _, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(c.P, dtype=np.float64) for c in cams]), grid=False)
+            rc = _lib.lib().avl_point_labels(*view, len(cams), P, T, float(self.pcd_range_max), iw, ih, C.byref(pl), _ptr(state[v0:]),
+                                             _ptr(margin[v0:]), s)
+            _lib.check(rc, "avl_point_labels")
+        return state, margin
 
     def project_pcd(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """mapping.py:357-389.  NumPy in, NumPy out: (pcd[:, mask] float64[4,M], label uint8[3,M]).

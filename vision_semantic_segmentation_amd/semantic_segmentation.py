@@ -257,10 +257,27 @@ class SemanticSegmentation(object):
         uint8 BGR [H,W,3] (ndarray or CUDA tensor) -> BGR->RGB, cv2.undistort(K, dist) (skipped when None), INTER_AREA by the integer
         `factor`, normalise, network, arg-max -> uint8 CUDA tensor.  Same labels as preprocess_device() + segmentation_device(), without
         the RGB frame in between.  Every precision and every rung of the self-check's ladder has such a stem (fp32: k_stem_pre_f32)."""
+        return self._run_raw(bgr, K, dist, factor).labels
+
+    def _run_raw(self, bgr, K, dist, factor):
+        """one forward of the raw-frame plan for bgr's size -> the plan"""
         H, W = int(bgr.shape[0]), int(bgr.shape[1])
         net = self.net_for(H // factor, W // factor, raw_frame=(H, W))
         net.set_camera(K, dist)
-        return net.forward(bgr)
+        net.forward(bgr)
+        return net
+
+    def logits_device_raw(self, bgr, K=None, dist=None, factor=1):
+        """segmentation_device_raw, returning the plan's logits instead of its labels: the fp32 CUDA view [h', w', classes] every plan
+        writes (no extra pass), which SemanticMapping.frame_device(..., src_kind="logits") reads.  The next forward of the same size
+        overwrites it."""
+        return self._run_raw(bgr, K, dist, factor).logits
+
+    def logits_device_raw_batch(self, frames, Ks=None, dists=None, factor=1):
+        """segmentation_device_raw_batch, returning the batched plan's logits [V, h', w', classes] (V = 1 included) for
+        SemanticMapping.frame_device_views(..., src_kind="logits")."""
+        net, V = self._run_raw_batch(frames, Ks, dists, factor)
+        return net.logits if V > 1 else net.logits.unsqueeze(0)
 
     def segmentation_device_raw_batch(self, frames, Ks=None, dists=None, factor=1):
         """segmentation_device_raw for the V frames of one trigger, each with its own camera, in ONE plan (net_for(raw_batch=True)):
@@ -269,6 +286,11 @@ class SemanticSegmentation(object):
         copied straight into the plan's input buffer and pre-processed inside the stem's loader with its own camera block, so view
         v's labels are bit for bit segmentation_device_raw(frames[v], Ks[v], dists[v], factor).  Returns the plan's uint8 CUDA labels
         [V, h', w'] (V = 1 included).  The mixed self-check and its fall-back ladder apply as for every other plan."""
+        net, V = self._run_raw_batch(frames, Ks, dists, factor)
+        return net.labels if V > 1 else net.labels.unsqueeze(0)
+
+    def _run_raw_batch(self, frames, Ks, dists, factor):
+        """one forward of the raw-batch plan for the frames' size and number -> (plan, V)"""
         if isinstance(frames, (list, tuple)):
             views = list(frames)
         else:
@@ -296,10 +318,10 @@ class SemanticSegmentation(object):
                 if t.dtype != torch.uint8:
                     raise ValueError("camera frames are uint8, not %s" % t.dtype)
                 slots[v].copy_(t, non_blocking=True)
-            labels = net.forward()
+            net.forward()
         else:
-            labels = net.forward(frames)
-        return labels if V > 1 else labels.unsqueeze(0)
+            net.forward(frames)
+        return net, V
 
     def segmentation(self, image_in, upsample_pred=False):
         """semantic_segmentation.py:41-57: numpy (h, w, 3) RGB -> int64 numpy label map ([h, w] with upsample_pred=True); a batch

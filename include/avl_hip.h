@@ -399,6 +399,31 @@ int avl_grid_box_filter(const void* src, void* dst, int map_dtype, int Hm, int W
 int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int x0, int y0, int h, int w,
                  int flags, const int32_t* priority_host, const double* thresholds_host, const int32_t* fill_priority_host,
                  int n_fill_priority, const double* car_host, const uint8_t* car_color_host, uint8_t* out, void* stream);
+/* avl_live_view: the same picture through a matrix -- rotated, scaled, heading-up -- in one kernel.  The arguments are
+ * avl_live_map's with x0, y0 replaced by matrix_host = double[6], the row-major 2 x 3 matrix M from output pixel centres to
+ * continuous grid coordinates in cells.  With B the whole-grid picture defined above (F, R, B; Hm x Wm), pixel (i, j) of
+ * out uint8[h][w][3] is, in float64, without contraction, in exactly this order:
+ *   a  = (double)i + 0.5;  b = (double)j + 0.5;
+ *   gx = (M[0][0]*a + M[0][1]*b) + M[0][2];      (grid row coordinate)
+ *   gy = (M[1][0]*a + M[1][1]*b) + M[1][2];      (grid column coordinate)
+ *   out[i][j] = 0.0 <= gx < (double)Hm && 0.0 <= gy < (double)Wm ? B[floor(gx)][floor(gy)] : black;
+ * the range is tested on the doubles, before any conversion to an integer.  Nearest-cell sampling is deliberate: the filter and
+ * the hole fill stay defined in the grid's frame.  Then, with car_host != NULL, the car block of avl_live_map is tested on the
+ * pixel's continuous coordinates: dx = gx - cx, dy = gy - cy, u = c*dx + s*dy, v = c*dy - s*dx, painted when
+ * u_lo <= u < u_hi and v_lo <= v < v_hi.  M = {1, 0, x0, 0, 1, y0} gives avl_live_map(x0, y0) byte for byte, the car included.
+ * A heading-up view with the vehicle (cx, cy cells, heading c, s) at pixel centre (ai, aj) and k cells per pixel is
+ *   M[0] = {-k*c, k*s, cx - (-k*c)*ai - (k*s)*aj},  M[1] = {-k*s, -k*c, cy - (-k*s)*ai - (-k*c)*aj}:
+ * up is +heading, right is the vehicle's right seen from above, (s, -c) in grid (x, y).
+ * Every entry of M must be finite, and |M[0][0]| + |M[0][1]| <= AVL_LIVE_VIEW_MAX_SPAN and |M[1][0]| + |M[1][1]| <=
+ * AVL_LIVE_VIEW_MAX_SPAN (2.875 exactly; the kernel keeps the grid cells under one 32 x 32 output tile in a fixed array).  A
+ * rotation by any angle at k cells per pixel has sums of at most k * sqrt(2), so every k <= 2.875 / sqrt(2) = 2.0329... is
+ * admitted at every angle, 0.25 to 2 included; there is no lower limit, and a singular M (a zero 2 x 2 part paints one cell
+ * everywhere) is legal.  All arguments are checked before anything touches the device.  The grid is only read. */
+#define AVL_LIVE_VIEW_MAX_SPAN 2.875
+int avl_live_view(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, const double* matrix_host,
+                  int h, int w, int flags, const int32_t* priority_host, const double* thresholds_host,
+                  const int32_t* fill_priority_host, int n_fill_priority, const double* car_host, const uint8_t* car_color_host,
+                  uint8_t* out, void* stream);
 /* fill_black (src/renderer.py:62-98) with resume_color (:101-105), reproduced as written: img uint8[X][Y][3] (device) ->
  * out uint8[X-2][Y-2][3].  EVERY interior pixel, black or not (:91 is commented out), looks at the R channel of its 3 x 3
  * neighbourhood; label i is present if a neighbour's R equals colors_host[i][0]; the last present label of priority_host

@@ -17,6 +17,7 @@ AVL_LABEL_ABSTAINED, AVL_LABEL_NONE = 254, 255   # avl_point_labels' states besi
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
 AVL_LIVE_FILTER, AVL_LIVE_THRESHOLDS, AVL_LIVE_FILL = 1, 2, 4   # avl_live_map's flags
 AVL_LIVE_CAR_DOUBLES = 8        # avl_live_map's car block
+AVL_LIVE_VIEW_MAX_SPAN = 2.875  # avl_live_view: the largest |M00| + |M01| and |M10| + |M11|
 AVL_PLANE_W_NONE, AVL_PLANE_W_XNORM = 0, 1
 AVL_PLANE_MAX_HYP = 1024
 AVL_PLANE_RESULT_WORDS = 24     # 8-byte words of avl_plane_ransac's result block
@@ -93,6 +94,7 @@ _SIGNATURES = {
     "avl_render_bev_map_thresholds": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avl_grid_box_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "avl_live_map": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "avl_live_view": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "avl_fill_black": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "avl_eval_map": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "avl_upsample_logits": (_i, [_vp, _i, _i, _i, _i64, _vp, _i, _i, _vp]),

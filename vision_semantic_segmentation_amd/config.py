@@ -163,6 +163,14 @@ def get_cfg_defaults():
     C.MAPPING.LIVE_MAP.FILL_PRIORITY = [0, 3, 4, 2, 1]    # low to high (renderer.py:67)
     C.MAPPING.LIVE_MAP.DRAW_CAR = True
     C.MAPPING.LIVE_MAP.CAR_SIZE = [4.0, 1.8]              # length, width in metres (src/mapping.py:502-503)
+    # build-specific: the live map's geometry as a heading-up view (SemanticMapping.live_view): the vehicle's heading points up, the
+    # vehicle sits at pixel ANCHOR * SIZE_PX, one pixel spans METRES_PER_PIXEL.  Filter, renderer, fill and car stay LIVE_MAP's.  With
+    # LIVE_MAP.ENABLED, HEADING_UP makes mapping() / mapping_views() render this view instead of the axis-aligned window
+    C.MAPPING.LIVE_VIEW = CfgNode()
+    C.MAPPING.LIVE_VIEW.HEADING_UP = False
+    C.MAPPING.LIVE_VIEW.SIZE_PX = [600, 600]              # height, width of the picture
+    C.MAPPING.LIVE_VIEW.METRES_PER_PIXEL = 0.0            # 0: MAPPING.RESOLUTION (one cell per pixel)
+    C.MAPPING.LIVE_VIEW.ANCHOR = [0.5, 0.5]               # fraction of the height from the top, of the width from the left
     # build-specific: occluded points do not vote (the reference lets a map point behind a wall take the wall's label).  Every view gets a
     # depth buffer of CELL_PX x CELL_PX pixel cells of the projection image; a point is culled when its depth exceeds
     # m * (1 + REL_TOL) + ABS_TOL, m the nearest depth within RADIUS cells (the rule: include/avl_hip.h, avl_occlusion).  Off by

@@ -21,9 +21,23 @@
 //   C  RGB stores, the car last: its red has the lane's R value and fill_black matches on R
 // The arg-max renderer streams the channels once (sum and arg-max in one pass); the thresholds renderer needs the sum before
 // the shares and evaluates the filter a second time for them instead of keeping C values per thread (no scratch, no LDS rows).
+//
+// k_live_view, the same picture through a 2 x 3 matrix from output pixel centres to grid coordinates (avl_live_view), one workgroup
+// per 32 x 32 output tile (square: its grid footprint is the same at every rotation):
+//   A  the grid-space bounding box of the tile's footprint, from its four corner pixel centres (rounding is monotone, so the
+//      extremes of gx and gy over the tile are at the corners), clamped to the grid plus one cell.  Lanes walk the box in GRID
+//      row-major order -- the filter's reads stay contiguous along Wm whatever the rotation -- and every cell's class is computed
+//      once, however many pixels sample it; with the fill, one more ring of cells -> one byte per cell in LDS
+//   B  after the barrier every pixel finds its cell: floor of its coordinates, range-tested on the doubles; the fill's 3 x 3 pass
+//      runs on the sampled cell's LDS neighbourhood, so filter and fill stay defined in the grid's frame
+//   C  RGB stores, the car last, tested on the pixel's continuous coordinates
+// The LDS box is static, kVBox x kVLd bytes, for the largest footprint avl_live_view admits (AVL_LIVE_VIEW_MAX_SPAN); the box's
+// size is clamped to it and a pixel whose cell fell outside the box would read nothing, so no LDS index leaves the array whatever
+// the matrix.
 #include "avl_common.h"
 #include "avl_render.h"
 
+#include <cmath>
 #include <cstdint>
 
 namespace {
@@ -33,6 +47,12 @@ constexpr int kTH = 16, kTW = 64;            // output tile
 constexpr int kPH = kTH + 2, kPW = kTW + 2;  // with the halo
 constexpr int kBlack = 255;                  // "no class" byte of the LDS tile
 constexpr int kMaxWindow = 32768;            // h, w: gridDim.y holds 65535 tiles
+constexpr int kVT = 32;                      // k_live_view's output tile, kVT x kVT
+// Cells per axis of a tile's footprint: its corner pixel centres are kVT - 1 apart, so gx spans at most (kVT - 1) * (|M00| + |M01|)
+// <= 31 * 2.875 = 89.125 (plus roundings of 2^-20 at most: a pixel that samples the grid has |gx| < 2^31 + 2^17), and an interval
+// of length L meets at most floor(L) + 2 cells: 91.  With the fill's ring on both sides: 93.
+constexpr int kVBox = 93, kVLd = 96;
+static_assert((kVT - 1) * AVL_LIVE_VIEW_MAX_SPAN + 0.5 < kVBox - 2 - 1, "the LDS box does not hold the largest admitted footprint");
 
 // fill_black's label walk, prepared on the host: list position k names label prio[k]; a pixel that ends with that label's R value
 // is coloured by resume_color as label final_[k] (the last label with the same R); no label present -> none (kBlack unless a
@@ -55,6 +75,11 @@ struct LiveParams {
     FillTable ft;
 };
 
+struct ViewParams {
+    LiveParams p;     // x0, y0 unused
+    double m[6];      // pixel centre (i + 0.5, j + 0.5) -> grid coordinates, row-major 2 x 3
+};
+
 // s_col[label] = its colour, s_col[16] = black; s_mask[byte] = labels whose R value the tile byte stands for.  A live tile holds
 // class indices (kBlack: R = 0), an image tile holds R values.
 template <bool kBytesAreClasses>
@@ -69,12 +94,13 @@ __device__ __forceinline__ void build_tables(const FillTable& ft, unsigned char*
 }
 
 // label (or kBlack) of the pixel whose tile byte is *centre: fill_black's mask_dict + priority walk + resume_color
+template <int kLd = kPW>
 __device__ __forceinline__ int fill_pick(const unsigned char* centre, const unsigned short* s_mask, const FillTable& ft) {
     unsigned present = 0;
 #pragma unroll
     for (int di = -1; di <= 1; ++di)
 #pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) present |= s_mask[centre[di * kPW + dj]];
+        for (int dj = -1; dj <= 1; ++dj) present |= s_mask[centre[di * kLd + dj]];
     int label = ft.none;
     for (int k = 0; k < ft.n_prio; ++k)
         if ((present >> ft.prio[k]) & 1u) label = ft.final_[k];
@@ -157,6 +183,75 @@ __global__ void __launch_bounds__(kBlock) k_live_map(const MapT* __restrict__ ma
     }
 }
 
+template <typename MapT>
+__global__ void __launch_bounds__(kBlock) k_live_view(const MapT* __restrict__ map, ViewParams vp, unsigned char* __restrict__ out) {
+    __shared__ unsigned char s_box[kVBox * kVLd];
+    __shared__ unsigned char s_col[(AVL_MAX_MAP_CLASSES + 1) * 3 + 1];
+    __shared__ unsigned short s_mask[256];
+    const LiveParams& p = vp.p;
+    build_tables<true>(p.ft, s_col, s_mask);
+    const int ti0 = blockIdx.y * kVT, tj0 = blockIdx.x * kVT;
+    const bool fill = p.flags & AVL_LIVE_FILL;
+    const double m00 = vp.m[0], m01 = vp.m[1], m02 = vp.m[2], m10 = vp.m[3], m11 = vp.m[4], m12 = vp.m[5];
+    // ---- A: the box of grid cells [xlo, xlo + nx) x [ylo, ylo + ny) that the tile's pixels can sample, from the corners of its
+    //         (ragged) pixel range; cells off the grid are black without a read, so the box is clamped to the grid plus one cell
+    const double a0 = (double)ti0 + 0.5, a1 = (double)(min(ti0 + kVT, p.h) - 1) + 0.5;
+    const double b0 = (double)tj0 + 0.5, b1 = (double)(min(tj0 + kVT, p.w) - 1) + 0.5;
+    auto box = [&](double ma, double mb, double mc, int n, int& lo) -> int {
+        const double c00 = (ma * a0 + mb * b0) + mc, c01 = (ma * a0 + mb * b1) + mc;
+        const double c10 = (ma * a1 + mb * b0) + mc, c11 = (ma * a1 + mb * b1) + mc;
+        const double top = (double)n;
+        const double mn = fmin(fmax(floor(fmin(fmin(c00, c01), fmin(c10, c11))), -1.0), top);
+        const double mx = fmin(fmax(floor(fmax(fmax(c00, c01), fmax(c10, c11))), -1.0), top);
+        lo = (int)mn;
+        return min((int)mx - lo + 1, kVBox - 2);
+    };
+    int xlo, ylo;
+    const int nx = box(m00, m01, m02, p.Hm, xlo), ny = box(m10, m11, m12, p.Wm, ylo);
+    // LDS byte (bi, bj), 0 <= bi <= nx + 1, 0 <= bj <= ny + 1, is grid cell (xlo - 1 + bi, ylo - 1 + bj): the ring is the fill's
+    const int bw = ny + 2;
+    for (int idx = threadIdx.x; idx < (nx + 2) * bw; idx += kBlock) {
+        const int bi = idx / bw, bj = idx - bi * bw;
+        const int gx = xlo - 1 + bi, gy = ylo - 1 + bj;
+        int cls = kBlack;
+        if ((fill || (bi >= 1 && bi <= nx && bj >= 1 && bj <= ny)) && gx >= 0 && gx < p.Hm && gy >= 0 && gy < p.Wm)
+            cls = cell_class(map, p, gx, gy);
+        s_box[bi * kVLd + bj] = (unsigned char)cls;
+    }
+    __syncthreads();
+    // ---- B, C
+    for (int idx = threadIdx.x; idx < kVT * kVT; idx += kBlock) {
+        const int li = idx / kVT, lj = idx - li * kVT;
+        const int i = ti0 + li, j = tj0 + lj;
+        if (i >= p.h || j >= p.w) continue;
+        const double a = (double)i + 0.5, b = (double)j + 0.5;
+        const double gx = (m00 * a + m01 * b) + m02, gy = (m10 * a + m11 * b) + m12;
+        int label = kBlack;
+        if (0.0 <= gx && gx < (double)p.Hm && 0.0 <= gy && gy < (double)p.Wm) {
+            const int cx = (int)gx, cy = (int)gy;                      // floor: both are >= 0 here
+            const int bi = cx - xlo + 1, bj = cy - ylo + 1;
+            if (bi >= 1 && bi <= nx && bj >= 1 && bj <= ny) {          // always, for a matrix avl_live_view admits
+                const unsigned char* centre = s_box + bi * kVLd + bj;
+                label = *centre;
+                if (fill) {
+                    const bool interior = cx >= 1 && cx <= p.Hm - 2 && cy >= 1 && cy <= p.Wm - 2;
+                    label = interior ? fill_pick<kVLd>(centre, s_mask, p.ft) : kBlack;
+                }
+            }
+        }
+        const int ci = label == kBlack ? AVL_MAX_MAP_CLASSES : label;
+        unsigned char r = s_col[3 * ci], g = s_col[3 * ci + 1], bl = s_col[3 * ci + 2];
+        if (p.has_car) {
+            const double dx = gx - p.car[0], dy = gy - p.car[1];
+            const double c = p.car[2], s = p.car[3];
+            const double u = c * dx + s * dy, v = c * dy - s * dx;
+            if (p.car[4] <= u && u < p.car[5] && p.car[6] <= v && v < p.car[7]) { r = p.car_rgb[0]; g = p.car_rgb[1]; bl = p.car_rgb[2]; }
+        }
+        unsigned char* o = out + ((long long)i * p.w + j) * 3;
+        o[0] = r; o[1] = g; o[2] = bl;
+    }
+}
+
 // fill_black on an image: img [X][Y][3] -> out [X - 2][Y - 2][3]
 __global__ void __launch_bounds__(kBlock) k_fill_black(const unsigned char* __restrict__ img, int X, int Y, FillTable ft,
                                                        unsigned char* __restrict__ out) {
@@ -206,12 +301,10 @@ int build_fill(FillTable& ft, const uint8_t* colors, int n, const int32_t* prio,
     return AVL_OK;
 }
 
-}  // namespace
-
-extern "C" int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int x0, int y0, int h,
-                            int w, int flags, const int32_t* priority_host, const double* thresholds_host,
-                            const int32_t* fill_priority_host, int n_fill_priority, const double* car_host,
-                            const uint8_t* car_color_host, uint8_t* out, void* stream) {
+// what avl_live_map and avl_live_view share: every check on the arguments, and the parameter block but for the window's geometry
+int live_params(LiveParams& p, const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int h, int w, int flags,
+                const int32_t* priority_host, const double* thresholds_host, const int32_t* fill_priority_host, int n_fill_priority,
+                const double* car_host, const uint8_t* car_color_host, const uint8_t* out) {
     AVL_REQUIRE(map, "map is NULL");
     AVL_REQUIRE(out, "out is NULL");
     AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
@@ -223,9 +316,8 @@ extern "C" int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int 
     AVL_REQUIRE(!(flags & AVL_LIVE_FILTER) || (Hm > 1 && Wm > 1), "the box filter reflects at the grid's edge: grid %d x %d", Hm, Wm);
     AVL_REQUIRE(!(flags & AVL_LIVE_FILL) || (Hm >= 3 && Wm >= 3), "fill_black needs a 3 x 3 grid at least: %d x %d", Hm, Wm);
     AVL_REQUIRE(!(flags & AVL_LIVE_THRESHOLDS) || thresholds_host, "AVL_LIVE_THRESHOLDS without thresholds_host");
-    LiveParams p;
     memset(&p, 0, sizeof(p));
-    p.Hm = Hm; p.Wm = Wm; p.C = C; p.x0 = x0; p.y0 = y0; p.h = h; p.w = w; p.flags = flags;
+    p.Hm = Hm; p.Wm = Wm; p.C = C; p.h = h; p.w = w; p.flags = flags;
     memcpy(p.rp.colors, colors_host, 3 * C);
     for (int k = 0; k < C; ++k) {
         p.rp.priority[k] = priority_host ? priority_host[k] : k;
@@ -241,9 +333,48 @@ extern "C" int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int 
         p.car_rgb[1] = car_color_host ? car_color_host[1] : 0;
         p.car_rgb[2] = car_color_host ? car_color_host[2] : 0;
     }
+    return AVL_OK;
+}
+
+}  // namespace
+
+extern "C" int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int x0, int y0, int h,
+                            int w, int flags, const int32_t* priority_host, const double* thresholds_host,
+                            const int32_t* fill_priority_host, int n_fill_priority, const double* car_host,
+                            const uint8_t* car_color_host, uint8_t* out, void* stream) {
+    LiveParams p;
+    int rc;
+    if ((rc = live_params(p, map, map_dtype, Hm, Wm, C, colors_host, h, w, flags, priority_host, thresholds_host, fill_priority_host,
+                          n_fill_priority, car_host, car_color_host, out))) return rc;
+    p.x0 = x0; p.y0 = y0;
     const dim3 grid((unsigned)((w + kTW - 1) / kTW), (unsigned)((h + kTH - 1) / kTH)), block(kBlock);
     if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_live_map<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(map), p, out);
     else hipLaunchKernelGGL(k_live_map<float>, grid, block, 0, avl::as_stream(stream), static_cast<const float*>(map), p, out);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+extern "C" int avl_live_view(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, const double* matrix_host,
+                             int h, int w, int flags, const int32_t* priority_host, const double* thresholds_host,
+                             const int32_t* fill_priority_host, int n_fill_priority, const double* car_host,
+                             const uint8_t* car_color_host, uint8_t* out, void* stream) {
+    ViewParams vp;
+    int rc;
+    if ((rc = live_params(vp.p, map, map_dtype, Hm, Wm, C, colors_host, h, w, flags, priority_host, thresholds_host, fill_priority_host,
+                          n_fill_priority, car_host, car_color_host, out))) return rc;
+    AVL_REQUIRE(matrix_host, "matrix_host is NULL");
+    for (int k = 0; k < 6; ++k) {
+        AVL_REQUIRE(std::isfinite(matrix_host[k]), "matrix[%d][%d] = %g is not finite", k / 3, k % 3, matrix_host[k]);
+        vp.m[k] = matrix_host[k];
+    }
+    for (int r = 0; r < 2; ++r) {
+        const double span = std::fabs(vp.m[3 * r]) + std::fabs(vp.m[3 * r + 1]);
+        AVL_REQUIRE(span <= AVL_LIVE_VIEW_MAX_SPAN, "|M%d0| + |M%d1| = %.17g cells per pixel step: the limit is %g", r, r, span,
+                    (double)AVL_LIVE_VIEW_MAX_SPAN);
+    }
+    const dim3 grid((unsigned)((w + kVT - 1) / kVT), (unsigned)((h + kVT - 1) / kVT)), block(kBlock);
+    if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_live_view<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(map), vp, out);
+    else hipLaunchKernelGGL(k_live_view<float>, grid, block, 0, avl::as_stream(stream), static_cast<const float*>(map), vp, out);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
 }

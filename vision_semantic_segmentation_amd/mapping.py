@@ -20,7 +20,8 @@ What differs from the reference, by design:
     (e.g. the argmax label map straight from SemanticSegmentation).
   * ``live_map()`` renders the window of the grid around the vehicle (filter, renderer, hole fill, ego car) in one kernel; with
     MAPPING.LIVE_MAP.ENABLED ``mapping()`` / ``mapping_views()`` do so after the grid update.  The reference renders once, at
-    shutdown.
+    shutdown.  ``live_view()`` is the same picture heading-up: rotated about the vehicle, scaled, the vehicle at a chosen pixel
+    (MAPPING.LIVE_VIEW), still one kernel.
   * with MAPPING.OCCLUSION.ENABLED, points hidden behind nearer ones in a view's image do not vote (a per-view depth buffer, the
     rule at struct avl_occlusion in include/avl_hip.h); ``visibility_device()`` returns the verdict per point.  The reference lets
     every point that lands in the image vote.  Off by default.
@@ -244,6 +245,8 @@ class SemanticMapping(object):
 
         # live vehicle-centred map (MAPPING.LIVE_MAP); off by default
         self.live_cfg = cfg.MAPPING.LIVE_MAP
+        self.live_view_cfg = cfg.MAPPING.LIVE_VIEW   # the heading-up view's geometry
+        self.live_view_matrix_last = None      # 2 x 3 float64: the matrix of the last live_view()
         self.live_map_image = None             # uint8 [h, w, 3] on the device, the last live map
         self.live_map_host = None              # the same in pinned host memory, valid once the stream is synchronised
         self.live_map_origin = None            # grid cell of live_map_image[0, 0]
@@ -584,8 +587,8 @@ class SemanticMapping(object):
 
     def live_map(self, pose=None, size_cells=None, out=None, stream=None):
         """The map around the vehicle as a uint8 CUDA tensor [h, w, 3], rendered by one kernel (renderer.render_window with
-        MAPPING.LIVE_MAP's settings): out[i, j] is grid cell (x0 + i, y0 + j) in the global map's orientation (no heading-up
-        rotation), black where the window leaves the grid, the ego footprint painted last.  ``pose`` None = the last pose mapped;
+        MAPPING.LIVE_MAP's settings): out[i, j] is grid cell (x0 + i, y0 + j) in the global map's orientation (live_view() is the
+        heading-up picture), black where the window leaves the grid, the ego footprint painted last.  ``pose`` None = the last pose mapped;
         ``size_cells`` None = LIVE_MAP.SIZE_M.  Reads the grid only -- unlike finish_run, which replaces it by its filtered self.
         On several GPUs this is the rank's private grid, not global_map()."""
         from . import renderer
@@ -609,13 +612,57 @@ class SemanticMapping(object):
         self.live_map_origin = origin
         return img
 
+    def live_view_matrix(self, pose, size_px=None):
+        """-> 2 x 3 float64 ndarray: renderer.view_matrix for `pose` with MAPPING.LIVE_VIEW's geometry -- the vehicle's un-truncated
+        grid position (live_map_window's) at pixel ANCHOR * size, its heading up, METRES_PER_PIXEL / RESOLUTION cells per pixel
+        (0 = one cell per pixel).  ``size_px`` None = LIVE_VIEW.SIZE_PX."""
+        from . import renderer
+        vc = self.live_view_cfg
+        size = vc.SIZE_PX if size_px is None else size_px
+        mpp = float(vc.METRES_PER_PIXEL)
+        return renderer.view_matrix(self.live_map_window(pose, (1, 1))[2], pose_heading(pose),
+                                    mpp / self.resolution if mpp > 0.0 else 1.0, size, vc.ANCHOR)
+
+    def live_view(self, pose=None, size_px=None, out=None, stream=None):
+        """The heading-up live map as a uint8 CUDA tensor [h, w, 3], rendered by one kernel (renderer.render_view through
+        live_view_matrix(pose), with MAPPING.LIVE_MAP's filter, renderer, fill and car settings): the vehicle's heading points up,
+        black where the view leaves the grid, the ego footprint painted last.  ``pose`` None = the last pose mapped; ``size_px``
+        None = LIVE_VIEW.SIZE_PX.  Reads the grid only."""
+        from . import renderer
+        lc = self.live_cfg
+        pose = self._live_pose if pose is None else pose
+        if pose is None:
+            raise RuntimeError("live_view needs a pose: none was given and no frame has been mapped with one")
+        size = [int(v) for v in (self.live_view_cfg.SIZE_PX if size_px is None else size_px)]
+        matrix = self.live_view_matrix(pose, size)
+        car = None
+        if lc.DRAW_CAR:
+            c, s = pose_heading(pose)
+            cx, cy = self.live_map_window(pose, (1, 1))[2]
+            car = renderer.car_block(cx, cy, c, s, self.resolution, lc.CAR_SIZE)
+        if lc.RENDER not in ("argmax", "thresholds"):
+            raise ValueError("MAPPING.LIVE_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (lc.RENDER,))
+        thresholds = None
+        if lc.RENDER == "thresholds":
+            thresholds = lc.THRESHOLDS if lc.THRESHOLDS is not None else [0.01] * self.map_depth
+        img = renderer.render_view(self.map_dev, self.label_colors, matrix, size, filter=bool(lc.FILTER), thresholds=thresholds,
+                                   priority=lc.PRIORITY if lc.RENDER == "thresholds" else None, fill=bool(lc.FILL_BLACK),
+                                   fill_priority=lc.FILL_PRIORITY, car=car, out=out, stream=stream)
+        self.live_view_matrix_last = matrix
+        return img
+
     def _live_map_step(self, pose):
-        """mapping()'s live branch: on every EVERY-th call (the first included) render the window, keep it, start its copy into pinned memory and --
+        """mapping()'s live branch: on every EVERY-th call (the first included) render the window (the heading-up view with
+        MAPPING.LIVE_VIEW.HEADING_UP), keep it, start its copy into pinned memory and --
         under ROS -- publish it (sensor_msgs/Image, 8UC3, as mapping.py:349-350 does with the end-of-run map)."""
         self._live_frames = getattr(self, "_live_frames", 0) + 1
         if self._live_pose is None or (self._live_frames - 1) % max(int(self.live_cfg.EVERY), 1) != 0:
             return
-        img = self.live_map()
+        if self.live_view_cfg.HEADING_UP:
+            img = self.live_view()                            # records live_view_matrix_last
+            self.live_map_origin = None                       # the picture is no window of the grid
+        else:
+            img = self.live_map()
         self.live_map_image = img
         if self.live_map_host is None or self.live_map_host.shape != img.shape:
             self.live_map_host = torch.empty(tuple(img.shape), dtype=torch.uint8).pin_memory()

@@ -6,7 +6,8 @@ back as NumPy) or CUDA tensors (results stay on the GPU), so a live map can be r
 The renderer's remaining functions are here too: fill_black with resume_color (:62-105) and fill_edge (:192-196), which the reference
 defines and never calls, and render_window, the per-frame front end: filter, renderer, hole fill and the ego car
 (src/mapping.py:490-526) over a window of the grid in one kernel (avl_live_map), bit-equal to a crop of the chain of the functions
-above.
+above.  render_view is the same picture through a 2 x 3 matrix from output pixels to grid cells (avl_live_view): rotated, scaled,
+heading-up with view_matrix.
 """
 import ctypes as C
 
@@ -120,15 +121,8 @@ def car_block(cx, cy, cos_yaw, sin_yaw, resolution, size=CAR_SIZE):
             -length / (4.0 * res), 3.0 * length / (4.0 * res), -width / (2.0 * res), width / (2.0 * res))
 
 
-def render_window(map, label_colors, origin, size, filter=True, thresholds=None, priority=None, fill=False,
-                  fill_priority=FILL_PRIORITY, car=None, car_color=CAR_COLOR, out=None, stream=None):
-    """The window of `size` = (h, w) cells whose first cell is grid cell `origin` = (x0, y0), uint8 [h, w, 3]: what
-    ``render_bev_map(apply_filter(map).astype(map.dtype), label_colors)[x0:x0 + h, y0:y0 + w]`` gives (bit for bit), black where the
-    window leaves the grid -- in one kernel, reading about nine windows' worth of the grid and writing no temporary.
-    filter=False skips apply_filter; `thresholds` (with `priority`, low to high) picks render_bev_map_with_thresholds; fill=True
-    applies fill_black (label_colors, fill_priority) over the grid's interior, with a one-cell black ring where its output is
-    smaller than the grid; `car` = car_block(...) paints the ego footprint last.  The grid is only read."""
-    t, is_np, dt = _prep(map)
+def _live_args(t, label_colors, size, filter, thresholds, priority, fill, fill_priority, car, car_color, out, stream):
+    """the arguments avl_live_map and avl_live_view share, as ctypes values (kept alive by the caller's tuple)"""
     hm, wm, c = t.shape
     h, w = int(size[0]), int(size[1])
     colors = _colors(label_colors, c)
@@ -156,7 +150,54 @@ def render_window(map, label_colors, origin, size, filter=True, thresholds=None,
     elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (h, w, t.device))
     s = _stream(t) if stream is None else C.c_void_p(int(stream))
+    return h, w, colors, flags, pr, th, (C.c_int32 * max(len(fp), 1))(*fp), len(fp), car_c, col_c, out, s
+
+
+def render_window(map, label_colors, origin, size, filter=True, thresholds=None, priority=None, fill=False,
+                  fill_priority=FILL_PRIORITY, car=None, car_color=CAR_COLOR, out=None, stream=None):
+    """The window of `size` = (h, w) cells whose first cell is grid cell `origin` = (x0, y0), uint8 [h, w, 3]: what
+    ``render_bev_map(apply_filter(map).astype(map.dtype), label_colors)[x0:x0 + h, y0:y0 + w]`` gives (bit for bit), black where the
+    window leaves the grid -- in one kernel, reading about nine windows' worth of the grid and writing no temporary.
+    filter=False skips apply_filter; `thresholds` (with `priority`, low to high) picks render_bev_map_with_thresholds; fill=True
+    applies fill_black (label_colors, fill_priority) over the grid's interior, with a one-cell black ring where its output is
+    smaller than the grid; `car` = car_block(...) paints the ego footprint last.  The grid is only read."""
+    t, is_np, dt = _prep(map)
+    hm, wm, c = t.shape
+    h, w, colors, flags, pr, th, fp, n_fp, car_c, col_c, out, s = _live_args(t, label_colors, size, filter, thresholds, priority, fill,
+                                                                             fill_priority, car, car_color, out, stream)
     _lib.check(_lib.lib().avl_live_map(C.c_void_p(t.data_ptr()), dt, hm, wm, c, colors, int(origin[0]), int(origin[1]), h, w,
-                                       flags, pr, th, (C.c_int32 * max(len(fp), 1))(*fp), len(fp), car_c, col_c,
-                                       C.c_void_p(out.data_ptr()), s), "avl_live_map")
+                                       flags, pr, th, fp, n_fp, car_c, col_c, C.c_void_p(out.data_ptr()), s), "avl_live_map")
+    return out.cpu().numpy() if is_np else out
+
+
+def view_matrix(centre_cells, heading, cells_per_pixel, size, anchor=(0.5, 0.5)):
+    """The 2 x 3 float64 matrix of render_view for a heading-up picture of `size` = (h, w) pixels: pixel centre (anchor[0] * h,
+    anchor[1] * w) -- fractions of the height from the top and of the width from the left -- shows the grid position `centre_cells`
+    = (cx, cy) in cells, up in the picture is `heading` = (cos, sin) in the grid's x, y axes (mapping.pose_heading), right is the
+    vehicle's right seen from above, (sin, -cos), and one pixel spans `cells_per_pixel` cells.  heading (-1, 0) at 1 cell per pixel
+    is the orientation of render_window."""
+    k, (c, s) = float(cells_per_pixel), (float(heading[0]), float(heading[1]))
+    cx, cy = float(centre_cells[0]), float(centre_cells[1])
+    ai, aj = float(anchor[0]) * int(size[0]), float(anchor[1]) * int(size[1])
+    m00, m01, m10, m11 = -k * c, k * s, -k * s, -k * c
+    return np.array([[m00, m01, (cx - m00 * ai) - m01 * aj], [m10, m11, (cy - m10 * ai) - m11 * aj]], dtype=np.float64)
+
+
+def render_view(map, label_colors, matrix, size, filter=True, thresholds=None, priority=None, fill=False,
+                fill_priority=FILL_PRIORITY, car=None, car_color=CAR_COLOR, out=None, stream=None):
+    """The live picture through `matrix` (2 x 3, float64), uint8 [h, w, 3] for `size` = (h, w): pixel (i, j) shows the grid cell
+    (floor(gx), floor(gy)) with gx = (M00 (i + 0.5) + M01 (j + 0.5)) + M02 and gy likewise from row 1 -- nearest-cell sampling of
+    what render_window draws for the whole grid (filter, renderer, fill_black with its black ring), black where (gx, gy) leaves
+    the grid; `car` = car_block(...) is tested on (gx, gy) itself and painted last.  One kernel, no temporary; the other arguments
+    are render_window's.  With matrix [[1, 0, x0], [0, 1, y0]] this is render_window(origin=(x0, y0)) byte for byte.  |M00| + |M01|
+    and |M10| + |M11| may not exceed _lib.AVL_LIVE_VIEW_MAX_SPAN (any rotation up to 2 cells per pixel does not)."""
+    t, is_np, dt = _prep(map)
+    hm, wm, c = t.shape
+    m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64))
+    if m.shape != (2, 3):
+        raise ValueError("matrix must be 2 x 3, not %s" % (m.shape,))
+    h, w, colors, flags, pr, th, fp, n_fp, car_c, col_c, out, s = _live_args(t, label_colors, size, filter, thresholds, priority, fill,
+                                                                             fill_priority, car, car_color, out, stream)
+    _lib.check(_lib.lib().avl_live_view(C.c_void_p(t.data_ptr()), dt, hm, wm, c, colors, (C.c_double * 6)(*m.ravel().tolist()), h, w,
+                                        flags, pr, th, fp, n_fp, car_c, col_c, C.c_void_p(out.data_ptr()), s), "avl_live_view")
     return out.cpu().numpy() if is_np else out

@@ -1,5 +1,5 @@
-"""Occlusion culling on the GPU (csrc/mapping.hip: k_occl_depth, k_fused_vote_occl, k_views_vote_occl, k_occl_visibility) against the
-NumPy restatement of the rule (tests/_occlusion_reference.py).
+"""Occlusion culling on the GPU (csrc/mapping.hip: k_occl_depth, the OCCL instantiations of k_fused_vote and k_views_vote,
+k_occl_visibility) against the NumPy restatement of the rule (tests/_occlusion_reference.py).
 
 States are compared point by point.  Grids are compared bit for bit with what the PLAIN calls do with the cloud from which the
 reference's culled points were removed (padded back to n with points that project nowhere, so that the same vote / apply path runs;

@@ -1,5 +1,5 @@
-"""Points labelled from interpolated logits on the GPU (csrc/mapping.hip: k_fused_vote_logits, k_views_vote_logits, k_point_labels)
-against the NumPy float32 restatement of the rule (tests/_point_logits_reference.py).
+"""Points labelled from interpolated logits on the GPU (csrc/mapping.hip: the logits instantiations of k_fused_vote and k_views_vote,
+k_point_labels) against the NumPy float32 restatement of the rule (tests/_point_logits_reference.py).
 
 States are compared point by point and margins bit for bit.  Grids are compared bit for bit with what the PLAIN class-map call does
 on the same cloud when it is fed the reference's full label map (255 where the pixel abstains), on the grids, clouds and path table

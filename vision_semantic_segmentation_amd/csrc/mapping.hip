@@ -16,6 +16,7 @@
 
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -52,13 +53,38 @@ struct LutParams {
     unsigned lut[256];
 };
 
-// avl_occlusion in kernel-argument form (the culling kernels are at the end of this file)
+// avl_occlusion in kernel-argument form
 struct OcclParams {
     unsigned* depth;     // [n_views][Hc][Wc]: bit pattern of the nearest candidate's float32 depth, 0xFFFFFFFF = empty cell
     int* culled;         // [n_views] culled candidates, or NULL
     double k, abs_tol;   // a candidate of depth q is culled iff (double)q > (double)m * k + abs_tol; k = 1 + rel_tol
     int s, R, Wc, Hc;    // cell edge in pixels, neighbourhood radius in cells, buffer size
 };
+
+constexpr int kMaxViews = AVL_MAX_VIEWS;
+static_assert(kMaxViews * 8 == 32, "one vote byte per view in the 32-bit mask word");
+
+// several cameras, one cloud: one P and one byte source per view, T and the range shared
+struct ViewsParams {
+    double P[kMaxViews][12];
+    double T[16];
+    const unsigned char* src[kMaxViews];
+    double range_max;
+    int has_T, n_views, img_w, img_h;
+};
+
+// avl_point_logits in kernel-argument form
+struct LogitsParams {
+    const float* logits[kMaxViews];
+    int* abstained;                   // [n_views] abstentions, or NULL
+    long long ld;
+    int h, w, K, net_h, net_w;
+    float sy, sx, min_margin;
+};
+
+// The semantic source of a vote kernel: the two public kinds, and the plan's fp32 logits (avl_fused_frame_logits and its kin)
+constexpr int kSrcLogits = 2;
+static_assert(kSrcLogits != AVL_SRC_RGB && kSrcLogits != AVL_SRC_CLASSMAP, "the logits source is no public AVL_SRC_*");
 
 __device__ __forceinline__ void load_point(const PtsView& v, int k, double& x, double& y, double& z, double& it) {
     if (v.aos_f32) {
@@ -120,23 +146,38 @@ __device__ __forceinline__ double dot4(const double* r, double a, double b, doub
     return s;
 }
 
-// `p2` = the third row of P . v, the divisor of :375: the depth the occlusion test compares (k_occl_depth, occl_culled)
-__device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy, double& p2) {
-    double v0 = x, v1 = y, v2 = z, v3 = 1.0;
-    if (pp.has_T) {
-        v0 = dot4(pp.T + 0, x, y, z, 1.0);
-        v1 = dot4(pp.T + 4, x, y, z, 1.0);
-        v2 = dot4(pp.T + 8, x, y, z, 1.0);
-        v3 = dot4(pp.T + 12, x, y, z, 1.0);
+// :371 and :378: v = T . (x, y, z, 1), or the point itself without a T; true when 0 < v.x < range_max.  The same for every view.
+__device__ __forceinline__ bool to_camera(const double* T, int has_T, double range_max, double x, double y, double z, double& v0,
+                                          double& v1, double& v2, double& v3) {
+    v0 = x; v1 = y; v2 = z; v3 = 1.0;
+    if (has_T) {
+        v0 = dot4(T + 0, x, y, z, 1.0);
+        v1 = dot4(T + 4, x, y, z, 1.0);
+        v2 = dot4(T + 8, x, y, z, 1.0);
+        v3 = dot4(T + 12, x, y, z, 1.0);
     }
-    const double p0 = dot4(pp.P + 0, v0, v1, v2, v3);
-    const double p1 = dot4(pp.P + 4, v0, v1, v2, v3);
-    p2 = dot4(pp.P + 8, v0, v1, v2, v3);
+    return (0.0 < v0) && (v0 < range_max);
+}
+
+// :375 and :381-383 through one view's P: true when the pixel lies in the image.  `p2` = the third row of P . v, the divisor of
+// :375: the depth the occlusion test compares (k_occl_depth, occl_culled)
+__device__ __forceinline__ bool project_view(const double* P, double v0, double v1, double v2, double v3, int img_w, int img_h, int& ix,
+                                             int& iy, double& p2) {
+    const double p0 = dot4(P + 0, v0, v1, v2, v3);
+    const double p1 = dot4(P + 4, v0, v1, v2, v3);
+    p2 = dot4(P + 8, v0, v1, v2, v3);
     const double rp2 = refine_rcp(p2);
     ix = div_i32_numpy(p0, p2, rp2);
     iy = div_i32_numpy(p1, p2, rp2);
-    const bool positive = (0.0 < v0) && (v0 < pp.range_max);
-    return positive && ix >= 0 && ix < pp.img_w && iy >= 0 && iy < pp.img_h;
+    return ix >= 0 && ix < img_w && iy >= 0 && iy < img_h;
+}
+
+// one camera: the pixel is computed whatever the range test says (k_project_points writes it)
+__device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy, double& p2) {
+    double v0, v1, v2, v3;
+    const bool positive = to_camera(pp.T, pp.has_T, pp.range_max, x, y, z, v0, v1, v2, v3);
+    const bool in_image = project_view(pp.P, v0, v1, v2, v3, pp.img_w, pp.img_h, ix, iy, p2);
+    return positive && in_image;
 }
 __device__ __forceinline__ bool project(const ProjParams& pp, double x, double y, double z, int& ix, int& iy) {
     double p2;
@@ -165,6 +206,123 @@ __device__ __forceinline__ unsigned vote_from_rg(const GridParams& g, unsigned r
 __device__ __forceinline__ unsigned add_bonus(unsigned vote, unsigned bonus_classes, double intensity) {
     if ((vote & bonus_classes) && (intensity < 2.0 || intensity > 14.0)) vote |= (vote & bonus_classes) << 16;
     return vote;
+}
+
+// the label fetch of a byte source at pixel (ix, iy) of the img_w x img_h projection image -> vote bits
+template <int SRC>
+__device__ __forceinline__ unsigned fetch_vote(const GridParams& g, const LutParams& lut, const unsigned char* __restrict__ src, int src_w,
+                                               int src_h, int img_w, int img_h, int ix, int iy) {
+    if (SRC == AVL_SRC_RGB) {
+        const unsigned char* px = src + 3ll * ((long long)iy * src_w + ix);
+        return vote_from_rg(g, px[0], px[1]);
+    }
+    // cv2 INTER_NEAREST source index: min(floor(d * (src/dst)), src - 1), double arithmetic
+    int sx = ix, sy = iy;
+    if (src_w != img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)img_w)), src_w - 1);
+    if (src_h != img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)img_h)), src_h - 1);
+    return lut.lut[src[(long long)sy * src_w + sx]];
+}
+
+// ---------------------------------------------------------------- occlusion culling (avl_fused_frame_occl and its kin)
+// A map point behind a wall projects onto the wall's pixels and takes its label.  Before the vote, every view gets a coarse depth
+// buffer in image space; a point votes only if it is not clearly behind the nearest point of its image neighbourhood.  The rule
+// (include/avl_hip.h states it in full):
+//   candidate: a point that passes project(): 0 < v0 < range_max and 0 <= ix < img_w, 0 <= iy < img_h, on the grid or not;
+//   key q = (float)p2, p2 the third row of P . v; only a finite key > 0 is written to the buffer or compared;
+//   depth[iy / s][ix / s] = min of the keys' bit patterns (positive floats order as unsigned integers), 0xFFFFFFFF = empty;
+//   m = min of depth over the (2R + 1)^2 cells around the candidate's, clipped to the buffer;
+//   culled iff (double)q > (double)m * k + abs_tol (a multiplication and an addition, each rounded: -ffp-contract=off).
+// Integer atomicMin and, for the counts, integer atomicAdd only: the result does not depend on the order of the points.
+
+// the key of depth p2 as its bit pattern; false for a key that is not finite and > 0 (it is neither written nor culled)
+__device__ __forceinline__ bool depth_key(double p2, unsigned& bits) {
+    const float q = (float)p2;
+    bits = __float_as_uint(q);
+    return q > 0.0f && q < __builtin_inff();
+}
+
+__device__ __forceinline__ long long depth_cell(const OcclParams& oc, int v, int ix, int iy) {
+    return ((long long)v * oc.Hc + iy / oc.s) * oc.Wc + ix / oc.s;
+}
+
+// the cull test of a candidate of view v with a valid key: its own cell is in the neighbourhood, so m <= bits and m is a key
+__device__ __forceinline__ bool occl_culled(const OcclParams& oc, int v, int ix, int iy, unsigned bits) {
+    const int cx = ix / oc.s, cy = iy / oc.s;
+    const int x0 = max(cx - oc.R, 0), x1 = min(cx + oc.R, oc.Wc - 1), y0 = max(cy - oc.R, 0), y1 = min(cy + oc.R, oc.Hc - 1);
+    const unsigned* depth = oc.depth + (long long)v * oc.Hc * oc.Wc;
+    unsigned m = 0xffffffffu;
+    for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) m = min(m, depth[y * oc.Wc + x]);
+    return (double)__uint_as_float(bits) > (double)__uint_as_float(m) * oc.k + oc.abs_tol;
+}
+
+// culled candidates of one view: one atomic per wave that has any.  Every lane of the wave must arrive here.
+__device__ __forceinline__ void count_culled(int* counts, int v, bool culled) {
+    if (!counts) return;
+    const unsigned long long m = __ballot(culled);
+    if (m != 0ull && (threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(&counts[v], __builtin_popcountll(m));
+}
+
+// ---------------------------------------------------------------- points labelled from interpolated logits (avl_fused_frame_logits and its kin)
+// The class-map source hands a point the arg-max of the nearest low-resolution pixel.  The logits source reads the plan's fp32 logits
+// instead and evaluates the reference model's full-resolution prediction (bilinear, align_corners=True, then arg-max:
+// deeplab_v3_plus.py:67-69) at the point's pixel alone, with the top-1 minus top-2 margin as a confidence: a point whose margin is
+// below min_margin abstains.  The rule is stated in full at struct avl_point_logits in include/avl_hip.h; the interpolation is that of
+// seg_head.hip (src_coord, corner, lerp4) with every float32 operation rounded on its own, which -ffp-contract=off gives here.
+// What a lane fetches: the K logits of four source pixels, each a run of K consecutive floats (76 bytes at K = 19, ld = K: 4-byte
+// aligned only, so no lane can count on a 16-byte boundary).  The loop takes four classes of each corner at a time -- sixteen
+// independent loads in flight before the first is used, which the compiler merges into dwordx4 / dwordx2 loads of 4-byte alignment
+// (gfx950 allows them on global memory) -- and keeps only the running best, second best and index.
+
+// One more class for the running arg-max: the first maximal index wins and a NaN counts as maximal (AVL_OP_ARGMAX, eval_pixel of
+// seg_head.hip); `second` follows as the largest of the others.  best = second = -inf, top = 0 to start with.
+__device__ __forceinline__ void take_logit(float v, int k, float& best, float& second, int& top) {
+    if (v > best || (v != v && best == best)) { second = best; best = v; top = k; }
+    else if (v > second) second = v;
+}
+
+// rules 2 - 5 at pixel (ix, iy) of the img_w x img_h projection image: -> top, and the margin
+__device__ __forceinline__ int point_label(const LogitsParams& lp, const float* __restrict__ src, int img_w, int img_h, int ix, int iy,
+                                           float& margin) {
+    int nx = ix, ny = iy;                                                  // the index rule of fetch_vote, towards the network's input
+    if (lp.net_w != img_w) nx = min((int)__builtin_floor((double)ix * ((double)lp.net_w / (double)img_w)), lp.net_w - 1);
+    if (lp.net_h != img_h) ny = min((int)__builtin_floor((double)iy * ((double)lp.net_h / (double)img_h)), lp.net_h - 1);
+    const float fy = lp.sy * (float)ny, fx = lp.sx * (float)nx;
+    const int y0 = min((int)fy, lp.h - 1), x0 = min((int)fx, lp.w - 1);
+    const int y1 = y0 + (y0 < lp.h - 1 ? 1 : 0), x1 = x0 + (x0 < lp.w - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float* __restrict__ a = src + ((long long)y0 * lp.w + x0) * lp.ld;
+    const float* __restrict__ b = src + ((long long)y0 * lp.w + x1) * lp.ld;
+    const float* __restrict__ c = src + ((long long)y1 * lp.w + x0) * lp.ld;
+    const float* __restrict__ d = src + ((long long)y1 * lp.w + x1) * lp.ld;
+    float best = -__builtin_inff(), second = -__builtin_inff();
+    int top = 0, k = 0;
+    for (; k + 4 <= lp.K; k += 4) {
+        float va[4], vb[4], vc[4], vd[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { va[j] = a[k + j]; vb[j] = b[k + j]; vc[j] = c[k + j]; vd[j] = d[k + j]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) take_logit(hy * (hx * va[j] + lx * vb[j]) + ly * (hx * vc[j] + lx * vd[j]), k + j, best, second, top);
+    }
+    for (; k < lp.K; ++k) take_logit(hy * (hx * a[k] + lx * b[k]) + ly * (hx * c[k] + lx * d[k]), k, best, second, top);
+    margin = lp.K == 1 ? __builtin_inff() : best - second;
+    return top;
+}
+
+// The vote of one candidate pixel, whatever the source: a byte source always has one (its bits may be zero); the logits source
+// abstains where the margin is below min_margin.  `src` / `logits`: this view's image.
+template <int SRC>
+__device__ __forceinline__ unsigned pixel_vote(const GridParams& g, const LutParams& lut, const LogitsParams& lp, const unsigned char* __restrict__ src,
+                                               const float* __restrict__ logits, int src_w, int src_h, int img_w, int img_h, int ix, int iy,
+                                               double intensity, bool& abstains) {
+    if (SRC == kSrcLogits) {
+        float margin;
+        const int top = point_label(lp, logits, img_w, img_h, ix, iy, margin);
+        abstains = margin < lp.min_margin;
+        return abstains ? 0u : add_bonus(lut.lut[top], g.bonus_classes, intensity);
+    }
+    return add_bonus(fetch_vote<SRC>(g, lut, src, src_w, src_h, img_w, img_h, ix, iy), g.bonus_classes, intensity);
 }
 
 // OR the vote into the cell; the lane that turns the mask non-zero records the cell.  The append
@@ -326,18 +484,12 @@ __global__ void __launch_bounds__(kBlock) k_vote_labelled(const double* __restri
 // (workgroups of k) x 256 entries, so `cap` = ceil(nwg / kLists) * 256 never overflows.
 constexpr int kLists = 64;
 constexpr int kListBase = 4;                 // counter[4 .. 4 + kLists): cursors; counter[4 + kLists .. 4 + 2 kLists): apply tickets
-__device__ __forceinline__ void cast_vote_byte_lists(unsigned* cell_mask, int* touched, int* counter, int cap, int cell, unsigned vote,
-                                                     int C, unsigned bonus_classes) {
+// The append of the lane's cell (`first`: this lane turned the cell's mask non-zero) to the workgroup's list; every lane of the
+// workgroup must arrive here.
+__device__ __forceinline__ void append_listed(int* touched, int* counter, int cap, bool first, int cell) {
     __shared__ int wg_count, wg_base;
     if (threadIdx.x == 0) wg_count = 0;
     __syncthreads();
-    bool first = false;
-    if (cell >= 0 && vote != 0) {
-        const unsigned enc = encode_vote_byte(vote, C, bonus_classes);
-        const unsigned sh = 8u * ((unsigned)cell & 3u);
-        const unsigned old = atomicOr(&cell_mask[cell >> 2], enc << sh);
-        first = ((old >> sh) & 0xffu) == 0u;          // this lane turned the cell's byte non-zero: it lists the cell
-    }
     const unsigned long long m = __ballot(first);
     const int lane = threadIdx.x & 63;
     int wave_off = 0;
@@ -348,47 +500,192 @@ __device__ __forceinline__ void cast_vote_byte_lists(unsigned* cell_mask, int* t
     if (threadIdx.x == 0 && wg_count > 0) wg_base = atomicAdd(&counter[kListBase + list], wg_count);
     __syncthreads();
     // cap = (vote workgroups of this list) x 256 cannot overflow while the cursors start from zero; they would not after an apply
-    // launch that failed (the host then resets them, avl_fused_frame), so the append is bounded all the same: an entry
+    // launch that failed (the host then resets them, lists_applied), so the append is bounded all the same: an entry
     // past cap is dropped, never written outside the list
     const int slot = wg_base + wave_off + __builtin_popcountll(m & ((1ull << lane) - 1ull));
     if (first && slot < cap) touched[(long long)list * cap + slot] = cell;
 }
+// byte mask + lists (MODE 3 of k_fused_vote)
+__device__ __forceinline__ void cast_vote_byte_lists(unsigned* cell_mask, int* touched, int* counter, int cap, int cell, unsigned vote,
+                                                     int C, unsigned bonus_classes) {
+    bool first = false;
+    if (cell >= 0 && vote != 0) {
+        const unsigned enc = encode_vote_byte(vote, C, bonus_classes);
+        const unsigned sh = 8u * ((unsigned)cell & 3u);
+        const unsigned old = atomicOr(&cell_mask[cell >> 2], enc << sh);
+        first = ((old >> sh) & 0xffu) == 0u;          // this lane turned the cell's byte non-zero: it lists the cell
+    }
+    append_listed(touched, counter, cap, first, cell);
+}
+// word mask + lists (k_views_vote): the whole word is the cell's mask
+__device__ __forceinline__ void cast_vote_word_lists(unsigned* cell_mask, int* touched, int* counter, int cap, int cell, unsigned word) {
+    bool first = false;
+    if (cell >= 0 && word != 0u) first = atomicOr(&cell_mask[cell], word) == 0u;   // this lane turned the word non-zero: it lists the cell
+    append_listed(touched, counter, cap, first, cell);
+}
 
+// One lane per point: project, cull (OCCL), cell, label, vote.
+// SRC:  AVL_SRC_RGB, AVL_SRC_CLASSMAP (src, src_w, src_h, lut) or kSrcLogits (lp, lut: class -> vote bits)
 // MODE: 0 = 32-bit mask + touched list, 1 = 32-bit mask only (sweep), 2 = byte mask only (sweep, see encode_vote_byte),
 //       3 = byte mask + partitioned touched lists (k_grid_apply_lists)
-template <int SRC, int MODE>
+// OCCL: the cull test against the depth buffer of k_occl_depth stands between the projection and the cell.  A culled candidate never
+//       evaluates grid_cell, so it casts no vote, fetches no label and, with the logits, is no abstention; it is counted.
+// lp and oc are passed whether used or not.  No early return: every lane reaches the ballots of count_culled and the barriers of
+// append_listed.
+template <int SRC, int MODE, int OCCL>
 __global__ void __launch_bounds__(kBlock) k_fused_vote(PtsView pv, ProjParams pp, GridParams g,
-                                                       const unsigned char* __restrict__ src, int src_w, int src_h,
+                                                       const unsigned char* __restrict__ src, int src_w, int src_h, LogitsParams lp,
                                                        LutParams lut, unsigned* __restrict__ cell_mask,
-                                                       int* __restrict__ touched, int* __restrict__ counter, int list_cap) {
+                                                       int* __restrict__ touched, int* __restrict__ counter, int list_cap, OcclParams oc) {
     const int k = blockIdx.x * kBlock + threadIdx.x;
     int cell = -1;
     unsigned vote = 0;
+    bool culled = false, abstains = false;
     if (k < pv.n) {
         double x, y, z, it;
         load_point(pv, k, x, y, z, it);
         int ix, iy;
-        if (project(pp, x, y, z, ix, iy)) {
-            cell = grid_cell(g, x, y, z);
-            if (cell >= 0) {
-                if (SRC == AVL_SRC_RGB) {
-                    const unsigned char* px = src + 3ll * ((long long)iy * src_w + ix);
-                    vote = vote_from_rg(g, px[0], px[1]);
-                } else {
-                    // cv2 INTER_NEAREST source index: min(floor(d * (src/dst)), src - 1), double arithmetic
-                    int sx = ix, sy = iy;
-                    if (src_w != pp.img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)pp.img_w)), src_w - 1);
-                    if (src_h != pp.img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)pp.img_h)), src_h - 1);
-                    vote = lut.lut[src[(long long)sy * src_w + sx]];
-                }
-                vote = add_bonus(vote, g.bonus_classes, it);
+        double p2;
+        if (project(pp, x, y, z, ix, iy, p2)) {
+            if (OCCL) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
             }
+            if (!culled) cell = grid_cell(g, x, y, z);
+            if (cell >= 0) vote = pixel_vote<SRC>(g, lut, lp, src, lp.logits[0], src_w, src_h, pp.img_w, pp.img_h, ix, iy, it, abstains);
         }
     }
+    if (OCCL) count_culled(oc.culled, 0, culled);
+    if (SRC == kSrcLogits) count_culled(lp.abstained, 0, abstains);
     if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
     else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
     else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
     else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
+}
+
+// Several cameras, one cloud (avl_fused_frame_views).  V synchronised cameras project the SAME cloud with the SAME pose
+// (src/mapping.py:273-285), and the grid cell of a point comes from its original coordinates (:403-409), not from the camera: every
+// view of a point votes into one cell.  So one lane per point loads it, applies T, tests the range and computes the cell ONCE, then
+// projects through each view's P, fetches that view's label and builds that view's vote byte (encode_vote_byte); the 32-bit word of
+// cell_mask holds byte v for view v and takes the votes of all views with one atomicOr.  The apply pass replays the bytes view by
+// view (apply_views_word), which is what V sequential frames do to the cell.
+// SRC, OCCL: as k_fused_vote, per view.  LISTS: 1 = word mask + partitioned lists (k_views_apply_lists), 0 = word mask only
+// (k_views_sweep_words).
+// An off-grid point casts no vote, so it is projected only with OCCL, where a culled off-grid candidate counts like any other (the
+// counts are those of k_occl_visibility's state 2).  Where a count is kept (OCCL, logits) its ballot sits in the loop over the views,
+// which every lane then runs in full; a plain byte source has no ballot, and only the lanes with a cell enter the loop.
+template <int SRC, int LISTS, int OCCL>
+__global__ void __launch_bounds__(kBlock) k_views_vote(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LogitsParams lp,
+                                                       LutParams lut, unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                       int* __restrict__ counter, int list_cap, OcclParams oc) {
+    constexpr bool kCounts = OCCL || SRC == kSrcLogits;
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned word = 0;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0;
+    if (k < pv.n) {
+        double x, y, z;
+        load_point(pv, k, x, y, z, it);
+        positive = to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3);
+        if (positive) cell = grid_cell(g, x, y, z);                        // :378 and :404-411: the same for every view
+    }
+    const bool candidate = positive && (OCCL || cell >= 0);
+    const int trips = (kCounts || candidate) ? vp.n_views : 0;             // kCounts: the same trip count in every lane
+    for (int v = 0; v < trips; ++v) {
+        bool culled = false, abstains = false;
+        int ix, iy;
+        double p2;
+        if (candidate && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {   // else this view does not see the point
+            if (OCCL) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
+            }
+            if (!culled && cell >= 0) {
+                const unsigned vote = pixel_vote<SRC>(g, lut, lp, vp.src[v], lp.logits[v], src_w, src_h, vp.img_w, vp.img_h, ix, iy, it, abstains);
+                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
+            }
+        }
+        if (OCCL) count_culled(oc.culled, v, culled);
+        if (SRC == kSrcLogits) count_culled(lp.abstained, v, abstains);
+    }
+    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
+    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);                // fire and forget, as cast_vote_nolist
+}
+
+// Depth pass, one view or several: one read of the cloud, T and the range test once per point, one atomicMin per candidate and
+// view (no return value: nothing waits for it).  Off-grid points take part: an off-grid wall hides what is behind it.
+__global__ void __launch_bounds__(kBlock) k_occl_depth(PtsView pv, ViewsParams vp, OcclParams oc) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= pv.n) return;
+    double x, y, z, it, v0, v1, v2, v3;
+    load_point(pv, k, x, y, z, it);
+    if (!to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3)) return;
+    for (int v = 0; v < vp.n_views; ++v) {
+        int ix, iy;
+        double p2;
+        unsigned bits;
+        if (project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2) && depth_key(p2, bits))
+            atomicMin(&oc.depth[depth_cell(oc, v, ix, iy)], bits);
+    }
+}
+
+// One state per point and view: 0 not a candidate, 1 visible, 2 culled; key (optional): the candidate's float32 depth, 0 for the rest.
+// Reads the depth buffer k_occl_depth filled.
+__global__ void __launch_bounds__(kBlock) k_occl_visibility(PtsView pv, ViewsParams vp, OcclParams oc, unsigned char* __restrict__ state,
+                                                            float* __restrict__ key) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = k < pv.n;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
+    if (live) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        positive = to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {
+        unsigned char st = 0;
+        unsigned bits = 0u;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2))
+            st = (depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits)) ? 2 : 1;
+        if (live) {
+            state[(long long)v * pv.n + k] = st;
+            if (key) key[(long long)v * pv.n + k] = st ? __uint_as_float(bits) : 0.0f;
+        }
+        count_culled(oc.culled, v, st == 2);
+    }
+}
+
+// The logits rule alone, per point and view, on the grid or not: state = top, 254 = abstained, 255 = no candidate of the view; margin
+// (optional) = the candidate's margin, 0 for the rest.
+__global__ void __launch_bounds__(kBlock) k_point_labels(PtsView pv, ViewsParams vp, LogitsParams lp, unsigned char* __restrict__ state,
+                                                         float* __restrict__ margin) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = k < pv.n;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
+    if (live) {
+        double x, y, z, it;
+        load_point(pv, k, x, y, z, it);
+        positive = to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3);
+    }
+    for (int v = 0; v < vp.n_views; ++v) {
+        unsigned char st = 255;
+        float m = 0.f;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
+            const int top = point_label(lp, lp.logits[v], vp.img_w, vp.img_h, ix, iy, m);
+            st = m < lp.min_margin ? 254 : (unsigned char)top;
+        }
+        if (live) {
+            state[(long long)v * pv.n + k] = st;
+            if (margin) margin[(long long)v * pv.n + k] = m;
+        }
+        count_culled(lp.abstained, v, st == 254);
+    }
 }
 
 // ---------------------------------------------------------------- touched cells -> grid (:424,437)
@@ -611,92 +908,7 @@ __global__ void __launch_bounds__(kBlock) k_grid_sweep_bytes(MapT* __restrict__ 
     }
 }
 
-// ================================================================ several cameras, one cloud (avl_fused_frame_views)
-// V synchronised cameras project the SAME cloud with the SAME pose (src/mapping.py:273-285), and the grid cell of a point comes
-// from its original coordinates (:403-409), not from the camera: every view of a point votes into one cell.  So one lane per
-// point loads it, applies T, tests the range and computes the cell ONCE, then projects through each view's P, fetches that
-// view's label and builds that view's vote byte (encode_vote_byte); the 32-bit word of cell_mask holds byte v for view v and
-// takes the votes of all views with one atomicOr.  The apply pass replays the bytes view by view (apply_views_word), which is
-// what V sequential frames do to the cell.
-constexpr int kMaxViews = AVL_MAX_VIEWS;
-static_assert(kMaxViews * 8 == 32, "one vote byte per view in the 32-bit mask word");
-
-struct ViewsParams {
-    double P[kMaxViews][12];
-    double T[16];
-    const unsigned char* src[kMaxViews];
-    double range_max;
-    int has_T, n_views, img_w, img_h;
-};
-
-// Word mask + partitioned touched lists: cast_vote_byte_lists with the whole word as the cell's mask.
-__device__ __forceinline__ void cast_vote_word_lists(unsigned* cell_mask, int* touched, int* counter, int cap, int cell, unsigned word) {
-    __shared__ int wg_count, wg_base;
-    if (threadIdx.x == 0) wg_count = 0;
-    __syncthreads();
-    bool first = false;
-    if (cell >= 0 && word != 0u) first = atomicOr(&cell_mask[cell], word) == 0u;   // this lane turned the word non-zero: it lists the cell
-    const unsigned long long m = __ballot(first);
-    const int lane = threadIdx.x & 63;
-    int wave_off = 0;
-    if (m != 0ull && lane == 0) wave_off = atomicAdd(&wg_count, __builtin_popcountll(m));
-    wave_off = __shfl(wave_off, 0);
-    __syncthreads();
-    const int list = blockIdx.x % kLists;
-    if (threadIdx.x == 0 && wg_count > 0) wg_base = atomicAdd(&counter[kListBase + list], wg_count);
-    __syncthreads();
-    // bounded like cast_vote_byte_lists: an entry past cap is dropped, never written outside the list
-    const int slot = wg_base + wave_off + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-    if (first && slot < cap) touched[(long long)list * cap + slot] = cell;
-}
-
-// LISTS: 1 = word mask + partitioned lists (k_views_apply_lists), 0 = word mask only (k_views_sweep_words)
-template <int SRC, int LISTS>
-__global__ void __launch_bounds__(kBlock) k_views_vote(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LutParams lut,
-                                                       unsigned* __restrict__ cell_mask, int* __restrict__ touched,
-                                                       int* __restrict__ counter, int list_cap) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    int cell = -1;
-    unsigned word = 0;
-    if (k < pv.n) {
-        double x, y, z, it;
-        load_point(pv, k, x, y, z, it);
-        double v0 = x, v1 = y, v2 = z, v3 = 1.0;
-        if (vp.has_T) {
-            v0 = dot4(vp.T + 0, x, y, z, 1.0);
-            v1 = dot4(vp.T + 4, x, y, z, 1.0);
-            v2 = dot4(vp.T + 8, x, y, z, 1.0);
-            v3 = dot4(vp.T + 12, x, y, z, 1.0);
-        }
-        if ((0.0 < v0) && (v0 < vp.range_max)) cell = grid_cell(g, x, y, z);      // :378 and :404-411: the same for every view
-        if (cell >= 0) {
-            for (int v = 0; v < vp.n_views; ++v) {
-                const double p0 = dot4(vp.P[v] + 0, v0, v1, v2, v3);
-                const double p1 = dot4(vp.P[v] + 4, v0, v1, v2, v3);
-                const double p2 = dot4(vp.P[v] + 8, v0, v1, v2, v3);
-                const double rp2 = refine_rcp(p2);
-                const int ix = div_i32_numpy(p0, p2, rp2);
-                const int iy = div_i32_numpy(p1, p2, rp2);
-                if (ix < 0 || ix >= vp.img_w || iy < 0 || iy >= vp.img_h) continue;   // this view does not see the point
-                unsigned vote;
-                if (SRC == AVL_SRC_RGB) {
-                    const unsigned char* px = vp.src[v] + 3ll * ((long long)iy * src_w + ix);
-                    vote = vote_from_rg(g, px[0], px[1]);
-                } else {
-                    int sx = ix, sy = iy;                                              // the index rule of k_fused_vote
-                    if (src_w != vp.img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)vp.img_w)), src_w - 1);
-                    if (src_h != vp.img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)vp.img_h)), src_h - 1);
-                    vote = lut.lut[vp.src[v][(long long)sy * src_w + sx]];
-                }
-                vote = add_bonus(vote, g.bonus_classes, it);
-                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
-            }
-        }
-    }
-    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
-    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);                // fire and forget, as cast_vote_nolist
-}
-
+// ================================================================ several cameras, one cloud: mask word -> grid
 // One cell's word -> its grid row: view 0's votes, then view 1's, ...; inside a view class i adds CM[:, i], then its bonus +2,
 // and every addition is rounded to the map type -- the sequence V calls of avl_fused_frame run on the cell, so the row ends
 // bit-identical to theirs (a store to MapT and a reload between two views changes nothing: the value is already a MapT).
@@ -1083,24 +1295,35 @@ int views_bits_check(const avl_grid* g, uint32_t bonus) {
     return AVL_OK;
 }
 
+// The semantic source of a fused frame as its entry point hands it on: byte images as the caller gave them (fill_frame checks
+// them), or the logits in kernel-argument form (logits_source has checked them).
+struct VoteSource {
+    bool logits;
+    int kind;                        // bytes: AVL_SRC_RGB or AVL_SRC_CLASSMAP
+    const uint8_t* const* bytes;     // bytes: one image per view
+    LogitsParams lp;
+    int w, h;
+};
 
-// What avl_fused_frame and avl_fused_frame_views take alike, validated and in kernel-argument form (`src`: the only or first view's
-// semantic source).  Everything here is refused before the empty cloud returns; touched_cap matters only to a cloud that votes.
+// What every fused frame takes, validated and in kernel-argument form.  Everything here is refused before the empty cloud returns;
+// touched_cap matters only to a cloud that votes.  The logits stand where a class map stands: a source, its size and a LUT.
 struct FrameArgs { PtsView pv; ProjParams pp; GridParams gp; LutParams lut; };
 int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-               const double* P_host, const double* T_host, double range_max, int src_kind, const uint8_t* src, int src_w, int src_h,
-               int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus) {
+               const double* P_host, const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h,
+               const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus) {
+    const int src_kind = src.logits ? AVL_SRC_CLASSMAP : src.kind;
+    const void* first = src.logits ? static_cast<const void*>(src.lp.logits[0]) : src.bytes[0];   // the only or first view's
     int rc;
     if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
     if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
     if ((rc = fill_grid(f.gp, g, label_colors_host, bonus))) return rc;
     AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
-    AVL_REQUIRE(src && src_w > 0 && src_h > 0, "bad semantic source");
+    AVL_REQUIRE(first && src.w > 0 && src.h > 0, "bad semantic source");
     AVL_REQUIRE(cm_host, "cm_host is NULL");
     memset(&f.lut, 0, sizeof(f.lut));
     if (src_kind == AVL_SRC_RGB) {
         AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
-        AVL_REQUIRE(src_w == img_w && src_h == img_h, "RGB source must be %dx%d", img_w, img_h);
+        AVL_REQUIRE(src.w == img_w && src.h == img_h, "RGB source must be %dx%d", img_w, img_h);
     } else {
         AVL_REQUIRE(lut_host, "lut_host is NULL");
         memcpy(f.lut.lut, lut_host, sizeof(f.lut.lut));
@@ -1108,18 +1331,6 @@ int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtyp
     if (n > 0) AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     return AVL_OK;
 }
-
-// Occlusion culling (avl_fused_frame_occl and its kin): defined with the culling kernels at the end of this file.
-//   occl_fill: validates an avl_occlusion for n_views views of img_w x img_h (host only) and puts it into kernel-argument form
-//   occl_reset: every depth cell back to empty and the culled counts to zero (two memsets) -- what makes a call independent of the last
-//   launch_occl_depth: the depth pass;  launch_*_vote_occl: the culling twin of k_fused_vote<SRC, mode> / k_views_vote<SRC, lists>
-int occl_fill(OcclParams& oc, const avl_occlusion* occl, int img_w, int img_h, int n_views);
-int occl_reset(const OcclParams& oc, int n_views, bool depth, hipStream_t s);
-int launch_occl_depth(const PtsView& pv, const ViewsParams& vp, const OcclParams& oc, hipStream_t s);
-int launch_fused_vote_occl(const FrameArgs& f, int src_kind, int mode, const uint8_t* src, int src_w, int src_h, const avl_grid* g, int list_cap,
-                           const OcclParams& oc, hipStream_t s);
-int launch_views_vote_occl(const FrameArgs& f, const ViewsParams& vp, int src_kind, bool lists, int src_w, int src_h, const avl_grid* g,
-                           int list_cap, const OcclParams& oc, hipStream_t s);
 
 void fill_views(ViewsParams& vp, const FrameArgs& f, int n_views, const double* P_host, const uint8_t* const* src_host) {
     memset(&vp, 0, sizeof(vp));
@@ -1133,49 +1344,219 @@ void fill_views(ViewsParams& vp, const FrameArgs& f, int n_views, const double* 
     vp.img_h = f.pp.img_h;
 }
 
-// what follows the vote kernel of path `mode` (avl_fused_frame_path) for a cloud of n points
+// ---- occlusion culling: an avl_occlusion validated for n_views views of img_w x img_h (host only) and in kernel-argument form
+long long occl_cells(int img_w, int img_h, int s) { return (long long)((img_w + s - 1) / s) * ((img_h + s - 1) / s); }
+
+int occl_fill(OcclParams& oc, const avl_occlusion* occl, int img_w, int img_h, int n_views) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    AVL_REQUIRE(occl->cell_px >= 1 && occl->cell_px <= 64, "occlusion cell_px = %d (1..64)", occl->cell_px);
+    AVL_REQUIRE(occl->radius >= 0 && occl->radius <= 2, "occlusion radius = %d (0..2)", occl->radius);
+    AVL_REQUIRE(occl->rel_tol >= 0.0, "occlusion rel_tol = %g (must be >= 0)", occl->rel_tol);     // a NaN fails the comparison too
+    AVL_REQUIRE(occl->abs_tol >= 0.0, "occlusion abs_tol = %g (must be >= 0)", occl->abs_tol);
+    AVL_REQUIRE(img_w > 0 && img_h > 0 && n_views >= 1 && n_views <= kMaxViews, "occlusion: %d views of %dx%d", n_views, img_w, img_h);
+    const long long words = occl_cells(img_w, img_h, occl->cell_px) * n_views;
+    AVL_REQUIRE(occl->depth, "occlusion depth scratch is NULL");
+    AVL_REQUIRE(occl->depth_words >= words, "occlusion depth scratch holds %lld words, %lld needed", (long long)occl->depth_words, words);
+    AVL_REQUIRE(words * 4 <= 0x7fffffffLL, "occlusion depth buffer of %lld words is too large", words);
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->depth) & 3) == 0, "occlusion depth scratch is not 4-byte aligned");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->culled) & 3) == 0, "occlusion culled counts are not 4-byte aligned");
+    oc.depth = occl->depth;
+    oc.culled = occl->culled;
+    oc.k = 1.0 + occl->rel_tol;
+    oc.abs_tol = occl->abs_tol;
+    oc.s = occl->cell_px;
+    oc.R = occl->radius;
+    oc.Wc = (img_w + oc.s - 1) / oc.s;
+    oc.Hc = (img_h + oc.s - 1) / oc.s;
+    return AVL_OK;
+}
+
+// every depth cell back to empty (`depth`) and the culled counts to zero: what makes a call independent of the last
+int occl_reset(const OcclParams& oc, int n_views, bool depth, hipStream_t s) {
+    if (depth) AVL_HIP_CHECK(hipMemsetAsync(oc.depth, 0xff, sizeof(unsigned) * (size_t)n_views * oc.Hc * oc.Wc, s));
+    if (oc.culled) AVL_HIP_CHECK(hipMemsetAsync(oc.culled, 0, sizeof(int) * n_views, s));
+    return AVL_OK;
+}
+
+int launch_occl_depth(const PtsView& pv, const ViewsParams& vp, const OcclParams& oc, hipStream_t s) {
+    hipLaunchKernelGGL(k_occl_depth, dim3((pv.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pv, vp, oc);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+// ---- logits: an avl_point_logits validated for n_views views (host only) and in kernel-argument form
+int logits_fill(LogitsParams& lp, const avl_point_logits* pl, int n_views) {
+    AVL_REQUIRE(pl, "avl_point_logits is NULL");
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    AVL_REQUIRE(pl->h > 0 && pl->w > 0, "logits of %dx%d pixels", pl->w, pl->h);
+    AVL_REQUIRE(pl->K >= 1 && pl->K <= 254, "logits K = %d (1..254)", pl->K);
+    AVL_REQUIRE(pl->ld >= pl->K, "logits ld = %lld < K = %d", (long long)pl->ld, pl->K);
+    AVL_REQUIRE(pl->ld <= (1ll << 61) / pl->h / pl->w, "logits of %dx%d pixels x ld %lld are too large", pl->w, pl->h, (long long)pl->ld);
+    AVL_REQUIRE(pl->net_h > 0 && pl->net_w > 0, "logits net size %dx%d", pl->net_w, pl->net_h);
+    AVL_REQUIRE(pl->min_margin >= 0.f, "logits min_margin = %g (must be >= 0)", (double)pl->min_margin);      // a NaN fails the comparison too
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->abstained) & 3) == 0, "logits abstained counts are not 4-byte aligned");
+    memset(&lp, 0, sizeof(lp));
+    for (int v = 0; v < n_views; ++v) {
+        AVL_REQUIRE(pl->logits[v], "view %d: logits are NULL", v);
+        AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->logits[v]) & 3) == 0, "view %d: logits are not 4-byte aligned", v);
+        lp.logits[v] = pl->logits[v];
+    }
+    lp.abstained = pl->abstained;
+    lp.ld = pl->ld;
+    lp.h = pl->h; lp.w = pl->w; lp.K = pl->K; lp.net_h = pl->net_h; lp.net_w = pl->net_w;
+    lp.sy = pl->net_h > 1 ? (float)(pl->h - 1) / (float)(pl->net_h - 1) : 0.f;          // as avl_seg_eval_full_res (seg_head.hip)
+    lp.sx = pl->net_w > 1 ? (float)(pl->w - 1) / (float)(pl->net_w - 1) : 0.f;
+    lp.min_margin = pl->min_margin;
+    return AVL_OK;
+}
+
+int logits_reset(const LogitsParams& lp, int n_views, hipStream_t s) {
+    if (lp.abstained) AVL_HIP_CHECK(hipMemsetAsync(lp.abstained, 0, sizeof(int) * n_views, s));
+    return AVL_OK;
+}
+
+// the source of the byte and of the logits entry points
+VoteSource bytes_source(int src_kind, const uint8_t* const* src_host, int src_w, int src_h) {
+    VoteSource src = {};
+    src.kind = src_kind; src.bytes = src_host; src.w = src_w; src.h = src_h;
+    return src;
+}
+int logits_source(VoteSource& src, const avl_point_logits* pl, int n_views) {
+    src = {};
+    src.logits = true;
+    int rc;
+    if ((rc = logits_fill(src.lp, pl, n_views))) return rc;
+    src.w = pl->w; src.h = pl->h;
+    return AVL_OK;
+}
+
+// ---- the vote.  A runtime value in [0, N) as a compile-time one: f(std::integral_constant<int, v>()); the template arguments of
+// the two vote kernels go through here, as the map's element type goes through launch_map_typed.
+template <int N, typename F>
+void with_constant(int v, F&& f) {
+    if constexpr (N == 1) f(std::integral_constant<int, 0>());
+    else if (v == N - 1) f(std::integral_constant<int, N - 1>());
+    else with_constant<N - 1>(v, f);
+}
+
+// `oc` is that of `occl`, or all zero without one
+int launch_fused_vote(const FrameArgs& f, const VoteSource& src, int mode, bool occl, const OcclParams& oc, const avl_grid* g, int list_cap,
+                      hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+    const uint8_t* bytes = src.logits ? nullptr : src.bytes[0];
+    with_constant<3>(src.logits ? kSrcLogits : src.kind, [&](auto S) {
+        with_constant<4>(mode, [&](auto M) {
+            with_constant<2>(occl, [&](auto O) {
+                hipLaunchKernelGGL((k_fused_vote<decltype(S)::value, decltype(M)::value, decltype(O)::value>), grid, block, 0, s, f.pv, f.pp,
+                                   f.gp, bytes, src.w, src.h, src.lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc);
+            });
+        });
+    });
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+int launch_views_vote(const FrameArgs& f, const ViewsParams& vp, const VoteSource& src, bool lists, bool occl, const OcclParams& oc,
+                      const avl_grid* g, int list_cap, hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+    with_constant<3>(src.logits ? kSrcLogits : src.kind, [&](auto S) {
+        with_constant<2>(lists, [&](auto L) {
+            with_constant<2>(occl, [&](auto O) {
+                hipLaunchKernelGGL((k_views_vote<decltype(S)::value, decltype(L)::value, decltype(O)::value>), grid, block, 0, s, f.pv, vp,
+                                   f.gp, src.w, src.h, src.lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc);
+            });
+        });
+    });
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+// ---- the apply.  What follows the vote kernel of path `mode` (avl_fused_frame_path) for a cloud of n points
 int apply_frame(const avl_grid* g, const double* cm_host, uint32_t bonus_classes, int mode, int n, hipStream_t s) {
     if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
     if (mode == 2) return launch_sweep_bytes(g, cm_host, bonus_classes, s);
     return mode == 1 ? launch_apply_scan(g, cm_host, s) : launch_apply(g, cm_host, nullptr, 0, s);
 }
 
-// avl_fused_frame, and with `occl` avl_fused_frame_occl: the path is decided from n alike, the depth pass runs first and the vote
-// kernel is the culling twin; the apply and sweep kernels are the same.
-int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
-                const double* T_host, double range_max, int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
-                const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes,
-                const avl_occlusion* occl, void* stream) {
-    FrameArgs f;
+// what follows the views vote kernel: the lists' apply (path 4) or the sweep of the word mask (path 5)
+int apply_views(const avl_grid* g, const double* cm_host, uint32_t bonus_classes, bool lists, const ListGeom& lg, hipStream_t s) {
+    CmParams cm;
+    int rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
+    const dim3 block(kBlock);
+    if (lists)
+        return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
+            typedef decltype(t) T;
+            hipLaunchKernelGGL(k_views_apply_lists<T>, dim3(lg.apply_wgs), block, 0, s, static_cast<T*>(g->map), g->C, bonus_classes, cm,
+                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
+        }), s);
+    const long long ncell = (long long)g->Hm * g->Wm;
+    const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
+                           bonus_classes, cm, g->cell_mask, ncell, vec);
+    });
+}
+
+// ---- the frame.  What every fused frame does once fill_frame has accepted it, whatever its source and arity: the resets, the
+// path from n, with `occl` the depth pass, the vote, the apply.  The apply and sweep kernels know nothing of source or culling.
+int run_frame(const avl_grid* g, const FrameArgs& f, int n_views, const double* P_host, const VoteSource& src, const double* cm_host,
+              uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    const int n = f.pv.n;
     OcclParams oc;
     int rc;
-    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
-                         lut_host, label_colors_host, cm_host, bonus_classes)))
-        return rc;
-    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, 1))) return rc;
+    memset(&oc, 0, sizeof(oc));
+    if (occl && (rc = occl_fill(oc, occl, f.pp.img_w, f.pp.img_h, n_views))) return rc;
     hipStream_t s = avl::as_stream(stream);
-    if (n == 0) return occl ? occl_reset(oc, 1, false, s) : AVL_OK;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const int mode = avl_fused_frame_path(g, n, bonus_classes);
-    if (mode < 0) return mode;
+    if (src.logits && (rc = logits_reset(src.lp, n_views, s))) return rc;
+    if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;         // an empty cloud resets the counts, not the depth buffer
+    const int path = n_views == 1 ? avl_fused_frame_path(g, n, bonus_classes) : (lists_fit(g, n) ? 4 : 5);
+    if (path < 0) return path;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, src.logits ? nullptr : src.bytes);
     if (occl) {
-        ViewsParams vp;
-        fill_views(vp, f, 1, P_host, nullptr);
-        if ((rc = occl_reset(oc, 1, true, s))) return rc;
+        if ((rc = occl_reset(oc, n_views, true, s))) return rc;
         if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
     }
-    if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
-    const int list_cap = list_geom(n).cap;
-    if (occl) {
-        if ((rc = launch_fused_vote_occl(f, src_kind, mode, src, src_w, src_h, g, list_cap, oc, s))) return rc;
-    } else {
-#define AVL_FV(SRC, MODE) hipLaunchKernelGGL((k_fused_vote<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap)
-        if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FV(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FV(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FV(AVL_SRC_RGB, 1); else AVL_FV(AVL_SRC_RGB, 0); }
-        else { if (mode == 3) AVL_FV(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FV(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FV(AVL_SRC_CLASSMAP, 1); else AVL_FV(AVL_SRC_CLASSMAP, 0); }
-#undef AVL_FV
-        AVL_LAUNCH_CHECK();
+    if (path == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
+    const ListGeom lg = list_geom(n);
+    if (n_views == 1) {
+        if ((rc = launch_fused_vote(f, src, path, occl != nullptr, oc, g, lg.cap, s))) return rc;
+        return apply_frame(g, cm_host, bonus_classes, path, n, s);
     }
-    return apply_frame(g, cm_host, bonus_classes, mode, n, s);
+    if ((rc = launch_views_vote(f, vp, src, path == 4, occl != nullptr, oc, g, lg.cap, s))) return rc;
+    return apply_views(g, cm_host, bonus_classes, path == 4, lg, s);
+}
+
+// one camera: avl_fused_frame, _occl (`occl`) and _logits (`src`)
+int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
+                const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h, const uint32_t* lut_host,
+                const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    int rc;
+    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
+                         label_colors_host, cm_host, bonus_classes)))
+        return rc;
+    return run_frame(g, f, 1, P_host, src, cm_host, bonus_classes, occl, stream);
+}
+
+// several cameras: avl_fused_frame_views, _views_occl and _views_logits; one view is the single camera's frame
+int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                      const double* P_host, const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h,
+                      const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes,
+                      const avl_occlusion* occl, void* stream) {
+    if (n_views == 1)
+        return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
+                           label_colors_host, cm_host, bonus_classes, occl, stream);
+    FrameArgs f;
+    int rc;
+    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
+                         label_colors_host, cm_host, bonus_classes)))
+        return rc;
+    if ((rc = views_bits_check(g, bonus_classes))) return rc;
+    return run_frame(g, f, n_views, P_host, src, cm_host, bonus_classes, occl, stream);
 }
 
 }  // namespace
@@ -1278,15 +1659,6 @@ extern "C" int avl_fused_frame_path(const avl_grid* g, int n, uint32_t bonus_cla
     return byte_mask_ok(g, bonus_classes) ? 2 : 1;
 }
 
-extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride,
-                               int64_t comp_stride, const double* P_host, const double* T_host, double range_max,
-                               int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
-                               const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
-                               uint32_t bonus_classes, void* stream) {
-    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
-                       lut_host, label_colors_host, cm_host, bonus_classes, nullptr, stream);
-}
-
 extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views, uint32_t bonus_classes) {
     AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
     AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
@@ -1299,74 +1671,120 @@ extern "C" int avl_fused_frame_views_path(const avl_grid* g, int n, int n_views,
     return lists_fit(g, n) ? 4 : 5;
 }
 
-namespace {
-// what follows the views vote kernel: the lists' apply (path 4) or the sweep of the word mask (path 5)
-int apply_views(const avl_grid* g, const CmParams& cm, uint32_t bonus_classes, bool lists, const ListGeom& lg, hipStream_t s) {
-    const dim3 block(kBlock);
-    if (lists)
-        return lists_applied(g, launch_map_typed(g->map_dtype, [&](auto t) {
-            typedef decltype(t) T;
-            hipLaunchKernelGGL(k_views_apply_lists<T>, dim3(lg.apply_wgs), block, 0, s, static_cast<T*>(g->map), g->C, bonus_classes, cm,
-                               g->cell_mask, g->touched, g->counter, lg.cap, lg.wgs_per_list);
-        }), s);
-    const long long ncell = (long long)g->Hm * g->Wm;
-    const int vec = (reinterpret_cast<uintptr_t>(g->cell_mask) & 15) == 0;
-    return launch_map_typed(g->map_dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_views_sweep_words<T>, dim3(sweep_blocks(ncell, kViewsSweepCells)), block, 0, s, static_cast<T*>(g->map), g->C,
-                           bonus_classes, cm, g->cell_mask, ncell, vec);
-    });
+// The six fused frames: each puts its semantic source into a VoteSource and goes through fused_frame / fused_frame_views.
+extern "C" int avl_fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride,
+                               int64_t comp_stride, const double* P_host, const double* T_host, double range_max,
+                               int src_kind, const uint8_t* src, int src_w, int src_h, int img_w, int img_h,
+                               const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                               uint32_t bonus_classes, void* stream) {
+    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, bytes_source(src_kind, &src, src_w, src_h),
+                       img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, nullptr, stream);
 }
 
-// avl_fused_frame_views, and with `occl` avl_fused_frame_views_occl (as fused_frame: same path, depth pass first, culling vote twin)
-int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                      int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
-                      const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
-                      const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
-                      uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
-    int rc;
-    if ((rc = views_check(n_views, src_host))) return rc;
-    if (n_views == 1)
-        return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h,
-                           img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
-    FrameArgs f;
-    OcclParams oc;
-    if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src_host[0], src_w, src_h, img_w,
-                         img_h, lut_host, label_colors_host, cm_host, bonus_classes)))
-        return rc;
-    if ((rc = views_bits_check(g, bonus_classes))) return rc;
-    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
-    hipStream_t s = avl::as_stream(stream);
-    if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;
-    ViewsParams vp;
-    fill_views(vp, f, n_views, P_host, src_host);
-    CmParams cm;
-    if ((rc = fill_cm(cm, g, cm_host))) return rc;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool lists = lists_fit(g, n);
-    const ListGeom lg = list_geom(n);
-    if (occl) {
-        if ((rc = occl_reset(oc, n_views, true, s))) return rc;
-        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
-        if ((rc = launch_views_vote_occl(f, vp, src_kind, lists, src_w, src_h, g, lg.cap, oc, s))) return rc;
-    } else {
-#define AVL_VV(SRC, LISTS) hipLaunchKernelGGL((k_views_vote<SRC, LISTS>), grid, block, 0, s, f.pv, vp, f.gp, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, lg.cap)
-        if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VV(AVL_SRC_RGB, 1); else AVL_VV(AVL_SRC_RGB, 0); }
-        else { if (lists) AVL_VV(AVL_SRC_CLASSMAP, 1); else AVL_VV(AVL_SRC_CLASSMAP, 0); }
-#undef AVL_VV
-        AVL_LAUNCH_CHECK();
-    }
-    return apply_views(g, cm, bonus_classes, lists, lg, s);
+extern "C" int avl_fused_frame_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                    const double* P_host, const double* T_host, double range_max, int src_kind, const uint8_t* src,
+                                    int src_w, int src_h, int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host,
+                                    const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, bytes_source(src_kind, &src, src_w, src_h),
+                       img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
 }
-}  // namespace
+
+extern "C" int avl_fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                      const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl,
+                                      int img_w, int img_h, const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes,
+                                      const avl_occlusion* occl, void* stream) {
+    VoteSource src;
+    int rc;
+    if ((rc = logits_source(src, pl, 1))) return rc;
+    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host, nullptr, cm_host,
+                       bonus_classes, occl, stream);
+}
 
 extern "C" int avl_fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
                                      int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
                                      const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
                                      const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
                                      uint32_t bonus_classes, void* stream) {
-    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src_kind, src_host, src_w, src_h,
-                             img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, nullptr, stream);
+    int rc;
+    if ((rc = views_check(n_views, src_host))) return rc;
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max,
+                             bytes_source(src_kind, src_host, src_w, src_h), img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes,
+                             nullptr, stream);
+}
+
+extern "C" int avl_fused_frame_views_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                          int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                                          const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                          const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                          uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    AVL_REQUIRE(occl, "occl is NULL");
+    int rc;
+    if ((rc = views_check(n_views, src_host))) return rc;
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max,
+                             bytes_source(src_kind, src_host, src_w, src_h), img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes,
+                             occl, stream);
+}
+
+extern "C" int avl_fused_frame_views_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                            int n_views, const double* P_host, const double* T_host, double range_max,
+                                            const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
+                                            const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+    VoteSource src;
+    int rc;
+    if ((rc = logits_source(src, pl, n_views))) return rc;
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src, img_w, img_h, lut_host,
+                             nullptr, cm_host, bonus_classes, occl, stream);
+}
+
+extern "C" int64_t avl_occlusion_depth_words(int img_w, int img_h, int cell_px, int n_views) {
+    if (img_w <= 0 || img_h <= 0 || cell_px < 1 || cell_px > 64 || n_views < 1) return 0;
+    return occl_cells(img_w, img_h, cell_px) * n_views;
+}
+
+extern "C" int avl_occlusion_visibility(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                                        const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
+                                        const avl_occlusion* occl, uint8_t* state, float* key, void* stream) {
+    FrameArgs f;
+    OcclParams oc;
+    int rc;
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    AVL_REQUIRE(n == 0 || state, "state is NULL");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(key) & 3) == 0, "key is not 4-byte aligned");
+    hipStream_t s = avl::as_stream(stream);
+    if (n == 0) return occl_reset(oc, n_views, false, s);
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    if ((rc = occl_reset(oc, n_views, true, s))) return rc;
+    if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
+    hipLaunchKernelGGL(k_occl_visibility, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, oc, state, key);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+extern "C" int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                                const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
+                                const avl_point_logits* pl, uint8_t* state, float* margin, void* stream) {
+    FrameArgs f;
+    LogitsParams lp;
+    int rc;
+    if ((rc = logits_fill(lp, pl, n_views))) return rc;
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    AVL_REQUIRE(n == 0 || state, "state is NULL");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(margin) & 3) == 0, "margin is not 4-byte aligned");
+    hipStream_t s = avl::as_stream(stream);
+    if ((rc = logits_reset(lp, n_views, s))) return rc;
+    if (n == 0) return AVL_OK;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    hipLaunchKernelGGL(k_point_labels, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, lp, state, margin);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
 }
 
 extern "C" int avl_colorize_labels(const uint8_t* labels, int lw, int lh, const uint8_t* palette_host, uint8_t* out,
@@ -1623,641 +2041,3 @@ extern "C" int avl_grid_box_filter(const void* src, void* dst, int map_dtype, in
     });
 }
 
-// ================================================================ occlusion culling (avl_fused_frame_occl, avl_fused_frame_views_occl)
-// A map point behind a wall projects onto the wall's pixels and takes its label.  Before the vote, every view gets a coarse depth
-// buffer in image space; a point votes only if it is not clearly behind the nearest point of its image neighbourhood.  The rule
-// (include/avl_hip.h states it in full):
-//   candidate: a point that passes project(): 0 < v0 < range_max and 0 <= ix < img_w, 0 <= iy < img_h, on the grid or not;
-//   key q = (float)p2, p2 the third row of P . v; only a finite key > 0 is written to the buffer or compared;
-//   depth[iy / s][ix / s] = min of the keys' bit patterns (positive floats order as unsigned integers), 0xFFFFFFFF = empty;
-//   m = min of depth over the (2R + 1)^2 cells around the candidate's, clipped to the buffer;
-//   culled iff (double)q > (double)m * k + abs_tol (a multiplication and an addition, each rounded: -ffp-contract=off).
-// Integer atomicMin and, for the counts, integer atomicAdd only: the result does not depend on the order of the points.
-namespace {
-
-// what k_views_vote computes per view, with the divisor: true when the pixel lies in the image
-__device__ __forceinline__ bool project_view(const double* P, double v0, double v1, double v2, double v3, int img_w, int img_h, int& ix,
-                                             int& iy, double& p2) {
-    const double p0 = dot4(P + 0, v0, v1, v2, v3);
-    const double p1 = dot4(P + 4, v0, v1, v2, v3);
-    p2 = dot4(P + 8, v0, v1, v2, v3);
-    const double rp2 = refine_rcp(p2);
-    ix = div_i32_numpy(p0, p2, rp2);
-    iy = div_i32_numpy(p1, p2, rp2);
-    return ix >= 0 && ix < img_w && iy >= 0 && iy < img_h;
-}
-
-// the key of depth p2 as its bit pattern; false for a key that is not finite and > 0 (it is neither written nor culled)
-__device__ __forceinline__ bool depth_key(double p2, unsigned& bits) {
-    const float q = (float)p2;
-    bits = __float_as_uint(q);
-    return q > 0.0f && q < __builtin_inff();
-}
-
-__device__ __forceinline__ long long depth_cell(const OcclParams& oc, int v, int ix, int iy) {
-    return ((long long)v * oc.Hc + iy / oc.s) * oc.Wc + ix / oc.s;
-}
-
-// the cull test of a candidate of view v with a valid key: its own cell is in the neighbourhood, so m <= bits and m is a key
-__device__ __forceinline__ bool occl_culled(const OcclParams& oc, int v, int ix, int iy, unsigned bits) {
-    const int cx = ix / oc.s, cy = iy / oc.s;
-    const int x0 = max(cx - oc.R, 0), x1 = min(cx + oc.R, oc.Wc - 1), y0 = max(cy - oc.R, 0), y1 = min(cy + oc.R, oc.Hc - 1);
-    const unsigned* depth = oc.depth + (long long)v * oc.Hc * oc.Wc;
-    unsigned m = 0xffffffffu;
-    for (int y = y0; y <= y1; ++y)
-        for (int x = x0; x <= x1; ++x) m = min(m, depth[y * oc.Wc + x]);
-    return (double)__uint_as_float(bits) > (double)__uint_as_float(m) * oc.k + oc.abs_tol;
-}
-
-// culled candidates of one view: one atomic per wave that has any.  Every lane of the wave must arrive here.
-__device__ __forceinline__ void count_culled(int* counts, int v, bool culled) {
-    if (!counts) return;
-    const unsigned long long m = __ballot(culled);
-    if (m != 0ull && (threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(&counts[v], __builtin_popcountll(m));
-}
-
-// the label fetch of k_fused_vote / k_views_vote at pixel (ix, iy) -> vote bits
-template <int SRC>
-__device__ __forceinline__ unsigned fetch_vote(const GridParams& g, const LutParams& lut, const unsigned char* __restrict__ src, int src_w,
-                                               int src_h, int img_w, int img_h, int ix, int iy) {
-    if (SRC == AVL_SRC_RGB) {
-        const unsigned char* px = src + 3ll * ((long long)iy * src_w + ix);
-        return vote_from_rg(g, px[0], px[1]);
-    }
-    int sx = ix, sy = iy;                                                  // cv2 INTER_NEAREST source index, as k_fused_vote
-    if (src_w != img_w) sx = min((int)__builtin_floor((double)ix * ((double)src_w / (double)img_w)), src_w - 1);
-    if (src_h != img_h) sy = min((int)__builtin_floor((double)iy * ((double)src_h / (double)img_h)), src_h - 1);
-    return lut.lut[src[(long long)sy * src_w + sx]];
-}
-
-// Depth pass, one view or several: one read of the cloud, T and the range test once per point, one atomicMin per candidate and
-// view (no return value: nothing waits for it).  Off-grid points take part: an off-grid wall hides what is behind it.
-__global__ void __launch_bounds__(kBlock) k_occl_depth(PtsView pv, ViewsParams vp, OcclParams oc) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= pv.n) return;
-    double x, y, z, it;
-    load_point(pv, k, x, y, z, it);
-    double v0 = x, v1 = y, v2 = z, v3 = 1.0;
-    if (vp.has_T) {
-        v0 = dot4(vp.T + 0, x, y, z, 1.0);
-        v1 = dot4(vp.T + 4, x, y, z, 1.0);
-        v2 = dot4(vp.T + 8, x, y, z, 1.0);
-        v3 = dot4(vp.T + 12, x, y, z, 1.0);
-    }
-    if (!((0.0 < v0) && (v0 < vp.range_max))) return;
-    for (int v = 0; v < vp.n_views; ++v) {
-        int ix, iy;
-        double p2;
-        unsigned bits;
-        if (project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2) && depth_key(p2, bits))
-            atomicMin(&oc.depth[depth_cell(oc, v, ix, iy)], bits);
-    }
-}
-
-// k_fused_vote<SRC, MODE> with the cull test between the projection and the vote
-template <int SRC, int MODE>
-__global__ void __launch_bounds__(kBlock) k_fused_vote_occl(PtsView pv, ProjParams pp, GridParams g,
-                                                            const unsigned char* __restrict__ src, int src_w, int src_h,
-                                                            LutParams lut, unsigned* __restrict__ cell_mask,
-                                                            int* __restrict__ touched, int* __restrict__ counter, int list_cap, OcclParams oc) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    int cell = -1;
-    unsigned vote = 0;
-    bool culled = false;
-    if (k < pv.n) {
-        double x, y, z, it;
-        load_point(pv, k, x, y, z, it);
-        int ix, iy;
-        double p2;
-        if (project(pp, x, y, z, ix, iy, p2)) {
-            unsigned bits;
-            culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
-            if (!culled) cell = grid_cell(g, x, y, z);
-            if (cell >= 0) {
-                vote = fetch_vote<SRC>(g, lut, src, src_w, src_h, pp.img_w, pp.img_h, ix, iy);
-                vote = add_bonus(vote, g.bonus_classes, it);
-            }
-        }
-    }
-    count_culled(oc.culled, 0, culled);
-    if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
-    else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
-    else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
-    else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
-}
-
-// k_views_vote<SRC, LISTS> with the cull test per view.  Off-grid points are projected as well: they cast no vote, but a culled one
-// counts like any other candidate (the counts are those of k_occl_visibility's state 2).
-template <int SRC, int LISTS>
-__global__ void __launch_bounds__(kBlock) k_views_vote_occl(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LutParams lut,
-                                                            unsigned* __restrict__ cell_mask, int* __restrict__ touched,
-                                                            int* __restrict__ counter, int list_cap, OcclParams oc) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    int cell = -1;
-    unsigned word = 0;
-    bool positive = false;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0;
-    if (k < pv.n) {
-        double x, y, z;
-        load_point(pv, k, x, y, z, it);
-        v0 = x; v1 = y; v2 = z;
-        if (vp.has_T) {
-            v0 = dot4(vp.T + 0, x, y, z, 1.0);
-            v1 = dot4(vp.T + 4, x, y, z, 1.0);
-            v2 = dot4(vp.T + 8, x, y, z, 1.0);
-            v3 = dot4(vp.T + 12, x, y, z, 1.0);
-        }
-        positive = (0.0 < v0) && (v0 < vp.range_max);
-        if (positive) cell = grid_cell(g, x, y, z);
-    }
-    for (int v = 0; v < vp.n_views; ++v) {                                 // the same trip count in every lane: count_culled ballots
-        bool culled = false;
-        int ix, iy;
-        double p2;
-        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
-            unsigned bits;
-            culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
-            if (!culled && cell >= 0) {
-                unsigned vote = fetch_vote<SRC>(g, lut, vp.src[v], src_w, src_h, vp.img_w, vp.img_h, ix, iy);
-                vote = add_bonus(vote, g.bonus_classes, it);
-                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
-            }
-        }
-        count_culled(oc.culled, v, culled);
-    }
-    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
-    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);
-}
-
-// One state per point and view: 0 not a candidate, 1 visible, 2 culled; key (optional): the candidate's float32 depth, 0 for the rest.
-// Reads the depth buffer k_occl_depth filled.
-__global__ void __launch_bounds__(kBlock) k_occl_visibility(PtsView pv, ViewsParams vp, OcclParams oc, unsigned char* __restrict__ state,
-                                                            float* __restrict__ key) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    const bool live = k < pv.n;
-    bool positive = false;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
-    if (live) {
-        double x, y, z, it;
-        load_point(pv, k, x, y, z, it);
-        v0 = x; v1 = y; v2 = z;
-        if (vp.has_T) {
-            v0 = dot4(vp.T + 0, x, y, z, 1.0);
-            v1 = dot4(vp.T + 4, x, y, z, 1.0);
-            v2 = dot4(vp.T + 8, x, y, z, 1.0);
-            v3 = dot4(vp.T + 12, x, y, z, 1.0);
-        }
-        positive = (0.0 < v0) && (v0 < vp.range_max);
-    }
-    for (int v = 0; v < vp.n_views; ++v) {
-        unsigned char st = 0;
-        unsigned bits = 0u;
-        int ix, iy;
-        double p2;
-        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2))
-            st = (depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits)) ? 2 : 1;
-        if (live) {
-            state[(long long)v * pv.n + k] = st;
-            if (key) key[(long long)v * pv.n + k] = st ? __uint_as_float(bits) : 0.0f;
-        }
-        count_culled(oc.culled, v, st == 2);
-    }
-}
-
-long long occl_cells(int img_w, int img_h, int s) { return (long long)((img_w + s - 1) / s) * ((img_h + s - 1) / s); }
-
-int occl_fill(OcclParams& oc, const avl_occlusion* occl, int img_w, int img_h, int n_views) {
-    AVL_REQUIRE(occl, "occl is NULL");
-    AVL_REQUIRE(occl->cell_px >= 1 && occl->cell_px <= 64, "occlusion cell_px = %d (1..64)", occl->cell_px);
-    AVL_REQUIRE(occl->radius >= 0 && occl->radius <= 2, "occlusion radius = %d (0..2)", occl->radius);
-    AVL_REQUIRE(occl->rel_tol >= 0.0, "occlusion rel_tol = %g (must be >= 0)", occl->rel_tol);     // a NaN fails the comparison too
-    AVL_REQUIRE(occl->abs_tol >= 0.0, "occlusion abs_tol = %g (must be >= 0)", occl->abs_tol);
-    AVL_REQUIRE(img_w > 0 && img_h > 0 && n_views >= 1 && n_views <= kMaxViews, "occlusion: %d views of %dx%d", n_views, img_w, img_h);
-    const long long words = occl_cells(img_w, img_h, occl->cell_px) * n_views;
-    AVL_REQUIRE(occl->depth, "occlusion depth scratch is NULL");
-    AVL_REQUIRE(occl->depth_words >= words, "occlusion depth scratch holds %lld words, %lld needed", (long long)occl->depth_words, words);
-    AVL_REQUIRE(words * 4 <= 0x7fffffffLL, "occlusion depth buffer of %lld words is too large", words);
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->depth) & 3) == 0, "occlusion depth scratch is not 4-byte aligned");
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(occl->culled) & 3) == 0, "occlusion culled counts are not 4-byte aligned");
-    oc.depth = occl->depth;
-    oc.culled = occl->culled;
-    oc.k = 1.0 + occl->rel_tol;
-    oc.abs_tol = occl->abs_tol;
-    oc.s = occl->cell_px;
-    oc.R = occl->radius;
-    oc.Wc = (img_w + oc.s - 1) / oc.s;
-    oc.Hc = (img_h + oc.s - 1) / oc.s;
-    return AVL_OK;
-}
-
-int occl_reset(const OcclParams& oc, int n_views, bool depth, hipStream_t s) {
-    if (depth) AVL_HIP_CHECK(hipMemsetAsync(oc.depth, 0xff, sizeof(unsigned) * (size_t)n_views * oc.Hc * oc.Wc, s));
-    if (oc.culled) AVL_HIP_CHECK(hipMemsetAsync(oc.culled, 0, sizeof(int) * n_views, s));
-    return AVL_OK;
-}
-
-int launch_occl_depth(const PtsView& pv, const ViewsParams& vp, const OcclParams& oc, hipStream_t s) {
-    hipLaunchKernelGGL(k_occl_depth, dim3((pv.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pv, vp, oc);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
-}
-
-int launch_fused_vote_occl(const FrameArgs& f, int src_kind, int mode, const uint8_t* src, int src_w, int src_h, const avl_grid* g, int list_cap,
-                           const OcclParams& oc, hipStream_t s) {
-    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
-#define AVL_FVO(SRC, MODE) hipLaunchKernelGGL((k_fused_vote_occl<SRC, MODE>), grid, block, 0, s, f.pv, f.pp, f.gp, src, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
-    if (src_kind == AVL_SRC_RGB) { if (mode == 3) AVL_FVO(AVL_SRC_RGB, 3); else if (mode == 2) AVL_FVO(AVL_SRC_RGB, 2); else if (mode == 1) AVL_FVO(AVL_SRC_RGB, 1); else AVL_FVO(AVL_SRC_RGB, 0); }
-    else { if (mode == 3) AVL_FVO(AVL_SRC_CLASSMAP, 3); else if (mode == 2) AVL_FVO(AVL_SRC_CLASSMAP, 2); else if (mode == 1) AVL_FVO(AVL_SRC_CLASSMAP, 1); else AVL_FVO(AVL_SRC_CLASSMAP, 0); }
-#undef AVL_FVO
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
-}
-
-int launch_views_vote_occl(const FrameArgs& f, const ViewsParams& vp, int src_kind, bool lists, int src_w, int src_h, const avl_grid* g,
-                           int list_cap, const OcclParams& oc, hipStream_t s) {
-    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
-#define AVL_VVO(SRC, LISTS) hipLaunchKernelGGL((k_views_vote_occl<SRC, LISTS>), grid, block, 0, s, f.pv, vp, f.gp, src_w, src_h, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
-    if (src_kind == AVL_SRC_RGB) { if (lists) AVL_VVO(AVL_SRC_RGB, 1); else AVL_VVO(AVL_SRC_RGB, 0); }
-    else { if (lists) AVL_VVO(AVL_SRC_CLASSMAP, 1); else AVL_VVO(AVL_SRC_CLASSMAP, 0); }
-#undef AVL_VVO
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t avl_occlusion_depth_words(int img_w, int img_h, int cell_px, int n_views) {
-    if (img_w <= 0 || img_h <= 0 || cell_px < 1 || cell_px > 64 || n_views < 1) return 0;
-    return occl_cells(img_w, img_h, cell_px) * n_views;
-}
-
-extern "C" int avl_fused_frame_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                                    const double* P_host, const double* T_host, double range_max, int src_kind, const uint8_t* src,
-                                    int src_w, int src_h, int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host,
-                                    const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
-    AVL_REQUIRE(occl, "occl is NULL");
-    return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src_kind, src, src_w, src_h, img_w, img_h,
-                       lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
-}
-
-extern "C" int avl_fused_frame_views_occl(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                                          int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
-                                          const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
-                                          const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
-                                          uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
-    AVL_REQUIRE(occl, "occl is NULL");
-    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src_kind, src_host, src_w, src_h,
-                             img_w, img_h, lut_host, label_colors_host, cm_host, bonus_classes, occl, stream);
-}
-
-extern "C" int avl_occlusion_visibility(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
-                                        const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
-                                        const avl_occlusion* occl, uint8_t* state, float* key, void* stream) {
-    FrameArgs f;
-    OcclParams oc;
-    int rc;
-    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
-    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
-    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
-    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
-    if ((rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
-    AVL_REQUIRE(n == 0 || state, "state is NULL");
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(key) & 3) == 0, "key is not 4-byte aligned");
-    hipStream_t s = avl::as_stream(stream);
-    if (n == 0) return occl_reset(oc, n_views, false, s);
-    ViewsParams vp;
-    fill_views(vp, f, n_views, P_host, nullptr);
-    if ((rc = occl_reset(oc, n_views, true, s))) return rc;
-    if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
-    hipLaunchKernelGGL(k_occl_visibility, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, oc, state, key);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
-}
-
-// ================================================================ points labelled from interpolated logits (avl_fused_frame_logits and its kin)
-// The class-map source hands a point the arg-max of the nearest low-resolution pixel.  These kernels read the plan's fp32 logits
-// instead and evaluate the reference model's full-resolution prediction (bilinear, align_corners=True, then arg-max:
-// deeplab_v3_plus.py:67-69) at the point's pixel alone, with the top-1 minus top-2 margin as a confidence: a point whose margin is
-// below min_margin abstains.  The rule is stated in full at struct avl_point_logits in include/avl_hip.h; the interpolation is that of
-// seg_head.hip (src_coord, corner, lerp4) with every float32 operation rounded on its own, which -ffp-contract=off gives here.
-// What a lane fetches: the K logits of four source pixels, each a run of K consecutive floats (76 bytes at K = 19, ld = K: 4-byte
-// aligned only, so no lane can count on a 16-byte boundary).  The loop takes four classes of each corner at a time -- sixteen
-// independent loads in flight before the first is used, which the compiler merges into dwordx4 / dwordx2 loads of 4-byte alignment
-// (gfx950 allows them on global memory) -- and keeps only the running best, second best and index.
-namespace {
-
-struct LogitsParams {
-    const float* logits[kMaxViews];
-    int* abstained;                   // [n_views] abstentions, or NULL
-    long long ld;
-    int h, w, K, net_h, net_w;
-    float sy, sx, min_margin;
-};
-
-// One more class for the running arg-max: the first maximal index wins and a NaN counts as maximal (AVL_OP_ARGMAX, eval_pixel of
-// seg_head.hip); `second` follows as the largest of the others.  best = second = -inf, top = 0 to start with.
-__device__ __forceinline__ void take_logit(float v, int k, float& best, float& second, int& top) {
-    if (v > best || (v != v && best == best)) { second = best; best = v; top = k; }
-    else if (v > second) second = v;
-}
-
-// rules 2 - 5 at pixel (ix, iy) of the img_w x img_h projection image: -> top, and the margin
-__device__ __forceinline__ int point_label(const LogitsParams& lp, const float* __restrict__ src, int img_w, int img_h, int ix, int iy,
-                                           float& margin) {
-    int nx = ix, ny = iy;                                                  // the index rule of fetch_vote, towards the network's input
-    if (lp.net_w != img_w) nx = min((int)__builtin_floor((double)ix * ((double)lp.net_w / (double)img_w)), lp.net_w - 1);
-    if (lp.net_h != img_h) ny = min((int)__builtin_floor((double)iy * ((double)lp.net_h / (double)img_h)), lp.net_h - 1);
-    const float fy = lp.sy * (float)ny, fx = lp.sx * (float)nx;
-    const int y0 = min((int)fy, lp.h - 1), x0 = min((int)fx, lp.w - 1);
-    const int y1 = y0 + (y0 < lp.h - 1 ? 1 : 0), x1 = x0 + (x0 < lp.w - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    const float* __restrict__ a = src + ((long long)y0 * lp.w + x0) * lp.ld;
-    const float* __restrict__ b = src + ((long long)y0 * lp.w + x1) * lp.ld;
-    const float* __restrict__ c = src + ((long long)y1 * lp.w + x0) * lp.ld;
-    const float* __restrict__ d = src + ((long long)y1 * lp.w + x1) * lp.ld;
-    float best = -__builtin_inff(), second = -__builtin_inff();
-    int top = 0, k = 0;
-    for (; k + 4 <= lp.K; k += 4) {
-        float va[4], vb[4], vc[4], vd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { va[j] = a[k + j]; vb[j] = b[k + j]; vc[j] = c[k + j]; vd[j] = d[k + j]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) take_logit(hy * (hx * va[j] + lx * vb[j]) + ly * (hx * vc[j] + lx * vd[j]), k + j, best, second, top);
-    }
-    for (; k < lp.K; ++k) take_logit(hy * (hx * a[k] + lx * b[k]) + ly * (hx * c[k] + lx * d[k]), k, best, second, top);
-    margin = lp.K == 1 ? __builtin_inff() : best - second;
-    return top;
-}
-
-// k_fused_vote<AVL_SRC_CLASSMAP, MODE> with the label and its gate computed from the logits; OCCL: the cull test of k_fused_vote_occl
-// between the projection and the fetch (a culled candidate is not evaluated and does not count as an abstention)
-template <int MODE, int OCCL>
-__global__ void __launch_bounds__(kBlock) k_fused_vote_logits(PtsView pv, ProjParams pp, GridParams g, LogitsParams lp, LutParams lut,
-                                                              unsigned* __restrict__ cell_mask, int* __restrict__ touched,
-                                                              int* __restrict__ counter, int list_cap, OcclParams oc) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    int cell = -1;
-    unsigned vote = 0;
-    bool culled = false, abstains = false;
-    if (k < pv.n) {
-        double x, y, z, it;
-        load_point(pv, k, x, y, z, it);
-        int ix, iy;
-        double p2;
-        if (project(pp, x, y, z, ix, iy, p2)) {
-            if (OCCL) {
-                unsigned bits;
-                culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
-            }
-            if (!culled) cell = grid_cell(g, x, y, z);
-            if (cell >= 0) {
-                float margin;
-                const int top = point_label(lp, lp.logits[0], pp.img_w, pp.img_h, ix, iy, margin);
-                abstains = margin < lp.min_margin;
-                if (!abstains) vote = add_bonus(lut.lut[top], g.bonus_classes, it);
-            }
-        }
-    }
-    if (OCCL) count_culled(oc.culled, 0, culled);
-    count_culled(lp.abstained, 0, abstains);
-    if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
-    else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
-    else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
-    else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
-}
-
-// k_views_vote<AVL_SRC_CLASSMAP, LISTS> with one logits image per view.  Without OCCL an off-grid point is not projected (as in
-// k_views_vote); with it, it is, because a culled off-grid candidate counts (k_views_vote_occl).  Every lane runs the loop over the
-// views: the counts ballot.
-template <int LISTS, int OCCL>
-__global__ void __launch_bounds__(kBlock) k_views_vote_logits(PtsView pv, ViewsParams vp, GridParams g, LogitsParams lp, LutParams lut,
-                                                              unsigned* __restrict__ cell_mask, int* __restrict__ touched,
-                                                              int* __restrict__ counter, int list_cap, OcclParams oc) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    int cell = -1;
-    unsigned word = 0;
-    bool positive = false;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0;
-    if (k < pv.n) {
-        double x, y, z;
-        load_point(pv, k, x, y, z, it);
-        v0 = x; v1 = y; v2 = z;
-        if (vp.has_T) {
-            v0 = dot4(vp.T + 0, x, y, z, 1.0);
-            v1 = dot4(vp.T + 4, x, y, z, 1.0);
-            v2 = dot4(vp.T + 8, x, y, z, 1.0);
-            v3 = dot4(vp.T + 12, x, y, z, 1.0);
-        }
-        positive = (0.0 < v0) && (v0 < vp.range_max);
-        if (positive) cell = grid_cell(g, x, y, z);
-    }
-    for (int v = 0; v < vp.n_views; ++v) {
-        bool culled = false, abstains = false;
-        int ix, iy;
-        double p2;
-        if (positive && (OCCL || cell >= 0) && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
-            if (OCCL) {
-                unsigned bits;
-                culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
-            }
-            if (!culled && cell >= 0) {
-                float margin;
-                const int top = point_label(lp, lp.logits[v], vp.img_w, vp.img_h, ix, iy, margin);
-                abstains = margin < lp.min_margin;
-                if (!abstains) {
-                    const unsigned vote = add_bonus(lut.lut[top], g.bonus_classes, it);
-                    word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
-                }
-            }
-        }
-        if (OCCL) count_culled(oc.culled, v, culled);
-        count_culled(lp.abstained, v, abstains);
-    }
-    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
-    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);
-}
-
-// The rule alone, per point and view, on the grid or not: state = top, 254 = abstained, 255 = no candidate of the view; margin
-// (optional) = the candidate's margin, 0 for the rest.
-__global__ void __launch_bounds__(kBlock) k_point_labels(PtsView pv, ViewsParams vp, LogitsParams lp, unsigned char* __restrict__ state,
-                                                         float* __restrict__ margin) {
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    const bool live = k < pv.n;
-    bool positive = false;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
-    if (live) {
-        double x, y, z, it;
-        load_point(pv, k, x, y, z, it);
-        v0 = x; v1 = y; v2 = z;
-        if (vp.has_T) {
-            v0 = dot4(vp.T + 0, x, y, z, 1.0);
-            v1 = dot4(vp.T + 4, x, y, z, 1.0);
-            v2 = dot4(vp.T + 8, x, y, z, 1.0);
-            v3 = dot4(vp.T + 12, x, y, z, 1.0);
-        }
-        positive = (0.0 < v0) && (v0 < vp.range_max);
-    }
-    for (int v = 0; v < vp.n_views; ++v) {
-        unsigned char st = 255;
-        float m = 0.f;
-        int ix, iy;
-        double p2;
-        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
-            const int top = point_label(lp, lp.logits[v], vp.img_w, vp.img_h, ix, iy, m);
-            st = m < lp.min_margin ? 254 : (unsigned char)top;
-        }
-        if (live) {
-            state[(long long)v * pv.n + k] = st;
-            if (margin) margin[(long long)v * pv.n + k] = m;
-        }
-        count_culled(lp.abstained, v, st == 254);
-    }
-}
-
-// validates an avl_point_logits for n_views views (host only) and puts it into kernel-argument form
-int logits_fill(LogitsParams& lp, const avl_point_logits* pl, int n_views) {
-    AVL_REQUIRE(pl, "avl_point_logits is NULL");
-    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
-    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
-    AVL_REQUIRE(pl->h > 0 && pl->w > 0, "logits of %dx%d pixels", pl->w, pl->h);
-    AVL_REQUIRE(pl->K >= 1 && pl->K <= 254, "logits K = %d (1..254)", pl->K);
-    AVL_REQUIRE(pl->ld >= pl->K, "logits ld = %lld < K = %d", (long long)pl->ld, pl->K);
-    AVL_REQUIRE(pl->ld <= (1ll << 61) / pl->h / pl->w, "logits of %dx%d pixels x ld %lld are too large", pl->w, pl->h, (long long)pl->ld);
-    AVL_REQUIRE(pl->net_h > 0 && pl->net_w > 0, "logits net size %dx%d", pl->net_w, pl->net_h);
-    AVL_REQUIRE(pl->min_margin >= 0.f, "logits min_margin = %g (must be >= 0)", (double)pl->min_margin);      // a NaN fails the comparison too
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->abstained) & 3) == 0, "logits abstained counts are not 4-byte aligned");
-    memset(&lp, 0, sizeof(lp));
-    for (int v = 0; v < n_views; ++v) {
-        AVL_REQUIRE(pl->logits[v], "view %d: logits are NULL", v);
-        AVL_REQUIRE((reinterpret_cast<uintptr_t>(pl->logits[v]) & 3) == 0, "view %d: logits are not 4-byte aligned", v);
-        lp.logits[v] = pl->logits[v];
-    }
-    lp.abstained = pl->abstained;
-    lp.ld = pl->ld;
-    lp.h = pl->h; lp.w = pl->w; lp.K = pl->K; lp.net_h = pl->net_h; lp.net_w = pl->net_w;
-    lp.sy = pl->net_h > 1 ? (float)(pl->h - 1) / (float)(pl->net_h - 1) : 0.f;          // as avl_seg_eval_full_res (seg_head.hip)
-    lp.sx = pl->net_w > 1 ? (float)(pl->w - 1) / (float)(pl->net_w - 1) : 0.f;
-    lp.min_margin = pl->min_margin;
-    return AVL_OK;
-}
-
-int logits_reset(const LogitsParams& lp, int n_views, hipStream_t s) {
-    if (lp.abstained) AVL_HIP_CHECK(hipMemsetAsync(lp.abstained, 0, sizeof(int) * n_views, s));
-    return AVL_OK;
-}
-
-// fill_frame for a logits source: the logits stand where the class map stands (its checks ask for a source and its size only)
-int fill_frame_logits(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                      const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl, int img_w, int img_h,
-                      const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes) {
-    return fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, AVL_SRC_CLASSMAP,
-                      reinterpret_cast<const uint8_t*>(pl->logits[0]), pl->w, pl->h, img_w, img_h, lut_host, nullptr, cm_host, bonus_classes);
-}
-
-// fused_frame with the logits as the source: the same path from n, the same depth pass and apply
-int fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
-                       const double* T_host, double range_max, const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
-                       const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
-    FrameArgs f;
-    LogitsParams lp;
-    OcclParams oc;
-    int rc;
-    if ((rc = logits_fill(lp, pl, 1))) return rc;
-    if ((rc = fill_frame_logits(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
-                                bonus_classes)))
-        return rc;
-    memset(&oc, 0, sizeof(oc));
-    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, 1))) return rc;
-    hipStream_t s = avl::as_stream(stream);
-    if ((rc = logits_reset(lp, 1, s))) return rc;
-    if (n == 0) return occl ? occl_reset(oc, 1, false, s) : AVL_OK;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const int mode = avl_fused_frame_path(g, n, bonus_classes);
-    if (mode < 0) return mode;
-    if (occl) {
-        ViewsParams vp;
-        fill_views(vp, f, 1, P_host, nullptr);
-        if ((rc = occl_reset(oc, 1, true, s))) return rc;
-        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
-    }
-    if (mode == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
-    const int list_cap = list_geom(n).cap;
-#define AVL_FVL(MODE, OCCL) hipLaunchKernelGGL((k_fused_vote_logits<MODE, OCCL>), grid, block, 0, s, f.pv, f.pp, f.gp, lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc)
-    if (occl) { if (mode == 3) AVL_FVL(3, 1); else if (mode == 2) AVL_FVL(2, 1); else if (mode == 1) AVL_FVL(1, 1); else AVL_FVL(0, 1); }
-    else { if (mode == 3) AVL_FVL(3, 0); else if (mode == 2) AVL_FVL(2, 0); else if (mode == 1) AVL_FVL(1, 0); else AVL_FVL(0, 0); }
-#undef AVL_FVL
-    AVL_LAUNCH_CHECK();
-    return apply_frame(g, cm_host, bonus_classes, mode, n, s);
-}
-
-}  // namespace
-
-extern "C" int avl_fused_frame_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                                      const double* P_host, const double* T_host, double range_max, const avl_point_logits* pl,
-                                      int img_w, int img_h, const uint32_t* lut_host, const double* cm_host, uint32_t bonus_classes,
-                                      const avl_occlusion* occl, void* stream) {
-    return fused_frame_logits(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
-                              bonus_classes, occl, stream);
-}
-
-extern "C" int avl_fused_frame_views_logits(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-                                            int n_views, const double* P_host, const double* T_host, double range_max,
-                                            const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
-                                            const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
-    FrameArgs f;
-    LogitsParams lp;
-    OcclParams oc;
-    int rc;
-    if ((rc = logits_fill(lp, pl, n_views))) return rc;
-    if (n_views == 1)
-        return fused_frame_logits(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
-                                  bonus_classes, occl, stream);
-    if ((rc = fill_frame_logits(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, pl, img_w, img_h, lut_host, cm_host,
-                                bonus_classes)))
-        return rc;
-    if ((rc = views_bits_check(g, bonus_classes))) return rc;
-    memset(&oc, 0, sizeof(oc));
-    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
-    hipStream_t s = avl::as_stream(stream);
-    if ((rc = logits_reset(lp, n_views, s))) return rc;
-    if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;
-    ViewsParams vp;
-    fill_views(vp, f, n_views, P_host, nullptr);
-    CmParams cm;
-    if ((rc = fill_cm(cm, g, cm_host))) return rc;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool lists = lists_fit(g, n);
-    const ListGeom lg = list_geom(n);
-    if (occl) {
-        if ((rc = occl_reset(oc, n_views, true, s))) return rc;
-        if ((rc = launch_occl_depth(f.pv, vp, oc, s))) return rc;
-    }
-#define AVL_VVL(LISTS, OCCL) hipLaunchKernelGGL((k_views_vote_logits<LISTS, OCCL>), grid, block, 0, s, f.pv, vp, f.gp, lp, f.lut, g->cell_mask, g->touched, g->counter, lg.cap, oc)
-    if (occl) { if (lists) AVL_VVL(1, 1); else AVL_VVL(0, 1); }
-    else { if (lists) AVL_VVL(1, 0); else AVL_VVL(0, 0); }
-#undef AVL_VVL
-    AVL_LAUNCH_CHECK();
-    return apply_views(g, cm, bonus_classes, lists, lg, s);
-}
-
-extern "C" int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
-                                const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
-                                const avl_point_logits* pl, uint8_t* state, float* margin, void* stream) {
-    FrameArgs f;
-    LogitsParams lp;
-    int rc;
-    if ((rc = logits_fill(lp, pl, n_views))) return rc;
-    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
-    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
-    AVL_REQUIRE(n == 0 || state, "state is NULL");
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(margin) & 3) == 0, "margin is not 4-byte aligned");
-    hipStream_t s = avl::as_stream(stream);
-    if ((rc = logits_reset(lp, n_views, s))) return rc;
-    if (n == 0) return AVL_OK;
-    ViewsParams vp;
-    fill_views(vp, f, n_views, P_host, nullptr);
-    hipLaunchKernelGGL(k_point_labels, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, lp, state, margin);
-    AVL_LAUNCH_CHECK();
-    return AVL_OK;
-}

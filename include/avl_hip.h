@@ -292,6 +292,73 @@ int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, in
                      const double* P_host /* [n_views][12] */, const double* T_host, double range_max, int img_w, int img_h,
                      const avl_point_logits* pl, uint8_t* state, float* margin, void* stream);
 
+/* ---- a9g: dense ground fill -- cells on the ground plane take the cameras' labels (not in the reference) ---------- */
+
+/* Everything above writes where a LiDAR point fell; beyond 15 - 20 m the rings of a spinning LiDAR lie metres apart and most road
+ * cells get no vote in a frame.  The calls below go the other way: every cell of a window of the grid puts its centre on the ground
+ * plane, projects it into each camera and takes that pixel's label as one Bayesian update -- one thread per cell, which owns the
+ * cell's row of the map: no vote mask, no atomics on the map, no apply pass.  (The reference's own answer for "no depth",
+ * update_map_planar, is avl_planar_update: a local map with four fixed anchors and a class test that is never true.)
+ * Of the grid only map, map_dtype, Hm, Wm, C, off_*, b00, b10 and resolution are read; cell_mask, touched and counter are never
+ * touched and may be NULL.  THE RULE, for every cell (i, j) of the window [x0, x0 + h) x [y0, y0 + w) clipped to the grid; every
+ * float64 operation is rounded on its own (no fused multiply-add except where avl_fused_frame has one):
+ *   1. point: x = (b00 + ((double)i + 0.5) * resolution) - off_x, y alike with j, b10, off_y: the cell's centre in the grid's frame,
+ *      the frame of the clouds mapped onto the grid.  With the plane (a, b, c, d) in that same frame: t = a * x; t = t + b * y;
+ *      t = t + d; z = (-t) / c, an IEEE division.
+ *   2. candidate and pixel, per view: exactly avl_fused_frame's for the point (x, y, z): v = T_host . (x, y, z, 1) (the point itself
+ *      when T_host is NULL), the test 0 < v0 < range_max with the fill's own range_max, then the pixel through that view's P with
+ *      the truncation rules of avl_fused_frame and the test 0 <= ix < img_w, 0 <= iy < img_h.  A NaN anywhere makes the cell no
+ *      candidate.
+ *   3. occlusion, only when occl != NULL: the key q = (float)p2 is valid as in rule 2 of avl_occlusion, and the cell is culled in
+ *      that view iff (double)q > (double)m * k + abs_tol, m the minimum of the depth buffer over the candidate's neighbourhood
+ *      (rules 4 - 5 of avl_occlusion).  The buffer holds real points only: avl_occlusion_depth fills it from a cloud and the fill
+ *      reads it; fill cells never write to it.  A neighbourhood without a real point (m = 0xFFFFFFFF, a NaN as a float) culls
+ *      nothing: a comparison with a NaN is false.
+ *   4. vote: bits = (the vote bits avl_fused_frame takes from that pixel of the view's source) & class_mask, bit i of class_mask
+ *      set meaning that map class i may be filled.  A cell has no intensity, so there is never a lane bonus.  With logits a
+ *      candidate whose margin is below min_margin abstains (rules 2 - 6 of avl_point_logits, unchanged).
+ *   5. apply, in place, by the cell's own thread: view 0 first; inside a view class i ascending, and for every set bit i
+ *      row[c] = (MapT)((double)row[c] + cm_host[c * C + i]) for all c: the sequence avl_fused_frame_views applies to a cell.  Any
+ *      C <= AVL_MAX_MAP_CLASSES goes with any n_views <= AVL_MAX_VIEWS (a cell's votes are not packed into a mask word).
+ *   6. counts, all optional, each reset by the call itself, one integer atomic per wave that has any: filled[v] = the cells with
+ *      non-zero bits in view v; pl->abstained[v] = view v's candidates that are not culled and abstain; occl->culled[v] = view v's
+ *      culled candidates.
+ * The grid after a call equals, bit for bit and for AVL_F32 and AVL_F64 maps, what avl_fused_frame_views does with the VIRTUAL
+ * CLOUD of the window's points of rule 1 (intensity 0, bonus_classes 0, the same range_max, a full class_mask, no occlusion),
+ * provided every such point falls into its own cell by :404-411 -- it does on the grids tried (tests/test_ground_fill_cpu.py).  The
+ * result does not depend on scheduling.  A cell that a LiDAR point also hit in the same frame gets both updates; a caller who
+ * wants the fill to weigh less scales cm_host. */
+typedef struct avl_ground_fill {
+    int32_t x0, y0, h, w;    /* the window in cells: [x0, x0 + h) along Hm, [y0, y0 + w) along Wm; may hang over the grid's edges */
+    double plane[4];         /* a, b, c, d of a x + b y + c z + d = 0 in the grid's frame; finite, c != 0                         */
+    double range_max;        /* > 0: the fill's own range along the velodyne x axis                                              */
+    uint32_t class_mask;     /* bit i set: map class i may be filled                                                             */
+    int32_t* filled;         /* int32[n_views] or NULL: receives, per view, the cells that took a vote                           */
+} avl_ground_fill;
+
+/* The fill from byte sources (src_kind, src_host, src_w, src_h, lut_host, label_colors_host as avl_fused_frame_views takes them)
+ * and from logits (pl, lut_host as avl_fused_frame_views_logits takes them).  T_host: grid frame -> velodyne, NULL when the grid is
+ * in the velodyne frame -- exactly avl_fused_frame's T_host.  occl: NULL, or an avl_occlusion whose depth buffer
+ * avl_occlusion_depth has filled for the same n_views, P_host, img_w and img_h.  One kernel launch; a window wholly off the grid (or
+ * an empty one) succeeds, resets the counts and launches nothing.  AVL_E_ARG, before any GPU work, for a NULL g, gf or map, a bad
+ * grid geometry, n_views outside 1..AVL_MAX_VIEWS, a negative h or w or more than 2^31 - 1 cells, a plane that is not finite or
+ * has c == 0, a NaN or non-positive range_max, a misaligned filled, and what the frame calls refuse of P_host, the image size, the
+ * sources, cm_host, pl and occl. */
+int avl_ground_fill_views(const avl_grid* g, const avl_ground_fill* gf, int n_views, const double* P_host /* [n_views][12] */,
+                          const double* T_host, int src_kind, const uint8_t* const* src_host /* n_views device pointers */,
+                          int src_w, int src_h, int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host,
+                          const double* cm_host, const avl_occlusion* occl, void* stream);
+int avl_ground_fill_views_logits(const avl_grid* g, const avl_ground_fill* gf, int n_views, const double* P_host /* [n_views][12] */,
+                                 const double* T_host, const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
+                                 const double* cm_host, const avl_occlusion* occl, void* stream);
+
+/* Rules 1 - 3 of avl_occlusion alone (points addressed as in avl_project_points): resets occl->depth and occl->culled, then fills
+ * the buffer from the cloud.  After it occl->depth holds, per view, [Hc][Wc] words: the bit pattern of the nearest candidate's key,
+ * 0xFFFFFFFF for an empty cell.  An empty cloud leaves every cell empty.  AVL_E_ARG as avl_occlusion_visibility. */
+int avl_occlusion_depth(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                        const double* P_host /* [n_views][12] */, const double* T_host, double range_max, int img_w, int img_h,
+                        const avl_occlusion* occl, void* stream);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

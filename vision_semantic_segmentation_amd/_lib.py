@@ -55,6 +55,14 @@ class AvlPointLogits(C.Structure):
     ]
 
 
+class AvlGroundFill(C.Structure):
+    """struct avl_ground_fill of include/avl_hip.h"""
+    _fields_ = [
+        ("x0", C.c_int32), ("y0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("plane", C.c_double * 4),
+        ("range_max", C.c_double), ("class_mask", C.c_uint32), ("filled", C.c_void_p),
+    ]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
 _SIGNATURES = {
@@ -83,6 +91,11 @@ _SIGNATURES = {
     "avl_fused_frame_views_logits": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, C.POINTER(AvlPointLogits), _i, _i,
                                           _vp, _vp, C.c_uint32, C.POINTER(AvlOcclusion), _vp]),
     "avl_point_labels": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlPointLogits), _vp, _vp, _vp]),
+    "avl_ground_fill_views": (_i, [C.POINTER(AvlGrid), C.POINTER(AvlGroundFill), _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
+                                   C.POINTER(AvlOcclusion), _vp]),
+    "avl_ground_fill_views_logits": (_i, [C.POINTER(AvlGrid), C.POINTER(AvlGroundFill), _i, _vp, _vp, C.POINTER(AvlPointLogits), _i, _i,
+                                          _vp, _vp, C.POINTER(AvlOcclusion), _vp]),
+    "avl_occlusion_depth": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlOcclusion), _vp]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -189,6 +189,20 @@ def get_cfg_defaults():
     # anything else).  The other sources ignore it
     C.MAPPING.CONFIDENCE = CfgNode()
     C.MAPPING.CONFIDENCE.MIN_MARGIN = 0.0
+    # build-specific: dense ground fill.  After the LiDAR frame, every cell of a SIZE_M window around the vehicle puts its centre on the
+    # ground plane (SemanticMapping.set_ground_plane / plane_callback), projects it into each camera and takes that pixel's label as one
+    # update (the rule: include/avl_hip.h, avl_ground_fill), with OCCLUSION.ENABLED only where no LiDAR point hides the ground.  Off by
+    # default: nothing of it runs.  RANGE_MAX is the fill's own range along the vehicle's x axis (a camera's label of the ground is
+    # worth little at the cloud's 100 m); CLASSES names the map classes a cell may take (LABELS_NAMES; vegetation is no ground);
+    # WEIGHT scales the confusion matrix of the fill's updates; a plane whose normal in the grid's frame is more than MAX_TILT_DEG
+    # from the z axis is refused.  The planar mode ignores the option
+    C.MAPPING.GROUND_FILL = CfgNode()
+    C.MAPPING.GROUND_FILL.ENABLED = False
+    C.MAPPING.GROUND_FILL.SIZE_M = [60.0, 60.0]           # window in metres along the grid's x, y, centred on the vehicle's cell
+    C.MAPPING.GROUND_FILL.RANGE_MAX = 30.0
+    C.MAPPING.GROUND_FILL.CLASSES = ["road", "crosswalk", "lane", "sidewalk"]
+    C.MAPPING.GROUND_FILL.WEIGHT = 1.0
+    C.MAPPING.GROUND_FILL.MAX_TILT_DEG = 30.0
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

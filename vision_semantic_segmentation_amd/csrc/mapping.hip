@@ -14,7 +14,9 @@
 #include "avl_common.h"
 #include "avl_render.h"
 
+#include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1040,6 +1042,92 @@ __global__ void __launch_bounds__(kBlock) k_views_sweep_words(MapT* __restrict__
     }
 }
 
+// ================================================================ dense ground fill (avl_ground_fill_views and its kin)
+// The inverse direction of the vote kernels: one lane per CELL of a window of the grid.  The lane puts the cell's centre on the
+// ground plane, takes it to the cameras as a point of the cloud would go (to_camera, project_view), tests it against the depth
+// buffer of real points (OCCL), fetches each view's label (pixel_vote) and updates its own row of the map.  A cell belongs to one
+// lane, so there is no vote mask, no atomic on the map and no apply pass.  The rule is stated in full at struct avl_ground_fill in
+// include/avl_hip.h.  What bounds the kernel: ~150 float64 operations per cell and view (two truncating divisions) in every
+// lane that is in front of the vehicle, a label gather served by L2, and, in voting lanes only, one read-modify-write of C map
+// values.  No LDS, integer atomics only (the counts, one per wave that has any).
+
+// avl_ground_fill in kernel-argument form: the window clipped to the grid
+struct FillParams {
+    double plane[4];
+    int x0, y0, h, w;
+    unsigned class_mask;
+    int* filled;         // [n_views] cells with a vote per view, or NULL
+};
+
+// One cell's votes -> its grid row: 16 vote bits per view, view 0 in the low bits; view 0's votes first, inside a view class i
+// adds CM[:, i], every addition rounded to the map type: apply_views_word without the byte packing and without a bonus.
+template <typename MapT>
+__device__ __forceinline__ void apply_fill_word(MapT* row, unsigned long long word, int C, const CmParams& cm) {
+    double vals[AVL_MAX_MAP_CLASSES];
+#pragma unroll
+    for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+        if (c < C) vals[c] = (double)row[c];
+    for (; word != 0ull; word >>= 16) {
+        const unsigned m = (unsigned)(word & 0xffffull);
+        if (m == 0u) continue;
+        for (int i = 0; i < C; ++i) {
+            if (m & (1u << i)) {
+#pragma unroll
+                for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+                    if (c < C) vals[c] = (double)(MapT)(vals[c] + cm.cm[c * C + i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < AVL_MAX_MAP_CLASSES; ++c)
+        if (c < C) row[c] = (MapT)vals[c];
+}
+static_assert(AVL_MAX_MAP_CLASSES * kMaxViews <= 64, "16 vote bits per view in the 64-bit word of apply_fill_word");
+
+// SRC, OCCL: as k_views_vote.  Lane -> cell (x0 + idx / w, y0 + idx % w): neighbouring lanes own neighbouring rows of the map.
+// g.bonus_classes is zero (a cell has no intensity), so pixel_vote adds no bonus.  Every lane runs the loop over the views in
+// full: the ballots of the counts sit in it.
+template <int SRC, int OCCL, typename MapT>
+__global__ void __launch_bounds__(kBlock) k_ground_fill(MapT* __restrict__ map, ViewsParams vp, GridParams g, FillParams fp, int src_w,
+                                                        int src_h, LogitsParams lp, LutParams lut, CmParams cm, OcclParams oc) {
+    const long long lane = (long long)blockIdx.x * kBlock + threadIdx.x;      // the last workgroup of a 2^31 - 1 cell window goes past an int
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0;
+    long long cell = 0;
+    if (lane < (long long)fp.h * fp.w) {
+        const int idx = (int)lane;
+        const int i = fp.x0 + idx / fp.w, j = fp.y0 + idx % fp.w;
+        const double x = (g.b00 + ((double)i + 0.5) * g.resolution) - g.off_x;
+        const double y = (g.b10 + ((double)j + 0.5) * g.resolution) - g.off_y;
+        double t = fp.plane[0] * x;
+        t = t + fp.plane[1] * y;
+        t = t + fp.plane[3];
+        const double z = (-t) / fp.plane[2];
+        positive = to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3);
+        cell = (long long)i * g.Wm + j;
+    }
+    unsigned long long word = 0ull;
+    for (int v = 0; v < vp.n_views; ++v) {
+        bool culled = false, abstains = false;
+        unsigned bits = 0u;
+        int ix, iy;
+        double p2;
+        if (positive && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {   // else this view does not see the cell
+            if (OCCL) {
+                unsigned key;
+                culled = depth_key(p2, key) && occl_culled(oc, v, ix, iy, key);
+            }
+            if (!culled)
+                bits = pixel_vote<SRC>(g, lut, lp, vp.src[v], lp.logits[v], src_w, src_h, vp.img_w, vp.img_h, ix, iy, 0.0, abstains) & fp.class_mask;
+        }
+        if (OCCL) count_culled(oc.culled, v, culled);
+        if (SRC == kSrcLogits) count_culled(lp.abstained, v, abstains);
+        count_culled(fp.filled, v, bits != 0u);
+        word |= (unsigned long long)bits << (16 * v);
+    }
+    if (word != 0ull) apply_fill_word(map + cell * g.C, word, g.C, cm);
+}
+
 // ================================================================ end-of-run rendering (src/renderer.py), SURVEY 8f row 3
 // RenderParams, numpy_row_sum (np.sum(map, axis=2) in NumPy's order) and the filter's tap loop are in avl_render.h: the live-map kernel
 // (seg_livemap.hip) computes the same values from them.
@@ -1143,8 +1231,9 @@ int fill_pts(PtsView& pv, const void* pts, int n, int dtype, int64_t point_strid
     return AVL_OK;
 }
 
-int fill_grid(GridParams& gp, const avl_grid* g, const uint8_t* colors, uint32_t bonus) {
-    if (!g || !g->map || !g->cell_mask || !g->touched || !g->counter) return avl::set_error(AVL_E_ARG, "avl_grid has NULL members");
+// the map and its geometry alone: what a call that needs none of the grid's scratch reads (avl_ground_fill_views)
+int fill_grid_map(GridParams& gp, const avl_grid* g, const uint8_t* colors, uint32_t bonus) {
+    if (!g || !g->map) return avl::set_error(AVL_E_ARG, "avl_grid has NULL members");
     if (g->Hm <= 0 || g->Wm <= 0 || g->C <= 0 || g->C > AVL_MAX_MAP_CLASSES)
         return avl::set_error(AVL_E_ARG, "grid %dx%dx%d (C must be 1..%d)", g->Hm, g->Wm, g->C, AVL_MAX_MAP_CLASSES);
     if ((long long)g->Hm * g->Wm > 0x7fffffffLL) return avl::set_error(AVL_E_ARG, "grid has more than 2^31 cells");
@@ -1157,6 +1246,11 @@ int fill_grid(GridParams& gp, const avl_grid* g, const uint8_t* colors, uint32_t
     memset(gp.colors, 0, sizeof(gp.colors));
     if (colors) memcpy(gp.colors, colors, 3 * g->C);
     return AVL_OK;
+}
+
+int fill_grid(GridParams& gp, const avl_grid* g, const uint8_t* colors, uint32_t bonus) {
+    if (!g || !g->map || !g->cell_mask || !g->touched || !g->counter) return avl::set_error(AVL_E_ARG, "avl_grid has NULL members");
+    return fill_grid_map(gp, g, colors, bonus);
 }
 
 int fill_cm(CmParams& cm, const avl_grid* g, const double* cm_host) {
@@ -1308,26 +1402,32 @@ struct VoteSource {
 // What every fused frame takes, validated and in kernel-argument form.  Everything here is refused before the empty cloud returns;
 // touched_cap matters only to a cloud that votes.  The logits stand where a class map stands: a source, its size and a LUT.
 struct FrameArgs { PtsView pv; ProjParams pp; GridParams gp; LutParams lut; };
-int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
-               const double* P_host, const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h,
-               const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus) {
+// what a frame and a ground fill refuse of a semantic source alike; the LUT of a class-map or logits source
+int fill_source(LutParams& lut, const VoteSource& src, int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host,
+                const double* cm_host) {
     const int src_kind = src.logits ? AVL_SRC_CLASSMAP : src.kind;
     const void* first = src.logits ? static_cast<const void*>(src.lp.logits[0]) : src.bytes[0];   // the only or first view's
-    int rc;
-    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
-    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
-    if ((rc = fill_grid(f.gp, g, label_colors_host, bonus))) return rc;
     AVL_REQUIRE(src_kind == AVL_SRC_RGB || src_kind == AVL_SRC_CLASSMAP, "src_kind %d", src_kind);
     AVL_REQUIRE(first && src.w > 0 && src.h > 0, "bad semantic source");
     AVL_REQUIRE(cm_host, "cm_host is NULL");
-    memset(&f.lut, 0, sizeof(f.lut));
+    memset(&lut, 0, sizeof(lut));
     if (src_kind == AVL_SRC_RGB) {
         AVL_REQUIRE(label_colors_host, "label_colors_host is NULL");
         AVL_REQUIRE(src.w == img_w && src.h == img_h, "RGB source must be %dx%d", img_w, img_h);
     } else {
         AVL_REQUIRE(lut_host, "lut_host is NULL");
-        memcpy(f.lut.lut, lut_host, sizeof(f.lut.lut));
+        memcpy(lut.lut, lut_host, sizeof(lut.lut));
     }
+    return AVL_OK;
+}
+int fill_frame(FrameArgs& f, const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+               const double* P_host, const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h,
+               const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus) {
+    int rc;
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = fill_grid(f.gp, g, label_colors_host, bonus))) return rc;
+    if ((rc = fill_source(f.lut, src, img_w, img_h, lut_host, label_colors_host, cm_host))) return rc;
     if (n > 0) AVL_REQUIRE(g->touched_cap >= (n < g->Hm * g->Wm ? n : g->Hm * g->Wm), "touched_cap %d too small", g->touched_cap);
     return AVL_OK;
 }
@@ -1559,6 +1659,56 @@ int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int6
     return run_frame(g, f, n_views, P_host, src, cm_host, bonus_classes, occl, stream);
 }
 
+// ---- the ground fill: avl_ground_fill_views (bytes) and _logits.  Everything is refused before any GPU work; the window is clipped
+// to the grid here, so the kernel's cells are all on it.
+int ground_fill(const avl_grid* g, const avl_ground_fill* gf, int n_views, const double* P_host, const double* T_host, const VoteSource& src,
+                int img_w, int img_h, const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    FillParams fp;
+    CmParams cm;
+    OcclParams oc;
+    int rc;
+    AVL_REQUIRE(gf, "avl_ground_fill is NULL");
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    AVL_REQUIRE(gf->range_max > 0.0, "ground fill range_max = %g (must be > 0)", gf->range_max);            // a NaN fails the comparison too
+    if ((rc = fill_proj(f.pp, P_host, T_host, gf->range_max, img_w, img_h))) return rc;
+    if ((rc = fill_grid_map(f.gp, g, label_colors_host, 0u))) return rc;
+    if ((rc = fill_source(f.lut, src, img_w, img_h, lut_host, label_colors_host, cm_host))) return rc;
+    if ((rc = fill_cm(cm, g, cm_host))) return rc;
+    AVL_REQUIRE(gf->h >= 0 && gf->w >= 0, "ground fill window of %d x %d cells", gf->h, gf->w);
+    AVL_REQUIRE((long long)gf->h * gf->w <= 0x7fffffffLL, "ground fill window of %d x %d cells has more than 2^31", gf->h, gf->w);
+    for (int k = 0; k < 4; ++k) AVL_REQUIRE(std::isfinite(gf->plane[k]), "ground plane coefficient %d = %g", k, gf->plane[k]);
+    AVL_REQUIRE(gf->plane[2] != 0.0, "ground plane with c = 0 is vertical");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(gf->filled) & 3) == 0, "ground fill filled counts are not 4-byte aligned");
+    memset(&oc, 0, sizeof(oc));
+    if (occl && (rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if (src.logits && (rc = logits_reset(src.lp, n_views, s))) return rc;
+    if (occl && (rc = occl_reset(oc, n_views, false, s))) return rc;             // the counts, not the buffer of real points
+    if (gf->filled) AVL_HIP_CHECK(hipMemsetAsync(gf->filled, 0, sizeof(int) * n_views, s));
+    const long long x0 = gf->x0 > 0 ? gf->x0 : 0, y0 = gf->y0 > 0 ? gf->y0 : 0;
+    const long long x1 = std::min<long long>((long long)gf->x0 + gf->h, g->Hm), y1 = std::min<long long>((long long)gf->y0 + gf->w, g->Wm);
+    if (x1 <= x0 || y1 <= y0) return AVL_OK;                                      // a window wholly off the grid
+    memcpy(fp.plane, gf->plane, sizeof(fp.plane));
+    fp.x0 = (int)x0; fp.y0 = (int)y0; fp.h = (int)(x1 - x0); fp.w = (int)(y1 - y0);
+    fp.class_mask = gf->class_mask;
+    fp.filled = gf->filled;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, src.logits ? nullptr : src.bytes);
+    const dim3 grid((unsigned)(((long long)fp.h * fp.w + kBlock - 1) / kBlock)), block(kBlock);
+    return launch_map_typed(g->map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        with_constant<3>(src.logits ? kSrcLogits : src.kind, [&](auto S) {
+            with_constant<2>(occl != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((k_ground_fill<decltype(S)::value, decltype(O)::value, T>), grid, block, 0, s, static_cast<T*>(g->map), vp,
+                                   f.gp, fp, src.w, src.h, src.lp, f.lut, cm, oc);
+            });
+        });
+    });
+}
+
 }  // namespace
 
 // ============================================================================ C ABI
@@ -1764,6 +1914,44 @@ extern "C" int avl_occlusion_visibility(const void* pts, int n, int dtype, int64
     hipLaunchKernelGGL(k_occl_visibility, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, f.pv, vp, oc, state, key);
     AVL_LAUNCH_CHECK();
     return AVL_OK;
+}
+
+extern "C" int avl_occlusion_depth(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
+                                   const double* P_host, const double* T_host, double range_max, int img_w, int img_h,
+                                   const avl_occlusion* occl, void* stream) {
+    FrameArgs f;
+    OcclParams oc;
+    int rc;
+    AVL_REQUIRE(n_views >= 1, "n_views = %d (at least one view)", n_views);
+    AVL_REQUIRE(n_views <= kMaxViews, "n_views = %d exceeds the limit of %d views", n_views, kMaxViews);
+    if ((rc = fill_pts(f.pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = fill_proj(f.pp, P_host, T_host, range_max, img_w, img_h))) return rc;
+    if ((rc = occl_fill(oc, occl, img_w, img_h, n_views))) return rc;
+    hipStream_t s = avl::as_stream(stream);
+    if ((rc = occl_reset(oc, n_views, true, s))) return rc;                      // the buffer is the result: an empty cloud leaves it empty
+    if (n == 0) return AVL_OK;
+    ViewsParams vp;
+    fill_views(vp, f, n_views, P_host, nullptr);
+    return launch_occl_depth(f.pv, vp, oc, s);
+}
+
+extern "C" int avl_ground_fill_views(const avl_grid* g, const avl_ground_fill* gf, int n_views, const double* P_host, const double* T_host,
+                                     int src_kind, const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                     const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                     const avl_occlusion* occl, void* stream) {
+    int rc;
+    if ((rc = views_check(n_views, src_host))) return rc;
+    return ground_fill(g, gf, n_views, P_host, T_host, bytes_source(src_kind, src_host, src_w, src_h), img_w, img_h, lut_host,
+                       label_colors_host, cm_host, occl, stream);
+}
+
+extern "C" int avl_ground_fill_views_logits(const avl_grid* g, const avl_ground_fill* gf, int n_views, const double* P_host,
+                                            const double* T_host, const avl_point_logits* pl, int img_w, int img_h, const uint32_t* lut_host,
+                                            const double* cm_host, const avl_occlusion* occl, void* stream) {
+    VoteSource src;
+    int rc;
+    if ((rc = logits_source(src, pl, n_views))) return rc;
+    return ground_fill(g, gf, n_views, P_host, T_host, src, img_w, img_h, lut_host, nullptr, cm_host, occl, stream);
 }
 
 extern "C" int avl_point_labels(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,

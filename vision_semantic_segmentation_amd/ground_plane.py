@@ -42,6 +42,37 @@ def plane_from_moments(p0, n, s1, s2, weight=None):
     return Plane3D(normal[0], normal[1], normal[2], d, weight=weight)
 
 
+def plane_coefficients(plane):
+    """(a, b, c, d) of a Plane3D, of a GroundPlaneResult that has been to the host, or of four numbers -> float64 [4]."""
+    plane = getattr(plane, "plane", plane)                          # GroundPlaneResult.plane
+    if plane is None:
+        raise ValueError("no plane: None, or a GroundPlaneResult without one (host() not called, or no hypothesis had an inlier)")
+    if hasattr(plane, "a"):
+        return np.array([plane.a, plane.b, plane.c, plane.d], dtype=np.float64)
+    p = np.asarray(plane, dtype=np.float64).reshape(-1)
+    if p.size != 4:
+        raise ValueError("a plane is a Plane3D or four numbers (a, b, c, d), got %d values" % p.size)
+    return p
+
+
+def plane_to_frame(plane, T):
+    """The plane a x + b y + c z + d = 0 of one frame, in the frame that the 4 x 4 transform ``T`` takes into it: a point X of that
+    other frame lies on the plane when (a, b, c, d) . (T X) = 0, so the result is ``np.array([a, b, c, d]) @ T``, one float64
+    matmul, not normalised.  ``T`` None gives the plane itself.  With the velodyne-frame ground plane and T = origin -> velodyne
+    (SemanticMapping._origin_to_velodyne) this is the plane in the world frame, the frame of a world-frame grid."""
+    p = plane_coefficients(plane)
+    if T is None:
+        return p
+    return np.matmul(p, np.asarray(T, dtype=np.float64).reshape(4, 4))
+
+
+def plane_tilt_deg(plane):
+    """The angle in degrees between the plane's normal and the z axis, whichever way the normal points; NaN for a zero normal."""
+    a, b, c, _ = plane_coefficients(plane)
+    with np.errstate(all="ignore"):
+        return float(np.degrees(np.arccos(abs(c) / np.sqrt(a * a + b * b + c * c))))
+
+
 class GroundPlaneWorkspace(object):
     """Every device buffer one estimate needs, for clouds of up to n_max points and n_hyp hypotheses.  A result made with a
     workspace refers to the workspace's tensors: the next estimate with the same workspace overwrites them."""

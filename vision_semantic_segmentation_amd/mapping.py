@@ -29,6 +29,10 @@ What differs from the reference, by design:
     reference model's full-resolution prediction is, and lets a point whose top-1 minus top-2 margin is below
     MAPPING.CONFIDENCE.MIN_MARGIN abstain (the rule at struct avl_point_logits in include/avl_hip.h); ``point_labels_device()``
     returns label and margin per point.  The reference votes the nearest low-resolution arg-max with full weight.
+  * with MAPPING.GROUND_FILL.ENABLED and a ground plane (``set_ground_plane()`` / ``plane_callback()``), every cell of a window around
+    the vehicle puts its centre on the plane, projects it into the cameras and takes the pixel's label as one update, after the
+    LiDAR frame (``ground_fill_device()``; the rule at struct avl_ground_fill in include/avl_hip.h): the map becomes dense where the
+    cameras see ground, not only where a LiDAR ring fell.  The reference has nothing of the kind that works.  Off by default.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -263,6 +267,11 @@ class SemanticMapping(object):
         self.min_margin = confidence_min_margin(cfg)   # a point whose top-1 minus top-2 margin is below it abstains; 0 gates nothing
         self.last_abstained = None             # int32 CUDA tensor [V]: votes the gate withheld per view in the last logits call (no sync)
 
+        # dense ground fill (MAPPING.GROUND_FILL); off by default: then nothing below is touched
+        self.ground_fill_cfg = getattr(cfg.MAPPING, "GROUND_FILL", None)
+        self.ground_plane = None               # float64 [4]: (a, b, c, d) in the velodyne frame (set_ground_plane, plane_callback)
+        self.last_filled = None                # int32 CUDA tensor [V]: cells that took a vote per view in the last ground fill (no sync)
+
         # device-side caches
         self._scratch = None
         self._pcd_dev = None
@@ -285,6 +294,9 @@ class SemanticMapping(object):
             self.sub_pcd = rospy.Subscriber("/reduced_map", PointCloud2, self.pcd_callback)
         elif self.depth_method == "points_raw":
             self.sub_pcd = rospy.Subscriber("/points_raw", PointCloud2, self.pcd_callback)
+        if self.cfg.MAPPING.GROUND_FILL.ENABLED:
+            from shape_msgs.msg import Plane
+            self.sub_plane = rospy.Subscriber("/estimated_plane", Plane, self.plane_callback)
 
     # ------------------------------------------------------------------ constants (mapping.py:142-170)
     def preprocessing(self):
@@ -509,6 +521,7 @@ class SemanticMapping(object):
                                         "semantic_image": np.array(_to_numpy(semantic_image)), "pose": pose})
             img = self._as_device_u8(semantic_image)
             self.frame_device(self.pcd, self.pcd_frame_id, img, pose, camera_calibration, src_kind="rgb")
+            self._ground_fill_step([img], pose, [camera_calibration])
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
         if self.save_map_to_file:                                                # mapping.py:323-345, both depth modes
@@ -535,8 +548,9 @@ class SemanticMapping(object):
                 for img in semantic_images:
                     self.input_list.append({"pcd": np.array(_to_numpy(self.pcd)), "pcd_frame_id": self.pcd_frame_id,
                                             "semantic_image": np.array(_to_numpy(img)), "pose": pose})
-            self.frame_device_views(self.pcd, self.pcd_frame_id, [self._as_device_u8(img) for img in semantic_images], pose, cameras,
-                                    src_kind="rgb")
+            images = [self._as_device_u8(img) for img in semantic_images]
+            self.frame_device_views(self.pcd, self.pcd_frame_id, images, pose, cameras, src_kind="rgb")
+            self._ground_fill_step(images, pose, cameras)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
         if self.save_map_to_file:
@@ -890,6 +904,126 @@ class SemanticMapping(object):
                                              _ptr(margin[v0:]), s)
             _lib.check(rc, "avl_point_labels")
         return state, margin
+
+    # ------------------------------------------------------------------ dense ground fill (MAPPING.GROUND_FILL)
+    def ground_fill_enabled(self):
+        return self.ground_fill_cfg is not None and bool(self.ground_fill_cfg.ENABLED)
+
+    def set_ground_plane(self, plane):
+        """The ground plane of the fill, in the VELODYNE frame: a Plane3D (the node's ``plane``), a GroundPlaneResult that has been
+        to the host (``estimate_ground_plane().host()``) or four numbers (a, b, c, d).  ValueError for anything that is not finite."""
+        from .ground_plane import plane_coefficients
+        p = plane_coefficients(plane)
+        if not np.isfinite(p).all():
+            raise ValueError("ground plane %r is not finite" % (p.tolist(),))
+        self.ground_plane = p
+
+    def plane_callback(self, msg):
+        """shape_msgs/Plane on /estimated_plane, as the segmentation node takes it (vision_semantic_segmentation_node.py:199-201)."""
+        self.set_ground_plane([msg.coef[0], msg.coef[1], msg.coef[2], msg.coef[3]])
+
+    def _ground_fill_class_mask(self):
+        names = list(self.ground_fill_cfg.CLASSES)
+        unknown = [n for n in names if n not in self.label_names]
+        if unknown:
+            raise ValueError("MAPPING.GROUND_FILL.CLASSES names %r, LABELS_NAMES has %r" % (unknown, list(self.label_names)))
+        return sum(1 << i for i, name in enumerate(self.label_names) if name in names)
+
+    def ground_fill_device(self, semantics, pose, cameras, plane=None, grid_frame_id=None, src_kind="classmap", image_size=None,
+                           net_size=None, net_palette=PALETTE_19, window=None, pcd=None, pcd_frame_id=None, stream=None):
+        """Dense ground fill (avl_ground_fill_views / _logits; the rule at struct avl_ground_fill in include/avl_hip.h): every cell of
+        ``window`` puts its centre on the ground plane, projects it into each camera of ``cameras`` (one calibration or a list) and
+        takes that pixel's label of ``semantics`` as one update, with MAPPING.GROUND_FILL's RANGE_MAX, CLASSES and WEIGHT.  Sources
+        as frame_device_views takes them (``src_kind`` "classmap", "rgb" or "logits"; one tensor for one camera).  ``plane``: in the
+        velodyne frame (set_ground_plane's forms), None = the plane last set.  ``grid_frame_id``: the frame of the clouds mapped onto
+        this grid (None = ``self.pcd_frame_id``, "velodyne" without a cloud); any other than "velodyne" needs the pose.  ``window``:
+        ((x0, y0), (h, w)) in cells, None = live_map_window of GROUND_FILL.SIZE_M around the vehicle (around the frame's origin for a
+        velodyne-frame grid).  With MAPPING.OCCLUSION.ENABLED and a cloud ``pcd`` (in ``pcd_frame_id``, None = the grid's frame) the
+        depth buffer is filled from it first (avl_occlusion_depth, the cloud's own range) and a cell behind a real point is culled.
+        Sets ``last_filled`` and, as the frame calls do, ``last_abstained`` and ``last_culled``.  ValueError for a plane whose normal
+        in the grid's frame is more than GROUND_FILL.MAX_TILT_DEG from the z axis."""
+        from .ground_plane import plane_tilt_deg, plane_to_frame
+        gf_cfg = self.ground_fill_cfg
+        single = not isinstance(cameras, (list, tuple))
+        cameras = [cameras] if single else list(cameras)
+        V = len(cameras)
+        if V < 1:
+            raise ValueError("ground_fill_device needs at least one camera")
+        if isinstance(semantics, torch.Tensor) and semantics.dim() == {"rgb": 3, "logits": 3}.get(src_kind, 2):
+            semantics = [semantics]                                  # one view's tensor, not a stack of views
+        plane = self.ground_plane if plane is None else plane
+        if plane is None:
+            raise RuntimeError("ground_fill_device needs a ground plane: none was given and set_ground_plane has not been called")
+        if grid_frame_id is None:
+            grid_frame_id = self.pcd_frame_id if self.pcd_frame_id is not None else "velodyne"
+        T_np = self._origin_to_velodyne(pose) if grid_frame_id != "velodyne" else None
+        plane_g = plane_to_frame(plane, T_np)
+        tilt = plane_tilt_deg(plane_g)
+        if not tilt <= float(gf_cfg.MAX_TILT_DEG):                   # a NaN (zero normal) fails the comparison too
+            raise ValueError("ground plane %r is tilted by %g degrees in the grid's frame (MAPPING.GROUND_FILL.MAX_TILT_DEG = %g)" % (
+                plane_g.tolist(), tilt, float(gf_cfg.MAX_TILT_DEG)))
+        if window is None:
+            centre = pose if grid_frame_id != "velodyne" else np.zeros(7)
+            window = self.live_map_window(centre, [int(float(v) / self.resolution) for v in gf_cfg.SIZE_M])[:2]
+        (x0, y0), (h, w) = window
+        if src_kind == "logits":
+            views = logits_views(semantics, V)[0]
+        else:
+            views = [semantics[v] for v in range(V)] if isinstance(semantics, torch.Tensor) else list(semantics)
+            if len(views) != V:
+                raise ValueError("%d semantic sources for %d cameras" % (len(views), V))
+            shape = tuple(views[0].shape)
+            for t in views:
+                if tuple(t.shape) != shape or t.dtype != torch.uint8 or not t.is_cuda:
+                    raise ValueError("the views' semantic sources must be uint8 CUDA tensors of one size")
+            sh, sw, ih, iw, kind, lut = self._semantic_source(shape, src_kind, image_size, net_palette)
+            views = [t.contiguous() for t in views]
+        cm = _dbl(np.asarray(self.confusion_matrix, dtype=np.float64) * float(gf_cfg.WEIGHT))
+        T = _dbl(T_np) if T_np is not None else None
+        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+        gs = self.grid.struct()
+        occlusion = self.occlusion_enabled() and pcd is not None
+        self.last_filled = torch.zeros(V, dtype=torch.int32, device=self.device)
+        if src_kind == "logits":
+            self.last_abstained = torch.zeros(V, dtype=torch.int32, device=self.device)
+        if occlusion:
+            self.last_culled = torch.zeros(V, dtype=torch.int32, device=self.device)
+        gf = _lib.AvlGroundFill()
+        gf.x0, gf.y0, gf.h, gf.w = int(x0), int(y0), int(h), int(w)
+        gf.plane[:] = [float(v) for v in plane_g]
+        gf.range_max = float(gf_cfg.RANGE_MAX)
+        gf.class_mask = self._ground_fill_class_mask()
+        for v0 in range(0, V, _lib.AVL_MAX_VIEWS):       # a cell takes its views in order whether one call holds them all or not
+            cams = cameras[v0:v0 + _lib.AVL_MAX_VIEWS]
+            n = len(cams)
+            P = _dbl(np.stack([np.asarray(c.P, dtype=np.float64) for c in cams]))
+            gf.filled = self.last_filled.data_ptr() + 4 * v0
+            if src_kind == "logits":
+                pl, ih, iw = self._point_logits(views[v0:v0 + n], image_size, net_size, (self.last_abstained, v0))
+            occ = None
+            if occlusion:
+                o = self._occlusion(n, ih, iw, (self.last_culled, v0))
+                pview, pT, _, _, _ = self._frame_args(pcd, grid_frame_id if pcd_frame_id is None else pcd_frame_id, pose, cams[0].P, grid=False)
+                rc = _lib.lib().avl_occlusion_depth(*pview, n, P, pT, float(self.pcd_range_max), iw, ih, C.byref(o), s)
+                _lib.check(rc, "avl_occlusion_depth")
+                occ = C.byref(o)
+            if src_kind == "logits":
+                rc = _lib.lib().avl_ground_fill_views_logits(C.byref(gs), C.byref(gf), n, P, T, C.byref(pl), iw, ih, self._lut_host(net_palette),
+                                                             cm, occ, s)
+                _lib.check(rc, "avl_ground_fill_views_logits")
+            else:
+                src = (C.c_void_p * n)(*[t.data_ptr() for t in views[v0:v0 + n]])
+                rc = _lib.lib().avl_ground_fill_views(C.byref(gs), C.byref(gf), n, P, T, kind, src, sw, sh, iw, ih, lut, self._colors_host(),
+                                                      cm, occ, s)
+                _lib.check(rc, "avl_ground_fill_views")
+        self._map_host = None
+
+    def _ground_fill_step(self, semantic_images, pose, cameras):
+        """mapping()'s / mapping_views()'s fill branch: with GROUND_FILL.ENABLED and a plane set, the fill from the frame's own colour
+        images, pose and cameras, right after the LiDAR frame.  With OCCLUSION.ENABLED the depth pass runs again for the fill."""
+        if self.ground_fill_enabled() and self.ground_plane is not None:
+            self.ground_fill_device(semantic_images, pose, cameras, grid_frame_id=self.pcd_frame_id, src_kind="rgb", pcd=self.pcd,
+                                    pcd_frame_id=self.pcd_frame_id)
 
     def project_pcd(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """mapping.py:357-389.  NumPy in, NumPy out: (pcd[:, mask] float64[4,M], label uint8[3,M]).

@@ -624,6 +624,34 @@ int avl_plane_ransac(const void* pts, int n, int dtype, int64_t point_stride, in
                      int weight_method, double x0, int norm /* 1 | 2 */, double tolerance, double min_c, double* planes_out,
                      int32_t* counts_out, void* result, void* scratch, void* stream);
 
+/* ---- the prior point map, tiled and cropped per frame (not in the reference; csrc/seg_pointsmap.hip) ----------------------------
+ * Replaces the /reduced_map subscription (src/mapping.py:61-62) and the unpacking of what arrives on it (pcd_callback, :172-183): in
+ * the reference's deployment a node outside the package crops the site's point map around the vehicle and republishes the crop.
+ * Here the whole map is on the device, stored as float32 [N'][4] (x, y, z, intensity; world frame) sorted by ground tile, and one
+ * kernel per frame copies the tiles of a rectangle into a contiguous cloud for the frame entry points above.
+ *
+ * DROP RULE.  A point is dropped if any of its four fields is NaN, or if x or y is infinite.
+ * TILE RULE.  ix = (int) floor(((double) x - ox) / tile_m), and the same for iy with oy.  ox = floor(min_x / tile_m) * tile_m over
+ * the kept points, in float64, and the same for oy.  rows = ix_max + 1, cols = iy_max + 1, key = ix * cols + iy.  An index is
+ * refused when rows * cols > 2^24 or N >= 2^31.
+ * The points are sorted by key, stable: inside a tile they keep the input's order.  offsets int32 [rows * cols + 1]: tile `key`
+ * is points[offsets[key] .. offsets[key + 1]).  Row r of a rectangle (r0..r1, c0..c1, both ends included) is therefore one run,
+ * offsets[r * cols + c0] .. offsets[r * cols + c1 + 1].  A rectangle with r0 > r1 or c0 > c1 is empty; any other must lie inside
+ * the index (AVL_E_ARG otherwise). */
+/* keys[k] = the key of points[k] by the two rules, -1 for a dropped point (and for one outside rows x cols, which the rule's own
+ * ox, oy, rows, cols never produce).  points float32 [n][4] on the device, 16-byte aligned; keys int32 [n] on the device. */
+int avl_points_map_keys(const float* points, int64_t n, double ox, double oy, double tile_m, int rows, int cols, int32_t* keys, void* stream);
+/* Host only, no HIP call: *m_out = the points of the rectangle (the sum of its run lengths), *runs_out = its non-empty runs. */
+int avl_points_map_window(const int32_t* offsets_host, int rows, int cols, int r0, int r1, int c0, int c1, int64_t* m_out,
+                          int32_t* runs_out);
+/* dst[0 .. M) = the rectangle's runs in row order, M as avl_points_map_window counts it from offsets_host, the host's copy of
+ * offsets_dev (sizes the launch; the kernel reads offsets_dev alone and never writes past M).  One lane copies one point as one
+ * 16-byte load and one 16-byte store: points and dst (float32 [dst_capacity][4]) are 16-byte aligned.  Nothing is copied from the
+ * host, allocated or waited for, so the call can be captured in a graph.  At most 1024 rows go into one launch, a taller rectangle
+ * takes several.  M = 0 launches nothing; dst_capacity < M is AVL_E_ARG. */
+int avl_points_map_gather(const float* points, const int32_t* offsets_dev, const int32_t* offsets_host, int rows, int cols, int r0, int r1,
+                          int c0, int c1, float* dst, int64_t dst_capacity, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

@@ -121,6 +121,9 @@ _SIGNATURES = {
     "avl_class_hulls": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avl_plane_scratch_bytes": (_i64, [_i, _i]),
     "avl_plane_ransac": (_i, [_vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _d, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "avl_points_map_keys": (_i, [_vp, _i64, _d, _d, _d, _i, _i, _vp, _vp]),
+    "avl_points_map_window": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    "avl_points_map_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
 }
 
 

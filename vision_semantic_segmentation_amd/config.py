@@ -203,6 +203,19 @@ def get_cfg_defaults():
     C.MAPPING.GROUND_FILL.CLASSES = ["road", "crosswalk", "lane", "sidewalk"]
     C.MAPPING.GROUND_FILL.WEIGHT = 1.0
     C.MAPPING.GROUND_FILL.MAX_TILT_DEG = 30.0
+    # build-specific: where the cloud of DEPTH_METHOD "points_map" comes from.  "topic" = /reduced_map (the reference: a node outside
+    # the package crops the site's point map around the vehicle and republishes it); nothing below is touched.  "index" = the whole
+    # point map is loaded once from PATH (a .npy array [N, 4] or [4, N]: x, y, z, intensity in the world frame; or
+    # SemanticMapping.load_points_map), sorted into ground tiles of TILE_M metres on the device, and every frame one kernel copies the
+    # tiles that can hold a voting point into the frame's cloud (points_map.py; the rules: include/avl_hip.h, avl_points_map_gather).
+    # RADIUS_M 0 = the exact window of the frame's cameras (the grid ends bit-equal to a frame on the whole map); > 0 = the square of
+    # that half-side around the sensor, an external reducer's crop.  MARGIN_M grows either.  Another DEPTH_METHOD refuses "index"
+    C.MAPPING.POINTS_MAP = CfgNode()
+    C.MAPPING.POINTS_MAP.SOURCE = "topic"
+    C.MAPPING.POINTS_MAP.PATH = ""
+    C.MAPPING.POINTS_MAP.TILE_M = 10.0
+    C.MAPPING.POINTS_MAP.RADIUS_M = 0.0
+    C.MAPPING.POINTS_MAP.MARGIN_M = 1.0
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

@@ -33,6 +33,10 @@ What differs from the reference, by design:
     the vehicle puts its centre on the plane, projects it into the cameras and takes the pixel's label as one update, after the
     LiDAR frame (``ground_fill_device()``; the rule at struct avl_ground_fill in include/avl_hip.h): the map becomes dense where the
     cameras see ground, not only where a LiDAR ring fell.  The reference has nothing of the kind that works.  Off by default.
+  * with MAPPING.POINTS_MAP.SOURCE = "index" the points-map mode needs no node that crops the site's point map and publishes
+    /reduced_map (mapping.py:61-62): ``load_points_map()`` puts the whole map on the device, sorted into ground tiles, and every frame
+    takes its cloud from ``reduced_map_device()``, one kernel that copies the tiles that can hold a voting point (points_map.py).  The
+    grid ends bit-equal to a frame on the whole map.  Off ("topic") by default.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -58,6 +62,11 @@ PCD_ORIGIN_OFFSET = (1369.0496826171875, 562.84814453125, 0.0)
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _raw_stream(s):
+    """A torch.cuda.Stream or a raw stream handle -> the raw handle; None stays None (torch's current stream)."""
+    return None if s is None else int(getattr(s, "cuda_stream", s))
 
 
 _DBL_CACHE = {}
@@ -184,6 +193,20 @@ class SemanticMapping(object):
         self._lock = threading.RLock()
 
         self.depth_method = cfg.MAPPING.DEPTH_METHOD
+        # the points-map mode's own index (MAPPING.POINTS_MAP); SOURCE "topic", the default: nothing of it runs and nothing is allocated
+        self.points_map_cfg = getattr(cfg.MAPPING, "POINTS_MAP", None)
+        self.points_map_source = "topic" if self.points_map_cfg is None else self.points_map_cfg.SOURCE
+        if self.points_map_source not in ("topic", "index"):
+            raise ValueError("MAPPING.POINTS_MAP.SOURCE must be 'topic' or 'index', not %r" % (self.points_map_source,))
+        if self.points_map_source == "index" and self.depth_method != "points_map":
+            raise ValueError("MAPPING.POINTS_MAP.SOURCE = 'index' needs MAPPING.DEPTH_METHOD = 'points_map', not %r" % (self.depth_method,))
+        self.points_map_index = None           # points_map.PointsMapIndex (load_points_map)
+        self.last_reduced = None               # {"points": M, "tiles": ..., "rows": ..., "reused": bool} of the last reduced_map_device
+        self._reduced_buf = None               # float32 CUDA [capacity, 4]: grows geometrically
+        self._reduced_rect = None              # the rectangle _reduced_buf holds
+        self._reduced_stream = None            # the stream the gather that filled it ran on
+        if self.points_map_indexed() and self.points_map_cfg.PATH != "":
+            self.load_points_map(self.points_map_cfg.PATH)     # before the subscribers exist: no frame can arrive ahead of the index
         self._ros = None
         if use_ros:
             self._setup_ros()
@@ -291,7 +314,8 @@ class SemanticMapping(object):
         self.pub_semantic_local_map = rospy.Publisher("/semantic_local_map", Image, queue_size=5)     # mapping.py:69
         self._ros_image_cls = Image
         if self.depth_method == "points_map":
-            self.sub_pcd = rospy.Subscriber("/reduced_map", PointCloud2, self.pcd_callback)
+            if not self.points_map_indexed():                  # with the index nothing outside the package has to publish the crop
+                self.sub_pcd = rospy.Subscriber("/reduced_map", PointCloud2, self.pcd_callback)
         elif self.depth_method == "points_raw":
             self.sub_pcd = rospy.Subscriber("/points_raw", PointCloud2, self.pcd_callback)
         if self.cfg.MAPPING.GROUND_FILL.ENABLED:
@@ -466,7 +490,7 @@ class SemanticMapping(object):
             # the reference only warns and then fails on an unbound variable (mapping.py:277-278)
             raise ValueError("cannot find camera for frame_id %s" % msg.header.frame_id)
         with self._lock:
-            if self.depth_method in ["points_map", "points_raw"]:
+            if self.depth_method in ["points_map", "points_raw"] and not self.points_map_indexed():
                 if len(self.pcd_header_queue) == 0:
                     return
                 self.pcd, self.pcd_time = self.update_pcd(msg.header.stamp)
@@ -494,7 +518,7 @@ class SemanticMapping(object):
         images = [m.data if isinstance(getattr(m, "data", None), (np.ndarray, torch.Tensor)) else _imgmsg_to_array(m) for m in msgs]
         cameras = [self._camera_for(m.header.frame_id) for m in msgs]
         with self._lock:
-            if self.depth_method in ["points_map", "points_raw"]:
+            if self.depth_method in ["points_map", "points_raw"] and not self.points_map_indexed():
                 if len(self.pcd_header_queue) == 0:
                     return
                 self.pcd, self.pcd_time = self.update_pcd(stamp)
@@ -502,6 +526,65 @@ class SemanticMapping(object):
                 return
             self.pose, self.pose_time = self.update_pose(stamp)
             self.mapping_views(images, self.pose, cameras)
+
+    # ------------------------------------------------------------------ the points map's own index (MAPPING.POINTS_MAP)
+    def points_map_indexed(self):
+        return self.points_map_source == "index"
+
+    def load_points_map(self, points_or_path, tile_m=None):
+        """Put the site's prior point map on the device and sort it into ground tiles (points_map.PointsMapIndex; once, not per
+        frame).  ``points_or_path``: [N, 4] or [4, N] (x, y, z, intensity in the world frame), NumPy or torch, float32 or float64, or
+        the path of a .npy file that holds one.  ``tile_m`` None = MAPPING.POINTS_MAP.TILE_M.  Returns the index."""
+        from .points_map import PointsMapIndex
+        if tile_m is None:
+            tile_m = self.points_map_cfg.TILE_M if self.points_map_cfg is not None else 10.0
+        with self._lock:
+            self.points_map_index = PointsMapIndex(points_or_path, tile_m, self.device)
+            self._reduced_rect = None
+            self.last_reduced = None
+        return self.points_map_index
+
+    def reduced_map_device(self, pose, cameras=None, image_size=None, stream=None):
+        """The frame's cloud, cropped from the index: a float32 CUDA tensor [M, 4] in the world frame, for frame_device(pcd, "world",
+        ...) and every other entry point that takes a cloud.  The crop is the tile rectangle of points_map.window for ``pose``,
+        ``cameras`` (None = both of the vehicle's) and ``image_size`` = (H, W) of the projection image (None = the calibrations' own),
+        with MAPPING.POINTS_MAP's RADIUS_M and MARGIN_M and the cloud's RANGE_MAX; one kernel copies it (avl_points_map_gather) on
+        ``stream``.  The tensor is a view of a buffer that the next call overwrites.  When the rectangle is the previous call's,
+        and the stream is the one that gather ran on, that buffer is returned as it is and nothing is launched; on another stream
+        the gather runs again, so the cloud is always ordered on the stream asked for.  The buffer itself is one: a caller who
+        alternates streams orders the earlier stream's readers before the later gather, as with any reused buffer.
+        ``last_reduced`` = {"points": M, "tiles": tiles of the rectangle, "rows": its rows that hold a point, "reused": bool,
+        "rect": (r0, r1, c0, c1)}."""
+        from . import points_map as pm
+        index = self.points_map_index
+        if index is None:
+            raise RuntimeError("MAPPING.POINTS_MAP.SOURCE = 'index' but no points map is loaded: set MAPPING.POINTS_MAP.PATH or call "
+                               "SemanticMapping.load_points_map() before the first frame")
+        if pose is None:
+            raise ValueError("reduced_map_device needs the frame's pose: the points map is in the world frame")
+        cameras = [self.cam1, self.cam6] if cameras is None else (list(cameras) if isinstance(cameras, (list, tuple)) else [cameras])
+        pc = self.points_map_cfg
+        radius, margin = (float(pc.RADIUS_M), float(pc.MARGIN_M)) if pc is not None else (0.0, 1.0)
+        if image_size is None and radius <= 0.0:
+            sizes = {tuple(cam.imSize) if cam.imSize is not None else None for cam in cameras}
+            if len(sizes) != 1 or None in sizes:
+                raise ValueError("reduced_map_device needs image_size = (H, W): the cameras do not carry one image size")
+            w, h = sizes.pop()
+            image_size = (h, w)
+        rect = pm.window(index, pose, cameras, image_size, float(self.pcd_range_max), radius, margin)
+        s = int(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+        if self._reduced_buf is not None and rect == self._reduced_rect and s == self._reduced_stream:
+            self.last_reduced = dict(self.last_reduced, reused=True)
+            return self._reduced_buf[:self.last_reduced["points"]]
+        m, runs = pm.window_count(index.offsets_host, index.rows, index.cols, rect)
+        if self._reduced_buf is None or int(self._reduced_buf.shape[0]) < m:
+            cap = max(m, 2 * (0 if self._reduced_buf is None else int(self._reduced_buf.shape[0])), 1 << 12)
+            self._reduced_buf = torch.empty((cap, 4), dtype=torch.float32, device=self.device)
+        pm.gather(index, rect, self._reduced_buf, s)
+        self._reduced_rect, self._reduced_stream = rect, s
+        r0, r1, c0, c1 = rect
+        self.last_reduced = {"points": m, "tiles": max(r1 - r0 + 1, 0) * max(c1 - c0 + 1, 0), "rows": runs, "reused": False, "rect": rect}
+        return self._reduced_buf[:m]
 
     # ------------------------------------------------------------------ per-frame hot path
     def mapping(self, semantic_image, pose, camera_calibration):
@@ -514,14 +597,20 @@ class SemanticMapping(object):
             self.update_map_planar(self.map_dev, img, camera_calibration)
             self.frames_mapped += 1
         else:
-            if self.pcd is None:
-                return
+            img = None
+            if self.points_map_indexed():                                        # the frame's cloud is cropped from the index
+                img = self._as_device_u8(semantic_image)
+                pcd, frame_id = self.reduced_map_device(pose, [camera_calibration], img.shape[:2]), "world"
+            else:
+                if self.pcd is None:
+                    return
+                pcd, frame_id = self.pcd, self.pcd_frame_id
             if self.record_inputs:                                               # mapping.py:309-313
-                self.input_list.append({"pcd": np.array(_to_numpy(self.pcd)), "pcd_frame_id": self.pcd_frame_id,
+                self.input_list.append({"pcd": np.array(_to_numpy(pcd)), "pcd_frame_id": frame_id,
                                         "semantic_image": np.array(_to_numpy(semantic_image)), "pose": pose})
-            img = self._as_device_u8(semantic_image)
-            self.frame_device(self.pcd, self.pcd_frame_id, img, pose, camera_calibration, src_kind="rgb")
-            self._ground_fill_step([img], pose, [camera_calibration])
+            img = self._as_device_u8(semantic_image) if img is None else img
+            self.frame_device(pcd, frame_id, img, pose, camera_calibration, src_kind="rgb")
+            self._ground_fill_step([img], pose, [camera_calibration], pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
         if self.save_map_to_file:                                                # mapping.py:323-345, both depth modes
@@ -542,15 +631,21 @@ class SemanticMapping(object):
                 self.update_map_planar(self.map_dev, self._as_device_u8(img), cam)
                 self.frames_mapped += 1
         else:
-            if self.pcd is None:
-                return
+            images = None
+            if self.points_map_indexed():
+                images = [self._as_device_u8(img) for img in semantic_images]
+                pcd, frame_id = self.reduced_map_device(pose, cameras, images[0].shape[:2]), "world"
+            else:
+                if self.pcd is None:
+                    return
+                pcd, frame_id = self.pcd, self.pcd_frame_id
             if self.record_inputs:
                 for img in semantic_images:
-                    self.input_list.append({"pcd": np.array(_to_numpy(self.pcd)), "pcd_frame_id": self.pcd_frame_id,
+                    self.input_list.append({"pcd": np.array(_to_numpy(pcd)), "pcd_frame_id": frame_id,
                                             "semantic_image": np.array(_to_numpy(img)), "pose": pose})
-            images = [self._as_device_u8(img) for img in semantic_images]
-            self.frame_device_views(self.pcd, self.pcd_frame_id, images, pose, cameras, src_kind="rgb")
-            self._ground_fill_step(images, pose, cameras)
+            images = [self._as_device_u8(img) for img in semantic_images] if images is None else images
+            self.frame_device_views(pcd, frame_id, images, pose, cameras, src_kind="rgb")
+            self._ground_fill_step(images, pose, cameras, pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
         if self.save_map_to_file:
@@ -1018,12 +1113,12 @@ class SemanticMapping(object):
                 _lib.check(rc, "avl_ground_fill_views")
         self._map_host = None
 
-    def _ground_fill_step(self, semantic_images, pose, cameras):
+    def _ground_fill_step(self, semantic_images, pose, cameras, pcd, pcd_frame_id):
         """mapping()'s / mapping_views()'s fill branch: with GROUND_FILL.ENABLED and a plane set, the fill from the frame's own colour
-        images, pose and cameras, right after the LiDAR frame.  With OCCLUSION.ENABLED the depth pass runs again for the fill."""
+        images, pose, cameras and cloud, right after the LiDAR frame.  With OCCLUSION.ENABLED the depth pass runs again for the fill."""
         if self.ground_fill_enabled() and self.ground_plane is not None:
-            self.ground_fill_device(semantic_images, pose, cameras, grid_frame_id=self.pcd_frame_id, src_kind="rgb", pcd=self.pcd,
-                                    pcd_frame_id=self.pcd_frame_id)
+            self.ground_fill_device(semantic_images, pose, cameras, grid_frame_id=pcd_frame_id, src_kind="rgb", pcd=pcd,
+                                    pcd_frame_id=pcd_frame_id)
 
     def project_pcd(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """mapping.py:357-389.  NumPy in, NumPy out: (pcd[:, mask] float64[4,M], label uint8[3,M]).
@@ -1202,9 +1297,16 @@ class SemanticMapping(object):
     def estimate_ground_plane(self, pose=None, **kw):
         """The ground plane of the current cloud (``self.pcd`` in ``self.pcd_frame_id``) in the velodyne frame, estimated on the GPU:
         ground_plane.estimate_ground_plane_device with its keyword arguments.  A cloud that is not in the velodyne frame needs the
-        pose (the transform of project_pcd, mapping.py:368-373).  Returns the GroundPlaneResult (asynchronous until ``.host()``)."""
+        pose (the transform of project_pcd, mapping.py:368-373).  Returns the GroundPlaneResult (asynchronous until ``.host()``).
+        With MAPPING.POINTS_MAP.SOURCE = "index" the cloud is ``reduced_map_device(pose)``, the crop of the vehicle's cameras around
+        ``pose``, a "world" cloud: the pose is needed."""
         from .ground_plane import estimate_ground_plane_device
         with self._lock:
+            if self.points_map_indexed():
+                if pose is None:
+                    raise ValueError("a cloud in frame 'world' needs the pose to reach the velodyne frame")
+                cloud = self.reduced_map_device(pose, stream=_raw_stream(kw.get("stream")))
+                return estimate_ground_plane_device(cloud, T=self._origin_to_velodyne(pose), device=self.device, **kw)
             if self.pcd is None:
                 raise RuntimeError("estimate_ground_plane needs a point cloud: no pcd yet")
             T = None

@@ -359,6 +359,79 @@ int avl_occlusion_depth(const void* pts, int n, int dtype, int64_t point_stride,
                         const double* P_host /* [n_views][12] */, const double* T_host, double range_max, int img_w, int img_h,
                         const avl_occlusion* occl, void* stream);
 
+/* ---- a9h: height-aware mapping -- a ground-height vote gate and an elevation layer (not in the reference) ---------- */
+
+/* update_map projects the cloud onto z = 0 (:403-406): a point 4 m up in a tree canopy votes "vegetation" into the road cell beneath
+ * it, and a point on a car roof that took a "road" pixel through label bleed votes "road".  With the ground plane in the grid's
+ * frame, the calls below let a class bit vote only while the point's height above the plane lies in that class's band, and
+ * accumulate the same points' z per cell as the elevation of the drivable surface.  The two parts are independent.  THE RULE, for a
+ * point that in view v is a candidate (:378-383 as avl_fused_frame computes it), falls on the grid, is not culled by occlusion, does
+ * not abstain, and whose pixel gave the vote bits b (class bit i, its lane bonus at bit 16 + i); every float64 operation is rounded
+ * on its own (no fused multiply-add):
+ *   1. height: the plane (a, b, c, d) = plane[0..3] is in the frame of the cloud as passed in, which is the grid's frame; the CALLER
+ *      normalises it in float64 to a unit normal with c > 0 (SemanticMapping.height_plane) and the library uses the four numbers as
+ *      they are.  t = a * x; u = b * y; t = t + u; u = c * z; t = t + u; h = t + d, with x, y, z the point's coordinates as loaded
+ *      (a float32 cloud converted to double): three products and three sums.
+ *   2. slack: s = slope * v0, v0 the forward distance of :371/:378 (the first row of T_host . (x, y, z, 1); the point's own x when
+ *      T_host is NULL): a plane fitted near the car drifts off a graded road.  For class i: lo_i = min_m[i] - s, hi_i = max_m[i] + s.
+ *   3. gate, only when gate != 0: class bit i of b stays iff lo_i <= h && h <= hi_i, both bounds inclusive.  A NaN h removes every
+ *      bit; max_m[i] = +inf never removes a bit above, min_m[i] = -inf never one below.  A removed class bit takes its bonus bit
+ *      with it.
+ *   4. count: gated[v] = the number of such points whose b was non-zero and is zero after rule 3 -- the votes the gate withheld.
+ *      The call resets it itself; one integer atomic per wave that has any.
+ *   5. elevation, only with a layer (elev_classes != 0 and the four arrays), whether the gate is on or not: a point contributes
+ *      once per call, however many views see it, when the union over the call's views of its surviving class bits meets
+ *      elev_classes.  q = rint(z / quantum): an IEEE division, then round half to even; a q outside int32 contributes nothing.
+ *      Otherwise, at the point's cell: elev_sum += q (int64), elev_cnt += 1, elev_min = min(elev_min, q), elev_max = max(elev_max, q).
+ *      The layer persists across calls; an empty cell holds sum 0, cnt 0, min INT32_MAX, max INT32_MIN (avl_elevation_reset).  Only
+ *      integer atomics: the layer does not depend on the order of the points.
+ *   6. everything else is avl_fused_frame_views's: the masks, the apply (inside a view class i ascending, each followed by its
+ *      bonus), the path -- avl_fused_frame_views_path's for n as passed in -- and the scratch contract of avl_grid.  The apply and
+ *      sweep kernels are the plain calls'.
+ * The grid after a gated call equals, bit for bit, what the plain call does with the cloud from which that view's gated points were
+ * removed (for a palette where every pixel gives one class). */
+typedef struct avl_height {
+    int32_t gate;                        /* 0 = no gate (plane, bounds, slope and gated are not read), 1 = rule 3                */
+    double plane[4];                     /* a, b, c, d in the grid's frame; finite, c > 0, normalised by the caller               */
+    double min_m[AVL_MAX_MAP_CLASSES];   /* per map class, metres; -inf = unbounded below; never a NaN; min_m[i] <= max_m[i]      */
+    double max_m[AVL_MAX_MAP_CLASSES];   /* per map class, metres; +inf = unbounded above                                         */
+    double slope;                        /* finite, >= 0: metres of extra tolerance per metre of forward distance                 */
+    int32_t* gated;                      /* int32[n_views] or NULL: receives, per view, the votes the gate withheld               */
+    uint32_t elev_classes;               /* bit i set: a point voting class i enters the layer; 0 = no layer                      */
+    double quantum;                      /* finite, > 0: metres per integer step of the layer                                     */
+    int64_t* elev_sum;                   /* [Hm * Wm], 8-byte aligned; all four arrays or none (none = no layer)                  */
+    int32_t* elev_cnt;                   /* [Hm * Wm]                                                                             */
+    int32_t* elev_min;                   /* [Hm * Wm]                                                                             */
+    int32_t* elev_max;                   /* [Hm * Wm]                                                                             */
+} avl_height;
+
+/* avl_fused_frame_views with the rule above, for every source and with or without culling: pl == NULL takes the byte source
+ * (src_kind, src_host, src_w, src_h, lut_host, label_colors_host as avl_fused_frame_views takes them), pl != NULL the logits (those
+ * arguments but lut_host are then not read); occl == NULL means no culling.  n_views == 1 runs the single-view kernel.  AVL_E_ARG,
+ * before any GPU work, for what the plain calls refuse (and avl_fused_frame_views_logits / _occl of a non-NULL pl / occl), a NULL ht,
+ * a gate other than 0 or 1, and with the gate on a plane that is not finite or has c <= 0, a NaN bound or min_m[i] > max_m[i] for a
+ * class i < C, a NaN, infinite or negative slope; a layer with some but not all of its four arrays, with elev_classes or arrays
+ * given a quantum that is not finite and > 0 or class bits beyond C; a misaligned gated or layer array. */
+int avl_fused_frame_views_height(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                 int n_views, const double* P_host /* [n_views][12] */, const double* T_host, double range_max,
+                                 int src_kind, const uint8_t* const* src_host /* n_views device pointers */,
+                                 int src_w, int src_h, int img_w, int img_h,
+                                 const uint32_t* lut_host, const uint8_t* label_colors_host,
+                                 const double* cm_host, uint32_t bonus_classes, const avl_point_logits* pl,
+                                 const avl_occlusion* occl, const avl_height* ht, void* stream);
+
+/* Rules 1 and 2 alone (points addressed as in avl_project_points), for every point, candidate or not: h double[n] and s double[n],
+ * both NaN for a point with a non-finite coordinate.  Of ht only plane and slope are read, whatever gate says.  AVL_E_ARG for a NULL
+ * ht, a plane or slope the frame call refuses, a NULL or misaligned h or s. */
+int avl_point_heights(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* T_host,
+                      const avl_height* ht, double* h, double* s, void* stream);
+
+/* The layer's mean: out[cell] = (float)(((double)sum[cell] / (double)cnt[cell]) * quantum), NaN where cnt[cell] == 0. */
+int avl_elevation_mean(const int64_t* sum, const int32_t* cnt, int64_t ncell, double quantum, float* out, void* stream);
+
+/* The four arrays to the empty state of rule 5: sum 0, cnt 0, min INT32_MAX, max INT32_MIN. */
+int avl_elevation_reset(int64_t* sum, int32_t* cnt, int32_t* qmin, int32_t* qmax, int64_t ncell, void* stream);
+
 /* a6: colourised full-resolution semantic image from the small argmax map
  * (vision_semantic_segmentation_node.py:102,109-116): nearest upscale + palette LUT.
  * labels uint8[lh][lw]; palette_host uint8[256][3]; out uint8[out_h][out_w][3]. */

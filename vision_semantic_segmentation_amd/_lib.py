@@ -63,6 +63,15 @@ class AvlGroundFill(C.Structure):
     ]
 
 
+class AvlHeight(C.Structure):
+    """struct avl_height of include/avl_hip.h"""
+    _fields_ = [
+        ("gate", C.c_int32), ("plane", C.c_double * 4), ("min_m", C.c_double * AVL_MAX_MAP_CLASSES),
+        ("max_m", C.c_double * AVL_MAX_MAP_CLASSES), ("slope", C.c_double), ("gated", C.c_void_p), ("elev_classes", C.c_uint32),
+        ("quantum", C.c_double), ("elev_sum", C.c_void_p), ("elev_cnt", C.c_void_p), ("elev_min", C.c_void_p), ("elev_max", C.c_void_p),
+    ]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
 _SIGNATURES = {
@@ -96,6 +105,12 @@ _SIGNATURES = {
     "avl_ground_fill_views_logits": (_i, [C.POINTER(AvlGrid), C.POINTER(AvlGroundFill), _i, _vp, _vp, C.POINTER(AvlPointLogits), _i, _i,
                                           _vp, _vp, C.POINTER(AvlOcclusion), _vp]),
     "avl_occlusion_depth": (_i, [_vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _i, C.POINTER(AvlOcclusion), _vp]),
+    "avl_fused_frame_views_height": (_i, [C.POINTER(AvlGrid), _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _d, _i, _vp, _i, _i, _i, _i,
+                                          _vp, _vp, _vp, C.c_uint32, C.POINTER(AvlPointLogits), C.POINTER(AvlOcclusion),
+                                          C.POINTER(AvlHeight), _vp]),
+    "avl_point_heights": (_i, [_vp, _i, _i, _i64, _i64, _vp, C.POINTER(AvlHeight), _vp, _vp, _vp]),
+    "avl_elevation_mean": (_i, [_vp, _vp, _i64, _d, _vp, _vp]),
+    "avl_elevation_reset": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "avl_colorize_labels": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "avl_preprocess_image": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "avl_preprocess_image_area": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -203,6 +203,22 @@ def get_cfg_defaults():
     C.MAPPING.GROUND_FILL.CLASSES = ["road", "crosswalk", "lane", "sidewalk"]
     C.MAPPING.GROUND_FILL.WEIGHT = 1.0
     C.MAPPING.GROUND_FILL.MAX_TILT_DEG = 30.0
+    # build-specific: height-aware mapping, two independent options, both off by default (then every call runs what it ran before).
+    # HEIGHT_GATE: with a ground plane (SemanticMapping.set_ground_plane / plane_callback) a LiDAR point votes class i only while its
+    # height above the plane lies in [MIN_M[i] - s, MAX_M[i] + s], s = SLOPE x its forward distance (the rule: include/avl_hip.h,
+    # avl_height): a canopy point no longer votes into the road cell beneath it.  MIN_M / MAX_M: one number for every class, or one
+    # per entry of LABELS_NAMES (inf = unbounded).  ELEVATION: the z of the points that vote one of CLASSES is accumulated per cell
+    # in steps of QUANTUM_M (sum, count, minimum, maximum: SemanticMapping.elevation_layer / elevation_device).  The ground fill,
+    # the planar mode and update_map ignore both
+    C.MAPPING.HEIGHT_GATE = CfgNode()
+    C.MAPPING.HEIGHT_GATE.ENABLED = False
+    C.MAPPING.HEIGHT_GATE.MIN_M = -0.5
+    C.MAPPING.HEIGHT_GATE.MAX_M = [0.5, 0.5, 0.5, float("inf"), 0.5]   # road, crosswalk, lane, vegetation (unbounded), sidewalk
+    C.MAPPING.HEIGHT_GATE.SLOPE = 0.02                    # metres of extra tolerance per metre of forward distance
+    C.MAPPING.ELEVATION = CfgNode()
+    C.MAPPING.ELEVATION.ENABLED = False
+    C.MAPPING.ELEVATION.CLASSES = ["road", "crosswalk", "lane", "sidewalk"]
+    C.MAPPING.ELEVATION.QUANTUM_M = 0.001
     # build-specific: where the cloud of DEPTH_METHOD "points_map" comes from.  "topic" = /reduced_map (the reference: a node outside
     # the package crops the site's point map around the vehicle and republishes it); nothing below is touched.  "index" = the whole
     # point map is loaded once from PATH (a .npy array [N, 4] or [4, N]: x, y, z, intensity in the world frame; or

@@ -615,6 +615,177 @@ __global__ void __launch_bounds__(kBlock) k_views_vote(PtsView pv, ViewsParams v
     else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);                // fire and forget, as cast_vote_nolist
 }
 
+// ---------------------------------------------------------------- height-aware votes (avl_fused_frame_views_height and its kin)
+// grid_cell() projects the cloud onto z = 0: a point in a tree canopy votes "vegetation" into the road cell beneath it.  With the
+// ground plane in the grid's frame a point's height above the ground costs three products and three sums on values the lane holds
+// anyway; a class bit stays only while that height lies in the class's band, and the same z, summed per cell in integer quanta,
+// is the elevation of the drivable surface.  The rule is stated in full at struct avl_height in include/avl_hip.h.
+// avl_height in kernel-argument form
+struct HeightParams {
+    double plane[4];                                   // unit normal, c > 0, in the frame of the cloud as passed in
+    double min_m[AVL_MAX_MAP_CLASSES], max_m[AVL_MAX_MAP_CLASSES];
+    double slope, quantum;
+    int* gated;                                        // [n_views] votes the gate withheld, or NULL
+    unsigned long long* elev_sum;                      // [Hm * Wm] sum of q (two's complement of an int64), NULL = no layer
+    int *elev_cnt, *elev_min, *elev_max;
+    unsigned elev_classes;
+    int gate;
+};
+
+// rule 1: three products, three sums, each rounded on its own
+__device__ __forceinline__ double point_height(const HeightParams& hp, double x, double y, double z) {
+    double t = hp.plane[0] * x;
+    double u = hp.plane[1] * y;
+    t = t + u;
+    u = hp.plane[2] * z;
+    t = t + u;
+    return t + hp.plane[3];
+}
+
+// rule 3: class bit i of `b` stays iff min_m[i] - s <= h <= max_m[i] + s, its bonus bit with it.  The bounds are read from the
+// by-value kernel argument with a wave-uniform index, as vote_from_rg reads GridParams::colors.
+__device__ __forceinline__ unsigned gate_vote(const HeightParams& hp, int C, unsigned b, double h, double s) {
+    unsigned keep = 0;
+    for (int i = 0; i < C; ++i) {
+        const double lo = hp.min_m[i] - s, hi = hp.max_m[i] + s;
+        if (lo <= h && h <= hi) keep |= 1u << i;                           // a NaN h fails both
+    }
+    return b & (keep | (keep << 16));
+}
+
+// rule 5: one point's z into its cell of the layer.  Integer atomics only.
+__device__ __forceinline__ void elevate(const HeightParams& hp, int cell, double z) {
+    const double r = __builtin_rint(z / hp.quantum);                       // IEEE division, then round half to even
+    if (!(r >= -2147483648.0 && r <= 2147483647.0)) return;
+    const int q = (int)r;
+    atomicAdd(&hp.elev_sum[cell], (unsigned long long)(long long)q);
+    atomicAdd(&hp.elev_cnt[cell], 1);
+    atomicMin(&hp.elev_min[cell], q);
+    atomicMax(&hp.elev_max[cell], q);
+}
+
+// k_fused_vote with the height rule behind pixel_vote.  Kernels of their own, so that the plain and OCCL instantiations above keep
+// their code; the occlusion test is a wave-uniform run-time branch here (oc.depth), as are the gate and the layer.
+template <int SRC, int MODE>
+__global__ void __launch_bounds__(kBlock) k_fused_vote_height(PtsView pv, ProjParams pp, GridParams g,
+                                                              const unsigned char* __restrict__ src, int src_w, int src_h, LogitsParams lp,
+                                                              LutParams lut, unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                              int* __restrict__ counter, int list_cap, OcclParams oc, HeightParams hp) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned vote = 0;
+    bool culled = false, abstains = false, gated = false;
+    if (k < pv.n) {
+        double x, y, z, it, v0, v1, v2, v3, p2;
+        load_point(pv, k, x, y, z, it);
+        int ix, iy;
+        const bool positive = to_camera(pp.T, pp.has_T, pp.range_max, x, y, z, v0, v1, v2, v3);
+        if (positive && project_view(pp.P, v0, v1, v2, v3, pp.img_w, pp.img_h, ix, iy, p2)) {
+            if (oc.depth) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, 0, ix, iy, bits);
+            }
+            if (!culled) cell = grid_cell(g, x, y, z);
+            if (cell >= 0) {
+                vote = pixel_vote<SRC>(g, lut, lp, src, lp.logits[0], src_w, src_h, pp.img_w, pp.img_h, ix, iy, it, abstains);
+                if (hp.gate && vote != 0u) {
+                    vote = gate_vote(hp, g.C, vote, point_height(hp, x, y, z), hp.slope * v0);
+                    gated = vote == 0u;
+                }
+                if (hp.elev_sum && (vote & hp.elev_classes)) elevate(hp, cell, z);
+            }
+        }
+    }
+    if (oc.depth) count_culled(oc.culled, 0, culled);
+    if (SRC == kSrcLogits) count_culled(lp.abstained, 0, abstains);
+    if (hp.gate) count_culled(hp.gated, 0, gated);
+    if (MODE == 0) cast_vote(cell_mask, touched, counter, cell, vote);
+    else if (MODE == 1) cast_vote_nolist(cell_mask, cell, vote);
+    else if (MODE == 2) cast_vote_byte(cell_mask, cell, vote, g.C, g.bonus_classes);
+    else cast_vote_byte_lists(cell_mask, touched, counter, list_cap, cell, vote, g.C, g.bonus_classes);
+}
+
+// k_views_vote with the height rule: the height and the slack once per point, the per-class comparison per view; the point enters
+// the layer once, with the union of the views' surviving class bits.  Every lane runs the loop in full (the ballots of the counts).
+template <int SRC, int LISTS>
+__global__ void __launch_bounds__(kBlock) k_views_vote_height(PtsView pv, ViewsParams vp, GridParams g, int src_w, int src_h, LogitsParams lp,
+                                                              LutParams lut, unsigned* __restrict__ cell_mask, int* __restrict__ touched,
+                                                              int* __restrict__ counter, int list_cap, OcclParams oc, HeightParams hp) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    int cell = -1;
+    unsigned word = 0, seen = 0;
+    bool positive = false;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 1.0, it = 0.0, z = 0.0, h = 0.0, slack = 0.0;
+    if (k < pv.n) {
+        double x, y;
+        load_point(pv, k, x, y, z, it);
+        positive = to_camera(vp.T, vp.has_T, vp.range_max, x, y, z, v0, v1, v2, v3);
+        if (positive) cell = grid_cell(g, x, y, z);
+        if (hp.gate && cell >= 0) {
+            h = point_height(hp, x, y, z);
+            slack = hp.slope * v0;
+        }
+    }
+    const bool candidate = positive && (oc.depth != nullptr || cell >= 0);
+    for (int v = 0; v < vp.n_views; ++v) {
+        bool culled = false, abstains = false, gated = false;
+        int ix, iy;
+        double p2;
+        if (candidate && project_view(vp.P[v], v0, v1, v2, v3, vp.img_w, vp.img_h, ix, iy, p2)) {
+            if (oc.depth) {
+                unsigned bits;
+                culled = depth_key(p2, bits) && occl_culled(oc, v, ix, iy, bits);
+            }
+            if (!culled && cell >= 0) {
+                unsigned vote = pixel_vote<SRC>(g, lut, lp, vp.src[v], lp.logits[v], src_w, src_h, vp.img_w, vp.img_h, ix, iy, it, abstains);
+                if (hp.gate && vote != 0u) {
+                    vote = gate_vote(hp, g.C, vote, h, slack);
+                    gated = vote == 0u;
+                }
+                seen |= vote;
+                word |= encode_vote_byte(vote, g.C, g.bonus_classes) << (8 * v);
+            }
+        }
+        if (oc.depth) count_culled(oc.culled, v, culled);
+        if (SRC == kSrcLogits) count_culled(lp.abstained, v, abstains);
+        if (hp.gate) count_culled(hp.gated, v, gated);
+    }
+    if (hp.elev_sum && (seen & hp.elev_classes)) elevate(hp, cell, z);         // seen != 0 only with a cell
+    if (LISTS) cast_vote_word_lists(cell_mask, touched, counter, list_cap, cell, word);
+    else if (cell >= 0 && word != 0u) atomicOr(&cell_mask[cell], word);
+}
+
+// Rules 1 and 2 alone, for every point of a cloud, candidate or not: h and the slack; both NaN for a non-finite coordinate.
+__global__ void __launch_bounds__(kBlock) k_point_heights(PtsView pv, ProjParams pp, HeightParams hp, double* __restrict__ h,
+                                                          double* __restrict__ s) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= pv.n) return;
+    double x, y, z, it, v0, v1, v2, v3;
+    load_point(pv, k, x, y, z, it);
+    to_camera(pp.T, pp.has_T, pp.range_max, x, y, z, v0, v1, v2, v3);
+    const bool finite = __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+    h[k] = finite ? point_height(hp, x, y, z) : __builtin_nan("");
+    s[k] = finite ? hp.slope * v0 : __builtin_nan("");
+}
+
+__global__ void __launch_bounds__(kBlock) k_elevation_mean(const long long* __restrict__ sum, const int* __restrict__ cnt, long long ncell,
+                                                           double quantum, float* __restrict__ out) {
+    const long long c = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= ncell) return;
+    const int n = cnt[c];
+    out[c] = n == 0 ? __builtin_nanf("") : (float)(((double)sum[c] / (double)n) * quantum);
+}
+
+__global__ void __launch_bounds__(kBlock) k_elevation_reset(long long* __restrict__ sum, int* __restrict__ cnt, int* __restrict__ qmin,
+                                                            int* __restrict__ qmax, long long ncell) {
+    const long long c = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= ncell) return;
+    sum[c] = 0;
+    cnt[c] = 0;
+    qmin[c] = INT_MAX;
+    qmax[c] = INT_MIN;
+}
+
 // Depth pass, one view or several: one read of the cloud, T and the range test once per point, one atomicMin per candidate and
 // view (no return value: nothing waits for it).  Off-grid points take part: an off-grid wall hides what is behind it.
 __global__ void __launch_bounds__(kBlock) k_occl_depth(PtsView pv, ViewsParams vp, OcclParams oc) {
@@ -1531,6 +1702,52 @@ int logits_source(VoteSource& src, const avl_point_logits* pl, int n_views) {
     return AVL_OK;
 }
 
+// ---- height: an avl_height validated (host only) and in kernel-argument form.  `g` NULL (avl_point_heights): the plane and the
+// slope alone, whatever `gate` says; else the gate's fields when it is on, and the layer's for a grid of g's size.
+int height_plane_fill(HeightParams& hp, const avl_height* ht) {
+    for (int k = 0; k < 4; ++k) AVL_REQUIRE(std::isfinite(ht->plane[k]), "height plane coefficient %d = %g", k, ht->plane[k]);
+    AVL_REQUIRE(ht->plane[2] > 0.0, "height plane with c = %g (the normal must point up: c > 0)", ht->plane[2]);
+    AVL_REQUIRE(ht->slope >= 0.0 && std::isfinite(ht->slope), "height slope = %g (finite, >= 0)", ht->slope);   // a NaN fails the comparison too
+    memcpy(hp.plane, ht->plane, sizeof(hp.plane));
+    hp.slope = ht->slope;
+    return AVL_OK;
+}
+int height_fill(HeightParams& hp, const avl_height* ht, const avl_grid* g) {
+    AVL_REQUIRE(ht, "avl_height is NULL");
+    memset(&hp, 0, sizeof(hp));
+    int rc;
+    if (!g) return height_plane_fill(hp, ht);
+    AVL_REQUIRE(ht->gate == 0 || ht->gate == 1, "height gate = %d (0 or 1)", ht->gate);
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(ht->gated) & 3) == 0, "height gated counts are not 4-byte aligned");
+    if (ht->gate) {
+        if ((rc = height_plane_fill(hp, ht))) return rc;
+        for (int i = 0; i < g->C; ++i) {
+            AVL_REQUIRE(ht->min_m[i] == ht->min_m[i] && ht->max_m[i] == ht->max_m[i], "height bound of class %d is a NaN", i);
+            AVL_REQUIRE(ht->min_m[i] <= ht->max_m[i], "height bounds of class %d: min %g > max %g", i, ht->min_m[i], ht->max_m[i]);
+            hp.min_m[i] = ht->min_m[i];
+            hp.max_m[i] = ht->max_m[i];
+        }
+        hp.gate = 1;
+        hp.gated = ht->gated;
+    }
+    const int ptrs = (ht->elev_sum != nullptr) + (ht->elev_cnt != nullptr) + (ht->elev_min != nullptr) + (ht->elev_max != nullptr);
+    AVL_REQUIRE(ptrs == 0 || ptrs == 4, "elevation layer with %d of its 4 arrays", ptrs);
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(ht->elev_sum) & 7) == 0, "elevation sum is not 8-byte aligned");
+    AVL_REQUIRE(((reinterpret_cast<uintptr_t>(ht->elev_cnt) | reinterpret_cast<uintptr_t>(ht->elev_min) |
+                  reinterpret_cast<uintptr_t>(ht->elev_max)) & 3) == 0, "elevation count, minimum or maximum is not 4-byte aligned");
+    if (ptrs == 4 || ht->elev_classes != 0u) {
+        AVL_REQUIRE(ht->quantum > 0.0 && std::isfinite(ht->quantum), "elevation quantum = %g (finite, > 0)", ht->quantum);
+        AVL_REQUIRE(!(ht->elev_classes >> g->C), "elev_classes has bits beyond C");
+    }
+    if (ptrs == 4 && ht->elev_classes != 0u) {
+        hp.elev_sum = reinterpret_cast<unsigned long long*>(ht->elev_sum);
+        hp.elev_cnt = ht->elev_cnt; hp.elev_min = ht->elev_min; hp.elev_max = ht->elev_max;
+        hp.elev_classes = ht->elev_classes;
+        hp.quantum = ht->quantum;
+    }
+    return AVL_OK;
+}
+
 // ---- the vote.  A runtime value in [0, N) as a compile-time one: f(std::integral_constant<int, v>()); the template arguments of
 // the two vote kernels go through here, as the map's element type goes through launch_map_typed.
 template <int N, typename F>
@@ -1572,6 +1789,34 @@ int launch_views_vote(const FrameArgs& f, const ViewsParams& vp, const VoteSourc
     return AVL_OK;
 }
 
+// the height forms of the two launches above: one kernel per SRC and MODE / LISTS, the occlusion test a run-time branch on oc.depth
+int launch_fused_vote_height(const FrameArgs& f, const VoteSource& src, int mode, const OcclParams& oc, const HeightParams& hp,
+                             const avl_grid* g, int list_cap, hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+    const uint8_t* bytes = src.logits ? nullptr : src.bytes[0];
+    with_constant<3>(src.logits ? kSrcLogits : src.kind, [&](auto S) {
+        with_constant<4>(mode, [&](auto M) {
+            hipLaunchKernelGGL((k_fused_vote_height<decltype(S)::value, decltype(M)::value>), grid, block, 0, s, f.pv, f.pp, f.gp, bytes,
+                               src.w, src.h, src.lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc, hp);
+        });
+    });
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+int launch_views_vote_height(const FrameArgs& f, const ViewsParams& vp, const VoteSource& src, bool lists, const OcclParams& oc,
+                             const HeightParams& hp, const avl_grid* g, int list_cap, hipStream_t s) {
+    const dim3 grid((f.pv.n + kBlock - 1) / kBlock), block(kBlock);
+    with_constant<3>(src.logits ? kSrcLogits : src.kind, [&](auto S) {
+        with_constant<2>(lists, [&](auto L) {
+            hipLaunchKernelGGL((k_views_vote_height<decltype(S)::value, decltype(L)::value>), grid, block, 0, s, f.pv, vp, f.gp, src.w,
+                               src.h, src.lp, f.lut, g->cell_mask, g->touched, g->counter, list_cap, oc, hp);
+        });
+    });
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
 // ---- the apply.  What follows the vote kernel of path `mode` (avl_fused_frame_path) for a cloud of n points
 int apply_frame(const avl_grid* g, const double* cm_host, uint32_t bonus_classes, int mode, int n, hipStream_t s) {
     if (mode == 3) return lists_applied(g, launch_apply_lists(g, cm_host, bonus_classes, n, s), s);
@@ -1603,7 +1848,7 @@ int apply_views(const avl_grid* g, const double* cm_host, uint32_t bonus_classes
 // ---- the frame.  What every fused frame does once fill_frame has accepted it, whatever its source and arity: the resets, the
 // path from n, with `occl` the depth pass, the vote, the apply.  The apply and sweep kernels know nothing of source or culling.
 int run_frame(const avl_grid* g, const FrameArgs& f, int n_views, const double* P_host, const VoteSource& src, const double* cm_host,
-              uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+              uint32_t bonus_classes, const avl_occlusion* occl, const HeightParams* hp, void* stream) {
     const int n = f.pv.n;
     OcclParams oc;
     int rc;
@@ -1611,6 +1856,7 @@ int run_frame(const avl_grid* g, const FrameArgs& f, int n_views, const double* 
     if (occl && (rc = occl_fill(oc, occl, f.pp.img_w, f.pp.img_h, n_views))) return rc;
     hipStream_t s = avl::as_stream(stream);
     if (src.logits && (rc = logits_reset(src.lp, n_views, s))) return rc;
+    if (hp && hp->gated) AVL_HIP_CHECK(hipMemsetAsync(hp->gated, 0, sizeof(int) * n_views, s));
     if (n == 0) return occl ? occl_reset(oc, n_views, false, s) : AVL_OK;         // an empty cloud resets the counts, not the depth buffer
     const int path = n_views == 1 ? avl_fused_frame_path(g, n, bonus_classes) : (lists_fit(g, n) ? 4 : 5);
     if (path < 0) return path;
@@ -1623,40 +1869,49 @@ int run_frame(const avl_grid* g, const FrameArgs& f, int n_views, const double* 
     if (path == 0) AVL_HIP_CHECK(hipMemsetAsync(g->counter, 0, 16, s));      // only the single touched-list path counts there
     const ListGeom lg = list_geom(n);
     if (n_views == 1) {
-        if ((rc = launch_fused_vote(f, src, path, occl != nullptr, oc, g, lg.cap, s))) return rc;
+        if ((rc = hp ? launch_fused_vote_height(f, src, path, oc, *hp, g, lg.cap, s)
+                     : launch_fused_vote(f, src, path, occl != nullptr, oc, g, lg.cap, s)))
+            return rc;
         return apply_frame(g, cm_host, bonus_classes, path, n, s);
     }
-    if ((rc = launch_views_vote(f, vp, src, path == 4, occl != nullptr, oc, g, lg.cap, s))) return rc;
+    if ((rc = hp ? launch_views_vote_height(f, vp, src, path == 4, oc, *hp, g, lg.cap, s)
+                 : launch_views_vote(f, vp, src, path == 4, occl != nullptr, oc, g, lg.cap, s)))
+        return rc;
     return apply_views(g, cm_host, bonus_classes, path == 4, lg, s);
 }
 
 // one camera: avl_fused_frame, _occl (`occl`) and _logits (`src`)
 int fused_frame(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* P_host,
                 const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h, const uint32_t* lut_host,
-                const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream) {
+                const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes, const avl_occlusion* occl, void* stream,
+                const avl_height* ht = nullptr) {
     FrameArgs f;
+    HeightParams hp;
     int rc;
     if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
                          label_colors_host, cm_host, bonus_classes)))
         return rc;
-    return run_frame(g, f, 1, P_host, src, cm_host, bonus_classes, occl, stream);
+    if (ht && (rc = height_fill(hp, ht, g))) return rc;
+    return run_frame(g, f, 1, P_host, src, cm_host, bonus_classes, occl, ht ? &hp : nullptr, stream);
 }
 
 // several cameras: avl_fused_frame_views, _views_occl and _views_logits; one view is the single camera's frame
 int fused_frame_views(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, int n_views,
                       const double* P_host, const double* T_host, double range_max, const VoteSource& src, int img_w, int img_h,
                       const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host, uint32_t bonus_classes,
-                      const avl_occlusion* occl, void* stream) {
+                      const avl_occlusion* occl, void* stream, const avl_height* ht = nullptr) {
     if (n_views == 1)
         return fused_frame(g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
-                           label_colors_host, cm_host, bonus_classes, occl, stream);
+                           label_colors_host, cm_host, bonus_classes, occl, stream, ht);
     FrameArgs f;
+    HeightParams hp;
     int rc;
     if ((rc = fill_frame(f, g, pts, n, dtype, point_stride, comp_stride, P_host, T_host, range_max, src, img_w, img_h, lut_host,
                          label_colors_host, cm_host, bonus_classes)))
         return rc;
     if ((rc = views_bits_check(g, bonus_classes))) return rc;
-    return run_frame(g, f, n_views, P_host, src, cm_host, bonus_classes, occl, stream);
+    if (ht && (rc = height_fill(hp, ht, g))) return rc;
+    return run_frame(g, f, n_views, P_host, src, cm_host, bonus_classes, occl, ht ? &hp : nullptr, stream);
 }
 
 // ---- the ground fill: avl_ground_fill_views (bytes) and _logits.  Everything is refused before any GPU work; the window is clipped
@@ -1885,6 +2140,70 @@ extern "C" int avl_fused_frame_views_logits(const avl_grid* g, const void* pts, 
     if ((rc = logits_source(src, pl, n_views))) return rc;
     return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src, img_w, img_h, lut_host,
                              nullptr, cm_host, bonus_classes, occl, stream);
+}
+
+extern "C" int avl_fused_frame_views_height(const avl_grid* g, const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride,
+                                            int n_views, const double* P_host, const double* T_host, double range_max, int src_kind,
+                                            const uint8_t* const* src_host, int src_w, int src_h, int img_w, int img_h,
+                                            const uint32_t* lut_host, const uint8_t* label_colors_host, const double* cm_host,
+                                            uint32_t bonus_classes, const avl_point_logits* pl, const avl_occlusion* occl,
+                                            const avl_height* ht, void* stream) {
+    AVL_REQUIRE(ht, "avl_height is NULL");
+    VoteSource src;
+    int rc;
+    if (pl) {
+        if ((rc = logits_source(src, pl, n_views))) return rc;
+    } else {
+        if ((rc = views_check(n_views, src_host))) return rc;
+        src = bytes_source(src_kind, src_host, src_w, src_h);
+    }
+    return fused_frame_views(g, pts, n, dtype, point_stride, comp_stride, n_views, P_host, T_host, range_max, src, img_w, img_h, lut_host,
+                             pl ? nullptr : label_colors_host, cm_host, bonus_classes, occl, stream, ht);
+}
+
+extern "C" int avl_point_heights(const void* pts, int n, int dtype, int64_t point_stride, int64_t comp_stride, const double* T_host,
+                                 const avl_height* ht, double* h, double* s, void* stream) {
+    PtsView pv;
+    ProjParams pp;
+    HeightParams hp;
+    int rc;
+    if ((rc = fill_pts(pv, pts, n, dtype, point_stride, comp_stride))) return rc;
+    if ((rc = height_fill(hp, ht, nullptr))) return rc;
+    AVL_REQUIRE(n == 0 || (h && s), "h or s is NULL");
+    AVL_REQUIRE(((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(s)) & 7) == 0, "h or s is not 8-byte aligned");
+    if (n == 0) return AVL_OK;
+    memset(&pp, 0, sizeof(pp));
+    pp.has_T = T_host ? 1 : 0;
+    if (T_host) memcpy(pp.T, T_host, sizeof(pp.T));
+    hipLaunchKernelGGL(k_point_heights, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, avl::as_stream(stream), pv, pp, hp, h, s);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+extern "C" int avl_elevation_mean(const int64_t* sum, const int32_t* cnt, int64_t ncell, double quantum, float* out, void* stream) {
+    AVL_REQUIRE(ncell >= 0 && ncell <= 0x7fffffffLL, "ncell = %lld", (long long)ncell);
+    AVL_REQUIRE(quantum > 0.0 && std::isfinite(quantum), "elevation quantum = %g (finite, > 0)", quantum);
+    AVL_REQUIRE(ncell == 0 || (sum && cnt && out), "NULL buffer");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(sum) & 7) == 0, "elevation sum is not 8-byte aligned");
+    AVL_REQUIRE(((reinterpret_cast<uintptr_t>(cnt) | reinterpret_cast<uintptr_t>(out)) & 3) == 0, "cnt or out is not 4-byte aligned");
+    if (ncell == 0) return AVL_OK;
+    hipLaunchKernelGGL(k_elevation_mean, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, avl::as_stream(stream),
+                       reinterpret_cast<const long long*>(sum), cnt, (long long)ncell, quantum, out);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+extern "C" int avl_elevation_reset(int64_t* sum, int32_t* cnt, int32_t* qmin, int32_t* qmax, int64_t ncell, void* stream) {
+    AVL_REQUIRE(ncell >= 0 && ncell <= 0x7fffffffLL, "ncell = %lld", (long long)ncell);
+    AVL_REQUIRE(ncell == 0 || (sum && cnt && qmin && qmax), "NULL buffer");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(sum) & 7) == 0, "elevation sum is not 8-byte aligned");
+    AVL_REQUIRE(((reinterpret_cast<uintptr_t>(cnt) | reinterpret_cast<uintptr_t>(qmin) | reinterpret_cast<uintptr_t>(qmax)) & 3) == 0,
+                "elevation count, minimum or maximum is not 4-byte aligned");
+    if (ncell == 0) return AVL_OK;
+    hipLaunchKernelGGL(k_elevation_reset, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, avl::as_stream(stream),
+                       reinterpret_cast<long long*>(sum), cnt, qmin, qmax, (long long)ncell);
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
 }
 
 extern "C" int64_t avl_occlusion_depth_words(int img_w, int img_h, int cell_px, int n_views) {

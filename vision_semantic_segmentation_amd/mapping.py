@@ -37,6 +37,10 @@ What differs from the reference, by design:
     /reduced_map (mapping.py:61-62): ``load_points_map()`` puts the whole map on the device, sorted into ground tiles, and every frame
     takes its cloud from ``reduced_map_device()``, one kernel that copies the tiles that can hold a voting point (points_map.py).  The
     grid ends bit-equal to a frame on the whole map.  Off ("topic") by default.
+  * with MAPPING.HEIGHT_GATE.ENABLED and a ground plane, a point votes class i only while its height above the plane lies in that
+    class's band (the rule at struct avl_height in include/avl_hip.h; ``last_gated``, ``point_heights_device()``): the reference
+    projects the cloud onto z = 0, so a canopy point votes into the road cell beneath it.  With MAPPING.ELEVATION.ENABLED the z of
+    the points that vote a ground class is accumulated per cell (``elevation_device()``, ``elevation_layer()``).  Both off by default.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -294,6 +298,14 @@ class SemanticMapping(object):
         self.ground_fill_cfg = getattr(cfg.MAPPING, "GROUND_FILL", None)
         self.ground_plane = None               # float64 [4]: (a, b, c, d) in the velodyne frame (set_ground_plane, plane_callback)
         self.last_filled = None                # int32 CUDA tensor [V]: cells that took a vote per view in the last ground fill (no sync)
+
+        # height-aware mapping (MAPPING.HEIGHT_GATE, MAPPING.ELEVATION); both off by default: then nothing below is touched
+        self.height_gate_cfg = getattr(cfg.MAPPING, "HEIGHT_GATE", None)
+        self.elevation_cfg = getattr(cfg.MAPPING, "ELEVATION", None)
+        self.last_gated = None                 # int32 CUDA tensor [V]: votes the height gate withheld per view in the last gated call (no sync)
+        self._height_bounds = self._parse_height_gate() if self.height_gate_enabled() else None    # (min_m [C], max_m [C], slope)
+        self._elevation_par = self._parse_elevation() if self.elevation_enabled() else None        # (class mask, quantum)
+        self._elevation = None                 # (sum int64, cnt, min, max int32) CUDA [Hm, Wm]: allocated on first use
 
         # device-side caches
         self._scratch = None
@@ -609,7 +621,7 @@ class SemanticMapping(object):
                 self.input_list.append({"pcd": np.array(_to_numpy(pcd)), "pcd_frame_id": frame_id,
                                         "semantic_image": np.array(_to_numpy(semantic_image)), "pose": pose})
             img = self._as_device_u8(semantic_image) if img is None else img
-            self.frame_device(pcd, frame_id, img, pose, camera_calibration, src_kind="rgb")
+            self.frame_device(pcd, frame_id, img, pose, camera_calibration, src_kind="rgb", **self._gate_if_plane())
             self._ground_fill_step([img], pose, [camera_calibration], pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
@@ -644,7 +656,7 @@ class SemanticMapping(object):
                     self.input_list.append({"pcd": np.array(_to_numpy(pcd)), "pcd_frame_id": frame_id,
                                             "semantic_image": np.array(_to_numpy(img)), "pose": pose})
             images = [self._as_device_u8(img) for img in semantic_images] if images is None else images
-            self.frame_device_views(pcd, frame_id, images, pose, cameras, src_kind="rgb")
+            self.frame_device_views(pcd, frame_id, images, pose, cameras, src_kind="rgb", **self._gate_if_plane())
             self._ground_fill_step(images, pose, cameras, pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
@@ -840,22 +852,33 @@ class SemanticMapping(object):
         return (state, keys) if return_keys else state
 
     def frame_device(self, pcd, pcd_frame_id, semantic, pose, camera_calibration, src_kind="rgb",
-                     image_size=None, net_palette=PALETTE_19, stream=None, _culled=None, net_size=None, _abstained=None):
+                     image_size=None, net_palette=PALETTE_19, stream=None, _culled=None, net_size=None, _abstained=None, _gate=None,
+                     _gated=None):
         """Fused frame (avl_fused_frame; avl_fused_frame_occl with MAPPING.OCCLUSION.ENABLED).  ``pcd``: NumPy/torch [4,N]
         float64|float32 (SoA, the reference layout) or [N,4] float32 (AoS); ``semantic``: CUDA uint8 tensor, either the colour
         image [H,W,3] (src_kind="rgb") or a class-id map [h,w] (src_kind="classmap", sampled as the
         nearest-upscaled image of size ``image_size`` = (H, W)).  With src_kind="logits" ``semantic`` is a plan's fp32 logits
         [h',w',K] (SegNet.logits): every point takes the arg-max of the logits interpolated to ``net_size`` = (h, w) (the network's
         input; ``image_size`` by default) at its pixel, and abstains when the top-1 minus top-2 margin is below ``self.min_margin``
-        (MAPPING.CONFIDENCE.MIN_MARGIN); ``last_abstained`` receives the count (avl_fused_frame_logits)."""
+        (MAPPING.CONFIDENCE.MIN_MARGIN); ``last_abstained`` receives the count (avl_fused_frame_logits).  With
+        MAPPING.HEIGHT_GATE.ENABLED or MAPPING.ELEVATION.ENABLED every source goes through avl_fused_frame_views_height: the gate
+        needs a ground plane (set_ground_plane; RuntimeError without one) and ``last_gated`` receives its count."""
         if src_kind == "logits":
             return self._frame_device_logits(pcd, pcd_frame_id, logits_views(semantic)[0], pose, [camera_calibration], image_size, net_size,
-                                             net_palette, stream, _culled, _abstained)
+                                             net_palette, stream, _culled, _abstained, _gate, _gated)
         assert semantic.dtype == torch.uint8
         sh, sw, ih, iw, kind, lut = self._semantic_source(semantic.shape, src_kind, image_size, net_palette)
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, camera_calibration.P, stream)
         semantic = semantic.contiguous()
-        if self.occlusion_enabled():
+        if self._height_routed(_gate):
+            occ = C.byref(self._occlusion(1, ih, iw, _culled)) if self.occlusion_enabled() else None
+            ht = self._height(1, pose, pcd_frame_id, _gate, _gated)
+            src = (C.c_void_p * 1)(semantic.data_ptr())
+            rc = _lib.lib().avl_fused_frame_views_height(C.byref(gs), *view, 1, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
+                                                         self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), None, occ,
+                                                         C.byref(ht), s)
+            _lib.check(rc, "avl_fused_frame_views_height")
+        elif self.occlusion_enabled():
             occ = self._occlusion(1, ih, iw, _culled)
             rc = _lib.lib().avl_fused_frame_occl(C.byref(gs), *view, P, T, float(self.pcd_range_max), kind, _ptr(semantic), sw, sh, iw, ih, lut,
                                                  self._colors_host(), _dbl(self.confusion_matrix), self._bonus_classes(), C.byref(occ), s)
@@ -868,20 +891,23 @@ class SemanticMapping(object):
         self.frames_mapped += 1
 
     def frame_device_views(self, pcd, pcd_frame_id, semantics, pose, cameras, src_kind="classmap", image_size=None,
-                           net_palette=PALETTE_19, stream=None, net_size=None):
+                           net_palette=PALETTE_19, stream=None, net_size=None, _gate=None):
         """V cameras on one cloud in one fused pass (avl_fused_frame_views): the grid ends bit-identical to V frame_device calls
         in view order.  ``semantics``: a uint8 CUDA tensor [V,h,w] of class maps (a batched plan's label buffer goes in as it is)
         or [V,H,W,3] of colour images (src_kind="rgb"), or a list of V such tensors of one size; with src_kind="logits" an fp32
         CUDA tensor [V,h',w',K] (a batched plan's logits) or a list of V tensors [h',w',K], ``net_size`` as in frame_device;
         ``cameras``: V calibrations.  More than AVL_MAX_VIEWS views, or more vote bits than a view's byte of the mask holds
-        (classes + lane classes > 8), are mapped by sequential frame_device calls."""
+        (classes + lane classes > 8), are mapped by sequential frame_device calls.  With MAPPING.HEIGHT_GATE.ENABLED or
+        MAPPING.ELEVATION.ENABLED the pass is avl_fused_frame_views_height; the sequential fall-back then gates per call
+        (``last_gated`` still holds one count per view) and lets the elevation layer take a point once per CALL, so a point that
+        several of the fall-back's views see enters the layer once per such view, not once per trigger."""
         cameras = list(cameras)
         V = len(cameras)
         if V < 1:
             raise ValueError("frame_device_views needs at least one camera")
         if src_kind == "logits":
             return self._frame_device_logits(pcd, pcd_frame_id, logits_views(semantics, V)[0], pose, cameras, image_size, net_size,
-                                             net_palette, stream)
+                                             net_palette, stream, _gate=_gate)
         want_dim = 3 if src_kind == "rgb" else 2
         if isinstance(semantics, torch.Tensor):
             if semantics.dim() != want_dim + 1 or int(semantics.shape[0]) != V:
@@ -898,18 +924,29 @@ class SemanticMapping(object):
         sh, sw, ih, iw, kind, lut = self._semantic_source(shape, src_kind, image_size, net_palette)
         bonus = self._bonus_classes()
         occlusion = self.occlusion_enabled()
+        gating = self._height_routed(_gate) and self._gate_on(_gate)
         if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
             culled = torch.zeros(V, dtype=torch.int32, device=self.device) if occlusion else None
+            gated = torch.zeros(V, dtype=torch.int32, device=self.device) if gating else None
             for v, (t, cam) in enumerate(zip(views, cameras)):
                 self.frame_device(pcd, pcd_frame_id, t, pose, cam, src_kind=src_kind, image_size=image_size, net_palette=net_palette,
-                                  stream=stream, _culled=(culled, v) if occlusion else None)
+                                  stream=stream, _culled=(culled, v) if occlusion else None, _gate=_gate,
+                                  _gated=(gated, v) if gating else None)
             if occlusion:
                 self.last_culled = culled
+            if gating:
+                self.last_gated = gated
             return
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]), stream)
         views = [t.contiguous() for t in views]
         src = (C.c_void_p * V)(*[t.data_ptr() for t in views])
-        if occlusion:
+        if self._height_routed(_gate):
+            occ = C.byref(self._occlusion(V, ih, iw)) if occlusion else None
+            ht = self._height(V, pose, pcd_frame_id, _gate)
+            rc = _lib.lib().avl_fused_frame_views_height(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
+                                                         self._colors_host(), _dbl(self.confusion_matrix), bonus, None, occ, C.byref(ht), s)
+            _lib.check(rc, "avl_fused_frame_views_height")
+        elif occlusion:
             occ = self._occlusion(V, ih, iw)
             rc = _lib.lib().avl_fused_frame_views_occl(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), kind, src, sw, sh, iw, ih, lut,
                                                        self._colors_host(), _dbl(self.confusion_matrix), bonus, C.byref(occ), s)
@@ -940,20 +977,24 @@ class SemanticMapping(object):
         return pl, ih, iw
 
     def _frame_device_logits(self, pcd, pcd_frame_id, views, pose, cameras, image_size, net_size, net_palette, stream,
-                             _culled=None, _abstained=None):
+                             _culled=None, _abstained=None, _gate=None, _gated=None):
         """frame_device / frame_device_views for src_kind="logits": ``views`` are V checked logits tensors (logits_views)."""
         V = len(cameras)
         bonus = self._bonus_classes()
         occlusion = self.occlusion_enabled()
+        gating = self._height_routed(_gate) and self._gate_on(_gate)
         if V > _lib.AVL_MAX_VIEWS or (V > 1 and self.map_depth + bin(bonus).count("1") > 8):
             abstained = torch.zeros(V, dtype=torch.int32, device=self.device)
             culled = torch.zeros(V, dtype=torch.int32, device=self.device) if occlusion else None
+            gated = torch.zeros(V, dtype=torch.int32, device=self.device) if gating else None
             for v, (t, cam) in enumerate(zip(views, cameras)):
                 self._frame_device_logits(pcd, pcd_frame_id, [t], pose, [cam], image_size, net_size, net_palette, stream,
-                                          (culled, v) if occlusion else None, (abstained, v))
+                                          (culled, v) if occlusion else None, (abstained, v), _gate, (gated, v) if gating else None)
             self.last_abstained = abstained
             if occlusion:
                 self.last_culled = culled
+            if gating:
+                self.last_gated = gated
             return
         if _abstained is None:
             if self.last_abstained is None or int(self.last_abstained.numel()) != V:
@@ -963,7 +1004,12 @@ class SemanticMapping(object):
         view, T, gs, P, s = self._frame_args(pcd, pcd_frame_id, pose, np.stack([np.asarray(cam.P, dtype=np.float64) for cam in cameras]), stream)
         occ = C.byref(self._occlusion(V, ih, iw, _culled)) if occlusion else None
         lut, cm = self._lut_host(net_palette), _dbl(self.confusion_matrix)
-        if V == 1:
+        if self._height_routed(_gate):
+            ht = self._height(V, pose, pcd_frame_id, _gate, _gated)
+            rc = _lib.lib().avl_fused_frame_views_height(C.byref(gs), *view, V, P, T, float(self.pcd_range_max), 0, None, 0, 0, iw, ih, lut, None,
+                                                         cm, bonus, C.byref(pl), occ, C.byref(ht), s)
+            _lib.check(rc, "avl_fused_frame_views_height")
+        elif V == 1:
             rc = _lib.lib().avl_fused_frame_logits(C.byref(gs), *view, P, T, float(self.pcd_range_max), C.byref(pl), iw, ih, lut, cm, bonus, occ, s)
             _lib.check(rc, "avl_fused_frame_logits")
         else:
@@ -1037,7 +1083,7 @@ class SemanticMapping(object):
         depth buffer is filled from it first (avl_occlusion_depth, the cloud's own range) and a cell behind a real point is culled.
         Sets ``last_filled`` and, as the frame calls do, ``last_abstained`` and ``last_culled``.  ValueError for a plane whose normal
         in the grid's frame is more than GROUND_FILL.MAX_TILT_DEG from the z axis."""
-        from .ground_plane import plane_tilt_deg, plane_to_frame
+        from .ground_plane import plane_tilt_deg
         gf_cfg = self.ground_fill_cfg
         single = not isinstance(cameras, (list, tuple))
         cameras = [cameras] if single else list(cameras)
@@ -1051,8 +1097,7 @@ class SemanticMapping(object):
             raise RuntimeError("ground_fill_device needs a ground plane: none was given and set_ground_plane has not been called")
         if grid_frame_id is None:
             grid_frame_id = self.pcd_frame_id if self.pcd_frame_id is not None else "velodyne"
-        T_np = self._origin_to_velodyne(pose) if grid_frame_id != "velodyne" else None
-        plane_g = plane_to_frame(plane, T_np)
+        plane_g, T_np = self._plane_in_grid_frame(plane, pose, grid_frame_id)
         tilt = plane_tilt_deg(plane_g)
         if not tilt <= float(gf_cfg.MAX_TILT_DEG):                   # a NaN (zero normal) fails the comparison too
             raise ValueError("ground plane %r is tilted by %g degrees in the grid's frame (MAPPING.GROUND_FILL.MAX_TILT_DEG = %g)" % (
@@ -1119,6 +1164,150 @@ class SemanticMapping(object):
         if self.ground_fill_enabled() and self.ground_plane is not None:
             self.ground_fill_device(semantic_images, pose, cameras, grid_frame_id=pcd_frame_id, src_kind="rgb", pcd=pcd,
                                     pcd_frame_id=pcd_frame_id)
+
+    def _plane_in_grid_frame(self, plane, pose, grid_frame_id):
+        """-> (the velodyne-frame ``plane`` (set_ground_plane's forms) in the frame of a grid whose clouds are in ``grid_frame_id``,
+        float64 [4], not normalised; the 4 x 4 grid frame -> velodyne transform, None for a velodyne-frame grid).  Any frame but
+        "velodyne" needs the pose."""
+        from .ground_plane import plane_to_frame
+        T_np = self._origin_to_velodyne(pose) if grid_frame_id != "velodyne" else None
+        return plane_to_frame(plane, T_np), T_np
+
+    # ------------------------------------------------------------------ height-aware mapping (MAPPING.HEIGHT_GATE, MAPPING.ELEVATION)
+    def height_gate_enabled(self):
+        return self.height_gate_cfg is not None and bool(self.height_gate_cfg.ENABLED)
+
+    def elevation_enabled(self):
+        return self.elevation_cfg is not None and bool(self.elevation_cfg.ENABLED)
+
+    def _gate_on(self, _gate):
+        return self.height_gate_enabled() if _gate is None else bool(_gate)
+
+    def _height_routed(self, _gate):
+        """whether a frame call takes avl_fused_frame_views_height: either option enabled (``_gate`` False: this call does not gate)"""
+        return self._gate_on(_gate) or self.elevation_enabled()
+
+    def _gate_if_plane(self):
+        """what mapping() / mapping_views() add to their frame call: with the gate enabled and no plane set yet the frame is mapped
+        ungated (``_gate=False``) and ``last_gated`` stays None, as the ground fill waits for its plane; otherwise nothing"""
+        return {"_gate": False} if self.height_gate_enabled() and self.ground_plane is None else {}
+
+    def _per_label(self, value, what):
+        """a number for every class, or one per entry of LABELS_NAMES -> float64 [C]; ValueError for a wrong length, a NaN or a
+        value that is no number"""
+        n = len(self.label_names)
+        vals = [value] * n if not isinstance(value, (list, tuple, np.ndarray)) else list(value)
+        if len(vals) != n:
+            raise ValueError("%s has %d entries, LABELS_NAMES has %d: %r" % (what, len(vals), n, list(self.label_names)))
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+                raise ValueError("%s = %r (numbers, inf for no bound, never a NaN)" % (what, value))
+        return np.array(vals, dtype=np.float64)
+
+    def _parse_height_gate(self):
+        hc = self.height_gate_cfg
+        lo, hi = self._per_label(hc.MIN_M, "MAPPING.HEIGHT_GATE.MIN_M"), self._per_label(hc.MAX_M, "MAPPING.HEIGHT_GATE.MAX_M")
+        if (lo > hi).any():
+            raise ValueError("MAPPING.HEIGHT_GATE: MIN_M %r exceeds MAX_M %r" % (lo.tolist(), hi.tolist()))
+        slope = hc.SLOPE
+        if isinstance(slope, bool) or not isinstance(slope, (int, float, np.integer, np.floating)) or not 0.0 <= float(slope) < np.inf:
+            raise ValueError("MAPPING.HEIGHT_GATE.SLOPE = %r (a finite number >= 0)" % (slope,))
+        return lo, hi, float(slope)
+
+    def _parse_elevation(self):
+        ec = self.elevation_cfg
+        names = list(ec.CLASSES)
+        unknown = [n for n in names if n not in self.label_names]
+        if unknown:
+            raise ValueError("MAPPING.ELEVATION.CLASSES names %r, LABELS_NAMES has %r" % (unknown, list(self.label_names)))
+        q = ec.QUANTUM_M
+        if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 < float(q) < np.inf:
+            raise ValueError("MAPPING.ELEVATION.QUANTUM_M = %r (a finite number > 0)" % (q,))
+        return sum(1 << i for i, name in enumerate(self.label_names) if name in names), float(q)
+
+    def height_plane(self, pose, grid_frame_id, plane=None):
+        """The plane the height gate hands the kernel, float64 [4]: ``plane`` (set_ground_plane's forms, velodyne frame; None = the
+        plane last set) taken to the frame of a grid whose clouds are in ``grid_frame_id`` as ground_fill_device takes it, then
+        normalised in float64: n = sqrt((a * a + b * b) + c * c), each of the four divided by n, all four negated when c < 0.
+        RuntimeError without a plane; ValueError for one that is not finite or has c = 0 in the grid's frame."""
+        plane = self.ground_plane if plane is None else plane
+        if plane is None:
+            raise RuntimeError("the height gate needs a ground plane: none was given and set_ground_plane has not been called")
+        p = self._plane_in_grid_frame(plane, pose, grid_frame_id)[0]
+        if not np.isfinite(p).all() or p[2] == 0.0:
+            raise ValueError("ground plane %r in the grid's frame is not finite or is vertical" % (p.tolist(),))
+        p = p / np.sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2])
+        return -p if p[2] < 0.0 else p
+
+    def elevation_layer(self):
+        """The elevation layer, four CUDA tensors [Hm, Wm]: (sum int64, cnt int32, min int32, max int32) of q = rint(z / QUANTUM_M)
+        over the points that voted one of MAPPING.ELEVATION.CLASSES (rule 5 at struct avl_height); an empty cell holds (0, 0,
+        INT32_MAX, INT32_MIN).  Allocated, empty, on first use; the frames write into these very tensors."""
+        if self._elevation is None:
+            shape = (self.map_height, self.map_width)
+            self._elevation = (torch.empty(shape, dtype=torch.int64, device=self.device),) + tuple(
+                torch.empty(shape, dtype=torch.int32, device=self.device) for _ in range(3))
+            self.reset_elevation()
+        return self._elevation
+
+    def reset_elevation(self, stream=None):
+        """Every cell of the layer back to empty (avl_elevation_reset)."""
+        if self._elevation is None:
+            self.elevation_layer()             # allocates and comes back here
+            return
+        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+        rc = _lib.lib().avl_elevation_reset(*[_ptr(t) for t in self._elevation], self.map_height * self.map_width, s)
+        _lib.check(rc, "avl_elevation_reset")
+
+    def elevation_device(self, stream=None):
+        """The mean elevation per cell in metres, float32 CUDA [Hm, Wm]: (float)((sum / cnt) * QUANTUM_M) in float64, NaN for a cell
+        without a point (avl_elevation_mean)."""
+        q = (self._elevation_par or self._parse_elevation())[1]
+        esum, ecnt = self.elevation_layer()[:2]
+        out = torch.empty((self.map_height, self.map_width), dtype=torch.float32, device=self.device)
+        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+        rc = _lib.lib().avl_elevation_mean(_ptr(esum), _ptr(ecnt), self.map_height * self.map_width, q, _ptr(out), s)
+        _lib.check(rc, "avl_elevation_mean")
+        return out
+
+    def _height(self, V, pose, grid_frame_id, _gate=None, gated=None):
+        """struct avl_height for a frame call of V views on a cloud in ``grid_frame_id``: the gate's fields with the gate on for this
+        call, the layer's with MAPPING.ELEVATION.ENABLED.  ``gated``: (int32 CUDA tensor, first element) that receives the V counts;
+        None = a fresh-or-reused ``self.last_gated`` of V elements."""
+        ht = _lib.AvlHeight()
+        if self._gate_on(_gate):
+            lo, hi, slope = self._height_bounds or self._parse_height_gate()
+            ht.gate = 1
+            ht.plane[:] = [float(v) for v in self.height_plane(pose, grid_frame_id)]
+            ht.min_m[:len(lo)] = lo.tolist()
+            ht.max_m[:len(hi)] = hi.tolist()
+            ht.slope = slope
+            if gated is None:
+                if self.last_gated is None or int(self.last_gated.numel()) != V:
+                    self.last_gated = torch.zeros(V, dtype=torch.int32, device=self.device)
+                gated = (self.last_gated, 0)
+            ht.gated = gated[0].data_ptr() + 4 * int(gated[1])
+        if self.elevation_enabled():
+            ht.elev_classes, ht.quantum = self._elevation_par or self._parse_elevation()
+            ht.elev_sum, ht.elev_cnt, ht.elev_min, ht.elev_max = (t.data_ptr() for t in self.elevation_layer())
+        return ht
+
+    def point_heights_device(self, pcd, pcd_frame_id, pose, plane=None):
+        """Rules 1 and 2 of struct avl_height alone (avl_point_heights, MAPPING.HEIGHT_GATE.SLOPE whether ENABLED or not): for every
+        point of ``pcd``, candidate or not, its height h above ``plane`` (velodyne frame, None = the plane last set; taken to the
+        cloud's frame by height_plane) and its slack s = SLOPE x forward distance.  Returns two float64 CUDA tensors [N], both NaN
+        for a point with a non-finite coordinate."""
+        slope = (self._height_bounds or self._parse_height_gate())[2]
+        ht = _lib.AvlHeight()
+        ht.plane[:] = [float(v) for v in self.height_plane(pose, pcd_frame_id, plane)]
+        ht.slope = slope
+        view, T, _, _, s = self._frame_args(pcd, pcd_frame_id, pose, np.zeros(12), grid=False)
+        n = view[1]
+        h = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)[:n]
+        sl = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)[:n]
+        rc = _lib.lib().avl_point_heights(*view, T, C.byref(ht), _ptr(h), _ptr(sl), s)
+        _lib.check(rc, "avl_point_heights")
+        return h, sl
 
     def project_pcd(self, pcd, pcd_frame_id, image, pose, camera_calibration):
         """mapping.py:357-389.  NumPy in, NumPy out: (pcd[:, mask] float64[4,M], label uint8[3,M]).

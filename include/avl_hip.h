@@ -725,6 +725,39 @@ int avl_points_map_window(const int32_t* offsets_host, int rows, int cols, int r
 int avl_points_map_gather(const float* points, const int32_t* offsets_dev, const int32_t* offsets_host, int rows, int cols, int r0, int r1,
                           int c0, int c1, float* dst, int64_t dst_capacity, void* stream);
 
+/* ---- the scrolling grid: tile jobs (not in the reference; csrc/seg_scroll.hip, vision_semantic_segmentation_amd/scroll.py) --------
+ * The reference's grid is the fixed rectangle of MAPPING.BOUNDARY (src/mapping.py:106-117) and a point outside it is dropped
+ * (:410-411).  With MAPPING.SCROLL the device grid [Hm][Wm][C] is a window whose origin moves in whole tiles of T x T cells; tiles
+ * that leave go to slabs of a tile store in HBM, tiles that enter come back from it or start empty.  A scroll, a reload, the assembly
+ * of a site and a save are all tables of the one job below.  THE RULE:
+ *   1. tile: T = tile_cells rows of T * bytes_per_cell bytes; row r of the source starts at src + r * src_pitch, of the destination
+ *      at dst + r * dst_pitch (pitches in bytes: Wm * bytes_per_cell for a tile of a window, T * bytes_per_cell for a slab).
+ *   2. copy: the destination tile becomes the source tile, byte for byte.  src == NULL: every 32-bit word of the destination tile
+ *      becomes `fill`, the layer's empty word (0 for the map and the elevation layer's sum and count, 0x7fffffff for its minimum,
+ *      0x80000000 for its maximum: avl_elevation_reset's state).  One call serves one layer.
+ *   3. flag: with flag >= 0, flags[flag] = 1 iff some 32-bit word of the SOURCE tile differs from `fill` (0 for src == NULL), else
+ *      flags[flag] = 0.  Bit patterns are compared: a tile that holds a -0.0 is not empty.  The call zeroes flags[0 .. n_flags) itself,
+ *      stream-ordered, before the kernel; the kernel sets a flag with an integer atomic OR.  A flag index >= n_flags is ignored.
+ *   4. no two jobs of a call write the same byte, and no job reads a byte another writes: the kernel orders nothing between jobs.
+ * The caller owns the table's validity: every src, dst and pitch 16-byte aligned, every range inside the buffer it belongs to.  The
+ * library cannot check a table that lives on the device; scroll.validate_jobs does, on the host, before the upload. */
+typedef struct avl_tile_job {
+    const void* src;      /* first byte of the source tile, or NULL: the destination is filled with the fill word */
+    int64_t src_pitch;    /* bytes between tile rows of the source                                               */
+    void* dst;            /* first byte of the destination tile                                                  */
+    int64_t dst_pitch;    /* bytes between tile rows of the destination                                          */
+    int32_t flag;         /* >= 0: the flag that receives rule 3; < 0: none                                      */
+    int32_t pad;
+} avl_tile_job;
+
+/* Executes jobs_dev[0 .. n_jobs), a DEVICE array, by the rule above, in one launch on `stream`: 16 bytes per lane, a tile split over
+ * enough workgroups that twenty jobs still fill the machine.  Nothing is allocated, copied from the host or waited for.  n_jobs == 0
+ * only zeroes the flags.  AVL_E_ARG, before any GPU work: n_jobs < 0 or above 2^20, a NULL jobs_dev with n_jobs > 0, n_flags < 0, a
+ * NULL flags with n_flags > 0, tile_cells outside 1 .. 16384, bytes_per_cell no multiple of 4 or outside 4 .. 128,
+ * tile_cells * bytes_per_cell no multiple of 16. */
+int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags, int n_flags,
+                  void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

@@ -232,6 +232,18 @@ def get_cfg_defaults():
     C.MAPPING.POINTS_MAP.TILE_M = 10.0
     C.MAPPING.POINTS_MAP.RADIUS_M = 0.0
     C.MAPPING.POINTS_MAP.MARGIN_M = 1.0
+    # build-specific: the scrolling grid.  Off: the grid is the fixed rectangle of BOUNDARY, as in the reference, and nothing below is
+    # touched.  On: the device grid keeps its size but is a window whose origin moves in whole tiles of TILE_M metres so that the
+    # vehicle stays near its centre (SemanticMapping.scroll_to, called by mapping() / mapping_views()); the BOUNDARY minimum is global
+    # cell (0, 0) for good.  The origin moves when the vehicle's tile is more than HYSTERESIS_TILES from the centred position on
+    # either axis.  Tiles that leave go to a store in HBM that grows by POOL_CHUNK_TILES tiles at a time (no host spill: until the
+    # allocator refuses), tiles that enter come back from it or start empty (scroll.py; the job kernel: include/avl_hip.h,
+    # avl_tile_job).  TILE_M / RESOLUTION must be a multiple of 4 cells and divide the grid; the planar mode and global_map() refuse
+    C.MAPPING.SCROLL = CfgNode()
+    C.MAPPING.SCROLL.ENABLED = False
+    C.MAPPING.SCROLL.TILE_M = 10.0
+    C.MAPPING.SCROLL.HYSTERESIS_TILES = 1
+    C.MAPPING.SCROLL.POOL_CHUNK_TILES = 64
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

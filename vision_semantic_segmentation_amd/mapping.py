@@ -41,6 +41,10 @@ What differs from the reference, by design:
     class's band (the rule at struct avl_height in include/avl_hip.h; ``last_gated``, ``point_heights_device()``): the reference
     projects the cloud onto z = 0, so a canopy point votes into the road cell beneath it.  With MAPPING.ELEVATION.ENABLED the z of
     the points that vote a ground class is accumulated per cell (``elevation_device()``, ``elevation_layer()``).  Both off by default.
+  * with MAPPING.SCROLL.ENABLED the grid is a window that follows the vehicle: its origin moves in whole tiles (``scroll_to()``, called
+    by ``mapping()`` / ``mapping_views()``), tiles that leave are kept in a store in HBM and come back when the vehicle returns
+    (scroll.py; ``site_map()``, ``site_tiles()``, ``save_site()``, ``load_site()``).  The reference drops every point outside
+    MAPPING.BOUNDARY.  Off by default.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -307,6 +311,16 @@ class SemanticMapping(object):
         self._elevation_par = self._parse_elevation() if self.elevation_enabled() else None        # (class mask, quantum)
         self._elevation = None                 # (sum int64, cnt, min, max int32) CUDA [Hm, Wm]: allocated on first use
 
+        # the scrolling grid (MAPPING.SCROLL); off by default: then there is no store, no second buffer and nothing of scroll.py
+        self.scroll_cfg = getattr(cfg.MAPPING, "SCROLL", None)
+        self.scroll_origin = (0, 0)            # the window's origin in global cells, multiples of the tile size
+        self.last_scroll = None                # {"shift": (di, dj) in tiles, "leaving", "entering", "loaded", "filled"} of the last scroll
+        self.scroll_count = 0
+        self._scroll = None                    # scroll.TileStore
+        if self.scroll_enabled():
+            from .scroll import TileStore
+            self._scroll = TileStore(self)     # ValueError for a tile size that does not fit the grid, and for the planar mode
+
         # device-side caches
         self._scratch = None
         self._pcd_dev = None
@@ -365,7 +379,8 @@ class SemanticMapping(object):
 
     @property
     def map_dev(self):
-        """The grid in HBM: torch tensor [map_height, map_width, map_depth]."""
+        """The grid in HBM: torch tensor [map_height, map_width, map_depth].  With MAPPING.SCROLL.ENABLED this is the window's CURRENT
+        buffer: a scroll swaps the two buffers, and a caller who kept the tensor from before the scroll holds stale memory."""
         return self.grid.map
 
     @property
@@ -604,6 +619,8 @@ class SemanticMapping(object):
         semantic_image: uint8[H,W,3] colourised labels (NumPy or a CUDA tensor)."""
         if pose is not None:
             self._live_pose = pose                                               # live_map(pose=None): the last pose mapped
+            if self._scroll is not None:
+                self._scroll.scroll_to(pose)                                     # host arithmetic only unless the window moves
         if self.depth_method not in ["points_map", "points_raw"]:                 # mapping.py:320-321
             img = self._as_device_u8(semantic_image)
             self.update_map_planar(self.map_dev, img, camera_calibration)
@@ -638,6 +655,8 @@ class SemanticMapping(object):
             raise ValueError("mapping_views needs one camera per semantic image, got %d and %d" % (len(semantic_images), len(cameras)))
         if pose is not None:
             self._live_pose = pose
+            if self._scroll is not None:
+                self._scroll.scroll_to(pose)
         if self.depth_method not in ["points_map", "points_raw"]:                 # planar mode has no cloud to share
             for img, cam in zip(semantic_images, cameras):
                 self.update_map_planar(self.map_dev, self._as_device_u8(img), cam)
@@ -1430,6 +1449,55 @@ class SemanticMapping(object):
             self._map_host = None
         return map_local
 
+    # ------------------------------------------------------------------ the scrolling grid (MAPPING.SCROLL)
+    def scroll_enabled(self):
+        return self.scroll_cfg is not None and bool(self.scroll_cfg.ENABLED)
+
+    def _scroll_store(self):
+        if self._scroll is None:
+            raise RuntimeError("MAPPING.SCROLL.ENABLED is False: this map is the fixed rectangle of MAPPING.BOUNDARY")
+        return self._scroll
+
+    def scroll_to(self, pose, stream=None):
+        """Move the window so that the vehicle at ``pose`` is near its centre (scroll.next_origin: whole tiles, a hysteresis band);
+        True when it moved.  While the origin stays this is host arithmetic: nothing is launched, copied or waited for, and
+        ``last_scroll`` is untouched.  A move is one avl_tile_copy launch per layer (the map; with MAPPING.ELEVATION its four arrays)
+        on ``stream``: leaving tiles go to the store, the overlap moves to the second window buffer, entering tiles come from the
+        store or start empty; then the buffers swap -- ``map_dev`` is another tensor afterwards -- and ``grid.boundary`` /
+        ``map_boundary`` become scroll.window_boundary(new origin), which is what every consumer of the boundary reads.
+        mapping() and mapping_views() call this before the frame's vote; frame_device*, ground_fill_device and the other
+        device-level entry points do not: their callers do.  All scrolls, frames and site calls of one map belong on one stream (or
+        the caller orders them): a slab freed by one call is reused by the next."""
+        with self._lock:
+            return self._scroll_store().scroll_to(pose, stream)
+
+    def site_tiles(self, layer="map"):
+        """The sorted tile coordinates (ti, tj) that hold something, in the window or in the store; ``layer`` "map" or "elevation".
+        Waits for the last scroll's emptiness flags."""
+        with self._lock:
+            return self._scroll_store().site_tiles(layer)
+
+    def site_map(self, rect=None, layer="map", stream=None):
+        """-> ((i0, j0), CUDA tensor): the tile rectangle ``rect`` = (ti0, ti1, tj0, tj1), both ends included, assembled from window
+        tiles, stored tiles and the empty state by the tile-job kernel; (i0, j0) is the global cell of its first element.  ``rect``
+        None = the bounding rectangle of site_tiles(layer).  ``layer`` "elevation" returns the layer's four arrays.  The window and
+        the store are left as they are.  render_bev_map(site_map()[1]) is the picture of the whole site."""
+        with self._lock:
+            return self._scroll_store().site_map(rect, layer, stream)
+
+    def save_site(self, path, stream=None):
+        """The whole site -- the window's own tiles included -- as one .npz: anchor, resolution, T, C, dtype and, per layer, the
+        coordinates and a [n, T, T, ...] array of its non-empty tiles (scroll.pack_site)."""
+        with self._lock:
+            return self._scroll_store().save_site(path, stream)
+
+    def load_site(self, path, stream=None):
+        """A site file into the store: every tile goes to a slab, the window is left empty at origin (0, 0) and the next scroll_to
+        brings in what belongs there.  What the map held before is dropped.  ValueError when the file's anchor, resolution, T, C,
+        dtype or layers are not this map's."""
+        with self._lock:
+            return self._scroll_store().load_site(path, stream)
+
     # ------------------------------------------------------------------ multi-GPU: shared global grid
     def global_map(self, group=None, dst=None, exchange_dtype=None, mode="dense"):
         """Sum of every rank's private grid: each rank maps its own camera stream into its
@@ -1440,6 +1508,9 @@ class SemanticMapping(object):
         ~0.6 MB per GPU at config C against 80 MB); "auto": sparse while every rank touched fewer than 5 % of the cells.
         Returns the CUDA tensor (valid on every rank, or on dst only); ``.last_exchange`` = (mode used, bytes this rank sent)."""
         from . import distributed as D
+        if self._scroll is not None:
+            raise RuntimeError("global_map() with MAPPING.SCROLL.ENABLED: every rank's window has its own origin, and a multi-GPU site "
+                               "map is out of scope; exchange site_map() regions instead")
         if mode == "dense":
             total = D.reduce_grids(self.grid.map, group=group, dst=dst, exchange_dtype=exchange_dtype)
             self.last_exchange = ("dense", int(total.numel() * total.element_size()))

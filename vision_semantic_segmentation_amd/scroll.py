@@ -1,0 +1,643 @@
+"""The scrolling grid (MAPPING.SCROLL): the device grid [Hm, Wm, C] as a window that follows the vehicle over an unbounded site.
+
+The reference's grid is the fixed rectangle of MAPPING.BOUNDARY (src/mapping.py:106-117); a point outside it is dropped (:410-411).
+Here the window's origin moves in whole tiles of T x T cells so that the vehicle stays near the centre; tiles that leave go to a tile
+store in HBM, tiles that enter come back from it or start in the empty state.  Off by default: nothing of this module then runs.
+
+GEOMETRY (pure host functions, float64 and Python integers):
+  * global cell (0, 0) is the configured MAPPING.BOUNDARY minimum, the ANCHOR; it never changes.
+  * the window's origin (i0, j0) is in global cells, both multiples of T = int(round(TILE_M / RESOLUTION)); T % 4 == 0, Hm % T == 0,
+    Wm % T == 0; |i0|, |j0| < 2^30.
+  * THE WINDOW'S BOUNDARY, stated once, here:  minimum = anchor + float(i0) * resolution  (one float64 product, one float64 sum; the
+    same along y), maximum = minimum + Hm * resolution (Wm along y).  With a resolution such as 0.1 the cell edges of two origins
+    differ by ulps; that is accepted, and the tests' NumPy site uses the same floats.
+  * the vehicle's cell is floor((pose.xy + PCD_ORIGIN_OFFSET.xy - anchor) / resolution): floor, a site extends to both sides.
+
+DEVICE WORK is one operation, a table of tile jobs (struct avl_tile_job of include/avl_hip.h, k_tile_copy of csrc/seg_scroll.hip): a
+scroll, a reload, the assembly of a site and a save build such a table on the host, VALIDATE it on the host -- every source and
+destination range inside the buffer it names, validate_jobs -- and launch it once per layer.  A table that fails is never launched.
+
+THE STORE.  One pool per layer (the map; with MAPPING.ELEVATION its four arrays), made of chunks of POOL_CHUNK_TILES slabs of
+T * T * bytes_per_cell bytes; a chunk is a CUDA tensor.  The pool grows by whole chunks, so a stored tile never moves and jobs carry
+plain device addresses.  The host owns the directory {(ti, tj): slab} and the free list; a slab index names the same slot in every
+layer's pool.  Nothing spills to host memory: the pool grows until the allocator refuses.
+"""
+import collections
+import math
+
+import numpy as np
+
+from .mapping import PCD_ORIGIN_OFFSET            # mapping.py imports this module only inside functions
+
+MAX_ORIGIN = 1 << 30
+
+Job = collections.namedtuple("Job", "src src_off src_pitch dst dst_off dst_pitch flag")
+"""One tile job in host form: ``src`` / ``dst`` name a buffer ("old", "new", "out", ("chunk", k), ...; src None = fill), the offsets
+and pitches are bytes.  encode_jobs turns it into struct avl_tile_job with the buffers' device addresses."""
+
+JOB_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("dst", "<u8"), ("dst_pitch", "<i8"), ("flag", "<i4"), ("pad", "<i4")])
+
+Layer = collections.namedtuple("Layer", "name bpc fill")
+ELEVATION_LAYERS = (Layer("elev_sum", 8, 0), Layer("elev_cnt", 4, 0), Layer("elev_min", 4, 0x7FFFFFFF), Layer("elev_max", 4, 0x80000000))
+
+
+# ------------------------------------------------------------------------------------------------ geometry
+def tile_cells(tile_m, resolution):
+    return int(round(float(tile_m) / float(resolution)))
+
+
+def check_geometry(Hm, Wm, T):
+    """ValueError, naming the numbers, unless T % 4 == 0, Hm % T == 0 and Wm % T == 0."""
+    if T < 4 or T % 4 != 0:
+        raise ValueError("MAPPING.SCROLL: a tile of T = %d cells (TILE_M / RESOLUTION) must be a positive multiple of 4" % T)
+    if Hm % T != 0 or Wm % T != 0:
+        raise ValueError("MAPPING.SCROLL: the grid of Hm = %d x Wm = %d cells is no whole number of tiles of T = %d cells" % (Hm, Wm, T))
+
+
+def check_origin(origin, T):
+    i0, j0 = int(origin[0]), int(origin[1])
+    if i0 % T != 0 or j0 % T != 0:
+        raise ValueError("scroll origin (%d, %d) is no multiple of the tile size T = %d" % (i0, j0, T))
+    if abs(i0) >= MAX_ORIGIN or abs(j0) >= MAX_ORIGIN:
+        raise ValueError("scroll origin (%d, %d) is at or beyond 2^30 cells from the anchor" % (i0, j0))
+    return i0, j0
+
+
+def window_boundary(anchor, origin, Hm, Wm, res):
+    """[[x_min, x_max], [y_min, y_max]] of the window at ``origin`` = (i0, j0): the module's one statement of the expression."""
+    res = float(res)
+    x0 = float(anchor[0]) + float(int(origin[0])) * res
+    y0 = float(anchor[1]) + float(int(origin[1])) * res
+    return [[x0, x0 + int(Hm) * res], [y0, y0 + int(Wm) * res]]
+
+
+def vehicle_cell(pose, anchor, res):
+    """The vehicle's global cell (i, j), Python integers, or None for a pose that is not finite (no scroll).  Plain float64
+    arithmetic, no array: this runs in front of every frame."""
+    if pose is None:
+        return None
+    if hasattr(pose, "position"):
+        x, y = float(pose.position.x), float(pose.position.y)
+    else:
+        x, y = float(pose[0]), float(pose[1])
+    cx = (x + PCD_ORIGIN_OFFSET[0] - anchor[0]) / res
+    cy = (y + PCD_ORIGIN_OFFSET[1] - anchor[1]) / res
+    if not (math.isfinite(cx) and math.isfinite(cy)):
+        return None
+    return math.floor(cx), math.floor(cy)
+
+
+def next_origin(current, cell, Ht, Wt, T, hysteresis):
+    """The window's next origin in cells.  ``current`` None = the first call of a run: the desired origin is taken.  Otherwise the
+    desired origin tile, vehicle tile - (Ht // 2, Wt // 2), replaces the current one on BOTH axes when it differs from it by more
+    than ``hysteresis`` tiles on either; else the origin stays.  ``cell`` None (vehicle_cell of a non-finite pose): no scroll,
+    ``current`` comes back ((0, 0) on a first call).  ValueError at or beyond 2^30 cells."""
+    if cell is None:
+        return (0, 0) if current is None else (int(current[0]), int(current[1]))
+    want = (cell[0] // T - Ht // 2, cell[1] // T - Wt // 2)                  # Python's // floors
+    if current is not None:
+        cur = (int(current[0]) // T, int(current[1]) // T)
+        if abs(want[0] - cur[0]) <= hysteresis and abs(want[1] - cur[1]) <= hysteresis:
+            return int(current[0]), int(current[1])
+    return check_origin((want[0] * T, want[1] * T), T)
+
+
+# ------------------------------------------------------------------------------------------------ job tables
+def window_tiles(origin_tile, Ht, Wt):
+    a, b = origin_tile
+    return [(a + i, b + j) for i in range(Ht) for j in range(Wt)]
+
+
+def plan_scroll(old_tile, new_tile, Ht, Wt, stored, window_valid=True):
+    """What a move of the window from origin tile ``old_tile`` to ``new_tile`` does, in tiles: {"leaving": tiles of the old window
+    that are not in the new one, "dst": [(tile, kind)] for every tile of the new window, kind "overlap" (it was in the old window),
+    "load" (it is in ``stored``) or "fill"}.  ``window_valid`` False: the old window holds nothing (after load_site) -- no tile
+    leaves, none overlaps.  A jump further than the window has no overlap; the code is the same."""
+    (a0, b0), (a1, b1) = old_tile, new_tile
+
+    def inside(t, a, b):
+        return a <= t[0] < a + Ht and b <= t[1] < b + Wt
+    leaving = [t for t in window_tiles(old_tile, Ht, Wt) if not inside(t, a1, b1)] if window_valid else []
+    dst = []
+    for t in window_tiles(new_tile, Ht, Wt):
+        if window_valid and inside(t, a0, b0):
+            dst.append((t, "overlap"))
+        else:
+            dst.append((t, "load" if t in stored else "fill"))
+    return {"leaving": leaving, "dst": dst}
+
+
+def window_ref(tile, origin_tile, T, Wm, bpc):
+    """(byte offset, pitch) of ``tile`` inside a window buffer [Hm, Wm, bpc bytes] whose first tile is ``origin_tile``"""
+    return (((tile[0] - origin_tile[0]) * T * Wm) + (tile[1] - origin_tile[1]) * T) * bpc, Wm * bpc
+
+
+def slab_ref(slab, chunk_tiles, T, bpc):
+    """(buffer key, byte offset, pitch) of slab ``slab`` in a pool of chunks of ``chunk_tiles`` slabs"""
+    return ("chunk", slab // chunk_tiles), (slab % chunk_tiles) * T * T * bpc, T * bpc
+
+
+def scroll_jobs(plan, old_tile, new_tile, T, Wm, bpc, chunk_tiles, slab_of_leaving, slab_of_stored):
+    """The job table of one layer for ``plan``: first one job "old" window -> fresh slab per leaving tile (flag k for the k-th),
+    then one job per tile of the new window into "new".  ``slab_of_leaving``: a slab per leaving tile, in order; ``slab_of_stored``:
+    {tile: slab} for the tiles of kind "load"."""
+    jobs = []
+    for k, t in enumerate(plan["leaving"]):
+        so, sp = window_ref(t, old_tile, T, Wm, bpc)
+        dk, do, dp = slab_ref(slab_of_leaving[k], chunk_tiles, T, bpc)
+        jobs.append(Job("old", so, sp, dk, do, dp, k))
+    for t, kind in plan["dst"]:
+        do, dp = window_ref(t, new_tile, T, Wm, bpc)
+        if kind == "overlap":
+            so, sp = window_ref(t, old_tile, T, Wm, bpc)
+            jobs.append(Job("old", so, sp, "new", do, dp, -1))
+        elif kind == "load":
+            sk, so, sp = slab_ref(slab_of_stored[t], chunk_tiles, T, bpc)
+            jobs.append(Job(sk, so, sp, "new", do, dp, -1))
+        else:
+            jobs.append(Job(None, 0, 0, "new", do, dp, -1))
+    return jobs
+
+
+def validate_jobs(jobs, buffers, T, bpc, n_flags=None):
+    """ValueError unless every job of the table is safe to launch.  ``buffers``: {key: (device address, bytes)}.  Every source and
+    destination tile -- T rows of T * bpc bytes, ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a
+    multiple of 16; a pitch is at least a row; no destination tile appears twice and no job reads a buffer range another writes
+    (checked per buffer: a buffer is read or written, never both, except distinct slabs of a chunk); a flag is below ``n_flags``."""
+    row = T * bpc
+    if bpc % 4 != 0 or not 4 <= bpc <= 128 or row % 16 != 0:
+        raise ValueError("tile jobs: bytes_per_cell = %d, T = %d (bytes_per_cell a multiple of 4 up to 128, T * bytes_per_cell of 16)" % (bpc, T))
+    written, read = set(), set()
+    for k, j in enumerate(jobs):
+        for what, key, off, pitch in (("src", j.src, j.src_off, j.src_pitch), ("dst", j.dst, j.dst_off, j.dst_pitch)):
+            if key is None:
+                if what == "dst":
+                    raise ValueError("tile job %d has no destination" % k)
+                continue
+            if key not in buffers:
+                raise ValueError("tile job %d: %s names the unknown buffer %r" % (k, what, key))
+            base, nbytes = buffers[key]
+            if pitch % 16 != 0 or pitch < row:
+                raise ValueError("tile job %d: %s pitch %d is misaligned or shorter than a tile row of %d bytes" % (k, what, pitch, row))
+            if (base + off) % 16 != 0:
+                raise ValueError("tile job %d: %s address %d + %d is not 16-byte aligned" % (k, what, base, off))
+            end = off + (T - 1) * pitch + row
+            if off < 0 or end > nbytes:
+                raise ValueError("tile job %d: %s bytes %d .. %d leave buffer %r of %d bytes" % (k, what, off, end, key, nbytes))
+            if what == "dst":
+                if (key, off) in written:
+                    raise ValueError("tile job %d: destination tile %r + %d appears twice" % (k, key, off))
+                written.add((key, off))
+            else:
+                read.add((key, off))
+        if n_flags is not None and j.flag >= n_flags:
+            raise ValueError("tile job %d: flag %d of %d" % (k, j.flag, n_flags))
+    both = written & read
+    if both:
+        raise ValueError("tile jobs: %d tiles are read and written in one table, the first %r" % (len(both), sorted(both)[0]))
+    wkeys = {k for k, _ in written}
+    for key in {k for k, _ in read} & wkeys:
+        if not (isinstance(key, tuple) and key[0] == "chunk"):
+            raise ValueError("tile jobs: buffer %r is read and written in one table" % (key,))
+
+
+def encode_jobs(jobs, buffers, out):
+    """``jobs`` as struct avl_tile_job records into the structured array ``out`` (JOB_DTYPE, at least len(jobs) long)."""
+    n = len(jobs)
+    base = {k: v[0] for k, v in buffers.items()}
+    out["src"][:n] = [0 if j.src is None else base[j.src] + j.src_off for j in jobs]
+    out["src_pitch"][:n] = [j.src_pitch for j in jobs]
+    out["dst"][:n] = [base[j.dst] + j.dst_off for j in jobs]
+    out["dst_pitch"][:n] = [j.dst_pitch for j in jobs]
+    out["flag"][:n] = [j.flag for j in jobs]
+    out["pad"][:n] = 0
+    return n
+
+
+# ------------------------------------------------------------------------------------------------ the site file
+def pack_site(anchor, resolution, T, C_, dtype, layers):
+    """The arrays of a site file (one .npz).  ``layers``: {layer name: (coords int [n, 2], tiles [n, T, T, ...])}."""
+    out = {"anchor": np.asarray(anchor, dtype=np.float64), "resolution": np.float64(resolution), "T": np.int64(T), "C": np.int64(C_),
+           "dtype": np.array(str(dtype)), "layers": np.array(sorted(layers))}
+    for name, (coords, tiles) in layers.items():
+        out[name + "_coords"] = np.asarray(coords, dtype=np.int64).reshape(-1, 2)
+        out[name + "_tiles"] = np.asarray(tiles)
+    return out
+
+
+def unpack_site(data, anchor=None, resolution=None, T=None, C_=None, dtype=None):
+    """-> (meta dict, {layer name: (coords, tiles)}) of the arrays of a site file; ValueError when a given ``anchor``, ``resolution``,
+    ``T``, ``C_`` or ``dtype`` is not the file's."""
+    meta = {"anchor": tuple(float(v) for v in data["anchor"]), "resolution": float(data["resolution"]), "T": int(data["T"]),
+            "C": int(data["C"]), "dtype": str(data["dtype"])}
+    for name, want in (("anchor", None if anchor is None else tuple(float(v) for v in anchor)),
+                       ("resolution", None if resolution is None else float(resolution)), ("T", T), ("C", C_), ("dtype", dtype)):
+        if want is not None and meta[name] != want:
+            raise ValueError("the site file has %s = %r, this map %r" % (name, meta[name], want))
+    layers = {}
+    for name in [str(n) for n in data["layers"]]:
+        coords, tiles = np.asarray(data[name + "_coords"]), np.asarray(data[name + "_tiles"])
+        if coords.shape[0] != tiles.shape[0] or (tiles.shape[0] and tuple(tiles.shape[1:3]) != (meta["T"], meta["T"])):
+            raise ValueError("the site file's layer %r holds %s coordinates and tiles of shape %s" % (name, coords.shape, tiles.shape))
+        layers[name] = (coords, tiles)
+    return meta, layers
+
+
+# ------------------------------------------------------------------------------------------------ the store
+class _DeviceLayer(object):
+    """One persistent layer on the device: its two window buffers and its pool"""
+
+    def __init__(self, layer, get, put, alloc):
+        self.name, self.bpc, self.fill = layer
+        self.get, self.put, self.alloc = get, put, alloc       # the current window tensor, its replacement, a fresh one like it
+        self.alt = None                                        # the second window buffer, allocated by the first scroll
+        self.chunks = []
+
+
+class TileStore(object):
+    """The window's origin, the tile store and the scroll step of one SemanticMapping (MAPPING.SCROLL.ENABLED)."""
+
+    def __init__(self, sm):
+        import torch
+        sc = sm.cfg.MAPPING.SCROLL
+        if sm.depth_method not in ("points_map", "points_raw"):
+            raise ValueError("MAPPING.SCROLL.ENABLED needs a LiDAR DEPTH_METHOD, not %r: the planar mode's discretize_matrix is tied to a "
+                             "fixed boundary" % (sm.depth_method,))
+        self.sm = sm
+        self.torch = torch
+        self.Hm, self.Wm, self.C = sm.map_height, sm.map_width, sm.map_depth
+        self.res = float(sm.resolution)
+        self.T = tile_cells(sc.TILE_M, self.res)
+        check_geometry(self.Hm, self.Wm, self.T)
+        self.Ht, self.Wt = self.Hm // self.T, self.Wm // self.T
+        self.hysteresis = int(sc.HYSTERESIS_TILES)
+        self.chunk_tiles = int(sc.POOL_CHUNK_TILES)
+        if self.hysteresis < 0 or self.chunk_tiles < 1:
+            raise ValueError("MAPPING.SCROLL: HYSTERESIS_TILES = %r (>= 0), POOL_CHUNK_TILES = %r (>= 1)" % (sc.HYSTERESIS_TILES, sc.POOL_CHUNK_TILES))
+        self.anchor = (float(sm.map_boundary[0][0]), float(sm.map_boundary[1][0]))
+        self.origin = (0, 0)
+        self.first = True                 # no scroll_to has run: the next takes the desired origin
+        self.band = None                  # set by a scroll: see _set_band; None = take the slow path (first call, after load_site)
+        self.window_valid = True          # False after load_site: the window holds nothing and the next scroll_to always runs
+        self.layers = None                # [_DeviceLayer], fixed by the first device operation
+        self.directory = {}               # (ti, tj) -> slab
+        self.nonempty = {}                # (ti, tj) -> bit mask of the layers whose stored tile holds something
+        self.free = []
+        self.n_slabs = 0
+        self.pending = None               # (leaving tiles, number of layers) of the last scroll until its flags are retired
+        self.tables = [None, None]        # ring of two job tables: [pinned host uint8, device uint8, event]
+        self.table_turn = 0
+        self.flags_dev = None
+        self.flags_host = None
+        self.flags_event = None
+
+    # -------------------------------------------------------------------------------------------- layers and pools
+    def _layers(self):
+        if self.layers is None:
+            sm, torch = self.sm, self.torch
+            es = 8 if sm.grid.torch_dtype == torch.float64 else 4
+
+            def put_map(t):
+                sm.grid.map = t
+            layers = [_DeviceLayer(Layer("map", es * self.C, 0), lambda: sm.grid.map, put_map, lambda: torch.empty_like(sm.grid.map))]
+            if sm.elevation_enabled():
+                sm.elevation_layer()                          # allocated, empty, now: the set of layers is fixed for the run
+                for k, layer in enumerate(ELEVATION_LAYERS):
+                    def put(t, k=k):
+                        e = list(sm._elevation)
+                        e[k] = t
+                        sm._elevation = tuple(e)
+                    layers.append(_DeviceLayer(layer, lambda k=k: sm._elevation[k], put, lambda k=k: torch.empty_like(sm._elevation[k])))
+            self.layers = layers
+        return self.layers
+
+    def _slabs(self, n):
+        """n slab indices off the free list, the pools grown by whole chunks as needed"""
+        torch = self.torch
+        while len(self.free) < n:
+            first = self.n_slabs
+            for L in self._layers():
+                L.chunks.append(torch.empty(self.chunk_tiles * self.T * self.T * L.bpc, dtype=torch.uint8, device=self.sm.device))
+            self.n_slabs += self.chunk_tiles
+            self.free.extend(range(self.n_slabs - 1, first - 1, -1))       # popped from the end: lowest first
+        return [self.free.pop() for _ in range(n)]
+
+    def _buffers(self, L, extra=None):
+        b = {("chunk", k): (c.data_ptr(), int(c.numel())) for k, c in enumerate(L.chunks)}
+        if extra:
+            b.update(extra)
+        return b
+
+    @staticmethod
+    def _extent(t):
+        return t.data_ptr(), int(t.numel()) * int(t.element_size())
+
+    # -------------------------------------------------------------------------------------------- launching a table
+    def _stream(self, stream):
+        torch = self.torch
+        if stream is None:
+            return torch.cuda.current_stream(self.sm.device)
+        if isinstance(stream, torch.cuda.Stream):
+            return stream
+        return torch.cuda.ExternalStream(int(stream), device=self.sm.device)
+
+    def _run(self, per_layer, st, n_flags=0):
+        """``per_layer``: [(layer, jobs, buffers)], all validated here, uploaded as one table through the ring and launched once per
+        layer on the torch stream ``st``; with ``n_flags`` every layer's flags go to flags_dev[l * n_flags ...] and their copy into
+        pinned memory is started, flags_event recorded behind it."""
+        import ctypes as C
+        from . import _lib
+        torch = self.torch
+        for L, jobs, buffers in per_layer:
+            validate_jobs(jobs, buffers, self.T, L.bpc, n_flags)          # raises before anything is uploaded or launched
+        total = sum(len(jobs) for _, jobs, _ in per_layer)
+        nbytes = max(total, 1) * JOB_DTYPE.itemsize
+        turn = self.table_turn
+        self.table_turn ^= 1
+        slot = self.tables[turn]
+        if slot is not None:
+            slot[2].synchronize()                                          # a table in flight is not overwritten
+        if slot is None or int(slot[0].numel()) < nbytes:
+            cap = max(2 * nbytes, 1 << 14)
+            slot = self.tables[turn] = [torch.empty(cap, dtype=torch.uint8).pin_memory(),
+                                        torch.empty(cap, dtype=torch.uint8, device=self.sm.device), torch.cuda.Event()]
+        host, dev, event = slot
+        rec = host.numpy()[:nbytes].view(JOB_DTYPE)
+        at, starts = 0, []
+        for L, jobs, buffers in per_layer:
+            starts.append(at)
+            at += encode_jobs(jobs, buffers, rec[at:])
+        n_layers = len(per_layer)
+        if n_flags and (self.flags_dev is None or int(self.flags_dev.numel()) < n_layers * n_flags):
+            if self.flags_event is not None:
+                self.flags_event.synchronize()
+            self.flags_event = torch.cuda.Event()
+            cap = max(2 * n_layers * n_flags, 256)
+            self.flags_dev = torch.empty(cap, dtype=torch.int32, device=self.sm.device)
+            self.flags_host = torch.empty(cap, dtype=torch.int32).pin_memory()
+        with torch.cuda.stream(st):
+            dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+            for l, (L, jobs, _) in enumerate(per_layer):
+                flags = C.c_void_p(self.flags_dev.data_ptr() + 4 * l * n_flags) if n_flags else None
+                rc = _lib.lib().avl_tile_copy(C.c_void_p(dev.data_ptr() + starts[l] * JOB_DTYPE.itemsize), len(jobs), self.T, L.bpc,
+                                              L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
+                _lib.check(rc, "avl_tile_copy")
+            event.record(st)
+            if n_flags:
+                self.flags_host[:n_layers * n_flags].copy_(self.flags_dev[:n_layers * n_flags], non_blocking=True)
+                self.flags_event.record(st)
+
+    # -------------------------------------------------------------------------------------------- the scroll
+    def retire(self):
+        """The previous scroll's emptiness flags, whose copy completed long ago: the slabs of leaving tiles that turned out empty in
+        every layer go back to the free list and leave the directory; the others keep the mask of their non-empty layers."""
+        if self.pending is None:
+            return
+        leaving, n_layers = self.pending
+        self.pending = None
+        self.flags_event.synchronize()
+        n = len(leaving)
+        flags = self.flags_host[:n_layers * n].numpy().reshape(n_layers, n)
+        for k, t in enumerate(leaving):
+            mask = sum(1 << l for l in range(n_layers) if flags[l, k])
+            if mask:
+                self.nonempty[t] = mask
+            else:
+                self.free.append(self.directory.pop(t))
+                self.nonempty.pop(t, None)
+
+    def _set_band(self):
+        """the vehicle cells for which the origin stays, as float bounds [lo, hi) per axis: floor(c) lies in an integer range exactly
+        when c lies in [first, last + 1)"""
+        T, h = self.T, self.hysteresis
+        a, b = self.origin[0] // T + self.Ht // 2, self.origin[1] // T + self.Wt // 2
+        self.band = (float((a - h) * T), float((a + h + 1) * T), float((b - h) * T), float((b + h + 1) * T))
+
+    def scroll_to(self, pose, stream=None):
+        band = self.band
+        if band is not None and pose is not None:     # the frame's fast path: vehicle_cell's two quotients against the hysteresis band
+            x, y = (pose.position.x, pose.position.y) if hasattr(pose, "position") else (pose[0], pose[1])
+            if band[0] <= (x + PCD_ORIGIN_OFFSET[0] - self.anchor[0]) / self.res < band[1] and \
+                    band[2] <= (y + PCD_ORIGIN_OFFSET[1] - self.anchor[1]) / self.res < band[3]:
+                return False
+        sm = self.sm
+        cell = vehicle_cell(pose, self.anchor, self.res)
+        if cell is None:
+            return False
+        new = next_origin(None if self.first else self.origin, cell, self.Ht, self.Wt, self.T, self.hysteresis)
+        self.first = False
+        if new == self.origin and self.window_valid:
+            if self.band is None:
+                self._set_band()
+            return False
+        self.retire()
+        T = self.T
+        old_tile, new_tile = (self.origin[0] // T, self.origin[1] // T), (new[0] // T, new[1] // T)
+        plan = plan_scroll(old_tile, new_tile, self.Ht, self.Wt, self.directory, self.window_valid)
+        leaving = plan["leaving"]
+        layers = self._layers()
+        fresh = self._slabs(len(leaving))
+        loaded = [t for t, kind in plan["dst"] if kind == "load"]
+        per_layer = []
+        for L in layers:
+            if L.alt is None:
+                L.alt = L.alloc()
+            jobs = scroll_jobs(plan, old_tile, new_tile, T, self.Wm, L.bpc, self.chunk_tiles, fresh, self.directory)
+            per_layer.append((L, jobs, self._buffers(L, {"old": self._extent(L.get()), "new": self._extent(L.alt)})))
+        try:
+            self._run(per_layer, self._stream(stream), len(leaving))
+        except Exception:
+            self.free.extend(fresh)
+            raise
+        for t, s in zip(leaving, fresh):
+            self.directory[t] = s
+            self.nonempty[t] = (1 << len(layers)) - 1          # until the flags say otherwise
+        for t in loaded:                                       # behind the launch, in stream order: the slab is free again
+            self.free.append(self.directory.pop(t))
+            self.nonempty.pop(t, None)
+        self.pending = (leaving, len(layers)) if leaving else None
+        for L in layers:                                       # the window is the second buffer now
+            cur = L.get()
+            L.put(L.alt)
+            L.alt = cur
+        filled = sum(1 for _, kind in plan["dst"] if kind == "fill")
+        sm.last_scroll = {"shift": (new_tile[0] - old_tile[0], new_tile[1] - old_tile[1]), "leaving": len(leaving),
+                          "entering": len(loaded) + filled, "loaded": len(loaded), "filled": filled}
+        self.origin = new
+        self.window_valid = True
+        self._set_band()
+        boundary = window_boundary(self.anchor, new, self.Hm, self.Wm, self.res)
+        sm.grid.boundary = boundary
+        sm.map_boundary = boundary
+        sm._map_host = None
+        sm.scroll_origin = new
+        sm.scroll_count += 1
+        return True
+
+    # -------------------------------------------------------------------------------------------- the site
+    def _window_nonempty(self):
+        """{tile of the window: mask of its non-empty layers}, by bit pattern (a -0.0 is something)"""
+        torch = self.torch
+        if not self.window_valid:
+            return {}
+        T, masks = self.T, None
+        for l, L in enumerate(self._layers()):
+            words = L.get().contiguous().view(torch.int32).view(self.Ht, T, self.Wt, T, L.bpc // 4)
+            fill = L.fill - (1 << 32) if L.fill >= (1 << 31) else L.fill
+            some = words.ne(fill).any(dim=4).any(dim=3).any(dim=1).to(torch.int64) << l
+            masks = some if masks is None else masks | some
+        masks = masks.cpu().numpy()
+        a, b = self.origin[0] // T, self.origin[1] // T
+        return {(a + i, b + j): int(masks[i, j]) for i in range(self.Ht) for j in range(self.Wt) if masks[i, j]}
+
+    def _layer_bits(self, layer):
+        names = [L.name for L in self._layers()]
+        if layer == "map":
+            return 1
+        if layer == "elevation":
+            if len(names) < 5:
+                raise ValueError("site layer 'elevation' needs MAPPING.ELEVATION.ENABLED")
+            return 0b11110
+        raise ValueError("site layer must be 'map' or 'elevation', not %r" % (layer,))
+
+    def site_tiles(self, layer="map"):
+        self.retire()
+        bits = self._layer_bits(layer)
+        tiles = {t for t, m in self._window_nonempty().items() if m & bits}
+        tiles |= {t for t, m in self.nonempty.items() if m & bits}
+        return sorted(tiles)
+
+    def _gather_jobs(self, L, tiles, dst_ref):
+        """one job per tile of ``tiles`` from wherever the tile lives (window, store, nowhere = fill) to dst_ref(k) = (key, off, pitch)"""
+        T = self.T
+        a, b = self.origin[0] // T, self.origin[1] // T
+        jobs = []
+        for k, t in enumerate(tiles):
+            dk, do, dp = dst_ref(k)
+            if self.window_valid and a <= t[0] < a + self.Ht and b <= t[1] < b + self.Wt:
+                so, sp = window_ref(t, (a, b), T, self.Wm, L.bpc)
+                jobs.append(Job("window", so, sp, dk, do, dp, -1))
+            elif t in self.directory:
+                sk, so, sp = slab_ref(self.directory[t], self.chunk_tiles, T, L.bpc)
+                jobs.append(Job(sk, so, sp, dk, do, dp, -1))
+            else:
+                jobs.append(Job(None, 0, 0, dk, do, dp, -1))
+        return jobs
+
+    def site_map(self, rect=None, layer="map", stream=None):
+        torch = self.torch
+        self.retire()
+        bits = self._layer_bits(layer)
+        layers = [L for l, L in enumerate(self._layers()) if bits >> l & 1]
+        if rect is None:
+            tiles = self.site_tiles(layer)
+            if not tiles:
+                rect = (0, -1, 0, -1)
+            else:
+                rect = (min(t[0] for t in tiles), max(t[0] for t in tiles), min(t[1] for t in tiles), max(t[1] for t in tiles))
+        ti0, ti1, tj0, tj1 = (int(v) for v in rect)
+        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+        T = self.T
+        check_origin((ti0 * T, tj0 * T), T)
+        st = self._stream(stream)
+        outs, per_layer = [], []
+        tiles = [(ti0 + i, tj0 + j) for i in range(nh) for j in range(nw)]
+        for L in layers:
+            cur = L.get()
+            with torch.cuda.stream(st):
+                out = torch.empty((nh * T, nw * T) + tuple(cur.shape[2:]), dtype=cur.dtype, device=cur.device)
+            outs.append(out)
+            pitch = nw * T * L.bpc
+
+            def dst_ref(k, pitch=pitch, bpc=L.bpc):
+                return "out", ((k // nw) * T * nw * T + (k % nw) * T) * bpc, pitch
+            jobs = self._gather_jobs(L, tiles, dst_ref)
+            per_layer.append((L, jobs, self._buffers(L, {"window": self._extent(cur), "out": self._extent(out)})))
+        if tiles:
+            self._run(per_layer, st)
+        return (ti0 * T, tj0 * T), (outs[0] if layer == "map" else tuple(outs))
+
+    def save_site(self, path, stream=None):
+        torch = self.torch
+        self.retire()
+        T = self.T
+        st = self._stream(stream)
+        window = self._window_nonempty()
+        masks = dict(self.nonempty)
+        masks.update(window)                                   # a tile is in the window or in the store, never both
+        outs, per_layer, coords = [], [], []
+        for l, L in enumerate(self._layers()):
+            tiles = sorted(t for t, m in masks.items() if m >> l & 1)
+            cur = L.get()
+            with torch.cuda.stream(st):
+                out = torch.empty((len(tiles), T, T) + tuple(cur.shape[2:]), dtype=cur.dtype, device=cur.device)
+            slab = T * T * L.bpc
+            jobs = self._gather_jobs(L, tiles, lambda k, slab=slab, bpc=L.bpc: ("out", k * slab, T * bpc))
+            coords.append(tiles)
+            outs.append(out)
+            if tiles:
+                per_layer.append((L, jobs, self._buffers(L, {"window": self._extent(cur), "out": self._extent(out)})))
+        if per_layer:
+            self._run(per_layer, st)
+        st.synchronize()
+        g = self.sm.grid
+        arrays = pack_site(self.anchor, self.res, T, self.C, "f64" if g.torch_dtype == torch.float64 else "f32",
+                           {L.name: (np.array(c, dtype=np.int64).reshape(-1, 2), o.cpu().numpy()) for L, c, o in zip(self._layers(), coords, outs)})
+        with open(path, "wb") as f:
+            np.savez_compressed(f, **arrays)
+
+    def load_site(self, path, stream=None):
+        torch = self.torch
+        sm = self.sm
+        g = sm.grid
+        with np.load(path) as data:
+            meta, file_layers = unpack_site(data, self.anchor, self.res, self.T, self.C, "f64" if g.torch_dtype == torch.float64 else "f32")
+        layers = self._layers()
+        if sorted(file_layers) != sorted(L.name for L in layers):
+            raise ValueError("the site file holds the layers %r, this map %r" % (sorted(file_layers), sorted(L.name for L in layers)))
+        self.retire()
+        st = self._stream(stream)
+        # the store starts over: every slab free, the window empty at origin (0, 0)
+        self.directory, self.nonempty = {}, {}
+        self.free = list(range(self.n_slabs - 1, -1, -1))
+        union = sorted({(int(c[0]), int(c[1])) for coords, _ in file_layers.values() for c in coords})
+        for t in union:
+            check_origin((t[0] * self.T, t[1] * self.T), self.T)
+        slabs = dict(zip(union, self._slabs(len(union))))
+        per_layer, keep = [], []
+        T = self.T
+        for l, L in enumerate(layers):
+            coords, tiles = file_layers[L.name]
+            cur = L.get()
+            want = (T, T) + tuple(cur.shape[2:])
+            if tiles.shape[0] and (tuple(tiles.shape[1:]) != want or torch.from_numpy(tiles[:0]).dtype != cur.dtype):
+                raise ValueError("the site file's layer %r has tiles %s %s, this map %s %s" % (L.name, tiles.shape[1:], tiles.dtype, want, cur.dtype))
+            with torch.cuda.stream(st):
+                stage = torch.from_numpy(np.ascontiguousarray(tiles)).to(sm.device) if tiles.shape[0] else torch.empty(16, dtype=torch.uint8, device=sm.device)
+            keep.append(stage)
+            have = {(int(c[0]), int(c[1])): k for k, c in enumerate(coords)}
+            jobs = []
+            for t in union:
+                dk, do, dp = slab_ref(slabs[t], self.chunk_tiles, T, L.bpc)
+                if t in have:
+                    jobs.append(Job("stage", have[t] * T * T * L.bpc, T * L.bpc, dk, do, dp, -1))
+                    self.nonempty[t] = self.nonempty.get(t, 0) | 1 << l
+                else:
+                    jobs.append(Job(None, 0, 0, dk, do, dp, -1))
+            per_layer.append((L, jobs, self._buffers(L, {"stage": self._extent(stage)})))
+        if union:
+            self._run(per_layer, st)
+        self.directory = slabs
+        with torch.cuda.stream(st):
+            g.map.zero_()
+            if sm.elevation_enabled():
+                sm.reset_elevation(st.cuda_stream)
+        for s in keep:
+            s.record_stream(st)
+        self.origin, self.first, self.window_valid, self.band = (0, 0), True, False, None
+        boundary = window_boundary(self.anchor, (0, 0), self.Hm, self.Wm, self.res)
+        g.boundary = boundary
+        sm.map_boundary = boundary
+        sm._map_host = None
+        sm.scroll_origin = (0, 0)
+        return meta

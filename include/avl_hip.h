@@ -758,6 +758,44 @@ typedef struct avl_tile_job {
 int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags, int n_flags,
                   void* stream);
 
+/* ---- the site overview: a reduced grid and its picture straight from the tiles (not in the reference; csrc/seg_overview.hip) ---------
+ * A scrolled map's site lives in tiles: in the window buffer and in the store's slabs.  The overview reads them where they are and
+ * writes a grid reduced by k x k cells per pixel and its picture; nothing of the site is assembled at full resolution.  THE RULE:
+ *   1. geometry: k = cells per pixel, an integer >= 1 that divides T = tile_cells, so a pixel block never straddles a tile.  For a
+ *      rectangle of nh x nw tiles the outputs have nh * T / k rows of nw * T / k pixels; pixel (p, q) covers the rectangle's cells
+ *      [p * k, p * k + k) x [q * k, q * k + k).  The tile at (row, col) of the rectangle holds the cells [row * T, +T) x [col * T, +T).
+ *   2. reduction: for every class c, R[p][q][c] is a left fold in the map's own type (f64 or f32): the accumulator starts at +0;
+ *      di = 0 .. k-1 is the outer loop and dj = 0 .. k-1 the inner one; each step is acc = acc + cell[p*k + di][q*k + dj][c].  No FMA,
+ *      no reassociation (the translation unit is built with -ffp-contract=off).  The order is part of the rule: it makes R
+ *      reproducible bit for bit on a log confusion matrix.  (k = 1: R = +0 + cell, so a cell's -0.0 arrives as +0.)
+ *   3. picture: pixel (p, q) is render_bev_map's rule on the row R[p][q][0 .. C): the colour of the first maximum (a NaN beats
+ *      every number, the first NaN wins: k_render_bev's clause), black where np.sum of the row in NumPy's order (numpy_row_sum of
+ *      csrc/avl_render.h) is 0.  With thresholds it is render_bev_map_with_thresholds' rule instead: the share R[..][ch] / sum in
+ *      the map's type against the threshold rounded to that type, priorities from low to high, later ones overwrite.
+ *      For k = 1 the picture is byte-equal to avl_render_bev_map(_thresholds) on the assembled rectangle.
+ *   4. absent tiles: a tile of the rectangle without a table entry (it is neither in the window nor in the store, or it is empty)
+ *      gives black pixels and R = +0.
+ * The caller owns the table's validity, as for avl_tile_job: src and src_pitch 16-byte aligned, every tile inside the buffer it
+ * belongs to, row / col inside nh x nw, no (row, col) twice.  scroll.validate_sources checks that on the host before the upload. */
+typedef struct avl_tile_src {
+    const void* src;      /* first byte of the tile: T rows of T * C * sizeof(map type) bytes                                   */
+    int64_t src_pitch;    /* bytes between tile rows: Wm * bytes_per_cell for a tile of the window, T * bytes_per_cell for a slab */
+    int32_t row, col;     /* the tile's place inside the rectangle of nh x nw tiles                                              */
+} avl_tile_src;
+
+/* The overview of tiles_dev[0 .. n_tiles), a DEVICE array, by the rule above, in one launch on `stream`: picture uint8
+ * [nh*T/k][nw*T/k][3], reduced (map type, or NULL: the picture only) [nh*T/k][nw*T/k][C].  colors_host uint8[C][3];
+ * thresholds_host double[C] or NULL = the arg-max renderer; priority_host int32[C] or NULL = 0 .. C-1 (read with thresholds only).
+ * The call zero-fills picture, and reduced if given, stream-ordered before the kernel, and launches only the listed tiles; it
+ * allocates nothing, copies nothing from the host and waits for nothing.  n_tiles == 0 does the zero fill alone.  AVL_E_ARG, before
+ * any GPU work: k < 1 or tile_cells % k != 0, tile_cells outside 1 .. 16384, C outside 1 .. AVL_MAX_MAP_CLASSES, a map_dtype that is
+ * neither AVL_F64 nor AVL_F32, a tile row (tile_cells * C elements) that is no multiple of 16 bytes, nh or nw <= 0, n_tiles outside
+ * 0 .. nh * nw, an output of 2^31 pixels or more, a NULL picture or colors_host, a NULL tiles_dev with n_tiles > 0, a tiles_dev that
+ * is not 8-byte aligned, a reduced that is not aligned to its element, a priority outside 0 .. C-1. */
+int avl_site_overview(const avl_tile_src* tiles_dev, int n_tiles, int nh, int nw, int tile_cells, int C, int map_dtype, int k,
+                      const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, uint8_t* picture,
+                      void* reduced, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

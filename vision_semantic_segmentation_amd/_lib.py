@@ -79,6 +79,11 @@ class AvlTileJob(C.Structure):
     ]
 
 
+class AvlTileSrc(C.Structure):
+    """struct avl_tile_src of include/avl_hip.h"""
+    _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_int64), ("row", C.c_int32), ("col", C.c_int32)]
+
+
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
 _SIGNATURES = {
@@ -147,6 +152,7 @@ _SIGNATURES = {
     "avl_points_map_window": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "avl_points_map_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "avl_tile_copy": (_i, [_vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp]),
+    "avl_site_overview": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

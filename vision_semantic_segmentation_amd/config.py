@@ -244,6 +244,16 @@ def get_cfg_defaults():
     C.MAPPING.SCROLL.TILE_M = 10.0
     C.MAPPING.SCROLL.HYSTERESIS_TILES = 1
     C.MAPPING.SCROLL.POOL_CHUNK_TILES = 64
+    # build-specific: the picture of a whole scrolled site (SemanticMapping.site_overview: one kernel from the tiles, where they live,
+    # to a grid reduced by k x k cells per pixel and its picture; the rule: include/avl_hip.h, avl_tile_src).  ENABLED: finish_run()
+    # of a scrolling map also writes site_map.png; off, nothing of it runs.  CELLS_PER_PIXEL 0 = the smallest divisor of the tile size
+    # for which the picture's longer side is at most MAX_SIDE_PX.  THRESHOLDS [] = the arg-max renderer (render_bev_map's rule), else
+    # one share per class (render_bev_map_with_thresholds' rule)
+    C.MAPPING.SITE_OVERVIEW = CfgNode()
+    C.MAPPING.SITE_OVERVIEW.ENABLED = False
+    C.MAPPING.SITE_OVERVIEW.CELLS_PER_PIXEL = 0
+    C.MAPPING.SITE_OVERVIEW.MAX_SIDE_PX = 4096
+    C.MAPPING.SITE_OVERVIEW.THRESHOLDS = []
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

@@ -1,0 +1,226 @@
+// The site overview: a grid reduced by k x k cells per pixel, and its picture, straight from the tiles of a scrolled map (not in the
+// reference: its grid is the fixed rectangle of MAPPING.BOUNDARY).  The tiles stay where they live -- the window buffer, the slabs of
+// the tile store -- and every byte of every listed tile is read once (the rule: struct avl_tile_src in include/avl_hip.h;
+// vision_semantic_segmentation_amd/scroll.py builds and validates the table).
+//
+//   k_site_overview   one table entry = one tile of P = T / k pixel rows, split over `split` workgroups by pixel rows.  A pixel row is
+//                     a strip of k tile rows; the workgroup takes it in column chunks of qn pixels and each chunk in STAGES: a stage is
+//                     rs tile rows of the chunk in LDS, loaded with 16 bytes per lane, lanes walking a tile row contiguously (the span
+//                     is widened to 16-byte bounds, which stay inside the tile row).  Thread idx = q * C + c then folds the stage into
+//                     the accumulator of pixel q, class c in the rule's order -- di outer, dj inner, acc = acc + cell -- and keeps
+//                     the accumulator in LDS between stages, so a strip of any size works: k = T at T = 100, C = 5, f64 is 400 KB and
+//                     goes through in ten stages.  A pixel whose single tile row exceeds a stage is walked in column parts of cw < k
+//                     cells with rs = 1 and qn = 1, which is still the rule's order.  After the last stage the chunk's R leaves as
+//                     one contiguous run, its colours are staged in LDS and leave as one contiguous run of bytes (dwords where the
+//                     address allows).  No atomics, no ordering between workgroups: every output byte has one writer, and the pixels
+//                     of tiles without an entry keep the zero fill that avl_site_overview puts in front of the kernel.
+//
+// Built with -ffp-contract=off, like every translation unit that includes avl_render.h.
+#include "avl_render.h"
+
+#include <cstdint>
+
+namespace {
+
+using avl::RenderParams;
+
+constexpr int kBlock = 256;
+constexpr int kTargetWorkgroups = 8192;                  // a handful of tiles is split until the machine is full
+constexpr int kStageBytes = 40960;                       // T = 100, C = 5, f64, k = 10: the whole strip of 10 rows of 4000 bytes (+ 16) is one stage
+constexpr int kAccBytes = 8192;                          // accumulators of one chunk; with the colours, LDS stays below 64 KiB
+
+struct OverviewShape {
+    int C, k, P, split;             // P = T / k pixel rows and columns per tile
+    int qn, cw, rs;                 // a chunk's pixels, a stage's cells per pixel (k unless a pixel's row exceeds a stage), a stage's rows
+    int pitch;                      // bytes between the rows of a stage in LDS, a multiple of 16
+    int stage_bytes;                // rs * pitch
+    int thresholds;                 // 0: k_render_bev's rule, 1: k_render_thresholds'
+    long long wpx;                  // pixels per output row, nw * P
+};
+
+// the colour of one reduced row: k_render_bev's rule (mapping.hip), restated -- first maximum wins, a NaN beats every number and the
+// first NaN wins; black where np.sum of the row is 0
+template <typename MapT>
+__device__ __forceinline__ void argmax_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
+    MapT best = row[0];
+    int bi = 0;
+    for (int c = 1; c < C; ++c) {
+        const MapT v = row[c];
+        if (v > best || (v != v && best == best)) { best = v; bi = c; }
+    }
+    unsigned char r = rp.colors[3 * bi], g = rp.colors[3 * bi + 1], b = rp.colors[3 * bi + 2];
+    if (avl::numpy_row_sum(row, C) == (MapT)0) r = g = b = 0;
+    rgb[0] = r; rgb[1] = g; rgb[2] = b;
+}
+
+// k_render_thresholds' rule (mapping.hip), restated: the share is a MapT quotient compared with the threshold in MapT, priorities
+// from low to high, later ones overwrite
+template <typename MapT>
+__device__ __forceinline__ void thresholds_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
+    const MapT s = avl::numpy_row_sum(row, C);
+    unsigned char r = 0, g = 0, b = 0;
+    if (s != (MapT)0) {
+        for (int i = 0; i < C; ++i) {
+            const int ch = rp.priority[i];
+            const MapT pn = row[ch] / s;
+            if (pn >= (MapT)rp.thresholds[i]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
+        }
+    }
+    rgb[0] = r; rgb[1] = g; rgb[2] = b;
+}
+
+template <typename MapT>
+__global__ void __launch_bounds__(kBlock) k_site_overview(const avl_tile_src* __restrict__ tiles, int n_tiles, OverviewShape s, RenderParams rp,
+                                                          unsigned char* __restrict__ picture, MapT* __restrict__ reduced) {
+    extern __shared__ uint4 lds[];
+    char* stage = reinterpret_cast<char*>(lds);
+    MapT* acc = reinterpret_cast<MapT*>(stage + s.stage_bytes);
+    unsigned char* pix = reinterpret_cast<unsigned char*>(acc + s.qn * s.C);         // qn * C elements: a multiple of 4 bytes
+    const int tile_idx = (int)(blockIdx.x / (unsigned)s.split);
+    const int part = (int)(blockIdx.x % (unsigned)s.split);
+    if (tile_idx >= n_tiles) return;
+    const avl_tile_src tile = tiles[tile_idx];
+    const char* src = static_cast<const char*>(tile.src);
+    const int tid = threadIdx.x;
+    const int C = s.C, k = s.k, P = s.P;
+    const int cell_bytes = C * (int)sizeof(MapT);
+    const int pitch_elems = s.pitch / (int)sizeof(MapT);
+    for (int p = part; p < P; p += s.split) {                                         // workgroup-uniform, as every loop bound below
+        const long long prow = (long long)tile.row * P + p;
+        for (int q0 = 0; q0 < P; q0 += s.qn) {
+            const int nq = min(s.qn, P - q0), nout = nq * C;
+            const MapT* first = nullptr;                                              // the chunk's first cell of the stage's first row, in LDS
+            for (int di0 = 0; di0 < k; di0 += s.rs) {
+                const int nr = min(s.rs, k - di0);
+                for (int dj0 = 0; dj0 < k; dj0 += s.cw) {                             // one trip unless cw < k; then nq == 1 and nr == 1
+                    const int ncw = min(s.cw, k - dj0);
+                    const int b0 = (q0 * k + dj0) * cell_bytes;                       // the stage's bytes of a tile row: [b0, b1)
+                    const int b1 = b0 + ((nq - 1) * k + ncw) * cell_bytes;
+                    const int a0 = b0 & ~15;
+                    const int nvec = (((b1 + 15) & ~15) - a0) >> 4;                   // <= pitch / 16; [a0, a0 + 16 * nvec) is inside the tile row
+                    __syncthreads();                                                  // the stage's last readers are done
+                    for (int v = tid; v < nr * nvec; v += kBlock) {
+                        const int r = v / nvec, c = v - r * nvec;
+                        const uint4* g = reinterpret_cast<const uint4*>(src + (long long)(p * k + di0 + r) * tile.src_pitch + a0);
+                        *reinterpret_cast<uint4*>(stage + r * s.pitch + 16 * c) = g[c];
+                    }
+                    __syncthreads();
+                    first = reinterpret_cast<const MapT*>(stage + (b0 - a0));
+                    for (int idx = tid; idx < nout; idx += kBlock) {
+                        const int q = idx / C, c = idx - q * C;
+                        MapT a = (di0 == 0 && dj0 == 0) ? (MapT)0 : acc[idx];
+                        const MapT* cell = first + q * k * C + c;
+                        for (int r = 0; r < nr; ++r)
+                            for (int dj = 0; dj < ncw; ++dj) a = a + cell[r * pitch_elems + dj * C];
+                        acc[idx] = a;
+                    }
+                }
+            }
+            __syncthreads();                                                          // acc holds R of the chunk
+            for (int q = tid; q < nq; q += kBlock) {
+                if (s.thresholds) thresholds_colour(acc + q * C, C, rp, pix + 3 * q);
+                else argmax_colour(acc + q * C, C, rp, pix + 3 * q);
+            }
+            const long long px0 = prow * s.wpx + (long long)tile.col * P + q0;       // the chunk's first pixel
+            if (reduced != nullptr) {
+                MapT* out = reduced + px0 * C;
+                for (int idx = tid; idx < nout; idx += kBlock) out[idx] = acc[idx];
+            }
+            __syncthreads();                                                          // the colours are staged
+            unsigned char* out = picture + 3 * px0;
+            const int n = 3 * nq;
+            const int head = min((int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(out) & 3u)) & 3u), n);
+            const int body = (n - head) >> 2;                                          // dwords from the first 4-byte bound on
+            for (int i = tid; i < body; i += kBlock) {
+                const unsigned char* b = pix + head + 4 * i;
+                reinterpret_cast<unsigned*>(out + head)[i] = (unsigned)b[0] | (unsigned)b[1] << 8 | (unsigned)b[2] << 16 | (unsigned)b[3] << 24;
+            }
+            const int rest = n - head - 4 * body;                                      // < 4 bytes in front and < 4 behind
+            if (tid < head) out[tid] = pix[tid];
+            else if (tid < head + rest) out[4 * body + tid] = pix[4 * body + tid];
+        }
+    }
+}
+
+int fill_params(RenderParams& rp, int C, const uint8_t* colors, const int32_t* priority, const double* thresholds) {
+    memset(&rp, 0, sizeof(rp));
+    memcpy(rp.colors, colors, 3 * (size_t)C);
+    for (int i = 0; i < C; ++i) {
+        rp.priority[i] = priority ? priority[i] : i;
+        AVL_REQUIRE(rp.priority[i] >= 0 && rp.priority[i] < C, "avl_site_overview: priority[%d] = %d", i, rp.priority[i]);
+        rp.thresholds[i] = thresholds ? thresholds[i] : 0.0;
+    }
+    return AVL_OK;
+}
+
+int round16(int v) { return (v + 15) & ~15; }
+
+}  // namespace
+
+extern "C" {
+
+int avl_site_overview(const avl_tile_src* tiles_dev, int n_tiles, int nh, int nw, int tile_cells, int C, int map_dtype, int k,
+                      const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, uint8_t* picture,
+                      void* reduced, void* stream) {
+    AVL_REQUIRE(tile_cells >= 1 && tile_cells <= (1 << 14), "avl_site_overview: tile_cells = %d (1 .. 16384)", tile_cells);
+    AVL_REQUIRE(k >= 1 && tile_cells % k == 0, "avl_site_overview: k = %d cells per pixel does not divide tile_cells = %d", k, tile_cells);
+    AVL_REQUIRE(C >= 1 && C <= AVL_MAX_MAP_CLASSES, "avl_site_overview: C = %d (1 .. %d)", C, AVL_MAX_MAP_CLASSES);
+    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "avl_site_overview: map dtype %d", map_dtype);
+    const int es = map_dtype == AVL_F64 ? 8 : 4;
+    AVL_REQUIRE((tile_cells * C * es) % 16 == 0, "avl_site_overview: a tile row of %d cells of %d bytes is no multiple of 16 bytes", tile_cells,
+                C * es);
+    AVL_REQUIRE(nh > 0 && nw > 0, "avl_site_overview: a rectangle of nh = %d x nw = %d tiles", nh, nw);
+    AVL_REQUIRE(n_tiles >= 0 && (long long)n_tiles <= (long long)nh * nw, "avl_site_overview: n_tiles = %d (0 .. nh * nw = %lld)", n_tiles,
+                (long long)nh * nw);
+    const int P = tile_cells / k;
+    const long long hpx = (long long)nh * P, wpx = (long long)nw * P;                 // each below 2^45
+    AVL_REQUIRE(hpx < (1ll << 31) && wpx < (1ll << 31) && hpx * wpx < (1ll << 31), "avl_site_overview: an output of %lld x %lld pixels (below 2^31)",
+                hpx, wpx);
+    AVL_REQUIRE(picture != nullptr && colors_host != nullptr, "avl_site_overview: picture or colors_host is NULL");
+    AVL_REQUIRE(n_tiles == 0 || tiles_dev != nullptr, "avl_site_overview: tiles_dev is NULL for %d tiles", n_tiles);
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(tiles_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(reduced) & (uintptr_t)(es - 1)) == 0,
+                "avl_site_overview: tiles_dev or reduced is misaligned");
+    RenderParams rp;
+    int rc;
+    if ((rc = fill_params(rp, C, colors_host, priority_host, thresholds_host))) return rc;
+
+    const size_t npx = (size_t)(hpx * wpx);
+    AVL_HIP_CHECK(hipMemsetAsync(picture, 0, npx * 3, avl::as_stream(stream)));
+    if (reduced != nullptr) AVL_HIP_CHECK(hipMemsetAsync(reduced, 0, npx * (size_t)C * (size_t)es, avl::as_stream(stream)));
+    if (n_tiles == 0) return AVL_OK;
+
+    OverviewShape s;
+    s.C = C; s.k = k; s.P = P; s.wpx = wpx; s.thresholds = thresholds_host != nullptr;
+    const int cell_bytes = C * es;
+    const long long px_row = (long long)k * cell_bytes;                               // one pixel's bytes of a tile row
+    if (px_row + 16 > kStageBytes) {                                                  // a pixel's row in column parts
+        s.cw = (kStageBytes - 16) / cell_bytes; s.rs = 1; s.qn = 1;
+    } else {
+        s.cw = k;
+        const long long rows_px = (long long)k * (px_row + 16);                       // all k rows of one pixel
+        if (rows_px > kStageBytes) { s.qn = 1; s.rs = (int)(kStageBytes / (px_row + 16)); }
+        else {
+            s.rs = k;
+            long long qn = (kStageBytes / k - 16) / px_row;
+            if (qn > kAccBytes / cell_bytes) qn = kAccBytes / cell_bytes;
+            s.qn = (int)(qn > P ? P : (qn < 1 ? 1 : qn));
+        }
+    }
+    s.pitch = round16((int)(s.qn > 1 ? s.qn * px_row : (long long)s.cw * cell_bytes)) + 16;
+    s.stage_bytes = s.rs * s.pitch;
+    const size_t lds_bytes = (size_t)s.stage_bytes + (size_t)round16(s.qn * cell_bytes) + (size_t)round16(3 * s.qn);
+    // workgroups per tile: enough that few tiles still fill the machine, never more than the tile has pixel rows
+    int split = (kTargetWorkgroups + n_tiles - 1) / n_tiles;
+    s.split = split < 1 ? 1 : (split > P ? P : split);
+    const dim3 grid((unsigned)n_tiles * (unsigned)s.split), block(kBlock);
+    if (map_dtype == AVL_F64)
+        hipLaunchKernelGGL(k_site_overview<double>, grid, block, lds_bytes, avl::as_stream(stream), tiles_dev, n_tiles, s, rp, picture,
+                           static_cast<double*>(reduced));
+    else
+        hipLaunchKernelGGL(k_site_overview<float>, grid, block, lds_bytes, avl::as_stream(stream), tiles_dev, n_tiles, s, rp, picture,
+                           static_cast<float*>(reduced));
+    AVL_LAUNCH_CHECK();
+    return AVL_OK;
+}
+
+}  // extern "C"

@@ -44,7 +44,8 @@ What differs from the reference, by design:
   * with MAPPING.SCROLL.ENABLED the grid is a window that follows the vehicle: its origin moves in whole tiles (``scroll_to()``, called
     by ``mapping()`` / ``mapping_views()``), tiles that leave are kept in a store in HBM and come back when the vehicle returns
     (scroll.py; ``site_map()``, ``site_tiles()``, ``save_site()``, ``load_site()``).  The reference drops every point outside
-    MAPPING.BOUNDARY.  Off by default.
+    MAPPING.BOUNDARY.  Off by default.  ``site_overview()`` is the picture of the whole site at k cells per pixel, rendered from the
+    tiles where they live; with MAPPING.SITE_OVERVIEW.ENABLED ``finish_run()`` also writes it as site_map.png.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -317,6 +318,7 @@ class SemanticMapping(object):
         self.last_scroll = None                # {"shift": (di, dj) in tiles, "leaving", "entering", "loaded", "filled"} of the last scroll
         self.scroll_count = 0
         self._scroll = None                    # scroll.TileStore
+        self.last_site_overview = None         # {"rect": (ti0, ti1, tj0, tj1), "cells_per_pixel": k, "tiles": entries launched} of the last site_overview
         if self.scroll_enabled():
             from .scroll import TileStore
             self._scroll = TileStore(self)     # ValueError for a tile size that does not fit the grid, and for the planar mode
@@ -687,14 +689,17 @@ class SemanticMapping(object):
         """The shutdown branch of mapping() (mapping.py:323-345): dump the recorded inputs, smooth the grid
         (apply_filter), render it (render_bev_map), write global_map.png and -- with GROUND_TRUTH_DIR set --
         print IoU / accuracy / missing rate.  Filter, renderer and evaluation are GPU kernels; only the PNG and
-        the printed numbers leave the device.  Returns the colour map (uint8 [Hm,Wm,3] NumPy)."""
+        the printed numbers leave the device.  Returns the colour map (uint8 [Hm,Wm,3] NumPy).  A scrolling map with
+        MAPPING.SITE_OVERVIEW.ENABLED first writes site_map.png, the overview of the whole, unfiltered site (site_overview)."""
         from .evaluation import Test
         from .renderer import apply_filter, render_bev_map
         if self.record_inputs and self.input_list:
             self.save_inputs()
         output_dir = output_dir or self.output_dir
         os.makedirs(output_dir, exist_ok=True)
-        smooth = apply_filter(self.map_dev)                                      # :332, the filtered grid replaces the map
+        if self._scroll is not None and self.cfg.MAPPING.SITE_OVERVIEW.ENABLED:
+            self._write_site_overview(output_dir)                                # before the filter: window and store in one state
+        smooth = apply_filter(self.map_dev)                                   # :332, the filtered grid replaces the map
         self.map_dev.copy_(smooth.to(self.map_dev.dtype))
         self._map_host = None
         color_dev = render_bev_map(self.map_dev, self.label_colors)              # :334
@@ -710,6 +715,24 @@ class SemanticMapping(object):
         if self.ground_truth_dir != "":                                          # :342-345
             Test(ground_truth_dir=self.ground_truth_dir, logger=self.logger).test_single_map(color_dev)
         return color_map
+
+    def _write_site_overview(self, output_dir):
+        """site_map.png: site_overview() with MAPPING.SITE_OVERVIEW's settings, of the unfiltered site (global_map.png is the filtered
+        window).  Channel order and the .npy fallback are global_map.png's."""
+        (i0, j0), picture = self.site_overview()
+        picture = picture.cpu().numpy()
+        if picture.size == 0:
+            self.logger.log("The site is empty: no site_map.png")
+            return
+        k = self.last_site_overview["cells_per_pixel"]
+        output_file = osp.join(output_dir, "site_map.png")
+        try:
+            from PIL import Image
+            Image.fromarray(np.ascontiguousarray(picture[:, :, ::-1])).save(output_file)
+        except ImportError:
+            output_file = output_file[:-4] + ".npy"
+            np.save(output_file, picture)
+        self.logger.log("Saving the site overview to %s: first cell (%d, %d), %d cells per pixel" % (output_file, i0, j0, k))
 
     # ------------------------------------------------------------------ live vehicle-centred map
     def live_map_window(self, pose, size_cells=None):
@@ -1484,6 +1507,25 @@ class SemanticMapping(object):
         the store are left as they are.  render_bev_map(site_map()[1]) is the picture of the whole site."""
         with self._lock:
             return self._scroll_store().site_map(rect, layer, stream)
+
+    def site_overview(self, cells_per_pixel=None, rect=None, thresholds=None, priority=None, reduced=False, out=None, stream=None):
+        """-> ((i0, j0), picture) or, with ``reduced``, ((i0, j0), picture, R): the tile rectangle ``rect`` (as site_map's; None = the
+        bounding rectangle of site_tiles("map")) at ``cells_per_pixel`` = k cells per pixel, by one kernel that reads the tiles where
+        they live (avl_site_overview; the rule: include/avl_hip.h).  R [h, w, C] is the k x k sum of every class in the map's type and
+        a fixed order, picture uint8 [h, w, 3] is render_bev_map's rule on R -- with ``thresholds`` render_bev_map_with_thresholds'
+        with ``priority`` -- and black where nothing was mapped; h = tile rows * T / k.  k must divide the tile size; None =
+        MAPPING.SITE_OVERVIEW.CELLS_PER_PIXEL, where 0 chooses the smallest k whose picture has no side above MAX_SIDE_PX.
+        ``thresholds`` None = MAPPING.SITE_OVERVIEW.THRESHOLDS ([] = arg-max).  ``out``: a contiguous uint8 CUDA tensor of the
+        picture's shape.  An empty site gives a 0 x 0 x 3 picture and launches nothing.  Nothing of the site is assembled: cost and
+        memory follow the mapped tiles and the output.  Same stream contract as site_map; the window and the store are only read."""
+        oc = self.cfg.MAPPING.SITE_OVERVIEW
+        if cells_per_pixel is None:
+            cells_per_pixel = int(oc.CELLS_PER_PIXEL)
+        if thresholds is None:
+            thresholds = list(oc.THRESHOLDS)
+        with self._lock:
+            return self._scroll_store().site_overview(cells_per_pixel, rect, self.label_colors, thresholds, priority, reduced, out, stream,
+                                                      int(oc.MAX_SIDE_PX))
 
     def save_site(self, path, stream=None):
         """The whole site -- the window's own tiles included -- as one .npz: anchor, resolution, T, C, dtype and, per layer, the

@@ -17,6 +17,10 @@ DEVICE WORK is one operation, a table of tile jobs (struct avl_tile_job of inclu
 scroll, a reload, the assembly of a site and a save build such a table on the host, VALIDATE it on the host -- every source and
 destination range inside the buffer it names, validate_jobs -- and launch it once per layer.  A table that fails is never launched.
 
+THE SITE OVERVIEW (TileStore.site_overview) is the one reader that assembles nothing: a table of tile SOURCES (struct avl_tile_src,
+k_site_overview of csrc/seg_overview.hip), built with index arithmetic on whole arrays (overview_sources), validated on the host
+(validate_sources) and launched once, gives the site reduced by k x k cells per pixel and its picture.
+
 THE STORE.  One pool per layer (the map; with MAPPING.ELEVATION its four arrays), made of chunks of POOL_CHUNK_TILES slabs of
 T * T * bytes_per_cell bytes; a chunk is a CUDA tensor.  The pool grows by whole chunks, so a stored tile never moves and jobs carry
 plain device addresses.  The host owns the directory {(ti, tj): slab} and the free list; a slab index names the same slot in every
@@ -214,6 +218,108 @@ def encode_jobs(jobs, buffers, out):
     return n
 
 
+# ------------------------------------------------------------------------------------------------ the overview's source table
+SOURCE_DTYPE = np.dtype([("buf", "<i4"), ("row", "<i4"), ("col", "<i4"), ("off", "<i8"), ("pitch", "<i8")])
+"""One tile of a site overview in host form: ``buf`` indexes a list of buffers -- 0 the window, 1 + c chunk c of the pool -- ``off`` and
+``pitch`` are bytes, (``row``, ``col``) is the tile's place in the rectangle.  encode_sources turns it into struct avl_tile_src."""
+
+SRC_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("row", "<i4"), ("col", "<i4")])
+
+
+def overview_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, stored_slabs, chunk_tiles):
+    """The source table (SOURCE_DTYPE, sorted by row, col) of the tile rectangle ``rect`` = (ti0, ti1, tj0, tj1), both ends included:
+    one record per tile that holds something, none for the others.  ``window_mask``: bool [Ht, Wt], the window's tiles that hold
+    something (None: the window holds nothing), the window's first tile being ``origin_tile``; ``stored_tiles`` int [n, 2] and
+    ``stored_slabs`` int [n]: the stored tiles that hold something and their slabs.  Index arithmetic on whole arrays: the cost
+    follows what was mapped, not the rectangle."""
+    ti0, ti1, tj0, tj1 = (int(v) for v in rect)
+    nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+    parts = []
+    if window_mask is not None:
+        wi, wj = np.nonzero(np.asarray(window_mask))
+        part = np.zeros(wi.size, dtype=SOURCE_DTYPE)
+        part["off"], part["pitch"] = (wi.astype(np.int64) * (T * Wm) + wj.astype(np.int64) * T) * bpc, Wm * bpc
+        parts.append((part, wi + int(origin_tile[0]) - ti0, wj + int(origin_tile[1]) - tj0))
+    stored_tiles = np.asarray(stored_tiles, dtype=np.int64).reshape(-1, 2)
+    slabs = np.asarray(stored_slabs, dtype=np.int64).reshape(-1)
+    part = np.zeros(slabs.size, dtype=SOURCE_DTYPE)
+    part["buf"] = 1 + slabs // chunk_tiles
+    part["off"], part["pitch"] = (slabs % chunk_tiles) * (T * T * bpc), T * bpc
+    parts.append((part, stored_tiles[:, 0] - ti0, stored_tiles[:, 1] - tj0))
+    kept = []
+    for part, r, c in parts:                                   # the window and the store: two trips
+        inside = (r >= 0) & (r < nh) & (c >= 0) & (c < nw)
+        part = part[inside]
+        part["row"], part["col"] = r[inside], c[inside]
+        kept.append(part)
+    table = np.concatenate(kept)
+    return table[np.lexsort((table["col"], table["row"]))]
+
+
+def validate_sources(table, buffers, T, bpc, nh, nw):
+    """ValueError unless every record of the source table is safe to launch.  ``buffers``: [(device address, bytes)], indexed by
+    ``buf``.  Every tile -- T rows of T * bpc bytes, ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a
+    multiple of 16 and a pitch is at least a row; row and col are inside nh x nw; no (row, col) appears twice."""
+    row = T * bpc
+    if bpc % 4 != 0 or not 4 <= bpc <= 128 or row % 16 != 0:
+        raise ValueError("tile sources: bytes_per_cell = %d, T = %d (bytes_per_cell a multiple of 4 up to 128, T * bytes_per_cell of 16)" % (bpc, T))
+    n = len(table)
+    if n == 0:
+        return
+
+    def refuse(bad, what):
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("tile source %d of %d %s: %r" % (k, n, what, table[k]))
+    buf = table["buf"].astype(np.int64)
+    bad = (buf < 0) | (buf >= len(buffers))
+    if bad.any():
+        refuse(bad, "names a buffer outside the %d given" % len(buffers))
+    base = np.array([b[0] for b in buffers], dtype=np.int64)[buf]
+    nbytes = np.array([b[1] for b in buffers], dtype=np.int64)[buf]
+    off, pitch = table["off"], table["pitch"]
+    bad = (pitch % 16 != 0) | (pitch < row)
+    if bad.any():
+        refuse(bad, "has a pitch that is misaligned or shorter than a tile row of %d bytes" % row)
+    bad = (base + off) % 16 != 0
+    if bad.any():
+        refuse(bad, "is not 16-byte aligned")
+    bad = (off < 0) | (off + (T - 1) * pitch + row > nbytes)
+    if bad.any():
+        refuse(bad, "leaves its buffer")
+    r, c = table["row"].astype(np.int64), table["col"].astype(np.int64)
+    bad = (r < 0) | (r >= nh) | (c < 0) | (c >= nw)
+    if bad.any():
+        refuse(bad, "lies outside the rectangle of %d x %d tiles" % (nh, nw))
+    place = r * nw + c
+    order = np.argsort(place, kind="stable")
+    twice = np.flatnonzero(np.diff(place[order]) == 0)
+    if twice.size:
+        bad = np.zeros(n, dtype=bool)
+        bad[order[twice[0] + 1]] = True
+        refuse(bad, "names a (row, col) that an earlier record names")
+
+
+def encode_sources(table, buffers, out):
+    """``table`` as struct avl_tile_src records into the structured array ``out`` (SRC_DTYPE, at least len(table) long)."""
+    n = len(table)
+    if n:
+        base = np.array([b[0] for b in buffers], dtype=np.uint64)
+        out["src"][:n] = base[table["buf"]] + table["off"].astype(np.uint64)
+        out["src_pitch"][:n] = table["pitch"]
+        out["row"][:n] = table["row"]
+        out["col"][:n] = table["col"]
+    return n
+
+
+def overview_cells_per_pixel(T, nh, nw, max_side_px):
+    """MAPPING.SITE_OVERVIEW.CELLS_PER_PIXEL = 0: the smallest divisor k of T for which the longer side of the picture of nh x nw tiles,
+    max(nh, nw) * T / k pixels, is at most ``max_side_px``; T (one pixel per tile) when none is."""
+    for k in range(1, T + 1):
+        if T % k == 0 and max(nh, nw) * (T // k) <= max_side_px:
+            return k
+    return T
+
+
 # ------------------------------------------------------------------------------------------------ the site file
 def pack_site(anchor, resolution, T, C_, dtype, layers):
     """The arrays of a site file (one .npz).  ``layers``: {layer name: (coords int [n, 2], tiles [n, T, T, ...])}."""
@@ -341,6 +447,21 @@ class TileStore(object):
             return stream
         return torch.cuda.ExternalStream(int(stream), device=self.sm.device)
 
+    def _ring_slot(self, nbytes):
+        """[pinned host uint8, device uint8, event] for a table of ``nbytes``: the ring's next slot, waited for if its last table is
+        still in flight, grown if it is too small.  The caller fills the host part, copies it on its stream and records the event."""
+        torch = self.torch
+        turn = self.table_turn
+        self.table_turn ^= 1
+        slot = self.tables[turn]
+        if slot is not None:
+            slot[2].synchronize()                                          # a table in flight is not overwritten
+        if slot is None or int(slot[0].numel()) < nbytes:
+            cap = max(2 * nbytes, 1 << 14)
+            slot = self.tables[turn] = [torch.empty(cap, dtype=torch.uint8).pin_memory(),
+                                        torch.empty(cap, dtype=torch.uint8, device=self.sm.device), torch.cuda.Event()]
+        return slot
+
     def _run(self, per_layer, st, n_flags=0):
         """``per_layer``: [(layer, jobs, buffers)], all validated here, uploaded as one table through the ring and launched once per
         layer on the torch stream ``st``; with ``n_flags`` every layer's flags go to flags_dev[l * n_flags ...] and their copy into
@@ -352,16 +473,7 @@ class TileStore(object):
             validate_jobs(jobs, buffers, self.T, L.bpc, n_flags)          # raises before anything is uploaded or launched
         total = sum(len(jobs) for _, jobs, _ in per_layer)
         nbytes = max(total, 1) * JOB_DTYPE.itemsize
-        turn = self.table_turn
-        self.table_turn ^= 1
-        slot = self.tables[turn]
-        if slot is not None:
-            slot[2].synchronize()                                          # a table in flight is not overwritten
-        if slot is None or int(slot[0].numel()) < nbytes:
-            cap = max(2 * nbytes, 1 << 14)
-            slot = self.tables[turn] = [torch.empty(cap, dtype=torch.uint8).pin_memory(),
-                                        torch.empty(cap, dtype=torch.uint8, device=self.sm.device), torch.cuda.Event()]
-        host, dev, event = slot
+        host, dev, event = self._ring_slot(nbytes)
         rec = host.numpy()[:nbytes].view(JOB_DTYPE)
         at, starts = 0, []
         for L, jobs, buffers in per_layer:
@@ -477,18 +589,25 @@ class TileStore(object):
     # -------------------------------------------------------------------------------------------- the site
     def _window_nonempty(self):
         """{tile of the window: mask of its non-empty layers}, by bit pattern (a -0.0 is something)"""
-        torch = self.torch
         if not self.window_valid:
             return {}
+        masks = self._window_masks()
+        a, b = self.origin[0] // self.T, self.origin[1] // self.T
+        return {(a + i, b + j): int(masks[i, j]) for i in range(self.Ht) for j in range(self.Wt) if masks[i, j]}
+
+    def _window_masks(self, bits=-1):
+        """int64 ndarray [Ht, Wt]: per tile of the window the mask of its non-empty layers, by bit pattern; only the layers of ``bits``
+        are looked at"""
+        torch = self.torch
         T, masks = self.T, None
         for l, L in enumerate(self._layers()):
+            if not bits >> l & 1:
+                continue
             words = L.get().contiguous().view(torch.int32).view(self.Ht, T, self.Wt, T, L.bpc // 4)
             fill = L.fill - (1 << 32) if L.fill >= (1 << 31) else L.fill
             some = words.ne(fill).any(dim=4).any(dim=3).any(dim=1).to(torch.int64) << l
             masks = some if masks is None else masks | some
-        masks = masks.cpu().numpy()
-        a, b = self.origin[0] // T, self.origin[1] // T
-        return {(a + i, b + j): int(masks[i, j]) for i in range(self.Ht) for j in range(self.Wt) if masks[i, j]}
+        return masks.cpu().numpy()
 
     def _layer_bits(self, layer):
         names = [L.name for L in self._layers()]
@@ -556,6 +675,87 @@ class TileStore(object):
         if tiles:
             self._run(per_layer, st)
         return (ti0 * T, tj0 * T), (outs[0] if layer == "map" else tuple(outs))
+
+    def overview_table(self, rect=None):
+        """-> (rect, source table, buffers) of the map layer: overview_sources on the window's non-empty tiles and the store's
+        directory and masks.  ``rect`` None = the bounding rectangle of what holds something, (0, -1, 0, -1) for an empty site."""
+        self.retire()
+        L = self._layers()[0]
+        T = self.T
+        window = (self._window_masks(1) & 1).astype(bool) if self.window_valid else None
+        masks = np.fromiter(self.nonempty.values(), dtype=np.int64, count=len(self.nonempty))
+        tiles = np.array(list(self.nonempty), dtype=np.int64).reshape(-1, 2)
+        slabs = np.fromiter(map(self.directory.__getitem__, self.nonempty), dtype=np.int64, count=len(self.nonempty))
+        has_map = (masks & 1) != 0
+        tiles, slabs = tiles[has_map], slabs[has_map]
+        origin_tile = (self.origin[0] // T, self.origin[1] // T)
+        if rect is None:
+            wi, wj = np.nonzero(window) if window is not None else (np.zeros(0, dtype=np.int64),) * 2
+            ti = np.concatenate([wi + origin_tile[0], tiles[:, 0]])
+            tj = np.concatenate([wj + origin_tile[1], tiles[:, 1]])
+            rect = (int(ti.min()), int(ti.max()), int(tj.min()), int(tj.max())) if ti.size else (0, -1, 0, -1)
+        rect = tuple(int(v) for v in rect)
+        table = overview_sources(rect, T, L.bpc, self.Wm, origin_tile, window, tiles, slabs, self.chunk_tiles)
+        buffers = [self._extent(L.get())] + [(c.data_ptr(), int(c.numel())) for c in L.chunks]
+        return rect, table, buffers
+
+    def site_overview(self, cells_per_pixel, rect=None, colors=None, thresholds=None, priority=None, reduced=False, out=None, stream=None,
+                      max_side_px=4096):
+        import ctypes as C
+        from . import _lib
+        torch = self.torch
+        sm = self.sm
+        rect, table, buffers = self.overview_table(rect)
+        ti0, ti1, tj0, tj1 = rect
+        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+        T, Cn = self.T, self.C
+        check_origin((ti0 * T, tj0 * T), T)
+        k = int(cells_per_pixel) if cells_per_pixel else overview_cells_per_pixel(T, nh, nw, int(max_side_px))
+        if k < 1 or T % k != 0:
+            raise ValueError("site_overview: cells_per_pixel = %d does not divide the tile size T = %d" % (k, T))
+        P = T // k
+        shape = (nh * P, nw * P, 3)
+        if shape[0] * shape[1] >= 1 << 31:
+            raise ValueError("site_overview: a picture of %d x %d pixels; choose more cells per pixel than %d" % (shape[0], shape[1], k))
+        st = self._stream(stream)
+        cur = self._layers()[0].get()
+        with torch.cuda.stream(st):
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=cur.device)
+            elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != cur.device or not out.is_contiguous():
+                raise ValueError("site_overview: out must be a contiguous uint8 tensor %r on %s" % (shape, cur.device))
+            red = torch.empty(shape[:2] + (Cn,), dtype=cur.dtype, device=cur.device) if reduced else None
+        result = ((ti0 * T, tj0 * T), out, red) if reduced else ((ti0 * T, tj0 * T), out)
+        sm.last_site_overview = {"rect": rect, "cells_per_pixel": k, "tiles": len(table)}
+        if nh == 0 or nw == 0:
+            return result                                                  # an empty site: nothing is launched
+        bpc = self._layers()[0].bpc
+        validate_sources(table, buffers, T, bpc, nh, nw)                   # raises before anything is uploaded or launched
+        colors = np.ascontiguousarray(np.asarray(sm.label_colors if colors is None else colors), dtype=np.uint8)
+        if colors.shape != (Cn, 3):
+            raise ValueError("site_overview: %r colours for %d classes" % (colors.shape, Cn))
+        col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
+        th = pr = None
+        if thresholds is not None and len(thresholds):
+            if len(thresholds) < Cn:
+                raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), Cn))
+            if priority is not None and len(priority) != Cn:
+                raise ValueError("Each channel should have a priority.")
+            th = (C.c_double * Cn)(*[float(x) for x in list(thresholds)[:Cn]])
+            pr = (C.c_int32 * Cn)(*[int(p) for p in (priority if priority is not None else range(Cn))])
+        n = len(table)
+        nbytes = max(n, 1) * SRC_DTYPE.itemsize
+        host, dev, event = self._ring_slot(nbytes)
+        encode_sources(table, buffers, host.numpy()[:nbytes].view(SRC_DTYPE))
+        dt = _lib.AVL_F64 if cur.dtype == torch.float64 else _lib.AVL_F32
+        with torch.cuda.stream(st):
+            if n:
+                dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+            rc = _lib.lib().avl_site_overview(C.c_void_p(dev.data_ptr()), n, nh, nw, T, Cn, dt, k, col, pr, th, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(red.data_ptr()) if reduced else None, C.c_void_p(st.cuda_stream))
+            _lib.check(rc, "avl_site_overview")
+            event.record(st)
+        return result
 
     def save_site(self, path, stream=None):
         torch = self.torch

@@ -1,7 +1,10 @@
-"""Per-launch times of the MX GEMMs from a rocprofv3 kernel trace of bench.py: the launches of one instantiation are told
+"""Per-launch times of a kernel family from a rocprofv3 kernel trace of bench.py: the launches of one instantiation are told
 apart by their place in the frame (every forward launches the same sequence), statistics are over the frames.
 
-    python3 tools/per_launch.py <dir with *kernel_trace.csv> <out.csv>
+    python3 tools/per_launch.py <dir with *kernel_trace.csv> <out.csv> [family regex]
+
+The family defaults to the MX GEMMs, k_gemm_(mx_pipe|ring_mx); k_gconv_mfma gives the grouped 3x3 launches (the nine MX ones of layer3 and
+layer4 are <f16,2,2,..>).
 """
 import csv
 import glob
@@ -10,11 +13,20 @@ import statistics
 import sys
 
 
-def main(root, out):
+def label(name, family):
+    """k_family<template arguments> of a mangled (Li<n>E, Lb<0|1>E, DF16_, DF16b) or demangled kernel name"""
+    m = re.search(r"(%s)I((?:DF16_|DF16b|Li\d+E|Lb[01]E)+)" % family, name)
+    if m:
+        args = [{"DF16_": "f16", "DF16b": "bf16"}.get(a, a[2:-1]) for a in re.findall(r"DF16_|DF16b|Li\d+E|Lb[01]E", m.group(2))]
+        return "%s<%s>" % (m.group(1), ",".join(args))
+    return re.search(r"(%s)<[^>]*>" % family, name).group(0).replace(" ", "")           # (a demangled trace)
+
+
+def main(root, out, family=r"k_gemm_(?:mx_pipe|ring_mx)"):
     rows = []
     for f in glob.glob(root + "/**/*kernel_trace.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            if re.search(r"k_gemm_(mx_pipe|ring_mx)", r["Kernel_Name"]):
+            if re.search(family, r["Kernel_Name"]):
                 rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     names = [r[2] for r in rows]
@@ -26,12 +38,10 @@ def main(root, out):
         for pos in range(period):
             us = [(rows[f * period + pos][1] - rows[f * period + pos][0]) / 1e3 for f in range(frames)]
             tot += statistics.median(us)
-            m = re.search(r"k_gemm_(mx_pipe|ring_mx)I((?:Li\d+E)+)", names[pos])
-            d = re.search(r"k_gemm_(mx_pipe|ring_mx)<[^>]*>", names[pos])           # (a demangled trace)
-            k = "k_gemm_%s<%s>" % (m.group(1), ",".join(re.findall(r"Li(\d+)E", m.group(2)))) if m else d.group(0).replace(" ", "")
+            k = label(names[pos], family)
             fo.write('"%s",%d,%d,%.2f,%.2f,%.2f,%.2f\n' % (k, pos, frames, statistics.mean(us), statistics.median(us), min(us), max(us)))
-    print("%s: %d MX GEMM launches per frame, %d frames, sum of medians %.1f us" % (out, period, frames, tot))
+    print("%s: %d launches per frame, %d frames, sum of medians %.1f us" % (out, period, frames, tot))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(*sys.argv[1:4])

@@ -1,7 +1,7 @@
 """Table of tools/pmc_mx_pipe.sh: per MX GEMM instantiation, counters summed over its launches of one forward, the
 instructions executed per MFMA by kind, and each unit's issue cycles as a share of the wave cycles.
 
-    python3 tools/pmc_mx_pipe_summary.py <dir with p1/ p2/>
+    python3 tools/pmc_mx_pipe_summary.py <dir with p1/ p2/> [family regex, default the MX GEMMs; e.g. k_gconv_mfma]
 """
 import collections
 import csv
@@ -10,21 +10,20 @@ import re
 import sys
 
 
-def short(name):
-    m = re.search(r"k_gemm_(mx_pipe|ring_mx)<[^>]*>", name)
-    if m:
-        return m.group(0)
-    m = re.search(r"k_gemm_(mx_pipe|ring_mx)I((?:Li\d+E)+)", name)
-    return "k_gemm_%s<%s>" % (m.group(1), ",".join(re.findall(r"Li(\d+)E", m.group(2)))) if m else None
+def short(name, family):
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import per_launch
+    return per_launch.label(name, family) if re.search(family, name) else None
 
 
-def main(root):
+def main(root, family=r"k_gemm_(?:mx_pipe|ring_mx)"):
     agg = collections.defaultdict(lambda: collections.defaultdict(float))
     launches = collections.defaultdict(set)
     for p in ("p1", "p2"):
         for f in glob.glob("%s/%s/**/*counter_collection.csv" % (root, p), recursive=True):
             for r in csv.DictReader(open(f)):
-                k = short(r["Kernel_Name"])
+                k = short(r["Kernel_Name"], family)
                 if k is None:
                     continue
                 agg[k][p + ":" + r["Counter_Name"]] += float(r["Counter_Value"])
@@ -46,4 +45,4 @@ def main(root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "/tmp/pmc_mx_pipe")
+    main(*(sys.argv[1:3] or ["/tmp/pmc_mx_pipe"]))

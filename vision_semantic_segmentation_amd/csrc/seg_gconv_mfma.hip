@@ -69,9 +69,32 @@ struct GconvArgs {
 // pixel and plane.
 // XS (WS = 1 only): the input is split too (f16 planes hi + lo): a second f16 tile in LDS and a third pass Wh . xl per tap -- every
 // operand of the 3x3 then carries ~22 bits (the complete-split plan of MODEL.MIXED_SELF_CHECK's ladder).
-template <typename HT, int WS, int NJ, bool XS = false>      // NJ = tile height / 2: sub-tiles per wave and tile
+//
+// ROWS (WS = 2, NJ = 2 only: the MX variant at stride 1 with tap distance 1 inside LDS -- dilation 1 or the comb -- on the four-row tile, which is
+// every conv2 of layer3 and layer4): the geometry is compile-time.  The LDS tile is 6 rows of PITCH = 40 pixels (34 used) instead of 6 x 34
+// packed densely, so
+//   * a DMA group is 8 pixels of ONE row: its image row, bounds test and row base are scalar, a lane keeps a column clamp and one multiply-add;
+//     PITCH % 8 == 0 makes the swizzle term pix & 7 the lane constant lx & 7 (columns 34 .. 39 fetch clamped in-image pixels that no tap reads);
+//   * the nine f16 taps of a sub-tile are THREE lane addresses (one per tap column, the wave's row folded in) + the compile-time byte offsets
+//     (2 j + r) * PITCH * 128 of ds_read_b128; the FP4 pixels and scale bytes are three lane addresses each (tap 4 g + kq) + immediates for
+//     plane and sub-tile; the scale byte is read as a byte (no shift-and-mask).  The nine addresses live in registers for the whole kernel
+//     and move between the two tile buffers by one add each per tile;
+//   * the tile indices (ty fastest, then tx, then the residue class: the walk order) are counters advanced at the loop latch, for the tile in
+//     the MFMA phase and for the one being staged: no division in the loop.
+// The MFMAs, their order and their operands are those of the general path: results are bit for bit the same.
+constexpr int ROWS_PITCH = 40, ROWS_IN_TH = 6;
+constexpr int ROWS_TILE_BYTES = ROWS_IN_TH * ROWS_PITCH * 128 + 4 * 4096 + 2 * 1024;      // f16 tile 30 KB + FP4 tiles 4 x 4 KB + scale dwords 2 x 1 KB = 48 KB
+static_assert(2 * ROWS_TILE_BYTES <= 160 * 1024 && ROWS_PITCH % 8 == 0 && ROWS_PITCH >= TW + 2, "two row-aligned tile buffers fit the CU's LDS");
+
+template <typename T>
+__device__ __forceinline__ T lds_load(unsigned byte_addr) {
+    return *(const __attribute__((address_space(3))) T*)(size_t)byte_addr;
+}
+
+template <typename HT, int WS, int NJ, bool XS = false, bool ROWS = false>      // NJ = tile height / 2: sub-tiles per wave and tile
 __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
     static_assert(!XS || WS == 1, "a split input goes with split weights");
+    static_assert(!ROWS || (WS == 2 && NJ == 2), "the row-aligned tile is the MX variant's four-row tile");
     typedef typename Half16<HT>::v8 v8;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -104,10 +127,13 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
     // Dilated layers (stride 1, pad = d): the outputs with (y mod d, x mod d) = (ry, rx) read only inputs of the same
     // residue class, so a tile is cut from that class's grid and is an ordinary d = 1 tile there: the halo is
     // (8+2) x (32+2) pixels instead of (8+2d) x (32+2d) (2.5x the tile at d = 4).
-    const int s = p.stride;
-    const int d = p.comb ? 1 : p.dil;            // tap distance inside the LDS tile
+    const int s = ROWS ? 1 : p.stride;
+    const int d = ROWS ? 1 : p.comb ? 1 : p.dil; // tap distance inside the LDS tile
     const int step = p.comb ? p.dil : 1;         // image pixels per tile-grid step
-    const int in_th = (p.th - 1) * s + 2 * d + 1, in_tw = (TW - 1) * s + 2 * d + 1;
+    const int th = ROWS ? 4 : p.th;
+    // (ROWS: in_tw is the row PITCH; everything below that is sized by it -- DMA groups, FP4 groups, the bases -- becomes a constant)
+    const int in_th = ROWS ? ROWS_IN_TH : (th - 1) * s + 2 * d + 1, in_tw = ROWS ? ROWS_PITCH : (TW - 1) * s + 2 * d + 1;
+    const int tile_bytes = ROWS ? ROWS_TILE_BYTES : p.tile_bytes;
     const int c0 = cchunk * CC;
     const int npix = in_th * in_tw;
     const int ngroups = (npix + 7) >> 3;
@@ -144,8 +170,8 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
             const int cy = min(max(iy, 0), p.H - 1), cx = min(max(ix, 0), p.W - 1);
             // uniform base (plane + channel chunk) + 32-bit lane offset
             const unsigned voff = ((unsigned)(cy * p.W + cx) * (unsigned)p.in_ld + ((cphys ^ (pix & 7)) << 3)) * (unsigned)sizeof(HT);
-            glds16_saddr(p.in + c0, voff, lds0 + buf * p.tile_bytes + gi * 1024);
-            if constexpr (XS) glds16_saddr(p.in_lo + c0, voff, lds0 + buf * p.tile_bytes + LOBASE + gi * 1024);
+            glds16_saddr(p.in + c0, voff, lds0 + buf * tile_bytes + gi * 1024);
+            if constexpr (XS) glds16_saddr(p.in_lo + c0, voff, lds0 + buf * tile_bytes + LOBASE + gi * 1024);
             oob |= outside << it;
         }
         if constexpr (WS == 2) {
@@ -164,7 +190,7 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
                 // (plane pointer = first plane + pl * distance, not p.xq[pl]: a dynamically indexed kernel argument -- or a select
                 // between two of them -- becomes a scalar load + lgkmcnt(0) per item)
                 glds16_saddr(xq0 + pl * xq_delta + c0 / 2 + w * 16, (unsigned)(cy * p.W + cx) * (unsigned)(p.C / 2),
-                             lds0 + buf * p.tile_bytes + QBASE + (pl * 2 + w) * QT + gq * 1024);
+                             lds0 + buf * tile_bytes + QBASE + (pl * 2 + w) * QT + gq * 1024);
                 oob |= outside << it;
             }
             // one scale dword per pixel and plane (the four windows of this 128-channel half); a clamped pixel's scales are valid
@@ -174,15 +200,87 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
                 const int ly = (pix * p.tw_magic) >> 16, lx = pix - ly * in_tw;
                 const int cy = min(max(iy0 + ly * step, 0), p.H - 1), cx = min(max(ix0 + lx * step, 0), p.W - 1);
                 glds4_saddr(xs0 + pl * xs_delta + ((long long)(c0 >> 8) * p.x_srows) * 8 + ((c0 >> 5) & 4), (unsigned)(cy * p.W + cx) * 8u,
-                            lds0 + buf * p.tile_bytes + SBASE + pl * ST + gq * 256);
+                            lds0 + buf * tile_bytes + SBASE + pl * ST + gq * 256);
             }
         }
         return oob;
     };
+    // ROWS: the same by rows, for tile (ty, tx) of residue class (ry, rx).  Per DMA group the row is scalar; a lane adds its column.
+    const int col_lane = (lane >> 3) * step;                                   // image columns from the group's first pixel to this lane's
+    const unsigned swz_lane = (unsigned)(((lane & 7) ^ (lane >> 3)) << 3) * (unsigned)sizeof(HT);
+    auto stage_rows = [&](int ty, int tx, int ry, int rx, int buf) -> unsigned {
+        const int iy0 = ry + (ty * 4 - 1) * step, ix0 = rx + (tx * TW - 1) * step;
+        const unsigned dst = lds0 + buf * ROWS_TILE_BYTES;
+        const unsigned ld_bytes = (unsigned)p.in_ld * (unsigned)sizeof(HT);
+        unsigned oob = 0;
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int gi = wave + 8 * it;                          // group gi = 8 pixels of row gi / 5
+            if (gi < ROWS_IN_TH * (ROWS_PITCH / 8)) {
+                const int ly = gi / (ROWS_PITCH / 8), g8 = gi - ly * (ROWS_PITCH / 8);
+                const int iy = iy0 + ly * step, ix = ix0 + g8 * 8 * step + col_lane;
+                const unsigned outside = (unsigned)((unsigned)iy >= (unsigned)p.H) | (unsigned)((unsigned)ix >= (unsigned)p.W);
+                // the clamps stay: an unclamped source address is a fault, not a wrong value
+                const int cy = min(max(iy, 0), p.H - 1), cx = min(max(ix, 0), p.W - 1);
+                const unsigned voff = (unsigned)(cy * p.W) * ld_bytes + __umul24((unsigned)cx, ld_bytes) + swz_lane;      // 24-bit multiply: W and in_ld * 2 are below 2^24 (validate_gconv_mfma)
+                glds16_saddr(p.in + c0, voff, dst + gi * 1024);
+                oob |= outside << it;
+            }
+        }
+        // FP4 tiles and scale dwords: items as in the general path (a wave's (group, plane, window) is the same for every tile); pixel -> (row, column)
+        // is a division by the constant pitch
+        const int pwbits = has_lo ? 2 : 1;
+        int it = 16;
+        for (int item = wave; item < (4 << pwbits); item += 8, ++it) {
+            const int pw = item & ((1 << pwbits) - 1), gq = item >> pwbits, w = pw & 1, pl = pw >> 1;
+            const int pix = gq * 64 + lane;
+            const int ly = (pix * 1639) >> 16, lx = pix - ly * ROWS_PITCH;         // pix / 40 for pix < 256
+            const int iy = __mul24(ly, step) + iy0, ix = __mul24(lx, step) + ix0;
+            const unsigned outside = (unsigned)(pix >= ROWS_IN_TH * ROWS_PITCH) | (unsigned)((unsigned)iy >= (unsigned)p.H) | (unsigned)((unsigned)ix >= (unsigned)p.W);
+            const int cy = min(max(iy, 0), p.H - 1), cx = min(max(ix, 0), p.W - 1);
+            glds16_saddr(xq0 + pl * xq_delta + c0 / 2 + w * 16, (__umul24((unsigned)cy, (unsigned)p.W) + (unsigned)cx) * (unsigned)(p.C / 2),
+                         dst + QBASE + (pl * 2 + w) * QT + gq * 1024);
+            oob |= outside << it;
+        }
+        for (int item = wave; item < (4 << (pwbits - 1)); item += 8) {
+            const int pl = item & ((1 << (pwbits - 1)) - 1), gq = item >> (pwbits - 1);
+            const int pix = gq * 64 + lane;
+            const int ly = (pix * 1639) >> 16, lx = pix - ly * ROWS_PITCH;
+            const int cy = min(max(__mul24(ly, step) + iy0, 0), p.H - 1), cx = min(max(__mul24(lx, step) + ix0, 0), p.W - 1);
+            glds4_saddr(xs0 + pl * xs_delta + ((long long)(c0 >> 8) * p.x_srows) * 8 + ((c0 >> 5) & 4), (__umul24((unsigned)cy, (unsigned)p.W) + (unsigned)cx) * 8u,
+                        dst + SBASE + pl * ST + gq * 256);
+        }
+        return oob;
+    };
     const int per = (p.nsp + p.nslots - 1) / p.nslots;
-    const int sp_step = p.walk ? 1 : p.nslots, sp_end = p.walk ? min(p.nsp, (slot + 1) * per) : p.nsp;
-    int sp = p.walk ? slot * per : slot, buf = 0;
-    unsigned oob = sp < sp_end ? stage(sp, 0) : 0u;
+    const int sp_step = ROWS || p.walk ? 1 : p.nslots, sp_end = ROWS || p.walk ? min(p.nsp, (slot + 1) * per) : p.nsp;      // (ROWS: the launcher always walks)
+    int sp = ROWS || p.walk ? slot * per : slot, buf = 0;
+    // ROWS: running tile indices of the tile in the MFMA phase (ty, tx, ry, rx) and of the next one (n..), in walk order: ty fastest, then tx, then
+    // the residue class; set once per workgroup from its first tile
+    int ty = 0, tx = 0, ry = 0, rx = 0, nty = 0, ntx = 0, nry = 0, nrx = 0;
+    auto advance = [&](int& y, int& x, int& cy, int& cx) {
+        if (++y == p.tiles_y) {
+            y = 0;
+            if (++x == p.tiles_x) {
+                x = 0;
+                if (++cx == p.dil) { cx = 0; ++cy; }
+            }
+        }
+    };
+    if constexpr (ROWS) {
+        ty = sp % p.tiles_y;
+        const int r1 = sp / p.tiles_y;
+        tx = r1 % p.tiles_x;
+        const int cmb = r1 / p.tiles_x;
+        ry = p.comb ? cmb / p.dil : 0; rx = p.comb ? cmb % p.dil : 0;
+        nty = ty; ntx = tx; nry = ry; nrx = rx;
+        advance(nty, ntx, nry, nrx);
+    }
+    auto stage_tile = [&](bool next, int b) -> unsigned {
+        if constexpr (ROWS) return next ? stage_rows(nty, ntx, nry, nrx, b) : stage_rows(ty, tx, ry, rx, b);
+        else return stage(next ? sp + sp_step : sp, b);
+    };
+    unsigned oob = sp < sp_end ? stage_tile(false, 0) : 0u;
 
     // ---- this wave's window and its weight fragments (registers for ALL of the workgroup's tiles)
     const int win = wave & 1;                  // window inside the 64-channel chunk
@@ -231,8 +329,8 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
             int it = 0;
             for (int gi = wave; gi < ngroups; gi += 8, ++it)
                 if ((mask >> it) & 1u) {
-                    *reinterpret_cast<uint4*>(lds + b * p.tile_bytes + gi * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
-                    if constexpr (XS) *reinterpret_cast<uint4*>(lds + b * p.tile_bytes + LOBASE + gi * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
+                    *reinterpret_cast<uint4*>(lds + b * tile_bytes + gi * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
+                    if constexpr (XS) *reinterpret_cast<uint4*>(lds + b * tile_bytes + LOBASE + gi * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
                 }
             if constexpr (WS == 2) {
                 const int pwbits = has_lo ? 2 : 1;
@@ -240,7 +338,7 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
                 for (int item = wave; item < (n64 << pwbits); item += 8, ++it)
                     if ((mask >> it) & 1u) {
                         const int pw = item & ((1 << pwbits) - 1), gq = item >> pwbits;
-                        *reinterpret_cast<uint4*>(lds + b * p.tile_bytes + QBASE + pw * QT + gq * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
+                        *reinterpret_cast<uint4*>(lds + b * tile_bytes + QBASE + pw * QT + gq * 1024 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
                     }
             }
         }
@@ -264,6 +362,21 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
             }
         }
     }
+    // ROWS: lane addresses (absolute LDS bytes, buffer 0) of the three f16 tap columns and of the FP4 pixel / scale byte of tap 4 g + kq
+    unsigned a_addr[3] = {0u, 0u, 0u}, q_addr[3] = {0u, 0u, 0u}, s_addr[3] = {0u, 0u, 0u};
+    if constexpr (ROWS) {
+        const int row0 = part >> 1, sx = (part & 1) * 16 + fr;         // the wave's first output row, this lane's column (the same for both sub-tiles)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            a_addr[c] = lds0 + (row0 * ROWS_PITCH + sx + c) * 128 + ((chunk_in ^ ((sx + c) & 7)) << 4);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const int t = min(4 * g + kq, 8);
+            const int pix = (row0 + t / 3) * ROWS_PITCH + sx + t % 3;
+            q_addr[g] = lds0 + QBASE + win * QT + pix * 16;
+            s_addr[g] = lds0 + SBASE + pix * 4 + (ssel >> 3);          // this window's scale BYTE of the pixel's dword
+        }
+    }
     // output addressing in 32 bits off the (uniform) plane bases -- the epilogue is VALU-issue bound, 64-bit address chains cost
     // as much as the arithmetic it is there for
     const unsigned o_ld = (unsigned)p.out_ld, q_ld = (unsigned)(p.C / 2);
@@ -278,15 +391,18 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
         // address), so one wave of the SIMD computes addresses while the other one's MFMAs run.
         const bool late_stage = NJ >= 2 && wave >= 4 && p.dephase;
         oob = 0u;
-        if (!late_stage && sp + sp_step < sp_end) oob = stage(sp + sp_step, buf ^ 1);
-        const char* tile = lds + buf * p.tile_bytes;
+        if (!late_stage && sp + sp_step < sp_end) oob = stage_tile(true, buf ^ 1);
+        const char* tile = lds + buf * tile_bytes;
         f32x4 acc[NJ][2];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            if (NJ >= 2 && j == NJ / 2 && late_stage && sp + sp_step < sp_end) oob = stage(sp + sp_step, buf ^ 1);
+            if (NJ >= 2 && j == NJ / 2 && late_stage && sp + sp_step < sp_end) oob = stage_tile(true, buf ^ 1);
             // all nine tap fragments are requested before the first MFMA: the LDS latency is paid once per sub-tile
             v8 a[9];
-            if constexpr (HOIST) {
+            if constexpr (ROWS) {
+#pragma unroll
+                for (int t = 0; t < 9; ++t) a[t] = lds_load<v8>(a_addr[t % 3] + (2 * j + t / 3) * (ROWS_PITCH * 128));
+            } else if constexpr (HOIST) {
 #pragma unroll
                 for (int t = 0; t < 9; ++t) a[t] = *reinterpret_cast<const v8*>(tile + toff[j][t]);
             } else {
@@ -316,6 +432,13 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
 #pragma unroll
                     for (int pl = 0; pl < 2; ++pl) {
                         if (pl == 1 && !has_lo) { bq[pl][g] = make_int4(0, 0, 0, 0); bs[pl][g] = 127; continue; }
+                        if constexpr (ROWS) {
+                            typedef int i4 __attribute__((ext_vector_type(4)));
+                            const i4 q = lds_load<i4>(q_addr[g] + pl * 2 * QT + 2 * j * ROWS_PITCH * 16);
+                            bq[pl][g] = make_int4(q.x, q.y, q.z, q.w);
+                            bs[pl][g] = (int)lds_load<unsigned char>(s_addr[g] + pl * ST + 2 * j * ROWS_PITCH * 4);
+                            continue;
+                        }
                         bq[pl][g] = *reinterpret_cast<const int4*>(tile + QBASE + (pl * 2 + win) * QT + pix * 16);
                         bs[pl][g] = (int)((*reinterpret_cast<const unsigned*>(tile + SBASE + pl * ST + pix * 4) >> ssel) & 0xffu);
                     }
@@ -377,16 +500,19 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         zero_oob(oob, buf ^ 1);
 
-        int tx, ty, cmb;
-        if (p.walk) { ty = sp % p.tiles_y; const int r1 = sp / p.tiles_y; tx = r1 % p.tiles_x; cmb = r1 / p.tiles_x; }
-        else { tx = sp % p.tiles_x; const int r1 = sp / p.tiles_x; ty = r1 % p.tiles_y; cmb = r1 / p.tiles_y; }
-        const int ry = p.comb ? cmb / p.dil : 0, rx = p.comb ? cmb % p.dil : 0;
-        const int oy0 = ty * p.th, ox0 = tx * TW;    // tile origin on its grid
+        int etx = tx, ety = ty, ery = ry, erx = rx;      // ROWS: the counters
+        if constexpr (!ROWS) {
+            int cmb;
+            if (p.walk) { ety = sp % p.tiles_y; const int r1 = sp / p.tiles_y; etx = r1 % p.tiles_x; cmb = r1 / p.tiles_x; }
+            else { etx = sp % p.tiles_x; const int r1 = sp / p.tiles_x; ety = r1 % p.tiles_y; cmb = r1 / p.tiles_y; }
+            ery = p.comb ? cmb / p.dil : 0; erx = p.comb ? cmb % p.dil : 0;
+        }
+        const int oy0 = ety * th, ox0 = etx * TW;    // tile origin on its grid
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int st = part + 4 * j;
             const int sy = st >> 1, sx = (st & 1) * 16 + fr;
-            const int oy = ry + (oy0 + sy) * step, ox = rx + (ox0 + sx) * step;
+            const int oy = ery + (oy0 + sy) * step, ox = erx + (ox0 + sx) * step;
             const bool live = oy < p.OH && ox < p.OW;
             const unsigned pix = live ? (unsigned)oy * (unsigned)p.OW + (unsigned)ox : 0u;
             float v[8];
@@ -457,6 +583,13 @@ __global__ void __launch_bounds__(512) k_gconv_mfma(GconvArgs<HT> p) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (ROWS) {          // loop latch: the next tile becomes this one; the lane addresses move to the other buffer
+            ty = nty; tx = ntx; ry = nry; rx = nrx;
+            advance(nty, ntx, nry, nrx);
+            const unsigned flip = buf ? (unsigned)-ROWS_TILE_BYTES : (unsigned)ROWS_TILE_BYTES;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { a_addr[i] += flip; q_addr[i] += flip; s_addr[i] += flip; }
         }
         __syncthreads();
     }
@@ -537,7 +670,9 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
     a.comb = (op.stride == 1 && op.dil > 1 && op.pad == op.dil) ? 1 : 0;
     a.th = gconv_pick_th(op, a.comb, device_cus(), &a.nsp, &a.nslots);
     AVL_REQUIRE(a.th > 0, "grouped conv: no tile height fits two LDS buffers");
-    a.tile_bytes = gconv_tile_bytes(op.stride, a.comb ? 1 : op.dil, a.th, WS == 2, XS);
+    // the row-aligned MX kernel (k_gconv_mfma<.., ROWS = true>): stride 1, tap distance 1 inside LDS, the four-row tile, no lo input plane
+    const bool rows = WS == 2 && !XS && op.w_split == 2 && op.stride == 1 && (op.dil == 1 || a.comb) && a.th == 4 && op.in_lo == nullptr;
+    a.tile_bytes = rows ? ROWS_TILE_BYTES : gconv_tile_bytes(op.stride, a.comb ? 1 : op.dil, a.th, WS == 2, XS);
     a.w4 = a.w4s = a.xq[0] = a.xq[1] = a.xs[0] = a.xs[1] = nullptr;
     a.x_srows = op.in_rows;
     if (WS == 2) {
@@ -559,21 +694,26 @@ int launch_gconv_typed(const avl_seg_op& op, hipStream_t s) {
     a.tiles_x = (gw + TW - 1) / TW;
     a.tiles_y = (gh + a.th - 1) / a.th;
     a.cchunks = op.in_c / CC;
-#define AVL_GCONV_LAUNCH(NJ)                                                                                                          \
+#define AVL_GCONV_LAUNCH(NJ, ROWS)                                                                                                    \
     do {                                                                                                                              \
-        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gconv_mfma<HT, WS, NJ, XS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((k_gconv_mfma<HT, WS, NJ, XS>), dim3(a.nslots * a.cchunks, 1, op_batch(op)), dim3(512), 2 * a.tile_bytes, s, a); \
+        AVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gconv_mfma<HT, WS, NJ, XS, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+        hipLaunchKernelGGL((k_gconv_mfma<HT, WS, NJ, XS, ROWS>), dim3(a.nslots * a.cchunks, 1, op_batch(op)), dim3(512), 2 * a.tile_bytes, s, a); \
     } while (0)
     // kernel arguments, not constants: folding them into the kernels changes their code
     a.dephase = 1;
     a.walk = 1;
     // (the MX variant never runs four sub-tiles per wave -- gconv_pick_th: it would spill -- so that kernel is not even instantiated)
     if (a.th == 8) {
-        if constexpr (WS != 2 && !XS) AVL_GCONV_LAUNCH(4);
+        if constexpr (WS != 2 && !XS) AVL_GCONV_LAUNCH(4, false);
         else return avl::set_error(AVL_E_ARG, "MX / split-input grouped conv: tile height 8 is not built");
     }
-    else if (a.th == 4) AVL_GCONV_LAUNCH(2);
-    else AVL_GCONV_LAUNCH(1);
+    else if (a.th == 4) {
+        if constexpr (WS == 2 && !XS) {
+            if (rows) AVL_GCONV_LAUNCH(2, true);
+            else AVL_GCONV_LAUNCH(2, false);
+        } else AVL_GCONV_LAUNCH(2, false);
+    }
+    else AVL_GCONV_LAUNCH(1, false);
 #undef AVL_GCONV_LAUNCH
     AVL_LAUNCH_CHECK();
     return AVL_OK;
@@ -597,6 +737,7 @@ int validate_gconv_mfma(const avl_seg_op& op) {
         AVL_REQUIRE((reinterpret_cast<uintptr_t>(op.w_mx) | reinterpret_cast<uintptr_t>(op.in_mx)) % 16 == 0, "MX grouped conv: unaligned bundles");
         AVL_REQUIRE(2 * gconv_tile_bytes(op.stride, (op.stride == 1 && op.pad == op.dil) ? 1 : op.dil, 2, true) <= 160 * 1024, "MX grouped conv: two tile buffers do not fit LDS");
         AVL_REQUIRE((long long)op.in_rows * (op.in_c / 2) < (1LL << 31), "MX grouped conv: FP4 plane beyond 2 GB (32-bit DMA offsets)");
+        AVL_REQUIRE(op.in_h < (1 << 24) && op.in_w < (1 << 24) && op.in_ld < (1 << 23), "MX grouped conv: image sides and row pitch must stay below 2^24 (24-bit multiplies in the row-aligned staging)");
     }
     AVL_REQUIRE(!op.out_mx || (op.w_split >= 1 && op.out_c % 256 == 0 && op.out_ld == op.out_c), "grouped conv: out_mx needs w_split, channels %% 256 == 0 and a dense output");
     AVL_REQUIRE(!(op.mx_flags & AVL_MX_OUT_LO) || (op.out_mx && !op.out_lo), "grouped conv: AVL_MX_OUT_LO needs out_mx and no out_lo");

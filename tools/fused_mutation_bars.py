@@ -7,7 +7,12 @@ the host evaluators of tests/_fused_mixed_operands.py -- once as the kernels are
 mutation lists.  Printed per mistake: max|wrong - right| / max|right| of what the old test compares (hi + lo plane, or the logits) and
 whether that is below the test's bar, i.e. whether a kernel with exactly this mistake and no other error would still pass.  (The exact
 suite, tests/test_gpu_fused_mixed_exact.py, turns every one of them into a changed byte: tests/test_fused_mixed_operands_cpu.py.)
-Mistakes that only move elements outside the compared region or only the labels are not listed: the old tests check those directly."""
+Mistakes that only move elements outside the compared region or only the labels are not listed: the old tests check those directly.
+
+Last, layer2's k_bottleneck_w256 under ALL the checks of tests/test_gpu_bottleneck_layer2.py (the hi plane's bar after 2^-11 |ref|, Q4(hi)
+byte for byte against the host quantiser of the stored hi plane, Q4(lo) within 0.25 amax of its block, hi + lo, the fill past the last
+pixel) on that file's own operands (its "exact t1" and its Gaussian draw, 37 x 53), with the evaluator and the mutation list of
+tests/_bottleneck2_operands.py; tests/test_gpu_bottleneck2_exact.py turns each of them into a changed byte."""
 import os
 import sys
 
@@ -15,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import _bottleneck2_operands as M2  # noqa: E402
 import _fused_mixed_operands as M  # noqa: E402
 
 TOL = 3e-6
@@ -91,6 +97,77 @@ def table(title, bar, c, o, exact, compared, mutations, applicable):
     return passed
 
 
+def b2_operands(c, seed, exact_t1):
+    """test_gpu_bottleneck_layer2._case's draw -> (the operand dict of _bottleneck2_operands.exact, that test's float64 reference [bm][512])"""
+    import torch.nn.functional as F
+    from vision_semantic_segmentation_amd.network import mx_dequant_fp4, mx_quant_fp4
+    H, W, CIN, WIDTH, COUT, G = c.H, c.W, M2.CIN, M2.WIDTH, M2.COUT, M2.GROUPS
+    g = torch.Generator().manual_seed(seed)
+    x64 = torch.randn((1, CIN, H, W), generator=g, dtype=torch.float64)
+    w1 = torch.randn((WIDTH, CIN), generator=g, dtype=torch.float64) * (2.0 / CIN) ** 0.5
+    w2 = torch.randn((WIDTH, WIDTH // G, 3, 3), generator=g, dtype=torch.float64) * (2.0 / (9 * WIDTH // G)) ** 0.5
+    w3 = torch.randn((COUT, WIDTH), generator=g, dtype=torch.float64) * (1.0 / WIDTH) ** 0.5
+    b = torch.randn(2 * WIDTH + COUT, generator=g) * 0.2
+    if exact_t1:
+        x64 = (torch.randint(1, 3, x64.shape, generator=g) * (torch.randint(0, 2, x64.shape, generator=g) * 2 - 1)).double() + x64 * 1e-4
+        w1 = torch.randint(-1, 2, w1.shape, generator=g).double() * (torch.rand(w1.shape, generator=g) < 0.25)
+        b[:WIDTH] = torch.randint(-3, 4, (WIDTH,), generator=g).float()
+        w2 = w2 * 0.1
+    xh = x64.to(torch.float16)
+    xl = (x64 - xh.double()).to(torch.float16)
+    rows = lambda t: t[0].permute(1, 2, 0).reshape(H * W, -1)                      # noqa: E731
+    o = {"xh": rows(xh).float(), "b1": b[:WIDTH], "b2": b[WIDTH:2 * WIDTH], "b3": b[2 * WIDTH:], "fcols": torch.zeros(COUT, dtype=torch.bool)}
+    o["xq"], o["xs"] = mx_quant_fp4(rows(xl).double())
+    xl_fp4 = mx_dequant_fp4(o["xq"], o["xs"])
+    for k, w in (("W1", w1), ("W2", w2), ("W3", w3)):
+        o[k + "h"], o[k + "l"] = _split(w)
+    q = lambda w: sum(t.double() for t in _split(w))                                # noqa: E731
+    t1 = F.relu(F.conv2d(xh.double(), q(w1).reshape(WIDTH, CIN, 1, 1), b[:WIDTH].double())).to(torch.float16).double()
+    t2 = F.relu(F.conv2d(t1, q(w2), b[WIDTH:2 * WIDTH].double(), padding=1, groups=G))
+    y = F.conv2d(t2, q(w3).reshape(COUT, WIDTH, 1, 1), b[2 * WIDTH:].double())
+    return o, F.relu(rows(y) + rows(xh).double() + xl_fp4)
+
+
+def b2_checks(c, bufs, ref, exact_t1):
+    """the assertions of test_gpu_bottleneck_layer2._case on stored buffers -> (err_hi, Q4(hi) bytes equal, err_lo, hi + lo, fill intact, passes)"""
+    from vision_semantic_segmentation_amd.network import mx_dequant_fp4, mx_quant_fp4
+    n = c.H * c.W
+    hi = bufs["out"]
+    got = hi[:n].double()
+    scale = float(ref.abs().max())
+    err_hi = ((got - ref).abs() - 2 ** -11 * ref.abs()).clamp_min(0).max().item() / scale
+    (qh, sh), (ql, sl) = M2.unbundle(c, bufs["out_mx"], 0), M2.unbundle(c, bufs["out_mx"], 1)
+    eq, es = mx_quant_fp4(got)
+    q_ok = torch.equal(qh[:n], eq) and torch.equal(sh[:, :n], es)
+    fill = all(bool((t == v).all()) for t, v in ((hi[n:], 7.0), (qh[n:], 0xA5), (sh[:, n:], 0xA5), (ql[n:], 0xA5), (sl[:, n:], 0xA5)))
+    lo_deq = mx_dequant_fp4(ql[:n], sl[:, :n])
+    lo_ref = ref - got
+    amax = lo_ref.reshape(n, -1, 32).abs().amax(dim=2, keepdim=True).expand(-1, -1, 32).reshape(n, -1)
+    err_lo = ((lo_deq - lo_ref).abs() - 0.25 * amax).clamp_min(0).max().item() / scale
+    tot = (got + lo_deq - ref).abs().max().item() / scale
+    ok = err_hi <= (3e-6 if exact_t1 else 3e-4) and q_ok and fill and (err_lo <= 3e-6 or not exact_t1) and tot <= (2 ** -13 if exact_t1 else 3e-4)
+    return err_hi, q_ok, err_lo, tot, fill, ok
+
+
+def b2_table(title, exact_t1, seed):
+    c = M2.B2Case(1, 37, 53)
+    o, ref = b2_operands(c, seed, exact_t1)
+    print("%s   bars: hi %.0e, Q4(hi) bytes, Q4(lo) %s, hi + lo %.1e of max|ref|" % (title, 3e-6 if exact_t1 else 3e-4, "3e-6 beyond 0.25 amax" if exact_t1 else "not checked",
+                                                                                        2 ** -13 if exact_t1 else 3e-4))
+    passed = []
+    for mut in (None,) + M2.MUTATIONS:
+        if mut is not None and not M2.applicable(c, mut):
+            continue
+        r = M2.exact(c, o, mut)
+        r["y"] = r["y"].float().double()                       # the kernel's y is an fp32 value
+        err_hi, q_ok, err_lo, tot, fill, ok = b2_checks(c, M2.stored(c, r, mut), ref, exact_t1)
+        print("    %-20s hi %.2e   Q4(hi) %-7s Q4(lo) %.2e   hi + lo %.2e   fill %-7s %s" % (
+            mut or "(as documented)", err_hi, "equal" if q_ok else "differs", err_lo, tot, "intact" if fill else "written", "PASSES every bar" if ok else "caught"))
+        if ok and mut is not None:
+            passed.append(mut)
+    return passed
+
+
 def main():
     D, B = M.DCase, M.BCase
     dw = [("k_dwpw<f16, 2>      test_split_fused_depthwise_pointwise 37x53 K128 d12", 4 * 2 ** -11 / 128 ** 0.5, D("w2", 1, 37, 53, 128, 256, 12, 12)),
@@ -106,6 +183,8 @@ def main():
           ("k_bottleneck<256, -, -, -, ->        23x45 (single-plane output)", 1.5 * 2 ** -11, B(256, False, False, False, 1, 23, 45))]
     for title, bar, c in bn:
         total[title] = table(title, bar, c, bn_gaussian(c, 2), M.bn_exact, bn_compared, M.BN_MUTATIONS, M.bn_applicable)
+    total["k_bottleneck_w256 (exact t1)"] = b2_table("k_bottleneck_w256   test_layer2_block_exact_t1 37x53", True, 37 * 131 + 53)
+    total["k_bottleneck_w256 (Gaussian)"] = b2_table("k_bottleneck_w256   test_layer2_block_gaussian 37x53", False, 7 + 37)
     print("\nmistakes that pass their bar:")
     for title, muts in total.items():
         print("    %s: %s" % (title.split("   ")[0].strip(), ", ".join(muts) if muts else "none"))

@@ -796,6 +796,52 @@ int avl_site_overview(const avl_tile_src* tiles_dev, int n_tiles, int nh, int nw
                       const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, uint8_t* picture,
                       void* reduced, void* stream);
 
+/* ---- the site finish: the filtered picture, the labels and the score of a scrolled site straight from its tiles (the reference's
+ * finish_run chain, src/mapping.py:323-345, on a site instead of one grid; csrc/seg_sitefinish.hip) ------------------------------------
+ * THE RULE.  For a rectangle of nh x nw tiles of T x T cells the result is DEFINED as this chain on the assembled rectangle:
+ *   1. A [nh*T][nw*T][C] is the rectangle at full resolution: the tile at (row, col) holds the cells [row*T, +T) x [col*T, +T); a
+ *      tile without data -- no record, or a record with src == NULL -- is +0.  This is what site_map(rect) assembles.
+ *   2. F = avl_grid_box_filter(A) with Hm = nh*T, Wm = nw*T: avl::box_filter3_taps of csrc/avl_render.h, nine products by
+ *      (double)(1.0f / 9.0f) accumulated in double from +0, dy outer and dx inner, BORDER_REFLECT_101 at the RECTANGLE's edge (never
+ *      at a tile's), rounded to the map's type.  Without AVL_LIVE_FILTER in `flags` the filter is off: F = A, bit for bit.
+ *   3. picture = avl_render_bev_map(F); with thresholds_host, avl_render_bev_map_thresholds(F, priority_host, thresholds_host)
+ *      (argmax_colour / thresholds_colour of csrc/avl_render.h, the one copy the overview shares).
+ *   4. labels = k_eval_map's colour -> label table on picture (colour_label of csrc/avl_render.h), 0 where the mask is 0.
+ *   5. counts[g * 8 + l] += 1 for every cell of every tile THAT HAS A RECORD, l its label and g the truth there (values above 7
+ *      count as 7).  Truth is a raster gt uint8[Hg][gt_ld] whose element [0][0] lies at rectangle cell (gt_r0, gt_c0), either may be
+ *      negative; the optional mask uint8[Hg][mask_ld] (0 = invalid) has the same geometry.  A cell outside the raster has g = 0 and
+ *      is unmasked.  counts is uint64[64]; the call zeroes it, stream-ordered.  The cells of tiles without a record are the caller's
+ *      to add (their label is 0): evaluation.SiteTruth.tile_hist.
+ * RECORDS.  A record is an avl_tile_fin, a sibling of avl_tile_src that also carries the neighbour lookup: nb[(dr + 1) * 3 + (dc + 1)]
+ * is the index of the record at (row + dr, col + dc), or -1 where there is none; nb[4] is the record's own index.  A record with
+ * src == NULL is a tile that holds nothing but is computed, written and counted in full: the host lists one for every absent tile with
+ * at least one present 8-neighbour, because the filter puts a ninth of the neighbour's border into that tile's outer ring.  Tiles
+ * without a record keep the zero fill: black, label 0.  So every output byte has exactly one writer.  A NULL record or a missing
+ * neighbour contributes +0 and none of its bytes is read -- a window tile that is masked out as empty may hold garbage.
+ * The caller owns the table's validity as for avl_tile_src, plus the neighbour indices: scroll.validate_finish checks all of it on
+ * the host before the upload.  (The kernel ignores an index outside 0 .. n_tiles-1.) */
+typedef struct avl_tile_fin {
+    const void* src;      /* first byte of the tile, or NULL: a tile of +0                                                         */
+    int64_t src_pitch;    /* bytes between tile rows                                                                              */
+    int32_t row, col;     /* the tile's place inside the rectangle of nh x nw tiles                                               */
+    int32_t nb[9];        /* record index of the tile at (row + dr, col + dc) in nb[(dr + 1) * 3 + (dc + 1)], -1 = none; nb[4] = own */
+    int32_t pad;
+} avl_tile_fin;
+
+/* The finish of tiles_dev[0 .. n_tiles), a DEVICE array, by the rule above, in one launch on `stream`.  Each output is optional
+ * (NULL): picture uint8 [nh*T][nw*T][3], labels uint8 [nh*T][nw*T], counts uint64[64] (device; given exactly when gt is); at least
+ * one must be given.  colors_host uint8[C][3]; thresholds_host double[C] or NULL = the arg-max renderer; priority_host int32[C] or
+ * NULL = 0 .. C-1.  flags: AVL_LIVE_FILTER or 0.  gt / mask are DEVICE rasters of Hg x Wg elements (the geometry is needed when
+ * either is given; a mask may come without gt, for labels).  The call zero-fills picture and labels and zeroes counts, stream-ordered
+ * before the kernel, and launches only the listed tiles; it allocates nothing, copies nothing from the host and waits for nothing.
+ * n_tiles == 0 does the fills alone.  AVL_E_ARG, before any GPU work: avl_site_overview's list (without k), tile_cells < 2, a flag
+ * other than AVL_LIVE_FILTER, no output given, counts without gt or gt without counts, Hg or Wg <= 0 with a gt or a mask, gt_ld < Wg
+ * or mask_ld < Wg (gt_r0 and gt_c0 may be any int), an output of 2^31 cells or more, a counts that is not 8-byte aligned. */
+int avl_site_finish(const avl_tile_fin* tiles_dev, int n_tiles, int nh, int nw, int tile_cells, int C, int map_dtype, int flags,
+                    const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, const uint8_t* gt,
+                    int Hg, int Wg, int64_t gt_ld, int gt_r0, int gt_c0, const uint8_t* mask, int64_t mask_ld, uint8_t* picture,
+                    uint8_t* labels, unsigned long long* counts, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

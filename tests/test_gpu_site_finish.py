@@ -1,0 +1,371 @@
+"""The site finish on the GPU: k_site_finish and SemanticMapping.site_finish against the NumPy twin of _site_finish_reference.py,
+picture, labels and counts byte for byte.
+
+* the kernel alone through the C ABI, picture and labels between guard strips of 0xAB that must survive: TableCase's rectangle of 3 x 4
+  tiles (window tiles beside slab tiles of another pitch, a masked-out window tile whose bytes are garbage, an absent tile with present
+  neighbours, -0.0 cells) with a NaN and a +inf cell written into a copy of its buffers; the four output combinations, the filter on and
+  off, the thresholds renderer with a permuted priority; T = 2 (every cell a border cell), T = 4 with rows of 16 bytes, T = 20 with
+  cells of 40 bytes, C = 16, T = 100 (several strips per tile); a tile row of 64 KiB taken in column chunks; truth rasters that start
+  inside the rectangle, before it, and end inside it, with and without a mask.
+* through the API: a drive that scrolls twice, once diagonally -- site_finish is render_bev_map(apply_filter(site_map())) and
+  evaluation._run's counts, the site is only read, finish_run writes site_global_map.png and prints the site's IoU lines."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+
+import _scroll_reference as ref
+import _site_finish_reference as fin
+import _site_overview_reference as ov
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 256
+
+
+# ------------------------------------------------------------------------------------------------ the kernel through the C ABI
+def run_finish(table, bufs, T, Cn, dtype, nh, nw, device, filter=True, thresholds=None, priority=None, gt=None, gt_r0=0, gt_c0=0, mask=None,
+               picture=True, labels=True):
+    """-> (picture, labels, counts), None for what was not asked for: ``table`` through validate_finish, encode_finish and
+    avl_site_finish; asserts that the guard strips around picture and labels survive"""
+    import torch
+    from vision_semantic_segmentation_amd import _lib, scroll as s
+    dtype = np.dtype(dtype)
+    dev_bufs = [torch.from_numpy(b).to(device) for b in bufs]
+    extents = [(t.data_ptr(), int(t.numel())) for t in dev_bufs]
+    s.validate_finish(table, extents, T, Cn * dtype.itemsize, nh, nw)
+    rec = np.zeros(max(len(table), 1), dtype=s.FIN_DTYPE)
+    s.encode_finish(table, extents, rec)
+    tiles = torch.from_numpy(rec.view(np.uint8)).to(device)
+    ncell = nh * T * nw * T
+    pic = torch.full((GUARD + 3 * ncell + GUARD,), 0xAB, dtype=torch.uint8, device=device)
+    lab = torch.full((GUARD + ncell + GUARD,), 0xAB, dtype=torch.uint8, device=device)
+    cnt = torch.full((64,), -1, dtype=torch.int64, device=device)
+    gt_t = torch.from_numpy(np.ascontiguousarray(gt)).to(device) if gt is not None else None
+    mask_t = torch.from_numpy(np.ascontiguousarray(mask)).to(device) if mask is not None else None
+    Hg, Wg = (gt if gt is not None else mask).shape if (gt is not None or mask is not None) else (0, 0)
+    colors = np.ascontiguousarray(ov.COLORS[:Cn])
+    col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
+    th = (C.c_double * Cn)(*thresholds) if thresholds is not None else None
+    pr = (C.c_int32 * Cn)(*priority) if priority is not None else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    stream = torch.cuda.current_stream(device).cuda_stream
+    rc = _lib.lib().avl_site_finish(C.c_void_p(tiles.data_ptr()), len(table), nh, nw, T, Cn, _lib.AVL_F64 if dtype == np.float64 else _lib.AVL_F32,
+                                    _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th, p(gt_t), Hg, Wg, Wg, gt_r0, gt_c0, p(mask_t), Wg,
+                                    C.c_void_p(pic.data_ptr() + GUARD) if picture else None, C.c_void_p(lab.data_ptr() + GUARD) if labels else None,
+                                    p(cnt) if gt is not None else None, C.c_void_p(stream))
+    _lib.check(rc, "avl_site_finish")
+    torch.cuda.synchronize(device)
+    pic, lab, cnt = pic.cpu().numpy(), lab.cpu().numpy(), cnt.cpu().numpy()
+    for name, a, asked in (("picture", pic, picture), ("labels", lab, labels)):
+        assert (a[:GUARD] == 0xAB).all() and (a[-GUARD:] == 0xAB).all(), "guard strip of %s written" % name
+        assert asked or (a == 0xAB).all(), "%s written although not asked for" % name
+    assert gt is not None or (cnt == -1).all()
+    return (pic[GUARD:-GUARD].reshape(nh * T, nw * T, 3) if picture else None, lab[GUARD:-GUARD].reshape(nh * T, nw * T) if labels else None,
+            cnt.reshape(8, 8) if gt is not None else None)
+
+
+class FinishCase(object):
+    """TableCase(T, C, dtype) with a NaN and a +inf cell written into a copy of its buffers, its finish table, the assembled rectangle
+    and a truth raster with a mask that starts before the rectangle's first column and ends inside its last row"""
+
+    def __init__(self, T, Cn, dtype):
+        case = ov.TableCase(T, Cn, dtype)
+        self.T, self.C, self.dtype, self.nh, self.nw = T, Cn, np.dtype(dtype), case.nh, case.nw
+        self.table = fin.finish_table(case)
+        self.bufs = [b.copy() for b in case.bufs]
+        has = self.table[self.table["buf"] >= 0]
+        es = self.dtype.itemsize
+        for rec, (r, c, ch), value in ((has[0], (T - 1, T - 1, 0), np.nan), (has[len(has) // 2], (0, 0, Cn - 1), np.inf)):
+            at = int(rec["off"]) + r * int(rec["pitch"]) + (c * Cn + ch) * es      # a border cell: it is somebody's halo
+            self.bufs[int(rec["buf"])][at:at + es] = np.array([value], dtype=dtype).view(np.uint8)
+        self.full = ov.assemble_sources(has, self.bufs, T, Cn, dtype, self.nh, self.nw)
+        assert np.isnan(self.full).sum() == 1 and np.isinf(self.full).sum() == 1 and np.signbit(self.full[self.full == 0]).any()
+        rng = np.random.default_rng(3 + T)
+        H, W = self.nh * T, self.nw * T
+        self.gt_r0, self.gt_c0 = 1, -2
+        self.gt = fin.truth_raster(rng, (H - 2, W + 1))
+        self.mask = (rng.random(self.gt.shape) < 0.8).astype(np.uint8)
+        self.cells = fin.record_cells(self.table["row"], self.table["col"], T, self.nh, self.nw)
+        self.colors = ov.COLORS[:Cn]
+        self._want = {}
+
+    def want(self, filter=True, thresholds=None, priority=None):
+        key = (filter, None if thresholds is None else tuple(thresholds), None if priority is None else tuple(priority))
+        if key not in self._want:
+            self._want[key] = fin.finish(self.full, self.colors, filter, thresholds, priority, self.gt, self.gt_r0, self.gt_c0, self.mask, self.cells)
+        return self._want[key]
+
+    def check(self, device, filter=True, thresholds=None, priority=None, picture=True, labels=True, counts=True):
+        want_pic, want_lab, want_cnt = self.want(filter, thresholds, priority)
+        pic, lab, cnt = run_finish(self.table, self.bufs, self.T, self.C, self.dtype, self.nh, self.nw, device, filter, thresholds, priority,
+                                   self.gt if counts else None, self.gt_r0, self.gt_c0, self.mask, picture, labels)
+        what = "T = %d, C = %d, %s, filter %s" % (self.T, self.C, self.dtype.name, filter)
+        if picture:
+            assert np.array_equal(pic, want_pic), "%s: %d pixels differ" % (what, int((pic != want_pic).any(axis=2).sum()))
+        if labels:
+            assert np.array_equal(lab, want_lab), "%s: %d labels differ" % (what, int((lab != want_lab).sum()))
+        if counts:
+            assert np.array_equal(cnt, want_cnt), "%s: counts differ\n%s\n%s" % (what, cnt, want_cnt)
+            assert cnt.sum() == self.cells.sum()
+        return pic, lab, cnt
+
+
+_CASES = {}
+
+
+def finish_case(T, Cn, dtype):
+    key = (T, Cn, np.dtype(dtype).name)
+    if key not in _CASES:
+        _CASES[key] = FinishCase(T, Cn, dtype)
+    return _CASES[key]
+
+
+COMBOS = [(True, True, True), (True, False, False), (False, True, False), (False, False, True)]     # picture, labels, counts
+
+
+@pytest.mark.parametrize("T,Cn,dtype", [(2, 2, np.float64), (2, 4, np.float32), (4, 1, np.float32), (20, 5, np.float64), (8, 16, np.float64),
+                                        (8, 16, np.float32)], ids=lambda v: v.__name__ if isinstance(v, type) else str(v))
+def test_kernel_equals_the_twin(T, Cn, dtype, cuda_device):
+    case = finish_case(T, Cn, dtype)
+    for filter in (True, False):
+        for picture, labels, counts in COMBOS:
+            case.check(cuda_device, filter, picture=picture, labels=labels, counts=counts)
+    on, off = case.want(True)[0], case.want(False)[0]
+    assert (on != off).any()
+    if Cn > 1:
+        assert len(np.unique(on.reshape(-1, 3), axis=0)) >= min(3, Cn) and case.want(True)[2][:, 1:].sum() > 0
+    if T > 2:                                                              # the absent tiles: an outer ring of colour, a black core
+        for r, c in ov.TableCase(T, Cn, dtype).absent:
+            tile = on[r * T:(r + 1) * T, c * T:(c + 1) * T]
+            assert tile.any() and not tile[1:-1, 1:-1].any()
+    if (T, Cn) in ((20, 5), (8, 16)):                                      # the thresholds renderer with a permuted priority, once per dtype
+        rng = np.random.default_rng(Cn)
+        th, pr = [float(v) for v in rng.uniform(0.01, 0.5, size=Cn)], [int(v) for v in rng.permutation(Cn)]
+        pic, _, _ = case.check(cuda_device, True, th, pr)
+        plain = case.check(cuda_device, True, th, list(range(Cn)), labels=False, counts=False)[0]
+        assert (pic != on).any() and (pic != plain).any()
+
+
+def test_kernel_several_strips_per_tile(cuda_device):
+    """T = 100, C = 5, f64: the default geometry, rows of 4000 bytes, 17 strips per tile"""
+    case = finish_case(100, 5, np.float64)
+    case.check(cuda_device, True)
+    case.check(cuda_device, False)
+
+
+def test_kernel_column_chunks(cuda_device):
+    """1 x 2 tiles of T = 512, C = 16, f64: a tile row is 64 KiB, more than the stage holds, so a strip is one row taken in column
+    chunks that overlap by their halo cell; one tile in a buffer of the window's pitch, one in a slab"""
+    from vision_semantic_segmentation_amd import scroll as s
+    T, Cn = 512, 16
+    rng = np.random.default_rng(5)
+    full = ov.payload(rng, (T, 2 * T, Cn), np.float64)
+    bufs = [full.reshape(-1).view(np.uint8).copy(), np.ascontiguousarray(full[:, T:]).reshape(-1).view(np.uint8).copy()]
+    table = s.finish_sources((0, 0, 0, 1), T, Cn * 8, 2 * T, (0, 0), np.array([[True, False]]), [(0, 1)], [0], 1)
+    assert [int(p) for p in table["pitch"]] == [2 * T * Cn * 8, T * Cn * 8] and table["nb"].tolist() == [[-1, -1, -1, -1, 0, 1, -1, -1, -1],
+                                                                                                      [-1, -1, -1, 0, 1, -1, -1, -1, -1]]
+    gt = fin.truth_raster(rng, (T, 2 * T))
+    want_pic, _, want_cnt = fin.finish(full, ov.COLORS, gt=gt)
+    pic, _, cnt = run_finish(table, bufs, T, Cn, np.float64, 1, 2, cuda_device, gt=gt, labels=False)
+    assert np.array_equal(pic, want_pic), "%d pixels differ" % int((pic != want_pic).any(axis=2).sum())
+    assert np.array_equal(cnt, want_cnt) and cnt.sum() == 2 * T * T
+
+
+def test_kernel_strips_of_several_rows(cuda_device):
+    """40 x 40 tiles of T = 16, f32, one in ten absent: with this many tiles a strip is two tile rows and a workgroup takes more than
+    one strip of its tile; absent tiles with and without present neighbours"""
+    from vision_semantic_segmentation_amd import scroll as s
+    T, Cn, n = 16, 5, 40
+    rng = np.random.default_rng(6)
+    full = ov.payload(rng, (n * T, n * T, Cn), np.float32)
+    mask = rng.random((n, n)) < 0.9
+    mask[20:26, 10:17] = False                                             # a hole whose inner tiles get no record
+    bufs = [full.reshape(-1).view(np.uint8).copy()]
+    for i, j in zip(*np.nonzero(~mask)):
+        full[i * T:(i + 1) * T, j * T:(j + 1) * T] = 0.0
+    table = s.finish_sources((0, n - 1, 0, n - 1), T, Cn * 4, n * T, (0, 0), mask, [], [], 1)
+    assert int(mask.sum()) < len(table) < n * n and 1366 <= len(table)      # ceil(8192 / 1366) = 6 workgroups a tile: strips of 16 // 6 = 2 rows
+    gt = fin.truth_raster(rng, (n * T, n * T))
+    cells = fin.record_cells(table["row"], table["col"], T, n, n)
+    want_pic, want_lab, want_cnt = fin.finish(full, ov.COLORS[:Cn], gt=gt, cells=cells)
+    pic, lab, cnt = run_finish(table, bufs, T, Cn, np.float32, n, n, cuda_device, gt=gt)
+    assert np.array_equal(pic, want_pic) and np.array_equal(lab, want_lab) and np.array_equal(cnt, want_cnt)
+    assert not want_pic[~cells].any() and cnt.sum() == cells.sum() < (n * T) ** 2
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["plain", "mask"])
+@pytest.mark.parametrize("geometry", ["starts_inside", "starts_before", "ends_inside"])
+def test_kernel_truth_geometry(geometry, masked, cuda_device):
+    case = finish_case(8, 5, np.float64)
+    H, W = case.nh * 8, case.nw * 8
+    shape, r0, c0 = {"starts_inside": ((H, W), 5, 9), "starts_before": ((H + 9, W + 20), -4, -13), "ends_inside": ((H - 7, W - 10), -2, -3)}[geometry]
+    rng = np.random.default_rng(len(geometry))
+    gt = fin.truth_raster(rng, shape)
+    mask = (rng.random(shape) < 0.7).astype(np.uint8) if masked else None
+    want_pic, want_lab, want_cnt = fin.finish(case.full, case.colors, gt=gt, gt_r0=r0, gt_c0=c0, mask=mask, cells=case.cells)
+    pic, lab, cnt = run_finish(case.table, case.bufs, 8, 5, np.float64, case.nh, case.nw, cuda_device, gt=gt, gt_r0=r0, gt_c0=c0, mask=mask)
+    assert np.array_equal(pic, want_pic) and np.array_equal(lab, want_lab) and np.array_equal(cnt, want_cnt)
+    assert cnt[1:].sum() > 0 and cnt[0].sum() > 0
+    if masked:                                                             # a mask alone, for the labels
+        _, lab2, none = run_finish(case.table, case.bufs, 8, 5, np.float64, case.nh, case.nw, cuda_device, gt=None, gt_r0=r0, gt_c0=c0, mask=mask)
+        assert none is None and np.array_equal(lab2, want_lab) and (want_lab != fin.labels_of(want_pic)).any()
+
+
+def test_kernel_no_tiles(cuda_device):
+    case = finish_case(8, 5, np.float64)
+    pic, lab, cnt = run_finish(case.table[:0], case.bufs, 8, 5, np.float64, 3, 4, cuda_device, gt=case.gt)
+    assert not pic.any() and not lab.any() and not cnt.any()
+
+
+# ------------------------------------------------------------------------------------------------ through the API
+_DRIVE = []
+
+
+def drive():
+    """a window of 40 x 40 cells of 0.5 m, tiles of 8 cells (the scrolling grid asks for a multiple of 4); out along x, then diagonally"""
+    if not _DRIVE:
+        route = [(1.0, 1.0, 0.0), (9.5, 1.0, 0.0), (18.5, 10.0, 0.8), (18.0, 10.5, math.pi)]
+        _DRIVE.append(ref.Drive(route, res=0.5, Hm=40, Wm=40, tile_m=4.0, range_max=7.0, n_points=1500, seed=2))
+    return _DRIVE[0]
+
+
+def make_sm(d, device, grid_dtype, finish=None):
+    from vision_semantic_segmentation_amd import SemanticMapping, synthetic as syn
+    from vision_semantic_segmentation_amd.utils.logger import MyLogger
+    cfg = d.cfg(grid_dtype)
+    for name, value in (finish or {}).items():
+        setattr(cfg.MAPPING.SITE_FINISH, name, value)
+    sm = SemanticMapping(cfg, device=device, logger=MyLogger("test", quiet=True))
+    sm.confusion_matrix = syn.log_confusion(sm.map_depth)
+    return sm
+
+
+def run_frames(sm, d):
+    import torch
+    for k in range(len(d.poses)):
+        sm.pcd, sm.pcd_frame_id = d.clouds[k], "world"
+        sm.mapping_views([torch.from_numpy(im).to(sm.device) for im in d.images[k]], d.poses[k], d.cams)
+
+
+def site_truth(origin, shape, seed=9):
+    """a raster that starts before the site's rectangle on one axis, inside it on the other, and is not aligned to tiles"""
+    from vision_semantic_segmentation_amd.evaluation import SiteTruth
+    rng = np.random.default_rng(seed)
+    r0, c0 = -3, 5
+    gt = rng.integers(0, 7, size=(shape[0] - 4, shape[1] + 2)).astype(np.float64)
+    mask = (rng.random(gt.shape) < 0.8).astype(np.uint8)
+    return SiteTruth(gt, (origin[0] + r0, origin[1] + c0), mask), (r0, c0)
+
+
+@pytest.mark.parametrize("grid_dtype", ["f64", "f32"])
+def test_site_finish_equals_the_assembled_route(grid_dtype, cuda_device):
+    import torch
+    from vision_semantic_segmentation_amd import evaluation
+    from vision_semantic_segmentation_amd.renderer import apply_filter, render_bev_map
+    d = drive()
+    moves = [(b[0][0] - a[0][0], b[0][1] - a[0][1]) for a, b in zip(d.origins, d.origins[1:]) if b[1]]
+    assert len(moves) >= 2 and any(m[0] and m[1] for m in moves), moves     # at least two scrolls, one of them diagonal
+    sm = make_sm(d, cuda_device, grid_dtype)
+    run_frames(sm, d)
+    assert sm.scroll_count >= 2
+    origin, before = sm.site_map()
+    assert before.shape[0] > d.Hm or before.shape[1] > d.Wm                 # the site outgrew the window
+    truth, (r0, c0) = site_truth(origin, tuple(before.shape[:2]))
+    res = sm.site_finish(truth=truth, labels=True)
+    want_pic = render_bev_map(apply_filter(before).to(before.dtype), sm.label_colors)
+    assert res.origin == origin and res.picture.dtype == torch.uint8 and torch.equal(res.picture, want_pic)
+    assert len(torch.unique(want_pic.reshape(-1, 3), dim=0)) >= 3
+    shape = tuple(before.shape[:2])
+    mask_w = fin.lay_over(truth.mask, shape, r0, c0, 1)
+    truth_w = fin.lay_over(truth.truth, shape, r0, c0, 0)
+    want_lab, want_cnt = evaluation._run(want_pic, mask_w, truth_w)
+    assert torch.equal(res.labels, want_lab) and np.array_equal(res.counts, want_cnt)
+    assert res.counts.dtype == np.int64 and res.counts.sum() == shape[0] * shape[1] and res.counts[1:, 1:].sum() > 0
+    n_tiles = len(sm.site_tiles())
+    assert res.tiles[0] == n_tiles and res.tiles[1] > 0 and sum(res.tiles) <= (shape[0] // d.T) * (shape[1] // d.T)
+    # counts alone: nothing of the rectangle's size is returned, the numbers are the same
+    alone = sm.site_finish(truth=truth, picture=False)
+    assert alone.picture is None and alone.labels is None and np.array_equal(alone.counts, want_cnt)
+    # Test.test_site on them is Test.iou on the label maps
+    t = evaluation.Test.for_site()
+    assert t.test_site(res.counts) == t.iou(torch.from_numpy(truth_w).to(cuda_device), want_lab)
+    # the filter off, a rectangle that cuts through the site and reaches past it, `out`
+    rect = (origin[0] // d.T - 1, origin[0] // d.T + 2, origin[1] // d.T + 1, origin[1] // d.T + 3)
+    o2, part = sm.site_map(rect)
+    out = torch.full(tuple(part.shape[:2]) + (3,), 0xAB, dtype=torch.uint8, device=cuda_device)
+    res2 = sm.site_finish(rect=rect, filter=False, out=out)
+    assert res2.picture is out and res2.origin == o2 and res2.counts is None and torch.equal(out, render_bev_map(part, sm.label_colors))
+    res3 = sm.site_finish(rect=rect)
+    assert torch.equal(res3.picture, render_bev_map(apply_filter(part).to(part.dtype), sm.label_colors))
+    with pytest.raises(ValueError, match="out must be"):
+        sm.site_finish(out=out)
+    # the call only reads
+    origin_after, after = sm.site_map()
+    assert origin_after == origin and torch.equal(after.view(torch.uint8), before.view(torch.uint8)) and sm.scroll_count >= 2
+
+
+def test_an_empty_site_and_a_map_that_does_not_scroll(cuda_device):
+    from vision_semantic_segmentation_amd import SemanticMapping
+    from vision_semantic_segmentation_amd.evaluation import SiteTruth
+    from vision_semantic_segmentation_amd.utils.logger import MyLogger
+    d = drive()
+    sm = make_sm(d, cuda_device, "f64")
+    truth = SiteTruth(np.array([[0, 1, 2], [3, 3, 9]]), (4, 4))
+    res = sm.site_finish(truth=truth, labels=True)
+    assert res.origin == (0, 0) and tuple(res.picture.shape) == (0, 0, 3) and tuple(res.labels.shape) == (0, 0) and res.tiles == (0, 0)
+    assert res.counts[:, 0].tolist() == [1, 1, 1, 2, 0, 0, 0, 1] and not res.counts[:, 1:].any()
+    assert sm._scroll.tables == [None, None]                                           # nothing was uploaded or launched
+    cfg = d.cfg()
+    cfg.MAPPING.SCROLL.ENABLED = False
+    with pytest.raises(RuntimeError, match="MAPPING.SCROLL.ENABLED is False"):
+        SemanticMapping(cfg, device=cuda_device, logger=MyLogger("test", quiet=True)).site_finish()
+
+
+def read_picture(folder, stem):
+    """the RGB picture finish_run wrote as ``stem``.png (channel 0 stored as blue) or, without PIL, ``stem``.npy"""
+    png, npy = os.path.join(folder, stem + ".png"), os.path.join(folder, stem + ".npy")
+    if os.path.exists(png):
+        from PIL import Image
+        return np.asarray(Image.open(png))[:, :, ::-1]
+    return np.load(npy)
+
+
+def test_finish_run_writes_site_global_map(tmp_path, capsys, cuda_device):
+    from vision_semantic_segmentation_amd import evaluation
+    d = drive()
+    folders, maps = {}, {}
+    truth_path = str(tmp_path / "site_truth.npz")
+    for enabled in (False, True):
+        sm = make_sm(d, cuda_device, "f64", finish={"ENABLED": enabled, "TRUTH_PATH": truth_path if enabled else ""})
+        run_frames(sm, d)
+        folders[enabled] = str(tmp_path / ("on" if enabled else "off"))
+        want = None
+        if enabled:
+            origin, site = sm.site_map()
+            truth, _ = site_truth(origin, tuple(site.shape[:2]))
+            truth.save(truth_path)
+            want = sm.site_finish(truth=truth)
+        capsys.readouterr()
+        maps[enabled] = sm.finish_run(folders[enabled])
+        printed = capsys.readouterr().out
+        names = sorted(os.listdir(folders[enabled]))
+        if enabled:
+            assert [n for n in names if n.startswith("site_global_map.")] in (["site_global_map.png"], ["site_global_map.npy"])
+            assert np.array_equal(read_picture(folders[enabled], "site_global_map"), want.picture.cpu().numpy())
+            capsys.readouterr()
+            evaluation.Test.for_site().test_site(want.counts)
+            assert printed.count("IOU for road") == 1 and capsys.readouterr().out in printed
+        else:
+            assert not [n for n in names if n.startswith("site_global_map")] and "IOU for" not in printed
+    assert np.array_equal(maps[False], maps[True])
+    assert sorted(n for n in os.listdir(folders[True]) if not n.startswith("site_global_map")) == sorted(os.listdir(folders[False]))
+    # a rectangle above MAX_PIXELS: the picture is skipped, the score is not
+    sm = make_sm(d, cuda_device, "f64", finish={"ENABLED": True, "TRUTH_PATH": truth_path, "MAX_PIXELS": 100})
+    run_frames(sm, d)
+    capsys.readouterr()
+    sm.finish_run(str(tmp_path / "small"))
+    assert not [n for n in os.listdir(str(tmp_path / "small")) if n.startswith("site_global_map")]
+    assert capsys.readouterr().out.count("IOU for road") == 1

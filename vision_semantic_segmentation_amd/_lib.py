@@ -153,6 +153,7 @@ _SIGNATURES = {
     "avl_points_map_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "avl_tile_copy": (_i, [_vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp]),
     "avl_site_overview": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avl_site_finish": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

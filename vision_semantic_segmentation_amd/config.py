@@ -254,6 +254,16 @@ def get_cfg_defaults():
     C.MAPPING.SITE_OVERVIEW.CELLS_PER_PIXEL = 0
     C.MAPPING.SITE_OVERVIEW.MAX_SIDE_PX = 4096
     C.MAPPING.SITE_OVERVIEW.THRESHOLDS = []
+    # build-specific: the end-of-run result of a whole scrolled site (SemanticMapping.site_finish: one kernel from the tiles, where they
+    # live, to the FILTERED picture at one pixel per cell, its labels and the ground-truth/label counts; the rule: include/avl_hip.h,
+    # avl_tile_fin).  ENABLED: finish_run() of a scrolling map also writes site_global_map.png -- skipped, with a log line, when the
+    # site's rectangle has more than MAX_PIXELS cells -- and, with TRUTH_PATH (an .npz of evaluation.SiteTruth.save), prints the site's
+    # IoU / accuracy / missing-rate lines; off, nothing of it runs.  THRESHOLDS as in SITE_OVERVIEW
+    C.MAPPING.SITE_FINISH = CfgNode()
+    C.MAPPING.SITE_FINISH.ENABLED = False
+    C.MAPPING.SITE_FINISH.TRUTH_PATH = ""
+    C.MAPPING.SITE_FINISH.THRESHOLDS = []
+    C.MAPPING.SITE_FINISH.MAX_PIXELS = 1 << 28
     C.VISION_SEM_SEG = CfgNode()
     C.VISION_SEM_SEG.IMAGE_SCALE = 1.0
     # build-specific: class indices whose convex hulls the node extracts from every frame's label map and back-projects onto the ground

@@ -1,5 +1,6 @@
-// Device arithmetic that the end-of-run renderer (mapping.hip) and the live-map kernel (seg_livemap.hip) share, so that a window of
-// the live map is bit-equal to a crop of apply_filter + render_bev_map.  Both translation units are built with -ffp-contract=off.
+// Device arithmetic that the end-of-run renderer (mapping.hip), the live-map kernel (seg_livemap.hip), the site overview
+// (seg_overview.hip) and the site finish (seg_sitefinish.hip) share, so that a window of the live map, and the finish of a scrolled
+// site, are bit-equal to apply_filter + render_bev_map.  All these translation units are built with -ffp-contract=off.
 #pragma once
 #include "avl_common.h"
 
@@ -38,6 +39,47 @@ __device__ __forceinline__ MapT numpy_row_sum_of(int C, At at) {
 template <typename MapT>
 __device__ __forceinline__ MapT numpy_row_sum(const MapT* row, int C) {
     return numpy_row_sum_of<MapT>(C, [row](int c) { return row[c]; });
+}
+
+// the colour of one row of C values that a kernel holds in LDS (the site overview, the site finish): k_render_bev's rule (mapping.hip),
+// restated -- first maximum wins, a NaN beats every number and the first NaN wins; black where np.sum of the row is 0
+template <typename MapT>
+__device__ __forceinline__ void argmax_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
+    MapT best = row[0];
+    int bi = 0;
+    for (int c = 1; c < C; ++c) {
+        const MapT v = row[c];
+        if (v > best || (v != v && best == best)) { best = v; bi = c; }
+    }
+    unsigned char r = rp.colors[3 * bi], g = rp.colors[3 * bi + 1], b = rp.colors[3 * bi + 2];
+    if (numpy_row_sum(row, C) == (MapT)0) r = g = b = 0;
+    rgb[0] = r; rgb[1] = g; rgb[2] = b;
+}
+
+// k_render_thresholds' rule (mapping.hip), restated: the share is a MapT quotient compared with the threshold in MapT, priorities
+// from low to high, later ones overwrite
+template <typename MapT>
+__device__ __forceinline__ void thresholds_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
+    const MapT s = numpy_row_sum(row, C);
+    unsigned char r = 0, g = 0, b = 0;
+    if (s != (MapT)0) {
+        for (int i = 0; i < C; ++i) {
+            const int ch = rp.priority[i];
+            const MapT pn = row[ch] / s;
+            if (pn >= (MapT)rp.thresholds[i]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
+        }
+    }
+    rgb[0] = r; rgb[1] = g; rgb[2] = b;
+}
+
+// k_eval_map's colour -> label table (mapping.hip; convert_labels of test/test_semantic_mapping.py:6-19), restated
+__device__ __forceinline__ int colour_label(unsigned char r, unsigned char g, unsigned char b) {
+    if (r == 128 && g == 64 && b == 128) return 1;            // road
+    if (r == 140 && g == 140 && b == 200) return 2;           // crosswalk
+    if (r == 255 && g == 255 && b == 255) return 3;           // lane
+    if (r == 244 && g == 35 && b == 232) return 4;            // sidewalk
+    if (r == 107 && g == 142 && b == 35) return 5;            // vegetation
+    return 0;
 }
 
 // apply_filter (renderer.py:175-189) at cell (y, x), channel c of src [Hm][Wm][C]: cv2.filter2D with ones(3,3,float32)/9,

@@ -38,36 +38,9 @@ struct OverviewShape {
     long long wpx;                  // pixels per output row, nw * P
 };
 
-// the colour of one reduced row: k_render_bev's rule (mapping.hip), restated -- first maximum wins, a NaN beats every number and the
-// first NaN wins; black where np.sum of the row is 0
-template <typename MapT>
-__device__ __forceinline__ void argmax_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
-    MapT best = row[0];
-    int bi = 0;
-    for (int c = 1; c < C; ++c) {
-        const MapT v = row[c];
-        if (v > best || (v != v && best == best)) { best = v; bi = c; }
-    }
-    unsigned char r = rp.colors[3 * bi], g = rp.colors[3 * bi + 1], b = rp.colors[3 * bi + 2];
-    if (avl::numpy_row_sum(row, C) == (MapT)0) r = g = b = 0;
-    rgb[0] = r; rgb[1] = g; rgb[2] = b;
-}
-
-// k_render_thresholds' rule (mapping.hip), restated: the share is a MapT quotient compared with the threshold in MapT, priorities
-// from low to high, later ones overwrite
-template <typename MapT>
-__device__ __forceinline__ void thresholds_colour(const MapT* row, int C, const RenderParams& rp, unsigned char* rgb) {
-    const MapT s = avl::numpy_row_sum(row, C);
-    unsigned char r = 0, g = 0, b = 0;
-    if (s != (MapT)0) {
-        for (int i = 0; i < C; ++i) {
-            const int ch = rp.priority[i];
-            const MapT pn = row[ch] / s;
-            if (pn >= (MapT)rp.thresholds[i]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
-        }
-    }
-    rgb[0] = r; rgb[1] = g; rgb[2] = b;
-}
+// the colour of one reduced row: argmax_colour / thresholds_colour of avl_render.h, shared with the site finish (seg_sitefinish.hip)
+using avl::argmax_colour;
+using avl::thresholds_colour;
 
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_site_overview(const avl_tile_src* __restrict__ tiles, int n_tiles, OverviewShape s, RenderParams rp,

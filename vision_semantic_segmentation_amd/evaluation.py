@@ -105,6 +105,99 @@ def stats_from_counts(J, class_lists=CLASS_LISTS):
     return iou_lists, acc_lists, miss, accuracy
 
 
+class SiteTruth(object):
+    """The ground truth of a scrolled site for SemanticMapping.site_finish: a label raster (any numeric type, binned by _bin_truth to
+    uint8) whose element [0, 0] lies at the GLOBAL cell ``origin_cell`` of the map (global cell (0, 0) is the MAPPING.BOUNDARY
+    minimum), and an optional validity mask of the same shape (0 = invalid: the label there counts as 0).  The rasters go to the
+    device at their first use there and stay.  Outside the raster the truth is 0 and nothing is masked."""
+
+    def __init__(self, truth, origin_cell, mask=None, tile_cells=None):
+        t = truth.cpu().numpy() if isinstance(truth, torch.Tensor) else np.asarray(truth)
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("SiteTruth: the truth must be a non-empty [H, W] raster, not %r" % (t.shape,))
+        self.truth = np.ascontiguousarray(_bin_truth(t))
+        self.origin_cell = (int(origin_cell[0]), int(origin_cell[1]))
+        self.mask = None
+        if mask is not None:
+            m = mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+            if m.shape != t.shape:
+                raise ValueError("SiteTruth: the mask %r is not of the truth's shape %r" % (m.shape, t.shape))
+            self.mask = np.ascontiguousarray((m != 0).astype(np.uint8))
+        self._dev = {}
+        self._hist = {}
+        if tile_cells:
+            self.tile_hist(int(tile_cells))
+
+    @classmethod
+    def load(cls, path, tile_cells=None):
+        """an .npz with ``truth``, ``origin_cell`` and an optional ``mask``"""
+        with np.load(path, allow_pickle=False) as data:
+            return cls(data["truth"], data["origin_cell"], data["mask"] if "mask" in data.files else None, tile_cells)
+
+    def save(self, path):
+        arrays = {"truth": self.truth, "origin_cell": np.asarray(self.origin_cell, dtype=np.int64)}
+        if self.mask is not None:
+            arrays["mask"] = self.mask
+        with open(path, "wb") as f:
+            np.savez_compressed(f, **arrays)
+
+    def on(self, device):
+        """-> (truth, mask or None) as contiguous uint8 tensors on ``device``"""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.truth).to(device), None if self.mask is None else torch.from_numpy(self.mask).to(device))
+        return self._dev[key]
+
+    def first_tile(self, T, anchor=(0, 0)):
+        """the tile that holds the raster's element [0, 0], for tiles of T cells whose corner lies at the global cell ``anchor``"""
+        return (self.origin_cell[0] - int(anchor[0])) // T, (self.origin_cell[1] - int(anchor[1])) // T
+
+    def tile_hist(self, T, anchor=(0, 0)):
+        """int64 [n_tiles_r, n_tiles_c, 8]: the histogram of the truth per map tile, for the tiles the raster touches -- element
+        [a, b] is tile first_tile(T, anchor) + (a, b); the cells of such a tile outside the raster count as truth 0, as they do for
+        the kernel.  Computed once per (T, anchor) with torch, then cached."""
+        T = int(T)
+        key = (T, int(anchor[0]), int(anchor[1]))
+        if key not in self._hist:
+            fi, fj = self.first_tile(T, anchor)
+            top, lft = self.origin_cell[0] - key[1] - fi * T, self.origin_cell[1] - key[2] - fj * T
+            Hg, Wg = self.truth.shape
+            nr, nc = -(-(top + Hg) // T), -(-(lft + Wg) // T)
+            g = torch.zeros((nr * T, nc * T), dtype=torch.uint8)
+            g[top:top + Hg, lft:lft + Wg] = torch.from_numpy(self.truth)
+            blocks = g.view(nr, T, nc, T)
+            self._hist[key] = torch.stack([(blocks == v).sum(dim=(1, 3)) for v in range(8)], dim=2).to(torch.int64).numpy()
+        return self._hist[key]
+
+    def total_hist(self):
+        return np.bincount(self.truth.ravel(), minlength=8).astype(np.int64)
+
+    def tiles_hist(self, T, ti, tj, anchor=(0, 0)):
+        """int64 [8]: the truth's histogram over the listed tiles (ti[k], tj[k]); a tile the raster does not touch is T * T zeros"""
+        hist = self.tile_hist(T, anchor)
+        fi, fj = self.first_tile(T, anchor)
+        a, b = np.asarray(ti, dtype=np.int64) - fi, np.asarray(tj, dtype=np.int64) - fj
+        inside = (a >= 0) & (a < hist.shape[0]) & (b >= 0) & (b < hist.shape[1])
+        out = hist[a[inside], b[inside]].sum(axis=0, dtype=np.int64).reshape(8)
+        out[0] += (a.size - int(inside.sum())) * T * T
+        return out
+
+    def rect_hist(self, T, rect, anchor=(0, 0)):
+        """int64 [8]: the truth's histogram over the tile rectangle ``rect`` = (ti0, ti1, tj0, tj1), both ends included"""
+        hist = self.tile_hist(T, anchor)
+        fi, fj = self.first_tile(T, anchor)
+        ti0, ti1, tj0, tj1 = (int(v) for v in rect)
+        a0, a1 = max(ti0 - fi, 0), min(ti1 - fi, hist.shape[0] - 1)
+        b0, b1 = max(tj0 - fj, 0), min(tj1 - fj, hist.shape[1] - 1)
+        out = np.zeros(8, dtype=np.int64)
+        n_in = 0
+        if a0 <= a1 and b0 <= b1:
+            out += hist[a0:a1 + 1, b0:b1 + 1].sum(axis=(0, 1), dtype=np.int64)
+            n_in = (a1 - a0 + 1) * (b1 - b0 + 1)
+        out[0] += (max(ti1 - ti0 + 1, 0) * max(tj1 - tj0 + 1, 0) - n_in) * T * T
+        return out
+
+
 class Test(object):
     def __init__(self, ground_truth_dir="./", shift_h=0, shift_w=0, logger=None):
         """:30-81.  Loads <ground_truth_dir>/truth.npy (and mask.npy when present).  The reference can also build
@@ -136,6 +229,21 @@ class Test(object):
         gmap = self._truth_window((h, w))
         _, J = _run(global_map, None, _bin_truth(gmap))
         return self._report(J, latex_mode=False, verbose=True)
+
+    @classmethod
+    def for_site(cls, logger=None):
+        """a Test without truth.npy: the truth of a scrolled site comes as a SiteTruth and arrives here as counts (test_site)"""
+        self = cls.__new__(cls)
+        self.ground_truth_mask = self.mask = self._truth_bins = None
+        self.d, self.class_lists = dict(CLASS_NAMES), list(CLASS_LISTS)
+        self.shift_w = self.shift_h = 0
+        self.logger = logger
+        return self
+
+    def test_site(self, counts):
+        """test_single_map's three lines and result for a scrolled site: ``counts`` is SemanticMapping.site_finish(truth=...).counts,
+        the joint histogram J[gt][label] over the whole rectangle."""
+        return self._report(np.asarray(counts, dtype=np.int64).reshape(8, 8), latex_mode=False, verbose=True)
 
     def iou(self, gmap, generate_map, latex_mode=False, verbose=False):
         """:128-161 -- gmap: ground-truth label map, generate_map: generated label map (both integer-valued)."""

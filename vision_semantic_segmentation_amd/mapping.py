@@ -45,7 +45,9 @@ What differs from the reference, by design:
     by ``mapping()`` / ``mapping_views()``), tiles that leave are kept in a store in HBM and come back when the vehicle returns
     (scroll.py; ``site_map()``, ``site_tiles()``, ``save_site()``, ``load_site()``).  The reference drops every point outside
     MAPPING.BOUNDARY.  Off by default.  ``site_overview()`` is the picture of the whole site at k cells per pixel, rendered from the
-    tiles where they live; with MAPPING.SITE_OVERVIEW.ENABLED ``finish_run()`` also writes it as site_map.png.
+    tiles where they live; with MAPPING.SITE_OVERVIEW.ENABLED ``finish_run()`` also writes it as site_map.png.  ``site_finish()`` is the
+    run's result for the whole site -- the filtered picture at one pixel per cell, its labels and the counts behind the IoU lines -- by
+    one kernel from the tiles; with MAPPING.SITE_FINISH.ENABLED ``finish_run()`` also writes it as site_global_map.png.
   * rospy subscribers/publishers are only created when ``use_ros=True`` and rospy imports; a lock
     serialises the three callbacks (the reference mutates its queues from three threads unlocked).
 """
@@ -690,7 +692,9 @@ class SemanticMapping(object):
         (apply_filter), render it (render_bev_map), write global_map.png and -- with GROUND_TRUTH_DIR set --
         print IoU / accuracy / missing rate.  Filter, renderer and evaluation are GPU kernels; only the PNG and
         the printed numbers leave the device.  Returns the colour map (uint8 [Hm,Wm,3] NumPy).  A scrolling map with
-        MAPPING.SITE_OVERVIEW.ENABLED first writes site_map.png, the overview of the whole, unfiltered site (site_overview)."""
+        MAPPING.SITE_OVERVIEW.ENABLED first writes site_map.png, the overview of the whole, unfiltered site (site_overview), and
+        with MAPPING.SITE_FINISH.ENABLED site_global_map.png, the filtered site at one pixel per cell, and the site's IoU lines
+        (site_finish); global_map.png and the GROUND_TRUTH_DIR branch stay the window's."""
         from .evaluation import Test
         from .renderer import apply_filter, render_bev_map
         if self.record_inputs and self.input_list:
@@ -699,6 +703,8 @@ class SemanticMapping(object):
         os.makedirs(output_dir, exist_ok=True)
         if self._scroll is not None and self.cfg.MAPPING.SITE_OVERVIEW.ENABLED:
             self._write_site_overview(output_dir)                                # before the filter: window and store in one state
+        if self._scroll is not None and self.cfg.MAPPING.SITE_FINISH.ENABLED:
+            self._write_site_finish(output_dir)                                  # before the filter too: it would be applied twice
         smooth = apply_filter(self.map_dev)                                   # :332, the filtered grid replaces the map
         self.map_dev.copy_(smooth.to(self.map_dev.dtype))
         self._map_host = None
@@ -733,6 +739,39 @@ class SemanticMapping(object):
             output_file = output_file[:-4] + ".npy"
             np.save(output_file, picture)
         self.logger.log("Saving the site overview to %s: first cell (%d, %d), %d cells per pixel" % (output_file, i0, j0, k))
+
+    def _write_site_finish(self, output_dir):
+        """site_global_map.png: site_finish() with MAPPING.SITE_FINISH's settings, the FILTERED site at one pixel per cell -- what
+        global_map.png is for the window -- and, with TRUTH_PATH, the site's IoU lines.  Channel order and the .npy fallback are
+        global_map.png's."""
+        from .evaluation import SiteTruth, Test
+        fc = self.cfg.MAPPING.SITE_FINISH
+        T = self._scroll.T
+        tiles = self.site_tiles("map")
+        if not tiles:
+            self.logger.log("The site is empty: no site_global_map.png")
+            return
+        cells = (max(t[0] for t in tiles) - min(t[0] for t in tiles) + 1) * (max(t[1] for t in tiles) - min(t[1] for t in tiles) + 1) * T * T
+        picture = cells <= int(fc.MAX_PIXELS)
+        if not picture:
+            self.logger.log("The site's rectangle has %d cells, more than MAPPING.SITE_FINISH.MAX_PIXELS = %d: site_global_map.png is "
+                            "skipped" % (cells, int(fc.MAX_PIXELS)))
+        truth = SiteTruth.load(fc.TRUTH_PATH, T) if fc.TRUTH_PATH != "" else None
+        if not picture and truth is None:
+            return
+        result = self.site_finish(truth=truth, picture=picture)
+        if picture:
+            color_map = result.picture.cpu().numpy()
+            output_file = osp.join(output_dir, "site_global_map.png")
+            try:
+                from PIL import Image
+                Image.fromarray(np.ascontiguousarray(color_map[:, :, ::-1])).save(output_file)
+            except ImportError:
+                output_file = output_file[:-4] + ".npy"
+                np.save(output_file, color_map)
+            self.logger.log("Saving the filtered site to %s: first cell (%d, %d), %d + %d tiles" % ((output_file,) + tuple(result.origin) + tuple(result.tiles)))
+        if truth is not None:
+            Test.for_site(logger=self.logger).test_site(result.counts)
 
     # ------------------------------------------------------------------ live vehicle-centred map
     def live_map_window(self, pose, size_cells=None):
@@ -1526,6 +1565,25 @@ class SemanticMapping(object):
         with self._lock:
             return self._scroll_store().site_overview(cells_per_pixel, rect, self.label_colors, thresholds, priority, reduced, out, stream,
                                                       int(oc.MAX_SIDE_PX))
+
+    def site_finish(self, rect=None, filter=True, thresholds=None, priority=None, truth=None, picture=True, labels=False, out=None,
+                    stream=None):
+        """-> scroll.SiteFinish(origin, picture, labels, counts, tiles): the run's end result for the whole site -- finish_run's chain
+        apply_filter -> render_bev_map -> convert_labels -> Test.iou's counting -- on the tile rectangle ``rect`` (as site_map's; None =
+        the bounding rectangle of site_tiles("map")), by one kernel that reads the tiles where they live (avl_site_finish; the rule:
+        include/avl_hip.h).  ``picture`` uint8 [H, W, 3] is render_bev_map(apply_filter(site_map(rect)[1])) byte for byte -- with
+        ``thresholds`` (None = MAPPING.SITE_FINISH.THRESHOLDS, [] = arg-max) render_bev_map_with_thresholds' with ``priority`` --
+        ``filter`` False leaves the smoothing out; ``labels`` uint8 [H, W] is convert_labels of it (0 where ``truth``'s mask is 0);
+        ``counts`` (with ``truth``, an evaluation.SiteTruth) is the int64 [8, 8] histogram J[truth][label] over the whole rectangle,
+        what evaluation._run gives on the assembled route, for evaluation.Test.test_site.  ``origin`` is the global cell of the first
+        element, ``tiles`` = (records with a source, empty records computed around them).  With picture=False and labels=False nothing
+        of the rectangle's size is allocated: the way to score a site whose rectangle no buffer could hold.  An empty site gives
+        empty tensors, launches nothing, and counts all of the truth as missed.  ``out``: a contiguous uint8 CUDA tensor of the
+        picture's shape.  Same stream contract as site_map; unlike finish_run's filter, the window and the store are only read."""
+        if thresholds is None:
+            thresholds = list(self.cfg.MAPPING.SITE_FINISH.THRESHOLDS)
+        with self._lock:
+            return self._scroll_store().site_finish(rect, self.label_colors, filter, thresholds, priority, truth, picture, labels, out, stream)
 
     def save_site(self, path, stream=None):
         """The whole site -- the window's own tiles included -- as one .npz: anchor, resolution, T, C, dtype and, per layer, the

@@ -21,6 +21,11 @@ THE SITE OVERVIEW (TileStore.site_overview) is the one reader that assembles not
 k_site_overview of csrc/seg_overview.hip), built with index arithmetic on whole arrays (overview_sources), validated on the host
 (validate_sources) and launched once, gives the site reduced by k x k cells per pixel and its picture.
 
+THE SITE FINISH (TileStore.site_finish) is the run's end result for the whole site -- the filtered picture at one pixel per cell, its
+labels and the ground-truth/label counts -- by the same scheme: a table of tile RECORDS (struct avl_tile_fin, k_site_finish of
+csrc/seg_sitefinish.hip), which is the overview's table plus a NULL record for every absent tile that touches a present one and every
+record's eight neighbour indices (finish_sources), validated on the host (validate_finish) and launched once.
+
 THE STORE.  One pool per layer (the map; with MAPPING.ELEVATION its four arrays), made of chunks of POOL_CHUNK_TILES slabs of
 T * T * bytes_per_cell bytes; a chunk is a CUDA tensor.  The pool grows by whole chunks, so a stored tile never moves and jobs carry
 plain device addresses.  The host owns the directory {(ti, tj): slab} and the free list; a slab index names the same slot in every
@@ -309,6 +314,116 @@ def encode_sources(table, buffers, out):
         out["row"][:n] = table["row"]
         out["col"][:n] = table["col"]
     return n
+
+
+# ------------------------------------------------------------------------------------------------ the finish's record table
+FINISH_DTYPE = np.dtype([("buf", "<i4"), ("row", "<i4"), ("col", "<i4"), ("off", "<i8"), ("pitch", "<i8"), ("nb", "<i4", (9,))])
+"""One tile of a site finish in host form: SOURCE_DTYPE's fields -- ``buf`` -1 = a NULL record, a tile that holds nothing but is computed
+because a present tile touches it -- and ``nb``, the index of the record at (row + dr, col + dc) in nb[(dr + 1) * 3 + (dc + 1)], -1 where
+there is none; nb[4] is the record's own index.  encode_finish turns it into struct avl_tile_fin."""
+
+FIN_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("row", "<i4"), ("col", "<i4"), ("nb", "<i4", (9,)), ("pad", "<i4")])
+
+NEIGHBOUR_OFFSETS = [(dr, dc) for dr in (-1, 0, 1) for dc in (-1, 0, 1)]
+
+
+def finish_neighbours(row, col, nh, nw):
+    """int32 [n, 9]: for records at (row[i], col[i]) -- no place twice -- the index of the record at each of NEIGHBOUR_OFFSETS, -1
+    where there is none or the place lies outside the rectangle.  A sort and nine searches on whole arrays."""
+    row, col = np.asarray(row, dtype=np.int64), np.asarray(col, dtype=np.int64)
+    n = row.size
+    nb = np.full((n, 9), -1, dtype=np.int32)
+    if n == 0:
+        return nb
+    place = row * nw + col
+    in_order = bool((place[1:] > place[:-1]).all())                         # finish_sources' own tables are sorted by (row, col)
+    order = None if in_order else np.argsort(place, kind="stable")
+    sorted_place = place if in_order else place[order]
+    for k, (dr, dc) in enumerate(NEIGHBOUR_OFFSETS):
+        r, c = row + dr, col + dc
+        inside = (r >= 0) & (r < nh) & (c >= 0) & (c < nw)
+        want = r * nw + c
+        at = np.minimum(np.searchsorted(sorted_place, want), n - 1)
+        found = inside & (sorted_place[at] == want)
+        nb[:, k] = np.where(found, at if in_order else order[at], -1)
+    return nb
+
+
+def finish_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, stored_slabs, chunk_tiles):
+    """The record table (FINISH_DTYPE, sorted by row, col) of the tile rectangle ``rect``: overview_sources' records, a NULL record
+    (``buf`` -1) for every absent tile of the rectangle with at least one present 8-neighbour, and every record's neighbour indices.
+    The arguments are overview_sources'.  Index arithmetic on whole arrays: the cost follows what was mapped, not the rectangle."""
+    ti0, ti1, tj0, tj1 = (int(v) for v in rect)
+    nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+    present = overview_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, stored_slabs, chunk_tiles)
+    r, c = present["row"].astype(np.int64), present["col"].astype(np.int64)
+    around = []
+    for dr, dc in NEIGHBOUR_OFFSETS:
+        rr, cc = r + dr, c + dc
+        inside = (rr >= 0) & (rr < nh) & (cc >= 0) & (cc < nw)
+        around.append((rr * nw + cc)[inside])
+    ring = np.setdiff1d(np.concatenate(around) if around else np.zeros(0, dtype=np.int64), r * nw + c)
+    table = np.zeros(len(present) + ring.size, dtype=FINISH_DTYPE)
+    for name in SOURCE_DTYPE.names:
+        table[name][:len(present)] = present[name]
+    table["buf"][len(present):] = -1
+    if ring.size:
+        table["row"][len(present):], table["col"][len(present):] = ring // nw, ring % nw
+    table = table[np.lexsort((table["col"], table["row"]))]
+    table["nb"] = finish_neighbours(table["row"], table["col"], nh, nw)
+    return table
+
+
+def validate_finish(table, buffers, T, bpc, nh, nw):
+    """ValueError, naming the first bad record, unless the record table is safe to launch: everything validate_sources checks for the
+    records with a source; T >= 2; every record, NULL ones included, inside nh x nw and no (row, col) twice; every neighbour index names
+    the record at exactly that offset, or is -1 where there is none (so no index leaves the table)."""
+    if T < 2:
+        raise ValueError("tile records: T = %d cells (at least 2: the filter reflects at the rectangle's edge)" % T)
+    n = len(table)
+    has = table["buf"] >= 0
+    validate_sources(table[has], buffers, T, bpc, nh, nw)
+    if n == 0:
+        return
+
+    def refuse(bad, what):
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("tile record %d of %d %s: %r" % (k, n, what, table[k]))
+    r, c = table["row"].astype(np.int64), table["col"].astype(np.int64)
+    bad = (r < 0) | (r >= nh) | (c < 0) | (c >= nw)
+    if bad.any():
+        refuse(bad, "lies outside the rectangle of %d x %d tiles" % (nh, nw))
+    place = r * nw + c
+    order = np.argsort(place, kind="stable")
+    twice = np.flatnonzero(np.diff(place[order]) == 0)
+    if twice.size:
+        bad = np.zeros(n, dtype=bool)
+        bad[order[twice[0] + 1]] = True
+        refuse(bad, "names a (row, col) that an earlier record names")
+    bad = (np.asarray(table["nb"]).reshape(n, 9) != finish_neighbours(r, c, nh, nw)).any(axis=1)
+    if bad.any():
+        refuse(bad, "has a neighbour index that does not name the record at that offset")
+
+
+def encode_finish(table, buffers, out):
+    """``table`` as struct avl_tile_fin records into the structured array ``out`` (FIN_DTYPE, at least len(table) long)."""
+    n = len(table)
+    if n:
+        base = np.array([b[0] for b in buffers] + [0], dtype=np.uint64)            # buf -1, a NULL record: the appended 0
+        has = table["buf"] >= 0
+        out["src"][:n] = np.where(has, base[table["buf"]] + table["off"].astype(np.uint64), np.uint64(0))
+        out["src_pitch"][:n] = table["pitch"]
+        out["row"][:n] = table["row"]
+        out["col"][:n] = table["col"]
+        out["nb"][:n] = table["nb"]
+        out["pad"][:n] = 0
+    return n
+
+
+SiteFinish = collections.namedtuple("SiteFinish", "origin picture labels counts tiles")
+"""What site_finish returns: ``origin`` the global cell of the first element, ``picture`` uint8 [H, W, 3] and ``labels`` uint8 [H, W]
+(CUDA tensors, or None when not asked for), ``counts`` int64 NumPy [8, 8] over the whole rectangle (None without truth), ``tiles`` =
+(records with a source, NULL records)."""
 
 
 def overview_cells_per_pixel(T, nh, nw, max_side_px):
@@ -676,9 +791,10 @@ class TileStore(object):
             self._run(per_layer, st)
         return (ti0 * T, tj0 * T), (outs[0] if layer == "map" else tuple(outs))
 
-    def overview_table(self, rect=None):
+    def overview_table(self, rect=None, sources=overview_sources):
         """-> (rect, source table, buffers) of the map layer: overview_sources on the window's non-empty tiles and the store's
-        directory and masks.  ``rect`` None = the bounding rectangle of what holds something, (0, -1, 0, -1) for an empty site."""
+        directory and masks (``sources`` = finish_sources: the finish's record table instead).  ``rect`` None = the bounding rectangle
+        of what holds something, (0, -1, 0, -1) for an empty site."""
         self.retire()
         L = self._layers()[0]
         T = self.T
@@ -695,7 +811,7 @@ class TileStore(object):
             tj = np.concatenate([wj + origin_tile[1], tiles[:, 1]])
             rect = (int(ti.min()), int(ti.max()), int(tj.min()), int(tj.max())) if ti.size else (0, -1, 0, -1)
         rect = tuple(int(v) for v in rect)
-        table = overview_sources(rect, T, L.bpc, self.Wm, origin_tile, window, tiles, slabs, self.chunk_tiles)
+        table = sources(rect, T, L.bpc, self.Wm, origin_tile, window, tiles, slabs, self.chunk_tiles)
         buffers = [self._extent(L.get())] + [(c.data_ptr(), int(c.numel())) for c in L.chunks]
         return rect, table, buffers
 
@@ -756,6 +872,86 @@ class TileStore(object):
             _lib.check(rc, "avl_site_overview")
             event.record(st)
         return result
+
+    def site_finish(self, rect=None, colors=None, filter=True, thresholds=None, priority=None, truth=None, picture=True, labels=False,
+                    out=None, stream=None):
+        """-> SiteFinish: the rule of struct avl_tile_fin (include/avl_hip.h) on the tile rectangle ``rect``, one launch.  The kernel
+        counts the tiles with a record; the truth histograms of the rectangle's other tiles (``truth.tile_hist``, exact integers)
+        are added on the host into label 0.  The window and the store are only read."""
+        import ctypes as C
+        from . import _lib
+        torch = self.torch
+        sm = self.sm
+        rect, table, buffers = self.overview_table(rect, finish_sources)
+        ti0, ti1, tj0, tj1 = rect
+        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+        T, Cn = self.T, self.C
+        origin = check_origin((ti0 * T, tj0 * T), T)
+        H, W = nh * T, nw * T
+        if H * W >= 1 << 31:
+            raise ValueError("site_finish: a rectangle of %d x %d cells (below 2^31)" % (H, W))
+        st = self._stream(stream)
+        cur = self._layers()[0].get()
+        with torch.cuda.stream(st):
+            if out is not None:
+                if not picture or tuple(out.shape) != (H, W, 3) or out.dtype != torch.uint8 or out.device != cur.device or not out.is_contiguous():
+                    raise ValueError("site_finish: out must be a contiguous uint8 tensor %r on %s, with picture=True" % ((H, W, 3), cur.device))
+                pic = out
+            else:
+                pic = torch.empty((H, W, 3), dtype=torch.uint8, device=cur.device) if picture else None
+            lab = torch.empty((H, W), dtype=torch.uint8, device=cur.device) if labels else None
+        n = len(table)
+        n_null = int((table["buf"] < 0).sum())
+        tiles = (n - n_null, n_null)
+        counts = None
+        if truth is not None:                                              # the tiles without a record: truth against label 0
+            counts = np.zeros((8, 8), dtype=np.int64)
+            if nh == 0 or nw == 0:                                         # an empty site: nothing was mapped, all of the truth is missed
+                counts[:, 0] = truth.total_hist()
+            else:
+                counts[:, 0] = truth.rect_hist(T, rect) - truth.tiles_hist(T, table["row"].astype(np.int64) + ti0,
+                                                                           table["col"].astype(np.int64) + tj0)
+        if nh == 0 or nw == 0 or (pic is None and lab is None and truth is None):
+            return SiteFinish(origin, pic, lab, counts, tiles)             # an empty site, or nothing asked for: nothing is launched
+        bpc = self._layers()[0].bpc
+        validate_finish(table, buffers, T, bpc, nh, nw)                    # raises before anything is uploaded or launched
+        colors = np.ascontiguousarray(np.asarray(sm.label_colors if colors is None else colors), dtype=np.uint8)
+        if colors.shape != (Cn, 3):
+            raise ValueError("site_finish: %r colours for %d classes" % (colors.shape, Cn))
+        col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
+        th = pr = None
+        if thresholds is not None and len(thresholds):
+            if len(thresholds) < Cn:
+                raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), Cn))
+            if priority is not None and len(priority) != Cn:
+                raise ValueError("Each channel should have a priority.")
+            th = (C.c_double * Cn)(*[float(x) for x in list(thresholds)[:Cn]])
+            pr = (C.c_int32 * Cn)(*[int(p) for p in (priority if priority is not None else range(Cn))])
+        gt = mask = cnt = None
+        Hg = Wg = r0 = c0 = 0
+        if truth is not None:
+            gt, mask = truth.on(cur.device)
+            Hg, Wg = int(gt.shape[0]), int(gt.shape[1])
+            r0, c0 = truth.origin_cell[0] - origin[0], truth.origin_cell[1] - origin[1]
+            if max(abs(r0), abs(c0)) >= 1 << 31:
+                raise ValueError("site_finish: the truth raster starts %d, %d cells from the rectangle" % (r0, c0))
+        nbytes = max(n, 1) * FIN_DTYPE.itemsize
+        host, dev, event = self._ring_slot(nbytes)
+        encode_finish(table, buffers, host.numpy()[:nbytes].view(FIN_DTYPE))
+        dt = _lib.AVL_F64 if cur.dtype == torch.float64 else _lib.AVL_F32
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.stream(st):
+            if truth is not None:
+                cnt = torch.empty(64, dtype=torch.int64, device=cur.device)
+            if n:
+                dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+            rc = _lib.lib().avl_site_finish(C.c_void_p(dev.data_ptr()), n, nh, nw, T, Cn, dt, _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th,
+                                            p(gt), Hg, Wg, Wg, r0, c0, p(mask), Wg, p(pic), p(lab), p(cnt), C.c_void_p(st.cuda_stream))
+            _lib.check(rc, "avl_site_finish")
+            event.record(st)
+            if cnt is not None:
+                counts += cnt.cpu().numpy().reshape(8, 8)                  # waits for the kernel: the counts are a host result
+        return SiteFinish(origin, pic, lab, counts, tiles)
 
     def save_site(self, path, stream=None):
         torch = self.torch

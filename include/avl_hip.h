@@ -768,10 +768,11 @@ int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int 
  *      di = 0 .. k-1 is the outer loop and dj = 0 .. k-1 the inner one; each step is acc = acc + cell[p*k + di][q*k + dj][c].  No FMA,
  *      no reassociation (the translation unit is built with -ffp-contract=off).  The order is part of the rule: it makes R
  *      reproducible bit for bit on a log confusion matrix.  (k = 1: R = +0 + cell, so a cell's -0.0 arrives as +0.)
- *   3. picture: pixel (p, q) is render_bev_map's rule on the row R[p][q][0 .. C): the colour of the first maximum (a NaN beats
- *      every number, the first NaN wins: k_render_bev's clause), black where np.sum of the row in NumPy's order (numpy_row_sum of
- *      csrc/avl_render.h) is 0.  With thresholds it is render_bev_map_with_thresholds' rule instead: the share R[..][ch] / sum in
- *      the map's type against the threshold rounded to that type, priorities from low to high, later ones overwrite.
+ *   3. picture: pixel (p, q) is the render rule of csrc/avl_render.h -- the one statement that avl_render_bev_map(_thresholds),
+ *      avl_live_map, avl_live_view and avl_site_finish call too -- on the row R[p][q][0 .. C): argmax_class, the colour of the first
+ *      maximum (a NaN beats every number, the first NaN wins), black where np.sum of the row in NumPy's order (numpy_row_sum_of)
+ *      is 0.  With thresholds it is thresholds_class instead: the share R[..][ch] / sum in the map's type against the threshold
+ *      rounded to that type, priorities from low to high, later ones overwrite.
  *      For k = 1 the picture is byte-equal to avl_render_bev_map(_thresholds) on the assembled rectangle.
  *   4. absent tiles: a tile of the rectangle without a table entry (it is neither in the window nor in the store, or it is empty)
  *      gives black pixels and R = +0.
@@ -805,8 +806,8 @@ int avl_site_overview(const avl_tile_src* tiles_dev, int n_tiles, int nh, int nw
  *      (double)(1.0f / 9.0f) accumulated in double from +0, dy outer and dx inner, BORDER_REFLECT_101 at the RECTANGLE's edge (never
  *      at a tile's), rounded to the map's type.  Without AVL_LIVE_FILTER in `flags` the filter is off: F = A, bit for bit.
  *   3. picture = avl_render_bev_map(F); with thresholds_host, avl_render_bev_map_thresholds(F, priority_host, thresholds_host)
- *      (argmax_colour / thresholds_colour of csrc/avl_render.h, the one copy the overview shares).
- *   4. labels = k_eval_map's colour -> label table on picture (colour_label of csrc/avl_render.h), 0 where the mask is 0.
+ *      (the same device functions: argmax_class / thresholds_class of csrc/avl_render.h).
+ *   4. labels = avl_eval_map's colour -> label table on picture (colour_label of csrc/avl_render.h), 0 where the mask is 0.
  *   5. counts[g * 8 + l] += 1 for every cell of every tile THAT HAS A RECORD, l its label and g the truth there (values above 7
  *      count as 7).  Truth is a raster gt uint8[Hg][gt_ld] whose element [0][0] lies at rectangle cell (gt_r0, gt_c0), either may be
  *      negative; the optional mask uint8[Hg][mask_ld] (0 = invalid) has the same geometry.  A cell outside the raster has g = 0 and

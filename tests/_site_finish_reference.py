@@ -100,3 +100,46 @@ def truth_raster(rng, shape):
     g[rng.random(shape) < 0.05] = 7
     g[rng.random(shape) < 0.02] = 200
     return g
+
+
+# ------------------------------------------------------------------------------------------------ the kernel through the C ABI
+def run_finish(table, bufs, T, Cn, dtype, nh, nw, device, filter=True, thresholds=None, priority=None, gt=None, gt_r0=0, gt_c0=0, mask=None,
+               picture=True, labels=True):
+    """-> (picture, labels, counts), None for what was not asked for: ``table`` through validate_finish, encode_finish and
+    avl_site_finish; asserts that the guard strips around picture and labels survive"""
+    import ctypes as C
+    import torch
+    from vision_semantic_segmentation_amd import _lib, scroll as s
+    dtype = np.dtype(dtype)
+    dev_bufs = [torch.from_numpy(b).to(device) for b in bufs]
+    extents = [(t.data_ptr(), int(t.numel())) for t in dev_bufs]
+    s.validate_finish(table, extents, T, Cn * dtype.itemsize, nh, nw)
+    rec = np.zeros(max(len(table), 1), dtype=s.FIN_DTYPE)
+    s.encode_finish(table, extents, rec)
+    tiles = torch.from_numpy(rec.view(np.uint8)).to(device)
+    ncell = nh * T * nw * T
+    pic = torch.full((ov.GUARD + 3 * ncell + ov.GUARD,), 0xAB, dtype=torch.uint8, device=device)
+    lab = torch.full((ov.GUARD + ncell + ov.GUARD,), 0xAB, dtype=torch.uint8, device=device)
+    cnt = torch.full((64,), -1, dtype=torch.int64, device=device)
+    gt_t = torch.from_numpy(np.ascontiguousarray(gt)).to(device) if gt is not None else None
+    mask_t = torch.from_numpy(np.ascontiguousarray(mask)).to(device) if mask is not None else None
+    Hg, Wg = (gt if gt is not None else mask).shape if (gt is not None or mask is not None) else (0, 0)
+    colors = np.ascontiguousarray(ov.COLORS[:Cn])
+    col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
+    th = (C.c_double * Cn)(*thresholds) if thresholds is not None else None
+    pr = (C.c_int32 * Cn)(*priority) if priority is not None else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    stream = torch.cuda.current_stream(device).cuda_stream
+    rc = _lib.lib().avl_site_finish(C.c_void_p(tiles.data_ptr()), len(table), nh, nw, T, Cn, _lib.AVL_F64 if dtype == np.float64 else _lib.AVL_F32,
+                                    _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th, p(gt_t), Hg, Wg, Wg, gt_r0, gt_c0, p(mask_t), Wg,
+                                    C.c_void_p(pic.data_ptr() + ov.GUARD) if picture else None, C.c_void_p(lab.data_ptr() + ov.GUARD) if labels else None,
+                                    p(cnt) if gt is not None else None, C.c_void_p(stream))
+    _lib.check(rc, "avl_site_finish")
+    torch.cuda.synchronize(device)
+    pic, lab, cnt = pic.cpu().numpy(), lab.cpu().numpy(), cnt.cpu().numpy()
+    for name, a, asked in (("picture", pic, picture), ("labels", lab, labels)):
+        assert (a[:ov.GUARD] == 0xAB).all() and (a[-ov.GUARD:] == 0xAB).all(), "guard strip of %s written" % name
+        assert asked or (a == 0xAB).all(), "%s written although not asked for" % name
+    assert gt is not None or (cnt == -1).all()
+    return (pic[ov.GUARD:-ov.GUARD].reshape(nh * T, nw * T, 3) if picture else None, lab[ov.GUARD:-ov.GUARD].reshape(nh * T, nw * T) if labels else None,
+            cnt.reshape(8, 8) if gt is not None else None)

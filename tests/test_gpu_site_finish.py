@@ -19,54 +19,11 @@ import pytest
 import _scroll_reference as ref
 import _site_finish_reference as fin
 import _site_overview_reference as ov
+from _site_finish_reference import run_finish
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-
-
 # ------------------------------------------------------------------------------------------------ the kernel through the C ABI
-def run_finish(table, bufs, T, Cn, dtype, nh, nw, device, filter=True, thresholds=None, priority=None, gt=None, gt_r0=0, gt_c0=0, mask=None,
-               picture=True, labels=True):
-    """-> (picture, labels, counts), None for what was not asked for: ``table`` through validate_finish, encode_finish and
-    avl_site_finish; asserts that the guard strips around picture and labels survive"""
-    import torch
-    from vision_semantic_segmentation_amd import _lib, scroll as s
-    dtype = np.dtype(dtype)
-    dev_bufs = [torch.from_numpy(b).to(device) for b in bufs]
-    extents = [(t.data_ptr(), int(t.numel())) for t in dev_bufs]
-    s.validate_finish(table, extents, T, Cn * dtype.itemsize, nh, nw)
-    rec = np.zeros(max(len(table), 1), dtype=s.FIN_DTYPE)
-    s.encode_finish(table, extents, rec)
-    tiles = torch.from_numpy(rec.view(np.uint8)).to(device)
-    ncell = nh * T * nw * T
-    pic = torch.full((GUARD + 3 * ncell + GUARD,), 0xAB, dtype=torch.uint8, device=device)
-    lab = torch.full((GUARD + ncell + GUARD,), 0xAB, dtype=torch.uint8, device=device)
-    cnt = torch.full((64,), -1, dtype=torch.int64, device=device)
-    gt_t = torch.from_numpy(np.ascontiguousarray(gt)).to(device) if gt is not None else None
-    mask_t = torch.from_numpy(np.ascontiguousarray(mask)).to(device) if mask is not None else None
-    Hg, Wg = (gt if gt is not None else mask).shape if (gt is not None or mask is not None) else (0, 0)
-    colors = np.ascontiguousarray(ov.COLORS[:Cn])
-    col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
-    th = (C.c_double * Cn)(*thresholds) if thresholds is not None else None
-    pr = (C.c_int32 * Cn)(*priority) if priority is not None else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    stream = torch.cuda.current_stream(device).cuda_stream
-    rc = _lib.lib().avl_site_finish(C.c_void_p(tiles.data_ptr()), len(table), nh, nw, T, Cn, _lib.AVL_F64 if dtype == np.float64 else _lib.AVL_F32,
-                                    _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th, p(gt_t), Hg, Wg, Wg, gt_r0, gt_c0, p(mask_t), Wg,
-                                    C.c_void_p(pic.data_ptr() + GUARD) if picture else None, C.c_void_p(lab.data_ptr() + GUARD) if labels else None,
-                                    p(cnt) if gt is not None else None, C.c_void_p(stream))
-    _lib.check(rc, "avl_site_finish")
-    torch.cuda.synchronize(device)
-    pic, lab, cnt = pic.cpu().numpy(), lab.cpu().numpy(), cnt.cpu().numpy()
-    for name, a, asked in (("picture", pic, picture), ("labels", lab, labels)):
-        assert (a[:GUARD] == 0xAB).all() and (a[-GUARD:] == 0xAB).all(), "guard strip of %s written" % name
-        assert asked or (a == 0xAB).all(), "%s written although not asked for" % name
-    assert gt is not None or (cnt == -1).all()
-    return (pic[GUARD:-GUARD].reshape(nh * T, nw * T, 3) if picture else None, lab[GUARD:-GUARD].reshape(nh * T, nw * T) if labels else None,
-            cnt.reshape(8, 8) if gt is not None else None)
-
-
 class FinishCase(object):
     """TableCase(T, C, dtype) with a NaN and a +inf cell written into a copy of its buffers, its finish table, the assembled rectangle
     and a truth raster with a mask that starts before the rectangle's first column and ends inside its last row"""

@@ -20,11 +20,9 @@ import pytest
 
 import _scroll_reference as ref
 import _site_overview_reference as ov
+from _site_overview_reference import run_kernel
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 256
-
 
 def bits(a):
     return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
@@ -35,40 +33,6 @@ def divisors(T):
 
 
 # ------------------------------------------------------------------------------------------------ the kernel against the executor
-def run_kernel(table, bufs, T, Cn, dtype, nh, nw, k, device, thresholds=None, priority=None, reduced=True, n_tiles=None):
-    """-> (picture, R or None): ``table`` through validate_sources, encode_sources and avl_site_overview; asserts that the guard
-    strips around both outputs survive"""
-    import torch
-    from vision_semantic_segmentation_amd import _lib, scroll as s
-    dtype = np.dtype(dtype)
-    dev_bufs = [torch.from_numpy(b).to(device) for b in bufs]
-    extents = [(t.data_ptr(), int(t.numel())) for t in dev_bufs]
-    s.validate_sources(table, extents, T, Cn * dtype.itemsize, nh, nw)
-    rec = np.zeros(max(len(table), 1), dtype=s.SRC_DTYPE)
-    s.encode_sources(table, extents, rec)
-    tiles = torch.from_numpy(rec.view(np.uint8)).to(device)
-    P = T // k
-    npx = nh * P * nw * P
-    pic = torch.full((GUARD + 3 * npx + GUARD,), 0xAB, dtype=torch.uint8, device=device)
-    red = torch.full((GUARD + npx * Cn * dtype.itemsize + GUARD,), 0xAB, dtype=torch.uint8, device=device)
-    colors = np.ascontiguousarray(ov.COLORS[:Cn])
-    col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
-    th = (C.c_double * Cn)(*thresholds) if thresholds is not None else None
-    pr = (C.c_int32 * Cn)(*priority) if priority is not None else None
-    stream = torch.cuda.current_stream(device).cuda_stream
-    rc = _lib.lib().avl_site_overview(C.c_void_p(tiles.data_ptr()), len(table) if n_tiles is None else n_tiles, nh, nw, T, Cn,
-                                      _lib.AVL_F64 if dtype == np.float64 else _lib.AVL_F32, k, col, pr, th, C.c_void_p(pic.data_ptr() + GUARD),
-                                      C.c_void_p(red.data_ptr() + GUARD) if reduced else None, C.c_void_p(stream))
-    _lib.check(rc, "avl_site_overview")
-    torch.cuda.synchronize(device)
-    pic, red = pic.cpu().numpy(), red.cpu().numpy()
-    for name, a in (("picture", pic), ("reduced", red)):
-        assert (a[:GUARD] == 0xAB).all() and (a[-GUARD:] == 0xAB).all(), "guard strip of %s written" % name
-    if not reduced:
-        assert (red == 0xAB).all()
-    return pic[GUARD:-GUARD].reshape(nh * P, nw * P, 3), (red[GUARD:-GUARD].view(dtype).reshape(nh * P, nw * P, Cn) if reduced else None)
-
-
 def check_case(case, k, device, thresholds=None, priority=None):
     want_R, want_pic = ov.execute_sources(case.table, case.bufs, case.T, case.C, case.dtype, case.nh, case.nw, k, ov.COLORS[:case.C],
                                           thresholds, priority)

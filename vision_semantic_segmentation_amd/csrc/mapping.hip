@@ -1300,47 +1300,30 @@ __global__ void __launch_bounds__(kBlock) k_ground_fill(MapT* __restrict__ map, 
 }
 
 // ================================================================ end-of-run rendering (src/renderer.py), SURVEY 8f row 3
-// RenderParams, numpy_row_sum (np.sum(map, axis=2) in NumPy's order) and the filter's tap loop are in avl_render.h: the live-map kernel
-// (seg_livemap.hip) computes the same values from them.
+// The rule itself -- arg-max or thresholds pick, NumPy's row sum, class -> colour -- and the filter's tap loop are in avl_render.h.
 using avl::RenderParams;
-using avl::numpy_row_sum;
 
-// render_bev_map (renderer.py:32-59): colour of np.argmax (first maximum wins), black where the channel sum is 0
+// render_bev_map (renderer.py:32-59) and render_bev_map_with_thresholds (renderer.py:131-172), one cell per thread
+template <typename MapT, bool kThresholds>
+__device__ __forceinline__ void render_cell(const MapT* __restrict__ map, long long ncell, int C, const RenderParams& rp,
+                                            unsigned char* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= ncell) return;
+    unsigned char rgb[3];
+    avl::row_colour(map + i * C, C, kThresholds, rp, rgb);
+    out[3 * i] = rgb[0]; out[3 * i + 1] = rgb[1]; out[3 * i + 2] = rgb[2];
+}
+
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_render_bev(const MapT* __restrict__ map, long long ncell, int C, RenderParams rp,
                                                        unsigned char* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= ncell) return;
-    const MapT* row = map + i * C;
-    MapT best = row[0];
-    int bi = 0;
-    for (int c = 1; c < C; ++c) {
-        const MapT v = row[c];
-        if (v > best || (v != v && best == best)) { best = v; bi = c; }
-    }
-    unsigned char r = rp.colors[3 * bi], g = rp.colors[3 * bi + 1], b = rp.colors[3 * bi + 2];
-    if (numpy_row_sum(row, C) == (MapT)0) r = g = b = 0;
-    out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
+    render_cell<MapT, false>(map, ncell, C, rp, out);
 }
 
-// render_bev_map_with_thresholds (renderer.py:131-172): later priorities overwrite earlier ones.  The share is a MapT quotient
-// and is compared with the threshold in MapT: NumPy compares a float32 array with a Python float in float32.
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_render_thresholds(const MapT* __restrict__ map, long long ncell, int C, RenderParams rp,
                                                               unsigned char* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= ncell) return;
-    const MapT* row = map + i * C;
-    const MapT s = numpy_row_sum(row, C);
-    unsigned char r = 0, g = 0, b = 0;
-    if (s != (MapT)0) {
-        for (int k = 0; k < C; ++k) {
-            const int ch = rp.priority[k];
-            const MapT pn = row[ch] / s;                          // np.divide(map, channel_sum), same element type as the map
-            if (pn >= (MapT)rp.thresholds[k]) { r = rp.colors[3 * ch]; g = rp.colors[3 * ch + 1]; b = rp.colors[3 * ch + 2]; }
-        }
-    }
-    out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
+    render_cell<MapT, true>(map, ncell, C, rp, out);
 }
 
 // apply_filter (renderer.py:175-189): cv2.filter2D with ones(3,3,float32)/9, BORDER_REFLECT_101, double accumulation
@@ -2442,48 +2425,36 @@ extern "C" int avl_unpack_pointcloud2(const uint8_t* data, int64_t n_points, int
 
 // ---------------------------------------------------------------------------------------- rendering
 namespace {
-int fill_render(RenderParams& rp, int C, const uint8_t* colors, const int32_t* priority, const double* thresholds) {
-    if (C <= 0 || C > AVL_MAX_MAP_CLASSES) return avl::set_error(AVL_E_ARG, "C = %d", C);
-    if (!colors) return avl::set_error(AVL_E_ARG, "colors_host is NULL");
-    memset(&rp, 0, sizeof(rp));
-    memcpy(rp.colors, colors, 3 * C);
-    for (int k = 0; k < C; ++k) {
-        rp.priority[k] = priority ? priority[k] : k;
-        if (rp.priority[k] < 0 || rp.priority[k] >= C) return avl::set_error(AVL_E_ARG, "priority[%d] = %d", k, rp.priority[k]);
-        rp.thresholds[k] = thresholds ? thresholds[k] : 0.01;
-    }
-    return AVL_OK;
+// the two end-of-run renderers: the checks, the parameter block and the launch of one thread per cell
+int render_whole_map(const char* who, bool thresholds, const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host,
+                     const int32_t* priority_host, const double* thresholds_host, uint8_t* out, void* stream) {
+    AVL_REQUIRE(C > 0 && C <= AVL_MAX_MAP_CLASSES, "C = %d", C);
+    AVL_REQUIRE(colors_host, "colors_host is NULL");
+    RenderParams rp;
+    int rc;
+    if ((rc = avl::fill_render_params(rp, who, C, colors_host, priority_host, thresholds_host))) return rc;
+    AVL_REQUIRE(map && out && Hm > 0 && Wm > 0, "bad map / out");
+    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
+    const long long n = (long long)Hm * Wm;
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    return launch_map_typed(map_dtype, [&](auto t) {
+        typedef decltype(t) T;
+        auto kernel = k_render_bev<T>;
+        if (thresholds) kernel = k_render_thresholds<T>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(map), n, C, rp, out);
+    });
 }
 }  // namespace
 
 extern "C" int avl_render_bev_map(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, uint8_t* out,
                                   void* stream) {
-    RenderParams rp;
-    int rc;
-    if ((rc = fill_render(rp, C, colors_host, nullptr, nullptr))) return rc;
-    AVL_REQUIRE(map && out && Hm > 0 && Wm > 0, "bad map / out");
-    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
-    const long long n = (long long)Hm * Wm;
-    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    return launch_map_typed(map_dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_render_bev<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(map), n, C, rp, out);
-    });
+    return render_whole_map("avl_render_bev_map", false, map, map_dtype, Hm, Wm, C, colors_host, nullptr, nullptr, out, stream);
 }
 
 extern "C" int avl_render_bev_map_thresholds(const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host,
                                              const int32_t* priority_host, const double* thresholds_host, uint8_t* out, void* stream) {
-    RenderParams rp;
-    int rc;
-    if ((rc = fill_render(rp, C, colors_host, priority_host, thresholds_host))) return rc;
-    AVL_REQUIRE(map && out && Hm > 0 && Wm > 0, "bad map / out");
-    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
-    const long long n = (long long)Hm * Wm;
-    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    return launch_map_typed(map_dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_render_thresholds<T>, grid, block, 0, avl::as_stream(stream), static_cast<const T*>(map), n, C, rp, out);
-    });
+    return render_whole_map("avl_render_bev_map_thresholds", true, map, map_dtype, Hm, Wm, C, colors_host, priority_host, thresholds_host,
+                            out, stream);
 }
 
 // ---- end-of-run evaluation (test/test_semantic_mapping.py: convert_labels :6-19, Test.iou :127-161) -----------------
@@ -2500,13 +2471,7 @@ __global__ void __launch_bounds__(kBlock) k_eval_map(const uint8_t* __restrict__
     const long long n = (long long)H * W;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
         const int y = (int)(i / W), x = (int)(i - (long long)y * W);
-        const uint8_t r = color[i * 3], g = color[i * 3 + 1], b = color[i * 3 + 2];
-        int lab = 0;
-        if (r == 128 && g == 64 && b == 128) lab = 1;            // road
-        else if (r == 140 && g == 140 && b == 200) lab = 2;      // crosswalk
-        else if (r == 255 && g == 255 && b == 255) lab = 3;      // lane
-        else if (r == 244 && g == 35 && b == 232) lab = 4;       // sidewalk
-        else if (r == 107 && g == 142 && b == 35) lab = 5;       // vegetation
+        int lab = avl::colour_label(color[i * 3], color[i * 3 + 1], color[i * 3 + 2]);
         if (mask && mask[(long long)y * mask_ld + x] == 0) lab = 0;
         if (labels) labels[i] = (uint8_t)lab;
         if (gt) {

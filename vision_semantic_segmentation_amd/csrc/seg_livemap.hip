@@ -5,8 +5,8 @@
 //
 // Reference (src/renderer.py, src/mapping.py):
 //   renderer.py:175-189  apply_filter            -> avl::box_filter3_taps (avl_render.h, shared with k_box_filter3)
-//   renderer.py:32-59    render_bev_map          -> first maximum, NaN rules and zero-sum test of k_render_bev
-//   renderer.py:131-172  render_bev_map_with_thresholds -> MapT quotient of k_render_thresholds
+//   renderer.py:32-59    render_bev_map          -> avl::argmax_class (avl_render.h, shared with k_render_bev)
+//   renderer.py:131-172  render_bev_map_with_thresholds -> avl::thresholds_class (avl_render.h, shared with k_render_thresholds)
 //   renderer.py:62-105   fill_black / resume_color, AS WRITTEN: every interior pixel (black or not, :91 is commented out) takes the
 //                        highest-priority label whose R value occurs among the R values of its 3 x 3 neighbourhood; matching is
 //                        on R only, so colours that share an R value are conflated (the last such label wins in resume_color)
@@ -107,34 +107,16 @@ __device__ __forceinline__ int fill_pick(const unsigned char* centre, const unsi
     return label;
 }
 
-// class index of grid cell (gx, gy) -- row gx of Hm, column gy of Wm -- or kBlack
+// class index of grid cell (gx, gy) -- row gx of Hm, column gy of Wm -- or kBlack: the render rule of avl_render.h on the cell's
+// row, read as it is or through the filter
 template <typename MapT>
 __device__ __forceinline__ int cell_class(const MapT* __restrict__ map, const LiveParams& p, int gx, int gy) {
     const int Hm = p.Hm, Wm = p.Wm, C = p.C;
     const bool filt = p.flags & AVL_LIVE_FILTER;
     const MapT* row = map + ((long long)gx * Wm + gy) * C;
     auto value = [&](int c) -> MapT { return filt ? (MapT)avl::box_filter3_taps(map, Hm, Wm, C, gx, gy, c) : row[c]; };
-    if (!(p.flags & AVL_LIVE_THRESHOLDS)) {
-        MapT best = (MapT)0;
-        int bi = 0;
-        const MapT s = avl::numpy_row_sum_of<MapT>(C, [&](int c) -> MapT {
-            const MapT v = value(c);
-            if (c == 0) best = v;
-            else if (v > best || (v != v && best == best)) { best = v; bi = c; }
-            return v;
-        });
-        return s == (MapT)0 ? kBlack : bi;
-    }
-    const MapT s = avl::numpy_row_sum_of<MapT>(C, value);
-    int cls = kBlack;
-    if (s != (MapT)0) {
-        for (int k = 0; k < C; ++k) {
-            const int ch = p.rp.priority[k];
-            const MapT pn = value(ch) / s;
-            if (pn >= (MapT)p.rp.thresholds[k]) cls = ch;
-        }
-    }
-    return cls;
+    const int cls = (p.flags & AVL_LIVE_THRESHOLDS) ? avl::thresholds_class<MapT>(C, p.rp, value) : avl::argmax_class<MapT>(C, value);
+    return cls == avl::kNoClass ? kBlack : cls;
 }
 
 template <typename MapT>
@@ -304,7 +286,7 @@ int build_fill(FillTable& ft, const uint8_t* colors, int n, const int32_t* prio,
 // what avl_live_map and avl_live_view share: every check on the arguments, and the parameter block but for the window's geometry
 int live_params(LiveParams& p, const void* map, int map_dtype, int Hm, int Wm, int C, const uint8_t* colors_host, int h, int w, int flags,
                 const int32_t* priority_host, const double* thresholds_host, const int32_t* fill_priority_host, int n_fill_priority,
-                const double* car_host, const uint8_t* car_color_host, const uint8_t* out) {
+                const double* car_host, const uint8_t* car_color_host, const uint8_t* out, const char* who) {
     AVL_REQUIRE(map, "map is NULL");
     AVL_REQUIRE(out, "out is NULL");
     AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "map dtype %d", map_dtype);
@@ -318,13 +300,8 @@ int live_params(LiveParams& p, const void* map, int map_dtype, int Hm, int Wm, i
     AVL_REQUIRE(!(flags & AVL_LIVE_THRESHOLDS) || thresholds_host, "AVL_LIVE_THRESHOLDS without thresholds_host");
     memset(&p, 0, sizeof(p));
     p.Hm = Hm; p.Wm = Wm; p.C = C; p.h = h; p.w = w; p.flags = flags;
-    memcpy(p.rp.colors, colors_host, 3 * C);
-    for (int k = 0; k < C; ++k) {
-        p.rp.priority[k] = priority_host ? priority_host[k] : k;
-        AVL_REQUIRE(p.rp.priority[k] >= 0 && p.rp.priority[k] < C, "priority[%d] = %d", k, p.rp.priority[k]);
-        p.rp.thresholds[k] = thresholds_host ? thresholds_host[k] : 0.01;
-    }
     int rc;
+    if ((rc = avl::fill_render_params(p.rp, who, C, colors_host, priority_host, thresholds_host))) return rc;
     if ((rc = build_fill(p.ft, colors_host, C, fill_priority_host, (flags & AVL_LIVE_FILL) ? n_fill_priority : 0))) return rc;
     if (car_host) {
         p.has_car = 1;
@@ -345,7 +322,7 @@ extern "C" int avl_live_map(const void* map, int map_dtype, int Hm, int Wm, int 
     LiveParams p;
     int rc;
     if ((rc = live_params(p, map, map_dtype, Hm, Wm, C, colors_host, h, w, flags, priority_host, thresholds_host, fill_priority_host,
-                          n_fill_priority, car_host, car_color_host, out))) return rc;
+                          n_fill_priority, car_host, car_color_host, out, "avl_live_map"))) return rc;
     p.x0 = x0; p.y0 = y0;
     const dim3 grid((unsigned)((w + kTW - 1) / kTW), (unsigned)((h + kTH - 1) / kTH)), block(kBlock);
     if (map_dtype == AVL_F64) hipLaunchKernelGGL(k_live_map<double>, grid, block, 0, avl::as_stream(stream), static_cast<const double*>(map), p, out);
@@ -361,7 +338,7 @@ extern "C" int avl_live_view(const void* map, int map_dtype, int Hm, int Wm, int
     ViewParams vp;
     int rc;
     if ((rc = live_params(vp.p, map, map_dtype, Hm, Wm, C, colors_host, h, w, flags, priority_host, thresholds_host, fill_priority_host,
-                          n_fill_priority, car_host, car_color_host, out))) return rc;
+                          n_fill_priority, car_host, car_color_host, out, "avl_live_view"))) return rc;
     AVL_REQUIRE(matrix_host, "matrix_host is NULL");
     for (int k = 0; k < 6; ++k) {
         AVL_REQUIRE(std::isfinite(matrix_host[k]), "matrix[%d][%d] = %g is not finite", k / 3, k % 3, matrix_host[k]);

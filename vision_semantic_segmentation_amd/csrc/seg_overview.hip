@@ -23,6 +23,7 @@
 namespace {
 
 using avl::RenderParams;
+using avl::round16;
 
 constexpr int kBlock = 256;
 constexpr int kTargetWorkgroups = 8192;                  // a handful of tiles is split until the machine is full
@@ -34,13 +35,9 @@ struct OverviewShape {
     int qn, cw, rs;                 // a chunk's pixels, a stage's cells per pixel (k unless a pixel's row exceeds a stage), a stage's rows
     int pitch;                      // bytes between the rows of a stage in LDS, a multiple of 16
     int stage_bytes;                // rs * pitch
-    int thresholds;                 // 0: k_render_bev's rule, 1: k_render_thresholds'
+    int thresholds;                 // the render rule's pick (avl_render.h): 0 arg-max, 1 thresholds
     long long wpx;                  // pixels per output row, nw * P
 };
-
-// the colour of one reduced row: argmax_colour / thresholds_colour of avl_render.h, shared with the site finish (seg_sitefinish.hip)
-using avl::argmax_colour;
-using avl::thresholds_colour;
 
 template <typename MapT>
 __global__ void __launch_bounds__(kBlock) k_site_overview(const avl_tile_src* __restrict__ tiles, int n_tiles, OverviewShape s, RenderParams rp,
@@ -90,10 +87,7 @@ __global__ void __launch_bounds__(kBlock) k_site_overview(const avl_tile_src* __
                 }
             }
             __syncthreads();                                                          // acc holds R of the chunk
-            for (int q = tid; q < nq; q += kBlock) {
-                if (s.thresholds) thresholds_colour(acc + q * C, C, rp, pix + 3 * q);
-                else argmax_colour(acc + q * C, C, rp, pix + 3 * q);
-            }
+            for (int q = tid; q < nq; q += kBlock) avl::row_colour(acc + q * C, C, s.thresholds != 0, rp, pix + 3 * q);
             const long long px0 = prow * s.wpx + (long long)tile.col * P + q0;       // the chunk's first pixel
             if (reduced != nullptr) {
                 MapT* out = reduced + px0 * C;
@@ -115,19 +109,6 @@ __global__ void __launch_bounds__(kBlock) k_site_overview(const avl_tile_src* __
     }
 }
 
-int fill_params(RenderParams& rp, int C, const uint8_t* colors, const int32_t* priority, const double* thresholds) {
-    memset(&rp, 0, sizeof(rp));
-    memcpy(rp.colors, colors, 3 * (size_t)C);
-    for (int i = 0; i < C; ++i) {
-        rp.priority[i] = priority ? priority[i] : i;
-        AVL_REQUIRE(rp.priority[i] >= 0 && rp.priority[i] < C, "avl_site_overview: priority[%d] = %d", i, rp.priority[i]);
-        rp.thresholds[i] = thresholds ? thresholds[i] : 0.0;
-    }
-    return AVL_OK;
-}
-
-int round16(int v) { return (v + 15) & ~15; }
-
 }  // namespace
 
 extern "C" {
@@ -135,27 +116,18 @@ extern "C" {
 int avl_site_overview(const avl_tile_src* tiles_dev, int n_tiles, int nh, int nw, int tile_cells, int C, int map_dtype, int k,
                       const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, uint8_t* picture,
                       void* reduced, void* stream) {
-    AVL_REQUIRE(tile_cells >= 1 && tile_cells <= (1 << 14), "avl_site_overview: tile_cells = %d (1 .. 16384)", tile_cells);
+    int rc;
+    if ((rc = avl::check_tile_table("avl_site_overview", tiles_dev, n_tiles, nh, nw, tile_cells, 1, C, map_dtype))) return rc;
     AVL_REQUIRE(k >= 1 && tile_cells % k == 0, "avl_site_overview: k = %d cells per pixel does not divide tile_cells = %d", k, tile_cells);
-    AVL_REQUIRE(C >= 1 && C <= AVL_MAX_MAP_CLASSES, "avl_site_overview: C = %d (1 .. %d)", C, AVL_MAX_MAP_CLASSES);
-    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "avl_site_overview: map dtype %d", map_dtype);
     const int es = map_dtype == AVL_F64 ? 8 : 4;
-    AVL_REQUIRE((tile_cells * C * es) % 16 == 0, "avl_site_overview: a tile row of %d cells of %d bytes is no multiple of 16 bytes", tile_cells,
-                C * es);
-    AVL_REQUIRE(nh > 0 && nw > 0, "avl_site_overview: a rectangle of nh = %d x nw = %d tiles", nh, nw);
-    AVL_REQUIRE(n_tiles >= 0 && (long long)n_tiles <= (long long)nh * nw, "avl_site_overview: n_tiles = %d (0 .. nh * nw = %lld)", n_tiles,
-                (long long)nh * nw);
     const int P = tile_cells / k;
     const long long hpx = (long long)nh * P, wpx = (long long)nw * P;                 // each below 2^45
     AVL_REQUIRE(hpx < (1ll << 31) && wpx < (1ll << 31) && hpx * wpx < (1ll << 31), "avl_site_overview: an output of %lld x %lld pixels (below 2^31)",
                 hpx, wpx);
     AVL_REQUIRE(picture != nullptr && colors_host != nullptr, "avl_site_overview: picture or colors_host is NULL");
-    AVL_REQUIRE(n_tiles == 0 || tiles_dev != nullptr, "avl_site_overview: tiles_dev is NULL for %d tiles", n_tiles);
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(tiles_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(reduced) & (uintptr_t)(es - 1)) == 0,
-                "avl_site_overview: tiles_dev or reduced is misaligned");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(reduced) & (uintptr_t)(es - 1)) == 0, "avl_site_overview: reduced is misaligned");
     RenderParams rp;
-    int rc;
-    if ((rc = fill_params(rp, C, colors_host, priority_host, thresholds_host))) return rc;
+    if ((rc = avl::fill_render_params(rp, "avl_site_overview", C, colors_host, priority_host, thresholds_host))) return rc;
 
     const size_t npx = (size_t)(hpx * wpx);
     AVL_HIP_CHECK(hipMemsetAsync(picture, 0, npx * 3, avl::as_stream(stream)));

@@ -14,7 +14,7 @@
 //                   A lane issues kLoads of these loads before it stores any of them to LDS, so their latencies overlap.
 //                   Thread idx = (r * nc + q) * C + c then forms F of the rule from the nine taps in LDS -- dy outer, dx inner,
 //                   acc = acc + (double)(1.0f / 9.0f) * tap, rounded to the map's type -- and keeps it in LDS; thread (r, q) colours
-//                   the cell from there (argmax_colour / thresholds_colour of avl_render.h), labels it, looks the truth up and counts
+//                   the cell from there (the render rule and colour_label of avl_render.h), labels it, looks the truth up and counts
 //                   into a 64-bin LDS histogram.  Colours and labels leave as contiguous runs per tile row (dwords where the address
 //                   allows; the bytes in front of and behind the dwords by one lane).  After the last strip the workgroup adds its
 //                   non-zero bins to counts with one integer atomicAdd each (k_eval_map's scheme): the result does not depend on order.
@@ -29,8 +29,7 @@
 namespace {
 
 using avl::RenderParams;
-using avl::argmax_colour;
-using avl::thresholds_colour;
+using avl::round16;
 
 constexpr int kBlock = 256;
 constexpr int kTargetWorkgroups = 8192;                  // a handful of tiles is split until the machine is full
@@ -42,7 +41,7 @@ struct FinishShape {
     int C, T, H, W;                 // the rectangle has H = nh * T rows of W = nw * T cells
     int split, strips, nr, nc;      // workgroups per tile, strips per tile, rows per strip, cells per column chunk
     int halo;                       // 1 with the filter, 0 without: nothing around the strip is loaded
-    int thresholds;                 // 0: k_render_bev's rule, 1: k_render_thresholds'
+    int thresholds;                 // the render rule's pick (avl_render.h): 0 arg-max, 1 thresholds
     int pitch, hp;                  // bytes between the rows of a stage / of a halo column in LDS, multiples of 16
     int off_left, off_right, off_filt, off_pix, off_lab, off_hist, off_nb;       // byte offsets of the LDS areas behind the stage
     int Hg, Wg, gt_r0, gt_c0;
@@ -176,8 +175,7 @@ __global__ void __launch_bounds__(kBlock) k_site_finish(const avl_tile_fin* __re
             }
             __syncthreads();                                                          // filt holds F of the chunk
             for (int i = tid; i < nrow * ncol; i += kBlock) {
-                if (s.thresholds) thresholds_colour(filt + i * C, C, rp, pix + 3 * i);
-                else argmax_colour(filt + i * C, C, rp, pix + 3 * i);
+                avl::row_colour(filt + i * C, C, s.thresholds != 0, rp, pix + 3 * i);
                 if (labels != nullptr || gt != nullptr) {
                     int l = avl::colour_label(pix[3 * i], pix[3 * i + 1], pix[3 * i + 2]);
                     const int r = i / ncol, q = i - r * ncol;
@@ -213,19 +211,6 @@ __global__ void __launch_bounds__(kBlock) k_site_finish(const avl_tile_fin* __re
     if (counts != nullptr && tid < 64 && hist[tid]) atomicAdd(&counts[tid], (unsigned long long)hist[tid]);
 }
 
-int fill_params(RenderParams& rp, int C, const uint8_t* colors, const int32_t* priority, const double* thresholds) {
-    memset(&rp, 0, sizeof(rp));
-    memcpy(rp.colors, colors, 3 * (size_t)C);
-    for (int i = 0; i < C; ++i) {
-        rp.priority[i] = priority ? priority[i] : i;
-        AVL_REQUIRE(rp.priority[i] >= 0 && rp.priority[i] < C, "avl_site_finish: priority[%d] = %d", i, rp.priority[i]);
-        rp.thresholds[i] = thresholds ? thresholds[i] : 0.0;
-    }
-    return AVL_OK;
-}
-
-int round16(int v) { return (v + 15) & ~15; }
-
 // the LDS areas of a stage of nr rows of nc cells into `s`; -> bytes
 long long lay_out(FinishShape& s, int nr, int nc, int cell_bytes) {
     s.nr = nr; s.nc = nc;
@@ -251,16 +236,10 @@ int avl_site_finish(const avl_tile_fin* tiles_dev, int n_tiles, int nh, int nw, 
                     const uint8_t* colors_host, const int32_t* priority_host, const double* thresholds_host, const uint8_t* gt,
                     int Hg, int Wg, int64_t gt_ld, int gt_r0, int gt_c0, const uint8_t* mask, int64_t mask_ld, uint8_t* picture,
                     uint8_t* labels, unsigned long long* counts, void* stream) {
-    AVL_REQUIRE(tile_cells >= 2 && tile_cells <= (1 << 14), "avl_site_finish: tile_cells = %d (2 .. 16384)", tile_cells);
-    AVL_REQUIRE(C >= 1 && C <= AVL_MAX_MAP_CLASSES, "avl_site_finish: C = %d (1 .. %d)", C, AVL_MAX_MAP_CLASSES);
-    AVL_REQUIRE(map_dtype == AVL_F64 || map_dtype == AVL_F32, "avl_site_finish: map dtype %d", map_dtype);
+    int rc;
+    if ((rc = avl::check_tile_table("avl_site_finish", tiles_dev, n_tiles, nh, nw, tile_cells, 2, C, map_dtype))) return rc;
     AVL_REQUIRE((flags & ~AVL_LIVE_FILTER) == 0, "avl_site_finish: flags = %d (AVL_LIVE_FILTER or 0)", flags);
     const int es = map_dtype == AVL_F64 ? 8 : 4;
-    AVL_REQUIRE((tile_cells * C * es) % 16 == 0, "avl_site_finish: a tile row of %d cells of %d bytes is no multiple of 16 bytes", tile_cells,
-                C * es);
-    AVL_REQUIRE(nh > 0 && nw > 0, "avl_site_finish: a rectangle of nh = %d x nw = %d tiles", nh, nw);
-    AVL_REQUIRE(n_tiles >= 0 && (long long)n_tiles <= (long long)nh * nw, "avl_site_finish: n_tiles = %d (0 .. nh * nw = %lld)", n_tiles,
-                (long long)nh * nw);
     const long long H = (long long)nh * tile_cells, W = (long long)nw * tile_cells;   // each below 2^45
     AVL_REQUIRE(H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31), "avl_site_finish: an output of %lld x %lld cells (below 2^31)", H, W);
     AVL_REQUIRE(picture != nullptr || labels != nullptr || counts != nullptr, "avl_site_finish: no output given (picture, labels and counts are NULL)");
@@ -270,12 +249,9 @@ int avl_site_finish(const avl_tile_fin* tiles_dev, int n_tiles, int nh, int nw, 
     AVL_REQUIRE(gt == nullptr || gt_ld >= Wg, "avl_site_finish: gt_ld = %lld < Wg = %d", (long long)gt_ld, Wg);
     AVL_REQUIRE(mask == nullptr || mask_ld >= Wg, "avl_site_finish: mask_ld = %lld < Wg = %d", (long long)mask_ld, Wg);
     AVL_REQUIRE(colors_host != nullptr, "avl_site_finish: colors_host is NULL");
-    AVL_REQUIRE(n_tiles == 0 || tiles_dev != nullptr, "avl_site_finish: tiles_dev is NULL for %d tiles", n_tiles);
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(tiles_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(counts) & 7) == 0,
-                "avl_site_finish: tiles_dev or counts is misaligned");
+    AVL_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7) == 0, "avl_site_finish: counts is misaligned");
     RenderParams rp;
-    int rc;
-    if ((rc = fill_params(rp, C, colors_host, priority_host, thresholds_host))) return rc;
+    if ((rc = avl::fill_render_params(rp, "avl_site_finish", C, colors_host, priority_host, thresholds_host))) return rc;
 
     const size_t ncell = (size_t)(H * W);
     if (picture != nullptr) AVL_HIP_CHECK(hipMemsetAsync(picture, 0, ncell * 3, avl::as_stream(stream)));

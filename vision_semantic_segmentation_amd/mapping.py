@@ -710,40 +710,29 @@ class SemanticMapping(object):
         self._map_host = None
         color_dev = render_bev_map(self.map_dev, self.label_colors)              # :334
         color_map = color_dev.cpu().numpy()
-        output_file = osp.join(output_dir, "global_map.png")
-        try:
-            from PIL import Image
-            # cv2.imwrite (:340) stores channel 0 of the array as BLUE; write the same file
-            Image.fromarray(np.ascontiguousarray(color_map[:, :, ::-1])).save(output_file)
+        output_file = _write_picture(osp.join(output_dir, "global_map.png"), color_map)
+        if output_file.endswith(".png"):
             self.logger.log("Saving image to %s" % output_file)
-        except ImportError:
-            np.save(output_file[:-4] + ".npy", color_map)
         if self.ground_truth_dir != "":                                          # :342-345
             Test(ground_truth_dir=self.ground_truth_dir, logger=self.logger).test_single_map(color_dev)
         return color_map
 
     def _write_site_overview(self, output_dir):
         """site_map.png: site_overview() with MAPPING.SITE_OVERVIEW's settings, of the unfiltered site (global_map.png is the filtered
-        window).  Channel order and the .npy fallback are global_map.png's."""
+        window).  Written by _write_picture, like global_map.png."""
         (i0, j0), picture = self.site_overview()
         picture = picture.cpu().numpy()
         if picture.size == 0:
             self.logger.log("The site is empty: no site_map.png")
             return
         k = self.last_site_overview["cells_per_pixel"]
-        output_file = osp.join(output_dir, "site_map.png")
-        try:
-            from PIL import Image
-            Image.fromarray(np.ascontiguousarray(picture[:, :, ::-1])).save(output_file)
-        except ImportError:
-            output_file = output_file[:-4] + ".npy"
-            np.save(output_file, picture)
+        output_file = _write_picture(osp.join(output_dir, "site_map.png"), picture)
         self.logger.log("Saving the site overview to %s: first cell (%d, %d), %d cells per pixel" % (output_file, i0, j0, k))
 
     def _write_site_finish(self, output_dir):
         """site_global_map.png: site_finish() with MAPPING.SITE_FINISH's settings, the FILTERED site at one pixel per cell -- what
-        global_map.png is for the window -- and, with TRUTH_PATH, the site's IoU lines.  Channel order and the .npy fallback are
-        global_map.png's."""
+        global_map.png is for the window -- and, with TRUTH_PATH, the site's IoU lines.  Written by _write_picture, like
+        global_map.png."""
         from .evaluation import SiteTruth, Test
         fc = self.cfg.MAPPING.SITE_FINISH
         T = self._scroll.T
@@ -761,14 +750,7 @@ class SemanticMapping(object):
             return
         result = self.site_finish(truth=truth, picture=picture)
         if picture:
-            color_map = result.picture.cpu().numpy()
-            output_file = osp.join(output_dir, "site_global_map.png")
-            try:
-                from PIL import Image
-                Image.fromarray(np.ascontiguousarray(color_map[:, :, ::-1])).save(output_file)
-            except ImportError:
-                output_file = output_file[:-4] + ".npy"
-                np.save(output_file, color_map)
+            output_file = _write_picture(osp.join(output_dir, "site_global_map.png"), result.picture.cpu().numpy())
             self.logger.log("Saving the filtered site to %s: first cell (%d, %d), %d + %d tiles" % ((output_file,) + tuple(result.origin) + tuple(result.tiles)))
         if truth is not None:
             Test.for_site(logger=self.logger).test_site(result.counts)
@@ -787,6 +769,24 @@ class SemanticMapping(object):
             centre = cxy.astype(np.int32)
         return (int(centre[0]) - h // 2, int(centre[1]) - w // 2), (h, w), (float(cxy[0]), float(cxy[1]))
 
+    def _live_settings(self, pose):
+        """MAPPING.LIVE_MAP's filter, renderer, fill and car settings as keyword arguments of renderer.render_window / render_view"""
+        from . import renderer
+        lc = self.live_cfg
+        car = None
+        if lc.DRAW_CAR:
+            c, s = pose_heading(pose)
+            cx, cy = self.live_map_window(pose, (1, 1))[2]
+            car = renderer.car_block(cx, cy, c, s, self.resolution, lc.CAR_SIZE)
+        if lc.RENDER not in ("argmax", "thresholds"):
+            raise ValueError("MAPPING.LIVE_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (lc.RENDER,))
+        thresholds = priority = None
+        if lc.RENDER == "thresholds":
+            thresholds = lc.THRESHOLDS if lc.THRESHOLDS is not None else [0.01] * self.map_depth
+            priority = lc.PRIORITY
+        return dict(filter=bool(lc.FILTER), thresholds=thresholds, priority=priority, fill=bool(lc.FILL_BLACK),
+                    fill_priority=lc.FILL_PRIORITY, car=car)
+
     def live_map(self, pose=None, size_cells=None, out=None, stream=None):
         """The map around the vehicle as a uint8 CUDA tensor [h, w, 3], rendered by one kernel (renderer.render_window with
         MAPPING.LIVE_MAP's settings): out[i, j] is grid cell (x0 + i, y0 + j) in the global map's orientation (live_view() is the
@@ -794,23 +794,11 @@ class SemanticMapping(object):
         ``size_cells`` None = LIVE_MAP.SIZE_M.  Reads the grid only -- unlike finish_run, which replaces it by its filtered self.
         On several GPUs this is the rank's private grid, not global_map()."""
         from . import renderer
-        lc = self.live_cfg
         pose = self._live_pose if pose is None else pose
         if pose is None:
             raise RuntimeError("live_map needs a pose: none was given and no frame has been mapped with one")
-        origin, size, (cx, cy) = self.live_map_window(pose, size_cells)
-        car = None
-        if lc.DRAW_CAR:
-            c, s = pose_heading(pose)
-            car = renderer.car_block(cx, cy, c, s, self.resolution, lc.CAR_SIZE)
-        if lc.RENDER not in ("argmax", "thresholds"):
-            raise ValueError("MAPPING.LIVE_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (lc.RENDER,))
-        thresholds = None
-        if lc.RENDER == "thresholds":
-            thresholds = lc.THRESHOLDS if lc.THRESHOLDS is not None else [0.01] * self.map_depth
-        img = renderer.render_window(self.map_dev, self.label_colors, origin, size, filter=bool(lc.FILTER), thresholds=thresholds,
-                                     priority=lc.PRIORITY if lc.RENDER == "thresholds" else None, fill=bool(lc.FILL_BLACK),
-                                     fill_priority=lc.FILL_PRIORITY, car=car, out=out, stream=stream)
+        origin, size, _ = self.live_map_window(pose, size_cells)
+        img = renderer.render_window(self.map_dev, self.label_colors, origin, size, out=out, stream=stream, **self._live_settings(pose))
         self.live_map_origin = origin
         return img
 
@@ -831,25 +819,12 @@ class SemanticMapping(object):
         black where the view leaves the grid, the ego footprint painted last.  ``pose`` None = the last pose mapped; ``size_px``
         None = LIVE_VIEW.SIZE_PX.  Reads the grid only."""
         from . import renderer
-        lc = self.live_cfg
         pose = self._live_pose if pose is None else pose
         if pose is None:
             raise RuntimeError("live_view needs a pose: none was given and no frame has been mapped with one")
         size = [int(v) for v in (self.live_view_cfg.SIZE_PX if size_px is None else size_px)]
         matrix = self.live_view_matrix(pose, size)
-        car = None
-        if lc.DRAW_CAR:
-            c, s = pose_heading(pose)
-            cx, cy = self.live_map_window(pose, (1, 1))[2]
-            car = renderer.car_block(cx, cy, c, s, self.resolution, lc.CAR_SIZE)
-        if lc.RENDER not in ("argmax", "thresholds"):
-            raise ValueError("MAPPING.LIVE_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (lc.RENDER,))
-        thresholds = None
-        if lc.RENDER == "thresholds":
-            thresholds = lc.THRESHOLDS if lc.THRESHOLDS is not None else [0.01] * self.map_depth
-        img = renderer.render_view(self.map_dev, self.label_colors, matrix, size, filter=bool(lc.FILTER), thresholds=thresholds,
-                                   priority=lc.PRIORITY if lc.RENDER == "thresholds" else None, fill=bool(lc.FILL_BLACK),
-                                   fill_priority=lc.FILL_PRIORITY, car=car, out=out, stream=stream)
+        img = renderer.render_view(self.map_dev, self.label_colors, matrix, size, out=out, stream=stream, **self._live_settings(pose))
         self.live_view_matrix_last = matrix
         return img
 
@@ -1766,6 +1741,19 @@ def pose_heading(pose):
 
 def _to_numpy(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _write_picture(png_path, picture):
+    """``picture`` (uint8 [h, w, 3] NumPy) as the file cv2.imwrite would write (mapping.py:340): channel 0 of the array is stored as
+    BLUE.  Without PIL the array goes to a .npy file of the same name.  Returns the path written."""
+    try:
+        from PIL import Image
+    except ImportError:
+        npy_path = png_path[:-4] + ".npy"
+        np.save(npy_path, picture)
+        return npy_path
+    Image.fromarray(np.ascontiguousarray(picture[:, :, ::-1])).save(png_path)
+    return png_path
 
 
 def _pose_to_array(pose):

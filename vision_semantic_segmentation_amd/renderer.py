@@ -41,6 +41,33 @@ def _colors(label_colors, c):
     return (C.c_uint8 * lc.size)(*lc.ravel().tolist())
 
 
+def render_params(label_colors, c, thresholds=None, priority=None):
+    """(colours, priority, thresholds) of a map of ``c`` channels as the ctypes arrays every renderer entry point of the library takes;
+    ``priority`` / ``thresholds`` None stay None (the library's defaults: 0 .. c - 1, and the arg-max renderer where it has the
+    choice).  Fewer thresholds than channels raise IndexError, as the reference's ``thresholds[i]`` does; further ones are ignored."""
+    colors = _colors(label_colors, c)
+    th = pr = None
+    if thresholds is not None:
+        thresholds = list(thresholds)
+        if len(thresholds) < c:
+            raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), c))
+        th = (C.c_double * c)(*[float(x) for x in thresholds[:c]])
+    if priority is not None:
+        if len(priority) != c:
+            raise ValueError("Each channel should have a priority.")
+        pr = (C.c_int32 * c)(*[int(p) for p in priority])
+    return colors, pr, th
+
+
+def out_picture(out, h, w, device):
+    """``out`` if it is a contiguous uint8 [h, w, 3] tensor on ``device`` (ValueError otherwise), a new one for None"""
+    if out is None:
+        return torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=device)
+    if tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (h, w, device))
+    return out
+
+
 def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
@@ -59,17 +86,11 @@ def render_bev_map_with_thresholds(map, label_colors, priority=None, thresholds=
     """renderer.py:131-172: a label is drawn where its normalised share reaches its threshold; `priority` lists the
     labels from low to high, higher ones overwrite lower ones.  Fewer thresholds than channels raise IndexError, as the
     reference's `thresholds[i]` does."""
-    thresholds = list(thresholds)
-    if len(thresholds) < int(map.shape[-1]):
-        raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), int(map.shape[-1])))
+    colors, pr, th = render_params(label_colors, int(map.shape[-1]), thresholds, priority)     # raises before the map is uploaded
     t, is_np, dt = _prep(map)
     h, w, c = t.shape
-    if priority is not None and len(priority) != c:
-        raise ValueError("Each channel should have a priority.")
-    pr = (C.c_int32 * c)(*[int(p) for p in (priority if priority is not None else range(c))])
-    th = (C.c_double * c)(*[float(x) for x in thresholds[:c]])
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
-    _lib.check(_lib.lib().avl_render_bev_map_thresholds(C.c_void_p(t.data_ptr()), dt, h, w, c, _colors(label_colors, c), pr, th,
+    _lib.check(_lib.lib().avl_render_bev_map_thresholds(C.c_void_p(t.data_ptr()), dt, h, w, c, colors, pr, th,
                                                         C.c_void_p(out.data_ptr()), _stream(t)), "avl_render_bev_map_thresholds")
     return out.cpu().numpy() if is_np else out
 
@@ -125,19 +146,9 @@ def _live_args(t, label_colors, size, filter, thresholds, priority, fill, fill_p
     """the arguments avl_live_map and avl_live_view share, as ctypes values (kept alive by the caller's tuple)"""
     hm, wm, c = t.shape
     h, w = int(size[0]), int(size[1])
-    colors = _colors(label_colors, c)
-    flags = (_lib.AVL_LIVE_FILTER if filter else 0) | (_lib.AVL_LIVE_THRESHOLDS if thresholds is not None else 0) | \
+    colors, pr, th = render_params(label_colors, c, thresholds, priority)
+    flags = (_lib.AVL_LIVE_FILTER if filter else 0) | (_lib.AVL_LIVE_THRESHOLDS if th is not None else 0) | \
             (_lib.AVL_LIVE_FILL if fill else 0)
-    pr = th = None
-    if thresholds is not None:
-        thresholds = list(thresholds)
-        if len(thresholds) < c:
-            raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), c))
-        th = (C.c_double * c)(*[float(x) for x in thresholds[:c]])
-    if priority is not None:
-        if len(priority) != c:
-            raise ValueError("Each channel should have a priority.")
-        pr = (C.c_int32 * c)(*[int(p) for p in priority])
     fp = [int(p) for p in fill_priority] if fill else []
     car_c = col_c = None
     if car is not None:
@@ -145,10 +156,7 @@ def _live_args(t, label_colors, size, filter, thresholds, priority, fill, fill_p
             raise ValueError("car is car_block(...): %d numbers" % _lib.AVL_LIVE_CAR_DOUBLES)
         car_c = (C.c_double * _lib.AVL_LIVE_CAR_DOUBLES)(*[float(v) for v in car])
         col_c = (C.c_uint8 * 3)(*[int(v) for v in car_color])
-    if out is None:
-        out = torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=t.device)
-    elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != t.device or not out.is_contiguous():
-        raise ValueError("out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (h, w, t.device))
+    out = out_picture(out, h, w, t.device)
     s = _stream(t) if stream is None else C.c_void_p(int(stream))
     return h, w, colors, flags, pr, th, (C.c_int32 * max(len(fp), 1))(*fp), len(fp), car_c, col_c, out, s
 

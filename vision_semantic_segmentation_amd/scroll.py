@@ -72,6 +72,14 @@ def check_origin(origin, T):
     return i0, j0
 
 
+def rect_shape(rect, T):
+    """(nh, nw), the tiles per side of the tile rectangle ``rect`` = (ti0, ti1, tj0, tj1), both ends included (0 for an empty side);
+    ValueError unless its first cell is an origin check_origin admits."""
+    ti0, ti1, tj0, tj1 = (int(v) for v in rect)
+    check_origin((ti0 * T, tj0 * T), T)
+    return max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+
+
 def window_boundary(anchor, origin, Hm, Wm, res):
     """[[x_min, x_max], [y_min, y_max]] of the window at ``origin`` = (i0, j0): the module's one statement of the expression."""
     res = float(res)
@@ -168,14 +176,20 @@ def scroll_jobs(plan, old_tile, new_tile, T, Wm, bpc, chunk_tiles, slab_of_leavi
     return jobs
 
 
+def tile_row_bytes(what, T, bpc):
+    """T * bpc, the bytes of a tile row of a table of ``what``; ValueError unless the tile kernels can move such rows"""
+    row = T * bpc
+    if bpc % 4 != 0 or not 4 <= bpc <= 128 or row % 16 != 0:
+        raise ValueError("%s: bytes_per_cell = %d, T = %d (bytes_per_cell a multiple of 4 up to 128, T * bytes_per_cell of 16)" % (what, bpc, T))
+    return row
+
+
 def validate_jobs(jobs, buffers, T, bpc, n_flags=None):
     """ValueError unless every job of the table is safe to launch.  ``buffers``: {key: (device address, bytes)}.  Every source and
     destination tile -- T rows of T * bpc bytes, ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a
     multiple of 16; a pitch is at least a row; no destination tile appears twice and no job reads a buffer range another writes
     (checked per buffer: a buffer is read or written, never both, except distinct slabs of a chunk); a flag is below ``n_flags``."""
-    row = T * bpc
-    if bpc % 4 != 0 or not 4 <= bpc <= 128 or row % 16 != 0:
-        raise ValueError("tile jobs: bytes_per_cell = %d, T = %d (bytes_per_cell a multiple of 4 up to 128, T * bytes_per_cell of 16)" % (bpc, T))
+    row = tile_row_bytes("tile jobs", T, bpc)
     written, read = set(), set()
     for k, j in enumerate(jobs):
         for what, key, off, pitch in (("src", j.src, j.src_off, j.src_pitch), ("dst", j.dst, j.dst_off, j.dst_pitch)):
@@ -237,8 +251,8 @@ def overview_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, s
     something (None: the window holds nothing), the window's first tile being ``origin_tile``; ``stored_tiles`` int [n, 2] and
     ``stored_slabs`` int [n]: the stored tiles that hold something and their slabs.  Index arithmetic on whole arrays: the cost
     follows what was mapped, not the rectangle."""
-    ti0, ti1, tj0, tj1 = (int(v) for v in rect)
-    nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+    ti0, tj0 = int(rect[0]), int(rect[2])
+    nh, nw = rect_shape(rect, T)
     parts = []
     if window_mask is not None:
         wi, wj = np.nonzero(np.asarray(window_mask))
@@ -265,16 +279,10 @@ def validate_sources(table, buffers, T, bpc, nh, nw):
     """ValueError unless every record of the source table is safe to launch.  ``buffers``: [(device address, bytes)], indexed by
     ``buf``.  Every tile -- T rows of T * bpc bytes, ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a
     multiple of 16 and a pitch is at least a row; row and col are inside nh x nw; no (row, col) appears twice."""
-    row = T * bpc
-    if bpc % 4 != 0 or not 4 <= bpc <= 128 or row % 16 != 0:
-        raise ValueError("tile sources: bytes_per_cell = %d, T = %d (bytes_per_cell a multiple of 4 up to 128, T * bytes_per_cell of 16)" % (bpc, T))
-    n = len(table)
-    if n == 0:
+    row = tile_row_bytes("tile sources", T, bpc)
+    if len(table) == 0:
         return
-
-    def refuse(bad, what):
-        k = int(np.flatnonzero(bad)[0])
-        raise ValueError("tile source %d of %d %s: %r" % (k, n, what, table[k]))
+    refuse = _refuser("source", table)
     buf = table["buf"].astype(np.int64)
     bad = (buf < 0) | (buf >= len(buffers))
     if bad.any():
@@ -291,6 +299,19 @@ def validate_sources(table, buffers, T, bpc, nh, nw):
     bad = (off < 0) | (off + (T - 1) * pitch + row > nbytes)
     if bad.any():
         refuse(bad, "leaves its buffer")
+    _validate_places(table, nh, nw, refuse)
+
+
+def _refuser(kind, table):
+    """refuse(bad, what): ValueError that names the first record of ``table`` that the bool array ``bad`` marks"""
+    def refuse(bad, what):
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("tile %s %d of %d %s: %r" % (kind, k, len(table), what, table[k]))
+    return refuse
+
+
+def _validate_places(table, nh, nw, refuse):
+    """every record's (row, col) is inside nh x nw and none appears twice, or refuse(...)"""
     r, c = table["row"].astype(np.int64), table["col"].astype(np.int64)
     bad = (r < 0) | (r >= nh) | (c < 0) | (c >= nw)
     if bad.any():
@@ -299,7 +320,7 @@ def validate_sources(table, buffers, T, bpc, nh, nw):
     order = np.argsort(place, kind="stable")
     twice = np.flatnonzero(np.diff(place[order]) == 0)
     if twice.size:
-        bad = np.zeros(n, dtype=bool)
+        bad = np.zeros(len(table), dtype=bool)
         bad[order[twice[0] + 1]] = True
         refuse(bad, "names a (row, col) that an earlier record names")
 
@@ -353,8 +374,7 @@ def finish_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, sto
     """The record table (FINISH_DTYPE, sorted by row, col) of the tile rectangle ``rect``: overview_sources' records, a NULL record
     (``buf`` -1) for every absent tile of the rectangle with at least one present 8-neighbour, and every record's neighbour indices.
     The arguments are overview_sources'.  Index arithmetic on whole arrays: the cost follows what was mapped, not the rectangle."""
-    ti0, ti1, tj0, tj1 = (int(v) for v in rect)
-    nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
+    nh, nw = rect_shape(rect, T)
     present = overview_sources(rect, T, bpc, Wm, origin_tile, window_mask, stored_tiles, stored_slabs, chunk_tiles)
     r, c = present["row"].astype(np.int64), present["col"].astype(np.int64)
     around = []
@@ -381,26 +401,12 @@ def validate_finish(table, buffers, T, bpc, nh, nw):
     if T < 2:
         raise ValueError("tile records: T = %d cells (at least 2: the filter reflects at the rectangle's edge)" % T)
     n = len(table)
-    has = table["buf"] >= 0
-    validate_sources(table[has], buffers, T, bpc, nh, nw)
+    validate_sources(table[table["buf"] >= 0], buffers, T, bpc, nh, nw)
     if n == 0:
         return
-
-    def refuse(bad, what):
-        k = int(np.flatnonzero(bad)[0])
-        raise ValueError("tile record %d of %d %s: %r" % (k, n, what, table[k]))
-    r, c = table["row"].astype(np.int64), table["col"].astype(np.int64)
-    bad = (r < 0) | (r >= nh) | (c < 0) | (c >= nw)
-    if bad.any():
-        refuse(bad, "lies outside the rectangle of %d x %d tiles" % (nh, nw))
-    place = r * nw + c
-    order = np.argsort(place, kind="stable")
-    twice = np.flatnonzero(np.diff(place[order]) == 0)
-    if twice.size:
-        bad = np.zeros(n, dtype=bool)
-        bad[order[twice[0] + 1]] = True
-        refuse(bad, "names a (row, col) that an earlier record names")
-    bad = (np.asarray(table["nb"]).reshape(n, 9) != finish_neighbours(r, c, nh, nw)).any(axis=1)
+    refuse = _refuser("record", table)
+    _validate_places(table, nh, nw, refuse)                                 # the NULL records too
+    bad = (np.asarray(table["nb"]).reshape(n, 9) != finish_neighbours(table["row"], table["col"], nh, nw)).any(axis=1)
     if bad.any():
         refuse(bad, "has a neighbour index that does not name the record at that offset")
 
@@ -577,6 +583,17 @@ class TileStore(object):
                                         torch.empty(cap, dtype=torch.uint8, device=self.sm.device), torch.cuda.Event()]
         return slot
 
+    def _launch_table(self, st, nbytes, fill, launch):
+        """A table of ``nbytes`` through the ring on the torch stream ``st``: fill(records), the slot's pinned bytes as a NumPy
+        uint8 array, writes it; it is copied to the device on ``st``; launch(address), called with ``st`` current, starts the
+        kernels that read it there; the slot's event is recorded behind them."""
+        host, dev, event = self._ring_slot(nbytes)
+        fill(host.numpy()[:nbytes])
+        with self.torch.cuda.stream(st):
+            dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+            launch(dev.data_ptr())
+            event.record(st)
+
     def _run(self, per_layer, st, n_flags=0):
         """``per_layer``: [(layer, jobs, buffers)], all validated here, uploaded as one table through the ring and launched once per
         layer on the torch stream ``st``; with ``n_flags`` every layer's flags go to flags_dev[l * n_flags ...] and their copy into
@@ -588,12 +605,13 @@ class TileStore(object):
             validate_jobs(jobs, buffers, self.T, L.bpc, n_flags)          # raises before anything is uploaded or launched
         total = sum(len(jobs) for _, jobs, _ in per_layer)
         nbytes = max(total, 1) * JOB_DTYPE.itemsize
-        host, dev, event = self._ring_slot(nbytes)
-        rec = host.numpy()[:nbytes].view(JOB_DTYPE)
-        at, starts = 0, []
-        for L, jobs, buffers in per_layer:
-            starts.append(at)
-            at += encode_jobs(jobs, buffers, rec[at:])
+        starts = []
+
+        def fill(records):
+            rec, at = records.view(JOB_DTYPE), 0
+            for L, jobs, buffers in per_layer:
+                starts.append(at)
+                at += encode_jobs(jobs, buffers, rec[at:])
         n_layers = len(per_layer)
         if n_flags and (self.flags_dev is None or int(self.flags_dev.numel()) < n_layers * n_flags):
             if self.flags_event is not None:
@@ -602,15 +620,16 @@ class TileStore(object):
             cap = max(2 * n_layers * n_flags, 256)
             self.flags_dev = torch.empty(cap, dtype=torch.int32, device=self.sm.device)
             self.flags_host = torch.empty(cap, dtype=torch.int32).pin_memory()
-        with torch.cuda.stream(st):
-            dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+
+        def launch(table):
             for l, (L, jobs, _) in enumerate(per_layer):
                 flags = C.c_void_p(self.flags_dev.data_ptr() + 4 * l * n_flags) if n_flags else None
-                rc = _lib.lib().avl_tile_copy(C.c_void_p(dev.data_ptr() + starts[l] * JOB_DTYPE.itemsize), len(jobs), self.T, L.bpc,
+                rc = _lib.lib().avl_tile_copy(C.c_void_p(table + starts[l] * JOB_DTYPE.itemsize), len(jobs), self.T, L.bpc,
                                               L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
                 _lib.check(rc, "avl_tile_copy")
-            event.record(st)
-            if n_flags:
+        self._launch_table(st, nbytes, fill, launch)
+        if n_flags:
+            with torch.cuda.stream(st):
                 self.flags_host[:n_layers * n_flags].copy_(self.flags_dev[:n_layers * n_flags], non_blocking=True)
                 self.flags_event.record(st)
 
@@ -769,10 +788,9 @@ class TileStore(object):
                 rect = (0, -1, 0, -1)
             else:
                 rect = (min(t[0] for t in tiles), max(t[0] for t in tiles), min(t[1] for t in tiles), max(t[1] for t in tiles))
-        ti0, ti1, tj0, tj1 = (int(v) for v in rect)
-        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
         T = self.T
-        check_origin((ti0 * T, tj0 * T), T)
+        ti0, tj0 = int(rect[0]), int(rect[2])
+        nh, nw = rect_shape(rect, T)
         st = self._stream(stream)
         outs, per_layer = [], []
         tiles = [(ti0 + i, tj0 + j) for i in range(nh) for j in range(nw)]
@@ -815,62 +833,48 @@ class TileStore(object):
         buffers = [self._extent(L.get())] + [(c.data_ptr(), int(c.numel())) for c in L.chunks]
         return rect, table, buffers
 
+    def _site_render_params(self, colors, thresholds, priority):
+        """renderer.render_params for the site calls: no or no thresholds at all mean the arg-max renderer, and a priority without
+        thresholds is ignored"""
+        from . import renderer
+        if thresholds is None or not len(thresholds):
+            thresholds = priority = None
+        return renderer.render_params(self.sm.label_colors if colors is None else colors, self.C, thresholds, priority)
+
     def site_overview(self, cells_per_pixel, rect=None, colors=None, thresholds=None, priority=None, reduced=False, out=None, stream=None,
                       max_side_px=4096):
         import ctypes as C
-        from . import _lib
+        from . import _lib, renderer
         torch = self.torch
         sm = self.sm
         rect, table, buffers = self.overview_table(rect)
-        ti0, ti1, tj0, tj1 = rect
-        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
         T, Cn = self.T, self.C
-        check_origin((ti0 * T, tj0 * T), T)
+        nh, nw = rect_shape(rect, T)
+        origin = (rect[0] * T, rect[2] * T)
         k = int(cells_per_pixel) if cells_per_pixel else overview_cells_per_pixel(T, nh, nw, int(max_side_px))
         if k < 1 or T % k != 0:
             raise ValueError("site_overview: cells_per_pixel = %d does not divide the tile size T = %d" % (k, T))
         P = T // k
-        shape = (nh * P, nw * P, 3)
-        if shape[0] * shape[1] >= 1 << 31:
-            raise ValueError("site_overview: a picture of %d x %d pixels; choose more cells per pixel than %d" % (shape[0], shape[1], k))
+        if nh * P * nw * P >= 1 << 31:
+            raise ValueError("site_overview: a picture of %d x %d pixels; choose more cells per pixel than %d" % (nh * P, nw * P, k))
         st = self._stream(stream)
         cur = self._layers()[0].get()
         with torch.cuda.stream(st):
-            if out is None:
-                out = torch.empty(shape, dtype=torch.uint8, device=cur.device)
-            elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != cur.device or not out.is_contiguous():
-                raise ValueError("site_overview: out must be a contiguous uint8 tensor %r on %s" % (shape, cur.device))
-            red = torch.empty(shape[:2] + (Cn,), dtype=cur.dtype, device=cur.device) if reduced else None
-        result = ((ti0 * T, tj0 * T), out, red) if reduced else ((ti0 * T, tj0 * T), out)
+            out = renderer.out_picture(out, nh * P, nw * P, cur.device)
+            red = torch.empty((nh * P, nw * P, Cn), dtype=cur.dtype, device=cur.device) if reduced else None
+        result = (origin, out, red) if reduced else (origin, out)
         sm.last_site_overview = {"rect": rect, "cells_per_pixel": k, "tiles": len(table)}
         if nh == 0 or nw == 0:
             return result                                                  # an empty site: nothing is launched
-        bpc = self._layers()[0].bpc
-        validate_sources(table, buffers, T, bpc, nh, nw)                   # raises before anything is uploaded or launched
-        colors = np.ascontiguousarray(np.asarray(sm.label_colors if colors is None else colors), dtype=np.uint8)
-        if colors.shape != (Cn, 3):
-            raise ValueError("site_overview: %r colours for %d classes" % (colors.shape, Cn))
-        col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
-        th = pr = None
-        if thresholds is not None and len(thresholds):
-            if len(thresholds) < Cn:
-                raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), Cn))
-            if priority is not None and len(priority) != Cn:
-                raise ValueError("Each channel should have a priority.")
-            th = (C.c_double * Cn)(*[float(x) for x in list(thresholds)[:Cn]])
-            pr = (C.c_int32 * Cn)(*[int(p) for p in (priority if priority is not None else range(Cn))])
-        n = len(table)
-        nbytes = max(n, 1) * SRC_DTYPE.itemsize
-        host, dev, event = self._ring_slot(nbytes)
-        encode_sources(table, buffers, host.numpy()[:nbytes].view(SRC_DTYPE))
+        validate_sources(table, buffers, T, self._layers()[0].bpc, nh, nw)  # raises before anything is uploaded or launched
+        col, pr, th = self._site_render_params(colors, thresholds, priority)
         dt = _lib.AVL_F64 if cur.dtype == torch.float64 else _lib.AVL_F32
-        with torch.cuda.stream(st):
-            if n:
-                dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
-            rc = _lib.lib().avl_site_overview(C.c_void_p(dev.data_ptr()), n, nh, nw, T, Cn, dt, k, col, pr, th, C.c_void_p(out.data_ptr()),
+
+        def launch(tiles):
+            rc = _lib.lib().avl_site_overview(C.c_void_p(tiles), len(table), nh, nw, T, Cn, dt, k, col, pr, th, C.c_void_p(out.data_ptr()),
                                               C.c_void_p(red.data_ptr()) if reduced else None, C.c_void_p(st.cuda_stream))
             _lib.check(rc, "avl_site_overview")
-            event.record(st)
+        self._launch_table(st, max(len(table), 1) * SRC_DTYPE.itemsize, lambda rec: encode_sources(table, buffers, rec.view(SRC_DTYPE)), launch)
         return result
 
     def site_finish(self, rect=None, colors=None, filter=True, thresholds=None, priority=None, truth=None, picture=True, labels=False,
@@ -879,26 +883,21 @@ class TileStore(object):
         counts the tiles with a record; the truth histograms of the rectangle's other tiles (``truth.tile_hist``, exact integers)
         are added on the host into label 0.  The window and the store are only read."""
         import ctypes as C
-        from . import _lib
+        from . import _lib, renderer
         torch = self.torch
-        sm = self.sm
         rect, table, buffers = self.overview_table(rect, finish_sources)
-        ti0, ti1, tj0, tj1 = rect
-        nh, nw = max(ti1 - ti0 + 1, 0), max(tj1 - tj0 + 1, 0)
         T, Cn = self.T, self.C
-        origin = check_origin((ti0 * T, tj0 * T), T)
+        nh, nw = rect_shape(rect, T)
+        origin = (rect[0] * T, rect[2] * T)
         H, W = nh * T, nw * T
         if H * W >= 1 << 31:
             raise ValueError("site_finish: a rectangle of %d x %d cells (below 2^31)" % (H, W))
+        if out is not None and not picture:
+            raise ValueError("site_finish: out must be given with picture=True")
         st = self._stream(stream)
         cur = self._layers()[0].get()
         with torch.cuda.stream(st):
-            if out is not None:
-                if not picture or tuple(out.shape) != (H, W, 3) or out.dtype != torch.uint8 or out.device != cur.device or not out.is_contiguous():
-                    raise ValueError("site_finish: out must be a contiguous uint8 tensor %r on %s, with picture=True" % ((H, W, 3), cur.device))
-                pic = out
-            else:
-                pic = torch.empty((H, W, 3), dtype=torch.uint8, device=cur.device) if picture else None
+            pic = renderer.out_picture(out, H, W, cur.device) if picture else None
             lab = torch.empty((H, W), dtype=torch.uint8, device=cur.device) if labels else None
         n = len(table)
         n_null = int((table["buf"] < 0).sum())
@@ -909,24 +908,12 @@ class TileStore(object):
             if nh == 0 or nw == 0:                                         # an empty site: nothing was mapped, all of the truth is missed
                 counts[:, 0] = truth.total_hist()
             else:
-                counts[:, 0] = truth.rect_hist(T, rect) - truth.tiles_hist(T, table["row"].astype(np.int64) + ti0,
-                                                                           table["col"].astype(np.int64) + tj0)
+                counts[:, 0] = truth.rect_hist(T, rect) - truth.tiles_hist(T, table["row"].astype(np.int64) + rect[0],
+                                                                           table["col"].astype(np.int64) + rect[2])
         if nh == 0 or nw == 0 or (pic is None and lab is None and truth is None):
             return SiteFinish(origin, pic, lab, counts, tiles)             # an empty site, or nothing asked for: nothing is launched
-        bpc = self._layers()[0].bpc
-        validate_finish(table, buffers, T, bpc, nh, nw)                    # raises before anything is uploaded or launched
-        colors = np.ascontiguousarray(np.asarray(sm.label_colors if colors is None else colors), dtype=np.uint8)
-        if colors.shape != (Cn, 3):
-            raise ValueError("site_finish: %r colours for %d classes" % (colors.shape, Cn))
-        col = (C.c_uint8 * colors.size)(*colors.ravel().tolist())
-        th = pr = None
-        if thresholds is not None and len(thresholds):
-            if len(thresholds) < Cn:
-                raise IndexError("%d thresholds for %d channels: every channel needs one" % (len(thresholds), Cn))
-            if priority is not None and len(priority) != Cn:
-                raise ValueError("Each channel should have a priority.")
-            th = (C.c_double * Cn)(*[float(x) for x in list(thresholds)[:Cn]])
-            pr = (C.c_int32 * Cn)(*[int(p) for p in (priority if priority is not None else range(Cn))])
+        validate_finish(table, buffers, T, self._layers()[0].bpc, nh, nw)  # raises before anything is uploaded or launched
+        col, pr, th = self._site_render_params(colors, thresholds, priority)
         gt = mask = cnt = None
         Hg = Wg = r0 = c0 = 0
         if truth is not None:
@@ -935,21 +922,18 @@ class TileStore(object):
             r0, c0 = truth.origin_cell[0] - origin[0], truth.origin_cell[1] - origin[1]
             if max(abs(r0), abs(c0)) >= 1 << 31:
                 raise ValueError("site_finish: the truth raster starts %d, %d cells from the rectangle" % (r0, c0))
-        nbytes = max(n, 1) * FIN_DTYPE.itemsize
-        host, dev, event = self._ring_slot(nbytes)
-        encode_finish(table, buffers, host.numpy()[:nbytes].view(FIN_DTYPE))
+            with torch.cuda.stream(st):
+                cnt = torch.empty(64, dtype=torch.int64, device=cur.device)
         dt = _lib.AVL_F64 if cur.dtype == torch.float64 else _lib.AVL_F32
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.stream(st):
-            if truth is not None:
-                cnt = torch.empty(64, dtype=torch.int64, device=cur.device)
-            if n:
-                dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
-            rc = _lib.lib().avl_site_finish(C.c_void_p(dev.data_ptr()), n, nh, nw, T, Cn, dt, _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th,
+
+        def launch(records):
+            rc = _lib.lib().avl_site_finish(C.c_void_p(records), n, nh, nw, T, Cn, dt, _lib.AVL_LIVE_FILTER if filter else 0, col, pr, th,
                                             p(gt), Hg, Wg, Wg, r0, c0, p(mask), Wg, p(pic), p(lab), p(cnt), C.c_void_p(st.cuda_stream))
             _lib.check(rc, "avl_site_finish")
-            event.record(st)
-            if cnt is not None:
+        self._launch_table(st, max(n, 1) * FIN_DTYPE.itemsize, lambda rec: encode_finish(table, buffers, rec.view(FIN_DTYPE)), launch)
+        if cnt is not None:
+            with torch.cuda.stream(st):
                 counts += cnt.cpu().numpy().reshape(8, 8)                  # waits for the kernel: the counts are a host result
         return SiteFinish(origin, pic, lab, counts, tiles)
 

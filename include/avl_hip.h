@@ -758,6 +758,56 @@ typedef struct avl_tile_job {
 int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags, int n_flags,
                   void* stream);
 
+/* ---- merging sites: tile merge jobs (not in the reference; csrc/seg_sitemerge.hip, scroll.TileStore.merge_site) -------------------
+ * A frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.  Another run's or another
+ * rank's tiles are accumulated into this map's tiles where those live: the window buffer, a slab of the store.  THE RULE:
+ *   1. tile: as rule 1 of avl_tile_job; bytes_per_cell is the DESTINATION's.  In AVL_MERGE_ADD_F32_TO_F64 the source tile is float32
+ *      and its rows hold half the destination row's bytes.
+ *   2. merge: result = acc (+) src, element by element, written to the destination.  acc is the destination's old content, read and
+ *      written in place by the same lane.  With fresh != 0, acc is the layer's fill word in every 32-bit word and the destination is
+ *      NOT read: whatever bytes it holds do not reach the result.  A fresh tile is no byte copy -- +0.0 + -0.0 = +0.0 -- so the
+ *      result never depends on whether the destination tile happened to exist before.
+ *   3. (+) is the call's `op`; the adds are ONE IEEE-754 (round to nearest even, denormals kept) or two's-complement addition per
+ *      element, no FMA:
+ *        AVL_MERGE_ADD_F64          float64 + float64
+ *        AVL_MERGE_ADD_F32          float32 + float32
+ *        AVL_MERGE_ADD_F32_TO_F64   acc + (double)src, float32 source, float64 destination: the exchange form, half the payload
+ *        AVL_MERGE_ADD_I64          int64 + int64, wraps          (the elevation layer's sum)
+ *        AVL_MERGE_ADD_I32          int32 + int32, WRAPS: two counts whose sum passes 2^31 - 1 come out negative (its count)
+ *        AVL_MERGE_MIN_I32          signed minimum                (its minimum, fill 0x7fffffff)
+ *        AVL_MERGE_MAX_I32          signed maximum                (its maximum, fill 0x80000000)
+ *      A NaN operand gives a NaN; which payload is not part of the rule.
+ *   4. flag: with flag >= 0, flags[flag] = 1 iff some 32-bit word of the RESULT tile differs from `fill`, else 0; bit patterns are
+ *      compared.  The mechanism is avl_tile_copy's: the call zeroes flags[0 .. n_flags), stream-ordered, before the kernel, which
+ *      sets a flag with an integer atomic OR.  A flag index >= n_flags is ignored.
+ *   5. no two jobs of a call name the same destination tile and no job's source is any job's destination: the kernel orders nothing
+ *      between jobs.  (A job reading and writing its OWN destination in place is the merge itself.)
+ * The caller owns the table's validity as for avl_tile_job: every src, dst and pitch 16-byte aligned, no NULL src or dst, every range
+ * inside the buffer it belongs to.  scroll.validate_merge checks that on the host before the upload. */
+#define AVL_MERGE_ADD_F64 0
+#define AVL_MERGE_ADD_F32 1
+#define AVL_MERGE_ADD_F32_TO_F64 2
+#define AVL_MERGE_ADD_I64 3
+#define AVL_MERGE_ADD_I32 4
+#define AVL_MERGE_MIN_I32 5
+#define AVL_MERGE_MAX_I32 6
+typedef struct avl_merge_job {
+    const void* src;      /* first byte of the source tile (never NULL)                                          */
+    int64_t src_pitch;    /* bytes between tile rows of the source                                               */
+    void* dst;            /* first byte of the destination tile: accumulator and result                          */
+    int64_t dst_pitch;    /* bytes between tile rows of the destination                                          */
+    int32_t flag;         /* >= 0: the flag that receives rule 4; < 0: none                                      */
+    int32_t fresh;        /* != 0: the accumulator is the fill word and the destination is not read (rule 2)     */
+} avl_merge_job;
+
+/* Executes jobs_dev[0 .. n_jobs), a DEVICE array, by the rule above, in one launch on `stream`: 16 bytes per lane and memory
+ * instruction, a tile split over workgroups by rows as in avl_tile_copy.  One call serves one layer.  Nothing is allocated, copied
+ * from the host or waited for.  n_jobs == 0 only zeroes the flags.  AVL_E_ARG, before any GPU work: avl_tile_copy's list, an op
+ * outside the seven above, bytes_per_cell no multiple of 8 for the 64-bit ops (ADD_F64, ADD_F32_TO_F64, ADD_I64), a destination row
+ * -- or, for ADD_F32_TO_F64, the source row of half its bytes -- that is no multiple of 16 bytes. */
+int avl_tile_merge(const avl_merge_job* jobs_dev, int n_jobs, int op, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags,
+                   int n_flags, void* stream);
+
 /* ---- the site overview: a reduced grid and its picture straight from the tiles (not in the reference; csrc/seg_overview.hip) ---------
  * A scrolled map's site lives in tiles: in the window buffer and in the store's slabs.  The overview reads them where they are and
  * writes a grid reduced by k x k cells per pixel and its picture; nothing of the site is assembled at full resolution.  THE RULE:

@@ -1,0 +1,214 @@
+"""NumPy restatement of merging sites, shared by test_site_merge_cpu.py and test_gpu_site_merge.py.
+
+* an executor of merge-job tables on NumPy byte buffers (struct avl_merge_job's rule, written out again here and not imported from
+  scroll.py): result = acc (+) src per element, acc the destination's old content or -- for a fresh job -- the fill word, the seven
+  ops, the flag of the RESULT;
+* the sum of sites keyed by global tile: a left fold over {tile: array} dictionaries, a missing tile standing for the fill state;
+* the second vehicle of the end-to-end tests, a drive that shares window, resolution and tile size with _scroll_reference.main_drive.
+"""
+import math
+
+import numpy as np
+
+import _scroll_reference as ref
+
+OPS = {"ADD_F64": 0, "ADD_F32": 1, "ADD_F32_TO_F64": 2, "ADD_I64": 3, "ADD_I32": 4, "MIN_I32": 5, "MAX_I32": 6}
+ELEMENT = {"ADD_F64": np.float64, "ADD_F32": np.float32, "ADD_F32_TO_F64": np.float64, "ADD_I64": np.int64, "ADD_I32": np.int32,
+           "MIN_I32": np.int32, "MAX_I32": np.int32}
+LAYER_OPS = {"elev_sum": ("ADD_I64", 0), "elev_cnt": ("ADD_I32", 0), "elev_min": ("MIN_I32", 0x7FFFFFFF), "elev_max": ("MAX_I32", 0x80000000)}
+
+
+def combine(op, acc, src):
+    """acc (+) src on arrays of the op's element type (src float32 for ADD_F32_TO_F64): one add per element, integer adds wrap"""
+    with np.errstate(all="ignore"):
+        if op in ("ADD_F64", "ADD_F32"):
+            return acc + src
+        if op == "ADD_F32_TO_F64":
+            return acc + src.astype(np.float64)
+        if op in ("ADD_I64", "ADD_I32"):
+            u = np.uint64 if op == "ADD_I64" else np.uint32
+            return (acc.view(u) + src.view(u)).view(acc.dtype)                       # unsigned: two's complement, it wraps
+        return np.minimum(acc, src) if op == "MIN_I32" else np.maximum(acc, src)
+
+
+def execute_merge(jobs, buffers, T, bpc, op, fill, n_flags):
+    """``jobs``: scroll.MergeJob records (or any object with their fields); ``buffers``: {key: np.uint8 array}, written in place.
+    ``bpc`` is the destination's; the source of ADD_F32_TO_F64 has rows of half the bytes.  -> int32 [n_flags]"""
+    flags = np.zeros(n_flags, dtype=np.int32)
+    row = T * bpc
+    src_row = row // 2 if op == "ADD_F32_TO_F64" else row
+    el = ELEMENT[op]
+    src_el = np.float32 if op == "ADD_F32_TO_F64" else el
+    fill_row = np.full(row // 4, fill, dtype=np.uint32).view(np.uint8)
+    for j in jobs:
+        dst = buffers[j.dst]
+        some = False
+        for r in range(T):
+            d0 = j.dst_off + r * j.dst_pitch
+            s0 = j.src_off + r * j.src_pitch
+            acc = (fill_row if j.fresh else dst[d0:d0 + row]).copy().view(el)
+            src = buffers[j.src][s0:s0 + src_row].copy().view(src_el)
+            out = np.ascontiguousarray(combine(op, acc, src)).view(np.uint8)
+            some = some or bool((out.view(np.uint32) != np.uint32(fill)).any())
+            dst[d0:d0 + row] = out
+        if j.flag >= 0:
+            flags[j.flag] |= int(some)
+    return flags
+
+
+# ------------------------------------------------------------------------------------------------ a merge as a job table
+def _values(rng, op, n, source):
+    """n random operands of the op's type with the cells that matter sprinkled in: -0.0, +-inf (inf + -inf among them), NaN,
+    float32 denormals, integers next to the ends of their range"""
+    el = (np.float32 if op == "ADD_F32_TO_F64" else ELEMENT[op]) if source else ELEMENT[op]
+    if np.issubdtype(el, np.floating):
+        v = rng.normal(size=n).astype(el) * el(1000.0)
+        special = [-0.0, 0.0, np.inf, -np.inf, np.nan, 1.0, -1.0]
+        if el == np.float32:
+            special += [1.0e-40, -3.0e-41, 1.4e-45, 1.1754942e-38]                    # denormals; their sums are denormal or just normal
+        else:
+            special += [5.0e-324, -2.0e-310, 1.0e-40]
+        at = rng.random(n) < 0.3
+        v[at] = rng.choice(np.array(special, dtype=el), size=int(at.sum()))
+        return v
+    info = np.iinfo(el)
+    v = rng.integers(info.min, info.max, size=n, dtype=el, endpoint=True)
+    at = rng.random(n) < 0.3
+    v[at] = rng.choice(np.array([info.max, info.min, info.max - 1, info.min + 1, 0, 1, -1], dtype=el), size=int(at.sum()))
+    return v
+
+
+class MergeCase(object):
+    """A window of 2 x 3 tiles, a store of two chunks and a staged "file" of eleven tiles, and the merge table that sums the file's
+    tiles into four window tiles (in place), four stored slabs (in place) and three new slabs (fresh, over 0xAB garbage).  Three
+    jobs have hand-placed operands: ``negated`` (a stored tile's exact negation -- for min / max: fill into fill), ``last`` (the
+    only non-fill word of the result is the tile's last) and ``minus_zero`` (a fresh job whose source is all -0.0, or all fill for
+    the integer ops).  Every buffer has a fake 16-byte-aligned device address for the validator."""
+
+    HT, WT, CHUNK = 2, 3, 5
+
+    def __init__(self, op, T, bpc, fill, seed=0):
+        from vision_semantic_segmentation_amd import scroll as s
+        rng = np.random.default_rng(seed + 31 * OPS[op] + 7 * T + bpc)
+        self.op, self.T, self.bpc, self.fill = op, T, bpc, fill
+        self.src_bpc = bpc // 2 if op == "ADD_F32_TO_F64" else bpc
+        el, src_el = ELEMENT[op], (np.float32 if op == "ADD_F32_TO_F64" else ELEMENT[op])
+        per_tile = T * T * bpc // el().itemsize
+        self.Hm, self.Wm = self.HT * T, self.WT * T
+        origin = (3, -2)
+        window_tiles = [(3, -2), (3, 0), (4, -1), (4, 0)]
+        fill_tile = np.full(per_tile * el().itemsize // 4, fill, dtype=np.uint32).view(el)
+        src_fill = np.full(per_tile * src_el().itemsize // 4, fill, dtype=np.uint32).view(src_el)
+        stage = [_values(rng, op, per_tile, True) for _ in range(11)]
+        slab_tiles = [_values(rng, op, per_tile, False) for _ in range(4)]
+        self.negated, self.last, self.minus_zero = 4, 5, 8
+        if np.issubdtype(el, np.floating):
+            keep = np.isfinite(slab_tiles[0])
+            slab_tiles[0] = np.where(keep, slab_tiles[0], el(2.5))
+            if op == "ADD_F32_TO_F64":
+                slab_tiles[0] = slab_tiles[0].astype(np.float32).astype(np.float64)       # its negation exists in float32
+            stage[4] = (-slab_tiles[0]).astype(src_el)
+            stage[8] = np.full(per_tile, -0.0, dtype=src_el)
+            one = src_el(1.0)
+        else:
+            if op in ("MIN_I32", "MAX_I32"):
+                slab_tiles[0], stage[4] = fill_tile.copy(), src_fill.copy()
+            else:
+                stage[4] = (-slab_tiles[0].astype(np.int64)).astype(el) if el == np.int32 else (np.uint64(0) - slab_tiles[0].view(np.uint64)).view(el)
+            stage[8] = src_fill.copy()
+            one = src_el(1 << 40) if el == np.int64 else src_el(5)
+        slab_tiles[1] = fill_tile.copy()
+        stage[5] = src_fill.copy() if not np.issubdtype(el, np.floating) else np.zeros(per_tile, dtype=src_el)
+        stage[5][-1] = one
+        window = _values(rng, op, self.Hm * self.Wm * bpc // el().itemsize, False)
+        slab = T * T * bpc
+        chunks = [np.full(self.CHUNK * slab, 0xAB, dtype=np.uint8) for _ in range(2)]
+        stored = [0, 2, 3, 6]                                      # slabs that hold a tile; 1, 4, 5 are new; 7 .. 9 stay garbage
+        for k, sl in enumerate(stored):
+            chunks[sl // self.CHUNK][(sl % self.CHUNK) * slab:(sl % self.CHUNK + 1) * slab] = slab_tiles[k].view(np.uint8)
+        self.bufs = {"stage": np.concatenate([v.view(np.uint8) for v in stage]), "window": window.view(np.uint8).copy(),
+                     ("chunk", 0): chunks[0], ("chunk", 1): chunks[1]}
+        entries = [(t, k, "window", None, -1) for k, t in enumerate(window_tiles)]
+        entries += [((10 + k, 0), 4 + k, "store", sl, k) for k, sl in enumerate(stored)]
+        entries += [((20 + k, 0), 8 + k, "fresh", sl, 4 + k) for k, sl in enumerate([1, 4, 5])]
+        self.n_flags = 7
+        self.jobs = s.merge_jobs(entries, T, self.Wm, bpc, self.CHUNK, origin, self.src_bpc)
+        self.extents = {key: (4096 * (k + 1) * 64, int(b.size)) for k, (key, b) in enumerate(self.bufs.items())}
+        self.element = el
+
+    def want(self):
+        """-> ({key: bytes after the merge}, flags) by the executor, on copies"""
+        bufs = {k: v.copy() for k, v in self.bufs.items()}
+        flags = execute_merge(self.jobs, bufs, self.T, self.bpc, self.op, self.fill, self.n_flags)
+        return bufs, flags
+
+
+def same_bits_or_both_nan(got, want, element):
+    """two byte buffers of ``element``s: NaN cells are NaN in both (whatever the payload), every other cell is equal bit for bit"""
+    g, w = got.view(element), want.view(element)
+    if not np.issubdtype(element, np.floating):
+        return bool(np.array_equal(got, want))
+    nan = np.isnan(w)
+    u = np.uint64 if element == np.float64 else np.uint32
+    return bool(np.array_equal(np.isnan(g), nan) and np.array_equal(g.view(u)[~nan], w.view(u)[~nan]))
+
+
+CASES = [("ADD_F64", 40, 0), ("ADD_F32", 20, 0), ("ADD_F32_TO_F64", 40, 0), ("ADD_F32_TO_F64", 8, 0), ("ADD_I64", 8, 0), ("ADD_I32", 4, 0), ("MIN_I32", 4, 0x7FFFFFFF),
+         ("MAX_I32", 4, 0x80000000)]
+"""(op, bytes per cell, fill) of the kernel tests: the map at C = 5 in both types and the exchange form, the elevation layer's arrays"""
+
+
+# ------------------------------------------------------------------------------------------------ the sum of sites, keyed by tile
+def tiles_of(site):
+    """{tile: copy of its array} of a BigSite's non-empty tiles"""
+    return {t: site.tile(t).copy() for t in site.nonempty_tiles()}
+
+
+def nonempty(tiles, fill=0):
+    """the tiles of a {tile: array} dictionary that hold something, by bit pattern"""
+    return {t: v for t, v in tiles.items() if (np.ascontiguousarray(v).view(np.uint32) != np.uint32(fill)).any()}
+
+
+def sum_sites(own, others, op="ADD_F64", fill=0):
+    """((own (+) others[0]) (+) others[1]) ...: a tile only ``own`` has stays as it is, a tile ``own`` lacks starts from the fill
+    word.  -> {tile: array}, empty results included (nonempty() drops them)"""
+    out = {t: v.copy() for t, v in own.items()}
+    for other in others:
+        for t, v in other.items():
+            if t in out:
+                acc = out[t]
+            else:
+                acc = np.full(v.size * ELEMENT[op]().itemsize // 4, fill, dtype=np.uint32).view(ELEMENT[op]).reshape(v.shape)
+            out[t] = combine(op, acc, v)
+    return out
+
+
+def big_site(tiles, T, tail, dtype, fill=0, cover=None):
+    """a BigSite over the bounding rectangle of ``tiles`` = {tile: array} (and of the tile rectangle ``cover``), the other tiles in
+    the fill state"""
+    ti, tj = [t[0] for t in tiles], [t[1] for t in tiles]
+    if cover is not None:
+        ti, tj = ti + list(cover[:2]), tj + list(cover[2:])
+    site = ref.BigSite((min(ti), max(ti), min(tj), max(tj)), T, tail, dtype)
+    site.big.reshape(-1).view(np.uint32)[...] = np.uint32(fill)
+    for t, v in tiles.items():
+        site.tile(t)[...] = v
+    return site
+
+
+# ------------------------------------------------------------------------------------------------ the second vehicle
+# it starts where the first vehicle turned (tiles that the first one's scrolls stored), comes back past the anchor (tiles in the first
+# one's last window) and leaves to a part of the site the first one never saw
+ROUTE_B = [(12.0, 7.0, 0.5), (15.0, 9.0, 1.3), (8.5, 4.0, math.pi), (1.0, 1.0, math.pi), (-3.5, -2.0, 2.0), (-24.0, 18.0, 0.7),
+           (-26.0, 20.5, 0.7)]
+
+
+def second_drive(seed=5):
+    return ref.Drive(ROUTE_B, res=0.5, Hm=48, Wm=32, tile_m=4.0, range_max=12.0, seed=seed)
+
+
+def window_tiles_at(drive, k=-1):
+    """the tiles of the window after frame k of a drive"""
+    (i0, j0), _ = drive.origins[k]
+    a, b = i0 // drive.T, j0 // drive.T
+    return {(a + i, b + j) for i in range(drive.Ht) for j in range(drive.Wt)}

@@ -1,0 +1,341 @@
+"""Merging sites without a GPU: the NumPy executor of merge tables on hand-made operands, scroll.validate_merge's refusals, merge_site's
+refusals on a CPU-device SemanticMapping, avl_tile_merge's argument errors through the real library, distributed.gather_sites under
+two-rank gloo, and the conditions the two-vehicle drive must meet so that the GPU test cannot pass on sites that never overlap."""
+import ctypes as C
+import collections
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import _scroll_reference as ref
+import _site_merge_reference as mref
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+J = collections.namedtuple("J", "src src_off src_pitch dst dst_off dst_pitch flag fresh")
+
+
+def scroll():
+    from vision_semantic_segmentation_amd import scroll as s
+    return s
+
+
+# ------------------------------------------------------------------------------------------------ the executor
+def _one_tile(op, acc, src, fill, fresh=0):
+    """one job on one T = 4 tile: acc and src are arrays of 16 cells' elements -> (result, flag)"""
+    bpc = acc.size * acc.itemsize // 16
+    bufs = {"s": np.ascontiguousarray(src).view(np.uint8).copy(), "d": np.ascontiguousarray(acc).view(np.uint8).copy()}
+    src_row = 4 * bpc // (2 if op == "ADD_F32_TO_F64" else 1)
+    flags = mref.execute_merge([J("s", 0, src_row, "d", 0, 4 * bpc, 0, fresh)], bufs, 4, bpc, op, fill, 1)
+    return bufs["d"].view(acc.dtype), int(flags[0])
+
+
+def test_executor_adds_and_widens_one_add_per_element():
+    a = np.arange(16, dtype=np.float64) * 0.1
+    b = np.arange(16, dtype=np.float64)[::-1] * 0.3
+    got, flag = _one_tile("ADD_F64", a, b, 0)
+    assert np.array_equal(got, a + b) and flag == 1
+    a32, b32 = a.astype(np.float32), b.astype(np.float32)
+    got, _ = _one_tile("ADD_F32", a32, b32, 0)
+    assert got.dtype == np.float32 and np.array_equal(got, a32 + b32)
+    got, _ = _one_tile("ADD_F32_TO_F64", a, b32, 0)
+    assert np.array_equal(got, a + b32.astype(np.float64)) and not np.array_equal(got, a + b)      # the source's float32 rounding is kept
+    tiny = np.full(16, 1.0e-40, dtype=np.float32)
+    got, flag = _one_tile("ADD_F32", tiny, tiny, 0)
+    assert got[0] == np.float32(1.0e-40) + np.float32(1.0e-40) and 0 < got[0] < np.finfo(np.float32).tiny and flag == 1     # denormals are kept
+
+
+def test_executor_fresh_ignores_the_destination_and_is_no_byte_copy():
+    garbage = np.frombuffer(bytes([0xAB]) * 128, dtype=np.float64).copy()
+    src = np.full(16, -0.0)
+    got, flag = _one_tile("ADD_F64", garbage, src, 0, fresh=1)
+    assert not np.signbit(got).any() and (got == 0).all() and flag == 0                 # +0.0 + -0.0 = +0.0: empty
+    got, flag = _one_tile("ADD_F64", np.full(16, -0.0), np.zeros(16), 0, fresh=0)
+    assert not np.signbit(got).any() and flag == 0
+    got, flag = _one_tile("ADD_F64", np.full(16, -0.0), np.full(16, -0.0), 0)
+    assert np.signbit(got).all() and flag == 1                                          # a -0.0 is something, by bit pattern
+    src = np.arange(16, dtype=np.float64)
+    got, flag = _one_tile("ADD_F64", garbage, src, 0, fresh=1)
+    assert np.array_equal(got, src) and flag == 1
+    a = np.arange(16, dtype=np.float64) - 7.5
+    got, flag = _one_tile("ADD_F64", a, -a, 0)
+    assert (got == 0).all() and not np.signbit(got).any() and flag == 0                 # the exact negation: the tile is empty again
+    last = np.zeros(16)
+    last[-1] = 1.0                                                                      # 0x3ff00000 00000000: only the tile's last word
+    got, flag = _one_tile("ADD_F64", np.zeros(16), last, 0)
+    assert flag == 1 and (got.view(np.uint32)[:-1] == 0).all()
+
+
+def test_executor_infinities_and_nan():
+    inf = np.inf
+    a = np.array([inf, inf, -inf, 1.0, np.nan, 0.0] + [0.0] * 10)
+    b = np.array([inf, -inf, -inf, inf, 1.0, np.nan] + [0.0] * 10)
+    got, flag = _one_tile("ADD_F64", a, b, 0)
+    assert got[0] == inf and np.isnan(got[1]) and got[2] == -inf and got[3] == inf and np.isnan(got[4]) and np.isnan(got[5]) and flag == 1
+    with np.errstate(invalid="ignore"):
+        assert mref.same_bits_or_both_nan(got.view(np.uint8), (a + b).view(np.uint8), np.float64)
+    other = got.copy()
+    other[1] = np.float64(1.0)
+    assert not mref.same_bits_or_both_nan(other.view(np.uint8), got.view(np.uint8), np.float64)
+
+
+def test_executor_integers_wrap_and_min_max_meet_their_fills():
+    big = np.iinfo(np.int32)
+    a = np.array([big.max, big.min, 5, 0] * 4, dtype=np.int32)
+    b = np.array([1, -1, -5, 0] * 4, dtype=np.int32)
+    got, flag = _one_tile("ADD_I32", a, b, 0)
+    assert got[:4].tolist() == [big.min, big.max, 0, 0] and flag == 1                    # the count wraps: documented
+    a64 = np.array([np.iinfo(np.int64).max, -3] * 8, dtype=np.int64)
+    got, _ = _one_tile("ADD_I64", a64, np.array([1, 3] * 8, dtype=np.int64), 0)
+    assert got[:2].tolist() == [np.iinfo(np.int64).min, 0]
+    empty_min, empty_max = np.full(16, big.max, dtype=np.int32), np.full(16, big.min, dtype=np.int32)
+    v = np.array([7, -7, big.max, big.min] * 4, dtype=np.int32)
+    got, flag = _one_tile("MIN_I32", empty_min, v, 0x7FFFFFFF)
+    assert np.array_equal(got, v) and flag == 1
+    got, flag = _one_tile("MAX_I32", empty_max, v, 0x80000000)
+    assert np.array_equal(got, v) and flag == 1
+    assert _one_tile("MIN_I32", empty_min, empty_min, 0x7FFFFFFF)[1] == 0 and _one_tile("MAX_I32", empty_max, empty_max, 0x80000000)[1] == 0
+    got, _ = _one_tile("MIN_I32", np.array([3] * 16, dtype=np.int32), v, 0x7FFFFFFF)
+    assert got[:4].tolist() == [3, -7, 3, big.min]
+    got, _ = _one_tile("MAX_I32", np.array([3] * 16, dtype=np.int32), v, 0x80000000)
+    assert got[:4].tolist() == [7, 3, big.max, 3]
+    got, flag = _one_tile("MAX_I32", np.frombuffer(bytes([0xAB]) * 64, dtype=np.int32).copy(), v, 0x80000000, fresh=1)
+    assert np.array_equal(got, v)                                                        # 0xabababab is negative: a leak would not show in a max ...
+    got, flag = _one_tile("MIN_I32", np.frombuffer(bytes([0xAB]) * 64, dtype=np.int32).copy(), v, 0x7FFFFFFF, fresh=1)
+    assert np.array_equal(got, v)                                                        # ... but it would in a min
+
+
+@pytest.mark.parametrize("op,bpc,fill", mref.CASES, ids=["%s_%d" % (c[0], c[1]) for c in mref.CASES])
+def test_merge_case_tables_do_what_the_gpu_test_assumes(op, bpc, fill):
+    s = scroll()
+    case = mref.MergeCase(op, 4, bpc, fill)
+    s.validate_merge(case.jobs, case.extents, case.T, bpc, case.src_bpc, case.n_flags)
+    assert len(case.jobs) == 11 and sum(j.fresh for j in case.jobs) == 3 and sum(j.dst == "window" for j in case.jobs) == 4
+    bufs, flags = case.want()
+    assert flags.tolist() == [0, 1, 1, 1, 0, 1, 1]                 # the negated tile and the -0.0 (fill) tile come out empty
+    slab = case.T * case.T * bpc
+    words = bufs[("chunk", 0)][2 * slab:3 * slab].view(np.uint32)  # slab 2: the job whose only non-fill result word is its last
+    assert (words[:-1] == fill).all() and words[-1] != fill
+    assert np.array_equal(bufs["stage"], case.bufs["stage"])
+    assert (bufs[("chunk", 1)][2 * slab:] == 0xAB).all()           # slabs 7 .. 9: no job names them
+    other = mref.MergeCase(op, 4, bpc, fill)                        # the new slabs hold other garbage: the result is the same
+    for sl in (1, 4):
+        other.bufs[("chunk", 0)][sl * slab:(sl + 1) * slab] = 0x55
+    assert all(np.array_equal(v, bufs[k]) for k, v in other.want()[0].items())
+    changed = sum(int((bufs[k] != case.bufs[k]).any()) for k in bufs)
+    assert changed == 3                                             # the window and both chunks
+
+
+# ------------------------------------------------------------------------------------------------ the validator
+def test_validate_merge_refuses_each_class_of_bad_table_and_names_the_job():
+    s = scroll()
+    case = mref.MergeCase("ADD_F64", 4, 40, 0)
+    jobs, ext, n = case.jobs, case.extents, case.n_flags
+    s.validate_merge(jobs, ext, 4, 40, None, n)
+
+    def refused(k, match, src_bpc=None, **kw):
+        bad = list(jobs)
+        bad[k] = jobs[k]._replace(**kw)
+        with pytest.raises(ValueError, match=match):
+            s.validate_merge(bad, ext, 4, 40, src_bpc, n)
+    row = case.Wm * 40
+    refused(2, "merge job 2: dst bytes .* leave buffer 'window'", dst_off=(case.Hm - 4 + 1) * row)         # out of range
+    refused(9, "merge job 9: src bytes .* leave buffer 'stage'", src_off=ext["stage"][1] - 4 * 4 * 40 + 16)
+    refused(6, "merge job 6: dst bytes .* leave buffer", dst_off=-160)
+    refused(1, "merge job 1: dst address .* not 16-byte aligned", dst_off=jobs[1].dst_off + 8)            # misaligned
+    refused(3, "merge job 3: src pitch", src_pitch=168)
+    refused(3, "merge job 3: dst pitch", dst_pitch=144)
+    refused(5, "merge job 5: destination tile .* appears twice \\(job 4\\)", dst=jobs[4].dst, dst_off=jobs[4].dst_off)
+    refused(1, "merge job 1: destination tile 'window' .* appears twice \\(job 0\\)", dst_off=jobs[0].dst_off)
+    refused(7, "merge job 7: its source .* is the destination of job 4", src=jobs[4].dst, src_off=jobs[4].dst_off, src_pitch=160)
+    refused(0, "merge job 0: its source buffer 'window' is written", src="window", src_off=jobs[0].dst_off + 160, src_pitch=row)
+    refused(4, "merge job 4: flag %d of %d" % (n, n), flag=n)
+    refused(4, "merge job 4 has no source", src=None)
+    refused(4, "unknown buffer", dst=("chunk", 9))
+    # in-place read and write of its own destination is the merge: validate_jobs forbids what this allows
+    assert all(j.src != j.dst for j in jobs)
+    # the float32 source of the exchange form: rows of half the bytes, so a source that fits as float32 overruns as float64
+    half = mref.MergeCase("ADD_F32_TO_F64", 4, 40, 0)
+    s.validate_merge(half.jobs, half.extents, 4, 40, 20, n)
+    with pytest.raises(ValueError, match="merge job 0: src pitch 80 is misaligned or shorter than a tile row of 160"):
+        s.validate_merge(half.jobs, half.extents, 4, 40, None, n)          # read as full rows, the half rows are too close
+    last = max(range(len(half.jobs)), key=lambda k: half.jobs[k].src_off)
+    bad = list(half.jobs)
+    bad[last] = half.jobs[last]._replace(src_off=half.jobs[last].src_off + 16)
+    with pytest.raises(ValueError, match="merge job %d: src bytes .* leave buffer 'stage'" % last):
+        s.validate_merge(bad, half.extents, 4, 40, 20, n)                  # 16 bytes past the end of the half-row tiles
+    with pytest.raises(ValueError, match="source of 12 bytes"):
+        s.validate_merge(half.jobs, half.extents, 4, 40, 12, n)
+    with pytest.raises(ValueError, match="bytes_per_cell"):
+        s.validate_merge(jobs, ext, 4, 6, None, n)
+    rec = np.zeros(len(jobs), dtype=s.MERGE_DTYPE)
+    assert s.encode_merge(jobs, ext, rec) == len(jobs) and rec["fresh"].tolist() == [j.fresh for j in jobs]
+    assert rec["dst"][4] == ext[jobs[4].dst][0] + jobs[4].dst_off and rec["src"][4] == ext["stage"][0] + jobs[4].src_off
+
+
+# ------------------------------------------------------------------------------------------------ merge_site's refusals
+def _site(T=8, C_=5, dtype="f64", anchor=(0.0, 0.0), res=0.5, layers=None, coords=((0, 0), (1, -2))):
+    s = scroll()
+    if layers is None:
+        layers = {"map": (np.array(coords), np.ones((len(coords), T, T, C_), dtype=np.float64 if dtype == "f64" else np.float32))}
+    return s.pack_site(anchor, res, T, C_, dtype, layers)
+
+
+def test_merge_site_refuses_before_any_device_work():
+    from test_scroll_cpu import _cpu_mapping
+    sm = _cpu_mapping([[0.0, 24.0], [0.0, 16.0]], 0.5, 4.0)
+    for kw, match in [({"T": 4}, "T = 4, this map 8"), ({"res": 0.25}, "resolution = 0.25, this map 0.5"), ({"C_": 4}, "C = 4, this map 5"),
+                      ({"dtype": "f32"}, "dtype = 'f32', this map 'f64'"), ({"anchor": (4.0, 0.0)}, "anchor = \\(4.0, 0.0\\), this map \\(0.0, 0.0\\)")]:
+        with pytest.raises(ValueError, match="site file has " + match):
+            sm.merge_site(_site(**kw))
+    T = 8
+    elev = {"map": (np.zeros((0, 2), dtype=np.int64), np.zeros((0, T, T, 5))), "elev_cnt": (np.zeros((0, 2), dtype=np.int64), np.zeros((0, T, T), dtype=np.int32))}
+    with pytest.raises(ValueError, match="holds the layers \\['elev_cnt', 'map'\\], this map \\['map'\\]"):
+        sm.merge_site(_site(layers=elev))
+    with pytest.raises(ValueError, match="names tile \\(1, -2\\) of layer 'map' twice, at 1 and 3"):
+        sm.merge_site(_site(coords=((0, 0), (1, -2), (5, 5), (1, -2))))
+    with pytest.raises(ValueError, match="2\\^30"):
+        sm.merge_site(_site(coords=((0, 0), (1 << 27, 0))))
+    with pytest.raises(ValueError, match="tiles \\(2, 8, 8, 5\\) float32 in layer 'map', this map tiles \\(8, 8, 5\\) float64"):
+        sm.merge_site(_site(layers={"map": (np.array([[0, 0], [1, 1]]), np.ones((2, T, T, 5), dtype=np.float32))}))
+    with pytest.raises(ValueError, match="holds \\(3, 2\\) coordinates and tiles of shape \\(2,"):
+        sm.merge_site(_site(layers={"map": (np.array([[0, 0], [1, 1], [2, 2]]), np.ones((2, T, T, 5)))}))
+    assert sm._grid is None and sm._scroll.layers is None and sm._scroll.n_slabs == 0       # nothing was allocated
+    off = _cpu_mapping([[0.0, 22.0], [0.0, 16.0]], 0.5, 3.0, enabled=False)
+    with pytest.raises(RuntimeError, match="MAPPING.SCROLL.ENABLED is False"):
+        off.merge_site(_site())
+    with pytest.raises(RuntimeError, match="MAPPING.SCROLL.ENABLED is False"):
+        off.global_site()
+    with pytest.raises(RuntimeError, match="multi-GPU site map is out of scope"):
+        sm.global_map()                                                                      # as before
+
+
+# ------------------------------------------------------------------------------------------------ the ABI
+def test_tile_merge_argument_errors_do_not_need_a_gpu():
+    from vision_semantic_segmentation_amd import _lib
+    s = scroll()
+    L = _lib.lib()
+    assert s.MERGE_DTYPE.itemsize == 40 and s.MERGE_DTYPE.fields["fresh"][1] == 36
+    assert [_lib.AVL_MERGE_ADD_F64, _lib.AVL_MERGE_ADD_F32, _lib.AVL_MERGE_ADD_F32_TO_F64, _lib.AVL_MERGE_ADD_I64, _lib.AVL_MERGE_ADD_I32,
+            _lib.AVL_MERGE_MIN_I32, _lib.AVL_MERGE_MAX_I32] == [mref.OPS[k] for k in ("ADD_F64", "ADD_F32", "ADD_F32_TO_F64", "ADD_I64", "ADD_I32", "MIN_I32", "MAX_I32")]
+    jobs = (C.c_uint64 * 10)()
+    flags = (C.c_int32 * 4)()
+    p, fl = C.cast(jobs, C.c_void_p), C.cast(flags, C.c_void_p)
+    odd = C.c_void_p(p.value + 4)
+    for args, word in [((None, 2, 0, 4, 40, 0, fl, 4, None), "jobs_dev is NULL"),
+                       ((p, -1, 0, 4, 40, 0, fl, 4, None), "n_jobs"),
+                       ((p, (1 << 20) + 1, 0, 4, 40, 0, fl, 4, None), "n_jobs"),
+                       ((p, 2, 0, 4, 40, 0, fl, -1, None), "n_flags"),
+                       ((p, 2, 7, 4, 40, 0, fl, 4, None), "op = 7"),
+                       ((p, 2, -1, 4, 40, 0, fl, 4, None), "op = -1"),
+                       ((p, 2, 0, 0, 40, 0, fl, 4, None), "tile_cells"),
+                       ((p, 2, 1, 4, 6, 0, fl, 4, None), "bytes_per_cell"),
+                       ((p, 2, 1, 4, 132, 0, fl, 4, None), "bytes_per_cell"),
+                       ((p, 2, 0, 4, 20, 0, fl, 4, None), "no multiple of 8"),            # ADD_F64 on 20-byte cells
+                       ((p, 2, 3, 4, 4, 0, fl, 4, None), "no multiple of 8"),             # ADD_I64 on 4-byte cells
+                       ((p, 2, 2, 4, 20, 0, fl, 4, None), "no multiple of 8"),            # the exchange form needs float64 cells
+                       ((p, 2, 1, 2, 12, 0, fl, 4, None), "destination tile row"),        # 24-byte rows
+                       ((p, 2, 2, 2, 8, 0, fl, 4, None), "float32 source tile row of 8 bytes"),   # 16-byte rows, 8-byte source rows
+                       ((p, 2, 0, 4, 40, 0, None, 4, None), "flags is NULL"),
+                       ((odd, 2, 0, 4, 40, 0, fl, 4, None), "misaligned")]:
+        assert L.avl_tile_merge(*args) == -1, word
+        assert word in _lib.last_error(), (word, _lib.last_error())
+
+
+# ------------------------------------------------------------------------------------------------ gather_sites under gloo
+def _gather_worker(rank, world, port, q):
+    try:
+        sys.path.insert(0, ROOT)
+        import torch
+        import torch.distributed as dist
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        from vision_semantic_segmentation_amd.distributed import gather_sites
+        T = 4
+
+        def own(r, n, dtype):
+            coords = torch.tensor([[10 * r + k, -k] for k in range(n)], dtype=torch.int64).reshape(-1, 2)
+            tiles = (torch.arange(n * T * T * 5, dtype=torch.float64).reshape(n, T, T, 5) + 1000.0 * r).to(dtype)
+            return coords, tiles
+        out = []
+        for counts, dtype in (((3, 5), torch.float64), ((4, 0), torch.float32), ((0, 2), torch.float64), ((0, 0), torch.float64)):
+            coords, tiles = own(rank, counts[rank], dtype)
+            parts = gather_sites(coords, tiles)
+            assert len(parts) == world
+            for r, (c, t) in enumerate(parts):
+                wc, wt = own(r, counts[r], dtype)
+                assert c.dtype == torch.int64 and t.dtype == dtype and tuple(t.shape) == (counts[r], T, T, 5)
+                assert torch.equal(c, wc) and torch.equal(t, wt), (rank, counts, r)
+            out.append([int(c.shape[0]) for c, _ in parts])
+        elev = gather_sites(torch.tensor([[rank, rank]]), torch.full((1, T, T), rank, dtype=torch.int32))
+        assert [int(t[0, 0, 0]) for _, t in elev] == [0, 1] and elev[1][1].dtype == torch.int32
+        dist.barrier()
+        if rank == 0:
+            q.put(("ok", out))
+        dist.destroy_process_group()
+    except Exception:            # the parent must not wait for a result that never comes
+        import traceback
+        q.put(("error", "rank %d: %s" % (rank, traceback.format_exc(limit=4))))
+        raise
+
+
+def test_gather_sites_two_ranks_ragged_counts_and_an_empty_rank():
+    import queue
+    import socket
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    with socket.socket() as sock:            # a free port
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+    procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        status, payload = q.get(timeout=240)
+    except queue.Empty:
+        status, payload = "error", "no result within 240 s (exit codes %r)" % [p.exitcode for p in procs]
+    if status != "ok":
+        for p in procs:
+            p.terminate()
+        pytest.fail(payload)
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    assert payload == [[3, 5], [4, 0], [0, 2], [0, 0]]
+
+
+def test_gather_sites_without_a_group_is_the_own_pair():
+    import torch
+    from vision_semantic_segmentation_amd.distributed import gather_sites
+    c, t = torch.zeros((2, 2), dtype=torch.int64), torch.ones((2, 4, 4, 5))
+    parts = gather_sites(c, t)
+    assert len(parts) == 1 and parts[0][0] is c and parts[0][1] is t
+
+
+# ------------------------------------------------------------------------------------------------ the two vehicles
+def test_the_two_drives_overlap_the_way_the_gpu_test_assumes():
+    s = scroll()
+    a, b = ref.main_drive(), mref.second_drive()
+    assert (a.res, a.Hm, a.Wm, a.T, a.anchor) == (b.res, b.Hm, b.Wm, b.T, b.anchor)
+    assert sum(1 for _, moved in b.origins if moved) >= 3
+    ta, tb = set(a.numpy_site(np.eye(5)).nonempty_tiles()), set(b.numpy_site(np.eye(5)).nonempty_tiles())
+    assert ta & tb and ta - tb and tb - ta                                   # the routes share tiles, each has tiles the other lacks
+    # the first vehicle's map receives the second one's file after its own last frame
+    window = mref.window_tiles_at(a)
+    assert window == set(s.window_tiles((a.origins[-1][0][0] // a.T, a.origins[-1][0][1] // a.T), a.Ht, a.Wt))
+    assert len(ta & tb & window) >= 2                                        # shared tiles in its window
+    assert len((ta & tb) - window) >= 2                                      # shared tiles in its store
+    assert len(tb - ta - window) >= 2                                        # tiles that the file adds as new slabs
+    # sites keyed by tile: the sum of the two is the site of all their frames on every shared tile
+    sa, sb = mref.tiles_of(a.numpy_site(np.eye(5))), mref.tiles_of(b.numpy_site(np.eye(5)))
+    total = mref.nonempty(mref.sum_sites(sa, [sb]))
+    assert set(total) == ta | tb
+    t = sorted(ta & tb)[0]
+    assert np.array_equal(total[t], sa[t] + sb[t]) and np.array_equal(total[sorted(tb - ta)[0]], sb[sorted(tb - ta)[0]])
+    big = mref.big_site(total, a.T, (5,), np.float64)
+    assert sorted(big.nonempty_tiles()) == sorted(total)
+    cancelled = mref.nonempty(mref.sum_sites(sa, [{t: -sa[t]}]))
+    assert set(cancelled) == ta - {t}

@@ -16,6 +16,8 @@ AVL_MAX_VIEWS = 4               # views of one avl_fused_frame_views call
 AVL_LABEL_ABSTAINED, AVL_LABEL_NONE = 254, 255   # avl_point_labels' states beside the classes
 AVL_COUNTER_INTS = 256          # avl_grid.counter block (include/avl_hip.h)
 AVL_LIVE_FILTER, AVL_LIVE_THRESHOLDS, AVL_LIVE_FILL = 1, 2, 4   # avl_live_map's flags
+(AVL_MERGE_ADD_F64, AVL_MERGE_ADD_F32, AVL_MERGE_ADD_F32_TO_F64, AVL_MERGE_ADD_I64, AVL_MERGE_ADD_I32, AVL_MERGE_MIN_I32,
+ AVL_MERGE_MAX_I32) = range(7)   # avl_tile_merge's ops
 AVL_LIVE_CAR_DOUBLES = 8        # avl_live_map's car block
 AVL_LIVE_VIEW_MAX_SPAN = 2.875  # avl_live_view: the largest |M00| + |M01| and |M10| + |M11|
 AVL_PLANE_W_NONE, AVL_PLANE_W_XNORM = 0, 1
@@ -152,6 +154,7 @@ _SIGNATURES = {
     "avl_points_map_window": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "avl_points_map_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "avl_tile_copy": (_i, [_vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp]),
+    "avl_tile_merge": (_i, [_vp, _i, _i, _i, _i, C.c_uint32, _vp, _i, _vp]),
     "avl_site_overview": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avl_site_finish": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
 }

@@ -77,6 +77,31 @@ def reduce_grids_sparse(private_grid, group=None, value_dtype=torch.float32, rec
     return total, int(nmax * (4 + C_ * pv.element_size()))
 
 
+def gather_sites(coords, tiles, group=None):
+    """One layer of every rank's scrolled site (SemanticMapping.global_site): ``coords`` int64 [n, 2] tile coordinates and ``tiles``
+    [n, T, T, ...], n differing between ranks and 0 being legal.  The counts are all-gathered, both tensors padded to the longest
+    rank's count and all-gathered; -> [(coords, tiles)] per rank, views trimmed to that rank's count.  CUDA tensors (nccl, or gloo)
+    and CPU tensors (gloo), as reduce_grids_sparse.  Without a process group, or with one rank, the answer is the rank's own pair."""
+    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+    if world == 1:
+        return [(coords, tiles)]
+    n = int(coords.shape[0])
+    counts = [torch.zeros(1, dtype=torch.int64, device=coords.device) for _ in range(world)]
+    dist.all_gather(counts, torch.tensor([n], dtype=torch.int64, device=coords.device), group=group)
+    counts = [int(c.item()) for c in counts]
+    longest = max(counts)
+    pc = torch.zeros((longest, 2), dtype=coords.dtype, device=coords.device)
+    pt = torch.zeros((longest,) + tuple(tiles.shape[1:]), dtype=tiles.dtype, device=tiles.device)
+    pc[:n] = coords
+    pt[:n] = tiles
+    all_c = [torch.empty_like(pc) for _ in range(world)]
+    all_t = [torch.empty_like(pt) for _ in range(world)]
+    if longest:
+        dist.all_gather(all_c, pc, group=group)
+        dist.all_gather(all_t, pt, group=group)
+    return [(all_c[r][:counts[r]], all_t[r][:counts[r]]) for r in range(world)]
+
+
 def reduce_grids_auto(private_grid, group=None, exchange_dtype=torch.float32, max_fraction=SPARSE_MAX_FRACTION):
     """Sparse record exchange when EVERY rank touched fewer than `max_fraction` of the cells, the dense all-reduce otherwise (the choice
     must be the same on all ranks: it is made on the all-reduced maximum of the touched counts).  Returns (grid, mode, bytes sent)."""

@@ -1573,6 +1573,37 @@ class SemanticMapping(object):
         with self._lock:
             return self._scroll_store().load_site(path, stream)
 
+    def merge_site(self, path_or_arrays, stream=None):
+        """Another run's or another vehicle's site -- a save_site file, or the dict scroll.pack_site makes -- SUMMED into this map:
+        a frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.  Per cell the result
+        is own (+) theirs by the rule of struct avl_merge_job (include/avl_hip.h): one IEEE add for the map; with MAPPING.ELEVATION
+        its sum and count add (the int32 count WRAPS past 2^31 - 1), its minimum and maximum take the minimum and maximum.  Merging
+        is a left fold: merge_site(B); merge_site(C) gives (own + B) + C.  A tile of the file inside the current window is summed
+        into the live window buffer in place, a stored one into its slab, a tile this map does not have gets a new slab; nothing is
+        assembled, cost and memory follow the file's tiles.  A tile of this map that the file lacks is left as it is; where both
+        have the tile, the file's +0 cells turn a -0.0 of this map into +0.0.  A stored tile whose result is empty in every layer
+        gives its slab back.  One avl_tile_merge launch per layer on ``stream``; the call waits for the result flags.  -> scroll.SiteMerge
+        (tiles summed in the window, summed in the store, added, freed).  ValueError, naming the numbers, before any device work
+        and with the map untouched: the file's anchor, resolution, T, C, dtype or layers are not this map's -- sites of another
+        anchor or resolution would need resampling and are out of scope, as for load_site -- a tile named twice in a layer, a
+        tile at or beyond 2^30 cells.  Same stream contract as site_map."""
+        with self._lock:
+            return self._scroll_store().merge_site(path_or_arrays, stream)
+
+    def global_site(self, group=None, exchange_dtype=None, stream=None):
+        """The end-of-run collective of a scrolled multi-GPU run: every rank's site becomes the sum of all ranks' sites.  Each rank
+        packs its non-empty tiles on the device (save_site's gather without the host copy), the ranks all-gather coordinates and
+        tiles layer by layer (distributed.gather_sites), and every rank rebuilds its site as ((empty + S_0) + S_1) + ... in rank
+        order with merge_site's kernel -- the store is reset as load_site resets it, the window is left empty at origin (0, 0) -- so
+        all ranks hold the bit-identical sum.  ``exchange_dtype=torch.float32`` on a float64 map: the packed copy of the map layer is
+        cast first and summed as acc + (double)tile, half the payload; identity-matrix sites stay exact, log-matrix sites take each
+        rank's float32 rounding.  With world size 1 only the own site is folded: empty + S_0, which is S_0 but for a -0.0 (it becomes
+        +0.0) and, with a float32 exchange, its rounding.  ``last_exchange`` = ("tiles", bytes this rank sent).  -> [scroll.SiteMerge],
+        one per rank.  A SECOND call on the same map raises RuntimeError: the site already holds the other ranks' frames and would
+        count them again (load_site starts over).  global_map() keeps refusing a scrolled map: there is no common window to return."""
+        with self._lock:
+            return self._scroll_store().global_site(group, exchange_dtype, stream)
+
     # ------------------------------------------------------------------ multi-GPU: shared global grid
     def global_map(self, group=None, dst=None, exchange_dtype=None, mode="dense"):
         """Sum of every rank's private grid: each rank maps its own camera stream into its

@@ -26,6 +26,11 @@ labels and the ground-truth/label counts -- by the same scheme: a table of tile 
 csrc/seg_sitefinish.hip), which is the overview's table plus a NULL record for every absent tile that touches a present one and every
 record's eight neighbour indices (finish_sources), validated on the host (validate_finish) and launched once.
 
+MERGING SITES (TileStore.merge_site, TileStore.global_site) sums another run's or another rank's tiles into the tiles where they live
+-- the live window buffer, a slab of the store, a new slab -- by a table of merge jobs (struct avl_merge_job, k_tile_merge of
+csrc/seg_sitemerge.hip: result = acc (+) src, in place), built by merge_jobs, validated on the host (validate_merge) and launched once
+per layer.  A frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.
+
 THE STORE.  One pool per layer (the map; with MAPPING.ELEVATION its four arrays), made of chunks of POOL_CHUNK_TILES slabs of
 T * T * bytes_per_cell bytes; a chunk is a CUDA tensor.  The pool grows by whole chunks, so a stored tile never moves and jobs carry
 plain device addresses.  The host owns the directory {(ti, tj): slab} and the free list; a slab index names the same slot in every
@@ -234,6 +239,114 @@ def encode_jobs(jobs, buffers, out):
     out["dst_pitch"][:n] = [j.dst_pitch for j in jobs]
     out["flag"][:n] = [j.flag for j in jobs]
     out["pad"][:n] = 0
+    return n
+
+
+# ------------------------------------------------------------------------------------------------ merge tables
+MergeJob = collections.namedtuple("MergeJob", "src src_off src_pitch dst dst_off dst_pitch flag fresh")
+"""One merge job in host form (struct avl_merge_job of include/avl_hip.h): Job's fields -- a source is never None -- and ``fresh``,
+true when the accumulator is the layer's fill word and the destination is not read."""
+
+MERGE_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("dst", "<u8"), ("dst_pitch", "<i8"), ("flag", "<i4"), ("fresh", "<i4")])
+
+SiteMerge = collections.namedtuple("SiteMerge", "window store added freed")
+"""What merge_site returns, in tiles: summed into the window in place, summed into slabs of the store, added as new slabs, and slabs
+(old or new) that went back to the free list because the result is empty in every layer."""
+
+
+def merge_op(layer_name, dst_dtype, src_dtype=None):
+    """avl_tile_merge's op for a layer: the elevation layer's arrays by name, the map by its type ("f64" | "f32"); a float32 source
+    on a float64 map is the exchange form AVL_MERGE_ADD_F32_TO_F64."""
+    from . import _lib
+    ops = {"elev_sum": _lib.AVL_MERGE_ADD_I64, "elev_cnt": _lib.AVL_MERGE_ADD_I32, "elev_min": _lib.AVL_MERGE_MIN_I32,
+           "elev_max": _lib.AVL_MERGE_MAX_I32}
+    if layer_name in ops:
+        return ops[layer_name]
+    src_dtype = dst_dtype if src_dtype is None else src_dtype
+    if (dst_dtype, src_dtype) == ("f64", "f32"):
+        return _lib.AVL_MERGE_ADD_F32_TO_F64
+    if dst_dtype != src_dtype or dst_dtype not in ("f64", "f32"):
+        raise ValueError("no merge of %s tiles into a %s map" % (src_dtype, dst_dtype))
+    return _lib.AVL_MERGE_ADD_F64 if dst_dtype == "f64" else _lib.AVL_MERGE_ADD_F32
+
+
+def merge_jobs(entries, T, Wm, bpc, chunk_tiles, origin_tile, src_bpc=None, src="stage"):
+    """The merge table of one layer.  ``entries``: [(tile, k, kind, slab, flag)] -- the tile's data is the k-th tile of the buffer
+    ``src`` (tiles of T * T * src_bpc bytes, one after the other; src_bpc None = bpc, bpc // 2 = the float32 exchange form); kind
+    "window": the destination is the tile's place in the live window buffer "window", whose first tile is ``origin_tile``, merged in
+    place and without a flag (the window's emptiness is looked up when it is asked for); "store": slab ``slab``, in place; "fresh":
+    slab ``slab``, a new one, never read.  A slab's job reports its result in ``flag``."""
+    src_bpc = bpc if src_bpc is None else src_bpc
+    jobs = []
+    for t, k, kind, slab, flag in entries:
+        if kind == "window":
+            do, dp = window_ref(t, origin_tile, T, Wm, bpc)
+            jobs.append(MergeJob(src, k * T * T * src_bpc, T * src_bpc, "window", do, dp, -1, 0))
+        elif kind in ("store", "fresh"):
+            dk, do, dp = slab_ref(slab, chunk_tiles, T, bpc)
+            jobs.append(MergeJob(src, k * T * T * src_bpc, T * src_bpc, dk, do, dp, flag, int(kind == "fresh")))
+        else:
+            raise ValueError("merge entry %r: kind %r" % (t, kind))
+    return jobs
+
+
+def validate_merge(jobs, buffers, T, bpc, src_bpc=None, n_flags=None):
+    """ValueError, naming the job, unless every job of the merge table is safe to launch.  ``buffers``: {key: (device address,
+    bytes)}.  Every source tile -- T rows of T * src_bpc bytes (src_bpc None = bpc; bpc // 2: the float32 source of the exchange
+    form, half a destination row) -- and every destination tile -- T rows of T * bpc bytes -- lies inside the buffer it names; every
+    address and pitch is a multiple of 16 and a pitch is at least a row; no destination tile is named twice; no job's source is any
+    job's destination, and a buffer is read or written, never both, except distinct slabs of a chunk; a flag is below ``n_flags``.
+    What validate_jobs forbids and this allows is the merge itself: a job reads and writes its own destination in place."""
+    src_bpc = bpc if src_bpc is None else src_bpc
+    rows = {"dst": tile_row_bytes("merge jobs", T, bpc)}
+    if src_bpc not in (bpc, bpc // 2) or (T * src_bpc) % 16 != 0:
+        raise ValueError("merge jobs: a source of %d bytes per cell for a destination of %d, T = %d (the same or half of it, rows a "
+                         "multiple of 16 bytes)" % (src_bpc, bpc, T))
+    rows["src"] = T * src_bpc
+    written, read = {}, {}
+    for k, j in enumerate(jobs):
+        for what, key, off, pitch in (("src", j.src, j.src_off, j.src_pitch), ("dst", j.dst, j.dst_off, j.dst_pitch)):
+            row = rows[what]
+            if key is None:
+                raise ValueError("merge job %d has no %s" % (k, "source" if what == "src" else "destination"))
+            if key not in buffers:
+                raise ValueError("merge job %d: %s names the unknown buffer %r" % (k, what, key))
+            base, nbytes = buffers[key]
+            if pitch % 16 != 0 or pitch < row:
+                raise ValueError("merge job %d: %s pitch %d is misaligned or shorter than a tile row of %d bytes" % (k, what, pitch, row))
+            if (base + off) % 16 != 0:
+                raise ValueError("merge job %d: %s address %d + %d is not 16-byte aligned" % (k, what, base, off))
+            end = off + (T - 1) * pitch + row
+            if off < 0 or end > nbytes:
+                raise ValueError("merge job %d: %s bytes %d .. %d leave buffer %r of %d bytes" % (k, what, off, end, key, nbytes))
+            if what == "dst":
+                if (key, off) in written:
+                    raise ValueError("merge job %d: destination tile %r + %d appears twice (job %d)" % (k, key, off, written[(key, off)]))
+                written[(key, off)] = k
+            else:
+                read.setdefault((key, off), k)
+        if n_flags is not None and j.flag >= n_flags:
+            raise ValueError("merge job %d: flag %d of %d" % (k, j.flag, n_flags))
+    both = set(written) & set(read)
+    if both:
+        place = min(both, key=read.get)
+        raise ValueError("merge job %d: its source %r + %d is the destination of job %d" % (read[place], place[0], place[1], written[place]))
+    wkeys = {key for key, _ in written}
+    mixed = [k for (key, _), k in read.items() if key in wkeys and not (isinstance(key, tuple) and key[0] == "chunk")]
+    if mixed:
+        raise ValueError("merge job %d: its source buffer %r is written in the same table" % (min(mixed), jobs[min(mixed)].src))
+
+
+def encode_merge(jobs, buffers, out):
+    """``jobs`` as struct avl_merge_job records into the structured array ``out`` (MERGE_DTYPE, at least len(jobs) long)."""
+    n = len(jobs)
+    base = {k: v[0] for k, v in buffers.items()}
+    out["src"][:n] = [base[j.src] + j.src_off for j in jobs]
+    out["src_pitch"][:n] = [j.src_pitch for j in jobs]
+    out["dst"][:n] = [base[j.dst] + j.dst_off for j in jobs]
+    out["dst_pitch"][:n] = [j.dst_pitch for j in jobs]
+    out["flag"][:n] = [j.flag for j in jobs]
+    out["fresh"][:n] = [j.fresh for j in jobs]
     return n
 
 
@@ -517,6 +630,7 @@ class TileStore(object):
         self.flags_dev = None
         self.flags_host = None
         self.flags_event = None
+        self.exchanged = False            # global_site has run: the site holds the other ranks' frames
 
     # -------------------------------------------------------------------------------------------- layers and pools
     def _layers(self):
@@ -600,7 +714,6 @@ class TileStore(object):
         pinned memory is started, flags_event recorded behind it."""
         import ctypes as C
         from . import _lib
-        torch = self.torch
         for L, jobs, buffers in per_layer:
             validate_jobs(jobs, buffers, self.T, L.bpc, n_flags)          # raises before anything is uploaded or launched
         total = sum(len(jobs) for _, jobs, _ in per_layer)
@@ -613,13 +726,7 @@ class TileStore(object):
                 starts.append(at)
                 at += encode_jobs(jobs, buffers, rec[at:])
         n_layers = len(per_layer)
-        if n_flags and (self.flags_dev is None or int(self.flags_dev.numel()) < n_layers * n_flags):
-            if self.flags_event is not None:
-                self.flags_event.synchronize()
-            self.flags_event = torch.cuda.Event()
-            cap = max(2 * n_layers * n_flags, 256)
-            self.flags_dev = torch.empty(cap, dtype=torch.int32, device=self.sm.device)
-            self.flags_host = torch.empty(cap, dtype=torch.int32).pin_memory()
+        self._flags_room(n_layers * n_flags)
 
         def launch(table):
             for l, (L, jobs, _) in enumerate(per_layer):
@@ -628,10 +735,53 @@ class TileStore(object):
                                               L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
                 _lib.check(rc, "avl_tile_copy")
         self._launch_table(st, nbytes, fill, launch)
-        if n_flags:
-            with torch.cuda.stream(st):
-                self.flags_host[:n_layers * n_flags].copy_(self.flags_dev[:n_layers * n_flags], non_blocking=True)
+        self._flags_home(st, n_layers * n_flags)
+
+    def _flags_room(self, n):
+        """flags_dev / flags_host hold at least ``n`` flags (grown once no copy of the old ones is in flight)"""
+        torch = self.torch
+        if n and (self.flags_dev is None or int(self.flags_dev.numel()) < n):
+            if self.flags_event is not None:
+                self.flags_event.synchronize()
+            self.flags_event = torch.cuda.Event()
+            cap = max(2 * n, 256)
+            self.flags_dev = torch.empty(cap, dtype=torch.int32, device=self.sm.device)
+            self.flags_host = torch.empty(cap, dtype=torch.int32).pin_memory()
+
+    def _flags_home(self, st, n):
+        """starts the copy of the first ``n`` flags into pinned memory on ``st`` and records flags_event behind it"""
+        if n:
+            with self.torch.cuda.stream(st):
+                self.flags_host[:n].copy_(self.flags_dev[:n], non_blocking=True)
                 self.flags_event.record(st)
+
+    def _run_merge(self, per_layer, st, n_flags):
+        """``per_layer``: [(layer, op, src_bpc, jobs, buffers)] of MergeJob tables, all validated here (validate_merge), uploaded as
+        one table through the ring and launched once per layer (avl_tile_merge) on ``st``; the layers' result flags go where _run
+        puts its flags."""
+        import ctypes as C
+        from . import _lib
+        for L, op, src_bpc, jobs, buffers in per_layer:
+            validate_merge(jobs, buffers, self.T, L.bpc, src_bpc, n_flags)   # raises before anything is uploaded or launched
+        total = sum(len(jobs) for _, _, _, jobs, _ in per_layer)
+        starts = []
+
+        def fill(records):
+            rec, at = records.view(MERGE_DTYPE), 0
+            for _, _, _, jobs, buffers in per_layer:
+                starts.append(at)
+                at += encode_merge(jobs, buffers, rec[at:])
+        n_layers = len(per_layer)
+        self._flags_room(n_layers * n_flags)
+
+        def launch(table):
+            for l, (L, op, _, jobs, _) in enumerate(per_layer):
+                flags = C.c_void_p(self.flags_dev.data_ptr() + 4 * l * n_flags) if n_flags else None
+                rc = _lib.lib().avl_tile_merge(C.c_void_p(table + starts[l] * MERGE_DTYPE.itemsize), len(jobs), op, self.T, L.bpc,
+                                               L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
+                _lib.check(rc, "avl_tile_merge")
+        self._launch_table(st, max(total, 1) * MERGE_DTYPE.itemsize, fill, launch)
+        self._flags_home(st, n_layers * n_flags)
 
     # -------------------------------------------------------------------------------------------- the scroll
     def retire(self):
@@ -937,11 +1087,12 @@ class TileStore(object):
                 counts += cnt.cpu().numpy().reshape(8, 8)                  # waits for the kernel: the counts are a host result
         return SiteFinish(origin, pic, lab, counts, tiles)
 
-    def save_site(self, path, stream=None):
+    def _pack(self, st):
+        """-> (coords, outs): per layer the sorted non-empty tiles of the whole site, the window's own included, and a device tensor
+        [n, T, T, ...] of them, gathered by the tile-job kernel on ``st``"""
         torch = self.torch
         self.retire()
         T = self.T
-        st = self._stream(stream)
         window = self._window_nonempty()
         masks = dict(self.nonempty)
         masks.update(window)                                   # a tile is in the window or in the store, never both
@@ -959,27 +1110,50 @@ class TileStore(object):
                 per_layer.append((L, jobs, self._buffers(L, {"window": self._extent(cur), "out": self._extent(out)})))
         if per_layer:
             self._run(per_layer, st)
+        return coords, outs
+
+    def _dtype_name(self):
+        return "f64" if self.sm.grid_dtype == "f64" else "f32"
+
+    def save_site(self, path, stream=None):
+        st = self._stream(stream)
+        coords, outs = self._pack(st)
         st.synchronize()
-        g = self.sm.grid
-        arrays = pack_site(self.anchor, self.res, T, self.C, "f64" if g.torch_dtype == torch.float64 else "f32",
+        arrays = pack_site(self.anchor, self.res, self.T, self.C, self._dtype_name(),
                            {L.name: (np.array(c, dtype=np.int64).reshape(-1, 2), o.cpu().numpy()) for L, c, o in zip(self._layers(), coords, outs)})
         with open(path, "wb") as f:
             np.savez_compressed(f, **arrays)
 
+    def _reset(self, st):
+        """the store starts over: every slab free, the window empty (not valid) at origin (0, 0), its buffers cleared on ``st``"""
+        sm = self.sm
+        g = sm.grid
+        self._layers()
+        self.directory, self.nonempty = {}, {}
+        self.free = list(range(self.n_slabs - 1, -1, -1))
+        with self.torch.cuda.stream(st):
+            g.map.zero_()
+            if sm.elevation_enabled():
+                sm.reset_elevation(st.cuda_stream)
+        self.origin, self.first, self.window_valid, self.band = (0, 0), True, False, None
+        self.exchanged = False
+        boundary = window_boundary(self.anchor, (0, 0), self.Hm, self.Wm, self.res)
+        g.boundary = boundary
+        sm.map_boundary = boundary
+        sm._map_host = None
+        sm.scroll_origin = (0, 0)
+
     def load_site(self, path, stream=None):
         torch = self.torch
         sm = self.sm
-        g = sm.grid
         with np.load(path) as data:
-            meta, file_layers = unpack_site(data, self.anchor, self.res, self.T, self.C, "f64" if g.torch_dtype == torch.float64 else "f32")
+            meta, file_layers = unpack_site(data, self.anchor, self.res, self.T, self.C, self._dtype_name())
         layers = self._layers()
         if sorted(file_layers) != sorted(L.name for L in layers):
             raise ValueError("the site file holds the layers %r, this map %r" % (sorted(file_layers), sorted(L.name for L in layers)))
         self.retire()
         st = self._stream(stream)
-        # the store starts over: every slab free, the window empty at origin (0, 0)
-        self.directory, self.nonempty = {}, {}
-        self.free = list(range(self.n_slabs - 1, -1, -1))
+        self._reset(st)
         union = sorted({(int(c[0]), int(c[1])) for coords, _ in file_layers.values() for c in coords})
         for t in union:
             check_origin((t[0] * self.T, t[1] * self.T), self.T)
@@ -1008,16 +1182,160 @@ class TileStore(object):
         if union:
             self._run(per_layer, st)
         self.directory = slabs
-        with torch.cuda.stream(st):
-            g.map.zero_()
-            if sm.elevation_enabled():
-                sm.reset_elevation(st.cuda_stream)
         for s in keep:
             s.record_stream(st)
-        self.origin, self.first, self.window_valid, self.band = (0, 0), True, False, None
-        boundary = window_boundary(self.anchor, (0, 0), self.Hm, self.Wm, self.res)
-        g.boundary = boundary
-        sm.map_boundary = boundary
-        sm._map_host = None
-        sm.scroll_origin = (0, 0)
         return meta
+
+    # -------------------------------------------------------------------------------------------- merging sites
+    def _check_site(self, file_layers, src_dtypes=None):
+        """ValueError, naming the numbers, unless ``file_layers`` = {name: (coords, tiles)} can be merged into this map: its layers,
+        tiles of this map's shape and type (``src_dtypes``: {layer: torch dtype} where the exchange form brings another), tile
+        coordinates unique per layer and inside check_origin's range.  -> {name: [(ti, tj)]}"""
+        T = self.T
+        specs = [("map", (self.C,), "float64" if self._dtype_name() == "f64" else "float32")]      # from the configuration: nothing
+        if self.sm.elevation_enabled():                                                           # is allocated for a refusal
+            specs += [(L.name, (), "int64" if L.bpc == 8 else "int32") for L in ELEVATION_LAYERS]
+        if sorted(file_layers) != sorted(name for name, _, _ in specs):
+            raise ValueError("the site to merge holds the layers %r, this map %r" % (sorted(file_layers), sorted(name for name, _, _ in specs)))
+        out = {}
+        for name, tail, own_dtype in specs:
+            coords, tiles = file_layers[name]
+            want = (T, T) + tail
+            want_dtype = str((src_dtypes or {}).get(name, own_dtype)).replace("torch.", "")
+            dtype = str(tiles.dtype).replace("torch.", "")
+            if len(coords) != int(tiles.shape[0]) or (len(coords) and (tuple(tiles.shape[1:]) != want or dtype != want_dtype)):
+                raise ValueError("the site to merge has %d coordinates and tiles %s %s in layer %r, this map tiles %s %s"
+                                 % (len(coords), tuple(tiles.shape), dtype, name, want, want_dtype))
+            ts = [(int(c[0]), int(c[1])) for c in np.asarray(coords).reshape(-1, 2)]
+            seen = {}
+            for k, t in enumerate(ts):
+                if t in seen:
+                    raise ValueError("the site to merge names tile (%d, %d) of layer %r twice, at %d and %d" % (t[0], t[1], name, seen[t], k))
+                seen[t] = k
+                check_origin((t[0] * T, t[1] * T), T)
+            out[name] = ts
+        return out
+
+    def merge_site(self, site, stream=None):
+        if isinstance(site, dict):
+            data = site
+        else:
+            with np.load(site) as f:
+                data = {k: f[k] for k in f.files}
+        meta, file_layers = unpack_site(data, self.anchor, self.res, self.T, self.C, self._dtype_name())
+        tiles = self._check_site(file_layers)
+        return self._merge(file_layers, tiles, self._stream(stream))
+
+    def _merge(self, file_layers, tiles_of, st, src_dtypes=None):
+        """``file_layers`` (checked: ``tiles_of`` is _check_site's answer) summed into this site, one avl_tile_merge launch per layer on
+        ``st``; waits for the result flags.  -> SiteMerge"""
+        torch = self.torch
+        sm = self.sm
+        self.retire()
+        layers = self._layers()
+        T = self.T
+        a, b = self.origin[0] // T, self.origin[1] // T
+        union = sorted({t for ts in tiles_of.values() for t in ts})
+        kinds = {}
+        for t in union:
+            if self.window_valid and a <= t[0] < a + self.Ht and b <= t[1] < b + self.Wt:
+                kinds[t] = "window"
+            else:
+                kinds[t] = "store" if t in self.directory else "fresh"
+        new = [t for t in union if kinds[t] == "fresh"]
+        slabs = dict(zip(new, self._slabs(len(new))))
+        per_layer, keep, bits = [], [], []
+        try:
+            for l, L in enumerate(layers):
+                coords, tiles = file_layers[L.name]
+                have = {t: k for k, t in enumerate(tiles_of[L.name])}
+                cur = L.get()
+                src_dtype = (src_dtypes or {}).get(L.name, cur.dtype)
+                src_bpc = L.bpc * torch.empty(0, dtype=src_dtype).element_size() // cur.element_size()
+                lacking = [t for t in new if t not in have]           # a new slab the file has nothing for: fill (+) fill = fill
+                n = len(have)
+                with torch.cuda.stream(st):
+                    if torch.is_tensor(tiles):
+                        stage = tiles.contiguous().view(torch.uint8).reshape(-1)
+                    else:
+                        stage = torch.from_numpy(np.ascontiguousarray(tiles)).to(sm.device).view(torch.uint8).reshape(-1)
+                    if lacking:
+                        fill = L.fill - (1 << 32) if L.fill >= (1 << 31) else L.fill
+                        empty = torch.full((T * T * src_bpc // 4,), fill, dtype=torch.int32, device=sm.device).view(torch.uint8)
+                        stage = torch.cat([stage, empty])
+                keep.append(stage)
+                entries = []                                           # none for a tile that exists and gets nothing in this layer
+                for k, t in enumerate(union):
+                    if t in have:
+                        entries.append((t, have[t], kinds[t], slabs[t] if t in slabs else self.directory.get(t), k))
+                    elif t in slabs:
+                        entries.append((t, n, "fresh", slabs[t], k))
+                jobs = merge_jobs(entries, T, self.Wm, L.bpc, self.chunk_tiles, (a, b), src_bpc)
+                op = merge_op(L.name, self._dtype_name(), "f32" if src_dtype == torch.float32 and L.name == "map" else None)
+                if jobs:
+                    per_layer.append((L, op, src_bpc, jobs, self._buffers(L, {"window": self._extent(cur), "stage": self._extent(stage)})))
+                    bits.append(1 << l)                                # the layer's bit in a tile's nonempty mask
+            if per_layer:
+                self._run_merge(per_layer, st, len(union))
+        except Exception:
+            self.free.extend(slabs.values())
+            raise
+        for s in keep:
+            s.record_stream(st)
+        self.directory.update(slabs)
+        counts = collections.Counter(kinds.values())
+        freed = 0
+        if per_layer:
+            self.flags_event.synchronize()                             # merging is rare: the call waits for its flags
+            flags = self.flags_host[:len(per_layer) * len(union)].numpy().reshape(len(per_layer), len(union))
+            masks = {t: self.nonempty.get(t, 0) for t in union if kinds[t] != "window"}
+            for p, (_, _, _, jobs, _) in enumerate(per_layer):         # a layer's bit follows the result where the layer had a job
+                for j in jobs:
+                    if j.flag >= 0:
+                        t = union[j.flag]
+                        masks[t] = masks[t] & ~bits[p] | (bits[p] if flags[p, j.flag] else 0)
+            for t, mask in masks.items():
+                if mask:
+                    self.nonempty[t] = mask
+                else:                                                  # empty in every layer: as retire() does
+                    self.free.append(self.directory.pop(t))
+                    self.nonempty.pop(t, None)
+                    freed += 1
+        sm._map_host = None
+        return SiteMerge(counts["window"], counts["store"], counts["fresh"], freed)
+
+    def global_site(self, group=None, exchange_dtype=None, stream=None):
+        from . import distributed as D
+        torch = self.torch
+        if self.exchanged:
+            raise RuntimeError("global_site() has run on this map: the site already holds the other ranks' frames, a second exchange "
+                               "would count them again")
+        layers = self._layers()
+        cur = layers[0].get()
+        src_dtypes = {}
+        if exchange_dtype is not None and exchange_dtype != cur.dtype:
+            if (cur.dtype, exchange_dtype) != (torch.float64, torch.float32):
+                raise ValueError("global_site: exchange_dtype %s on a %s map (torch.float32 on a float64 map, or None)" % (exchange_dtype, cur.dtype))
+            src_dtypes["map"] = exchange_dtype
+        st = self._stream(stream)
+        coords, outs = self._pack(st)
+        gathered, sent = [], 0
+        with torch.cuda.stream(st):
+            for L, c, o in zip(layers, coords, outs):
+                if L.name in src_dtypes:
+                    o = o.to(src_dtypes[L.name])                       # the copy that travels: half the payload
+                ct = torch.tensor(c, dtype=torch.int64, device=o.device).reshape(-1, 2)
+                parts = D.gather_sites(ct, o, group=group)
+                longest = max(int(p[0].shape[0]) for p in parts)
+                if len(parts) > 1:                                     # one rank: nothing travels
+                    sent += 8 + longest *(16 + int(np.prod(o.shape[1:])) * o.element_size())     # the count; coordinates and tiles, padded
+                gathered.append(parts)
+        sites = []
+        for r in range(len(gathered[0])):                              # checked before the store is reset
+            site = {L.name: (gathered[l][r][0].cpu().numpy(), gathered[l][r][1]) for l, L in enumerate(layers)}
+            sites.append((site, self._check_site(site, src_dtypes)))
+        self._reset(st)
+        self.exchanged = True
+        merged = [self._merge(site, tiles_of, st, src_dtypes) for site, tiles_of in sites]   # ((empty + S_0) + S_1) + ...
+        self.sm.last_exchange = ("tiles", sent)
+        return merged

@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(kThreads) k_bilinear(const T* __restrict__ in,
     const int pix = (int)(idx / c8n), oy = pix / OW, ox = pix % OW;
     const float sy = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
     const float sx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    const float fy = sy * oy, fx = sx * ox;
+    const float fy = src_coord(sy, oy), fx = src_coord(sx, ox);      // rounded before the corner and the weight are taken (seg_types.h)
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
     const float ly = fy - y0, lx = fx - x0, hy = 1.f - ly, hx = 1.f - lx;

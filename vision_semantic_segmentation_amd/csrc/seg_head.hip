@@ -36,14 +36,7 @@ struct Geo {
     long long image_stride;            // floats between two images' logits (image_rows * ld); blockIdx.z = image
 };
 
-// The product is rounded before the corner and weight are taken from it: torch rounds it too, and the tile's window below must see the
-// very same value as every pixel inside it.  The empty asm makes it opaque, so hipcc cannot contract sy * oy - y0 into one FMA (the
-// weight would then move by up to an ulp of the source coordinate: 2e-5 relative at 266 -> 1080).
-__device__ __forceinline__ float src_coord(float scale, int dst) {
-    float p = scale * (float)dst;
-    asm("" : "+v"(p));
-    return p;
-}
+// src_coord (seg_types.h): the product is rounded, and the tile's window below must see the very same value as every pixel inside it.
 
 struct Corner {
     int y0, y1, x0, x1;

@@ -89,6 +89,17 @@ __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 template <typename T>
 __device__ __forceinline__ T from_f32(float v) { return (T)v; }
 
+// The source coordinate of every align_corners resampler (k_bilinear in seg_conv.hip, the full-resolution head in seg_head.hip):
+// src = dst * scale with scale = (in - 1) / (out - 1) a float32 division (0 when out = 1).  The product is rounded before the corner and
+// the weight are taken from it, as torch rounds it.  The empty asm makes it opaque, so hipcc cannot contract scale * dst - corner into one
+// FMA whatever the file's contraction setting (the weight would then move by up to an ulp of the source coordinate: 2e-5 relative at
+// 266 -> 1080).  mapping.hip states the same rule under -ffp-contract=off.
+__device__ __forceinline__ float src_coord(float scale, int dst) {
+    float p = scale * (float)dst;
+    asm("" : "+v"(p));
+    return p;
+}
+
 // The same DMA issued from inline asm: hipcc then does not know LDS is being written behind its back, so it
 // neither drains the queue (vmcnt(0)) in front of every ds_read nor before the next DMA; completion is
 // counted by hand (s_waitcnt vmcnt(N) + s_barrier in the caller).  M0 carries the wave-uniform LDS base.

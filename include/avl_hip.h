@@ -893,6 +893,45 @@ int avl_site_finish(const avl_tile_fin* tiles_dev, int n_tiles, int nh, int nw, 
                     int Hg, int Wg, int64_t gt_ld, int gt_r0, int gt_c0, const uint8_t* mask, int64_t mask_ld, uint8_t* picture,
                     uint8_t* labels, unsigned long long* counts, void* stream);
 
+/* ---- the live cost map: class costs, lethal cells and an inflated margin over the live map's window (csrc/seg_costmap.hip) --------
+ * The reference has no cost map; like avl_live_map this is a build-specific consumer of the grid: what the vehicle's planner
+ * reads instead of a picture.  THE RULE.  The result for a window is DEFINED as the crop of the following, taken over the WHOLE
+ * PLANE of cells, (gx, gy) any pair of integers:
+ *   class   cls(gx, gy) is the class of grid cell (gx, gy) by avl_live_map's rule: the cell's row through avl::box_filter3_taps
+ *           rounded to map_dtype with AVL_LIVE_FILTER (reflect-101 at the GRID's edge), then avl::argmax_class, or
+ *           avl::thresholds_class with AVL_LIVE_THRESHOLDS (priority_host NULL = 0..C-1; thresholds_host is required then); all of
+ *           csrc/avl_render.h.  A cell off the grid has no class.  AVL_LIVE_FILL is refused: the hole filler is a picture operation.
+ *   base    b = cost_host[cls]; cost_host int8[C + 1], entry C the cost of a cell with no class -- empty or off the grid.  Legal
+ *           values are 0 .. 100 and -1, "no information"; 100 is lethal (AVL_COST_LETHAL).
+ *   ego     with car_host != NULL, avl_live_map's double[AVL_LIVE_CAR_DOUBLES], a cell whose centre lies in the ego rectangle --
+ *           dx = (gx + 0.5) - cx, dy = (gy + 0.5) - cy, u = c*dx + s*dy, v = c*dy - s*dx (float64, no contraction), u_lo <= u < u_hi
+ *           and v_lo <= v < v_hi -- gets b = 0 before anything else: a noisy label under the car must not inflate.
+ *   d2      d2(gx, gy) = the minimum of dx*dx + dy*dy over the lethal cells (gx + dx, gy + dy) with |dx|, |dy| <= R, where that
+ *           minimum is <= R*R; AVL_COST_FAR (65535) if there is no such cell.  An integer; R = radius_cells, 0 ..
+ *           AVL_COST_MAX_RADIUS (32).  A lethal cell has d2 = 0.
+ *   infl    v = infl_host[d2] when d2 <= R*R, else 0.  infl_host uint8[R*R + 1] is built on the host (renderer.inflation_table):
+ *           infl_host[0] == 100, values 0 .. 100, non-increasing in d2.  The kernels see only the table: no floating point takes
+ *           part in the distance or the inflation.
+ *   result  out = max(b, v) when b >= 0;  out = v > 0 ? v : -1 when b == -1.
+ * cost_out int8: element (i, j) of the window stands for grid cell (x0 + i, y0 + j) and sits at i * stride_i + j * stride_j
+ * (elements).  (w, 1) is [h][w], the live map's order; (1, h) is [w][h], nav_msgs/OccupancyGrid's order, x fastest.  The strides
+ * must address h * w distinct elements: both in 1 .. 2^40, and the larger steps over the other axis' whole extent (an axis of one
+ * element asks nothing).  d2_out uint16, same addressing, or NULL: the clearance itself.
+ * scratch: avl_cost_map_scratch_bytes(h, w, radius_cells) bytes of device memory, about (h + 2R)(w + 2R) -- the base cost of the
+ * window and its ring of R cells; 0 for sizes the call refuses.  Two launches on `stream`; the call allocates nothing, copies
+ * nothing and waits for nothing.  The grid is only read; the window may lie partly or wholly off it.  1 <= h, w <= 32768;
+ * C <= AVL_MAX_MAP_CLASSES; the filter needs Hm, Wm >= 2.  AVL_E_ARG, before anything touches the device: a NULL map, cost_host,
+ * infl_host, cost_out or scratch, a size, radius, flag, cost, table or pair of strides outside the above, a scratch_bytes below
+ * avl_cost_map_scratch_bytes. */
+#define AVL_COST_LETHAL 100
+#define AVL_COST_FAR 65535
+#define AVL_COST_MAX_RADIUS 32
+int64_t avl_cost_map_scratch_bytes(int h, int w, int radius_cells);
+int avl_cost_map(const void* map, int map_dtype, int Hm, int Wm, int C, int x0, int y0, int h, int w, int flags,
+                 const int32_t* priority_host, const double* thresholds_host, const int8_t* cost_host, const double* car_host,
+                 int radius_cells, const uint8_t* infl_host, int8_t* cost_out, int64_t stride_i, int64_t stride_j, uint16_t* d2_out,
+                 void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- a1-a5: segmentation forward (DeepLabV3+ / ResNeXt-50 OS8, eval mode) -------------------
  *
  * The reference builds the network from torch modules (src/semantic_segmentation.py:21-57,

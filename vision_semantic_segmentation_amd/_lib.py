@@ -20,6 +20,7 @@ AVL_LIVE_FILTER, AVL_LIVE_THRESHOLDS, AVL_LIVE_FILL = 1, 2, 4   # avl_live_map's
  AVL_MERGE_MAX_I32) = range(7)   # avl_tile_merge's ops
 AVL_LIVE_CAR_DOUBLES = 8        # avl_live_map's car block
 AVL_LIVE_VIEW_MAX_SPAN = 2.875  # avl_live_view: the largest |M00| + |M01| and |M10| + |M11|
+AVL_COST_LETHAL, AVL_COST_FAR, AVL_COST_MAX_RADIUS = 100, 65535, 32   # avl_cost_map: the lethal cost, "no lethal cell within R", the largest R
 AVL_PLANE_W_NONE, AVL_PLANE_W_XNORM = 0, 1
 AVL_PLANE_MAX_HYP = 1024
 AVL_PLANE_RESULT_WORDS = 24     # 8-byte words of avl_plane_ransac's result block
@@ -157,6 +158,8 @@ _SIGNATURES = {
     "avl_tile_merge": (_i, [_vp, _i, _i, _i, _i, C.c_uint32, _vp, _i, _vp]),
     "avl_site_overview": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avl_site_finish": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "avl_cost_map_scratch_bytes": (_i64, [_i, _i, _i]),
+    "avl_cost_map": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

@@ -171,6 +171,27 @@ def get_cfg_defaults():
     C.MAPPING.LIVE_VIEW.SIZE_PX = [600, 600]              # height, width of the picture
     C.MAPPING.LIVE_VIEW.METRES_PER_PIXEL = 0.0            # 0: MAPPING.RESOLUTION (one cell per pixel)
     C.MAPPING.LIVE_VIEW.ANCHOR = [0.5, 0.5]               # fraction of the height from the top, of the width from the left
+    # build-specific: the live cost map (SemanticMapping.cost_map): LIVE_MAP's window as what a planner reads -- an int8 cost per cell
+    # (0 .. 100, 100 lethal, -1 no information) and an inflated margin around the lethal cells (the rule: include/avl_hip.h,
+    # avl_cost_map).  With ENABLED, mapping() / mapping_views() compute it after every EVERY-th mapped frame into
+    # SemanticMapping.cost_map_image (device) and cost_map_host (pinned, valid once the stream is synchronised) and publish a
+    # nav_msgs/OccupancyGrid on /semantic_cost_map under ROS.  The cost map only reads the grid
+    C.MAPPING.COST_MAP = CfgNode()
+    C.MAPPING.COST_MAP.ENABLED = False
+    C.MAPPING.COST_MAP.SIZE_M = [60.0, 60.0]              # window in metres along the grid's x, y; cells = int(size / RESOLUTION)
+    C.MAPPING.COST_MAP.EVERY = 1
+    C.MAPPING.COST_MAP.FILTER = True                      # renderer.apply_filter before the class is taken
+    C.MAPPING.COST_MAP.RENDER = "argmax"                  # the class of render_bev_map; "thresholds": of render_bev_map_with_thresholds
+    C.MAPPING.COST_MAP.PRIORITY = None
+    C.MAPPING.COST_MAP.THRESHOLDS = None
+    C.MAPPING.COST_MAP.CLASS_COST = [0, 0, 0, 100, 100]   # per entry of LABELS_NAMES: vegetation and sidewalk are lethal
+    C.MAPPING.COST_MAP.UNKNOWN_COST = -1                  # an empty cell and everything off the grid: no information
+    C.MAPPING.COST_MAP.INFLATION_RADIUS_M = 1.5           # cells = int(radius / RESOLUTION), 32 at the most
+    C.MAPPING.COST_MAP.INSCRIBED_RADIUS_M = 0.9           # within it the cost stays 99
+    C.MAPPING.COST_MAP.DECAY_PER_M = 3.0                  # beyond it: max(1, round(99 exp(-DECAY_PER_M (d - INSCRIBED_RADIUS_M))))
+    C.MAPPING.COST_MAP.CLEAR_FOOTPRINT = True             # cells under the ego rectangle cost 0 and do not inflate
+    C.MAPPING.COST_MAP.CAR_SIZE = [4.0, 1.8]              # length, width in metres (src/mapping.py:502-503)
+    C.MAPPING.COST_MAP.ORDER = "yx"                       # "yx": [w, h], OccupancyGrid's data with x fastest; "xy": [h, w], the live map's
     # build-specific: occluded points do not vote (the reference lets a map point behind a wall take the wall's label).  Every view gets a
     # depth buffer of CELL_PX x CELL_PX pixel cells of the projection image; a point is culled when its depth exceeds
     # m * (1 + REL_TOL) + ABS_TOL, m the nearest depth within RADIUS cells (the rule: include/avl_hip.h, avl_occlusion).  Off by

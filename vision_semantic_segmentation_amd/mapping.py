@@ -22,6 +22,9 @@ What differs from the reference, by design:
     MAPPING.LIVE_MAP.ENABLED ``mapping()`` / ``mapping_views()`` do so after the grid update.  The reference renders once, at
     shutdown.  ``live_view()`` is the same picture heading-up: rotated about the vehicle, scaled, the vehicle at a chosen pixel
     (MAPPING.LIVE_VIEW), still one kernel.
+  * ``cost_map()`` is the same window as a planner reads it: an int8 cost per cell from the cell's class (100 lethal, -1 no
+    information), 0 under the ego footprint, and an inflated margin around the lethal cells, in nav_msgs/OccupancyGrid's order
+    (MAPPING.COST_MAP; the rule at avl_cost_map in include/avl_hip.h); ``cost_map_info()`` has the grid's other fields.  Off by default.
   * with MAPPING.OCCLUSION.ENABLED, points hidden behind nearer ones in a view's image do not vote (a per-view depth buffer, the
     rule at struct avl_occlusion in include/avl_hip.h); ``visibility_device()`` returns the verdict per point.  The reference lets
     every point that lands in the image vote.  Off by default.
@@ -292,6 +295,16 @@ class SemanticMapping(object):
         self.pub_semantic_local_map = getattr(self, "pub_semantic_local_map", None)
         self._live_pose = None
 
+        # live cost map (MAPPING.COST_MAP); off by default: then nothing below is touched
+        self.cost_cfg = cfg.MAPPING.COST_MAP
+        self.cost_map_image = None             # int8 [w, h] (ORDER "yx") or [h, w] ("xy") on the device, the last cost map
+        self.cost_map_host = None              # the same in pinned host memory, valid once the stream is synchronised
+        self.cost_map_origin = None            # grid cell of the cost map's element (i, j) = (0, 0)
+        self.cost_map_size = None              # (h, w) cells of the last cost map
+        self.cost_map_ready = None             # event recorded behind the copy into cost_map_host
+        self.pub_semantic_cost_map = getattr(self, "pub_semantic_cost_map", None)
+        self._cost_par = self._parse_cost_map() if self.cost_cfg.ENABLED else None      # ValueError for a CLASS_COST or a radius that does not fit
+
         # occlusion culling (MAPPING.OCCLUSION); off by default: then nothing below is touched
         self.occlusion_cfg = getattr(cfg.MAPPING, "OCCLUSION", None)
         self.last_culled = None                # int32 CUDA tensor [V]: culled candidates per view of the last culling call (no sync to fill it)
@@ -343,6 +356,10 @@ class SemanticMapping(object):
         self.image_sub_cam6 = rospy.Subscriber("/camera6/semantic", Image, self.image_callback)
         self.pub_semantic_local_map = rospy.Publisher("/semantic_local_map", Image, queue_size=5)     # mapping.py:69
         self._ros_image_cls = Image
+        if self.cfg.MAPPING.COST_MAP.ENABLED:
+            from nav_msgs.msg import OccupancyGrid
+            self.pub_semantic_cost_map = rospy.Publisher("/semantic_cost_map", OccupancyGrid, queue_size=5)
+            self._ros_grid_cls = OccupancyGrid
         if self.depth_method == "points_map":
             if not self.points_map_indexed():                  # with the index nothing outside the package has to publish the crop
                 self.sub_pcd = rospy.Subscriber("/reduced_map", PointCloud2, self.pcd_callback)
@@ -646,6 +663,8 @@ class SemanticMapping(object):
             self._ground_fill_step([img], pose, [camera_calibration], pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
+        if self.cost_cfg.ENABLED:
+            self._cost_map_step(pose)
         if self.save_map_to_file:                                                # mapping.py:323-345, both depth modes
             self.save_map_to_file = False
             self.finish_run()
@@ -683,6 +702,8 @@ class SemanticMapping(object):
             self._ground_fill_step(images, pose, cameras, pcd, frame_id)
         if self.live_cfg.ENABLED:
             self._live_map_step(pose)
+        if self.cost_cfg.ENABLED:
+            self._cost_map_step(pose)
         if self.save_map_to_file:
             self.save_map_to_file = False
             self.finish_run()
@@ -854,6 +875,99 @@ class SemanticMapping(object):
             msg.data = self.live_map_host.numpy().tobytes()
             msg.header.frame_id = "semantic_local_map"
             self.pub_semantic_local_map.publish(msg)
+
+    # ------------------------------------------------------------------ live cost map (MAPPING.COST_MAP)
+    def _parse_cost_map(self):
+        """MAPPING.COST_MAP as renderer.cost_window's keyword arguments (without the car, which needs a pose).  ValueError for a
+        CLASS_COST that has not one entry per map class and for an inflation radius above _lib.AVL_COST_MAX_RADIUS cells."""
+        from . import renderer
+        cc = self.cost_cfg
+        class_cost = [int(v) for v in cc.CLASS_COST]
+        if len(class_cost) != self.map_depth:
+            raise ValueError("MAPPING.COST_MAP.CLASS_COST has %d entries for %d map classes (LABELS_NAMES)" % (len(class_cost), self.map_depth))
+        radius = int(float(cc.INFLATION_RADIUS_M) / self.resolution)
+        if not 0 <= radius <= _lib.AVL_COST_MAX_RADIUS:
+            raise ValueError("MAPPING.COST_MAP.INFLATION_RADIUS_M = %g is %d cells of %g m: 0 .. %d" % (
+                float(cc.INFLATION_RADIUS_M), radius, self.resolution, _lib.AVL_COST_MAX_RADIUS))
+        if cc.RENDER not in ("argmax", "thresholds"):
+            raise ValueError("MAPPING.COST_MAP.RENDER must be 'argmax' or 'thresholds', not %r" % (cc.RENDER,))
+        if cc.ORDER not in ("xy", "yx"):
+            raise ValueError("MAPPING.COST_MAP.ORDER must be 'xy' or 'yx', not %r" % (cc.ORDER,))
+        thresholds = priority = None
+        if cc.RENDER == "thresholds":
+            thresholds = cc.THRESHOLDS if cc.THRESHOLDS is not None else [0.01] * self.map_depth
+            priority = cc.PRIORITY
+        table = renderer.inflation_table(radius, self.resolution, float(cc.INSCRIBED_RADIUS_M), float(cc.DECAY_PER_M))
+        return dict(class_cost=class_cost, unknown_cost=int(cc.UNKNOWN_COST), radius_cells=radius, inflation=table,
+                    filter=bool(cc.FILTER), thresholds=thresholds, priority=priority, order=str(cc.ORDER))
+
+    def _cost_window(self, pose, size_cells):
+        if size_cells is None:
+            size_cells = [int(float(v) / self.resolution) for v in self.cost_cfg.SIZE_M]
+        return self.live_map_window(pose, size_cells)
+
+    def cost_map(self, pose=None, size_cells=None, d2=False, out=None, stream=None):
+        """The cost map around the vehicle as an int8 CUDA tensor (renderer.cost_window with MAPPING.COST_MAP's settings): the
+        window is live_map_window's for COST_MAP.SIZE_M, element (i, j) stands for grid cell (x0 + i, y0 + j) and the tensor is
+        [w, h] with ORDER "yx" -- nav_msgs/OccupancyGrid's data, x fastest; cost_map_info() has its other fields -- or [h, w] with
+        "xy".  With CLEAR_FOOTPRINT the cells under the ego rectangle (car_block, CAR_SIZE) cost 0 and do not inflate.  ``d2`` True
+        also returns the squared clearance in cells, uint16 (65535: no lethal cell within the radius): -> (cost, d2).  ``pose``
+        None = the last pose mapped; ``size_cells`` None = COST_MAP.SIZE_M.  Reads the grid only."""
+        from . import renderer
+        pose = self._live_pose if pose is None else pose
+        if pose is None:
+            raise RuntimeError("cost_map needs a pose: none was given and no frame has been mapped with one")
+        if self._cost_par is None:
+            self._cost_par = self._parse_cost_map()
+        origin, size, (cx, cy) = self._cost_window(pose, size_cells)
+        car = None
+        if self.cost_cfg.CLEAR_FOOTPRINT:
+            c, s = pose_heading(pose)
+            car = renderer.car_block(cx, cy, c, s, self.resolution, self.cost_cfg.CAR_SIZE)
+        res = renderer.cost_window(self.map_dev, origin, size, car=car, out=out, d2_out=True if d2 else None, stream=stream, **self._cost_par)
+        self.cost_map_origin, self.cost_map_size = origin, size
+        return res
+
+    def cost_map_info(self, pose=None, size_cells=None):
+        """The nav_msgs/OccupancyGrid fields of the cost map -- of the last one, or with ``pose`` of the one cost_map(pose, size_cells)
+        gives: {"resolution", "width", "height", "origin_x", "origin_y"}.  width counts the cells along the grid's x (the window's
+        h), height those along y (its w); (origin_x, origin_y) is the corner of the window's first cell in the map frame, the inverse
+        of live_map_window's expression: boundary minimum + cell * resolution - PCD_ORIGIN_OFFSET."""
+        if pose is not None:
+            origin, size, _ = self._cost_window(pose, size_cells)
+        elif self.cost_map_origin is not None:
+            origin, size = self.cost_map_origin, self.cost_map_size
+        else:
+            raise RuntimeError("cost_map_info needs a pose or a cost map: none was given and cost_map has not run")
+        return {"resolution": float(self.resolution), "width": int(size[0]), "height": int(size[1]),
+                "origin_x": float(self.map_boundary[0][0]) + origin[0] * float(self.resolution) - PCD_ORIGIN_OFFSET[0],
+                "origin_y": float(self.map_boundary[1][0]) + origin[1] * float(self.resolution) - PCD_ORIGIN_OFFSET[1]}
+
+    def _cost_map_step(self, pose):
+        """mapping()'s cost map branch: on every EVERY-th call (the first included) compute the cost map, keep it, start its copy into
+        pinned memory and -- under ROS -- publish it as a nav_msgs/OccupancyGrid on /semantic_cost_map."""
+        self._cost_frames = getattr(self, "_cost_frames", 0) + 1
+        if self._live_pose is None or (self._cost_frames - 1) % max(int(self.cost_cfg.EVERY), 1) != 0:
+            return
+        img = self.cost_map()
+        self.cost_map_image = img
+        if self.cost_map_host is None or self.cost_map_host.shape != img.shape:
+            self.cost_map_host = torch.empty(tuple(img.shape), dtype=torch.int8).pin_memory()
+            self.cost_map_ready = torch.cuda.Event()
+        self.cost_map_host.copy_(img, non_blocking=True)      # stream-ordered behind the kernels and behind the previous copy
+        self.cost_map_ready.record(torch.cuda.current_stream(self.device))
+        if self._ros is not None and self.pub_semantic_cost_map is not None:
+            self.cost_map_ready.synchronize()
+            info = self.cost_map_info()
+            host = self.cost_map_host.numpy()
+            msg = self._ros_grid_cls()
+            msg.header.frame_id = "map"
+            msg.info.resolution = info["resolution"]
+            msg.info.width, msg.info.height = info["width"], info["height"]
+            msg.info.origin.position.x, msg.info.origin.position.y = info["origin_x"], info["origin_y"]
+            msg.info.origin.orientation.w = 1.0
+            msg.data = (host if self.cost_cfg.ORDER == "yx" else host.T).ravel().tolist()
+            self.pub_semantic_cost_map.publish(msg)
 
     # ------------------------------------------------------------------ occlusion culling (MAPPING.OCCLUSION)
     def occlusion_enabled(self):

@@ -7,7 +7,8 @@ The renderer's remaining functions are here too: fill_black with resume_color (:
 defines and never calls, and render_window, the per-frame front end: filter, renderer, hole fill and the ego car
 (src/mapping.py:490-526) over a window of the grid in one kernel (avl_live_map), bit-equal to a crop of the chain of the functions
 above.  render_view is the same picture through a 2 x 3 matrix from output pixels to grid cells (avl_live_view): rotated, scaled,
-heading-up with view_matrix.
+heading-up with view_matrix.  cost_window is the window as a planner reads it (avl_cost_map): an int8 cost per cell from its class and
+an inflated margin around the lethal cells, from inflation_table.
 """
 import ctypes as C
 
@@ -209,3 +210,87 @@ def render_view(map, label_colors, matrix, size, filter=True, thresholds=None, p
     _lib.check(_lib.lib().avl_live_view(C.c_void_p(t.data_ptr()), dt, hm, wm, c, colors, (C.c_double * 6)(*m.ravel().tolist()), h, w,
                                         flags, pr, th, fp, n_fp, car_c, col_c, C.c_void_p(out.data_ptr()), s), "avl_live_view")
     return out.cpu().numpy() if is_np else out
+
+
+# ---------------------------------------------------------------------------------------------------- the live cost map
+_cost_scratch = {}       # (device, stream, bytes) -> uint8 CUDA tensor: avl_cost_map's byte plane
+
+
+def inflation_table(radius_cells, resolution, inscribed_m, decay_per_m, max_cost=99):
+    """avl_cost_map's inflation table, uint8 [R * R + 1] indexed by the squared distance in cells to the nearest lethal cell: entry 0
+    is 100 (the lethal cell itself); for d = sqrt(d2) * resolution metres, ``max_cost`` while d <= inscribed_m, else
+    max(1, round(max_cost * exp(-decay_per_m * (d - inscribed_m)))) -- costmap_2d's inflation curve.  float64, host only: the
+    kernels see the table alone."""
+    r = int(radius_cells)
+    if not 0 <= r <= _lib.AVL_COST_MAX_RADIUS:
+        raise ValueError("radius_cells = %d: 0 .. %d" % (r, _lib.AVL_COST_MAX_RADIUS))
+    if not 1 <= int(max_cost) <= _lib.AVL_COST_LETHAL or float(decay_per_m) < 0.0:
+        raise ValueError("max_cost must lie in 1 .. %d and decay_per_m may not be negative" % _lib.AVL_COST_LETHAL)
+    d = np.sqrt(np.arange(r * r + 1, dtype=np.float64)) * float(resolution)
+    beyond = np.maximum(d - float(inscribed_m), 0.0)
+    table = np.maximum(1.0, np.round(float(max_cost) * np.exp(-float(decay_per_m) * beyond)))
+    table[d <= float(inscribed_m)] = float(max_cost)
+    table = table.astype(np.uint8)
+    table[0] = _lib.AVL_COST_LETHAL
+    return table
+
+
+def cost_window(map, origin, size, class_cost, unknown_cost=-1, radius_cells=0, inflation=None, filter=True, thresholds=None,
+                priority=None, car=None, order="xy", out=None, d2_out=None, stream=None):
+    """The cost map of the window of `size` = (h, w) cells whose first cell is grid cell `origin` = (x0, y0), an int8 CUDA tensor
+    (avl_cost_map, include/avl_hip.h): every cell's class by render_window's rule (`filter`, `thresholds`, `priority`), its cost
+    ``class_cost[class]`` (``unknown_cost`` for an empty cell and off the grid; 0 .. 100 or -1 = no information, 100 lethal), 0 under
+    `car` = car_block(...), then for every cell within `radius_cells` of a lethal one ``inflation[d2]`` (inflation_table; d2 the
+    squared distance in cells) where that is higher; a cell without information takes it where it is above 0.  order "xy" gives
+    [h, w], the live map's; "yx" gives [w, h], nav_msgs/OccupancyGrid's row-major data with x fastest.  `d2_out`: True, or a uint16
+    tensor of the result's shape, also returns the squared clearance (65535 = none within the radius): -> (cost, d2).  `map` is a
+    CUDA tensor or a NumPy array (uploaded); the result stays on the device.  The grid is only read."""
+    t, _, dt = _prep(map)
+    hm, wm, c = t.shape
+    h, w, r = int(size[0]), int(size[1]), int(radius_cells)
+    if order not in ("xy", "yx"):
+        raise ValueError("order must be 'xy' ([h, w]) or 'yx' ([w, h]), not %r" % (order,))
+    if len(class_cost) != c:
+        raise ValueError("%d class costs for a map of %d channels" % (len(class_cost), c))
+    if not 0 <= r <= _lib.AVL_COST_MAX_RADIUS:
+        raise ValueError("radius_cells = %d: 0 .. %d" % (r, _lib.AVL_COST_MAX_RADIUS))
+    if inflation is None:
+        if r:
+            raise ValueError("radius_cells = %d needs an inflation table (inflation_table)" % r)
+        inflation = [_lib.AVL_COST_LETHAL]
+    infl = np.ascontiguousarray(np.asarray(inflation), dtype=np.uint8)
+    if infl.shape != (r * r + 1,):
+        raise ValueError("the inflation table of radius %d has %d entries, not %s" % (r, r * r + 1, infl.shape))
+    costs = [int(v) for v in class_cost] + [int(unknown_cost)]
+    if any(v < -128 or v > 127 for v in costs):
+        raise ValueError("a cost is -1 or 0 .. 100")
+    _, pr, th = render_params(np.zeros((c, 3), dtype=np.uint8), c, thresholds, priority)
+    flags = (_lib.AVL_LIVE_FILTER if filter else 0) | (_lib.AVL_LIVE_THRESHOLDS if th is not None else 0)
+    car_c = None
+    if car is not None:
+        if len(car) != _lib.AVL_LIVE_CAR_DOUBLES:
+            raise ValueError("car is car_block(...): %d numbers" % _lib.AVL_LIVE_CAR_DOUBLES)
+        car_c = (C.c_double * _lib.AVL_LIVE_CAR_DOUBLES)(*[float(v) for v in car])
+    shape = (max(h, 0), max(w, 0)) if order == "xy" else (max(w, 0), max(h, 0))
+    stride_i, stride_j = (w, 1) if order == "xy" else (1, h)
+
+    def result(given, dtype, name):
+        if given is None:
+            return torch.empty(shape, dtype=dtype, device=t.device)
+        if tuple(given.shape) != shape or given.dtype != dtype or given.device != t.device or not given.is_contiguous():
+            raise ValueError("%s must be a contiguous %s %s tensor on %s" % (name, dtype, list(shape), t.device))
+        return given
+
+    out = result(out, torch.int8, "out")
+    d2 = None if d2_out is None or d2_out is False else result(None if d2_out is True else d2_out, torch.uint16, "d2_out")
+    s = _stream(t) if stream is None else C.c_void_p(int(stream))
+    need = int(_lib.lib().avl_cost_map_scratch_bytes(h, w, r))
+    key = (t.device, int(s.value or 0), need)
+    scratch = _cost_scratch.get(key)
+    if scratch is None:
+        scratch = _cost_scratch[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=t.device)
+    _lib.check(_lib.lib().avl_cost_map(C.c_void_p(t.data_ptr()), dt, hm, wm, c, int(origin[0]), int(origin[1]), h, w, flags, pr, th,
+                                       (C.c_int8 * (c + 1))(*costs), car_c, r, (C.c_uint8 * infl.size)(*infl.tolist()),
+                                       C.c_void_p(out.data_ptr()), stride_i, stride_j, C.c_void_p(d2.data_ptr()) if d2 is not None else None,
+                                       C.c_void_p(scratch.data_ptr()), need, s), "avl_cost_map")
+    return out if d2 is None else (out, d2)

@@ -740,14 +740,15 @@ int avl_points_map_gather(const float* points, const int32_t* offsets_dev, const
  *      stream-ordered, before the kernel; the kernel sets a flag with an integer atomic OR.  A flag index >= n_flags is ignored.
  *   4. no two jobs of a call write the same byte, and no job reads a byte another writes: the kernel orders nothing between jobs.
  * The caller owns the table's validity: every src, dst and pitch 16-byte aligned, every range inside the buffer it belongs to.  The
- * library cannot check a table that lives on the device; scroll.validate_jobs does, on the host, before the upload. */
+ * library cannot check a table that lives on the device; scroll.validate_jobs does, on the host, before the upload.  The same record
+ * serves avl_tile_merge below, whose rule reads its last word. */
 typedef struct avl_tile_job {
     const void* src;      /* first byte of the source tile, or NULL: the destination is filled with the fill word */
     int64_t src_pitch;    /* bytes between tile rows of the source                                               */
     void* dst;            /* first byte of the destination tile                                                  */
     int64_t dst_pitch;    /* bytes between tile rows of the destination                                          */
     int32_t flag;         /* >= 0: the flag that receives rule 3; < 0: none                                      */
-    int32_t pad;
+    int32_t fresh;        /* read by avl_tile_merge only (!= 0: its rule 2), ignored by avl_tile_copy            */
 } avl_tile_job;
 
 /* Executes jobs_dev[0 .. n_jobs), a DEVICE array, by the rule above, in one launch on `stream`: 16 bytes per lane, a tile split over
@@ -761,8 +762,9 @@ int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int 
 /* ---- merging sites: tile merge jobs (not in the reference; csrc/seg_sitemerge.hip, scroll.TileStore.merge_site) -------------------
  * A frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.  Another run's or another
  * rank's tiles are accumulated into this map's tiles where those live: the window buffer, a slab of the store.  THE RULE:
- *   1. tile: as rule 1 of avl_tile_job; bytes_per_cell is the DESTINATION's.  In AVL_MERGE_ADD_F32_TO_F64 the source tile is float32
- *      and its rows hold half the destination row's bytes.
+ *   1. tile: the record is struct avl_tile_job above, with its rule 1; src is never NULL, dst is accumulator and result, and
+ *      bytes_per_cell is the DESTINATION's.  In AVL_MERGE_ADD_F32_TO_F64 the source tile is float32 and its rows hold half the
+ *      destination row's bytes.
  *   2. merge: result = acc (+) src, element by element, written to the destination.  acc is the destination's old content, read and
  *      written in place by the same lane.  With fresh != 0, acc is the layer's fill word in every 32-bit word and the destination is
  *      NOT read: whatever bytes it holds do not reach the result.  A fresh tile is no byte copy -- +0.0 + -0.0 = +0.0 -- so the
@@ -782,8 +784,8 @@ int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int 
  *      sets a flag with an integer atomic OR.  A flag index >= n_flags is ignored.
  *   5. no two jobs of a call name the same destination tile and no job's source is any job's destination: the kernel orders nothing
  *      between jobs.  (A job reading and writing its OWN destination in place is the merge itself.)
- * The caller owns the table's validity as for avl_tile_job: every src, dst and pitch 16-byte aligned, no NULL src or dst, every range
- * inside the buffer it belongs to.  scroll.validate_merge checks that on the host before the upload. */
+ * The caller owns the table's validity as for avl_tile_copy: every src, dst and pitch 16-byte aligned, no NULL src or dst, every range
+ * inside the buffer it belongs to.  scroll.validate_jobs(..., merge=True) checks that on the host before the upload. */
 #define AVL_MERGE_ADD_F64 0
 #define AVL_MERGE_ADD_F32 1
 #define AVL_MERGE_ADD_F32_TO_F64 2
@@ -791,21 +793,13 @@ int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int 
 #define AVL_MERGE_ADD_I32 4
 #define AVL_MERGE_MIN_I32 5
 #define AVL_MERGE_MAX_I32 6
-typedef struct avl_merge_job {
-    const void* src;      /* first byte of the source tile (never NULL)                                          */
-    int64_t src_pitch;    /* bytes between tile rows of the source                                               */
-    void* dst;            /* first byte of the destination tile: accumulator and result                          */
-    int64_t dst_pitch;    /* bytes between tile rows of the destination                                          */
-    int32_t flag;         /* >= 0: the flag that receives rule 4; < 0: none                                      */
-    int32_t fresh;        /* != 0: the accumulator is the fill word and the destination is not read (rule 2)     */
-} avl_merge_job;
 
 /* Executes jobs_dev[0 .. n_jobs), a DEVICE array, by the rule above, in one launch on `stream`: 16 bytes per lane and memory
  * instruction, a tile split over workgroups by rows as in avl_tile_copy.  One call serves one layer.  Nothing is allocated, copied
  * from the host or waited for.  n_jobs == 0 only zeroes the flags.  AVL_E_ARG, before any GPU work: avl_tile_copy's list, an op
  * outside the seven above, bytes_per_cell no multiple of 8 for the 64-bit ops (ADD_F64, ADD_F32_TO_F64, ADD_I64), a destination row
  * -- or, for ADD_F32_TO_F64, the source row of half its bytes -- that is no multiple of 16 bytes. */
-int avl_tile_merge(const avl_merge_job* jobs_dev, int n_jobs, int op, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags,
+int avl_tile_merge(const avl_tile_job* jobs_dev, int n_jobs, int op, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags,
                    int n_flags, void* stream);
 
 /* ---- the site overview: a reduced grid and its picture straight from the tiles (not in the reference; csrc/seg_overview.hip) ---------

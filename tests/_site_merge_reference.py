@@ -1,7 +1,7 @@
 """NumPy restatement of merging sites, shared by test_site_merge_cpu.py and test_gpu_site_merge.py.
 
-* an executor of merge-job tables on NumPy byte buffers (struct avl_merge_job's rule, written out again here and not imported from
-  scroll.py): result = acc (+) src per element, acc the destination's old content or -- for a fresh job -- the fill word, the seven
+* an executor of merge-job tables on NumPy byte buffers (avl_tile_merge's rule for struct avl_tile_job, written out again here and not
+  imported from scroll.py): result = acc (+) src per element, acc the destination's old content or -- for a fresh job -- the fill word, the seven
   ops, the flag of the RESULT;
 * the sum of sites keyed by global tile: a left fold over {tile: array} dictionaries, a missing tile standing for the fill state;
 * the second vehicle of the end-to-end tests, a drive that shares window, resolution and tile size with _scroll_reference.main_drive.
@@ -32,7 +32,7 @@ def combine(op, acc, src):
 
 
 def execute_merge(jobs, buffers, T, bpc, op, fill, n_flags):
-    """``jobs``: scroll.MergeJob records (or any object with their fields); ``buffers``: {key: np.uint8 array}, written in place.
+    """``jobs``: scroll.Job records (or any object with their fields); ``buffers``: {key: np.uint8 array}, written in place.
     ``bpc`` is the destination's; the source of ADD_F32_TO_F64 has rows of half the bytes.  -> int32 [n_flags]"""
     flags = np.zeros(n_flags, dtype=np.int32)
     row = T * bpc

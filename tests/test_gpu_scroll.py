@@ -81,6 +81,18 @@ def test_tile_copy_rows_of_4000_bytes(shift, cuda_device):
     check_table(ref.TableCase(shift, 40, 0, 100, 2, 3, 5, (2, -1)), cuda_device)
 
 
+@pytest.mark.parametrize("bpc,fill", [(40, 0), (4, 0x7FFFFFFF)], ids=["40", "4_max"])
+def test_tile_copy_ignores_the_fresh_word(bpc, fill, cuda_device):
+    """struct avl_tile_job's last word is avl_tile_merge's: with 1 in every record the copy is the executor's, byte for byte"""
+    from vision_semantic_segmentation_amd import scroll as s
+    case = ref.TableCase((1, -2), bpc, fill, 4, 6, 4, 5, (2, -1))
+    case.jobs = [j._replace(fresh=1) for j in case.jobs]
+    rec = np.zeros(len(case.jobs), dtype=s.JOB_DTYPE)
+    s.encode_jobs(case.jobs, case.extents, rec)
+    assert (rec["fresh"] == 1).all()                                # the word reaches the device table
+    check_table(case, cuda_device)
+
+
 # ------------------------------------------------------------------------------------------------ the drive
 _DRIVES = {}
 

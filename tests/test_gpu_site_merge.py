@@ -26,7 +26,7 @@ AB32 = -0x54545455           # 0xABABABAB
 
 # ------------------------------------------------------------------------------------------------ the kernel against the executor
 def run_merge_on_device(case, device):
-    """-> ({key: bytes after the launch, guards included}, flags with guards): case.jobs through validate_merge, encode_merge and
+    """-> ({key: bytes after the launch, guards included}, flags with guards): case.jobs through validate_jobs, encode_jobs and
     avl_tile_merge, every buffer of case.bufs between two guard strips of 0xAB"""
     import torch
     from vision_semantic_segmentation_amd import _lib, scroll as s
@@ -36,9 +36,9 @@ def run_merge_on_device(case, device):
         t[GUARD:GUARD + host.size] = torch.from_numpy(host).to(device)
         dev[key] = t
         extents[key] = (t.data_ptr() + GUARD, int(host.size))
-    s.validate_merge(case.jobs, extents, case.T, case.bpc, case.src_bpc, case.n_flags)
-    rec = np.zeros(len(case.jobs), dtype=s.MERGE_DTYPE)
-    s.encode_merge(case.jobs, extents, rec)
+    s.validate_jobs(case.jobs, extents, case.T, case.bpc, case.n_flags, case.src_bpc, merge=True)
+    rec = np.zeros(len(case.jobs), dtype=s.JOB_DTYPE)
+    s.encode_jobs(case.jobs, extents, rec)
     table = torch.from_numpy(rec.view(np.uint8)).to(device)
     flags = torch.full((16 + case.n_flags + 16,), AB32, dtype=torch.int32, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream

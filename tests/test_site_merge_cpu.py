@@ -1,6 +1,6 @@
-"""Merging sites without a GPU: the NumPy executor of merge tables on hand-made operands, scroll.validate_merge's refusals, merge_site's
-refusals on a CPU-device SemanticMapping, avl_tile_merge's argument errors through the real library, distributed.gather_sites under
-two-rank gloo, and the conditions the two-vehicle drive must meet so that the GPU test cannot pass on sites that never overlap."""
+"""Merging sites without a GPU: the NumPy executor of merge tables on hand-made operands, scroll.validate_jobs' refusals of merge
+tables, merge_site's refusals on a CPU-device SemanticMapping, avl_tile_merge's argument errors through the real library,
+distributed.gather_sites under two-rank gloo, and the conditions the two-vehicle drive must meet so that the GPU test cannot pass on sites that never overlap."""
 import ctypes as C
 import collections
 import os
@@ -110,7 +110,7 @@ def test_executor_integers_wrap_and_min_max_meet_their_fills():
 def test_merge_case_tables_do_what_the_gpu_test_assumes(op, bpc, fill):
     s = scroll()
     case = mref.MergeCase(op, 4, bpc, fill)
-    s.validate_merge(case.jobs, case.extents, case.T, bpc, case.src_bpc, case.n_flags)
+    s.validate_jobs(case.jobs, case.extents, case.T, bpc, case.n_flags, case.src_bpc, merge=True)
     assert len(case.jobs) == 11 and sum(j.fresh for j in case.jobs) == 3 and sum(j.dst == "window" for j in case.jobs) == 4
     bufs, flags = case.want()
     assert flags.tolist() == [0, 1, 1, 1, 0, 1, 1]                 # the negated tile and the -0.0 (fill) tile come out empty
@@ -128,17 +128,17 @@ def test_merge_case_tables_do_what_the_gpu_test_assumes(op, bpc, fill):
 
 
 # ------------------------------------------------------------------------------------------------ the validator
-def test_validate_merge_refuses_each_class_of_bad_table_and_names_the_job():
+def test_validate_jobs_refuses_each_class_of_bad_table_and_names_the_job():
     s = scroll()
     case = mref.MergeCase("ADD_F64", 4, 40, 0)
     jobs, ext, n = case.jobs, case.extents, case.n_flags
-    s.validate_merge(jobs, ext, 4, 40, None, n)
+    s.validate_jobs(jobs, ext, 4, 40, n, merge=True)
 
     def refused(k, match, src_bpc=None, **kw):
         bad = list(jobs)
         bad[k] = jobs[k]._replace(**kw)
         with pytest.raises(ValueError, match=match):
-            s.validate_merge(bad, ext, 4, 40, src_bpc, n)
+            s.validate_jobs(bad, ext, 4, 40, n, src_bpc, merge=True)
     row = case.Wm * 40
     refused(2, "merge job 2: dst bytes .* leave buffer 'window'", dst_off=(case.Hm - 4 + 1) * row)         # out of range
     refused(9, "merge job 9: src bytes .* leave buffer 'stage'", src_off=ext["stage"][1] - 4 * 4 * 40 + 16)
@@ -153,24 +153,24 @@ def test_validate_merge_refuses_each_class_of_bad_table_and_names_the_job():
     refused(4, "merge job 4: flag %d of %d" % (n, n), flag=n)
     refused(4, "merge job 4 has no source", src=None)
     refused(4, "unknown buffer", dst=("chunk", 9))
-    # in-place read and write of its own destination is the merge: validate_jobs forbids what this allows
+    # in-place read and write of its own destination is the merge, done by the kernel: no src names a destination, as in a copy table
     assert all(j.src != j.dst for j in jobs)
     # the float32 source of the exchange form: rows of half the bytes, so a source that fits as float32 overruns as float64
     half = mref.MergeCase("ADD_F32_TO_F64", 4, 40, 0)
-    s.validate_merge(half.jobs, half.extents, 4, 40, 20, n)
+    s.validate_jobs(half.jobs, half.extents, 4, 40, n, 20, merge=True)
     with pytest.raises(ValueError, match="merge job 0: src pitch 80 is misaligned or shorter than a tile row of 160"):
-        s.validate_merge(half.jobs, half.extents, 4, 40, None, n)          # read as full rows, the half rows are too close
+        s.validate_jobs(half.jobs, half.extents, 4, 40, n, merge=True)             # read as full rows, the half rows are too close
     last = max(range(len(half.jobs)), key=lambda k: half.jobs[k].src_off)
     bad = list(half.jobs)
     bad[last] = half.jobs[last]._replace(src_off=half.jobs[last].src_off + 16)
     with pytest.raises(ValueError, match="merge job %d: src bytes .* leave buffer 'stage'" % last):
-        s.validate_merge(bad, half.extents, 4, 40, 20, n)                  # 16 bytes past the end of the half-row tiles
+        s.validate_jobs(bad, half.extents, 4, 40, n, 20, merge=True)         # 16 bytes past the end of the half-row tiles
     with pytest.raises(ValueError, match="source of 12 bytes"):
-        s.validate_merge(half.jobs, half.extents, 4, 40, 12, n)
+        s.validate_jobs(half.jobs, half.extents, 4, 40, n, 12, merge=True)
     with pytest.raises(ValueError, match="bytes_per_cell"):
-        s.validate_merge(jobs, ext, 4, 6, None, n)
-    rec = np.zeros(len(jobs), dtype=s.MERGE_DTYPE)
-    assert s.encode_merge(jobs, ext, rec) == len(jobs) and rec["fresh"].tolist() == [j.fresh for j in jobs]
+        s.validate_jobs(jobs, ext, 4, 6, n, merge=True)
+    rec = np.zeros(len(jobs), dtype=s.JOB_DTYPE)
+    assert s.encode_jobs(jobs, ext, rec) == len(jobs) and rec["fresh"].tolist() == [j.fresh for j in jobs]
     assert rec["dst"][4] == ext[jobs[4].dst][0] + jobs[4].dst_off and rec["src"][4] == ext["stage"][0] + jobs[4].src_off
 
 
@@ -216,7 +216,7 @@ def test_tile_merge_argument_errors_do_not_need_a_gpu():
     from vision_semantic_segmentation_amd import _lib
     s = scroll()
     L = _lib.lib()
-    assert s.MERGE_DTYPE.itemsize == 40 and s.MERGE_DTYPE.fields["fresh"][1] == 36
+    assert s.JOB_DTYPE.itemsize == 40 and s.JOB_DTYPE.fields["fresh"][1] == 36
     assert [_lib.AVL_MERGE_ADD_F64, _lib.AVL_MERGE_ADD_F32, _lib.AVL_MERGE_ADD_F32_TO_F64, _lib.AVL_MERGE_ADD_I64, _lib.AVL_MERGE_ADD_I32,
             _lib.AVL_MERGE_MIN_I32, _lib.AVL_MERGE_MAX_I32] == [mref.OPS[k] for k in ("ADD_F64", "ADD_F32", "ADD_F32_TO_F64", "ADD_I64", "ADD_I32", "MIN_I32", "MAX_I32")]
     jobs = (C.c_uint64 * 10)()

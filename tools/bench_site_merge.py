@@ -129,9 +129,9 @@ def ready_table(store, l, coords, src, src_bpc, slabs):
             entries.append((t, k, "fresh", slabs[t], k))
     jobs = S.merge_jobs(entries, T, store.Wm, L.bpc, store.chunk_tiles, (a, b), src_bpc)
     buffers = store._buffers(L, {"window": store._extent(L.get()), "stage": store._extent(src)})
-    S.validate_merge(jobs, buffers, T, L.bpc, src_bpc, len(coords))
-    rec = np.zeros(len(jobs), dtype=S.MERGE_DTYPE)
-    S.encode_merge(jobs, buffers, rec)
+    S.validate_jobs(jobs, buffers, T, L.bpc, len(coords), src_bpc, merge=True)
+    rec = np.zeros(len(jobs), dtype=S.JOB_DTYPE)
+    S.encode_jobs(jobs, buffers, rec)
     return torch.from_numpy(rec.view(np.uint8)).to(dev), jobs
 
 

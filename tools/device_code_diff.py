@@ -1,13 +1,14 @@
 """Did the device code of libavl_hip.so move between two builds?
 
-    python tools/device_code_diff.py OLD.so NEW.so
+    python tools/device_code_diff.py [--rename OLD=NEW ...] OLD.so NEW.so
 
 For every kernel of the two libraries (tools/kernel_notes.py unbundles their gfx950 code objects) it compares the resource notes
 (registers, spills, LDS and scratch sizes) and the disassembled instruction stream.  Kernels of an anonymous namespace carry a hash
 of their compilation unit in the symbol name, which changes with any edit of the source file: it is cut out before names are
 compared.  Prints the kernels that differ or exist on one side only, and says whether the kernels lie in the same order in their
 code objects (same order and same code: same addresses); the exit status is 1 if anything differs.  A refactor of host code must end
-with "0 differ".
+with "0 differ".  --rename OLD=NEW replaces OLD by NEW in every symbol first, for a refactor that renames a kernel's parameter type
+(mangled names carry the length, 7old_job=7new_job; the notes' names are demangled, old_job=new_job: give both, the longer first).
 """
 import re
 import sys
@@ -15,8 +16,13 @@ import sys
 import kernel_notes as kn
 
 
+RENAMES = []          # (old, new) of --rename
+
+
 def _plain(symbol):
-    """a symbol without its compilation-unit hash (_GLOBAL__N__<hash>_<file> in mangled names)"""
+    """a symbol without its compilation-unit hash (_GLOBAL__N__<hash>_<file> in mangled names), the --rename pairs applied"""
+    for old, new in RENAMES:
+        symbol = symbol.replace(old, new)
     return re.sub(r"_GLOBAL__N__[0-9a-f]+_", "_GLOBAL__N__", symbol)
 
 
@@ -24,10 +30,13 @@ def device_code(lib):
     """({kernel name: notes}, {symbol: instructions}) of `lib`, names and instruction operands free of the unit hash.  "..." is how
     llvm-objdump prints the zero padding behind the last kernel of a code object (whichever kernel that is): not an instruction"""
     code = {_plain(sym): [_plain(line) for line in ins if line != "..."] for sym, ins in kn.disassembly(lib, "").items()}
-    return kn.kernel_notes(lib), code
+    return {_plain(name): notes for name, notes in kn.kernel_notes(lib).items()}, code
 
 
 def main():
+    while len(sys.argv) > 2 and sys.argv[1] == "--rename":
+        RENAMES.append(tuple(sys.argv[2].split("=", 1)))
+        del sys.argv[1:3]
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     (notes_a, code_a), (notes_b, code_b) = device_code(sys.argv[1]), device_code(sys.argv[2])

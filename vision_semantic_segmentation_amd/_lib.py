@@ -78,7 +78,7 @@ class AvlHeight(C.Structure):
 class AvlTileJob(C.Structure):
     """struct avl_tile_job of include/avl_hip.h"""
     _fields_ = [
-        ("src", C.c_void_p), ("src_pitch", C.c_int64), ("dst", C.c_void_p), ("dst_pitch", C.c_int64), ("flag", C.c_int32), ("pad", C.c_int32),
+        ("src", C.c_void_p), ("src_pitch", C.c_int64), ("dst", C.c_void_p), ("dst_pitch", C.c_int64), ("flag", C.c_int32), ("fresh", C.c_int32),
     ]
 
 

@@ -14,16 +14,11 @@
 //                 never alias (the window is double-buffered).
 //
 // The kernel does no arithmetic on the payload: a tile arrives byte for byte, a -0.0 is a non-fill word like any other.
-#include "avl_common.h"
-
-#include <cstdint>
+#include "avl_tile_table.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTargetWorkgroups = 2048;                  // a one-tile-row scroll (20 jobs) is split until the machine is full
-constexpr int kMaxBytesPerCell = 128;
+using namespace avl_tile_table;
 
 __global__ void __launch_bounds__(kBlock) k_tile_copy(const avl_tile_job* __restrict__ jobs, int n_jobs, int split, int rows, int row_vecs,
                                                       uint32_t fill, int32_t* __restrict__ flags, int n_flags) {
@@ -45,7 +40,7 @@ __global__ void __launch_bounds__(kBlock) k_tile_copy(const avl_tile_job* __rest
                 uint4 v = fill4;
                 if (s != nullptr) {
                     v = s[c];
-                    differs |= (v.x != fill) | (v.y != fill) | (v.z != fill) | (v.w != fill);
+                    differs |= (v.x != fill) | (v.y != fill) | (v.z != fill) | (v.w != fill);   // differs_from, spelled out: the call swaps two ORs' operands
                 }
                 d[c] = v;
             }
@@ -63,23 +58,9 @@ extern "C" {
 
 int avl_tile_copy(const avl_tile_job* jobs_dev, int n_jobs, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags, int n_flags,
                   void* stream) {
-    AVL_REQUIRE(n_jobs >= 0 && n_jobs <= (1 << 20), "avl_tile_copy: n_jobs = %d (0 .. 2^20)", n_jobs);
-    AVL_REQUIRE(n_flags >= 0, "avl_tile_copy: n_flags = %d", n_flags);
-    AVL_REQUIRE(tile_cells >= 1 && tile_cells <= (1 << 14), "avl_tile_copy: tile_cells = %d (1 .. 16384)", tile_cells);
-    AVL_REQUIRE(bytes_per_cell >= 4 && bytes_per_cell <= kMaxBytesPerCell && bytes_per_cell % 4 == 0,
-                "avl_tile_copy: bytes_per_cell = %d (a multiple of 4, 4 .. %d)", bytes_per_cell, kMaxBytesPerCell);
-    AVL_REQUIRE((tile_cells * bytes_per_cell) % 16 == 0, "avl_tile_copy: a tile row of %d cells of %d bytes is no multiple of 16 bytes",
-                tile_cells, bytes_per_cell);
-    AVL_REQUIRE(n_jobs == 0 || jobs_dev != nullptr, "avl_tile_copy: jobs_dev is NULL for %d jobs", n_jobs);
-    AVL_REQUIRE(n_flags == 0 || flags != nullptr, "avl_tile_copy: flags is NULL for %d flags", n_flags);
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(jobs_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(flags) & 3) == 0,
-                "avl_tile_copy: jobs_dev or flags is misaligned");
-    if (n_flags > 0) AVL_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)n_flags * sizeof(int32_t), avl::as_stream(stream)));
-    if (n_jobs == 0) return AVL_OK;
-    // workgroups per tile: enough that few jobs still fill the machine, never more than the tile has groups of kWaves rows
-    int split = (kTargetWorkgroups + n_jobs - 1) / n_jobs;
-    const int max_split = (tile_cells + kWaves - 1) / kWaves;
-    split = split < 1 ? 1 : (split > max_split ? max_split : split);
+    int split;
+    const int rc = avl_tile_table::begin("avl_tile_copy", jobs_dev, n_jobs, tile_cells, bytes_per_cell, flags, n_flags, avl::as_stream(stream), &split);
+    if (rc != AVL_OK || split == 0) return rc;
     const int row_vecs = tile_cells * bytes_per_cell / 16;
     hipLaunchKernelGGL(k_tile_copy, dim3((unsigned)n_jobs * (unsigned)split), dim3(kBlock), 0, avl::as_stream(stream), jobs_dev, n_jobs, split,
                        tile_cells, row_vecs, fill, flags, n_flags);

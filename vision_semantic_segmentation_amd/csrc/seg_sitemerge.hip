@@ -1,8 +1,8 @@
-// Merging sites: a table of merge jobs, executed by one kernel (not in the reference: it has one grid and one run).  A frame's
+// Merging sites: a table of tile jobs, executed by one kernel (not in the reference: it has one grid and one run).  A frame's
 // contribution never reads the grid, so the sum of two sites is the site of all their frames; what the scrolling grid
 // lacked is an operation that accumulates a tile into a tile where the tiles live -- the window buffer, a slab of the store -- instead
 // of assembling rectangles (vision_semantic_segmentation_amd/scroll.py builds and validates the tables; the rule: struct
-// avl_merge_job in include/avl_hip.h).
+// avl_tile_job in include/avl_hip.h).
 //
 //   k_tile_merge<OP>   one job = one destination tile of T rows, split over `split` workgroups by rows, shaped like k_tile_copy: a wave
 //                      takes one tile row at a time and its lanes walk it contiguously, 16 bytes per lane and memory instruction; the
@@ -15,16 +15,11 @@
 //
 // Every op is one IEEE or two's-complement operation per element; the translation unit is built with -ffp-contract=off like the other
 // map kernels, although an add alone leaves nothing to contract.
-#include "avl_common.h"
-
-#include <cstdint>
+#include "avl_tile_table.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTargetWorkgroups = 2048;                  // as k_tile_copy: few jobs are split until the machine is full
-constexpr int kMaxBytesPerCell = 128;
+using namespace avl_tile_table;
 
 __device__ __forceinline__ uint2 bits_of(double v) { return __builtin_bit_cast(uint2, v); }
 __device__ __forceinline__ double f64_of(uint32_t lo, uint32_t hi) { return __builtin_bit_cast(double, make_uint2(lo, hi)); }
@@ -66,16 +61,14 @@ __device__ __forceinline__ uint4 widen_vec(uint4 a, uint32_t s0, uint32_t s1) {
     return make_uint4(lo.x, lo.y, hi.x, hi.y);
 }
 
-__device__ __forceinline__ bool differs_from(uint4 v, uint32_t fill) { return (v.x != fill) | (v.y != fill) | (v.z != fill) | (v.w != fill); }
-
 // row_vecs: the 16-byte vectors of a SOURCE row (for AVL_MERGE_ADD_F32_TO_F64 the destination row has twice as many)
 template <int OP>
-__global__ void __launch_bounds__(kBlock) k_tile_merge(const avl_merge_job* __restrict__ jobs, int n_jobs, int split, int rows, int row_vecs,
+__global__ void __launch_bounds__(kBlock) k_tile_merge(const avl_tile_job* __restrict__ jobs, int n_jobs, int split, int rows, int row_vecs,
                                                        uint32_t fill, int32_t* __restrict__ flags, int n_flags) {
     const int job_idx = (int)(blockIdx.x / (unsigned)split);
     const int part = (int)(blockIdx.x % (unsigned)split);
     if (job_idx >= n_jobs) return;
-    const avl_merge_job job = jobs[job_idx];
+    const avl_tile_job job = jobs[job_idx];
     if (job.src == nullptr || job.dst == nullptr) return;                     // no such job in a validated table; wave-uniform
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const char* src = static_cast<const char*>(job.src);
@@ -119,7 +112,7 @@ __global__ void __launch_bounds__(kBlock) k_tile_merge(const avl_merge_job* __re
 }
 
 template <int OP>
-void launch(const avl_merge_job* jobs_dev, int n_jobs, int split, int rows, int row_vecs, uint32_t fill, int32_t* flags, int n_flags,
+void launch(const avl_tile_job* jobs_dev, int n_jobs, int split, int rows, int row_vecs, uint32_t fill, int32_t* flags, int n_flags,
             hipStream_t stream) {
     hipLaunchKernelGGL(k_tile_merge<OP>, dim3((unsigned)n_jobs * (unsigned)split), dim3(kBlock), 0, stream, jobs_dev, n_jobs, split, rows,
                        row_vecs, fill, flags, n_flags);
@@ -129,35 +122,24 @@ void launch(const avl_merge_job* jobs_dev, int n_jobs, int split, int rows, int 
 
 extern "C" {
 
-int avl_tile_merge(const avl_merge_job* jobs_dev, int n_jobs, int op, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags,
+int avl_tile_merge(const avl_tile_job* jobs_dev, int n_jobs, int op, int tile_cells, int bytes_per_cell, uint32_t fill, int32_t* flags,
                    int n_flags, void* stream) {
-    AVL_REQUIRE(n_jobs >= 0 && n_jobs <= (1 << 20), "avl_tile_merge: n_jobs = %d (0 .. 2^20)", n_jobs);
-    AVL_REQUIRE(n_flags >= 0, "avl_tile_merge: n_flags = %d", n_flags);
+    // this call's own conditions first, on the raw arguments: begin() zeroes the flags, and a refused call does no GPU work.  A
+    // destination row that is no multiple of 16 bytes is begin()'s to name.
     AVL_REQUIRE(op >= AVL_MERGE_ADD_F64 && op <= AVL_MERGE_MAX_I32, "avl_tile_merge: op = %d (AVL_MERGE_ADD_F64 .. AVL_MERGE_MAX_I32)", op);
-    AVL_REQUIRE(tile_cells >= 1 && tile_cells <= (1 << 14), "avl_tile_merge: tile_cells = %d (1 .. 16384)", tile_cells);
-    AVL_REQUIRE(bytes_per_cell >= 4 && bytes_per_cell <= kMaxBytesPerCell && bytes_per_cell % 4 == 0,
-                "avl_tile_merge: bytes_per_cell = %d (a multiple of 4, 4 .. %d)", bytes_per_cell, kMaxBytesPerCell);
     const bool wide = op == AVL_MERGE_ADD_F64 || op == AVL_MERGE_ADD_I64 || op == AVL_MERGE_ADD_F32_TO_F64;
     AVL_REQUIRE(!wide || bytes_per_cell % 8 == 0, "avl_tile_merge: bytes_per_cell = %d is no multiple of 8, the element of op %d",
                 bytes_per_cell, op);
-    const int dst_row = tile_cells * bytes_per_cell;
-    const int src_row = op == AVL_MERGE_ADD_F32_TO_F64 ? dst_row / 2 : dst_row;
-    AVL_REQUIRE(dst_row % 16 == 0, "avl_tile_merge: a destination tile row of %d cells of %d bytes is no multiple of 16 bytes", tile_cells,
-                bytes_per_cell);
-    AVL_REQUIRE(src_row % 16 == 0, "avl_tile_merge: a float32 source tile row of %d bytes (%d cells of %d / 2 bytes) is no multiple of 16 bytes",
-                src_row, tile_cells, bytes_per_cell);
-    AVL_REQUIRE(n_jobs == 0 || jobs_dev != nullptr, "avl_tile_merge: jobs_dev is NULL for %d jobs", n_jobs);
-    AVL_REQUIRE(n_flags == 0 || flags != nullptr, "avl_tile_merge: flags is NULL for %d flags", n_flags);
-    AVL_REQUIRE((reinterpret_cast<uintptr_t>(jobs_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(flags) & 3) == 0,
-                "avl_tile_merge: jobs_dev or flags is misaligned");
+    const int64_t dst_row = (int64_t)tile_cells * bytes_per_cell;
+    const int64_t src_row = op == AVL_MERGE_ADD_F32_TO_F64 ? dst_row / 2 : dst_row;
+    AVL_REQUIRE(dst_row % 16 != 0 || src_row % 16 == 0,
+                "avl_tile_merge: a float32 source tile row of %d bytes (%d cells of %d / 2 bytes) is no multiple of 16 bytes", (int)src_row,
+                tile_cells, bytes_per_cell);
     hipStream_t st = avl::as_stream(stream);
-    if (n_flags > 0) AVL_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)n_flags * sizeof(int32_t), st));
-    if (n_jobs == 0) return AVL_OK;
-    // workgroups per tile: enough that few jobs still fill the machine, never more than the tile has groups of kWaves rows
-    int split = (kTargetWorkgroups + n_jobs - 1) / n_jobs;
-    const int max_split = (tile_cells + kWaves - 1) / kWaves;
-    split = split < 1 ? 1 : (split > max_split ? max_split : split);
-    const int row_vecs = src_row / 16;
+    int split;
+    const int rc = avl_tile_table::begin("avl_tile_merge", jobs_dev, n_jobs, tile_cells, bytes_per_cell, flags, n_flags, st, &split);
+    if (rc != AVL_OK || split == 0) return rc;
+    const int row_vecs = (int)(src_row / 16);
     switch (op) {
         case AVL_MERGE_ADD_F64: launch<AVL_MERGE_ADD_F64>(jobs_dev, n_jobs, split, tile_cells, row_vecs, fill, flags, n_flags, st); break;
         case AVL_MERGE_ADD_F32: launch<AVL_MERGE_ADD_F32>(jobs_dev, n_jobs, split, tile_cells, row_vecs, fill, flags, n_flags, st); break;

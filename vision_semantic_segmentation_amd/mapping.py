@@ -1690,7 +1690,7 @@ class SemanticMapping(object):
     def merge_site(self, path_or_arrays, stream=None):
         """Another run's or another vehicle's site -- a save_site file, or the dict scroll.pack_site makes -- SUMMED into this map:
         a frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.  Per cell the result
-        is own (+) theirs by the rule of struct avl_merge_job (include/avl_hip.h): one IEEE add for the map; with MAPPING.ELEVATION
+        is own (+) theirs by the rule of avl_tile_merge (include/avl_hip.h): one IEEE add for the map; with MAPPING.ELEVATION
         its sum and count add (the int32 count WRAPS past 2^31 - 1), its minimum and maximum take the minimum and maximum.  Merging
         is a left fold: merge_site(B); merge_site(C) gives (own + B) + C.  A tile of the file inside the current window is summed
         into the live window buffer in place, a stored one into its slab, a tile this map does not have gets a new slab; nothing is

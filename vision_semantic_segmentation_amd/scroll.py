@@ -27,9 +27,10 @@ csrc/seg_sitefinish.hip), which is the overview's table plus a NULL record for e
 record's eight neighbour indices (finish_sources), validated on the host (validate_finish) and launched once.
 
 MERGING SITES (TileStore.merge_site, TileStore.global_site) sums another run's or another rank's tiles into the tiles where they live
--- the live window buffer, a slab of the store, a new slab -- by a table of merge jobs (struct avl_merge_job, k_tile_merge of
-csrc/seg_sitemerge.hip: result = acc (+) src, in place), built by merge_jobs, validated on the host (validate_merge) and launched once
-per layer.  A frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.
+-- the live window buffer, a slab of the store, a new slab -- by a table of the same tile jobs, read by another kernel (k_tile_merge of
+csrc/seg_sitemerge.hip: result = acc (+) src, in place; a job's ``fresh`` word says that acc is the fill word), built by merge_jobs
+and validated, encoded, uploaded and launched once per layer by the code that serves the copy tables (validate_jobs(merge=True),
+encode_jobs, TileStore._run).  A frame's contribution never reads the grid, so the sum of two sites is the site of all their frames.
 
 THE STORE.  One pool per layer (the map; with MAPPING.ELEVATION its four arrays), made of chunks of POOL_CHUNK_TILES slabs of
 T * T * bytes_per_cell bytes; a chunk is a CUDA tensor.  The pool grows by whole chunks, so a stored tile never moves and jobs carry
@@ -45,11 +46,12 @@ from .mapping import PCD_ORIGIN_OFFSET            # mapping.py imports this modu
 
 MAX_ORIGIN = 1 << 30
 
-Job = collections.namedtuple("Job", "src src_off src_pitch dst dst_off dst_pitch flag")
-"""One tile job in host form: ``src`` / ``dst`` name a buffer ("old", "new", "out", ("chunk", k), ...; src None = fill), the offsets
-and pitches are bytes.  encode_jobs turns it into struct avl_tile_job with the buffers' device addresses."""
+Job = collections.namedtuple("Job", "src src_off src_pitch dst dst_off dst_pitch flag fresh", defaults=(0,))
+"""One tile job in host form: ``src`` / ``dst`` name a buffer ("old", "new", "out", ("chunk", k), ...; src None = fill, in a copy table
+only), the offsets and pitches are bytes.  ``fresh`` is read by a merge alone: true when the accumulator is the layer's fill word and
+the destination is not read.  encode_jobs turns it into struct avl_tile_job with the buffers' device addresses."""
 
-JOB_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("dst", "<u8"), ("dst_pitch", "<i8"), ("flag", "<i4"), ("pad", "<i4")])
+JOB_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("dst", "<u8"), ("dst_pitch", "<i8"), ("flag", "<i4"), ("fresh", "<i4")])
 
 Layer = collections.namedtuple("Layer", "name bpc fill")
 ELEVATION_LAYERS = (Layer("elev_sum", 8, 0), Layer("elev_cnt", 4, 0), Layer("elev_min", 4, 0x7FFFFFFF), Layer("elev_max", 4, 0x80000000))
@@ -181,6 +183,11 @@ def scroll_jobs(plan, old_tile, new_tile, T, Wm, bpc, chunk_tiles, slab_of_leavi
     return jobs
 
 
+def fill_int32(fill):
+    """a layer's fill word as the int32 of the same bits, for tensors viewed as torch.int32"""
+    return fill - (1 << 32) if fill >= (1 << 31) else fill
+
+
 def tile_row_bytes(what, T, bpc):
     """T * bpc, the bytes of a tile row of a table of ``what``; ValueError unless the tile kernels can move such rows"""
     row = T * bpc
@@ -189,66 +196,71 @@ def tile_row_bytes(what, T, bpc):
     return row
 
 
-def validate_jobs(jobs, buffers, T, bpc, n_flags=None):
-    """ValueError unless every job of the table is safe to launch.  ``buffers``: {key: (device address, bytes)}.  Every source and
-    destination tile -- T rows of T * bpc bytes, ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a
-    multiple of 16; a pitch is at least a row; no destination tile appears twice and no job reads a buffer range another writes
-    (checked per buffer: a buffer is read or written, never both, except distinct slabs of a chunk); a flag is below ``n_flags``."""
-    row = tile_row_bytes("tile jobs", T, bpc)
-    written, read = set(), set()
-    for k, j in enumerate(jobs):
-        for what, key, off, pitch in (("src", j.src, j.src_off, j.src_pitch), ("dst", j.dst, j.dst_off, j.dst_pitch)):
+def validate_jobs(jobs, buffers, T, bpc, n_flags=None, src_bpc=None, merge=False):
+    """ValueError, naming the job, unless every job of the table is safe to launch: a copy table (avl_tile_copy), with ``merge`` a
+    merge table (avl_tile_merge).  ``buffers``: {key: (device address, bytes)}.  Every source and destination tile -- T rows,
+    ``pitch`` apart -- lies inside the buffer it names; every address and pitch is a multiple of 16 and a pitch is at least a row; no
+    destination tile is named twice; no job's source is any job's destination, and a buffer is read or written, never both, except
+    distinct slabs of a chunk; a flag is below ``n_flags``.  A row is T * bpc bytes.  The two kinds differ in the source alone: a
+    copy job without one fills its destination, a merge job must have one; and a merge table's source rows may be T * ``src_bpc``
+    bytes with src_bpc = bpc // 2, the float32 source of the exchange form (None = bpc; a copy table takes None only).  In both, the
+    only range a job may read and write is a merge job's own destination, which the kernel reads by itself and no ``src`` names."""
+    what = "merge job" if merge else "tile job"
+    dst_row = tile_row_bytes(what + "s", T, bpc)
+    if src_bpc is not None and not merge:
+        raise ValueError("tile jobs: a source of %d bytes per cell; only a merge table has source rows of their own" % src_bpc)
+    src_bpc = bpc if src_bpc is None else src_bpc
+    if src_bpc not in (bpc, bpc // 2) or (T * src_bpc) % 16 != 0:
+        raise ValueError("merge jobs: a source of %d bytes per cell for a destination of %d, T = %d (the same or half of it, rows a "
+                         "multiple of 16 bytes)" % (src_bpc, bpc, T))
+    src_row, last = T * src_bpc, T - 1
+    written, read = {}, {}                                                 # {(key, off): the first job that names it}
+    # this loop is most of a scroll's host time: what a side of a job needs is bound once, (name, row bytes, first namer of a place)
+    extent_of = buffers.get
+    src_side, dst_side = ("src", src_row, read.setdefault), ("dst", dst_row, written.setdefault)
+    for k, (src, src_off, src_pitch, dst, dst_off, dst_pitch, flag, _) in enumerate(jobs):
+        for (side, row, first), key, off, pitch in ((src_side, src, src_off, src_pitch), (dst_side, dst, dst_off, dst_pitch)):
             if key is None:
-                if what == "dst":
-                    raise ValueError("tile job %d has no destination" % k)
-                continue
-            if key not in buffers:
-                raise ValueError("tile job %d: %s names the unknown buffer %r" % (k, what, key))
-            base, nbytes = buffers[key]
-            if pitch % 16 != 0 or pitch < row:
-                raise ValueError("tile job %d: %s pitch %d is misaligned or shorter than a tile row of %d bytes" % (k, what, pitch, row))
-            if (base + off) % 16 != 0:
-                raise ValueError("tile job %d: %s address %d + %d is not 16-byte aligned" % (k, what, base, off))
-            end = off + (T - 1) * pitch + row
+                if side == "src" and not merge:
+                    continue                                               # a fill
+                raise ValueError("%s %d has no %s" % (what, k, "source" if side == "src" else "destination"))
+            extent = extent_of(key)
+            if extent is None:
+                raise ValueError("%s %d: %s names the unknown buffer %r" % (what, k, side, key))
+            base, nbytes = extent
+            if (pitch | (base + off)) & 15 or pitch < row:                 # one test for both alignments
+                if pitch % 16 != 0 or pitch < row:
+                    raise ValueError("%s %d: %s pitch %d is misaligned or shorter than a tile row of %d bytes" % (what, k, side, pitch, row))
+                raise ValueError("%s %d: %s address %d + %d is not 16-byte aligned" % (what, k, side, base, off))
+            end = off + last * pitch + row
             if off < 0 or end > nbytes:
-                raise ValueError("tile job %d: %s bytes %d .. %d leave buffer %r of %d bytes" % (k, what, off, end, key, nbytes))
-            if what == "dst":
-                if (key, off) in written:
-                    raise ValueError("tile job %d: destination tile %r + %d appears twice" % (k, key, off))
-                written.add((key, off))
-            else:
-                read.add((key, off))
-        if n_flags is not None and j.flag >= n_flags:
-            raise ValueError("tile job %d: flag %d of %d" % (k, j.flag, n_flags))
-    both = written & read
+                raise ValueError("%s %d: %s bytes %d .. %d leave buffer %r of %d bytes" % (what, k, side, off, end, key, nbytes))
+            if first((key, off), k) != k and side == "dst":
+                raise ValueError("%s %d: destination tile %r + %d appears twice (job %d)" % (what, k, key, off, written[(key, off)]))
+        if n_flags is not None and flag >= n_flags:
+            raise ValueError("%s %d: flag %d of %d" % (what, k, flag, n_flags))
+    both = written.keys() & read.keys()
     if both:
-        raise ValueError("tile jobs: %d tiles are read and written in one table, the first %r" % (len(both), sorted(both)[0]))
-    wkeys = {k for k, _ in written}
-    for key in {k for k, _ in read} & wkeys:
+        place = min(both, key=read.get)
+        raise ValueError("%s %d: its source %r + %d is the destination of job %d: read and written in one table"
+                         % (what, read[place], place[0], place[1], written[place]))
+    for key in {key for key, _ in read} & {key for key, _ in written}:
         if not (isinstance(key, tuple) and key[0] == "chunk"):
-            raise ValueError("tile jobs: buffer %r is read and written in one table" % (key,))
+            raise ValueError("%s %d: its source buffer %r is written in the same table"
+                             % (what, min(k for (other, _), k in read.items() if other == key), key))
 
 
 def encode_jobs(jobs, buffers, out):
     """``jobs`` as struct avl_tile_job records into the structured array ``out`` (JOB_DTYPE, at least len(jobs) long)."""
     n = len(jobs)
-    base = {k: v[0] for k, v in buffers.items()}
-    out["src"][:n] = [0 if j.src is None else base[j.src] + j.src_off for j in jobs]
-    out["src_pitch"][:n] = [j.src_pitch for j in jobs]
-    out["dst"][:n] = [base[j.dst] + j.dst_off for j in jobs]
-    out["dst_pitch"][:n] = [j.dst_pitch for j in jobs]
-    out["flag"][:n] = [j.flag for j in jobs]
-    out["pad"][:n] = 0
+    if n:
+        base = {key: extent[0] for key, extent in buffers.items()}
+        out[:n] = [(0 if src is None else base[src] + src_off, src_pitch, base[dst] + dst_off, dst_pitch, flag, fresh)
+                   for src, src_off, src_pitch, dst, dst_off, dst_pitch, flag, fresh in jobs]       # one pass, one assignment of whole records
     return n
 
 
 # ------------------------------------------------------------------------------------------------ merge tables
-MergeJob = collections.namedtuple("MergeJob", "src src_off src_pitch dst dst_off dst_pitch flag fresh")
-"""One merge job in host form (struct avl_merge_job of include/avl_hip.h): Job's fields -- a source is never None -- and ``fresh``,
-true when the accumulator is the layer's fill word and the destination is not read."""
-
-MERGE_DTYPE = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("dst", "<u8"), ("dst_pitch", "<i8"), ("flag", "<i4"), ("fresh", "<i4")])
-
 SiteMerge = collections.namedtuple("SiteMerge", "window store added freed")
 """What merge_site returns, in tiles: summed into the window in place, summed into slabs of the store, added as new slabs, and slabs
 (old or new) that went back to the free list because the result is empty in every layer."""
@@ -281,73 +293,13 @@ def merge_jobs(entries, T, Wm, bpc, chunk_tiles, origin_tile, src_bpc=None, src=
     for t, k, kind, slab, flag in entries:
         if kind == "window":
             do, dp = window_ref(t, origin_tile, T, Wm, bpc)
-            jobs.append(MergeJob(src, k * T * T * src_bpc, T * src_bpc, "window", do, dp, -1, 0))
+            jobs.append(Job(src, k * T * T * src_bpc, T * src_bpc, "window", do, dp, -1, 0))
         elif kind in ("store", "fresh"):
             dk, do, dp = slab_ref(slab, chunk_tiles, T, bpc)
-            jobs.append(MergeJob(src, k * T * T * src_bpc, T * src_bpc, dk, do, dp, flag, int(kind == "fresh")))
+            jobs.append(Job(src, k * T * T * src_bpc, T * src_bpc, dk, do, dp, flag, int(kind == "fresh")))
         else:
             raise ValueError("merge entry %r: kind %r" % (t, kind))
     return jobs
-
-
-def validate_merge(jobs, buffers, T, bpc, src_bpc=None, n_flags=None):
-    """ValueError, naming the job, unless every job of the merge table is safe to launch.  ``buffers``: {key: (device address,
-    bytes)}.  Every source tile -- T rows of T * src_bpc bytes (src_bpc None = bpc; bpc // 2: the float32 source of the exchange
-    form, half a destination row) -- and every destination tile -- T rows of T * bpc bytes -- lies inside the buffer it names; every
-    address and pitch is a multiple of 16 and a pitch is at least a row; no destination tile is named twice; no job's source is any
-    job's destination, and a buffer is read or written, never both, except distinct slabs of a chunk; a flag is below ``n_flags``.
-    What validate_jobs forbids and this allows is the merge itself: a job reads and writes its own destination in place."""
-    src_bpc = bpc if src_bpc is None else src_bpc
-    rows = {"dst": tile_row_bytes("merge jobs", T, bpc)}
-    if src_bpc not in (bpc, bpc // 2) or (T * src_bpc) % 16 != 0:
-        raise ValueError("merge jobs: a source of %d bytes per cell for a destination of %d, T = %d (the same or half of it, rows a "
-                         "multiple of 16 bytes)" % (src_bpc, bpc, T))
-    rows["src"] = T * src_bpc
-    written, read = {}, {}
-    for k, j in enumerate(jobs):
-        for what, key, off, pitch in (("src", j.src, j.src_off, j.src_pitch), ("dst", j.dst, j.dst_off, j.dst_pitch)):
-            row = rows[what]
-            if key is None:
-                raise ValueError("merge job %d has no %s" % (k, "source" if what == "src" else "destination"))
-            if key not in buffers:
-                raise ValueError("merge job %d: %s names the unknown buffer %r" % (k, what, key))
-            base, nbytes = buffers[key]
-            if pitch % 16 != 0 or pitch < row:
-                raise ValueError("merge job %d: %s pitch %d is misaligned or shorter than a tile row of %d bytes" % (k, what, pitch, row))
-            if (base + off) % 16 != 0:
-                raise ValueError("merge job %d: %s address %d + %d is not 16-byte aligned" % (k, what, base, off))
-            end = off + (T - 1) * pitch + row
-            if off < 0 or end > nbytes:
-                raise ValueError("merge job %d: %s bytes %d .. %d leave buffer %r of %d bytes" % (k, what, off, end, key, nbytes))
-            if what == "dst":
-                if (key, off) in written:
-                    raise ValueError("merge job %d: destination tile %r + %d appears twice (job %d)" % (k, key, off, written[(key, off)]))
-                written[(key, off)] = k
-            else:
-                read.setdefault((key, off), k)
-        if n_flags is not None and j.flag >= n_flags:
-            raise ValueError("merge job %d: flag %d of %d" % (k, j.flag, n_flags))
-    both = set(written) & set(read)
-    if both:
-        place = min(both, key=read.get)
-        raise ValueError("merge job %d: its source %r + %d is the destination of job %d" % (read[place], place[0], place[1], written[place]))
-    wkeys = {key for key, _ in written}
-    mixed = [k for (key, _), k in read.items() if key in wkeys and not (isinstance(key, tuple) and key[0] == "chunk")]
-    if mixed:
-        raise ValueError("merge job %d: its source buffer %r is written in the same table" % (min(mixed), jobs[min(mixed)].src))
-
-
-def encode_merge(jobs, buffers, out):
-    """``jobs`` as struct avl_merge_job records into the structured array ``out`` (MERGE_DTYPE, at least len(jobs) long)."""
-    n = len(jobs)
-    base = {k: v[0] for k, v in buffers.items()}
-    out["src"][:n] = [base[j.src] + j.src_off for j in jobs]
-    out["src_pitch"][:n] = [j.src_pitch for j in jobs]
-    out["dst"][:n] = [base[j.dst] + j.dst_off for j in jobs]
-    out["dst_pitch"][:n] = [j.dst_pitch for j in jobs]
-    out["flag"][:n] = [j.flag for j in jobs]
-    out["fresh"][:n] = [j.fresh for j in jobs]
-    return n
 
 
 # ------------------------------------------------------------------------------------------------ the overview's source table
@@ -526,14 +478,9 @@ def validate_finish(table, buffers, T, bpc, nh, nw):
 
 def encode_finish(table, buffers, out):
     """``table`` as struct avl_tile_fin records into the structured array ``out`` (FIN_DTYPE, at least len(table) long)."""
-    n = len(table)
+    n = encode_sources(table, list(buffers) + [(0, 0)], out)                        # buf -1, a NULL record: the appended address 0 ...
     if n:
-        base = np.array([b[0] for b in buffers] + [0], dtype=np.uint64)            # buf -1, a NULL record: the appended 0
-        has = table["buf"] >= 0
-        out["src"][:n] = np.where(has, base[table["buf"]] + table["off"].astype(np.uint64), np.uint64(0))
-        out["src_pitch"][:n] = table["pitch"]
-        out["row"][:n] = table["row"]
-        out["col"][:n] = table["col"]
+        out["src"][:n][table["buf"] < 0] = 0                                       # ... whatever its offset says
         out["nb"][:n] = table["nb"]
         out["pad"][:n] = 0
     return n
@@ -709,31 +656,37 @@ class TileStore(object):
             event.record(st)
 
     def _run(self, per_layer, st, n_flags=0):
-        """``per_layer``: [(layer, jobs, buffers)], all validated here, uploaded as one table through the ring and launched once per
-        layer on the torch stream ``st``; with ``n_flags`` every layer's flags go to flags_dev[l * n_flags ...] and their copy into
-        pinned memory is started, flags_event recorded behind it."""
+        """``per_layer``: [(layer, jobs, buffers)] for copy tables (avl_tile_copy), [(layer, jobs, buffers, op, src_bpc)] for merge
+        tables (avl_tile_merge), all validated here, uploaded as one table through the ring and launched once per layer on the torch
+        stream ``st``; with ``n_flags`` every layer's flags go to flags_dev[l * n_flags ...] and their copy into pinned memory is
+        started, flags_event recorded behind it."""
         import ctypes as C
         from . import _lib
-        for L, jobs, buffers in per_layer:
-            validate_jobs(jobs, buffers, self.T, L.bpc, n_flags)          # raises before anything is uploaded or launched
-        total = sum(len(jobs) for _, jobs, _ in per_layer)
+        per_layer = [e if len(e) == 5 else tuple(e) + (None, None) for e in per_layer]       # op None: a copy
+        for L, jobs, buffers, op, src_bpc in per_layer:                   # raises before anything is uploaded or launched
+            validate_jobs(jobs, buffers, self.T, L.bpc, n_flags, src_bpc, merge=op is not None)
+        total = sum(len(e[1]) for e in per_layer)
         nbytes = max(total, 1) * JOB_DTYPE.itemsize
         starts = []
 
         def fill(records):
             rec, at = records.view(JOB_DTYPE), 0
-            for L, jobs, buffers in per_layer:
+            for _, jobs, buffers, _, _ in per_layer:
                 starts.append(at)
                 at += encode_jobs(jobs, buffers, rec[at:])
         n_layers = len(per_layer)
         self._flags_room(n_layers * n_flags)
 
         def launch(table):
-            for l, (L, jobs, _) in enumerate(per_layer):
+            lib = _lib.lib()
+            for l, (L, jobs, _, op, _) in enumerate(per_layer):
                 flags = C.c_void_p(self.flags_dev.data_ptr() + 4 * l * n_flags) if n_flags else None
-                rc = _lib.lib().avl_tile_copy(C.c_void_p(table + starts[l] * JOB_DTYPE.itemsize), len(jobs), self.T, L.bpc,
-                                              L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
-                _lib.check(rc, "avl_tile_copy")
+                head = (C.c_void_p(table + starts[l] * JOB_DTYPE.itemsize), len(jobs))
+                tail = (self.T, L.bpc, L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
+                if op is None:
+                    _lib.check(lib.avl_tile_copy(*head, *tail), "avl_tile_copy")
+                else:
+                    _lib.check(lib.avl_tile_merge(*head, op, *tail), "avl_tile_merge")
         self._launch_table(st, nbytes, fill, launch)
         self._flags_home(st, n_layers * n_flags)
 
@@ -754,34 +707,6 @@ class TileStore(object):
             with self.torch.cuda.stream(st):
                 self.flags_host[:n].copy_(self.flags_dev[:n], non_blocking=True)
                 self.flags_event.record(st)
-
-    def _run_merge(self, per_layer, st, n_flags):
-        """``per_layer``: [(layer, op, src_bpc, jobs, buffers)] of MergeJob tables, all validated here (validate_merge), uploaded as
-        one table through the ring and launched once per layer (avl_tile_merge) on ``st``; the layers' result flags go where _run
-        puts its flags."""
-        import ctypes as C
-        from . import _lib
-        for L, op, src_bpc, jobs, buffers in per_layer:
-            validate_merge(jobs, buffers, self.T, L.bpc, src_bpc, n_flags)   # raises before anything is uploaded or launched
-        total = sum(len(jobs) for _, _, _, jobs, _ in per_layer)
-        starts = []
-
-        def fill(records):
-            rec, at = records.view(MERGE_DTYPE), 0
-            for _, _, _, jobs, buffers in per_layer:
-                starts.append(at)
-                at += encode_merge(jobs, buffers, rec[at:])
-        n_layers = len(per_layer)
-        self._flags_room(n_layers * n_flags)
-
-        def launch(table):
-            for l, (L, op, _, jobs, _) in enumerate(per_layer):
-                flags = C.c_void_p(self.flags_dev.data_ptr() + 4 * l * n_flags) if n_flags else None
-                rc = _lib.lib().avl_tile_merge(C.c_void_p(table + starts[l] * MERGE_DTYPE.itemsize), len(jobs), op, self.T, L.bpc,
-                                               L.fill, flags, n_flags, C.c_void_p(st.cuda_stream))
-                _lib.check(rc, "avl_tile_merge")
-        self._launch_table(st, max(total, 1) * MERGE_DTYPE.itemsize, fill, launch)
-        self._flags_home(st, n_layers * n_flags)
 
     # -------------------------------------------------------------------------------------------- the scroll
     def retire(self):
@@ -888,8 +813,7 @@ class TileStore(object):
             if not bits >> l & 1:
                 continue
             words = L.get().contiguous().view(torch.int32).view(self.Ht, T, self.Wt, T, L.bpc // 4)
-            fill = L.fill - (1 << 32) if L.fill >= (1 << 31) else L.fill
-            some = words.ne(fill).any(dim=4).any(dim=3).any(dim=1).to(torch.int64) << l
+            some = words.ne(fill_int32(L.fill)).any(dim=4).any(dim=3).any(dim=1).to(torch.int64) << l
             masks = some if masks is None else masks | some
         return masks.cpu().numpy()
 
@@ -910,17 +834,24 @@ class TileStore(object):
         tiles |= {t for t, m in self.nonempty.items() if m & bits}
         return sorted(tiles)
 
+    def _homes(self, tiles):
+        """where each tile of ``tiles`` lives: "window" (the window is valid and covers it), "store" (it has a slab) or None"""
+        a, b = self.origin[0] // self.T, self.origin[1] // self.T
+        a1, b1 = (a + self.Ht, b + self.Wt) if self.window_valid else (a, b)          # not valid: the window covers nothing
+        stored = self.directory
+        return ["window" if a <= t[0] < a1 and b <= t[1] < b1 else "store" if t in stored else None for t in tiles]
+
     def _gather_jobs(self, L, tiles, dst_ref):
-        """one job per tile of ``tiles`` from wherever the tile lives (window, store, nowhere = fill) to dst_ref(k) = (key, off, pitch)"""
+        """one job per tile of ``tiles`` from wherever the tile lives (_homes; nowhere = fill) to dst_ref(k) = (key, off, pitch)"""
         T = self.T
-        a, b = self.origin[0] // T, self.origin[1] // T
+        origin_tile = (self.origin[0] // T, self.origin[1] // T)
         jobs = []
-        for k, t in enumerate(tiles):
+        for k, (t, home) in enumerate(zip(tiles, self._homes(tiles))):
             dk, do, dp = dst_ref(k)
-            if self.window_valid and a <= t[0] < a + self.Ht and b <= t[1] < b + self.Wt:
-                so, sp = window_ref(t, (a, b), T, self.Wm, L.bpc)
+            if home == "window":
+                so, sp = window_ref(t, origin_tile, T, self.Wm, L.bpc)
                 jobs.append(Job("window", so, sp, dk, do, dp, -1))
-            elif t in self.directory:
+            elif home == "store":
                 sk, so, sp = slab_ref(self.directory[t], self.chunk_tiles, T, L.bpc)
                 jobs.append(Job(sk, so, sp, dk, do, dp, -1))
             else:
@@ -1236,12 +1167,7 @@ class TileStore(object):
         T = self.T
         a, b = self.origin[0] // T, self.origin[1] // T
         union = sorted({t for ts in tiles_of.values() for t in ts})
-        kinds = {}
-        for t in union:
-            if self.window_valid and a <= t[0] < a + self.Ht and b <= t[1] < b + self.Wt:
-                kinds[t] = "window"
-            else:
-                kinds[t] = "store" if t in self.directory else "fresh"
+        kinds = {t: home or "fresh" for t, home in zip(union, self._homes(union))}
         new = [t for t in union if kinds[t] == "fresh"]
         slabs = dict(zip(new, self._slabs(len(new))))
         per_layer, keep, bits = [], [], []
@@ -1260,8 +1186,7 @@ class TileStore(object):
                     else:
                         stage = torch.from_numpy(np.ascontiguousarray(tiles)).to(sm.device).view(torch.uint8).reshape(-1)
                     if lacking:
-                        fill = L.fill - (1 << 32) if L.fill >= (1 << 31) else L.fill
-                        empty = torch.full((T * T * src_bpc // 4,), fill, dtype=torch.int32, device=sm.device).view(torch.uint8)
+                        empty = torch.full((T * T * src_bpc // 4,), fill_int32(L.fill), dtype=torch.int32, device=sm.device).view(torch.uint8)
                         stage = torch.cat([stage, empty])
                 keep.append(stage)
                 entries = []                                           # none for a tile that exists and gets nothing in this layer
@@ -1273,10 +1198,10 @@ class TileStore(object):
                 jobs = merge_jobs(entries, T, self.Wm, L.bpc, self.chunk_tiles, (a, b), src_bpc)
                 op = merge_op(L.name, self._dtype_name(), "f32" if src_dtype == torch.float32 and L.name == "map" else None)
                 if jobs:
-                    per_layer.append((L, op, src_bpc, jobs, self._buffers(L, {"window": self._extent(cur), "stage": self._extent(stage)})))
+                    per_layer.append((L, jobs, self._buffers(L, {"window": self._extent(cur), "stage": self._extent(stage)}), op, src_bpc))
                     bits.append(1 << l)                                # the layer's bit in a tile's nonempty mask
             if per_layer:
-                self._run_merge(per_layer, st, len(union))
+                self._run(per_layer, st, len(union))
         except Exception:
             self.free.extend(slabs.values())
             raise
@@ -1289,7 +1214,7 @@ class TileStore(object):
             self.flags_event.synchronize()                             # merging is rare: the call waits for its flags
             flags = self.flags_host[:len(per_layer) * len(union)].numpy().reshape(len(per_layer), len(union))
             masks = {t: self.nonempty.get(t, 0) for t in union if kinds[t] != "window"}
-            for p, (_, _, _, jobs, _) in enumerate(per_layer):         # a layer's bit follows the result where the layer had a job
+            for p, (_, jobs, _, _, _) in enumerate(per_layer):         # a layer's bit follows the result where the layer had a job
                 for j in jobs:
                     if j.flag >= 0:
                         t = union[j.flag]
